@@ -11,9 +11,18 @@ p-value assembly, and (N > 1) ONE RCCL all-gather of the per-gene results.  Noth
 between steps: only the uploaded inputs (coordinates on the host, raw fp64 tiles on the device) persist.
 
 `value` is that resident-operand step (the contract: inputs in HBM when the timed region starts);
-`value_public_api` is SURVEY 8(d)'s literal metric, G / wall time of morans_i(adata, ...) with host
-arrays in and a DataFrame out.  `value_uint16_source` / `value_float32_source` repeat the step with the
-gathered operand forced to the wider exact types (counts >= 256; log-normalised float matrices).
+`ms_per_step` is the wall time of one timed step.  A plain run sets up, warms up, times --steps steps,
+writes their outputs (--dump-outputs DIR) and prints the result line; the roofline it reports comes from
+the HIP-event times of the timed kernels.
+
+    python bench.py --gpus N --steps K --warmup W --full
+
+adds, after the timed region, the legs that take runs of their own: `value_public_api` is SURVEY 8(d)'s
+literal metric, G / wall time of morans_i(adata, ...) with host arrays in and a DataFrame out;
+`value_uint16_source` / `value_float32_source` repeat the step with the gathered operand forced to the
+wider exact types (counts >= 256; log-normalised float matrices); `roofline.alone` scores 128 permutations
+with the chip to itself; `cpu_baseline` and `verification` (the oracle's CPU port and its check of two
+genes over all permutations).
 
 `python bench.py --gpus N` with no launcher in front starts its own N ranks (launch_ranks).
 
@@ -48,22 +57,53 @@ HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 
 
 def synth_inputs(n_cells: int, n_genes: int, seed: int, gene_offset: int = 0):
     """uniform tie-free coordinates (one cell per ~100 um^2); half the genes spatially
-    smooth (sin/cos field x Poisson), half i.i.d. Poisson, lambda ~ LogUniform(0.05, 5); float32."""
+    smooth (sin/cos field x Poisson), half i.i.d. Poisson, lambda ~ LogUniform(0.05, 5); float32.
+
+    The Poisson draws are one sequential stream (numpy's sampler takes a data-dependent number of uniforms per draw), so
+    only the work around them runs on other threads: a gene's sin/cos field is evaluated in row chunks, and finished
+    genes are copied into the cells x genes matrix in blocks of 16 while the next genes draw.  Each element comes from
+    the same numpy expression as in a whole-column evaluation, so the matrix is the same bit for bit."""
+    from concurrent.futures import ThreadPoolExecutor
+
     rng = np.random.default_rng(seed)
     L = np.sqrt(n_cells) * 10.0
     coords = rng.uniform(0, L, (n_cells, 2))
     X = np.empty((n_cells, n_genes), dtype=np.float32)
     grng = np.random.default_rng([seed, 1 + gene_offset])
-    for g in range(n_genes):
-        lam = np.exp(grng.uniform(np.log(0.05), np.log(5.0)))
-        if g % 2 == 0:
-            wl = grng.uniform(L / 8, L / 2, 2)
-            ph = grng.uniform(0, 2 * np.pi, 2)
-            field = 1.0 + 0.9 * np.sin(2 * np.pi * coords[:, 0] / wl[0] + ph[0]) * np.cos(
-                2 * np.pi * coords[:, 1] / wl[1] + ph[1])
-            X[:, g] = grng.poisson(lam * field)
-        else:
-            X[:, g] = grng.poisson(lam, n_cells)
+    cx, cy = np.ascontiguousarray(coords[:, 0]), np.ascontiguousarray(coords[:, 1])
+    threads = max(1, min(len(os.sched_getaffinity(0)), 16))
+    step = max(1 << 14, (-(-n_cells // (4 * threads)) + 1023) & ~1023)     # row chunks, multiples of 1024
+    spans = [(a, min(a + step, n_cells)) for a in range(0, n_cells, step)]
+    B = 16
+
+    def field_part(f, wl, ph, a, b):
+        f[a:b] = 1.0 + 0.9 * np.sin(2 * np.pi * cx[a:b] / wl[0] + ph[0]) * np.cos(2 * np.pi * cy[a:b] / wl[1] + ph[1])
+
+    def store_part(block, g0, a, b):
+        X[a:b, g0:g0 + block.shape[0]] = block[:, a:b].T
+
+    with ThreadPoolExecutor(threads) as fields, ThreadPoolExecutor(max(1, threads // 4)) as stores:
+        writes = []
+        block = np.empty((min(B, n_genes), n_cells), dtype=np.float32)
+        for g in range(n_genes):
+            lam = np.exp(grng.uniform(np.log(0.05), np.log(5.0)))
+            if g % 2 == 0:
+                wl = grng.uniform(L / 8, L / 2, 2)
+                ph = grng.uniform(0, 2 * np.pi, 2)
+                field = np.empty(n_cells)
+                for fut in [fields.submit(field_part, field, wl, ph, a, b) for a, b in spans]:
+                    fut.result()
+                block[g % B] = grng.poisson(lam * field)
+            else:
+                block[g % B] = grng.poisson(lam, n_cells)
+            if g % B == B - 1 or g == n_genes - 1:
+                for fut in writes:
+                    fut.result()
+                rows = g % B + 1
+                writes = [stores.submit(store_part, block[:rows], g + 1 - rows, a, b) for a, b in spans]
+                block = np.empty_like(block)
+        for fut in writes:
+            fut.result()
     return coords, X
 
 
@@ -171,6 +211,21 @@ def public_api_rate(coords, X, k: int, P: int, seed: int, device: int):
     return X.shape[1] / walls[1], walls, ad.uns["morans_i"]
 
 
+def dump_outputs(out_dir: str, batch_results: list, gathered) -> None:
+    """--dump-outputs: what the last timed step returned, one float64 .npy per array.  Per-gene arrays of the batches of
+    the step are concatenated in gene order; the per-step scalars (expected_I, var_norm) become 1-element arrays.  At
+    N > 1, `gathered_I_p_value` holds the all-gathered (I, p_value) rows of every rank.  A few KB per 1000 genes."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name in batch_results[0] if batch_results else ():
+        parts = [np.atleast_1d(np.asarray(r[name], dtype=np.float64)) for r in batch_results]
+        arrays[name] = parts[-1] if parts[0].size == 1 else np.concatenate(parts)
+    if gathered is not None:
+        arrays["gathered_I_p_value"] = np.asarray(gathered, dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def launch_ranks(n_ranks: int) -> int:
     """`python bench.py --gpus N` without an external launcher: start N child processes of this same command with
     RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT (and a rendezvous file in a fresh private directory)
@@ -233,12 +288,19 @@ def main() -> None:
     ap.add_argument("--perms", type=int, default=1000)
     ap.add_argument("--k", type=int, default=15)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline + oracle verification leg")
-    ap.add_argument("--no-public-api", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs that take runs of their own: roofline.alone, the "
+                         "other-source repeats of the step, the public-API wall time, the CPU baseline + oracle "
+                         "verification (each can still be skipped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0: per-gene I, p-values, counts, ...) as "
+                         "DIR/<name>.npy in float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline + oracle verification leg")
+    ap.add_argument("--no-public-api", action="store_true", help="--full: skip the public-API leg")
     ap.add_argument("--no-other-sources", action="store_true",
-                    help="skip the uint16- / float32-source repeats of the step (value_uint16_source, value_float32_source)")
+                    help="--full: skip the uint16- / float32-source repeats of the step (value_uint16_source, value_float32_source)")
     ap.add_argument("--no-alone", action="store_true",
-                    help="skip roofline.alone (counter passes: its launches would be averaged into the per-launch traffic)")
+                    help="--full: skip roofline.alone (counter passes: its launches would be averaged into the per-launch traffic)")
     ap.add_argument("--source-bits", type=int, default=8, choices=(4, 8, 16, 32, 64),
                     help="narrowest exact copy of the expression values the permutation kernel may gather "
                          "(4: nibble slots for count data when they take fewer rows, 8 / 16: uint8 / uint16 for count data, "
@@ -294,6 +356,7 @@ def main() -> None:
         return X if bi == 0 else np.roll(X, 7919 * bi, axis=0)
 
     gathered = None
+    batch_results = []   # the result dicts of the last step's batches (what a caller of _moran_resident receives)
     mem_peak = 0
     batch_walls = []     # (batch index, wall seconds) of every batch call: strong mode reports the generator's share
 
@@ -313,7 +376,7 @@ def main() -> None:
         return res
 
     def device_part():
-        nonlocal mem_peak
+        nonlocal mem_peak, batch_results
         # the neighbour search and the graph are enqueued without waiting (nothing is fetched), then the permutation
         # generator -- it needs only n and the seed, and it is the longest chain of the step -- starts beside them with
         # three chunks enqueued; the scoring joins it (morans_i starts the generator first as well: there an upload follows)
@@ -323,6 +386,7 @@ def main() -> None:
         if begun is not None:
             ctx.moran_seeded_begin(begun, n, P, ahead_chunks=3)
         rows = []
+        results = []
         res = None
         for bi, (b0, b1) in enumerate(batches):
             tb = time.perf_counter()
@@ -334,8 +398,10 @@ def main() -> None:
                 res = _moran_resident(ctx, n, P, args.seed, reuse_table=True)   # the rank's resident table
             batch_walls.append((bi, time.perf_counter() - tb))   # (every call ends with a stream synchronisation)
             rows.append(np.stack([res["I"], res["p_value"]], axis=1))
+            results.append(res)
         mem_peak = max(mem_peak, ctx.device_mem())
         mine = np.concatenate(rows, axis=0) if rows else np.zeros((0, 2))
+        batch_results = results
         return res, mine
 
     def fence():
@@ -354,6 +420,8 @@ def main() -> None:
     fence()
     elapsed = float(comm.max_over_ranks([time.perf_counter() - t0])[0])
     timed_batch_walls = list(batch_walls)     # (the legs after the timed region call step() again)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, batch_results, gathered)     # (before the --full legs step again)
     pg = tuple(a - b for a, b in zip(ctx.permgen_stats(), pg0))
 
     perm_ms, perm_launches = ctx.kernel_time(_lib.K_MORAN_PERM)
@@ -369,7 +437,7 @@ def main() -> None:
     timed_lag_bits = ctx.moran_lag_bits()
     timed_groups = ctx.moran_row_groups()
     alone = None
-    if rank == 0 and len(batches) == 1 and not rehearse and P >= 128 and not args.no_alone:
+    if args.full and rank == 0 and len(batches) == 1 and not rehearse and P >= 128 and not args.no_alone:
         ctx.reset_timers()
         for _ in range(3):
             ctx.moran(128, return_sims=False)
@@ -401,7 +469,8 @@ def main() -> None:
     # batch): what a panel with counts >= 256 (uint16 rows, 64 genes each) or a log-normalised float matrix (float32
     # rows, 32 genes each) pays.  The statistics are those of the timed run (lattice genes: same integers).
     other_sources = {}
-    if rank == 0 and world == 1 and len(batches) == 1 and not rehearse and not args.no_other_sources and args.source_bits <= 8:
+    if (args.full and rank == 0 and world == 1 and len(batches) == 1 and not rehearse and not args.no_other_sources
+            and args.source_bits <= 8):
         for bits_alt in ((8, 16, 32) if timed_bits == 4 else (4, 16, 32)):
             ctx.set_moran_source_bits(bits_alt)
             step()
@@ -531,13 +600,13 @@ def main() -> None:
                 "status": "unmeasured on hardware for N > 1: a bound from this rank's own per-batch times"}
         if fallbacks:
             line["warning"] = "the block-parallel generator fell back to the sequential scan inside the timed region"
-        if world == 1 and not strong and not args.no_public_api:
+        if args.full and world == 1 and not strong and not args.no_public_api:
             rate, walls, _ = public_api_rate(coords, X, k, P, args.seed, local_rank)
             line["value_public_api"] = rate
             line["public_api"] = {"call": f"morans_i(adata, genes=all {X.shape[1]}, n_neighbors={k}, n_permutations={P}, "
                                           f"seed={args.seed}) on a float32 CSR AnnData, host arrays in, DataFrame out",
                                   "wall_s_first_call": walls[0], "wall_s": walls[1]}
-        if world == 1 and not strong and not args.no_cpu_baseline:
+        if args.full and world == 1 and not strong and not args.no_cpu_baseline:
             base, verify = cpu_baseline_and_verify(coords, X, k, P, args.seed, res, (0, X.shape[1] - 1))
             line["cpu_baseline"] = base
             line["verified"] = verify["verified"] and fallbacks == 0

@@ -1,7 +1,7 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r04prof; mkdir -p $O
-timeout -k 10 420 python3 bench.py > $O/r04_bench_default_run.json 2> $O/bench_default.err; tail -c 300 $O/r04_bench_default_run.json; echo
+timeout -k 10 420 python3 bench.py --full > $O/r04_bench_default_run.json 2> $O/bench_default.err; tail -c 300 $O/r04_bench_default_run.json; echo
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-public-api --no-alone --no-other-sources > $O/r04_bench_under_rocprof.json 2> $O/stats.err
 cp $(ls $O/stats/*/*kernel_stats.csv | head -1) $O/r04_bench_kernel_stats.csv

@@ -12,6 +12,12 @@ for p in (ROOT, os.path.join(ROOT, "oracle")):
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
+# The GPU tests assert the block-parallel permutation generator, whose streams need hardware queues of their own.  The
+# library asks for 24 (GPU_MAX_HW_QUEUES) only when the variable is unset, so a launcher that exports HIP's default of 4
+# would silently turn those tests into runs of the sequential scan.  The suite asks for the library's value before
+# anything initialises HIP; subprocesses inherit it, and tests that need another value set it for their own child.
+os.environ["GPU_MAX_HW_QUEUES"] = "24"
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")

@@ -166,6 +166,52 @@ def test_bench_launches_its_own_ranks_without_a_launcher(tmp_path):
     assert line["value"] > 0 and line["permgen_stats"]["verification_fallbacks_max_over_ranks"] == 0
 
 
+def test_bench_plain_run_dumps_what_its_last_step_computed(tmp_path, oracle):
+    """`bench.py --dump-outputs DIR` without --full: exactly --steps timed steps, none of the --full legs, and the last
+    step's per-gene results on disk -- the same files from two runs (same inputs), I equal to the oracle's for every
+    gene and the permutation counts of two genes equal to the oracle's over all permutations."""
+    n, G, P, k = 150000, 40, 200, 15
+
+    def run(out):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cells", str(n), "--genes", str(G),
+               "--perms", str(P), "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, res.stdout[-2000:]
+        return json.loads(lines[0])
+
+    line = run(tmp_path / "a")
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(G * 1e3 / line["ms_per_step"], rel=1e-9)
+    assert line["unit"] == "genes/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert not {"cpu_baseline", "verification", "value_public_api", "value_uint16_source"} & set(line)
+    assert line["roofline"]["alone"] is None
+    run(tmp_path / "b")
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert {"I.npy", "p_value.npy", "count_ge.npy"} <= set(names)
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float64 and (a.shape == (G,) or a.size == 1), name
+        np.testing.assert_array_equal(a, b, err_msg=name)
+
+    import bench
+
+    coords, X = bench.synth_inputs(n, G, seed=42)
+    g = oracle.row_normalize_l1(oracle.csr_matrix((np.ones(n * k), oracle.knn_tree(coords, k).reshape(-1),
+                                                   np.arange(0, n * k + 1, k)), shape=(n, n)))
+    vals = np.ascontiguousarray(X.T, dtype=np.float64)
+    I_ref = oracle.morans_i_scores(g, vals)
+    np.testing.assert_allclose(np.load(tmp_path / "a" / "I.npy"), I_ref, rtol=1e-9)
+    cols = [0, G - 1]
+    perms, _ = oracle.perm_table(0, n, P)
+    sims = oracle.morans_i_sims_gather(g, vals[cols], perms)
+    want, lattice = oracle.morans_count_ge(g, vals[cols], perms, sims, I_ref[cols])
+    assert lattice.all()
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "count_ge.npy")[cols], want)
+
+
 def test_rccl_communicator_world_of_one():
     """dlopen(librccl) + ncclGetUniqueId + ncclCommInitRank + ncclAllGather + ncclAllReduce on the real device."""
     from spatialcore_amd._lib import Context, RcclComm
