@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <functional>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -58,11 +59,11 @@ struct KTimer {
     int64_t launches = 0;
 };
 
-struct PermPipe;   // a generator job in flight (sc_moran.hip: sc_moran_seeded_begin .. _finish)
+struct PermPipe;   // a generator job in flight (sc_perm.hip; begun by sc_moran_seeded_begin, consumed by _finish)
 
 struct sc_ctx {
     int device = 0;
-    PermPipe *pipe = nullptr;        // the generator / consumer pipeline begun by sc_moran_seeded_begin, until _finish
+    std::unique_ptr<PermPipe> pipe;  // the generator / consumer pipeline begun by sc_moran_seeded_begin, until _finish
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;  // fused permutation/Moran pipeline: rejection scan runs ahead here
     hipStream_t stream3 = nullptr;  // ... and the Fisher-Yates swaps of the scanned chunk here
@@ -79,7 +80,6 @@ struct sc_ctx {
     bool pg_probed = false;           // the stream-concurrency probe ran (once per context, before the first block-parallel job)
     std::string pg_note;              // why the generator left the block-parallel form, if it did (sc_ctx_permgen_note)
     std::string pg_form;              // scratch of sc_ctx_permgen_form
-    int pg_ahead = 1;                 // launch units the preparation runs ahead of the chain (callers that share the chip raise it)
     int64_t pg_jobs_parallel = 0, pg_jobs_sequential = 0, pg_fallbacks = 0;  // generator jobs by scan form
     int64_t pg_blocks_prepared = 0, pg_blocks_chain = 0;  // block-parallel jobs: blocks resolved by table lookup / by the chain workgroup
     int64_t mem = 0;  // bytes allocated through DBuf
@@ -213,7 +213,7 @@ struct PermJob {
     uint64_t unit_start[8] = {};  // first block of the last launch units (ring)
     int64_t unit_no = 0;
     int64_t gate_seen[4] = {};   // per preparation stream: the "units completed by the chain" count its last gate waited for
-    int ahead = 1;             // units prepared ahead of the chain
+    int units_ahead = 1;       // launch units prepared ahead of the chain
 };
 // A generator job whose chunks are (being) enqueued on the generator's streams while the consumer catches up.
 struct PermPipe {
@@ -224,20 +224,32 @@ struct PermPipe {
     int64_t n = 0, n_perm = 0, enqueued = 0;   // generator chunks enqueued so far
     uint64_t state0[6] = {};           // the generator state the job started from (a sequential rerun starts there again)
 };
-void sc_perm_pipe_abort(sc_ctx *c);    // drain and drop c->pipe (no results)
 #define SC_PERMGEN_RETRY 1000  // internal: the block-parallel scan failed its verification, rerun sequentially
 bool permgen_is_block_parallel(const sc_ctx *c, int64_t n);  // which scan form a job of length n takes
-int permgen_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, PermJob *job, hipStream_t s);
+// units_ahead: launch units the block-parallel scan's preparation runs ahead of its chain (clamped to [1, PHI_AHEAD_MAX])
+int permgen_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int units_ahead, PermJob *job, hipStream_t s);
 int permgen_scan_chunk(sc_ctx *c, PermJob *job, int64_t p1, hipStream_t s, hipStream_t post, hipEvent_t done);
 int permgen_swap_chunk(sc_ctx *c, PermJob *job, int64_t p0, int64_t p1, hipStream_t s, bool inverse, int pw_req);
 bool permgen_can_swap_inverse(int64_t n);
 int sc_perm_forward_ensure(sc_ctx *c);  // materialise c->perm from c->inv after a pipeline that only made the inverse
+int invert_rows(sc_ctx *c, int64_t p0, int64_t p1, hipStream_t s);   // inverse rows [p0, p1) of the active table on stream s
 int permgen_finish(sc_ctx *c, PermJob *job, uint64_t *state6);
 int sc_perm_alloc(sc_ctx *c, int64_t n, int64_t n_perm);
-// generator / consumer pipeline (sc_moran.hip): table 0 = permutation rows, 1 = inverse rows only, 2 = both
 int sc_permgen_profile(unsigned long long *out32, int reset);   // development builds (-DPHI_PROFILE): computed blocks by class
-int sc_perm_pipeline(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_perm, int table,
+// generator / consumer pipeline (sc_perm.hip): table 0 = permutation rows, 1 = inverse rows only, 2 = both
+int pipe_units_ahead();                 // the Moran scoring's unit lookahead: PIPE_AHEAD (SC_PIPE_AHEAD: development)
+int64_t pipe_tail_total();              // permutations of the tapering last chunks
+int pipe_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int table, int units_ahead, PermPipe &pp,
+               int64_t chunks_ahead, const std::function<int()> &after_first_chunk = nullptr);
+int pipe_consume(sc_ctx *c, PermPipe &pp, uint64_t *state6, const std::function<int()> &after_first,
+                 const std::function<int(int64_t, int64_t)> &score);
+void pipe_drain(sc_ctx *c, PermPipe &pp);
+void sc_perm_pipe_abort(sc_ctx *c);    // drain and drop c->pipe (no results)
+int sc_perm_pipeline(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_perm, int table, int units_ahead,
                      const std::function<int()> &after_first, const std::function<int(int64_t, int64_t)> &score);
+// Runs attempt(); if the block-parallel scan failed its verification, runs undo() (may be empty) and then attempt() once
+// more with the sequential scan.  pg_mode is the caller's again on return, on every path.
+int permgen_rerun_on_failure(sc_ctx *c, const std::function<int()> &attempt, const std::function<int()> &undo);
 
 int sc_timer_collect(sc_ctx *c);
 int sc_expr_zscores(sc_ctx *c);  // Z = (X - mean) / population sd per gene (0 for zero variance), variances in g_var

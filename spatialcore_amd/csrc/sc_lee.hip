@@ -252,19 +252,13 @@ extern "C" int sc_lee_seeded(sc_ctx *c, uint64_t *state6, const int32_t *pair_x,
             // injection mode) the sub-job's counts are rolled back and it is rerun with the sequential scan
             SC_HIP(hipMemcpyAsync(d_cnt_backup, c->lee_cnt.p, sizeof(unsigned long long) * (size_t)n_pairs,
                                   hipMemcpyDeviceToDevice, c->stream));
-            const int ahead = c->pg_ahead;
-            c->pg_ahead = 2;
-            int rc = sc_perm_pipeline(c, state6, n, rows, 0, nullptr, score);
-            if (rc == SC_PERMGEN_RETRY) {
-                SC_HIP(hipMemcpyAsync(c->lee_cnt.p, d_cnt_backup, sizeof(unsigned long long) * (size_t)n_pairs,
-                                      hipMemcpyDeviceToDevice, c->stream));
-                const int mode = c->pg_mode;
-                c->pg_mode = 1;
-                rc = sc_perm_pipeline(c, state6, n, rows, 0, nullptr, score);
-                c->pg_mode = mode;
-            }
-            c->pg_ahead = ahead;
-            SC_TRY(rc);
+            SC_TRY(permgen_rerun_on_failure(
+                c, [&]() { return sc_perm_pipeline(c, state6, n, rows, 0, 2, nullptr, score); },
+                [&]() -> int {
+                    SC_HIP(hipMemcpyAsync(c->lee_cnt.p, d_cnt_backup, sizeof(unsigned long long) * (size_t)n_pairs,
+                                          hipMemcpyDeviceToDevice, c->stream));
+                    return SC_OK;
+                }));
             if (L_perm_out) {
                 std::vector<double> lp((size_t)rows);
                 SC_HIP(hipMemcpy(lp.data(), c->lee_lperm.p, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost));
@@ -679,20 +673,15 @@ extern "C" int sc_lee_shared(sc_ctx *c, uint64_t *state6, const int32_t *genes_x
         if (!state6) {   // the resident table, chunk by chunk
             SC_TRY(sc_perm_forward_ensure(c));
             for (int64_t p0 = 0; p0 < n_perm; p0 += PERM_CHUNK) SC_TRY(score(p0, p0 + PERM_CHUNK < n_perm ? p0 + PERM_CHUNK : n_perm));
+        } else {   // a job that fails its verification is rerun with the sequential scan, its counts rolled back
+            SC_HIP(hipMemcpyAsync(d_cnt_backup, c->lee_cnt.p, sizeof(unsigned long long) * (size_t)per, hipMemcpyDeviceToDevice, c->stream));
+            SC_TRY(permgen_rerun_on_failure(
+                c, [&]() { return sc_perm_pipeline(c, state6, n, n_perm, 0, 2, nullptr, score); },
+                [&]() -> int {
+                    SC_HIP(hipMemcpyAsync(c->lee_cnt.p, d_cnt_backup, sizeof(unsigned long long) * (size_t)per, hipMemcpyDeviceToDevice, c->stream));
+                    return SC_OK;
+                }));
         }
-        SC_HIP(hipMemcpyAsync(d_cnt_backup, c->lee_cnt.p, sizeof(unsigned long long) * (size_t)per, hipMemcpyDeviceToDevice, c->stream));
-        const int ahead = c->pg_ahead;
-        c->pg_ahead = 2;
-        int rc = state6 ? sc_perm_pipeline(c, state6, n, n_perm, 0, nullptr, score) : SC_OK;
-        if (rc == SC_PERMGEN_RETRY) {
-            SC_HIP(hipMemcpyAsync(c->lee_cnt.p, d_cnt_backup, sizeof(unsigned long long) * (size_t)per, hipMemcpyDeviceToDevice, c->stream));
-            const int mode = c->pg_mode;
-            c->pg_mode = 1;
-            rc = sc_perm_pipeline(c, state6, n, n_perm, 0, nullptr, score);
-            c->pg_mode = mode;
-        }
-        c->pg_ahead = ahead;
-        SC_TRY(rc);
         if (L_perm_out)
             SC_HIP(hipMemcpyAsync(L_perm_out, c->lee_lperm.p, sizeof(double) * (size_t)per * (size_t)n_perm, hipMemcpyDeviceToHost, c->stream));
     }

@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include <functional>
+#include <optional>
 #include <thread>
 #include <vector>
 
@@ -1740,7 +1741,7 @@ static int moran_prepare(sc_ctx *c, int64_t n_perm, bool allow_lattice)
 }
 
 // inverse rows [p0, p1) of the active table on stream s
-static int invert_rows(sc_ctx *c, int64_t p0, int64_t p1, hipStream_t s)
+int invert_rows(sc_ctx *c, int64_t p0, int64_t p1, hipStream_t s)
 {
     const int rows = (int)(p1 - p0);
     if (rows <= 0) return SC_OK;
@@ -1968,209 +1969,6 @@ extern "C" int sc_moran(sc_ctx *c, int64_t n_perm, double *I_out, double *sims_o
                                  // 128 -> 162.2 / 162.6, 144 -> 171.0 / 169.5; the scoring launches take the same 117 ms on 144 CUs
                                  // as on 160 (13 rounds of tasks either way), the generator's preparation gets its CUs sooner
 #endif
-#ifndef PIPE_AHEAD
-#define PIPE_AHEAD 3         // launch units the generator's preparation runs ahead of its chain inside the pipeline
-#endif
-#ifndef PIPE_FIRST
-#define PIPE_FIRST 32        // permutations of the first pipeline chunk
-#endif
-#ifndef PIPE_TAIL
-#define PIPE_TAIL "96,48,24" // the last chunks, tapering: see pipe_tail_perms
-#endif
-#ifndef PIPE_SWAP_STREAMS
-#define PIPE_SWAP_STREAMS 2  // swap chunks in flight (they are latency-bound: two overlap almost for free)
-#endif
-
-// permutations of the pipeline's first chunk (SC_PIPE_FIRST: development, to sweep the schedule)
-static int64_t pipe_first_perms()
-{
-    int64_t v = PIPE_FIRST;
-    if (const char *e = getenv("SC_PIPE_FIRST")) v = atoi(e);
-    return v < 8 || v > PERM_CHUNK ? PIPE_FIRST : v;
-}
-// The job ends with what is left once the generator's chain has finished: the swaps of its last chunk (~10 ms whatever
-// its size: one workgroup per permutation, latency-bound) and the consumption of every chunk not consumed yet.  Behind
-// a 128-permutation chunk that is its swaps AND its 10-ms consumption; tapering chunks leave a few milliseconds (bench
-// step, same box, ms: one 32-permutation last chunk 173.5 / 174.6; 64,32: 172.4 / 178.8; 64,32,16: 172.8 / 173.1; 96,48,24: 169.4 / 169.4).
-// SC_PIPE_TAIL="a,b,...": development, to sweep the schedule ("0": no short chunks at the end).
-static std::vector<int64_t> pipe_tail_perms()
-{
-    const char *e = getenv("SC_PIPE_TAIL");
-    std::vector<int64_t> t;
-    for (const char *p = e ? e : PIPE_TAIL; *p;) {
-        char *end = nullptr;
-        const long v = strtol(p, &end, 10);
-        if (end == p) break;
-        if (v >= 8 && v <= PERM_CHUNK) t.push_back(v);
-        p = *end == ',' ? end + 1 : end;
-    }
-    return t;
-}
-static int64_t pipe_tail_total()
-{
-    int64_t s = 0;
-    for (int64_t v : pipe_tail_perms()) s += v;
-    return s;
-}
-
-// The generator / consumer pipeline shared by sc_moran_seeded and sc_lee_seeded: numpy-exact permutation rows
-// [0, n_perm) of length n are produced chunk by chunk on the generator's streams (stream2: rejection scan chain,
-// stream_pg: its preparation, stream_px: verification + expansion, stream3/4: Fisher-Yates swaps) while
-// `score(p0, p1)` consumes finished chunks on the context stream.  table: 0 = permutation rows (c->perm),
-// 1 = inverse rows only (c->inv; the same transpositions in ascending order), 2 = both (rows + k_invert_perm).
-// `after_first` runs on the host right after the first chunk of the generator has been enqueued (the generator is
-// the longest chain and depends on nothing else; everything host-blocking of the consumer's set-up goes here).
-static int pipe_generate(sc_ctx *c, PermPipe &pp, int64_t k)
-{
-    hipEvent_t &scanned = pp.ev[(size_t)(2 * k)], &swapped = pp.ev[(size_t)(2 * k + 1)];
-    // Two swap kernels in flight only for the job's LAST chunks (r04).  A swap workgroup is 8 wavefronts that live ~10 ms;
-    // two chunks' worth of them (256) spread over the ~96 CUs the scoring kernel leaves, next to the table builders' two-
-    // wavefront workgroups, left no CU with the 16 free wavefront slots a 1024-thread preparation workgroup needs: the
-    // chain's clock profile showed its units arriving 1-8 ms late behind every chunk boundary (55 k clocks of waiting per
-    // permutation; 37 k with one swap kernel at a time).  The tapering last chunks arrive 2-6 ms apart after the chain
-    // is all but done, and keep overlapping.
-    const int64_t chunks = (int64_t)pp.bounds.size() - 1;
-    const bool overlap = PIPE_SWAP_STREAMS > 1 && (k & 1) && (k >= chunks - 3 || getenv("SC_SWAP_OVERLAP_ALL") != nullptr);
-    hipStream_t sw = overlap ? c->stream4 : c->stream3;
-    SC_HIP(hipEventCreateWithFlags(&scanned, hipEventDisableTiming));
-    SC_HIP(hipEventCreateWithFlags(&swapped, hipEventDisableTiming));
-    SC_TRY(permgen_scan_chunk(c, &pp.job, pp.bounds[(size_t)k + 1], c->stream2, c->stream_px, scanned));
-    SC_HIP(hipStreamWaitEvent(sw, scanned, 0));
-    // Two permutations per swap workgroup while the chain still runs -- workgroups of the preparation kernels' own size --
-    // but only beside the Moran scoring kernel (the one consumer that fills its CUs with wavefronts that live for
-    // milliseconds): there the step gains 5 ms (151 against 156).  Two permutations in lockstep take 13-15 ms per chunk
-    // instead of 10-12, and a light consumer (Lee's row sums, the local counts) leaves the chain at 12.8 ms per chunk:
-    // with the pairs the swap stream became the bottleneck (Lee 10 x 10 pairs: 27.8 against 24.9 ms per pair).
-    const int pw = (k < chunks - 3 && c->score_leave_cus > 8) ? 2 : 1;
-    SC_TRY(permgen_swap_chunk(c, &pp.job, pp.bounds[(size_t)k], pp.bounds[(size_t)k + 1], sw, pp.table == 1, pw));
-    if (pp.table == 2) SC_TRY(invert_rows(c, pp.bounds[(size_t)k], pp.bounds[(size_t)k + 1], sw));
-    SC_HIP(hipEventRecord(swapped, sw));
-    pp.enqueued = k + 1;
-    return SC_OK;
-}
-
-static void pipe_drain(sc_ctx *c, PermPipe &pp)
-{
-    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-    if (c->stream3) (void)hipStreamSynchronize(c->stream3);
-    if (c->stream4) (void)hipStreamSynchronize(c->stream4);
-    if (c->stream_px) (void)hipStreamSynchronize(c->stream_px);
-    if (c->stream_fr) (void)hipStreamSynchronize(c->stream_fr);
-    for (hipStream_t sp : c->stream_pg)
-        if (sp) (void)hipStreamSynchronize(sp);
-    (void)hipStreamSynchronize(c->stream);
-    for (hipEvent_t e : pp.ev)
-        if (e) (void)hipEventDestroy(e);
-    pp.ev.clear();
-}
-
-// Begin: allocations, chunk schedule, the generator's set-up and its first `ahead` chunks (all of them when ahead
-// >= the number of chunks).  Needs nothing but n and the generator state -- no graph, no expression.
-static int pipe_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int table, PermPipe &pp, int64_t ahead,
-                      const std::function<int()> &after_first_chunk = nullptr)
-{
-    SC_REQUIRE(state6, SC_ERR_INVALID, "permutation pipeline: null generator state");
-    SC_REQUIRE(n_perm >= 1, SC_ERR_INVALID, "permutation pipeline: n_perm must be >= 1");
-    SC_REQUIRE(table == 0 || permgen_can_swap_inverse(n) || table == 2, SC_ERR_STATE, "inverse-only tables need a longer permutation");
-    SC_TRY(sc_perm_alloc(c, n, n_perm));
-    // the resident table is being overwritten from here on: nothing may take it for valid until the job has been consumed
-    // (sc_moran / sc_local_moran / sc_lee_shared with a resident table then fail with "holds 0 rows" instead of reading
-    // rows the generator's streams are still writing)
-    c->p_count = 0;
-    c->inv_rows_valid = 0;
-    c->perm_forward_valid = false;
-    if (!c->stream2) {  // (SC_STREAM_PRIORITY=1: the r01 prioritised chain stream, for experiments; no gain measured in r02)
-        int prio_lo = 0, prio_hi = 0;
-        if (!getenv("SC_STREAM_PRIORITY") || hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess ||
-            hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_hi) != hipSuccess) {
-            (void)hipGetLastError();
-            c->stream2 = nullptr;
-            SC_HIP(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-        }
-    }
-    if (!c->stream_px) SC_HIP(hipStreamCreateWithFlags(&c->stream_px, hipStreamNonBlocking));
-    if (!c->stream3) SC_HIP(hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
-    if (!c->stream4) SC_HIP(hipStreamCreateWithFlags(&c->stream4, hipStreamNonBlocking));
-    // allocations first (hipMalloc synchronises the device), then the streams run freely
-    if (table >= 1) SC_TRY(c->inv.ensure(sizeof(int32_t) * (size_t)(c->p_stride * n_perm + 32), &c->mem));
-    // chunk schedule: a short first chunk so that the consumer starts early, PERM_CHUNK each in the middle, a short
-    // last chunk (the job ends with the swaps and the consumption of the last chunk after the scan is done)
-    pp.bounds.clear();
-    pp.bounds.push_back(0);
-    if (n_perm > 3 * PERM_CHUNK) {
-        const int64_t first = pipe_first_perms(), last = pipe_tail_total();
-        const std::vector<int64_t> tail = pipe_tail_perms();
-        const int64_t rest = (n_perm - last - first) % PERM_CHUNK;
-        static const bool join = getenv("SC_PIPE_JOIN") != nullptr;   // development: a small remainder joins the first chunk (r02 / early r03)
-        int64_t p = first + (join && rest < PERM_CHUNK / 2 ? rest : 0);
-        pp.bounds.push_back(p);
-        if (p == first && rest > 0) { p += rest; pp.bounds.push_back(p); }   // the remainder: a chunk of its own, second
-        for (; p < n_perm - last; ) { p += PERM_CHUNK; pp.bounds.push_back(p); }
-        for (int64_t v : tail) { p += v; pp.bounds.push_back(p); }
-    } else {
-        for (int64_t p = PERM_CHUNK; p < n_perm; p += PERM_CHUNK) pp.bounds.push_back(p);
-        pp.bounds.push_back(n_perm);
-    }
-    const int64_t chunks = (int64_t)pp.bounds.size() - 1;
-    // stream2: scan(0) scan(1) ...   stream3/4: swaps(k) (+ inverse(k)) after scan(k)   stream: score(k) after swaps(k)
-    pp.ev.assign((size_t)chunks * 2, nullptr);
-    pp.table = table; pp.n = n; pp.n_perm = n_perm; pp.enqueued = 0;
-    for (int k = 0; k < 6; ++k) pp.state0[k] = state6[k];
-    pp.job = PermJob();
-    int rc = permgen_begin(c, state6, n, n_perm, &pp.job, c->stream2);
-    for (int64_t k = 0; k < chunks && k < ahead && rc == SC_OK; ++k) {
-        rc = pipe_generate(c, pp, k);
-        if (k == 0 && rc == SC_OK && after_first_chunk) rc = after_first_chunk();
-    }
-    if (rc != SC_OK) pipe_drain(c, pp);
-    return rc;
-}
-
-// Consume: `after_first` (the consumer's host-blocking set-up) runs once, then `score(p0, p1)` behind every chunk's
-// swaps on the context stream, with the generator kept TWO chunks ahead in the host's enqueue order (r03 timeline: with
-// one chunk ahead the chain sat idle for 5 ms behind the consumer's set-up; a chunk is some 250 API calls).
-static int pipe_consume(sc_ctx *c, PermPipe &pp, uint64_t *state6, const std::function<int()> &after_first,
-                        const std::function<int(int64_t, int64_t)> &score)
-{
-    const int64_t chunks = (int64_t)pp.bounds.size() - 1;
-    int rc = SC_OK;
-    if (after_first) rc = after_first();
-    c->perm_bijective = true;  // device-generated rows are permutations by construction
-    c->perm_forward_valid = pp.table != 1;
-    for (int64_t k = 0; k < chunks && rc == SC_OK; ++k) {
-        while (rc == SC_OK && pp.enqueued < chunks && pp.enqueued < k + 3) rc = pipe_generate(c, pp, pp.enqueued);
-        if (rc == SC_OK && hipStreamWaitEvent(c->stream, pp.ev[(size_t)(2 * k + 1)], 0) != hipSuccess) {
-            sc_set_error("permutation pipeline: event plumbing failed");
-            rc = SC_ERR_HIP;
-        }
-        if (rc == SC_OK) rc = score(pp.bounds[(size_t)k], pp.bounds[(size_t)k + 1]);
-    }
-    pipe_drain(c, pp);
-    if (rc != SC_OK) return rc;
-    SC_TRY(permgen_finish(c, &pp.job, state6));
-    c->p_count = pp.n_perm;
-    c->inv_rows_valid = pp.table >= 1 ? pp.n_perm : 0;
-    return SC_OK;
-}
-
-void sc_perm_pipe_abort(sc_ctx *c)
-{
-    if (!c->pipe) return;
-    pipe_drain(c, *c->pipe);
-    delete c->pipe;
-    c->pipe = nullptr;
-    c->p_count = 0;
-}
-
-int sc_perm_pipeline(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_perm, int table,
-                     const std::function<int()> &after_first, const std::function<int(int64_t, int64_t)> &score)
-{
-    sc_perm_pipe_abort(c);   // (a job begun with sc_moran_seeded_begin and never finished)
-    PermPipe pp;
-    SC_TRY(pipe_begin(c, state6, n, n_perm, table, pp, 2));
-    return pipe_consume(c, pp, state6, after_first, score);
-}
-
 static int moran_seeded_once(sc_ctx *c, uint64_t *state6, int64_t n_perm, double *I_out, double *sims_out,
                              int64_t *count_ge_out, double *sim_sum_out, double *sim_sumsq_out, PermPipe *begun)
 {
@@ -2211,7 +2009,7 @@ static int moran_seeded_once(sc_ctx *c, uint64_t *state6, int64_t n_perm, double
         return rc;
     };
     if (begun) SC_TRY(pipe_consume(c, *begun, state6, prepare, score));   // the generator has been running since _begin
-    else SC_TRY(sc_perm_pipeline(c, state6, n, n_perm, inverse_only ? 1 : 2, prepare, score));
+    else SC_TRY(sc_perm_pipeline(c, state6, n, n_perm, inverse_only ? 1 : 2, pipe_units_ahead(), prepare, score));
     return moran_finish(c, n_perm, I_out, sims_out, count_ge_out, sim_sum_out, sim_sumsq_out);
 }
 
@@ -2234,15 +2032,11 @@ static int moran_seeded_once(sc_ctx *c, uint64_t *state6, int64_t n_perm, double
 static int moran_seeded_streams(sc_ctx *c, uint64_t *state6, int64_t n_perm, double *I_out, double *sims_out,
                                 int64_t *count_ge_out, double *sim_sum_out, double *sim_sumsq_out, PermPipe *begun = nullptr)
 {
-    const int ahead = c->pg_ahead;
     int leave = c && c->e_n > 0 && permgen_is_block_parallel(c, c->e_n) ? SCORE_RESERVED_CUS : 8;
     if (const char *v = getenv("SC_SCORE_LEAVE_CUS")) leave = atoi(v);  // development: sweep the reservation
-    c->pg_ahead = PIPE_AHEAD;
-    if (const char *v = getenv("SC_PIPE_AHEAD")) c->pg_ahead = atoi(v);  // development: sweep the lookahead
     c->score_leave_cus = leave;
     const int rc = moran_seeded_once(c, state6, n_perm, I_out, sims_out, count_ge_out, sim_sum_out, sim_sumsq_out, begun);
     c->score_leave_cus = 0;
-    c->pg_ahead = ahead;
     return rc;
 }
 
@@ -2250,14 +2044,11 @@ extern "C" int sc_moran_seeded(sc_ctx *c, uint64_t *state6, int64_t n_perm, doub
                                int64_t *count_ge_out, double *sim_sum_out, double *sim_sumsq_out)
 {
     SC_REQUIRE(c, SC_ERR_INVALID, "sc_moran_seeded: null context");
-    int rc = moran_seeded_streams(c, state6, n_perm, I_out, sims_out, count_ge_out, sim_sum_out, sim_sumsq_out);
-    if (rc == SC_PERMGEN_RETRY) {  // the block-parallel scan failed its verification: nothing was returned yet
-        const int mode = c->pg_mode;
-        c->pg_mode = 1;
-        rc = moran_seeded_streams(c, state6, n_perm, I_out, sims_out, count_ge_out, sim_sum_out, sim_sumsq_out);
-        c->pg_mode = mode;
-    }
-    return rc;
+    // (nothing is returned before the job has passed its verification: nothing to undo before the sequential rerun, whose
+    // call recomputes the CU reservation for the sequential scan)
+    return permgen_rerun_on_failure(
+        c, [&]() { return moran_seeded_streams(c, state6, n_perm, I_out, sims_out, count_ge_out, sim_sum_out, sim_sumsq_out); },
+        nullptr);
 }
 
 // The same call in two halves, so that the generator -- the longest chain of the job, which needs nothing but n_cells and
@@ -2274,10 +2065,7 @@ extern "C" int sc_moran_seeded_begin(sc_ctx *c, const uint64_t *state6, int64_t 
     SC_REQUIRE(n_perm >= 1 && n_perm <= (1 << 24), SC_ERR_INVALID, "sc_moran_seeded_begin: n_perm=%lld out of range", (long long)n_perm);
     SC_HIP(hipSetDevice(c->device));
     sc_perm_pipe_abort(c);
-    const int ahead = c->pg_ahead;
-    c->pg_ahead = PIPE_AHEAD;
-    if (const char *v = getenv("SC_PIPE_AHEAD")) c->pg_ahead = atoi(v);
-    PermPipe *pp = new PermPipe;
+    auto pp = std::make_unique<PermPipe>();
     // ahead_chunks: chunks of the generator enqueued before returning (a chunk is ~250 launches, ~3.5 ms of host time);
     // 0 = all of them (a caller with tens of milliseconds of host-blocking work in front of _finish: an upload), else at
     // least 2 (_finish enqueues the rest, two ahead of the scoring)
@@ -2286,10 +2074,8 @@ extern "C" int sc_moran_seeded_begin(sc_ctx *c, const uint64_t *state6, int64_t 
     // generator's FIRST chunk for callers whose operands are resident -- scoring starts ~9 ms earlier, the step is 3.5 ms
     // LONGER (165.4 vs 161.9 ms, same box): the full-chip column-sum kernels delay the generator's first units, and the
     // scoring then only waits longer for its first chunks.)
-    const int rc = pipe_begin(c, state6, n_cells, n_perm, permgen_can_swap_inverse(n_cells) ? 1 : 2, *pp, ahead_n);
-    c->pg_ahead = ahead;
-    if (rc != SC_OK) { delete pp; return rc; }
-    c->pipe = pp;
+    SC_TRY(pipe_begin(c, state6, n_cells, n_perm, permgen_can_swap_inverse(n_cells) ? 1 : 2, pipe_units_ahead(), *pp, ahead_n));
+    c->pipe = std::move(pp);
     return SC_OK;
 }
 
@@ -2307,26 +2093,23 @@ extern "C" int sc_moran_seeded_finish(sc_ctx *c, uint64_t *state6, double *I_out
     SC_REQUIRE(c && state6, SC_ERR_INVALID, "sc_moran_seeded_finish: null pointer");
     SC_REQUIRE(c->pipe, SC_ERR_STATE, "sc_moran_seeded_finish: no job begun (sc_moran_seeded_begin)");
     SC_HIP(hipSetDevice(c->device));
-    PermPipe *pp = c->pipe;
+    std::unique_ptr<PermPipe> pp = std::move(c->pipe);
     const int64_t n_perm = pp->n_perm;
-    int rc = SC_OK;
-    if (pp->n != c->e_n) {
-        sc_set_error("sc_moran_seeded_finish: the job was begun for %lld cells, the expression has %lld", (long long)pp->n, (long long)c->e_n);
-        rc = SC_ERR_INVALID;
-    }
-    if (rc == SC_OK) rc = moran_seeded_streams(c, state6, n_perm, I_out, sims_out, count_ge_out, sim_sum_out, sim_sumsq_out, pp);
-    uint64_t state0[6];
-    for (int k = 0; k < 6; ++k) state0[k] = pp->state0[k];
-    c->pipe = nullptr;
-    pipe_drain(c, *pp);       // (no-op after a completed consume; an error path may have left launches in flight)
-    delete pp;
-    if (rc == SC_PERMGEN_RETRY) {  // the block-parallel scan failed its verification: nothing was returned, rerun in one piece
-        for (int k = 0; k < 6; ++k) state6[k] = state0[k];
-        const int mode = c->pg_mode;
-        c->pg_mode = 1;
-        rc = moran_seeded_streams(c, state6, n_perm, I_out, sims_out, count_ge_out, sim_sum_out, sim_sumsq_out);
-        c->pg_mode = mode;
-    }
+    // first the begun job; if it fails its verification, nothing was returned: the job is dropped and rerun in one piece
+    auto attempt = [&]() -> int {
+        if (!pp) return moran_seeded_streams(c, state6, n_perm, I_out, sims_out, count_ge_out, sim_sum_out, sim_sumsq_out);
+        SC_REQUIRE(pp->n == c->e_n, SC_ERR_INVALID, "sc_moran_seeded_finish: the job was begun for %lld cells, the expression has %lld",
+                   (long long)pp->n, (long long)c->e_n);
+        return moran_seeded_streams(c, state6, n_perm, I_out, sims_out, count_ge_out, sim_sum_out, sim_sumsq_out, pp.get());
+    };
+    auto drop = [&]() -> int {
+        pipe_drain(c, *pp);
+        for (int k = 0; k < 6; ++k) state6[k] = pp->state0[k];
+        pp.reset();
+        return SC_OK;
+    };
+    const int rc = permgen_rerun_on_failure(c, attempt, drop);
+    if (pp) pipe_drain(c, *pp);   // (no-op after a completed consume; an error path may have left launches in flight)
     return rc;
 }
 
@@ -3152,7 +2935,8 @@ static int lm_finish(sc_ctx *c, const LmJob &j, int64_t n_perm, float *z_out, fl
                      int32_t *count_out, uint8_t *zero_var_out, bool arrays_done = false)
 {
     const int64_t n = j.n, G = j.G;
-    SC_TRY(c->lee_a.ensure(sizeof(float) * (size_t)n * (size_t)G, &c->mem));
+    const bool counts = n_perm > 0 && count_out;
+    if (!arrays_done || counts) SC_TRY(c->lee_a.ensure(sizeof(float) * (size_t)n * (size_t)G, &c->mem));   // (staging)
     unsigned gu = (unsigned)ceil_div64(n * G, 256);
     struct { const float *src; float *dst; } outs[3] = {{j.Z32, z_out}, {j.Lag32, lag_out}, {j.I32, I_out}};
     for (auto &o : outs) {
@@ -3161,7 +2945,7 @@ static int lm_finish(sc_ctx *c, const LmJob &j, int64_t n_perm, float *z_out, fl
         SC_HIP(hipMemcpyAsync(o.dst, c->lee_a.p, sizeof(float) * (size_t)n * (size_t)G, hipMemcpyDeviceToHost,
                               c->stream));
     }
-    if (n_perm > 0 && count_out) {
+    if (counts) {
         hipLaunchKernelGGL(k_untile<int32_t>, dim3(gu), dim3(256), 0, c->stream, j.cnt, c->lee_a.as<int32_t>(), n, G);
         SC_HIP(hipMemcpyAsync(count_out, c->lee_a.p, sizeof(int32_t) * (size_t)n * (size_t)G, hipMemcpyDeviceToHost,
                               c->stream));
@@ -3196,6 +2980,12 @@ extern "C" int sc_local_moran(sc_ctx *c, int64_t n_perm, int64_t perm_row0, floa
     return lm_finish(c, j, n_perm, z_out, lag_out, I_out, count_out, zero_var_out);
 }
 
+// A thread that is joined when it is destroyed (C++17 has no std::jthread)
+struct JoiningThread {
+    std::thread t;
+    ~JoiningThread() { if (t.joinable()) t.join(); }
+};
+
 // The same with the permutations drawn here: n_perm numpy-exact permutations of the cells from state6 (as
 // sc_perm_generate would draw them; state6 is advanced the same way, the table stays resident), generated chunk
 // by chunk while the per-cell counts of the finished chunks are taken -- the generator's chain is the longest part of
@@ -3214,8 +3004,8 @@ extern "C" int sc_local_moran_seeded(sc_ctx *c, uint64_t *state6, int64_t n_perm
     // 100 genes, that r03 copied to the caller's (pageable) arrays AFTER the last count, 0.1 s of a 0.5-s call.  A helper
     // thread un-tiles and copies them out on a stream of its own while the generator and the counts run (neither uses
     // the PCIe link); this thread keeps enqueuing the pipeline.
-    std::thread copier;
     int copier_rc = SC_OK;
+    std::optional<JoiningThread> copier;   // (declared after what its thread writes; reset() joins)
     bool copier_started = false;
     static const bool copy_beside = !getenv("SC_LM_COPY_LATE");   // (A/B)
     auto prepare = [&]() -> int {
@@ -3230,7 +3020,7 @@ extern "C" int sc_local_moran_seeded(sc_ctx *c, uint64_t *state6, int64_t n_perm
         SC_HIP(hipEventDestroy(ready));
         const LmJob jj = j;
         try {   // (no thread to be had: the arrays are copied at the end, as in r03)
-            copier = std::thread([c, jj, z_out, lag_out, I_out, &copier_rc]() {
+            copier.emplace().t = std::thread([c, jj, z_out, lag_out, I_out, &copier_rc]() {
             if (hipSetDevice(c->device) != hipSuccess) { copier_rc = SC_ERR_HIP; return; }
             const unsigned gu = (unsigned)ceil_div64(jj.n * jj.G, 256);
             const struct { const float *src; float *dst; } outs[3] = {{jj.Z32, z_out}, {jj.Lag32, lag_out}, {jj.I32, I_out}};
@@ -3253,18 +3043,12 @@ extern "C" int sc_local_moran_seeded(sc_ctx *c, uint64_t *state6, int64_t n_perm
         if (j.mode == 0) return p1 == n_perm ? lm_count(c, j, 0, 0, n_perm) : SC_OK;   // (the one-kernel form: all rows at the end)
         return lm_count(c, j, 0, p0, p1);
     };
-    const int ahead = c->pg_ahead;
-    c->pg_ahead = 2;
-    int rc = sc_perm_pipeline(c, state6, c->e_n, n_perm, 0, prepare, count);
-    if (rc == SC_PERMGEN_RETRY) {   // the block-parallel scan failed its verification: the counts restart at permutation 0
-        if (copier.joinable()) copier.join();   // (the second preparation rewrites what it reads -- with the same values)
-        const int mode = c->pg_mode;
-        c->pg_mode = 1;
-        rc = sc_perm_pipeline(c, state6, c->e_n, n_perm, 0, prepare, count);
-        c->pg_mode = mode;
-    }
-    c->pg_ahead = ahead;
-    if (copier.joinable()) copier.join();
+    // a job that fails its verification is rerun with the sequential scan: the counts restart at permutation 0, and the
+    // copier is joined first (the second preparation rewrites what it reads -- with the same values)
+    const int rc = permgen_rerun_on_failure(
+        c, [&]() { return sc_perm_pipeline(c, state6, c->e_n, n_perm, 0, 2, prepare, count); },
+        [&]() { copier.reset(); return SC_OK; });
+    copier.reset();
     SC_TRY(rc);
     if (copier_started && copier_rc != SC_OK) {
         sc_set_error("sc_local_moran_seeded: the copy of z / lag / I to the host failed");
@@ -3471,6 +3255,52 @@ __global__ __launch_bounds__(256) void k_lee_local_count_sorted(const long long 
     count[i] = first ? cnt : count[i] + cnt;
 }
 
+// The vectors of one local Lee job (sc_lee_local, sc_lee_local_seeded), n each
+struct LlJob { int64_t n = 0; double *zx = nullptr, *zy = nullptr, *lag = nullptr, *L = nullptr; int32_t *cnt = nullptr; };
+
+// z_x and z_y from the standardised tiles (c->Z), lag = W z_y, L_local = z_x * lag; and what the per-cell counts of
+// n_perm permutations need
+static int ll_prepare(sc_ctx *c, int32_t gene_x, int32_t gene_y, int64_t n_perm, const LlJob &j)
+{
+    const int64_t n = j.n;
+    const unsigned gcol = (unsigned)ceil_div64(n, 256);
+    hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_x, j.zx);
+    hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_y, j.zy);
+    sc_launch_spmv_vec(c, c->g_indptr.as<int64_t>(), c->g_indices.as<int32_t>(), c->g_data.as<double>(), j.zy, j.lag, n);
+    hipLaunchKernelGGL(k_vec_mul, dim3(gcol), dim3(256), 0, c->stream, j.zx, j.lag, j.L, n);
+    if (n_perm > 0 && !c->lm_direct) {
+        SC_TRY(sc_graph_ensure_order(c));
+        SC_TRY(c->lm_ys.ensure(sizeof(double) * (size_t)LL_PERM_BATCH * (size_t)n, &c->mem));
+    }
+    SC_HIP(hipGetLastError());
+    return SC_OK;
+}
+
+// counts of permutations [p0, p1) of the job (rows row0 + p of the forward table); p0 == 0 starts the counts
+static int ll_count(sc_ctx *c, const LlJob &j, int64_t row0, int64_t p0, int64_t p1)
+{
+    const int64_t n = j.n;
+    const unsigned gcol = (unsigned)ceil_div64(n, 256);
+    if (c->lm_direct) {   // r01 form (development A/B)
+        SC_REQUIRE(p0 == 0, SC_ERR_STATE, "internal: the one-kernel local Lee form counts all permutations at once");
+        hipLaunchKernelGGL(k_lee_local_count, dim3(gcol), dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
+                           c->g_indices.as<int32_t>(), c->g_data.as<double>(), j.zx, j.zy, j.L,
+                           c->perm.as<int32_t>() + row0 * c->p_stride, c->p_stride, (int)(p1 - p0), j.cnt, n);
+    } else {
+        for (int64_t p = p0; p < p1; p += LL_PERM_BATCH) {
+            const int nb = (int)(p1 - p < LL_PERM_BATCH ? p1 - p : LL_PERM_BATCH);
+            hipLaunchKernelGGL(k_lee_local_gather, dim3(gcol, (unsigned)nb), dim3(256), 0, c->stream, j.zy,
+                               c->g_order.as<int32_t>(), c->perm.as<int32_t>() + (row0 + p) * c->p_stride, c->p_stride,
+                               n, c->lm_ys.as<double>());
+            hipLaunchKernelGGL(k_lee_local_count_sorted, dim3(gcol), dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
+                               c->g_indices_r.as<int32_t>(), c->g_data.as<double>(), c->g_order.as<int32_t>(), j.zx,
+                               c->lm_ys.as<double>(), j.L, nb, j.cnt, n, p == 0 ? 1 : 0);
+        }
+    }
+    SC_HIP(hipGetLastError());
+    return SC_OK;
+}
+
 extern "C" int sc_lee_local(sc_ctx *c, int32_t gene_x, int32_t gene_y, int64_t n_perm, int64_t perm_row0,
                             double *zx_out, double *lag_out, double *L_local_out, int32_t *count_out)
 {
@@ -3492,38 +3322,19 @@ extern "C" int sc_lee_local(sc_ctx *c, int32_t gene_x, int32_t gene_y, int64_t n
     hipLaunchKernelGGL(k_div_sd, dim3((unsigned)ceil_div64(n * SC_TILE, 256), (unsigned)T), dim3(256), 0, c->stream,
                        c->Z.as<double>(), c->g_var.as<double>(), n);
     SC_TRY(c->lee_a.ensure(sizeof(double) * (size_t)n * 5, &c->mem));
-    double *vx = c->lee_a.as<double>(), *vy = vx + n, *vlag = vx + 2 * n, *vL = vx + 3 * n;
-    int32_t *vcnt = reinterpret_cast<int32_t *>(vx + 4 * n);
-    unsigned gcol = (unsigned)ceil_div64(n, 256);
-    hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_x, vx);
-    hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_y, vy);
-    sc_launch_spmv_vec(c, c->g_indptr.as<int64_t>(), c->g_indices.as<int32_t>(), c->g_data.as<double>(), vy, vlag, n);
-    hipLaunchKernelGGL(k_vec_mul, dim3(gcol), dim3(256), 0, c->stream, vx, vlag, vL, n);
-    if (n_perm > 0 && c->lm_direct) {   // r01 form (development A/B)
+    LlJob j;
+    j.n = n; j.zx = c->lee_a.as<double>(); j.zy = j.zx + n; j.lag = j.zx + 2 * n; j.L = j.zx + 3 * n;
+    j.cnt = reinterpret_cast<int32_t *>(j.zx + 4 * n);
+    SC_TRY(ll_prepare(c, gene_x, gene_y, n_perm, j));
+    if (n_perm > 0) {
         KernelTimerScope ts(c, SC_K_LEE_PERM);
-        hipLaunchKernelGGL(k_lee_local_count, dim3(gcol), dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
-                           c->g_indices.as<int32_t>(), c->g_data.as<double>(), vx, vy, vL,
-                           c->perm.as<int32_t>() + perm_row0 * c->p_stride, c->p_stride, (int)n_perm, vcnt, n);
-    } else if (n_perm > 0) {
-        SC_TRY(sc_graph_ensure_order(c));
-        SC_TRY(c->lm_ys.ensure(sizeof(double) * (size_t)LL_PERM_BATCH * (size_t)n, &c->mem));
-        KernelTimerScope ts(c, SC_K_LEE_PERM);
-        for (int64_t p0 = 0; p0 < n_perm; p0 += LL_PERM_BATCH) {
-            const int nb = (int)(n_perm - p0 < LL_PERM_BATCH ? n_perm - p0 : LL_PERM_BATCH);
-            hipLaunchKernelGGL(k_lee_local_gather, dim3(gcol, (unsigned)nb), dim3(256), 0, c->stream, vy,
-                               c->g_order.as<int32_t>(), c->perm.as<int32_t>() + (perm_row0 + p0) * c->p_stride, c->p_stride,
-                               n, c->lm_ys.as<double>());
-            hipLaunchKernelGGL(k_lee_local_count_sorted, dim3(gcol), dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
-                               c->g_indices_r.as<int32_t>(), c->g_data.as<double>(), c->g_order.as<int32_t>(), vx,
-                               c->lm_ys.as<double>(), vL, nb, vcnt, n, p0 == 0 ? 1 : 0);
-        }
+        SC_TRY(ll_count(c, j, perm_row0, 0, n_perm));
     }
-    SC_HIP(hipGetLastError());
-    SC_HIP(hipMemcpyAsync(zx_out, vx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(lag_out, vlag, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(L_local_out, vL, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(zx_out, j.zx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(lag_out, j.lag, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(L_local_out, j.L, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     if (n_perm > 0)
-        SC_HIP(hipMemcpyAsync(count_out, vcnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        SC_HIP(hipMemcpyAsync(count_out, j.cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     return SC_OK;
 }
@@ -3552,8 +3363,8 @@ extern "C" int sc_lee_local_seeded(sc_ctx *c, uint64_t *state6, int32_t gene_x, 
     const int64_t n = c->e_n, T = c->e_tiles, Pg = n_perm_global, Pl = n_perm_local;
     const int blocks = (int)ceil_div64(n, LEE_CELLS_PER_BLOCK);
     const unsigned gcol = (unsigned)ceil_div64(n, 256);
-    double *va = nullptr, *vlag_g = nullptr, *vu = nullptr, *vb = nullptr, *vlag = nullptr, *vL = nullptr;
-    int32_t *vcnt = nullptr;
+    double *vlag_g = nullptr, *vu = nullptr;
+    LlJob j;   // (z_x, z_y: sc_lee's operands too)
     auto prepare = [&]() -> int {
         // ---- sc_lee's operands: z-scores (population sd), Lag = W Z, u = W^T z_x ----
         SC_TRY(expr_center(c));
@@ -3567,25 +3378,19 @@ extern "C" int sc_lee_local_seeded(sc_ctx *c, uint64_t *state6, int32_t gene_x, 
         SC_HIP(hipStreamSynchronize(c->stream));
         SC_REQUIRE(var[0] > 0.0 && var[1] > 0.0, SC_ERR_INVALID, "sc_lee_local_seeded: a gene of the pair has zero variance");
         SC_TRY(c->lee_a.ensure(sizeof(double) * (size_t)n * 8, &c->mem));
-        va = c->lee_a.as<double>(); vlag_g = va + n; vu = va + 2 * n; vb = va + 3 * n;   // va = z_x, vb = z_y: sc_lee_local's vx, vy too
-        vlag = va + 4 * n; vL = va + 5 * n;
-        vcnt = reinterpret_cast<int32_t *>(va + 6 * n);
+        j.n = n; j.zx = c->lee_a.as<double>(); vlag_g = j.zx + n; vu = j.zx + 2 * n; j.zy = j.zx + 3 * n;
+        j.lag = j.zx + 4 * n; j.L = j.zx + 5 * n;
+        j.cnt = reinterpret_cast<int32_t *>(j.zx + 6 * n);
         SC_TRY(c->lee_b.ensure(sizeof(double) * (size_t)blocks * (size_t)(Pg + 1), &c->mem));
         SC_TRY(c->lee_out.ensure(sizeof(double) * (size_t)(Pg + 1 > T * SC_TILE ? Pg + 1 : T * SC_TILE), &c->mem));
         if (Pg > 0) SC_TRY(sc_graph_ensure_transpose(c));
-        hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_x, va);
+        // ---- sc_lee_local's: z_x, z_y, lag = W z_y on the vector, L_local = z_x * lag ----
+        SC_TRY(ll_prepare(c, gene_x, gene_y, Pl, j));
+        // ---- sc_lee's: the observed sum and u = W^T z_x ----
         hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Lag.as<double>(), n, (int64_t)gene_y, vlag_g);
-        hipLaunchKernelGGL(k_vec_dot, dim3(blocks), dim3(256), 0, c->stream, va, vlag_g, n, c->lee_b.as<double>() + (size_t)Pg * blocks);
-        hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_y, vb);
+        hipLaunchKernelGGL(k_vec_dot, dim3(blocks), dim3(256), 0, c->stream, j.zx, vlag_g, n, c->lee_b.as<double>() + (size_t)Pg * blocks);
         if (Pg > 0)
-            sc_launch_spmv_vec(c, c->gt_indptr.as<int64_t>(), c->gt_indices.as<int32_t>(), c->gt_data.as<double>(), va, vu, n);
-        // ---- sc_lee_local's: lag = W z_y on the vector, L_local = z_x * lag ----
-        sc_launch_spmv_vec(c, c->g_indptr.as<int64_t>(), c->g_indices.as<int32_t>(), c->g_data.as<double>(), vb, vlag, n);
-        hipLaunchKernelGGL(k_vec_mul, dim3(gcol), dim3(256), 0, c->stream, va, vlag, vL, n);
-        if (Pl > 0 && !c->lm_direct) {
-            SC_TRY(sc_graph_ensure_order(c));
-            SC_TRY(c->lm_ys.ensure(sizeof(double) * (size_t)LL_PERM_BATCH * (size_t)n, &c->mem));
-        }
+            sc_launch_spmv_vec(c, c->gt_indptr.as<int64_t>(), c->gt_indices.as<int32_t>(), c->gt_data.as<double>(), j.zx, vu, n);
         SC_HIP(hipGetLastError());
         return SC_OK;
     };
@@ -3593,47 +3398,27 @@ extern "C" int sc_lee_local_seeded(sc_ctx *c, uint64_t *state6, int32_t gene_x, 
         KernelTimerScope ts(c, SC_K_LEE_PERM);
         const int64_t a1 = p1 < Pg ? p1 : Pg;
         if (p0 < a1)   // rows of the global statistic
-            hipLaunchKernelGGL(k_vec_gather_dot, dim3(blocks, (unsigned)(a1 - p0)), dim3(256), 0, c->stream, vu, vb,
+            hipLaunchKernelGGL(k_vec_gather_dot, dim3(blocks, (unsigned)(a1 - p0)), dim3(256), 0, c->stream, vu, j.zy,
                                c->perm.as<int32_t>() + p0 * c->p_stride, c->p_stride, n, c->lee_b.as<double>() + (size_t)p0 * blocks);
+        // rows of the per-cell counts: permutations [b0 - Pg, p1 - Pg) of the local job (the one-kernel form: all at the end)
         const int64_t b0 = p0 > Pg ? p0 : Pg;
-        if (b0 < p1 && c->lm_direct) {   // r01 form (development A/B): all rows at the end
-            if (p1 == Pg + Pl)
-                hipLaunchKernelGGL(k_lee_local_count, dim3(gcol), dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
-                                   c->g_indices.as<int32_t>(), c->g_data.as<double>(), va, vb, vL,
-                                   c->perm.as<int32_t>() + Pg * c->p_stride, c->p_stride, (int)Pl, vcnt, n);
-        } else {
-            for (int64_t q0 = b0; q0 < p1; q0 += LL_PERM_BATCH) {   // rows of the per-cell counts
-                const int nb = (int)(p1 - q0 < LL_PERM_BATCH ? p1 - q0 : LL_PERM_BATCH);
-                hipLaunchKernelGGL(k_lee_local_gather, dim3(gcol, (unsigned)nb), dim3(256), 0, c->stream, vb,
-                                   c->g_order.as<int32_t>(), c->perm.as<int32_t>() + q0 * c->p_stride, c->p_stride, n, c->lm_ys.as<double>());
-                hipLaunchKernelGGL(k_lee_local_count_sorted, dim3(gcol), dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
-                                   c->g_indices_r.as<int32_t>(), c->g_data.as<double>(), c->g_order.as<int32_t>(), va,
-                                   c->lm_ys.as<double>(), vL, nb, vcnt, n, q0 == Pg ? 1 : 0);
-            }
-        }
+        if (b0 < p1 && !c->lm_direct) SC_TRY(ll_count(c, j, Pg, b0 - Pg, p1 - Pg));
+        if (b0 < p1 && c->lm_direct && p1 == Pg + Pl) SC_TRY(ll_count(c, j, Pg, 0, Pl));
         SC_HIP(hipGetLastError());
         return SC_OK;
     };
-    const int ahead = c->pg_ahead;
-    c->pg_ahead = 2;
-    int rc = sc_perm_pipeline(c, state6, n, Pg + Pl, 0, prepare, score);
-    if (rc == SC_PERMGEN_RETRY) {   // the block-parallel scan failed its verification: everything restarts at permutation 0
-        const int mode = c->pg_mode;
-        c->pg_mode = 1;
-        rc = sc_perm_pipeline(c, state6, n, Pg + Pl, 0, prepare, score);
-        c->pg_mode = mode;
-    }
-    c->pg_ahead = ahead;
-    SC_TRY(rc);
+    // a job that fails its verification is rerun with the sequential scan: everything restarts at permutation 0 (the
+    // first rows' flag restarts the counts)
+    SC_TRY(permgen_rerun_on_failure(c, [&]() { return sc_perm_pipeline(c, state6, n, Pg + Pl, 0, 2, prepare, score); }, nullptr));
     std::vector<double> host((size_t)Pg + 1);
     hipLaunchKernelGGL(k_row_sum, dim3((unsigned)ceil_div64(Pg + 1, 256)), dim3(256), 0, c->stream, c->lee_b.as<double>(),
                        (int)(Pg + 1), blocks, c->lee_out.as<double>());
     SC_HIP(hipGetLastError());
     SC_HIP(hipMemcpyAsync(host.data(), c->lee_out.p, sizeof(double) * (size_t)(Pg + 1), hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(zx_out, va, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(lag_out, vlag, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(L_local_out, vL, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (Pl > 0) SC_HIP(hipMemcpyAsync(count_out, vcnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(zx_out, j.zx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(lag_out, j.lag, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(L_local_out, j.L, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (Pl > 0) SC_HIP(hipMemcpyAsync(count_out, j.cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     const double L = host[(size_t)Pg];
     *L_out = L;

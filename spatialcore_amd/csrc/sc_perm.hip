@@ -177,3 +177,222 @@ extern "C" int sc_perm_generate(sc_ctx *c, uint64_t *state6, int64_t n, int64_t 
     }
     return SC_OK;
 }
+
+// ---- the generator / consumer pipeline of the seeded statistics ----
+#ifndef PIPE_AHEAD
+#define PIPE_AHEAD 3         // launch units the generator's preparation runs ahead of its chain inside the pipeline
+#endif
+#ifndef PIPE_FIRST
+#define PIPE_FIRST 32        // permutations of the first pipeline chunk
+#endif
+#ifndef PIPE_TAIL
+#define PIPE_TAIL "96,48,24" // the last chunks, tapering: see pipe_tail_perms
+#endif
+#ifndef PIPE_SWAP_STREAMS
+#define PIPE_SWAP_STREAMS 2  // swap chunks in flight (they are latency-bound: two overlap almost for free)
+#endif
+
+// permutations of the pipeline's first chunk (SC_PIPE_FIRST: development, to sweep the schedule)
+static int64_t pipe_first_perms()
+{
+    int64_t v = PIPE_FIRST;
+    if (const char *e = getenv("SC_PIPE_FIRST")) v = atoi(e);
+    return v < 8 || v > PERM_CHUNK ? PIPE_FIRST : v;
+}
+// The job ends with what is left once the generator's chain has finished: the swaps of its last chunk (~10 ms whatever
+// its size: one workgroup per permutation, latency-bound) and the consumption of every chunk not consumed yet.  Behind
+// a 128-permutation chunk that is its swaps AND its 10-ms consumption; tapering chunks leave a few milliseconds (bench
+// step, same box, ms: one 32-permutation last chunk 173.5 / 174.6; 64,32: 172.4 / 178.8; 64,32,16: 172.8 / 173.1; 96,48,24: 169.4 / 169.4).
+// SC_PIPE_TAIL="a,b,...": development, to sweep the schedule ("0": no short chunks at the end).
+static std::vector<int64_t> pipe_tail_perms()
+{
+    const char *e = getenv("SC_PIPE_TAIL");
+    std::vector<int64_t> t;
+    for (const char *p = e ? e : PIPE_TAIL; *p;) {
+        char *end = nullptr;
+        const long v = strtol(p, &end, 10);
+        if (end == p) break;
+        if (v >= 8 && v <= PERM_CHUNK) t.push_back(v);
+        p = *end == ',' ? end + 1 : end;
+    }
+    return t;
+}
+int64_t pipe_tail_total()
+{
+    int64_t s = 0;
+    for (int64_t v : pipe_tail_perms()) s += v;
+    return s;
+}
+int pipe_units_ahead()
+{
+    if (const char *v = getenv("SC_PIPE_AHEAD")) return atoi(v);  // development: sweep the lookahead
+    return PIPE_AHEAD;
+}
+
+// The generator / consumer pipeline shared by sc_moran_seeded and sc_lee_seeded: numpy-exact permutation rows
+// [0, n_perm) of length n are produced chunk by chunk on the generator's streams (stream2: rejection scan chain,
+// stream_pg: its preparation, stream_px: verification + expansion, stream3/4: Fisher-Yates swaps) while
+// `score(p0, p1)` consumes finished chunks on the context stream.  table: 0 = permutation rows (c->perm),
+// 1 = inverse rows only (c->inv; the same transpositions in ascending order), 2 = both (rows + k_invert_perm).
+// `after_first` runs on the host right after the first chunk of the generator has been enqueued (the generator is
+// the longest chain and depends on nothing else; everything host-blocking of the consumer's set-up goes here).
+static int pipe_generate(sc_ctx *c, PermPipe &pp, int64_t k)
+{
+    hipEvent_t &scanned = pp.ev[(size_t)(2 * k)], &swapped = pp.ev[(size_t)(2 * k + 1)];
+    // Two swap kernels in flight only for the job's LAST chunks (r04).  A swap workgroup is 8 wavefronts that live ~10 ms;
+    // two chunks' worth of them (256) spread over the ~96 CUs the scoring kernel leaves, next to the table builders' two-
+    // wavefront workgroups, left no CU with the 16 free wavefront slots a 1024-thread preparation workgroup needs: the
+    // chain's clock profile showed its units arriving 1-8 ms late behind every chunk boundary (55 k clocks of waiting per
+    // permutation; 37 k with one swap kernel at a time).  The tapering last chunks arrive 2-6 ms apart after the chain
+    // is all but done, and keep overlapping.
+    const int64_t chunks = (int64_t)pp.bounds.size() - 1;
+    const bool overlap = PIPE_SWAP_STREAMS > 1 && (k & 1) && (k >= chunks - 3 || getenv("SC_SWAP_OVERLAP_ALL") != nullptr);
+    hipStream_t sw = overlap ? c->stream4 : c->stream3;
+    SC_HIP(hipEventCreateWithFlags(&scanned, hipEventDisableTiming));
+    SC_HIP(hipEventCreateWithFlags(&swapped, hipEventDisableTiming));
+    SC_TRY(permgen_scan_chunk(c, &pp.job, pp.bounds[(size_t)k + 1], c->stream2, c->stream_px, scanned));
+    SC_HIP(hipStreamWaitEvent(sw, scanned, 0));
+    // Two permutations per swap workgroup while the chain still runs -- workgroups of the preparation kernels' own size --
+    // but only beside the Moran scoring kernel (the one consumer that fills its CUs with wavefronts that live for
+    // milliseconds): there the step gains 5 ms (151 against 156).  Two permutations in lockstep take 13-15 ms per chunk
+    // instead of 10-12, and a light consumer (Lee's row sums, the local counts) leaves the chain at 12.8 ms per chunk:
+    // with the pairs the swap stream became the bottleneck (Lee 10 x 10 pairs: 27.8 against 24.9 ms per pair).
+    const int pw = (k < chunks - 3 && c->score_leave_cus > 8) ? 2 : 1;
+    SC_TRY(permgen_swap_chunk(c, &pp.job, pp.bounds[(size_t)k], pp.bounds[(size_t)k + 1], sw, pp.table == 1, pw));
+    if (pp.table == 2) SC_TRY(invert_rows(c, pp.bounds[(size_t)k], pp.bounds[(size_t)k + 1], sw));
+    SC_HIP(hipEventRecord(swapped, sw));
+    pp.enqueued = k + 1;
+    return SC_OK;
+}
+
+void pipe_drain(sc_ctx *c, PermPipe &pp)
+{
+    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
+    if (c->stream3) (void)hipStreamSynchronize(c->stream3);
+    if (c->stream4) (void)hipStreamSynchronize(c->stream4);
+    if (c->stream_px) (void)hipStreamSynchronize(c->stream_px);
+    if (c->stream_fr) (void)hipStreamSynchronize(c->stream_fr);
+    for (hipStream_t sp : c->stream_pg)
+        if (sp) (void)hipStreamSynchronize(sp);
+    (void)hipStreamSynchronize(c->stream);
+    for (hipEvent_t e : pp.ev)
+        if (e) (void)hipEventDestroy(e);
+    pp.ev.clear();
+}
+
+// Begin: allocations, chunk schedule, the generator's set-up and its first `chunks_ahead` chunks (all of them when
+// chunks_ahead >= the number of chunks).  Needs nothing but n and the generator state -- no graph, no expression.
+// units_ahead: launch units the scan's preparation runs ahead of its chain (permgen_begin).
+int pipe_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int table, int units_ahead, PermPipe &pp,
+               int64_t chunks_ahead, const std::function<int()> &after_first_chunk)
+{
+    SC_REQUIRE(state6, SC_ERR_INVALID, "permutation pipeline: null generator state");
+    SC_REQUIRE(n_perm >= 1, SC_ERR_INVALID, "permutation pipeline: n_perm must be >= 1");
+    SC_REQUIRE(table == 0 || permgen_can_swap_inverse(n) || table == 2, SC_ERR_STATE, "inverse-only tables need a longer permutation");
+    SC_TRY(sc_perm_alloc(c, n, n_perm));
+    // the resident table is being overwritten from here on: nothing may take it for valid until the job has been consumed
+    // (sc_moran / sc_local_moran / sc_lee_shared with a resident table then fail with "holds 0 rows" instead of reading
+    // rows the generator's streams are still writing)
+    c->p_count = 0;
+    c->inv_rows_valid = 0;
+    c->perm_forward_valid = false;
+    if (!c->stream2) {  // (SC_STREAM_PRIORITY=1: the r01 prioritised chain stream, for experiments; no gain measured in r02)
+        int prio_lo = 0, prio_hi = 0;
+        if (!getenv("SC_STREAM_PRIORITY") || hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess ||
+            hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_hi) != hipSuccess) {
+            (void)hipGetLastError();
+            c->stream2 = nullptr;
+            SC_HIP(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
+        }
+    }
+    if (!c->stream_px) SC_HIP(hipStreamCreateWithFlags(&c->stream_px, hipStreamNonBlocking));
+    if (!c->stream3) SC_HIP(hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
+    if (!c->stream4) SC_HIP(hipStreamCreateWithFlags(&c->stream4, hipStreamNonBlocking));
+    // allocations first (hipMalloc synchronises the device), then the streams run freely
+    if (table >= 1) SC_TRY(c->inv.ensure(sizeof(int32_t) * (size_t)(c->p_stride * n_perm + 32), &c->mem));
+    // chunk schedule: a short first chunk so that the consumer starts early, PERM_CHUNK each in the middle, a short
+    // last chunk (the job ends with the swaps and the consumption of the last chunk after the scan is done)
+    pp.bounds.clear();
+    pp.bounds.push_back(0);
+    if (n_perm > 3 * PERM_CHUNK) {
+        const int64_t first = pipe_first_perms(), last = pipe_tail_total();
+        const std::vector<int64_t> tail = pipe_tail_perms();
+        const int64_t rest = (n_perm - last - first) % PERM_CHUNK;
+        static const bool join = getenv("SC_PIPE_JOIN") != nullptr;   // development: a small remainder joins the first chunk (r02 / early r03)
+        int64_t p = first + (join && rest < PERM_CHUNK / 2 ? rest : 0);
+        pp.bounds.push_back(p);
+        if (p == first && rest > 0) { p += rest; pp.bounds.push_back(p); }   // the remainder: a chunk of its own, second
+        for (; p < n_perm - last; ) { p += PERM_CHUNK; pp.bounds.push_back(p); }
+        for (int64_t v : tail) { p += v; pp.bounds.push_back(p); }
+    } else {
+        for (int64_t p = PERM_CHUNK; p < n_perm; p += PERM_CHUNK) pp.bounds.push_back(p);
+        pp.bounds.push_back(n_perm);
+    }
+    const int64_t chunks = (int64_t)pp.bounds.size() - 1;
+    // stream2: scan(0) scan(1) ...   stream3/4: swaps(k) (+ inverse(k)) after scan(k)   stream: score(k) after swaps(k)
+    pp.ev.assign((size_t)chunks * 2, nullptr);
+    pp.table = table; pp.n = n; pp.n_perm = n_perm; pp.enqueued = 0;
+    for (int k = 0; k < 6; ++k) pp.state0[k] = state6[k];
+    pp.job = PermJob();
+    int rc = permgen_begin(c, state6, n, n_perm, units_ahead, &pp.job, c->stream2);
+    for (int64_t k = 0; k < chunks && k < chunks_ahead && rc == SC_OK; ++k) {
+        rc = pipe_generate(c, pp, k);
+        if (k == 0 && rc == SC_OK && after_first_chunk) rc = after_first_chunk();
+    }
+    if (rc != SC_OK) pipe_drain(c, pp);
+    return rc;
+}
+
+// Consume: `after_first` (the consumer's host-blocking set-up) runs once, then `score(p0, p1)` behind every chunk's
+// swaps on the context stream, with the generator kept TWO chunks ahead in the host's enqueue order (r03 timeline: with
+// one chunk ahead the chain sat idle for 5 ms behind the consumer's set-up; a chunk is some 250 API calls).
+int pipe_consume(sc_ctx *c, PermPipe &pp, uint64_t *state6, const std::function<int()> &after_first,
+                 const std::function<int(int64_t, int64_t)> &score)
+{
+    const int64_t chunks = (int64_t)pp.bounds.size() - 1;
+    int rc = SC_OK;
+    if (after_first) rc = after_first();
+    c->perm_bijective = true;  // device-generated rows are permutations by construction
+    c->perm_forward_valid = pp.table != 1;
+    for (int64_t k = 0; k < chunks && rc == SC_OK; ++k) {
+        while (rc == SC_OK && pp.enqueued < chunks && pp.enqueued < k + 3) rc = pipe_generate(c, pp, pp.enqueued);
+        if (rc == SC_OK && hipStreamWaitEvent(c->stream, pp.ev[(size_t)(2 * k + 1)], 0) != hipSuccess) {
+            sc_set_error("permutation pipeline: event plumbing failed");
+            rc = SC_ERR_HIP;
+        }
+        if (rc == SC_OK) rc = score(pp.bounds[(size_t)k], pp.bounds[(size_t)k + 1]);
+    }
+    pipe_drain(c, pp);
+    if (rc != SC_OK) return rc;
+    SC_TRY(permgen_finish(c, &pp.job, state6));
+    c->p_count = pp.n_perm;
+    c->inv_rows_valid = pp.table >= 1 ? pp.n_perm : 0;
+    return SC_OK;
+}
+
+void sc_perm_pipe_abort(sc_ctx *c)
+{
+    if (!c->pipe) return;
+    pipe_drain(c, *c->pipe);
+    c->pipe.reset();
+    c->p_count = 0;
+}
+
+int sc_perm_pipeline(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_perm, int table, int units_ahead,
+                     const std::function<int()> &after_first, const std::function<int(int64_t, int64_t)> &score)
+{
+    sc_perm_pipe_abort(c);   // (a job begun with sc_moran_seeded_begin and never finished)
+    PermPipe pp;
+    SC_TRY(pipe_begin(c, state6, n, n_perm, table, units_ahead, pp, 2));
+    return pipe_consume(c, pp, state6, after_first, score);
+}
+
+int permgen_rerun_on_failure(sc_ctx *c, const std::function<int()> &attempt, const std::function<int()> &undo)
+{
+    int rc = attempt();
+    if (rc != SC_PERMGEN_RETRY) return rc;
+    if (undo) SC_TRY(undo());
+    struct ModeRestore { sc_ctx *c; int mode; ~ModeRestore() { c->pg_mode = mode; } } restore{c, c->pg_mode};
+    c->pg_mode = 1;
+    return attempt();
+}

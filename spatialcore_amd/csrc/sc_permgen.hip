@@ -2471,7 +2471,7 @@ static double expected_draws_per_perm(int64_t n)
 
 bool permgen_is_block_parallel(const sc_ctx *c, int64_t n) { return c->pg_mode != 1 && !c->pg_streams_serial && n >= PHI_MIN_N; }
 
-int permgen_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, PermJob *job, hipStream_t s)
+int permgen_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int units_ahead, PermJob *job, hipStream_t s)
 {
     job->n = n;
     job->n_perm = n_perm;
@@ -2499,7 +2499,7 @@ int permgen_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, 
     job->phi = permgen_is_block_parallel(c, n);
     job->B_done = 0; job->unit_no = 0;
     for (int64_t &g : job->gate_seen) g = 0;
-    job->ahead = c->pg_ahead >= 1 && c->pg_ahead <= PHI_AHEAD_MAX ? c->pg_ahead : 1;
+    job->units_ahead = units_ahead >= 1 && units_ahead <= PHI_AHEAD_MAX ? units_ahead : 1;
     if (job->phi && !c->pg_probed) {   // first block-parallel job of this context: can its streams overlap at all?
         for (hipStream_t &sp : c->stream_pg)
             if (!sp) SC_HIP(hipStreamCreateWithFlags(&sp, hipStreamNonBlocking));
@@ -2607,9 +2607,9 @@ int permgen_scan_chunk(sc_ctx *c, PermJob *job, int64_t p1, hipStream_t s, hipSt
             hipStream_t sp = c->stream_pg[(size_t)(u % PHI_STREAMS)];
             // The guess of unit u uses the exact state at the start of unit u - ahead, which the chain leaves when it
             // completes unit u - ahead - 1; that unit also is the last reader of the ring slots unit u overwrites.
-            const int64_t dep = u - job->ahead - 1;
+            const int64_t dep = u - job->units_ahead - 1;
             uint32_t *seglist = c->pg_seglist.as<uint32_t>() + (size_t)(u % PHI_FLAG_SLOTS) * (1 + PHI_UNIT);
-            const uint64_t ref = u >= job->ahead ? job->unit_start[(size_t)((u - job->ahead) % 8)] : 0;
+            const uint64_t ref = u >= job->units_ahead ? job->unit_start[(size_t)((u - job->units_ahead) % 8)] : 0;
             if (u < PHI_STREAMS) SC_HIP(hipStreamWaitEvent(sp, c->pg_ev[32], 0));  // the raw stream (recorded by permgen_begin)
             // (a gate in front of this stream's last k_seg_fill has waited for the same or a later "unit done" already)
             if (dep >= 0 && dep + 1 > job->gate_seen[(size_t)(u % PHI_STREAMS)])
@@ -2907,15 +2907,12 @@ static int perm_generate_once(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_
         // a long job: the chunked pipeline of the seeded statistics with nothing to consume -- the Fisher-Yates swaps of
         // chunk k run (on their own streams) beside the rejection scan of chunk k + 1 instead of all behind the scan
         // (r03, 999 permutations of 1M cells: 55 ms of swaps out of the call's critical path)
-        const int ahead = c->pg_ahead;
-        c->pg_ahead = 2;
-        const int rc = sc_perm_pipeline(c, state6, n, n_perm, 0, nullptr, [](int64_t, int64_t) -> int { return SC_OK; });
-        c->pg_ahead = ahead;
+        const int rc = sc_perm_pipeline(c, state6, n, n_perm, 0, 2, nullptr, [](int64_t, int64_t) -> int { return SC_OK; });
         if (rc == SC_OK) c->perm_forward_valid = true;
         return rc;
     }
     PermJob job;
-    SC_TRY(permgen_begin(c, state6, n, n_perm, &job, c->stream));
+    SC_TRY(permgen_begin(c, state6, n, n_perm, 1, &job, c->stream));
     for (int64_t p0 = 0; p0 < n_perm; p0 += PERM_CHUNK) {
         const int64_t p1 = p0 + PERM_CHUNK < n_perm ? p0 + PERM_CHUNK : n_perm;
         SC_TRY(permgen_scan_chunk(c, &job, p1, c->stream, nullptr, nullptr));
@@ -2931,12 +2928,6 @@ static int perm_generate_once(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_
 
 int sc_perm_generate_device(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_perm)
 {
-    int rc = perm_generate_once(c, state6, n, n_perm);
-    if (rc == SC_PERMGEN_RETRY) {  // state6 is only written on success: rerun with the sequential scan
-        const int mode = c->pg_mode;
-        c->pg_mode = 1;
-        rc = perm_generate_once(c, state6, n, n_perm);
-        c->pg_mode = mode;
-    }
-    return rc;
+    // (state6 is only written on success: nothing to undo before the sequential rerun)
+    return permgen_rerun_on_failure(c, [&]() { return perm_generate_once(c, state6, n, n_perm); }, nullptr);
 }

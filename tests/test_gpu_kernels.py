@@ -140,6 +140,63 @@ def test_block_parallel_scan_modes_agree_with_numpy(ctx, oracle, seed, n, P):
         ctx.set_permgen_mode(3)
 
 
+def test_sequential_rerun_through_every_pipeline_entry_point(ctx):
+    """Every entry point that runs the generator / consumer pipeline (P > 3 * PERM_CHUNK: the tapered chunk schedule)
+    reruns a job whose block-parallel scan failed its verification (mode 2) with the sequential scan: outputs and the
+    final generator state bit for bit those of mode 0, one fallback and one sequential job per generator job, and the
+    mode is the caller's again afterwards (the next call falls back too)."""
+    from spatialcore_amd._lib import rng_state_words
+
+    n, G, k, P = 140001, 21, 8, 400
+    rng = np.random.default_rng(140)
+    coords = rng.uniform(0, np.sqrt(n) * 10, (n, 2))
+    X = rng.poisson(rng.uniform(0.1, 3.0, G), (n, G)).astype(np.float32)
+    ctx.knn(coords, k, fetch=False)
+    ctx.graph_from_knn(1.0 / k)
+    ctx.set_expression(X, np.arange(G))
+    lee_x, lee_y = np.divmod(np.arange(45), G)          # 45 pairs: two sub-jobs of lee_seeded at this size
+
+    def begun_then_finished(w):
+        ctx.moran_seeded_begin(w, n, P)
+        return ctx.moran_seeded_finish(w)
+
+    calls = [   # name, call, generator jobs
+        ("generate", lambda w: {"perm": ctx.generate_permutations(w, n, P, fetch=True)}, 1),
+        ("moran_seeded", lambda w: ctx.moran_seeded(w, P), 1),
+        ("moran_begin_finish", begun_then_finished, 1),
+        ("lee_seeded", lambda w: ctx.lee_seeded(w, lee_x, lee_y, P, return_perms=True), 2),
+        ("lee_shared", lambda w: ctx.lee_shared(w, [0, 1, 2], [3, 4], P, return_perms=True), 1),
+        ("local_moran_seeded", lambda w: ctx.local_moran_seeded(w, n, P, fetch_counts=True), 1),
+        ("lee_local_seeded", lambda w: ctx.lee_local_seeded(w, n, 0, 1, 200, 200), 1),
+    ]
+
+    def run(name, call):
+        before = ctx.permgen_stats()
+        w = rng_state_words(np.random.default_rng(9))
+        out = call(w)
+        delta = tuple(a - b for a, b in zip(ctx.permgen_stats(), before))
+        return {key: np.asarray(v) for key, v in out.items() if v is not None}, w, delta
+
+    try:
+        ctx.set_permgen_mode(0)
+        want = {}
+        for name, call, jobs in calls:
+            out, w, (par, seq, fb, prepared, chained) = run(name, call)
+            assert (par, seq, fb) == (jobs, 0, 0), (name, par, seq, fb, ctx.permgen_note())
+            want[name] = out, w, prepared > 0    # a job with no prepared block has nothing to corrupt
+        ctx.set_permgen_mode(2)
+        for name, call, jobs in calls + calls[:1]:   # (the last call shows the one before left the mode as it was)
+            out, w, (par, seq, fb, _, _) = run(name, call)
+            w_out, w_w, had_prepared = want[name]
+            assert (par, seq, fb) == ((0, jobs, jobs) if had_prepared else (jobs, 0, 0)), (name, par, seq, fb)
+            assert w.tobytes() == w_w.tobytes(), name
+            assert out.keys() == w_out.keys(), name
+            for key, v in out.items():
+                assert v.dtype == w_out[key].dtype and v.tobytes() == w_out[key].tobytes(), (name, key)
+    finally:
+        ctx.set_permgen_mode(0)
+
+
 def test_device_permutation_stream_golden_and_midword(ctx):
     """numpy's own known answers (tests/golden/rng_kat.npz), incl. a generator that starts with a
     buffered 32-bit half."""
