@@ -43,7 +43,9 @@ extern "C" {
 #define SC_K_LEE_PERM 4
 #define SC_K_PERM_SCAN 5 /* rejection scan of the permutation generator (chain of exact block states + verification) */
 #define SC_K_PERM_SWAP 6 /* Fisher-Yates application, one workgroup (or wavefront) per permutation */
-#define SC_K_COUNT_ 8
+#define SC_K_KMEANS_SEED 7  /* centring + k-means++ seeding rounds of sc_kmeans_fit (all runs) */
+#define SC_K_KMEANS_LLOYD 8 /* Lloyd E-step + fixed-order centre reduction of sc_kmeans_fit, final E-step included */
+#define SC_K_COUNT_ 9
 
 typedef struct sc_ctx sc_ctx;
 
@@ -331,6 +333,31 @@ int sc_enrichment_counts(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t 
  * sum_p (count_p - observed)^2, #{p : count_p >= observed}: exact and order-free, ranks add theirs (sc_allreduce_sum_i64). */
 int sc_enrichment_counter(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_types, uint64_t seed, int64_t p_first,
                           int64_t n_perm, int64_t batch, int64_t *observed_out, int64_t *sums_out);
+
+/* ---- N5: niches -- k-means of the neighbourhood profiles (identify_niches, NB:299-522) ---------------------------
+ * The reference calls sklearn's KMeans(n_clusters=K, init="k-means++", n_init, max_iter, random_state).fit_predict;
+ * this replays sklearn 1.7.2 step for step, all n_init runs side by side on the device.  The caller supplies what
+ * numpy computes: tol = mean(var(X, axis=0)) * 1e-4 and x_mean = X.mean(axis=0) of the input, and the runs' draws of
+ * ONE RandomState(random_state): per run 1 + (K - 1) * L doubles, L = 2 + int(log(K)) -- the random_sample() of
+ * choice(n, p=w / sum(w)) (mapped to the first centre here by numpy's rule: cdf of the unit weights in the input type,
+ * searchsorted right), then uniform(size=L) of each later centre.  The stream does not depend on the data.
+ *  - X: n x C, row-major, dtype SC_F32 or SC_F64 (x_mean and centers_out in the same type); centred on the device;
+ *  - seeding: D^2 = (-2 x.c + |c|^2) + |x|^2 in fp64, stored in the input type and clipped at 0; potentials and the
+ *    prefix sum searched for rand_vals = u * pot are fp64 sums in one fixed order, rounded to the input type once;
+ *    the candidate of lowest potential wins (first on ties);
+ *  - Lloyd: fp64 distances, first index on ties; per-workgroup fp64 partial sums reduced in a fixed order (no
+ *    floating-point atomics); stop when the labels do not change (strict) or when sum |shift|^2 <= tol; without strict
+ *    convergence one more E-step against the final centres; an empty cluster takes the point farthest from its centre
+ *    (sklearn's _relocate_empty_clusters_dense; equal distances: lowest point index first);
+ *  - best run: a later run replaces it only if inertia < best and its partition differs (_is_same_clustering).
+ * Out: labels_out[n] of the best run, centers_out[K][C] (+ x_mean), inertia_out (fp64), seeds_out[n_init][K] (every
+ * run's k-means++ indices), n_iter_out and strict_out (1: labels unchanged in the last iteration) of the best run,
+ * distinct_out = number of distinct labels (< K: sklearn's ConvergenceWarning).  The result is a function of the
+ * arguments alone, bit for bit.  Invalid arguments (K < 2, K > n, C < 1, ...) give SC_ERR_INVALID. */
+int sc_kmeans_fit(sc_ctx *ctx, const void *X, int dtype, int64_t n, int32_t C, int32_t K, int32_t n_init,
+                  int32_t max_iter, double tol, const void *x_mean, const double *uniforms, int32_t *labels_out,
+                  void *centers_out, double *inertia_out, int64_t *seeds_out, int32_t *n_iter_out, int32_t *strict_out,
+                  int32_t *distinct_out);
 
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across

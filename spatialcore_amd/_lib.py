@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("SPATIALCORE_HIP_LIB") or os.path.join(_HERE, "libspat
 SC_OK, SC_ERR_INVALID, SC_ERR_STATE, SC_ERR_HIP, SC_ERR_NOMEM, SC_ERR_EMPTY = 0, 1, 2, 3, 4, 5
 SC_F32, SC_F64 = 0, 1
 K_MORAN_PERM, K_LAG, K_KNN, K_PERMGEN, K_LEE_PERM, K_PERM_SCAN, K_PERM_SWAP = 0, 1, 2, 3, 4, 5, 6
+K_KMEANS_SEED, K_KMEANS_LLOYD = 7, 8
 
 # every symbol include/spatialcore_hip.h declares: (name, argtypes); restype is always int
 _P = c_void_p
@@ -83,6 +84,8 @@ SYMBOLS = {
     "sc_profile_counts": [_P, _P, c_int64, c_int32, _P, POINTER(c_int64)],
     "sc_enrichment_counts": [_P, _P, c_int64, c_int32, c_int64, c_int64, _P],
     "sc_enrichment_counter": [_P, _P, c_int64, c_int32, ctypes.c_uint64, c_int64, c_int64, c_int64, _P, _P],
+    "sc_kmeans_fit": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P,
+                      POINTER(c_double), _P, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)],
     "sc_comm_unique_id": [_P],
     "sc_comm_create": [_P, _P, c_int, c_int, POINTER(c_void_p)],
     "sc_comm_destroy": [_P],
@@ -628,6 +631,30 @@ class Context:
         _check(self._lib.sc_profile_counts(self._h, _ptr(lab), lab.size, int(n_types), _ptr(out), byref(empty)))
         return out
 
+
+    # ---- N5: niches (k-means) ----------------------------------------------------------------
+    def kmeans(self, X, n_clusters: int, n_init: int, max_iter: int, tol: float, x_mean, uniforms) -> dict:
+        """sc_kmeans_fit on a float32 or float64 (n, C) matrix (see the header for the draws' layout)."""
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64) or X.ndim != 2:
+            raise ValueError(f"kmeans: X must be a 2-D float32 or float64 array, got {X.dtype} {X.shape}")
+        n, C = X.shape
+        K = int(n_clusters)
+        xm = np.ascontiguousarray(x_mean, dtype=X.dtype)
+        u = _c(uniforms, np.float64)
+        L = 2 + int(np.log(K)) if K >= 1 else 0
+        if xm.shape != (C,) or u.size != int(n_init) * (1 + (K - 1) * L):
+            raise ValueError("kmeans: x_mean must have C entries and uniforms n_init * (1 + (K - 1) * L)")
+        labels = np.empty(n, dtype=np.int32)
+        centers = np.empty((K, C), dtype=X.dtype)
+        seeds = np.empty((int(n_init), K), dtype=np.int64)
+        inertia, n_iter, strict, distinct = c_double(0.0), c_int32(0), c_int32(0), c_int32(0)
+        _check(self._lib.sc_kmeans_fit(self._h, _ptr(X), SC_F32 if X.dtype == np.float32 else SC_F64, n, C, K,
+                                       int(n_init), int(max_iter), float(tol), _ptr(xm), _ptr(u), _ptr(labels),
+                                       _ptr(centers), byref(inertia), _ptr(seeds), byref(n_iter), byref(strict),
+                                       byref(distinct)))
+        return {"labels": labels, "centers": centers, "inertia": inertia.value, "seeds": seeds,
+                "n_iter": n_iter.value, "strict": bool(strict.value), "distinct": distinct.value}
 
     # ---- N4 (extension) ---------------------------------------------------------------------
     def enrichment_counts(self, labels, n_types: int, n_perm: int, perm_row0: int = 0) -> np.ndarray:

@@ -4,11 +4,13 @@ Drop-in mirror of the reference's ``compute_neighborhood_profile``
 (reference src/spatialcore/spatial/neighborhoods.py:48-296, ``NB`` below): same keywords, defaults,
 outputs (``adata.obsm[key_added]`` float32, ``adata.uns[key_added + '_celltypes']``), and errors.
 Neighbour search (exact kNN or closed-ball radius) and the per-cell label counting run in HIP
-kernels; ``identify_niches`` (k-means clustering, NB:299-522) is outside the hot-path scope.
+kernels.  ``identify_niches`` (NB:299-522) clusters the profiles with sklearn's k-means (k-means++ seeding, Lloyd
+iterations, best of ``n_init`` runs) replayed step for step in HIP (``sc_kmeans_fit``).
 """
 
 from __future__ import annotations
 
+import warnings
 from typing import Optional
 
 import numpy as np
@@ -19,6 +21,10 @@ from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
 
 logger = get_logger("spatial.neighborhoods")
+
+
+class ConvergenceWarning(UserWarning):
+    """Raised as sklearn's ``ConvergenceWarning`` (same text) when k-means finds fewer distinct clusters than asked."""
 
 
 def _request_problem(adata, celltype_column, method, k, radius, spatial_key) -> Optional[str]:
@@ -244,5 +250,141 @@ def neighborhood_enrichment(
                     "permgen_form": (ctx.permgen_form(n_cells) if rng == "numpy" else "counter-based (philox)")
                                     if n_permutations > 0 else None},
         outputs={"uns": key_added, "n_celltypes": T, "n_cells": n_cells},
+    )
+    return adata
+
+
+def _niche_request_problem(adata, n_niches, method, neighborhood_key) -> Optional[str]:
+    """The first thing wrong with an identify_niches request, as the reference words it (NB:416-436), else None."""
+    if neighborhood_key not in adata.obsm:
+        return (f"adata.obsm['{neighborhood_key}'] not found. "
+                "Run compute_neighborhood_profile() first.")
+    if method not in ["kmeans", "minibatch_kmeans"]:
+        return f"Invalid method: '{method}'. Must be 'kmeans' or 'minibatch_kmeans'."
+    if n_niches < 2:
+        return f"n_niches must be >= 2, got {n_niches}"
+    if n_niches > adata.n_obs:
+        return f"n_niches ({n_niches}) cannot exceed number of cells ({adata.n_obs})"
+    return None
+
+
+def kmeans_draws(random_state, n_init: int, n_clusters: int) -> np.ndarray:
+    """Every draw of sklearn's k-means++ over ``n_init`` runs of ONE ``check_random_state(random_state)``: per run the
+    ``random_sample()`` of the first centre's ``choice`` and ``uniform(size=L)`` for each later centre,
+    L = 2 + int(log(K)).  The stream does not depend on the data, so it is drawn here up front."""
+    if random_state is None:
+        rs = np.random.mtrand._rand
+    elif isinstance(random_state, np.random.RandomState):
+        rs = random_state
+    else:
+        rs = np.random.RandomState(random_state)
+    L = 2 + int(np.log(n_clusters))
+    out = np.empty((n_init, 1 + (n_clusters - 1) * L), dtype=np.float64)
+    for r in range(n_init):
+        out[r, 0] = rs.random_sample()
+        for c in range(n_clusters - 1):
+            out[r, 1 + c * L:1 + (c + 1) * L] = rs.uniform(size=L)
+    return out
+
+
+def identify_niches(
+    adata,
+    n_niches: int,
+    method: str = "kmeans",
+    neighborhood_key: str = "neighborhood_profile",
+    key_added: str = "niche",
+    random_state: int = 0,
+    n_init: int = 10,
+    max_iter: int = 300,
+    copy: bool = False,
+    *,
+    device: int = 0,
+):
+    """Cluster neighbourhood profiles into niches (NB:299-522): sklearn's ``KMeans(init="k-means++")`` on the GPU.
+
+    Same outputs as the reference: ``adata.obs[key_added]`` (Categorical ``niche_1..niche_K``),
+    ``adata.uns["niche_centroids"]`` (K, C) in the input's dtype and ``adata.uns["niche_params"]``.
+    ``method="minibatch_kmeans"`` is answered with the same exact full-batch algorithm (sklearn's
+    minibatch stream draws depend on the data); ``niche_params["method"]`` records what was asked.
+    """
+    problem = _niche_request_problem(adata, n_niches, method, neighborhood_key)
+    if problem:
+        raise ValueError(problem)
+    n_cells = adata.n_obs
+    adata = adata.copy() if copy else adata
+    profiles = adata.obsm[neighborhood_key]
+    logger.info(
+        f"Identifying {n_niches} niches from {n_cells:,} cells "
+        f"(method={method}, random_state={random_state})"
+    )
+    empty_mask = profiles.sum(axis=1) == 0
+    n_empty = int(np.asarray(empty_mask).sum())
+    if n_empty > 0:
+        raise ValueError(f"{n_empty} cells have empty neighborhood profiles. "
+                         "Increase radius, switch to knn, or pre-filter isolated cells before profiling.")
+
+    X = profiles.toarray() if hasattr(profiles, "toarray") else np.asarray(profiles)
+    if X.dtype not in (np.float32, np.float64):      # sklearn's validate_data: float64 unless float32
+        X = X.astype(np.float64)
+    X = np.ascontiguousarray(X)
+    if method == "kmeans":
+        logger.debug(f"Running KMeans (n_init={n_init}, max_iter={max_iter})")
+    else:
+        logger.info("method='minibatch_kmeans' is answered with full-batch Lloyd k-means on the GPU "
+                    "(exact; the same result as method='kmeans')")
+    tol = np.mean(np.var(X, axis=0)) * 1e-4           # sklearn's _tolerance, on the input
+    x_mean = X.mean(axis=0)
+    draws = kmeans_draws(random_state, n_init, n_niches)
+
+    ctx = _lib.default_context(device)
+    fit = ctx.kmeans(X, n_niches, n_init, max_iter, float(tol), x_mean, draws)
+    labels, centroids, inertia = fit["labels"], fit["centers"], fit["inertia"]
+    if fit["distinct"] < n_niches:
+        warnings.warn(
+            "Number of distinct clusters ({}) found smaller than "
+            "n_clusters ({}). Possibly due to duplicate points "
+            "in X.".format(fit["distinct"], n_niches),
+            ConvergenceWarning,
+            stacklevel=2,
+        )
+
+    niche_names = [f"niche_{i + 1}" for i in range(n_niches)]
+    adata.obs[key_added] = pd.Categorical.from_codes(labels, categories=niche_names)
+    adata.uns["niche_centroids"] = centroids
+    adata.uns["niche_params"] = {
+        "n_niches": n_niches,
+        "method": method,
+        "neighborhood_key": neighborhood_key,
+        "random_state": random_state,
+        "n_init": n_init,
+        "max_iter": max_iter,
+        "inertia": float(inertia),
+    }
+    cluster_sizes = np.bincount(labels, minlength=n_niches)
+    cluster_sizes = cluster_sizes[cluster_sizes > 0]
+    logger.info(f"Niche sizes: min={cluster_sizes.min()}, "
+                f"max={cluster_sizes.max()}, mean={cluster_sizes.mean():.0f}")
+    logger.info(f"Stored niche labels in adata.obs['{key_added}'] "
+                f"and centroids in adata.uns['niche_centroids']")
+    update_metadata(
+        adata,
+        function_name="identify_niches",
+        parameters={
+            "n_niches": n_niches,
+            "method": method,
+            "neighborhood_key": neighborhood_key,
+            "random_state": random_state,
+            "n_init": n_init,
+            "max_iter": max_iter,
+            "algorithm": "lloyd",
+        },
+        outputs={
+            "obs": key_added,
+            "uns_centroids": "niche_centroids",
+            "uns_params": "niche_params",
+            "inertia": float(inertia),
+            "n_iter": fit["n_iter"],
+            "strict_convergence": fit["strict"],
+        },
     )
     return adata
