@@ -359,6 +359,35 @@ int sc_kmeans_fit(sc_ctx *ctx, const void *X, int dtype, int64_t n, int32_t C, i
                   void *centers_out, double *inertia_out, int64_t *seeds_out, int32_t *n_iter_out, int32_t *strict_out,
                   int32_t *distinct_out);
 
+/* ---- N6 (extension; no reference site: nothing in the reference computes a point-pattern statistic) ----------------
+ * Cross-type Ripley's K: pair counts by cell-type pair and radius, observed and under label permutations.
+ * Definition: for radii r_1 < ... < r_R (1 <= R <= 32) and T cell types,
+ *   count[a][b][j] = number of ORDERED pairs (i, i'), i != i', type(i) = a, type(i') = b, with
+ *                    fl(fl(dx dx) + fl(dy dy)) <= fl(r_j r_j)   (fp64, no FMA: the closed ball of sc_radius_count_2d),
+ * cumulative in j.  Hence sum_ab count[a][b][j] = nnz of the radius graph at r_j, count[.][.][j] = the counts of
+ * sc_enrichment_counts on that graph, and count[a][b][j] = count[b][a][j].  Integer arithmetic, exact, run-to-run
+ * identical.  K, L and the p-values are host arithmetic on these integers (spatialcore_amd.spatial.ripley_k).
+ *
+ * sc_ripley_build: bins the points and builds, on the device, the list of pairs within r_R, each with one byte (the
+ *   index of the smallest radius that contains it).  The list is kept beside the active graph (which it does not touch)
+ *   and stays valid until the next neighbour search of the context (sc_knn_2d, sc_radius_count_2d, sc_nearest_*,
+ *   sc_ripley_build): the counting entry points then return SC_ERR_STATE.  n_pairs_out = ordered pairs within r_R.
+ *   More than 4.2e9 stored pairs: SC_ERR_INVALID.
+ * sc_ripley_counts: counts_out[((p T + a) T + b) R + j] for the label vectors labels[perm_p], perm_p = rows
+ *   [perm_row0, perm_row0 + n_perm) of the active permutation table; p = n_perm holds the observed counts.
+ * sc_ripley_counter: the same test for ONE RANK'S RANGE [p_first, p_first + n_perm) of counter-based permutations
+ *   (sc_perm_generate_counter's definition) in one call: batch b + 1 is generated on a second stream beside the pair
+ *   counting of batch b, and only integer sums come back -- observed_out[T*T*R]; sums_out[4][T*T*R] =
+ *   sum_p (count_p - observed), sum_p (count_p - observed)^2, #{p : count_p >= observed}, #{p : count_p <= observed}:
+ *   exact and order-free, ranks add theirs (sc_allreduce_sum_i64).
+ * Envelope: T <= 96 and T (T + 1) / 2 * R <= 16384 (one histogram of the unordered type pairs in 64 KB of LDS; covers
+ * every shape with T T R <= 16384); beyond it SC_ERR_INVALID with the limit in the message. */
+int sc_ripley_build(sc_ctx *ctx, const double *xy, int64_t n, const double *radii, int32_t n_radii, int64_t *n_pairs_out);
+int sc_ripley_counts(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_types, int64_t n_perm, int64_t perm_row0,
+                     int64_t *counts_out);
+int sc_ripley_counter(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_types, uint64_t seed, int64_t p_first,
+                      int64_t n_perm, int64_t batch, int64_t *observed_out, int64_t *sums_out);
+
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across
  * one process per GPU with no data-path communication; at the end ONE ncclAllGather over RCCL (xGMI inside a node)

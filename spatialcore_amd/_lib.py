@@ -84,6 +84,9 @@ SYMBOLS = {
     "sc_profile_counts": [_P, _P, c_int64, c_int32, _P, POINTER(c_int64)],
     "sc_enrichment_counts": [_P, _P, c_int64, c_int32, c_int64, c_int64, _P],
     "sc_enrichment_counter": [_P, _P, c_int64, c_int32, ctypes.c_uint64, c_int64, c_int64, c_int64, _P, _P],
+    "sc_ripley_build": [_P, _P, c_int64, _P, c_int32, _P],
+    "sc_ripley_counts": [_P, _P, c_int64, c_int32, c_int64, c_int64, _P],
+    "sc_ripley_counter": [_P, _P, c_int64, c_int32, ctypes.c_uint64, c_int64, c_int64, c_int64, _P, _P],
     "sc_kmeans_fit": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P,
                       POINTER(c_double), _P, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)],
     "sc_comm_unique_id": [_P],
@@ -203,6 +206,7 @@ class Context:
         _check(self._lib.sc_ctx_create(int(device), byref(h)))
         self._h = h
         self.device = int(device)
+        self._ripley_radii = 0   # radii of the resident Ripley pair list (shape of ripley_counts / ripley_counter results)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -673,6 +677,35 @@ class Context:
         sums = np.empty((3, n_types, n_types), dtype=np.int64)
         _check(self._lib.sc_enrichment_counter(self._h, _ptr(lab), lab.size, int(n_types), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                int(p_first), int(n_perm), int(batch), _ptr(obs), _ptr(sums)))
+        return obs, sums
+
+    # ---- N6 (extension): Ripley's K ---------------------------------------------------------
+    def ripley_build(self, coords, radii) -> int:
+        """Builds the device-resident list of pairs within radii[-1], each tagged with the smallest radius that contains
+        it; returns the number of ORDERED pairs (nnz of the radius graph at radii[-1]).  The active graph is untouched."""
+        xy = _c(coords, np.float64)
+        r = _c(radii, np.float64)
+        n_pairs = c_int64(0)
+        _check(self._lib.sc_ripley_build(self._h, _ptr(xy), xy.shape[0], _ptr(r), r.size, byref(n_pairs)))
+        self._ripley_radii = int(r.size)
+        return n_pairs.value
+
+    def ripley_counts(self, labels, n_types: int, n_perm: int, perm_row0: int = 0) -> np.ndarray:
+        """(n_perm + 1, T, T, R) cumulative ordered pair counts under rows [perm_row0, perm_row0 + n_perm) of the
+        resident permutation table; the last slice is the observed table."""
+        lab = _c(labels, np.int32)
+        out = np.empty((n_perm + 1, n_types, n_types, self._ripley_radii), dtype=np.int64)
+        _check(self._lib.sc_ripley_counts(self._h, _ptr(lab), lab.size, int(n_types), int(n_perm), int(perm_row0), _ptr(out)))
+        return out
+
+    def ripley_counter(self, labels, n_types: int, seed: int, p_first: int, n_perm: int, batch: int = 512):
+        """Observed (T, T, R) table and the four integer sum rows (deviation, squared deviation, #{>=}, #{<=}) over the
+        counter-based label permutations p_first .. p_first + n_perm - 1, generation overlapped with counting."""
+        lab = _c(labels, np.int32)
+        obs = np.empty((n_types, n_types, self._ripley_radii), dtype=np.int64)
+        sums = np.empty((4, n_types, n_types, self._ripley_radii), dtype=np.int64)
+        _check(self._lib.sc_ripley_counter(self._h, _ptr(lab), lab.size, int(n_types), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           int(p_first), int(n_perm), int(batch), _ptr(obs), _ptr(sums)))
         return obs, sums
 
 

@@ -101,6 +101,13 @@ struct sc_ctx {
     DBuf knn_hd, knn_hi;   // k > 32: the per-query candidate heaps, [slot][query]
     double radius = -1.0;
     DBuf rad_indptr;  // [n+1] int64 of the last radius count
+    // ---- Ripley's K pair list (sc_ripley.hip): the unordered pairs within the largest radius, kept BESIDE the graph ----
+    // Positions are those of the bin-sorted order of the points (sid: position -> cell), so the list is valid exactly as
+    // long as the bins are those it was built from: sc_bin_points clears rp_valid, and every neighbour search goes through it.
+    bool rp_valid = false;
+    int64_t rp_n = 0, rp_pairs = 0;   // cells, stored pairs (each unordered pair once: row position < column position)
+    int rp_radii = 0;
+    DBuf rp_cnt, rp_indptr, rp_row, rp_col, rp_bin, rp_rank;   // per-position counts / offsets, pair ends, radius bin (1 byte), cell -> position
 
     // ---- graph (CSR, rows sorted by column) + transpose ----
     int64_t g_n = 0, g_nnz = 0;
@@ -262,6 +269,12 @@ int sc_lag_tiles(sc_ctx *c, const DBuf &indptr, const DBuf &indices, const DBuf 
 // r itself, in the same kernel, never failed.  Device code therefore keeps per-lane 64-bit shifts out of the ISA: these
 // helpers compile to v_lshlrev_b32 / v_lshrrev_b32 / v_alignbit_b32 with amounts masked to [0, 31] in the source.
 #if defined(__HIPCC__)
+// bin of a coordinate on the neighbour searches' uniform grid (sc_graph.hip, sc_ripley.hip), clamped to the grid
+__device__ __forceinline__ int bin_coord(double v, double v0, double inv_h, int nb)
+{
+    int b = (int)floor((v - v0) * inv_h);
+    return b < 0 ? 0 : (b >= nb ? nb - 1 : b);
+}
 __device__ __forceinline__ uint64_t sc_low_mask64(uint32_t d)   // the d low bits set, d in [0, 64]
 {
     const uint32_t part = (1u << (d & 31u)) - 1u;
@@ -288,6 +301,8 @@ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b;
 static inline int64_t align_up64(int64_t a, int64_t b) { return ceil_div64(a, b) * b; }
 
 // ---- implemented across translation units ----
+// bins the points for a neighbour search (sx / sy / sid / bin_start; bins of side >= min_h, about target_per_bin points each)
+int sc_bin_points(sc_ctx *c, const double *xy, int64_t n, double target_per_bin, double min_h);
 int sc_graph_ensure_transpose(sc_ctx *c);
 int sc_graph_ensure_s0(sc_ctx *c);
 int sc_graph_weight_sum_blocks(const sc_ctx *c);

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "sc_ctx.h"
+#include "sc_enrich.h"
 
 // ------------------------------------------------------------------------------------------------
 // binning
@@ -28,12 +29,6 @@ __global__ __launch_bounds__(256) void k_split_xy(const double *__restrict__ xy,
     double2 v = reinterpret_cast<const double2 *>(xy)[i];
     x[i] = v.x;
     y[i] = v.y;
-}
-
-__device__ __forceinline__ int bin_coord(double v, double v0, double inv_h, int nb)
-{
-    int b = (int)floor((v - v0) * inv_h);
-    return b < 0 ? 0 : (b >= nb ? nb - 1 : b);
 }
 
 __global__ __launch_bounds__(256) void k_bin_keys(const double *__restrict__ x, const double *__restrict__ y,
@@ -69,8 +64,9 @@ __global__ __launch_bounds__(256) void k_bin_start(const uint32_t *__restrict__ 
     for (uint32_t b = prev; b <= cur && b <= (uint32_t)nbins; ++b) bin_start[b] = (int32_t)i;
 }
 
-static int build_bins(sc_ctx *c, const double *xy, int64_t n, double target_per_bin, double min_h)
+int sc_bin_points(sc_ctx *c, const double *xy, int64_t n, double target_per_bin, double min_h)
 {
+    c->rp_valid = false;   // (the Ripley pair list holds positions of the bin order this call replaces)
     SC_REQUIRE(n >= 1 && n <= 0x7fffffffLL, SC_ERR_INVALID, "n=%lld out of range", (long long)n);
     double xmin = DBL_MAX, xmax = -DBL_MAX, ymin = DBL_MAX, ymax = -DBL_MAX;
     for (int64_t i = 0; i < n; ++i) {
@@ -349,7 +345,7 @@ extern "C" int sc_knn_2d(sc_ctx *c, const double *xy, int64_t n, int k, int incl
                "sc_knn_2d: k=%d needs more than the %lld available points", k, (long long)n);
     SC_HIP(hipSetDevice(c->device));
     c->knn_n = 0;
-    SC_TRY(build_bins(c, xy, n, 0.5 * (k + 1) > 4.0 ? 0.5 * (k + 1) : 4.0, 0.0));
+    SC_TRY(sc_bin_points(c, xy, n, 0.5 * (k + 1) > 4.0 ? 0.5 * (k + 1) : 4.0, 0.0));
     SC_TRY(c->knn_idx.ensure(sizeof(int32_t) * (size_t)n * k, &c->mem));
     SC_TRY(c->knn_rd.ensure(sizeof(double) * (size_t)n * k, &c->mem));
     {
@@ -476,7 +472,7 @@ extern "C" int sc_radius_count_2d(sc_ctx *c, const double *xy, int64_t n, double
     c->radius = -1.0;
     sc_graph_moments_drain(c);   // (a moments job on the side stream uses gt_cursor and reads the graph's arrays)
     // bins no smaller than the radius: a 3x3 window always covers the closed ball
-    SC_TRY(build_bins(c, xy, n, 4.0, radius));
+    SC_TRY(sc_bin_points(c, xy, n, 4.0, radius));
     int rings = (int)ceil(radius / c->gh * (1.0 + 1e-9));
     if (rings < 1) rings = 1;
     SC_TRY(c->rad_indptr.ensure(sizeof(long long) * (size_t)(n + 1), &c->mem));
@@ -1225,7 +1221,7 @@ static int nearest_impl(sc_ctx *c, const char *who, const double *xy_targets, co
     SC_HIP(hipSetDevice(c->device));
     c->knn_n = 0;
     c->radius = -1.0;
-    SC_TRY(build_bins(c, xy_targets, n_targets, 4.0, 0.0));
+    SC_TRY(sc_bin_points(c, xy_targets, n_targets, 4.0, 0.0));
     for (int64_t i = 0; i < n_queries; ++i)
         SC_REQUIRE(isfinite(xy_queries[2 * i]) && isfinite(xy_queries[2 * i + 1]), SC_ERR_INVALID,
                    "query coordinate %lld is not finite", (long long)i);
@@ -1459,29 +1455,6 @@ extern "C" int sc_pair_table_2d(sc_ctx *c, const double *xy_a, const int64_t *a_
 
 #define ENR_EDGES_PER_BLOCK 65536
 
-// labp[p][r] = lab[perm_p[order[r]]] (p == n_perm: the identity, i.e. the observed labels): the permuted label of
-// the cell at position r of the graph's spatially sorted processing order.  The edge kernel then needs ONE byte per
-// edge end from an n-byte array (instead of a 4-byte index gather followed by a byte gather), and the two ends of an
-// edge -- spatial neighbours -- sit at nearby positions: the row's k + 1 bytes come from one or two cache lines.
-__global__ __launch_bounds__(256) void k_enrich_relabel(const unsigned char *__restrict__ lab,
-                                                        const int32_t *__restrict__ order,
-                                                        const int32_t *__restrict__ perm, int64_t pstride, int n_perm,
-                                                        int64_t n, int64_t lstride, unsigned char *__restrict__ labp)
-{
-    const int p = blockIdx.y;
-    const int32_t *prow = p < n_perm ? perm + (int64_t)p * pstride : nullptr;
-    const int64_t r0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (r0 >= n) return;
-    unsigned char *dst = labp + (int64_t)p * lstride;
-    uint32_t v = 0;
-    for (int k = 0; k < 4 && r0 + k < n; ++k) {
-        const int32_t cell = order[r0 + k];
-        v |= (uint32_t)lab[prow ? prow[cell] : cell] << (8 * k);
-    }
-    if (r0 + 4 <= n) *reinterpret_cast<uint32_t *>(dst + r0) = v;
-    else for (int k = 0; r0 + k < n; ++k) dst[r0 + k] = (unsigned char)(v >> (8 * k));
-}
-
 // counts[p][a][b] += #{edges of the block : label(row) = a, label(column) = b}.  One thread per EDGE (coalesced reads of
 // the two relabelled end positions; consecutive workgroups are the permutations of ONE edge block, which L2 serves),
 // `copies` private T x T histograms per workgroup (lane l adds into copy l % copies, copy stride odd: with ~20 skewed
@@ -1576,23 +1549,6 @@ extern "C" int sc_enrichment_counts(sc_ctx *c, const int32_t *labels, int64_t n,
 // in the rotated order (s + l) % 16, so that a wavefront's 64 atomics of one step spread over 16 histograms (what
 // k_enrich's 16 private copies did).
 #define ENR16_MAX_TT 768   // 16 histograms of <= 768 bins: 48 KB of LDS (T <= 27)
-
-// lab16[g][rank[cell]] = the labels of `cell` under permutations 16 g .. 16 g + 15 (rows clamped to rows - 1)
-__global__ __launch_bounds__(256) void k_enrich_relabel16(const unsigned char *__restrict__ lab, const int32_t *__restrict__ rank,
-                                                          const int32_t *__restrict__ perm, int64_t pstride, int rows, int64_t n,
-                                                          uint4 *__restrict__ lab16)
-{
-    const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (cell >= n) return;
-    const int g = blockIdx.y;
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int p = 0; p < 16; ++p) {
-        const int row = 16 * g + p < rows ? 16 * g + p : rows - 1;
-        w[p >> 2] |= (uint32_t)lab[perm[(int64_t)row * pstride + cell]] << (8 * (p & 3));
-    }
-    lab16[(int64_t)g * n + rank[cell]] = make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 __global__ __launch_bounds__(256) void k_enrich16(const int32_t *__restrict__ erow_r, const int32_t *__restrict__ ecol_r,
                                                   int64_t nnz, const uint4 *__restrict__ lab16, int64_t n, int n_types,

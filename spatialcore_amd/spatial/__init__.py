@@ -13,6 +13,7 @@ from spatialcore_amd.spatial.neighborhoods import (
     compute_neighborhood_profile,
     identify_niches,
     neighborhood_enrichment,
+    ripley_k,
 )
 
 __all__ = [
@@ -24,6 +25,7 @@ __all__ = [
     "compute_neighborhood_profile",
     "identify_niches",
     "neighborhood_enrichment",  # extension: not in the reference
+    "ripley_k",  # extension: not in the reference
     "calculate_domain_distances",
     "get_distance_matrix",
 ]

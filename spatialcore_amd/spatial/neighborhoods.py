@@ -254,6 +254,181 @@ def neighborhood_enrichment(
     return adata
 
 
+def _ripley_request_problem(adata, celltype_column, radii, n_permutations, area, spatial_key, rng, comm) -> Optional[str]:
+    """The first thing wrong with a ``ripley_k`` request (checked before any device work), else None."""
+    if spatial_key not in adata.obsm:
+        return (f"adata.obsm['{spatial_key}'] not found. "
+                "Spatial coordinates are required for Ripley's K.")
+    if celltype_column not in adata.obs.columns:
+        return (f"Column '{celltype_column}' not found in adata.obs. "
+                f"Available columns: {list(adata.obs.columns)[:10]}...")
+    shape = np.shape(adata.obsm[spatial_key])
+    if len(shape) != 2 or shape[1] != 2:
+        return ("only 2-D coordinates are supported by the MI355X path "
+                f"(adata.obsm['{spatial_key}'] has shape {tuple(shape)})")
+    try:
+        r = np.asarray(radii, dtype=np.float64)
+    except (TypeError, ValueError):
+        return f"radii must be a 1-D sequence of numbers, got {radii!r}"
+    if r.ndim != 1:
+        return f"radii must be 1-D, got shape {r.shape}"
+    if r.size == 0:
+        return "radii must not be empty"
+    if r.size > 32:
+        return f"at most 32 radii are supported, got {r.size}"
+    if not np.all(np.isfinite(r)):
+        return f"radii must be finite, got {r[~np.isfinite(r)][0]}"
+    if np.any(r <= 0):
+        return f"radii must be > 0, got {r[r <= 0][0]}"
+    if np.any(np.diff(r) <= 0):
+        j = int(np.argmax(np.diff(r) <= 0))
+        return f"radii must be strictly increasing, got {r[j + 1]} after {r[j]}"
+    if not np.all(np.isfinite(r * r)):
+        return f"radii must have a finite square, got {r[-1]}"
+    if n_permutations < 0:
+        return f"n_permutations must be >= 0, got {n_permutations}"
+    if rng not in ("numpy", "philox"):
+        return f"rng must be 'numpy' or 'philox', got '{rng}'"
+    if comm is not None and rng != "philox":
+        return "permutations can only be sharded over ranks (comm=) with rng='philox': the numpy stream is sequential"
+    if area is not None and not (np.isfinite(area) and area > 0):
+        return f"area must be > 0, got {area}"
+    return None
+
+
+def ripley_statistics(count, n_per_type, area: float, sums=None, n_permutations: int = 0) -> dict:
+    """K, L and the permutation statistics from the integer tables alone (pure host arithmetic, no device).
+
+    ``count``: (T, T, R) cumulative ordered pair counts; ``n_per_type``: (T,) cells per type.
+    ``K[a, b, j] = area * count[a, b, j] / (n_a n_b)`` for a != b and ``/ (n_a (n_a - 1))`` for a = b, NaN where that
+    denominator is 0; ``L = sqrt(K / pi)``.  ``sums``: (4, T, T, R) integers over the ``n_permutations`` null tables --
+    sum of (null - count), sum of (null - count)^2, #{null >= count}, #{null <= count} -- giving ``mean``, ``std``
+    (population), ``zscore = (count - mean) / std``, ``p_value = (#{>=} + 1) / (P + 1)`` and
+    ``p_value_less = (#{<=} + 1) / (P + 1)``.
+    """
+    count = np.asarray(count, dtype=np.int64)
+    n_t = np.asarray(n_per_type, dtype=np.int64)
+    denom = (n_t[:, None] * n_t[None, :]).astype(np.float64)
+    denom[np.diag_indices(n_t.size)] = (n_t * (n_t - 1)).astype(np.float64)
+    denom = np.where(denom > 0, denom, np.nan)
+    K = float(area) * count / denom[:, :, None]
+    out = {"K": K, "L": np.sqrt(K / np.pi)}
+    if n_permutations > 0:
+        s1, s2, ge, le = (np.asarray(x, dtype=np.int64) for x in sums)
+        mean_dev = s1 / n_permutations
+        std = np.sqrt(np.maximum(s2 / n_permutations - mean_dev * mean_dev, 0.0))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            z = -mean_dev / std
+        out.update({"mean": count + mean_dev, "std": std, "zscore": z,
+                    "p_value": (ge + 1) / (n_permutations + 1), "p_value_less": (le + 1) / (n_permutations + 1)})
+    return out
+
+
+def ripley_k(
+    adata,
+    celltype_column: str,
+    radii,
+    n_permutations: int = 0,
+    seed: int = 0,
+    area: Optional[float] = None,
+    spatial_key: str = "spatial",
+    key_added: str = "ripley_k",
+    copy: bool = False,
+    *,
+    device: int = 0,
+    perm_batch: int = 512,
+    rng: str = "numpy",
+    comm=None,
+):
+    """Cross-type Ripley's K function at several radii, with a label-permutation null.
+
+    EXTENSION -- the reference has no point-pattern statistic; its documentation sends users to Ripley's K where
+    Moran's I breaks down (sparse markers: pass a boolean column, two types).  Semantics defined here
+    (include/spatialcore_hip.h, N6): for radii ``r_1 < ... < r_R`` (at most 32),
+    ``count[a, b, j]`` = number of ORDERED pairs of distinct cells (i, i') of types (a, b) with squared distance
+    ``fl(fl(dx dx) + fl(dy dy)) <= fl(r_j r_j)`` (fp64, the closed ball of the radius graph), cumulative in j.  So
+    ``count[:, :, j].sum()`` is the nnz of the radius graph at ``r_j``, ``count[:, :, j]`` equals
+    ``neighborhood_enrichment(method="radius", radius=r_j)["count"]`` and the table is symmetric in (a, b).
+    ``K[a, b, j] = area * count / (n_a n_b)`` (``n_a (n_a - 1)`` on the diagonal; NaN where that is 0),
+    ``L = sqrt(K / pi)``; ``area`` defaults to the bounding box of all cells.  NO EDGE CORRECTION is applied: it
+    cancels in the permutation null, which is the inference this function offers.
+
+    Null: the label vector permuted ``n_permutations`` times exactly as ``neighborhood_enrichment`` does it
+    (``rng="numpy"``: ``default_rng(seed).permutation(n)`` continued across batches; ``rng="philox"``: counter-based,
+    and with ``comm`` sharded over the ranks and merged by one integer all-reduce).  Stored in ``adata.uns[key_added]``:
+    ``radii``, ``celltypes``, ``n_per_type``, ``area``, ``count`` (T, T, R int64), ``K``, ``L`` and, with permutations,
+    ``mean``, ``std`` (population), ``zscore``, ``p_value = (#{null >= count} + 1) / (P + 1)``,
+    ``p_value_less = (#{null <= count} + 1) / (P + 1)``, plus ``n_permutations``, ``seed``, ``rng``.
+
+    All R radii come from ONE pass over the pairs within ``r_R`` (each tagged with the smallest radius containing it)
+    per batch of permutations; the pair list is built on the device and never visits the host.
+    """
+    problem = _ripley_request_problem(adata, celltype_column, radii, n_permutations, area, spatial_key, rng, comm)
+    if problem:
+        raise ValueError(problem)
+    if copy:
+        adata = adata.copy()
+    n_cells = adata.n_obs
+    celltypes, codes = _label_codes(adata, celltype_column)
+    coords = _coordinates(adata, spatial_key)
+    radii = np.ascontiguousarray(radii, dtype=np.float64)
+    T, R = len(celltypes), radii.size
+    if area is None:
+        ext = coords.max(axis=0) - coords.min(axis=0) if n_cells else np.zeros(2)
+        area = float(ext[0] * ext[1])
+        if not area > 0:
+            raise ValueError(f"the bounding box of the cells has area {area}; pass area= explicitly")
+    logger.info(f"Computing Ripley's K: {n_cells:,} cells, {T} cell types, {R} radii up to {radii[-1]:g}, "
+                f"permutations={n_permutations}")
+
+    ctx = _lib.default_context(device)
+    n_pairs = ctx.ripley_build(coords, radii)
+    logger.debug(f"{n_pairs:,} ordered pairs within r={radii[-1]:g}")
+
+    lo, hi = 0, n_permutations
+    if comm is not None and comm.world > 1:
+        from spatialcore_amd.parallel import shard_bounds
+
+        lo, hi = shard_bounds(n_permutations, comm.world, comm.rank)
+    # integer sums of the deviations (null - observed), of their squares, and the two exceedance counts: exact and
+    # order-free, so permutation shards merge with an integer all-reduce
+    sums = np.zeros((4, T, T, R), dtype=np.int64)
+    if rng == "philox":
+        # one device call for this rank's whole range: generation of batch b + 1 beside the pair counting of batch b
+        observed, sums = ctx.ripley_counter(codes, T, seed, lo, hi - lo, perm_batch)
+    else:
+        words = _lib.rng_state_words(np.random.default_rng(seed))
+        done = 0
+        while True:
+            batch = min(perm_batch, n_permutations - done)
+            if batch > 0:
+                ctx.generate_permutations(words, n_cells, batch)   # one stream, continued batch after batch
+            cnt = ctx.ripley_counts(codes, T, batch)
+            observed = cnt[batch]
+            dev = cnt[:batch] - observed
+            sums += np.stack([dev.sum(axis=0), (dev * dev).sum(axis=0), (dev >= 0).sum(axis=0), (dev <= 0).sum(axis=0)])
+            done += batch
+            if done >= n_permutations:
+                break
+    if comm is not None and comm.world > 1:
+        sums = comm.sum_over_ranks_i64(sums)     # the one collective of this path
+    n_per_type = np.bincount(codes, minlength=T).astype(np.int64)
+    result = {"radii": radii, "celltypes": list(celltypes), "n_per_type": n_per_type, "area": float(area), "count": observed}
+    result.update(ripley_statistics(observed, n_per_type, area, sums, n_permutations))
+    result.update({"n_permutations": n_permutations, "seed": seed, "rng": rng})
+    adata.uns[key_added] = result
+    update_metadata(
+        adata,
+        function_name="ripley_k",
+        parameters={"celltype_column": celltype_column, "radii": [float(r) for r in radii], "n_permutations": n_permutations,
+                    "seed": seed, "area": float(area), "spatial_key": spatial_key, "rng": rng,
+                    "permgen_form": (ctx.permgen_form(n_cells) if rng == "numpy" else "counter-based (philox)")
+                                    if n_permutations > 0 else None},
+        outputs={"uns": key_added, "n_celltypes": T, "n_cells": n_cells, "n_radii": R, "n_pairs": n_pairs},
+    )
+    return adata
+
+
 def _niche_request_problem(adata, n_niches, method, neighborhood_key) -> Optional[str]:
     """The first thing wrong with an identify_niches request, as the reference words it (NB:416-436), else None."""
     if neighborhood_key not in adata.obsm:
