@@ -101,7 +101,7 @@ struct sc_ctx {
     DBuf knn_hd, knn_hi;   // k > 32: the per-query candidate heaps, [slot][query]
     double radius = -1.0;
     DBuf rad_indptr;  // [n+1] int64 of the last radius count
-    // ---- Ripley's K pair list (sc_ripley.hip): the unordered pairs within the largest radius, kept BESIDE the graph ----
+    // ---- Ripley's K pair list (sc_labelperm.hip): the unordered pairs within the largest radius, kept BESIDE the graph ----
     // Positions are those of the bin-sorted order of the points (sid: position -> cell), so the list is valid exactly as
     // long as the bins are those it was built from: sc_bin_points clears rp_valid, and every neighbour search goes through it.
     bool rp_valid = false;
@@ -242,6 +242,8 @@ int sc_perm_forward_ensure(sc_ctx *c);  // materialise c->perm from c->inv after
 int invert_rows(sc_ctx *c, int64_t p0, int64_t p1, hipStream_t s);   // inverse rows [p0, p1) of the active table on stream s
 int permgen_finish(sc_ctx *c, PermJob *job, uint64_t *state6);
 int sc_perm_alloc(sc_ctx *c, int64_t n, int64_t n_perm);
+// rows [0, n_perm) of the allocated table <- counter-based permutations p_first .. (sc_permgen.hip), on stream s
+int sc_perm_counter_rows(sc_ctx *c, uint64_t seed, int64_t n, int64_t p_first, int64_t n_perm, hipStream_t s);
 int sc_permgen_profile(unsigned long long *out32, int reset);   // development builds (-DPHI_PROFILE): computed blocks by class
 // generator / consumer pipeline (sc_perm.hip): table 0 = permutation rows, 1 = inverse rows only, 2 = both
 int pipe_units_ahead();                 // the Moran scoring's unit lookahead: PIPE_AHEAD (SC_PIPE_AHEAD: development)
@@ -269,7 +271,7 @@ int sc_lag_tiles(sc_ctx *c, const DBuf &indptr, const DBuf &indices, const DBuf 
 // r itself, in the same kernel, never failed.  Device code therefore keeps per-lane 64-bit shifts out of the ISA: these
 // helpers compile to v_lshlrev_b32 / v_lshrrev_b32 / v_alignbit_b32 with amounts masked to [0, 31] in the source.
 #if defined(__HIPCC__)
-// bin of a coordinate on the neighbour searches' uniform grid (sc_graph.hip, sc_ripley.hip), clamped to the grid
+// bin of a coordinate on the neighbour searches' uniform grid (sc_graph.hip, sc_labelperm.hip), clamped to the grid
 __device__ __forceinline__ int bin_coord(double v, double v0, double inv_h, int nb)
 {
     int b = (int)floor((v - v0) * inv_h);

@@ -77,6 +77,60 @@ def _activate_neighbour_graph(ctx, coords: np.ndarray, method: str, k: int, radi
         ctx.set_graph_csr(indptr, indices, np.ones(indices.size), coords.shape[0])
 
 
+def _label_permutation_null(ctx, counts, counter, codes, n_types: int, n_sums: int, n_permutations: int, seed: int,
+                            perm_batch: int, rng: str, comm):
+    """The observed table and the integer sums of the label-permutation null of ``neighborhood_enrichment`` and
+    ``ripley_k``: sum of (null - observed), sum of (null - observed)^2, #{null >= observed} and, with ``n_sums = 4``,
+    #{null <= observed}.  They are exact and order-free, so the permutation shards of the ranks of ``comm`` merge with
+    one integer all-reduce.  ``counts(codes, T, batch)``: the tables of the resident permutation rows, then the observed
+    one (``rng="numpy"``); ``counter(codes, T, seed, lo, n, batch)``: the observed table and the sums over the
+    counter-based permutations lo .. lo + n - 1 (``rng="philox"``)."""
+    lo, hi = 0, n_permutations
+    if comm is not None and comm.world > 1:
+        from spatialcore_amd.parallel import shard_bounds
+
+        lo, hi = shard_bounds(n_permutations, comm.world, comm.rank)
+    if rng == "philox":
+        # one device call for this rank's whole range: generation of batch b + 1 beside the counting of batch b,
+        # integer sums accumulated on the device
+        observed, sums = counter(codes, n_types, seed, lo, hi - lo, perm_batch)
+    else:
+        words = _lib.rng_state_words(np.random.default_rng(seed))
+        sums, done = 0, lo
+        while True:
+            batch = min(perm_batch, hi - done)
+            if batch > 0:
+                ctx.generate_permutations(words, codes.size, batch)   # one stream, continued batch after batch
+            cnt = counts(codes, n_types, batch)
+            observed = cnt[batch]
+            dev = cnt[:batch] - observed
+            rows = [dev.sum(axis=0), (dev * dev).sum(axis=0), (dev >= 0).sum(axis=0)]
+            if n_sums > 3:
+                rows.append((dev <= 0).sum(axis=0))
+            sums = sums + np.stack(rows)
+            done += batch
+            if done >= hi:
+                break
+    if comm is not None and comm.world > 1:
+        sums = comm.sum_over_ranks_i64(sums)     # the one collective of this path
+    return observed, sums
+
+
+def _null_statistics(count, sums, n_permutations: int) -> dict:
+    """``mean``, ``std`` (population), ``zscore = (count - mean) / std`` and ``p_value = (#{>=} + 1) / (P + 1)`` from the
+    integer sums of ``_label_permutation_null`` over P = ``n_permutations`` > 0 null tables, and
+    ``p_value_less = (#{<=} + 1) / (P + 1)`` when the sums have that fourth row."""
+    s1, s2, ge, *le = (np.asarray(x, dtype=np.int64) for x in sums)
+    mean_dev = s1 / n_permutations
+    std = np.sqrt(np.maximum(s2 / n_permutations - mean_dev * mean_dev, 0.0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = -mean_dev / std
+    out = {"mean": count + mean_dev, "std": std, "zscore": z, "p_value": (ge + 1) / (n_permutations + 1)}
+    if le:
+        out["p_value_less"] = (le[0] + 1) / (n_permutations + 1)
+    return out
+
+
 def compute_neighborhood_profile(
     adata,
     celltype_column: str,
@@ -198,48 +252,11 @@ def neighborhood_enrichment(
     ctx = _lib.default_context(device)
     _activate_neighbour_graph(ctx, coords, method, k, radius)
 
-    words = _lib.rng_state_words(np.random.default_rng(seed)) if rng == "numpy" else None
-    lo, hi = 0, n_permutations
-    if comm is not None and comm.world > 1:
-        from spatialcore_amd.parallel import shard_bounds
-
-        lo, hi = shard_bounds(n_permutations, comm.world, comm.rank)
-    observed = None
-    # integer sums of the deviations (null - observed) and of their squares, and the exceedance counts: exact and
-    # order-free, so permutation shards merge with an integer all-reduce
-    s1 = np.zeros((T, T), dtype=np.int64)
-    s2 = np.zeros((T, T), dtype=np.int64)
-    ge = np.zeros((T, T), dtype=np.int64)
-    done = lo
-    while rng == "philox":
-        # one device call for this rank's whole range: generation of batch b + 1 beside the edge counting of batch b,
-        # integer sums accumulated on the device
-        observed, (s1, s2, ge) = ctx.enrichment_counter(codes, T, seed, lo, hi - lo, perm_batch)
-        break
-    while rng == "numpy":
-        batch = min(perm_batch, hi - done)
-        if batch > 0:
-            ctx.generate_permutations(words, n_cells, batch)   # one stream, continued batch after batch
-        cnt = ctx.enrichment_counts(codes, T, batch)
-        observed = cnt[batch]
-        dev = cnt[:batch] - observed
-        s1 += dev.sum(axis=0)
-        s2 += (dev * dev).sum(axis=0)
-        ge += (dev >= 0).sum(axis=0)
-        done += batch
-        if done >= hi:
-            break
-    if comm is not None and comm.world > 1:
-        s1, s2, ge = comm.sum_over_ranks_i64(np.stack([s1, s2, ge]))     # the one collective of this path
+    observed, sums = _label_permutation_null(ctx, ctx.enrichment_counts, ctx.enrichment_counter, codes, T, 3, n_permutations,
+                                             seed, perm_batch, rng, comm)
     result = {"count": observed, "celltypes": list(celltypes), "n_permutations": n_permutations, "seed": seed, "rng": rng}
     if n_permutations > 0:
-        mean_dev = s1 / n_permutations
-        var = np.maximum(s2 / n_permutations - mean_dev * mean_dev, 0.0)
-        std = np.sqrt(var)
-        mean = observed + mean_dev
-        with np.errstate(divide="ignore", invalid="ignore"):
-            z = -mean_dev / std
-        result.update({"mean": mean, "std": std, "zscore": z, "p_value": (ge + 1) / (n_permutations + 1)})
+        result.update(_null_statistics(observed, sums, n_permutations))
     adata.uns[key_added] = result
     update_metadata(
         adata,
@@ -314,13 +331,7 @@ def ripley_statistics(count, n_per_type, area: float, sums=None, n_permutations:
     K = float(area) * count / denom[:, :, None]
     out = {"K": K, "L": np.sqrt(K / np.pi)}
     if n_permutations > 0:
-        s1, s2, ge, le = (np.asarray(x, dtype=np.int64) for x in sums)
-        mean_dev = s1 / n_permutations
-        std = np.sqrt(np.maximum(s2 / n_permutations - mean_dev * mean_dev, 0.0))
-        with np.errstate(divide="ignore", invalid="ignore"):
-            z = -mean_dev / std
-        out.update({"mean": count + mean_dev, "std": std, "zscore": z,
-                    "p_value": (ge + 1) / (n_permutations + 1), "p_value_less": (le + 1) / (n_permutations + 1)})
+        out.update(_null_statistics(count, sums, n_permutations))
     return out
 
 
@@ -385,33 +396,8 @@ def ripley_k(
     n_pairs = ctx.ripley_build(coords, radii)
     logger.debug(f"{n_pairs:,} ordered pairs within r={radii[-1]:g}")
 
-    lo, hi = 0, n_permutations
-    if comm is not None and comm.world > 1:
-        from spatialcore_amd.parallel import shard_bounds
-
-        lo, hi = shard_bounds(n_permutations, comm.world, comm.rank)
-    # integer sums of the deviations (null - observed), of their squares, and the two exceedance counts: exact and
-    # order-free, so permutation shards merge with an integer all-reduce
-    sums = np.zeros((4, T, T, R), dtype=np.int64)
-    if rng == "philox":
-        # one device call for this rank's whole range: generation of batch b + 1 beside the pair counting of batch b
-        observed, sums = ctx.ripley_counter(codes, T, seed, lo, hi - lo, perm_batch)
-    else:
-        words = _lib.rng_state_words(np.random.default_rng(seed))
-        done = 0
-        while True:
-            batch = min(perm_batch, n_permutations - done)
-            if batch > 0:
-                ctx.generate_permutations(words, n_cells, batch)   # one stream, continued batch after batch
-            cnt = ctx.ripley_counts(codes, T, batch)
-            observed = cnt[batch]
-            dev = cnt[:batch] - observed
-            sums += np.stack([dev.sum(axis=0), (dev * dev).sum(axis=0), (dev >= 0).sum(axis=0), (dev <= 0).sum(axis=0)])
-            done += batch
-            if done >= n_permutations:
-                break
-    if comm is not None and comm.world > 1:
-        sums = comm.sum_over_ranks_i64(sums)     # the one collective of this path
+    observed, sums = _label_permutation_null(ctx, ctx.ripley_counts, ctx.ripley_counter, codes, T, 4, n_permutations, seed,
+                                             perm_batch, rng, comm)
     n_per_type = np.bincount(codes, minlength=T).astype(np.int64)
     result = {"radii": radii, "celltypes": list(celltypes), "n_per_type": n_per_type, "area": float(area), "count": observed}
     result.update(ripley_statistics(observed, n_per_type, area, sums, n_permutations))

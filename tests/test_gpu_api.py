@@ -420,6 +420,49 @@ def test_neighborhood_enrichment_extension(oracle):
         neighborhood_enrichment(ad, "cell_type", rng="mt19937")
 
 
+def _knn_graph_and_codes(seed, n, T, k, extent):
+    from spatialcore_amd import _lib
+
+    rng = np.random.default_rng(seed)
+    coords = rng.uniform(0, extent, (n, 2))
+    codes = rng.integers(0, T, n).astype(np.int32)
+    ctx = _lib.default_context(0)
+    ctx.knn(coords, k, fetch=False)
+    ctx.graph_from_knn(1.0)
+    return ctx, coords, codes
+
+
+def test_enrichment_counter_narrow_form_at_30_types(oracle):
+    """T = 30: T x T = 900 bins do not fit the sixteen-permutations-per-edge form (at most 768), so sc_enrichment_counter
+    counts with k_enrich, one permutation per edge pass.  21 counter-based permutations in batches of 8 (the last batch
+    ragged): the observed table and every sum row equal the oracle's restatement of the definition, exactly."""
+    n, T, k, P, seed = 4000, 30, 8, 21, 91
+    ctx, coords, codes = _knn_graph_and_codes(30, n, T, k, 700.0)
+    obs, sums = ctx.enrichment_counter(codes, T, seed, 0, P, batch=8)
+    perms = np.stack([oracle.counter_permutation(seed, n, p) for p in range(P)])
+    want = oracle.enrichment_counts(np.arange(0, n * k + 1, k), oracle.knn_bruteforce(coords, k).reshape(-1), codes, T, perms)
+    dev = want[:-1] - want[-1]
+    np.testing.assert_array_equal(obs, want[-1])
+    np.testing.assert_array_equal(sums, np.stack([dev.sum(axis=0), (dev * dev).sum(axis=0), (dev >= 0).sum(axis=0)]))
+
+
+def test_enrichment_counter_without_permutations_keeps_the_resident_table(oracle):
+    """sc_enrichment_counter with n_perm = 0 writes no permutation rows, so it leaves the table of generate_permutations
+    valid: enrichment_counts still counts those rows afterwards."""
+    from spatialcore_amd import _lib
+
+    n, T, k, P = 2000, 5, 6, 6
+    ctx, coords, codes = _knn_graph_and_codes(12, n, T, k, 450.0)
+    ctx.generate_permutations(_lib.rng_state_words(np.random.default_rng(3)), n, P)
+    obs, sums = ctx.enrichment_counter(codes, T, 1, 0, 0)
+    cnt = ctx.enrichment_counts(codes, T, P)
+    perms, _ = oracle.perm_table(3, n, P)
+    want = oracle.enrichment_counts(np.arange(0, n * k + 1, k), oracle.knn_bruteforce(coords, k).reshape(-1), codes, T, perms)
+    np.testing.assert_array_equal(cnt, want)
+    np.testing.assert_array_equal(obs, want[-1])
+    assert not sums.any()
+
+
 def test_counter_permutations_on_the_device_and_lee_shared_philox(oracle):
     """The device's counter-based table equals the host definition (both long-permutation swap forms), and
     lees_l(shared_permutations=True, rng="philox") scores exactly those rows."""
