@@ -1,5 +1,5 @@
-"""Development: run bench.py against another build of the library (same box, same process order A/B).
-usage: python scripts/bench_variant.py spatialcore_amd/libvar_X.so [bench.py flags]"""
+"""Development: run bench.py against another build of the library, e.g. one built from another commit (A/B on the
+same box in the same call).  usage: python scripts/bench_variant.py path/to/libspatialcore_hip.so [bench.py flags]"""
 import sys, runpy
 sys.path.insert(0, ".")
 from spatialcore_amd import _lib

@@ -9,7 +9,7 @@ permutation of 10^6 cells ends: where the exact prefix stands after each round, 
 r04 findings: the plain iteration needs ~15 rounds for such a block (the kernel's counter: 16.1), half of
 them for the last ~20 threads (thresholds of a few hundred: the front moves 2-3 threads a round); predicting the entering
 counts with the linearised sensitivity (an affine scan) saves 2 rounds; solving the last 512 / 1024 / 2048 steps exactly
-saves 5 / 7 / 8.5 -- built (-DPHI_TAIL=true), and slower on the device: the solver is one wavefront."""
+saves 5 / 7 / 8.5 -- built once as a device variant, slower there (the solver is one wavefront), and removed since."""
 import os
 import sys
 import numpy as np

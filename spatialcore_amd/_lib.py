@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (SPATIALCORE_HIP_LIB: another build of the same library -- the sanitizer build of `make asan`, a variant of scripts/build_variant.sh)
+# (SPATIALCORE_HIP_LIB: another build of the same library -- the sanitizer build of `make asan`, a build of another commit)
 LIB_PATH = os.environ.get("SPATIALCORE_HIP_LIB") or os.path.join(_HERE, "libspatialcore_hip.so")
 
 SC_OK, SC_ERR_INVALID, SC_ERR_STATE, SC_ERR_HIP, SC_ERR_NOMEM, SC_ERR_EMPTY = 0, 1, 2, 3, 4, 5
@@ -44,7 +44,7 @@ SYMBOLS = {
     "sc_ctx_moran_row_groups": [_P, _P],
     "sc_ctx_permgen_stats": [_P, _P, _P, _P, _P, _P],
     "sc_ctx_device_mem": [_P, POINTER(c_int64)],
-    "sc_debug_copy": [_P, c_int, c_int64, _P, c_int64],
+    "sc_debug_copy": [_P, c_int, c_int64, _P, c_int64],   # buffers: 0 J, 1 raw stream, 2 accept masks, 3 entering counts, 4 block states, 5 scan state, 6 table, 7 inverse table
     "sc_knn_2d": [_P, _P, c_int64, c_int, c_int, _P, _P],
     "sc_knn_fetch": [_P, _P, _P],
     "sc_radius_count_2d": [_P, _P, c_int64, c_double, _P],

@@ -95,7 +95,6 @@ int sc_timer_collect(sc_ctx *c)
     for (hipStream_t sp : c->stream_pg)
         if (sp) SC_HIP(hipStreamSynchronize(sp));
     if (c->stream_px) SC_HIP(hipStreamSynchronize(c->stream_px));
-    if (c->stream_fr) SC_HIP(hipStreamSynchronize(c->stream_fr));
     if (c->stream_out) SC_HIP(hipStreamSynchronize(c->stream_out));
     for (int k = 0; k < SC_K_COUNT_; ++k) {
         KTimer &t = c->timers[k];
@@ -147,7 +146,6 @@ int sc_ctx_create(int device, sc_ctx **out)
     }
     sc_ctx *c = new sc_ctx();
     c->device = device;
-    if (getenv("SC_LOCAL_MORAN_DIRECT")) c->lm_direct = true;  // development: A/B of the per-cell count kernels
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete c;
@@ -180,7 +178,7 @@ int sc_ctx_destroy(sc_ctx *c)
                     &c->partial, &c->sims, &c->counts, &c->sim_sum, &c->sim_sumsq, &c->lee_a,
                     &c->lee_b, &c->lee_out, &c->lee_pairs, &c->lee_U, &c->lee_Zc, &c->lee_Uc, &c->lee_part, &c->lee_obs, &c->lee_cnt,
                     &c->lee_rowmap, &c->lee_lperm, &c->g_slag, &c->g_xsum, &c->g_flags, &c->g_xmax, &c->g_lat, &c->g_meanc, &c->g_seff, &c->g_corr, &c->g_thr, &c->sims_raw, &c->g_order, &c->g_rank, &c->g_indices_r, &c->g_w32, &c->g_erow_r, &c->lm_ys, &c->lm_out, &c->lm_tab, &c->s0_tmp, &c->pg_J, &c->pg_raw, &c->pg_out, &c->pg_flags, &c->pg_bits, &c->pg_enter, &c->pg_sblk,
-                    &c->pg_desc, &c->pg_tbits, &c->pg_events, &c->pg_hard, &c->pg_seg, &c->pg_ctbits, &c->pg_segmode, &c->pg_seglist, &c->pg_fresh, &c->nib_map,
+                    &c->pg_desc, &c->pg_tbits, &c->pg_events, &c->pg_hard, &c->pg_seg, &c->pg_ctbits, &c->pg_segmode, &c->pg_seglist, &c->nib_map,
                     &c->np_cnt, &c->np_comp, &c->np_leaves, &c->np_leafsum,
                     &c->rp_cnt, &c->rp_indptr, &c->rp_row, &c->rp_col, &c->rp_bin, &c->rp_rank};
     for (DBuf *b : bufs) b->release(&c->mem);
@@ -200,7 +198,6 @@ int sc_ctx_destroy(sc_ctx *c)
     for (hipStream_t sp : c->stream_pg)
         if (sp) (void)hipStreamDestroy(sp);
     if (c->stream_px) (void)hipStreamDestroy(c->stream_px);
-    if (c->stream_fr) (void)hipStreamDestroy(c->stream_fr);
     if (c->stream_out) (void)hipStreamDestroy(c->stream_out);
     for (hipEvent_t e : c->pg_ev)
         if (e) (void)hipEventDestroy(e);
@@ -222,11 +219,7 @@ int sc_debug_copy(sc_ctx *c, int which, int64_t offset, void *out, int64_t bytes
 {
     SC_REQUIRE(c && out && offset >= 0 && bytes >= 0, SC_ERR_INVALID, "sc_debug_copy: bad argument");
     SC_HIP(hipSetDevice(c->device));
-    if (which == 100) {   // development builds of the generator (-DPHI_PROFILE): 32 words, reset when offset != 0
-        SC_REQUIRE(bytes == 32 * (int64_t)sizeof(unsigned long long), SC_ERR_INVALID, "sc_debug_copy: the generator profile is 32 words");
-        return sc_permgen_profile(reinterpret_cast<unsigned long long *>(out), offset != 0);
-    }
-    const DBuf *bufs[] = {&c->pg_J, &c->pg_raw, &c->pg_bits, &c->pg_enter, &c->pg_sblk, &c->pg_out, &c->perm, &c->inv, &c->pg_fresh};
+    const DBuf *bufs[] = {&c->pg_J, &c->pg_raw, &c->pg_bits, &c->pg_enter, &c->pg_sblk, &c->pg_out, &c->perm, &c->inv};
     SC_REQUIRE(which >= 0 && which < (int)(sizeof(bufs) / sizeof(bufs[0])), SC_ERR_INVALID, "sc_debug_copy: unknown buffer %d", which);
     const DBuf *b = bufs[which];
     SC_REQUIRE((size_t)(offset + bytes) <= b->cap, SC_ERR_INVALID, "sc_debug_copy: range exceeds the buffer (%zu bytes)", b->cap);

@@ -13,9 +13,7 @@
 #include "../../include/spatialcore_hip.h"
 
 #define SC_TILE 16  // genes per tile: one 128-byte fp64 row per cell and tile
-#ifndef PERM_CHUNK
 #define PERM_CHUNK 128  // permutations per pipeline stage (generator scan -> swaps -> scoring)
-#endif
 
 void sc_set_error(const char *fmt, ...);
 
@@ -70,7 +68,6 @@ struct sc_ctx {
     hipStream_t stream4 = nullptr;  // ... alternating with this one
     hipStream_t stream_pg[4] = {};    // block-parallel scan: the chip prepares blocks here ahead of the chain
     hipStream_t stream_px = nullptr;     // ... and verifies + expands a finished chunk here, beside the next chunk's chain
-    hipStream_t stream_fr = nullptr;     // ... and the fresh-table helpers of a chain launch live here (k_fresh)
     hipStream_t stream_out = nullptr;    // r04: result copies that run beside a pipeline, issued by a helper thread (sc_local_moran_seeded)
     hipEvent_t pg_ev[34] = {};        // rings of events between the preparation and the chain launches + start marker
     int pg_mode = 0;                  // 0 auto, 1 sequential scan only, 2 fault injection (tests)
@@ -170,7 +167,6 @@ struct sc_ctx {
     DBuf pg_J, pg_raw, pg_out, pg_bits, pg_enter, pg_sblk;  // device generator scratch: accepted j per step, raw 32-bit stream
     DBuf pg_flags;       // hand-over words between the chain workgroup and the preparation launches (sc_permgen.hip)
     DBuf pg_desc, pg_tbits, pg_events, pg_hard;  // block-parallel scan: per-block descriptors + gap-transfer tables (ring), hard flags
-    DBuf pg_fresh;                               // ... fresh tables for the ends of the permutations: control block, descriptors, tables
     DBuf pg_seglist;                             // ... per unit in flight: [count | first blocks of the segments k_phi_compose builds]
     DBuf pg_seg, pg_ctbits, pg_segmode;          // ... segments of prepared blocks: descriptors + composed tables (ring), per-block mode
 
@@ -178,7 +174,6 @@ struct sc_ctx {
     DBuf partial, sims, counts, sim_sum, sim_sumsq;
     DBuf lee_a, lee_b, lee_out, lee_pairs;
     DBuf lee_U, lee_Zc, lee_Uc, lee_part, lee_obs, lee_cnt, lee_rowmap, lee_lperm;  // batched Lee (sc_lee.hip)
-    bool lm_direct = false;  // local Moran per-cell counts: the r01 one-kernel form instead of the two-phase sorted form (A/B)
     bool lm_valid = false;   // z / lag / counts of the last sc_local_moran are still resident
     int64_t lm_perms = 0;
     DBuf lm_out;             // local Moran: row-major staging of one output array for the helper thread's device-to-host copies
@@ -244,10 +239,10 @@ int permgen_finish(sc_ctx *c, PermJob *job, uint64_t *state6);
 int sc_perm_alloc(sc_ctx *c, int64_t n, int64_t n_perm);
 // rows [0, n_perm) of the allocated table <- counter-based permutations p_first .. (sc_permgen.hip), on stream s
 int sc_perm_counter_rows(sc_ctx *c, uint64_t seed, int64_t n, int64_t p_first, int64_t n_perm, hipStream_t s);
-int sc_permgen_profile(unsigned long long *out32, int reset);   // development builds (-DPHI_PROFILE): computed blocks by class
 // generator / consumer pipeline (sc_perm.hip): table 0 = permutation rows, 1 = inverse rows only, 2 = both
-int pipe_units_ahead();                 // the Moran scoring's unit lookahead: PIPE_AHEAD (SC_PIPE_AHEAD: development)
-int64_t pipe_tail_total();              // permutations of the tapering last chunks
+constexpr int PIPE_AHEAD = 3;                      // launch units the generator's preparation runs ahead of its chain inside the pipeline
+constexpr int64_t PIPE_TAIL[] = {96, 48, 24};      // permutations of the tapering last chunks (sc_perm.hip: pipe_begin)
+constexpr int64_t PIPE_TAIL_TOTAL = 96 + 48 + 24;
 int pipe_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int table, int units_ahead, PermPipe &pp,
                int64_t chunks_ahead, const std::function<int()> &after_first_chunk = nullptr);
 int pipe_consume(sc_ctx *c, PermPipe &pp, uint64_t *state6, const std::function<int()> &after_first,

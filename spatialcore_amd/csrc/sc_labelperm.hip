@@ -311,7 +311,7 @@ extern "C" int sc_enrichment_counter(sc_ctx *c, const int32_t *labels, int64_t n
     const int cstride = tt | 1;   // odd: copy c starts at a different LDS bank
     while (copies > 1 && (size_t)copies * cstride > 12288) copies >>= 1;   // <= 48 KB of LDS per workgroup
     const unsigned eblocks = (unsigned)ceil_div64(c->g_nnz, ENR_EDGES_PER_BLOCK);
-    const bool wide = tt <= ENR16_MAX_TT && !getenv("SC_ENRICH_NARROW");   // sixteen permutations per edge (k_enrich16)
+    const bool wide = tt <= ENR16_MAX_TT;   // sixteen permutations per edge (k_enrich16)
     const int hstride = tt | 1;
     auto relabel = [&](int rows, const int32_t *table) {
         if (wide && table)

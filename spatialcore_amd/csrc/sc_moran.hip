@@ -1004,9 +1004,7 @@ __global__ __launch_bounds__(SCORE_PRIVATE_WAVES * 64) void k_moran_score(
 // SCORE_WG_MIN_PERMS permutations in their last task to k_moran_score instead.
 // ------------------------------------------------------------------------------------------------
 #define SCORE_SB 16   // cells per lag super-block
-#ifndef SCORE_WG_MIN_PERMS
 #define SCORE_WG_MIN_PERMS 24   // permutations in a chunk's last (partial) task from which the workgroup form is used
-#endif
 
 template <int BITS, int CB, bool BIG, bool L16 = false>
 __global__ __launch_bounds__(SCORE_WAVES * 64) void k_moran_score_wg(
@@ -1617,7 +1615,7 @@ static int moran_prepare(sc_ctx *c, int64_t n_perm, bool allow_lattice)
     }
     // an all-lattice uint8 batch (count data on a kNN graph): narrow copy first, then neighbour sums + both column sums
     // from the uint8 rows in one pass (k_lag_u8); no Z tiles at all (the lattice operand IS the raw value)
-    const bool u8_prelude = n_perm > 0 && bits == 8 && lat_all && c->g_deg_max <= 257 && !getenv("SC_NO_U8_PRELUDE");
+    const bool u8_prelude = n_perm > 0 && bits == 8 && lat_all && c->g_deg_max <= 257;
     // ... or as NIBBLE slots (r04, "the 4-bit source" above) when that takes fewer gathered rows per (permutation, cell)
     int64_t nw = 0;
     uint32_t xmax_all = 0;
@@ -1630,8 +1628,8 @@ static int moran_prepare(sc_ctx *c, int64_t n_perm, bool allow_lattice)
                      15.0 * (double)xmax_all * (double)c->g_deg_max * (double)score_cells_per_split(n) < 2.0e9;
     c->nib_groups = nib ? (int)nib_groups : 0;
     // ... with the neighbour sums kept as the 16-bit integers they are (r04): a quarter of the bytes k_lag_u8 writes in the
-    // serial prelude and of the lag bytes every scoring launch streams (SC_LAG_FP64: the r03 form, for A/B runs)
-    const bool lag16 = u8_prelude && !nib && !getenv("SC_LAG_FP64");
+    // serial prelude and of the lag bytes every scoring launch streams
+    const bool lag16 = u8_prelude && !nib;
     bool narrow_packed = false;   // the narrow copy of the batch exists already (built in front of the lag that reads it)
     c->lag_u16 = lag16;
     if (nib) {
@@ -1691,7 +1689,7 @@ static int moran_prepare(sc_ctx *c, int64_t n_perm, bool allow_lattice)
         SC_HIP(hipGetLastError());
     } else {
         SC_TRY(expr_write_z(c, c->g_meanc.as<double>()));
-        const bool lag_from_rows = n_perm > 0 && bits == 32 && !getenv("SC_LAG_FP64_ROWS");   // (SC_LAG_FP64_ROWS: the r03 form, A/B)
+        const bool lag_from_rows = n_perm > 0 && bits == 32;
         if (lag_from_rows) {   // the float32 narrow copy first, then the lag from ITS rows (half the gathered bytes of the fp64 tiles)
             SC_TRY(c->X32.ensure(sizeof(float) * (size_t)((T + 1) / 2) * n * 32, &c->mem));
             hipLaunchKernelGGL(k_pack_narrow<32>, dim3((unsigned)ceil_div64(n * 8, 256), (unsigned)ceil_div64(T, 2)), dim3(256), 0,
@@ -1798,13 +1796,11 @@ static int moran_table_is_bijective(sc_ctx *c, int64_t n_perm, bool *bijective)
 template <int BITS, int CB, bool BIG, bool L16 = false>
 static void launch_score(sc_ctx *c, int wgs, const uint4 *rows, int64_t p0, int cnt, int64_t cps, int splits, int groups)
 {
-    static const bool private_lag = getenv("SC_SCORE_PRIVATE_LAG") != nullptr;   // development: the r02 form, for A/B runs
     // the workgroup form scores 128 permutations per task; wavefronts beyond a short chunk's permutations only help with
     // the lag rows.  Below SCORE_WG_MIN_PERMS live permutations a compute unit has too few gathers in flight: such chunks
-    // take the per-wavefront form -- same results (SC_SCORE_WG_MIN: development, to sweep the threshold)
-    static const int wg_min = getenv("SC_SCORE_WG_MIN") ? atoi(getenv("SC_SCORE_WG_MIN")) : SCORE_WG_MIN_PERMS;
+    // take the per-wavefront form -- same results
     const int last_task = cnt % (8 * SCORE_WAVES);
-    if (BITS == 4 || (!private_lag && (last_task == 0 || last_task >= (BITS == 64 ? 6 * SCORE_WAVES : wg_min)))) {
+    if (BITS == 4 || last_task == 0 || last_task >= (BITS == 64 ? 6 * SCORE_WAVES : SCORE_WG_MIN_PERMS)) {
         const int64_t tasks = (int64_t)groups * splits * ((cnt + 8 * SCORE_WAVES - 1) / (8 * SCORE_WAVES));
         if (wgs > tasks) wgs = (int)tasks;
         // (r03 measured the grid rounded to whole rounds of tasks -- 1956 tasks are 13 rounds on 160 workgroups, 12 on 163,
@@ -1964,11 +1960,9 @@ extern "C" int sc_moran(sc_ctx *c, int64_t n_perm, double *I_out, double *sims_o
 }
 
 // (what the number means and how it was chosen: the comment in front of moran_seeded_streams)
-#ifndef SCORE_RESERVED_CUS
 #define SCORE_RESERVED_CUS 112   // r04 (two runs of 20 steps each, same box, ms per step): 96 -> 163.1 / 162.2, 112 -> 157.7 / 158.5,
                                  // 128 -> 162.2 / 162.6, 144 -> 171.0 / 169.5; the scoring launches take the same 117 ms on 144 CUs
                                  // as on 160 (13 rounds of tasks either way), the generator's preparation gets its CUs sooner
-#endif
 static int moran_seeded_once(sc_ctx *c, uint64_t *state6, int64_t n_perm, double *I_out, double *sims_out,
                              int64_t *count_ge_out, double *sim_sum_out, double *sim_sumsq_out, PermPipe *begun)
 {
@@ -1987,29 +1981,27 @@ static int moran_seeded_once(sc_ctx *c, uint64_t *state6, int64_t n_perm, double
         // CUs left to the generator, by source width (r04, bench size, ms per step at 64 / 80 / 96 / 112 CUs left): the uint8
         // step is balanced between generator and scoring (SCORE_RESERVED_CUS); uint16 243.0 / 246.8 / 238.5 / 239.2; float32,
         // whose step is scoring-bound, 389.3 / 390.4 / 398.1 / 408.6
-        if (c->score_leave_cus > 8 && !getenv("SC_SCORE_LEAVE_CUS")) c->score_leave_cus = bits == 8 ? SCORE_RESERVED_CUS : bits == 16 ? 96 : 64;
+        if (c->score_leave_cus > 8) c->score_leave_cus = bits == 8 ? SCORE_RESERVED_CUS : bits == 16 ? 96 : 64;
         return SC_OK;
     };
     auto score = [&](int64_t p0, int64_t p1) -> int {
         // The last chunk is scored after the generator has finished (its own swaps are the generator's last launches):
         // it takes the CUs the earlier launches left to the generator; the one before it runs beside the generator's
-        // short last chunk only.  SC_SCORE_LEAVE_TAIL="a,b" (development): CUs left by the second-to-last / last
-        // chunk's launch; measured at bench size (ms per step): 64,64 -> 211.5, 64,8 -> 209.9, 32,8 -> 207.1, 8,8 -> 207.9.
+        // short last chunk only.  CUs left by the second-to-last / last chunk's launch, measured at bench size (ms per
+        // step): 64,64 -> 211.5, 64,8 -> 209.9, 32,8 -> 207.1, 8,8 -> 207.9.
         const int keep = c->score_leave_cus;
         if (keep > 8) {
-            int tail_prev = keep < 32 ? keep : 32, tail_last = 8;
-            if (const char *v = getenv("SC_SCORE_LEAVE_TAIL")) sscanf(v, "%d,%d", &tail_prev, &tail_last);
-            int64_t tail_from = pipe_tail_total();   // launches with fewer permutations than this still to come use tail_prev
-            if (const char *v = getenv("SC_SCORE_TAIL_PERMS")) tail_from = atoi(v);   // development: sweep
+            const int tail_prev = keep < 32 ? keep : 32, tail_last = 8;
             if (p1 == n_perm) c->score_leave_cus = tail_last;
-            else if (n_perm > 3 * PERM_CHUNK && n_perm - p1 < tail_from) c->score_leave_cus = tail_prev;
+            // launches with fewer permutations than the tapering chunks' still to come use tail_prev
+            else if (n_perm > 3 * PERM_CHUNK && n_perm - p1 < PIPE_TAIL_TOTAL) c->score_leave_cus = tail_prev;
         }
         const int rc = moran_perm_range(c, p0, p1, bits, false);
         c->score_leave_cus = keep;
         return rc;
     };
     if (begun) SC_TRY(pipe_consume(c, *begun, state6, prepare, score));   // the generator has been running since _begin
-    else SC_TRY(sc_perm_pipeline(c, state6, n, n_perm, inverse_only ? 1 : 2, pipe_units_ahead(), prepare, score));
+    else SC_TRY(sc_perm_pipeline(c, state6, n, n_perm, inverse_only ? 1 : 2, PIPE_AHEAD, prepare, score));
     return moran_finish(c, n_perm, I_out, sims_out, count_ge_out, sim_sum_out, sim_sumsq_out);
 }
 
@@ -2032,9 +2024,7 @@ static int moran_seeded_once(sc_ctx *c, uint64_t *state6, int64_t n_perm, double
 static int moran_seeded_streams(sc_ctx *c, uint64_t *state6, int64_t n_perm, double *I_out, double *sims_out,
                                 int64_t *count_ge_out, double *sim_sum_out, double *sim_sumsq_out, PermPipe *begun = nullptr)
 {
-    int leave = c && c->e_n > 0 && permgen_is_block_parallel(c, c->e_n) ? SCORE_RESERVED_CUS : 8;
-    if (const char *v = getenv("SC_SCORE_LEAVE_CUS")) leave = atoi(v);  // development: sweep the reservation
-    c->score_leave_cus = leave;
+    c->score_leave_cus = c && c->e_n > 0 && permgen_is_block_parallel(c, c->e_n) ? SCORE_RESERVED_CUS : 8;
     const int rc = moran_seeded_once(c, state6, n_perm, I_out, sims_out, count_ge_out, sim_sum_out, sim_sumsq_out, begun);
     c->score_leave_cus = 0;
     return rc;
@@ -2074,7 +2064,7 @@ extern "C" int sc_moran_seeded_begin(sc_ctx *c, const uint64_t *state6, int64_t 
     // generator's FIRST chunk for callers whose operands are resident -- scoring starts ~9 ms earlier, the step is 3.5 ms
     // LONGER (165.4 vs 161.9 ms, same box): the full-chip column-sum kernels delay the generator's first units, and the
     // scoring then only waits longer for its first chunks.)
-    SC_TRY(pipe_begin(c, state6, n_cells, n_perm, permgen_can_swap_inverse(n_cells) ? 1 : 2, pipe_units_ahead(), *pp, ahead_n));
+    SC_TRY(pipe_begin(c, state6, n_cells, n_perm, permgen_can_swap_inverse(n_cells) ? 1 : 2, PIPE_AHEAD, *pp, ahead_n));
     c->pipe = std::move(pp);
     return SC_OK;
 }
@@ -2501,42 +2491,9 @@ __global__ __launch_bounds__(256) void k_lm_observed(const long long *__restrict
         make_float4(__fmul_rn(zi.x, s.x), __fmul_rn(zi.y, s.y), __fmul_rn(zi.z, s.z), __fmul_rn(zi.w, s.w));
 }
 
-// count[i][g] += #{p : |Z[perm_p[i]] * sum_e w_e Z[perm_p[col_e]]| >= |I[i]|}
-__global__ __launch_bounds__(256) void k_lm_perm_count(const long long *__restrict__ indptr,
-                                                       const int32_t *__restrict__ indices,
-                                                       const double *__restrict__ w, const float *__restrict__ Z32,
-                                                       const float *__restrict__ I32,
-                                                       const int32_t *__restrict__ perm, int64_t pstride,
-                                                       int n_perm, int32_t *__restrict__ count, int64_t n)
-{
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t i = t >> 2;
-    int q = (int)(t & 3);
-    if (i >= n) return;
-    const float4 *Zt = reinterpret_cast<const float4 *>(Z32 + (int64_t)blockIdx.y * n * SC_TILE) + q;
-    const int64_t o = (int64_t)blockIdx.y * n * 4 + i * 4 + q;
-    const float4 obs = reinterpret_cast<const float4 *>(I32)[o];
-    const float ax = fabsf(obs.x), ay = fabsf(obs.y), az = fabsf(obs.z), aw = fabsf(obs.w);
-    const long long e0 = indptr[i], e1 = indptr[i + 1];
-    int cx = 0, cy = 0, cz = 0, cw = 0;
-    for (int p = 0; p < n_perm; ++p) {
-        const int32_t *prow = perm + (int64_t)p * pstride;
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (long long e = e0; e < e1; ++e) {
-            const float ww = (float)w[e];
-            const float4 z = Zt[(int64_t)prow[indices[e]] * 4];
-            s.x = __fadd_rn(s.x, __fmul_rn(ww, z.x)); s.y = __fadd_rn(s.y, __fmul_rn(ww, z.y));
-            s.z = __fadd_rn(s.z, __fmul_rn(ww, z.z)); s.w = __fadd_rn(s.w, __fmul_rn(ww, z.w));
-        }
-        const float4 zi = Zt[(int64_t)prow[i] * 4];
-        cx += fabsf(__fmul_rn(zi.x, s.x)) >= ax; cy += fabsf(__fmul_rn(zi.y, s.y)) >= ay;
-        cz += fabsf(__fmul_rn(zi.z, s.z)) >= az; cw += fabsf(__fmul_rn(zi.w, s.w)) >= aw;
-    }
-    reinterpret_cast<int4 *>(count)[o] = make_int4(cx, cy, cz, cw);
-}
-
-// ---- the same count in two phases per batch of permutations, in the graph's processing order (r02) ----
-// k_lm_perm_count above reads, per permutation and cell, k + 1 permutation indices and k + 1 random 64-byte z rows
+// ---- count[i][g] += #{p : |Z[perm_p[i]] * sum_e w_e Z[perm_p[col_e]]| >= |I[i]|}, in two phases per batch of
+// permutations, in the graph's processing order (r02) ----
+// A one-kernel form (r01) read, per permutation and cell, k + 1 permutation indices and k + 1 random 64-byte z rows
 // per gene tile.  Per cell i the permuted vector y = z[perm] is all that matters: I_perm[i] = y[i] * sum_e w_e y[col_e].
 // Phase A materialises y once per (permutation, tile) -- ONE random row per cell -- at the cell's position r in a
 // spatially sorted order (Ys[r] = Z[perm[order[r]]]); phase B is then a LOCAL sparse product: the neighbours of a cell
@@ -2788,7 +2745,7 @@ struct LmJob {
     int32_t *cnt = nullptr;
     unsigned char *zero = nullptr;
     dim3 gc;
-    int mode = 2;        // 0: one-kernel r01 form, 1: uint8 code rows, 2: float rows
+    int mode = 2;        // 1: uint8 code rows, 2: float rows
     int groups = 0;      // code rows: 128-gene groups
     int64_t batch = 0;   // permutations per launch
     bool uni = false;
@@ -2862,7 +2819,6 @@ static int lm_prepare(sc_ctx *c, int64_t n_perm, LmJob &j)
     j.n = n; j.G = G; j.T = T; j.tile_f = tile_f;
     j.mean32 = mean32; j.sd32 = sd32; j.Z32 = Z32; j.I32 = I32; j.Lag32 = Lag32; j.cnt = cnt; j.zero = zero; j.gc = gc;
     if (n_perm <= 0) return SC_OK;
-    if (c->lm_direct) { j.mode = 0; return SC_OK; }   // r01 form (development A/B, sc_ctx_set_local_moran_direct)
     SC_TRY(sc_graph_ensure_order(c));
     bool codes = false;
     SC_TRY(lm_codes_ok(c, &codes));
@@ -2898,12 +2854,7 @@ static int lm_count(sc_ctx *c, const LmJob &j, int64_t row0, int64_t p0, int64_t
     const int64_t n = j.n, T = j.T;
     if (p1 <= p0) return SC_OK;
     KernelTimerScope ts(c, SC_K_LEE_PERM);
-    if (j.mode == 0) {
-        SC_REQUIRE(p0 == 0, SC_ERR_STATE, "internal: the one-kernel local Moran form counts all permutations at once");
-        hipLaunchKernelGGL(k_lm_perm_count, j.gc, dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
-                           c->g_indices.as<int32_t>(), c->g_data.as<double>(), j.Z32, j.I32,
-                           c->perm.as<int32_t>() + row0 * c->p_stride, c->p_stride, (int)(p1 - p0), j.cnt, n);
-    } else if (j.mode == 1) {
+    if (j.mode == 1) {
         const dim3 g8((unsigned)ceil_div64(n * 8, 256), (unsigned)j.groups);
         auto count_u8 = j.uni ? k_lm_count_u8<true> : k_lm_count_u8<false>;
         for (int64_t p = p0; p < p1; p += j.batch) {
@@ -3007,10 +2958,9 @@ extern "C" int sc_local_moran_seeded(sc_ctx *c, uint64_t *state6, int64_t n_perm
     int copier_rc = SC_OK;
     std::optional<JoiningThread> copier;   // (declared after what its thread writes; reset() joins)
     bool copier_started = false;
-    static const bool copy_beside = !getenv("SC_LM_COPY_LATE");   // (A/B)
     auto prepare = [&]() -> int {
         SC_TRY(lm_prepare(c, n_perm, j));
-        if (!copy_beside || copier_started) return SC_OK;
+        if (copier_started) return SC_OK;
         if (!c->stream_out) SC_HIP(hipStreamCreateWithFlags(&c->stream_out, hipStreamNonBlocking));
         SC_TRY(c->lm_out.ensure(sizeof(float) * (size_t)j.n * (size_t)j.G, &c->mem));
         hipEvent_t ready;
@@ -3039,10 +2989,7 @@ extern "C" int sc_local_moran_seeded(sc_ctx *c, uint64_t *state6, int64_t n_perm
         }
         return SC_OK;
     };
-    auto count = [&](int64_t p0, int64_t p1) -> int {
-        if (j.mode == 0) return p1 == n_perm ? lm_count(c, j, 0, 0, n_perm) : SC_OK;   // (the one-kernel form: all rows at the end)
-        return lm_count(c, j, 0, p0, p1);
-    };
+    auto count = [&](int64_t p0, int64_t p1) -> int { return lm_count(c, j, 0, p0, p1); };
     // a job that fails its verification is rerun with the sequential scan: the counts restart at permutation 0, and the
     // copier is joined first (the second preparation rewrites what it reads -- with the same values)
     const int rc = permgen_rerun_on_failure(
@@ -3176,30 +3123,6 @@ extern "C" int sc_local_moran_classify(sc_ctx *c, const float *p_tab, const floa
 // optional per-cell permutation count  #{p : |float32(z_x[i] * (W z_y[perm_p])[i])| >= |L_local[i]|}
 // ------------------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(256) void k_lee_local_count(const long long *__restrict__ indptr,
-                                                         const int32_t *__restrict__ indices,
-                                                         const double *__restrict__ w, const double *__restrict__ zx,
-                                                         const double *__restrict__ zy,
-                                                         const double *__restrict__ Llocal,
-                                                         const int32_t *__restrict__ perm, int64_t pstride,
-                                                         int n_perm, int32_t *__restrict__ count, int64_t n)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const long long e0 = indptr[i], e1 = indptr[i + 1];
-    const double x = zx[i], obs = fabs(Llocal[i]);
-    int cnt = 0;
-    for (int p = 0; p < n_perm; ++p) {
-        const int32_t *prow = perm + (int64_t)p * pstride;
-        double s = 0.0;
-        for (long long e = e0; e < e1; ++e) s = __dadd_rn(s, __dmul_rn(w[e], zy[prow[indices[e]]]));
-        // the reference stores the permuted values in a float32 array before comparing (AC:1402,1408)
-        const double lp = (double)(float)__dmul_rn(x, s);
-        cnt += fabs(lp) >= obs;
-    }
-    count[i] = cnt;
-}
-
 __global__ __launch_bounds__(256) void k_vec_mul(const double *__restrict__ a, const double *__restrict__ b,
                                                  double *__restrict__ out, int64_t n)
 {
@@ -3207,8 +3130,8 @@ __global__ __launch_bounds__(256) void k_vec_mul(const double *__restrict__ a, c
     if (i < n) out[i] = __dmul_rn(a[i], b[i]);
 }
 
-// The same count in two phases per batch of permutations, in the graph's processing order (see k_lm_gather_sorted):
-// ys[p][r] = z_y[perm_p[order[r]]] once per permutation, then a LOCAL sparse product.  (k_lee_local_count above
+// The count in two phases per batch of permutations, in the graph's processing order (see k_lm_gather_sorted):
+// ys[p][r] = z_y[perm_p[order[r]]] once per permutation, then a LOCAL sparse product.  (A one-kernel form, r01,
 // fetched 900 GB for 999 permutations of 1M cells: 7 random 8-byte reads per cell and permutation, 128 bytes each.)
 #define LL_PERM_BATCH 16
 
@@ -3268,7 +3191,7 @@ static int ll_prepare(sc_ctx *c, int32_t gene_x, int32_t gene_y, int64_t n_perm,
     hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_y, j.zy);
     sc_launch_spmv_vec(c, c->g_indptr.as<int64_t>(), c->g_indices.as<int32_t>(), c->g_data.as<double>(), j.zy, j.lag, n);
     hipLaunchKernelGGL(k_vec_mul, dim3(gcol), dim3(256), 0, c->stream, j.zx, j.lag, j.L, n);
-    if (n_perm > 0 && !c->lm_direct) {
+    if (n_perm > 0) {
         SC_TRY(sc_graph_ensure_order(c));
         SC_TRY(c->lm_ys.ensure(sizeof(double) * (size_t)LL_PERM_BATCH * (size_t)n, &c->mem));
     }
@@ -3281,21 +3204,14 @@ static int ll_count(sc_ctx *c, const LlJob &j, int64_t row0, int64_t p0, int64_t
 {
     const int64_t n = j.n;
     const unsigned gcol = (unsigned)ceil_div64(n, 256);
-    if (c->lm_direct) {   // r01 form (development A/B)
-        SC_REQUIRE(p0 == 0, SC_ERR_STATE, "internal: the one-kernel local Lee form counts all permutations at once");
-        hipLaunchKernelGGL(k_lee_local_count, dim3(gcol), dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
-                           c->g_indices.as<int32_t>(), c->g_data.as<double>(), j.zx, j.zy, j.L,
-                           c->perm.as<int32_t>() + row0 * c->p_stride, c->p_stride, (int)(p1 - p0), j.cnt, n);
-    } else {
-        for (int64_t p = p0; p < p1; p += LL_PERM_BATCH) {
-            const int nb = (int)(p1 - p < LL_PERM_BATCH ? p1 - p : LL_PERM_BATCH);
-            hipLaunchKernelGGL(k_lee_local_gather, dim3(gcol, (unsigned)nb), dim3(256), 0, c->stream, j.zy,
-                               c->g_order.as<int32_t>(), c->perm.as<int32_t>() + (row0 + p) * c->p_stride, c->p_stride,
-                               n, c->lm_ys.as<double>());
-            hipLaunchKernelGGL(k_lee_local_count_sorted, dim3(gcol), dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
-                               c->g_indices_r.as<int32_t>(), c->g_data.as<double>(), c->g_order.as<int32_t>(), j.zx,
-                               c->lm_ys.as<double>(), j.L, nb, j.cnt, n, p == 0 ? 1 : 0);
-        }
+    for (int64_t p = p0; p < p1; p += LL_PERM_BATCH) {
+        const int nb = (int)(p1 - p < LL_PERM_BATCH ? p1 - p : LL_PERM_BATCH);
+        hipLaunchKernelGGL(k_lee_local_gather, dim3(gcol, (unsigned)nb), dim3(256), 0, c->stream, j.zy,
+                           c->g_order.as<int32_t>(), c->perm.as<int32_t>() + (row0 + p) * c->p_stride, c->p_stride,
+                           n, c->lm_ys.as<double>());
+        hipLaunchKernelGGL(k_lee_local_count_sorted, dim3(gcol), dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
+                           c->g_indices_r.as<int32_t>(), c->g_data.as<double>(), c->g_order.as<int32_t>(), j.zx,
+                           c->lm_ys.as<double>(), j.L, nb, j.cnt, n, p == 0 ? 1 : 0);
     }
     SC_HIP(hipGetLastError());
     return SC_OK;
@@ -3400,10 +3316,9 @@ extern "C" int sc_lee_local_seeded(sc_ctx *c, uint64_t *state6, int32_t gene_x, 
         if (p0 < a1)   // rows of the global statistic
             hipLaunchKernelGGL(k_vec_gather_dot, dim3(blocks, (unsigned)(a1 - p0)), dim3(256), 0, c->stream, vu, j.zy,
                                c->perm.as<int32_t>() + p0 * c->p_stride, c->p_stride, n, c->lee_b.as<double>() + (size_t)p0 * blocks);
-        // rows of the per-cell counts: permutations [b0 - Pg, p1 - Pg) of the local job (the one-kernel form: all at the end)
+        // rows of the per-cell counts: permutations [b0 - Pg, p1 - Pg) of the local job
         const int64_t b0 = p0 > Pg ? p0 : Pg;
-        if (b0 < p1 && !c->lm_direct) SC_TRY(ll_count(c, j, Pg, b0 - Pg, p1 - Pg));
-        if (b0 < p1 && c->lm_direct && p1 == Pg + Pl) SC_TRY(ll_count(c, j, Pg, 0, Pl));
+        if (b0 < p1) SC_TRY(ll_count(c, j, Pg, b0 - Pg, p1 - Pg));
         SC_HIP(hipGetLastError());
         return SC_OK;
     };

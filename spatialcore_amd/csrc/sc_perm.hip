@@ -179,55 +179,12 @@ extern "C" int sc_perm_generate(sc_ctx *c, uint64_t *state6, int64_t n, int64_t 
 }
 
 // ---- the generator / consumer pipeline of the seeded statistics ----
-#ifndef PIPE_AHEAD
-#define PIPE_AHEAD 3         // launch units the generator's preparation runs ahead of its chain inside the pipeline
-#endif
-#ifndef PIPE_FIRST
 #define PIPE_FIRST 32        // permutations of the first pipeline chunk
-#endif
-#ifndef PIPE_TAIL
-#define PIPE_TAIL "96,48,24" // the last chunks, tapering: see pipe_tail_perms
-#endif
-#ifndef PIPE_SWAP_STREAMS
 #define PIPE_SWAP_STREAMS 2  // swap chunks in flight (they are latency-bound: two overlap almost for free)
-#endif
-
-// permutations of the pipeline's first chunk (SC_PIPE_FIRST: development, to sweep the schedule)
-static int64_t pipe_first_perms()
-{
-    int64_t v = PIPE_FIRST;
-    if (const char *e = getenv("SC_PIPE_FIRST")) v = atoi(e);
-    return v < 8 || v > PERM_CHUNK ? PIPE_FIRST : v;
-}
 // The job ends with what is left once the generator's chain has finished: the swaps of its last chunk (~10 ms whatever
 // its size: one workgroup per permutation, latency-bound) and the consumption of every chunk not consumed yet.  Behind
-// a 128-permutation chunk that is its swaps AND its 10-ms consumption; tapering chunks leave a few milliseconds (bench
+// a 128-permutation chunk that is its swaps AND its 10-ms consumption; tapering chunks (PIPE_TAIL) leave a few milliseconds (bench
 // step, same box, ms: one 32-permutation last chunk 173.5 / 174.6; 64,32: 172.4 / 178.8; 64,32,16: 172.8 / 173.1; 96,48,24: 169.4 / 169.4).
-// SC_PIPE_TAIL="a,b,...": development, to sweep the schedule ("0": no short chunks at the end).
-static std::vector<int64_t> pipe_tail_perms()
-{
-    const char *e = getenv("SC_PIPE_TAIL");
-    std::vector<int64_t> t;
-    for (const char *p = e ? e : PIPE_TAIL; *p;) {
-        char *end = nullptr;
-        const long v = strtol(p, &end, 10);
-        if (end == p) break;
-        if (v >= 8 && v <= PERM_CHUNK) t.push_back(v);
-        p = *end == ',' ? end + 1 : end;
-    }
-    return t;
-}
-int64_t pipe_tail_total()
-{
-    int64_t s = 0;
-    for (int64_t v : pipe_tail_perms()) s += v;
-    return s;
-}
-int pipe_units_ahead()
-{
-    if (const char *v = getenv("SC_PIPE_AHEAD")) return atoi(v);  // development: sweep the lookahead
-    return PIPE_AHEAD;
-}
 
 // The generator / consumer pipeline shared by sc_moran_seeded and sc_lee_seeded: numpy-exact permutation rows
 // [0, n_perm) of length n are produced chunk by chunk on the generator's streams (stream2: rejection scan chain,
@@ -246,7 +203,7 @@ static int pipe_generate(sc_ctx *c, PermPipe &pp, int64_t k)
     // permutation; 37 k with one swap kernel at a time).  The tapering last chunks arrive 2-6 ms apart after the chain
     // is all but done, and keep overlapping.
     const int64_t chunks = (int64_t)pp.bounds.size() - 1;
-    const bool overlap = PIPE_SWAP_STREAMS > 1 && (k & 1) && (k >= chunks - 3 || getenv("SC_SWAP_OVERLAP_ALL") != nullptr);
+    const bool overlap = PIPE_SWAP_STREAMS > 1 && (k & 1) && k >= chunks - 3;
     hipStream_t sw = overlap ? c->stream4 : c->stream3;
     SC_HIP(hipEventCreateWithFlags(&scanned, hipEventDisableTiming));
     SC_HIP(hipEventCreateWithFlags(&swapped, hipEventDisableTiming));
@@ -271,7 +228,6 @@ void pipe_drain(sc_ctx *c, PermPipe &pp)
     if (c->stream3) (void)hipStreamSynchronize(c->stream3);
     if (c->stream4) (void)hipStreamSynchronize(c->stream4);
     if (c->stream_px) (void)hipStreamSynchronize(c->stream_px);
-    if (c->stream_fr) (void)hipStreamSynchronize(c->stream_fr);
     for (hipStream_t sp : c->stream_pg)
         if (sp) (void)hipStreamSynchronize(sp);
     (void)hipStreamSynchronize(c->stream);
@@ -296,15 +252,7 @@ int pipe_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int
     c->p_count = 0;
     c->inv_rows_valid = 0;
     c->perm_forward_valid = false;
-    if (!c->stream2) {  // (SC_STREAM_PRIORITY=1: the r01 prioritised chain stream, for experiments; no gain measured in r02)
-        int prio_lo = 0, prio_hi = 0;
-        if (!getenv("SC_STREAM_PRIORITY") || hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess ||
-            hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_hi) != hipSuccess) {
-            (void)hipGetLastError();
-            c->stream2 = nullptr;
-            SC_HIP(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-        }
-    }
+    if (!c->stream2) SC_HIP(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
     if (!c->stream_px) SC_HIP(hipStreamCreateWithFlags(&c->stream_px, hipStreamNonBlocking));
     if (!c->stream3) SC_HIP(hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
     if (!c->stream4) SC_HIP(hipStreamCreateWithFlags(&c->stream4, hipStreamNonBlocking));
@@ -315,15 +263,12 @@ int pipe_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int
     pp.bounds.clear();
     pp.bounds.push_back(0);
     if (n_perm > 3 * PERM_CHUNK) {
-        const int64_t first = pipe_first_perms(), last = pipe_tail_total();
-        const std::vector<int64_t> tail = pipe_tail_perms();
-        const int64_t rest = (n_perm - last - first) % PERM_CHUNK;
-        static const bool join = getenv("SC_PIPE_JOIN") != nullptr;   // development: a small remainder joins the first chunk (r02 / early r03)
-        int64_t p = first + (join && rest < PERM_CHUNK / 2 ? rest : 0);
+        const int64_t rest = (n_perm - PIPE_TAIL_TOTAL - PIPE_FIRST) % PERM_CHUNK;
+        int64_t p = PIPE_FIRST;
         pp.bounds.push_back(p);
-        if (p == first && rest > 0) { p += rest; pp.bounds.push_back(p); }   // the remainder: a chunk of its own, second
-        for (; p < n_perm - last; ) { p += PERM_CHUNK; pp.bounds.push_back(p); }
-        for (int64_t v : tail) { p += v; pp.bounds.push_back(p); }
+        if (rest > 0) { p += rest; pp.bounds.push_back(p); }   // the remainder: a chunk of its own, second
+        for (; p < n_perm - PIPE_TAIL_TOTAL; ) { p += PERM_CHUNK; pp.bounds.push_back(p); }
+        for (int64_t v : PIPE_TAIL) { p += v; pp.bounds.push_back(p); }
     } else {
         for (int64_t p = PERM_CHUNK; p < n_perm; p += PERM_CHUNK) pp.bounds.push_back(p);
         pp.bounds.push_back(n_perm);

@@ -103,13 +103,9 @@ __device__ static inline uint64_t xsl_rr32(u128 s)
 // jump A^16384 between blocks.
 // ------------------------------------------------------------------------------------------------
 
-#ifndef SCAN_THREADS
 #define SCAN_THREADS 1024
-#endif
-#ifndef SCAN_D
 #define SCAN_D 16  // draws per thread and round (r01 sweep at 1M cells, sequential / block-parallel scan of 300
                    // permutations: 8 -> 145 / 83 ms, 12 -> 119 / 72, 16 -> 107 / 58, 20 -> 103 / 59, 24 -> 114 / 63, 32 -> 154 / 84)
-#endif
 #define SCAN_BLOCK (SCAN_THREADS * SCAN_D)
 #define SCAN_GROUPS (SCAN_D / 4)
 #if SCAN_D <= 32
@@ -178,71 +174,13 @@ __device__ __forceinline__ void scan_thread(const uint32_t (&u)[SCAN_D], uint32_
     // fast path: neither a mask change, nor the end of a permutation, nor the end of the job can
     // happen within SCAN_D accepts
     const bool fast = i0 > (mask >> 1) + SCAN_D && c_in + SCAN_D < limit;
-#ifndef SCAN_GAP_FORM
-#define SCAN_GAP_FORM 2      // 1: (shift, xor, min) per draw; 2: two unsigned mins (A/B builds)
-#endif
-#ifndef SCAN_GENERAL_GAP
-#define SCAN_GENERAL_GAP 0   // 1: the general loop tracks the gap for its fast lanes (first step of r04; A/B builds)
-#endif
-#ifdef SCAN_R03_PATHS
-    if (fast) {
-        uint32_t thr = i0, gap = 0xffffffffu;
-        bits_t bits = 0;
-#pragma unroll
-        for (int s = 0; s < SCAN_D; ++s) {
-            const uint32_t v = u[s] & mask;
-            const int32_t d = (int32_t)(thr - v);        // both < 2^31; accepted iff d >= 0
-            const uint32_t acc = (uint32_t)(~d) >> 31;
-            gap = min(gap, (uint32_t)(d ^ (d >> 31)));   // d if accepted, -d - 1 if rejected
-            bits |= (bits_t)acc << s;
-            thr -= acc;
-        }
-        r.cnt = i0 - thr; r.bits = bits; r.gap = gap; r.fast = 1;
-    }
-    if (!__any(!fast)) return;  // a wavefront-uniform branch: the straight-line code below must not be merged into every pass
-    if (fast) return;
-    // general path, branch-free: the band / permutation bookkeeping is evaluated for every draw (it is the
-    // identity unless the draw was accepted), so a wavefront with a single such thread pays ~13 plain ALU
-    // operations per draw instead of a divergent branch tree
-    uint32_t i = i0, off = c_in, end = 0;
-    bits_t bits = 0;
-#pragma unroll
-    for (int s = 0; s < SCAN_D; ++s) {
-        const uint32_t v = u[s] & mask;
-        const uint32_t acc = ((off < limit) & (v <= i)) ? 1u : 0u;
-        bits |= (bits_t)acc << s;
-        off += acc;
-        i -= acc;
-        end = (acc & (off == limit ? 1u : 0u)) ? (uint32_t)s + 1 : end;
-        const bool wrap = i == 0;                 // the permutation is complete: the next one starts at M
-        const uint32_t half = mask >> 1;
-        mask = wrap ? top_mask : (i <= half ? half : mask);
-        i = wrap ? M : i;
-    }
-    const uint32_t cnt = off - c_in;
-    r.end = end;
-    r.cnt = cnt; r.bits = bits; r.gap = 0; r.fast = 0;
-#else
     // r04: ONE pass per wavefront (r03 ran the fast loop for its fast lanes and then the general loop for the others: the
     // wavefront that holds a band change -- the one every round of a computed block waits for -- paid both, ~310
-    // instructions).  All lanes fast: the fast loop.  Otherwise every lane takes the general loop, which also tracks the
-    // gap, so a fast lane leaves it with exactly what the fast loop would have given it; and the job's end is looked for
-    // only by wavefronts that can reach it.
+    // instructions).  All lanes fast: the fast loop.  Otherwise every lane takes the general loop; and the job's end is
+    // looked for only by wavefronts that can reach it.
     if (!__any(!fast)) {
         uint32_t thr = i0;
         bits_t bits = 0;
-#if SCAN_GAP_FORM == 1
-        uint32_t gap = 0xffffffffu;
-#pragma unroll
-        for (int s = 0; s < SCAN_D; ++s) {
-            const uint32_t v = u[s] & mask;
-            const int32_t d = (int32_t)(thr - v);        // both < 2^31; accepted iff d >= 0
-            const uint32_t acc = (uint32_t)(~d) >> 31;
-            gap = min(gap, (uint32_t)(d ^ (d >> 31)));   // d if accepted, -d - 1 if rejected
-            bits |= (bits_t)acc << s;
-            thr -= acc;
-        }
-#else
         // the slack of an accepted draw is d, of a rejected one -d - 1 = ~d: as UNSIGNED numbers the other one of the pair is
         // >= 2^31 and never the minimum -- two mins on values the loop has anyway, instead of (shift, xor, min)
         uint32_t gacc = 0xffffffffu, grej = 0xffffffffu;
@@ -258,7 +196,6 @@ __device__ __forceinline__ void scan_thread(const uint32_t (&u)[SCAN_D], uint32_
             thr -= acc;
         }
         const uint32_t gap = min(gacc, grej);
-#endif
         r.cnt = i0 - thr; r.bits = bits; r.gap = gap; r.fast = 1;
         return;
     }
@@ -267,21 +204,15 @@ __device__ __forceinline__ void scan_thread(const uint32_t (&u)[SCAN_D], uint32_
     // (r04, second step: no gap in the general loop.  A wavefront comes here because one of its lanes sits at a band edge or
     // a permutation's end; whatever moves its entering counts moves that edge, and the wavefront is re-evaluated as a whole
     // anyway -- a validity range for its fast lanes bought nothing in the rounds counter, and costs 3 of 12 operations a draw.)
-    uint32_t i = i0, gap = 0xffffffffu;
+    uint32_t i = i0;
     bits_t bits = 0;
     if (!__any(!(c_in + SCAN_D < limit))) {   // (wavefront-uniform) the job does not end inside these draws
-#ifndef SCAN_WRAP_ALWAYS
-#define SCAN_WRAP_ALWAYS 0   // (A/B builds)
-#endif
-        if (!SCAN_WRAP_ALWAYS && !__any(i0 <= SCAN_D)) {           // (wavefront-uniform) nor does a permutation: mask changes only
+        if (!__any(i0 <= SCAN_D)) {           // (wavefront-uniform) nor does a permutation: mask changes only
 #pragma unroll
             for (int s = 0; s < SCAN_D; ++s) {
                 const uint32_t v = u[s] & mask;
                 const int32_t d = (int32_t)(i - v);          // accepted iff d >= 0
                 const uint32_t acc = (uint32_t)(~d) >> 31;
-#if SCAN_GENERAL_GAP
-                gap = min(gap, (uint32_t)(d ^ (d >> 31)));
-#endif
                 bits |= (bits_t)acc << s;
                 i -= acc;
                 const uint32_t half = mask >> 1;
@@ -293,9 +224,6 @@ __device__ __forceinline__ void scan_thread(const uint32_t (&u)[SCAN_D], uint32_
                 const uint32_t v = u[s] & mask;
                 const int32_t d = (int32_t)(i - v);
                 const uint32_t acc = (uint32_t)(~d) >> 31;
-#if SCAN_GENERAL_GAP
-                gap = min(gap, (uint32_t)(d ^ (d >> 31)));
-#endif
                 bits |= (bits_t)acc << s;
                 i -= acc;
                 const bool wrap = i == 0;                 // the permutation is complete: the next one starts at M
@@ -305,12 +233,7 @@ __device__ __forceinline__ void scan_thread(const uint32_t (&u)[SCAN_D], uint32_
             }
         }
         r.cnt = (uint32_t)__popcll((unsigned long long)bits);
-#if SCAN_GENERAL_GAP
-        r.bits = bits; r.gap = fast ? gap : 0u; r.fast = fast ? 1u : 0u;
-#else
-        (void)gap;
         r.bits = bits; r.gap = 0u; r.fast = 0u;
-#endif
         return;
     }
     uint32_t off = c_in, end = 0;
@@ -329,7 +252,6 @@ __device__ __forceinline__ void scan_thread(const uint32_t (&u)[SCAN_D], uint32_
     }
     r.end = end;
     r.cnt = off - c_in; r.bits = bits; r.gap = 0; r.fast = 0;
-#endif
 }
 
 // Is the cached result still the exact result for entering count c_new?  On the fast path every
@@ -388,10 +310,6 @@ __device__ __forceinline__ uint32_t expected_steps(uint32_t rem, float q, uint32
     return (uint32_t)(acc + 0.5f);
 }
 
-#ifdef PHI_PROFILE
-__device__ unsigned long long g_phi_prof[32 + 2 * 128];   // development: see k_chain, block_fixed_point (read by sc_permgen_profile);
-                                                          // [32 ..): log of (unit | first unit of the launch << 32, clocks waited) of long waits
-#endif
 
 __device__ __forceinline__ uint32_t select64(uint64_t x, uint32_t r)  // position of the set bit of rank r < popc(x)
 {
@@ -407,72 +325,6 @@ __device__ __forceinline__ uint32_t select64(uint64_t x, uint32_t r)  // positio
 struct BlockShared {
     uint32_t wsum[2][SCAN_THREADS / 64];   // per wavefront: accept count | (recomputed something last round) << 31; by round parity
 };
-
-// r04: the END of a permutation, solved draw by draw (k_chain's computed blocks).
-// The fixed point below grows its exact prefix band by band, and through the last few hundred steps of a permutation --
-// thresholds of a few hundred, where every accepted draw before a thread changes what the thread does -- by two or three
-// THREADS a round: 8 of the ~16 rounds of the block in which a permutation ends (CPU restatement of the rounds: the
-// front's thread by round reads 924, 926, 937, 939, 940, 943, 945 of 1024; scripts/fixed_point_rounds_sim.py).  Once the
-// exact prefix has reached TAIL_I steps before the permutation's end, wavefront 0 takes over from there with one LANE per
-// draw: 64 draws at a time, accept set = fixed point of "v <= i - (accepted lanes below)" by ballot (2-3 iterations, ~50
-// clocks each), cut at the draw that halves the mask or completes the permutation.  It runs to the end of the thread in
-// which the permutation ends; those threads take their accept bits and entering counts from LDS and are never stale
-// again; the threads behind start a permutation with i = M, where a round settles them.
-#ifndef TAIL_I
-#define TAIL_I 1024                    // steps before the permutation's end at which the lanes take over
-#endif
-#define TAIL_THREADS (TAIL_I / 4 + 32) // threads' worth of staged draws: the last TAIL_I steps take ~1.37 TAIL_I draws (sd ~ sqrt)
-struct TailShared {
-    uint32_t fst[2][SCAN_THREADS / 64];            // per wavefront: (first stale thread << 16 | min(steps left there, 0xffff)), or ~0; by round parity
-    uint32_t u[TAIL_THREADS * SCAN_D];             // the staged draws
-    uint8_t acc[TAIL_THREADS * SCAN_D];            // their accept decisions
-    uint32_t cin[TAIL_THREADS];                    // entering count of each solved thread, relative to the front's
-    uint32_t nsolved;                              // threads solved
-    uint32_t open;                                 // this block may still call the lanes (kept here: k_chain has no register to spare)
-};
-
-// wavefront 0: draws tu[0 .. nq) entered with i steps left in the permutation (mask = mask_of(i)); returns the number of
-// draws decided (a multiple of SCAN_D: through the thread in which the permutation ends, or all nq)
-__device__ __forceinline__ uint32_t tail_solve(TailShared &ts, uint32_t nq, uint32_t i, uint32_t M, uint32_t top_mask)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    uint32_t mask = mask_of(i), c = 0, q = 0;
-    bool wrapped = false;
-    while (q < nq) {
-        uint32_t len = nq - q < 64u ? nq - q : 64u;
-        if (wrapped) {                       // finish the thread in which the permutation ended, then stop
-            const uint32_t restd = (SCAN_D - (q & (SCAN_D - 1))) & (SCAN_D - 1);
-            if (restd == 0) break;
-            len = restd;
-        }
-        const bool in = lane < len;
-        const uint32_t v = in ? (ts.u[q + lane] & mask) : 0xffffffffu;
-        unsigned long long A = __ballot(in && v <= i);          // every threshold at its upper bound
-        for (int it = 0; it < 66; ++it) {                        // (the exact prefix grows by a lane an iteration at least)
-            const uint32_t pre = (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(A >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)A, 0u));
-            const unsigned long long A2 = __ballot(in && pre <= i && v <= i - pre);
-            if (A2 == A) break;
-            A = A2;
-        }
-        // the accepts that change the mask (or complete the permutation): i falls to mask >> 1 after i - (mask >> 1) of them
-        const uint32_t half = mask >> 1, nb = i - half;
-        uint32_t T = (uint32_t)__popcll(A);
-        if (T >= nb) {
-            len = select64(A, nb - 1u) + 1u;
-            A &= sc_low_mask64(len);
-            T = nb;
-        }
-        if (lane < len) {
-            ts.acc[q + lane] = (uint8_t)((A >> lane) & 1ull);
-            if (((q + lane) & (SCAN_D - 1)) == 0)
-                ts.cin[(q + lane) / SCAN_D] = c + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(A >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)A, 0u));
-        }
-        c += T; i -= T; q += len;
-        if (i == 0) { i = M; mask = top_mask; wrapped = true; }
-        else if (i <= half) mask = half;
-    }
-    return q;
-}
 
 // inclusive prefix sum inside each row of 16 lanes
 __device__ __forceinline__ uint32_t row16_inclusive_scan(uint32_t x)
@@ -495,11 +347,9 @@ __device__ __forceinline__ uint32_t row16_inclusive_scan(uint32_t x)
 // of bookkeeping per wavefront and round -- 16 wavefronts on one CU make a round throughput-bound, ~2.5 us; measured
 // 3.6 rounds for an ordinary computed block, 13 for the block in which a permutation ends.)
 // Returns 1 if the iteration cap was hit (cannot happen: the prefix grows by at least one thread a round).
-template <bool TAIL = false>
 __device__ __forceinline__ int block_fixed_point(const uint32_t (&u)[SCAN_D], uint64_t S_block,
                                                  uint32_t rem_block, uint32_t M, uint32_t top_mask, uint64_t total_steps, BlockShared &sh,
-                                                 uint32_t &parity, ScanRes &r, uint32_t &excl, uint32_t &total_cnt,
-                                                 int *rounds_out = nullptr, TailShared *ts = nullptr)
+                                                 uint32_t &parity, ScanRes &r, uint32_t &excl, uint32_t &total_cnt)
 {
     // rem_block = M - S_block % M, the steps left in the current permutation (callers carry it along: a
     // 64-bit modulo per block by every wavefront costs more than a fifth of the block)
@@ -510,100 +360,24 @@ __device__ __forceinline__ int block_fixed_point(const uint32_t (&u)[SCAN_D], ui
     const uint64_t left = total_steps - S_block;
     const uint32_t limit = left > 0xffffffffULL ? 0xffffffffu : (uint32_t)left;
     // first guess of the entering count: the expected count (any guess converges; a good one saves rounds)
-#ifdef PHI_PROFILE
-    const long long pf_a = clock64();
-#endif
     scan_thread(u, expected_steps(rem_block, (float)(tau * SCAN_D), M), rem_block, M, top_mask, limit, r);
-#ifdef PHI_PROFILE
-    if (rounds_out && tau == 0) { atomicAdd(&g_phi_prof[24], (unsigned long long)(clock64() - pf_a)); atomicAdd(&g_phi_prof[25], 1ull); }
-#endif
     excl = 0; total_cnt = 0;
     uint32_t recomputed = 1u;
-#ifdef PHI_PROFILE
-    long long pf_r = 0;
-#endif
-    // TAIL: only where the permutation that ends is not the job's last (its end is the job's `limit`, which the lanes do not know)
-    if (TAIL) {
-        if (tau == 0) ts->open = (left > (uint64_t)rem_block && rem_block <= SCAN_BLOCK) ? 1u : 0u;
-        if (lane == 0) ts->fst[parity][wave] = 0xffffffffu;   // (no front before the first round)
-    }
     uint32_t incl = 0;
     for (int iter = 0;; ++iter) {
         if (recomputed) incl = wave_inclusive_scan(r.cnt);   // (wavefront-uniform: a wavefront that re-evaluated nothing keeps its sums)
         if (lane == 63) sh.wsum[parity][wave] = incl | (recomputed << 31);
-#ifdef PHI_PROFILE
-        const long long pf_b0 = clock64();
-        if (rounds_out && tau == 0 && iter > 0) atomicAdd(&g_phi_prof[3], (unsigned long long)(pf_b0 - pf_r));   // wavefront 0's own work of a round
-#endif
         __syncthreads();
-#ifdef PHI_PROFILE
-        pf_r = clock64();
-        if (rounds_out && tau == 0) { atomicAdd(&g_phi_prof[7], (unsigned long long)(pf_r - pf_b0)); atomicAdd(&g_phi_prof[11], 1ull); }   // its wait at the barrier
-#endif
         const uint32_t mine = lane < NW ? sh.wsum[parity][lane] : 0u;
-        const bool tail_open = TAIL && ts->open != 0u;
-        const uint32_t fst = (tail_open && lane < NW) ? ts->fst[parity][lane] : 0xffffffffu;
         parity ^= 1u;   // the other buffer is rewritten only after the next barrier, i.e. after everybody has read this one
         const bool anybody = __any((int)(mine >> 31));
         const uint32_t run = row16_inclusive_scan(mine & 0x7fffffffu);
         total_cnt = (uint32_t)__builtin_amdgcn_readlane((int)run, NW - 1);
         const uint32_t before = wave ? (uint32_t)__builtin_amdgcn_readlane((int)run, wave - 1) : 0u;
         excl = before + incl - r.cnt;
-        if (!anybody) {           // the counts are those of the previous round, in which every cached result was valid
-            if (rounds_out) *rounds_out = iter + 1;
-            return 0;
-        }
-        bool pinned_now = false;
-        if (tail_open) {
-            // The front: the first stale thread of the previous round.  Nobody in front of it was stale, so its entering
-            // count was exact then and still is (and it has been recomputed with it since).
-            const unsigned long long has = __ballot(fst != 0xffffffffu);
-            if (has) {
-                const uint32_t f = (uint32_t)__builtin_amdgcn_readlane((int)fst, (int)__builtin_ctzll(has));
-                const uint32_t s = f >> 16, i_front = f & 0xffffu;
-                if (i_front <= TAIL_I) {   // (uniform) -- steps left in the permutation the BLOCK was entered in
-                    const uint32_t nthr = SCAN_THREADS - s < TAIL_THREADS ? SCAN_THREADS - s : TAIL_THREADS;
-                    if (tau >= s && tau < s + nthr) {
-#pragma unroll
-                        for (int k = 0; k < SCAN_D; ++k) ts->u[(tau - s) * SCAN_D + k] = u[k];
-                    }
-                    __syncthreads();
-                    if (wave == 0) {
-                        const uint32_t nq = tail_solve(*ts, nthr * SCAN_D, i_front, M, top_mask);
-                        if (lane == 0) { ts->nsolved = nq / SCAN_D; ts->open = 0u; }   // (everybody has read `open` in front of the barrier above)
-                    }
-                    __syncthreads();
-                    const uint32_t ns = ts->nsolved;
-                    if (tau >= s && tau < s + ns) {
-                        bits_t b = 0;
-#pragma unroll
-                        for (int k = 0; k < SCAN_D; ++k) b |= (bits_t)ts->acc[(tau - s) * SCAN_D + k] << k;
-                        r.bits = b; r.cnt = (uint32_t)__popcll((unsigned long long)b); r.gap = 0; r.fast = 0; r.end = 0;
-                        r.c_used = (rem_block - i_front) + ts->cin[tau - s];   // exact: valid from the next round on, and for good
-                        pinned_now = true;
-                    }
-                }
-            }
-        }
-        const bool stale = !pinned_now && !scan_still_valid(r, excl, M, limit);
-        recomputed = (__any(stale) || __any(pinned_now)) ? 1u : 0u;
-        if (tail_open) {   // my wavefront's first stale thread | steps left there, for the next round (that buffer's readers are done)
-            const unsigned long long sm = __ballot(stale);
-            uint32_t my_front = 0xffffffffu;
-            if (sm) {
-                const int fl = (int)__builtin_ctzll(sm);
-                const uint32_t ce = (uint32_t)__builtin_amdgcn_readlane((int)excl, fl);
-                // steps left at that thread in the permutation the block was entered in (beyond its end: not our business)
-                const uint32_t il = ce < rem_block ? rem_block - ce : 0xffffu;
-                my_front = (((uint32_t)wave * 64u + (uint32_t)fl) << 16) | (il < 0xffffu ? il : 0xffffu);
-            }
-            if (lane == 0) ts->fst[parity][wave] = my_front;
-        }
-#ifdef PHI_PROFILE
-        if (rounds_out && lane == 0) {   // wavefronts that recompute, by round (1, 2, 3, later)
-            if (recomputed) atomicAdd(&g_phi_prof[26 + (iter < 3 ? iter : 3)], 1ull);
-        }
-#endif
+        if (!anybody) return 0;   // the counts are those of the previous round, in which every cached result was valid
+        const bool stale = !scan_still_valid(r, excl, M, limit);
+        recomputed = __ballot(stale) ? 1u : 0u;
         if (recomputed) {
             if (stale) scan_thread(u, excl, rem_block, M, top_mask, limit, r);
         }
@@ -741,26 +515,16 @@ __global__ __launch_bounds__(256) void k_expand(const uint32_t *__restrict__ raw
 
 #define PHI_W 16384               // window bits per side
 #define PHI_WORDS (PHI_W / 64)
-#ifndef PHI_MAX_EV
 #define PHI_MAX_EV 2048           // events per side a prepared block may hold
-#endif
-#ifndef PHI_WINDOW
 #define PHI_WINDOW 2.25           // window half-width in units of sqrt(draws since the reference state) (= 4.5 sigma)
-#endif
-#ifndef PHI_UNIT
 #define PHI_UNIT 512              // blocks per launch unit (the chain pays ~0.17 ms between launches; with 32-draw
                                   // threads: 80 -> 842, 112 -> 900, 160 -> 1017, 224 -> 1024, 320 -> 1020-1033 genes/s in
                                   // the pipeline; with 16-draw threads: 384 -> 1068, 448 -> 1067, 512 -> 1071)
-#endif
-#ifndef PHI_AHEAD_MAX
 #define PHI_AHEAD_MAX 3
-#endif
                                   // units prepared ahead of the chain (their guesses use a state ahead + 1 units old):
                                   // 1 when the generator has the chip to itself, 3 next to the scoring kernel, whose
                                   // workgroups hold the CUs for milliseconds (wider windows, ~25 % more computed blocks)
-#ifndef PHI_RING
 #define PHI_RING 4096
-#endif
                                 // table ring slots: EIGHT units.  Units are cut at chunk ends, so a short unit shifts the ring
                                   // positions of its successors, and unit v + 5 can then land on slots of unit v.  The chain is
                                   // done with unit v by then (k_gate), but k_seg_fill(v) -- which runs behind the chain on stream
@@ -962,18 +726,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_phi_events(const uint32_t *__r
     }
 }
 
-#ifndef PHI_SEG_MAX
 #define PHI_SEG_MAX 16        // blocks per segment at most (segments are cut at multiples of this inside a unit)
-#endif
 #define PHI_COMPOSE_WGS (PHI_UNIT / 2)   // workgroups of k_phi_compose: one per multi-block segment, the others leave at once
-#ifndef PHI_TAIL_PLUS
-#define PHI_TAIL_PLUS
-#endif
-#ifndef PHI_TAIL
-#define PHI_TAIL false        // r04 NEGATIVE RESULT, kept as a development build (-DPHI_TAIL=true): the end of a permutation inside a
-                              // computed block by lanes (tail_solve, see BlockShared) -- rounds 16.1 -> 10.2, clocks 67.9 k -> 76.2 k
-#endif
-#define PHI_TAIL_LDS (0 PHI_TAIL_PLUS)   // (the preprocessor cannot test `true`: build the variant with -DPHI_TAIL=true -DPHI_TAIL_PLUS=+1)
 #define PHI_NS 6              // segments whose tables the chain stages in LDS at once (a run of prepared blocks)
 #define PHI_STAGE_PIECES 64   // 16-byte pieces per side the chain stages: entry gaps up to 8192 (beyond: global memory)
 
@@ -1174,28 +928,6 @@ extern "C" int sc_ctx_permgen_form(sc_ctx *c, int64_t n, const char **form)
     return SC_OK;
 }
 
-#ifdef PHI_PROFILE
-int sc_permgen_profile(unsigned long long *out32, int reset)
-{
-    SC_HIP(hipDeviceSynchronize());
-    SC_HIP(hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_phi_prof), sizeof(unsigned long long) * 32));
-    if (getenv("SC_PHI_WAIT_LOG")) {   // development: the long waits of the chain, one line each
-        unsigned long long lg[2 * 128];
-        SC_HIP(hipMemcpyFromSymbol(lg, HIP_SYMBOL(g_phi_prof), sizeof(lg), sizeof(unsigned long long) * 32));
-        const unsigned long long cnt = out32[30] < 128 ? out32[30] : 128;
-        for (unsigned long long k = 0; k < cnt; ++k)
-            fprintf(stderr, "wait: unit %llu (launch began at unit %llu) %.0f us\n", lg[2 * k] & 0xffffffffull, lg[2 * k] >> 32, (double)lg[2 * k + 1] / 2100.0);
-    }
-    if (reset) {
-        unsigned long long z[32 + 2 * 128] = {};
-        SC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_phi_prof), z, sizeof(z)));
-    }
-    return SC_OK;
-}
-#else
-int sc_permgen_profile(unsigned long long *out32, int) { memset(out32, 0, sizeof(unsigned long long) * 32); return SC_OK; }
-#endif
-
 // ------------------------------------------------------------------------------------------------
 // r04: SEGMENTS -- the gap-transfer tables of consecutive prepared blocks composed into one.
 //
@@ -1381,320 +1113,6 @@ __global__ __launch_bounds__(64) void k_seg_fill(uint64_t b0, uint64_t b1, const
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// r04: FRESH TABLES for the end of a permutation -- a second tier of preparation.
-//
-// Of the ~10 blocks per permutation (of 1M cells) the chain computes itself, 7.4 hold a band change or the permutation's
-// end and cannot be tabulated; the other 2.6 are blocks of the permutation's last bands whose FIRST-tier preparation
-// failed only because its window was too wide for them: a guess made 2-4 launch units ahead is +-13 k states uncertain,
-// which is a third of the band [32768, 65535] (the narrowed windows miss, or the events exceed the table limit).  A guess
-// made from the exact state at the START of the permutation is +-2 k states uncertain when it reaches those blocks.
-// k_fresh runs beside the chain (a handful of workgroups on a stream of their own, for the life of the chain launch): the
-// chain posts the exact state of every block boundary at which a new permutation has begun; each helper takes one of the
-// clean-looking blocks among the last FR_TAIL of that permutation, solves it from the fresh guess, and turns its events
-// into the gap-transfer table of a +-2047 window by walking every entry gap through the event list (with so narrow a
-// window that is cheaper than the rank-select build of k_phi_tbuild, and it is done before the chain arrives).  The chain
-// consults the fresh table when it meets a block it would otherwise compute (or whose first-tier window missed) in the
-// permutation's last FR_REM_MAX steps; what it takes from it is verified by k_block_exact like any prepared block.
-// ------------------------------------------------------------------------------------------------
-#ifndef PHI_FRESH_TABLES
-#define PHI_FRESH_TABLES 0     // r04 NEGATIVE RESULT, kept as a development build (-DPHI_FRESH_TABLES=1; scripts/build_variant.sh): see DESIGN.md 4.3
-#endif
-#define FR_RING 128            // fresh descriptors / tables (the tails of consecutive permutations are ~85 blocks apart)
-#define FR_W 2047              // entry gaps covered per side
-#define FR_WORDS 32            // 64-bit words of a side's table
-#ifndef FR_HELPERS
-#define FR_HELPERS 3
-#ifndef FR_ROUNDS
-#define FR_ROUNDS 2             // blocks per helper and post
-#endif
-#endif
-#define FR_TAIL 12             // candidates: the blocks before the expected end of the permutation
-#define FR_MAX_EV 2048         // events per side
-#define FR_REM_MAX 150000u     // the chain asks for a fresh table when at most this many steps of the permutation are left
-#define FR_POST_REM 120000u    // ... and posts the reference state for the NEXT permutation's tables when this many are left
-#ifndef FR_WINDOW
-#define FR_WINDOW 1.75         // window half-width in units of sqrt(draws since the reference state) (3.6 sigma)
-#endif
-
-struct FreshDesc {
-    unsigned long long G;      // guessed entry state
-    uint32_t cnt, i_in;        // accepts of the base trajectory, steps left in G's permutation
-    uint16_t w_pos, w_neg;     // covered entry gaps per side
-    uint32_t pad_;
-    unsigned long long ready;  // block index + 1 once the table is complete (release / acquire)
-};
-struct FreshCtl {
-    uint32_t seq, done;        // posts so far (chain), id of the last chain launch that has ended
-    unsigned long long post_b[2], post_S[2];   // [seq & 1]: a block boundary at which a permutation has just begun + its exact state
-    unsigned long long post_t[2];              // ... and the wall clock (100 MHz) of the post (diagnostics)
-    unsigned long long diag[9];                // diagnostics (scripts/generator_probe.py)
-};
-static_assert(sizeof(FreshDesc) == 32 && sizeof(FreshCtl) == 128, "fresh-table records");
-
-// Mean-field walk inside ONE permutation, in single precision with the fast intrinsics (a helper has ~5 us for all its
-// guesses; steps < 2^24 are exact in float, and a guess needs +-a few states): the steps left after q more draws from
-// `rem` steps left (0 when the permutation is over), and the draws until it is over.
-__device__ static uint32_t phi_rem_after(uint32_t rem, float q)
-{
-    float i = (float)rem;
-    for (int guard = 0; guard < 40 && q > 0.f && i >= 1.f; ++guard) {
-        const uint32_t m = mask_of((uint32_t)i);
-        const float top = (float)m + 1.f, lo = (float)((m >> 1) + 1);
-        const float need = top * __logf((i + 1.f) / lo);   // draws to leave the band
-        if (need <= q) { q -= need; i = lo - 1.f; }
-        else { i = (i + 1.f) * __expf(-q / top) - 1.f; q = 0.f; }
-    }
-    return q > 0.f || i < 1.f ? 0u : (uint32_t)(i + 0.5f);
-}
-__device__ static float phi_draws_to_finish(uint32_t rem)
-{
-    float q = 0.f, i = (float)rem;
-    for (int guard = 0; guard < 40 && i >= 1.f; ++guard) {
-        const uint32_t m = mask_of((uint32_t)i);
-        const float lo = (float)((m >> 1) + 1);
-        q += ((float)m + 1.f) * __logf((i + 1.f) / lo);
-        i = lo - 1.f;
-    }
-    return q;
-}
-
-__global__ __launch_bounds__(SCAN_THREADS) void k_fresh(const uint32_t *__restrict__ raw, uint64_t n_blocks, uint32_t n,
-                                                        uint64_t total_steps, double dpp, FreshCtl *__restrict__ ctl,
-                                                        FreshDesc *__restrict__ fdesc,
-                                                        unsigned long long *__restrict__ ftbits,
-                                                        const unsigned long long *__restrict__ st, uint32_t launch_id)
-{
-    __shared__ BlockShared sh;
-    __shared__ uint32_t shCmd, shSeq, shW, shIin;
-    __shared__ unsigned long long shB, shG, shBref, shSref, shE, shGs[FR_TAIL + 1];
-    __shared__ uint32_t wpk[SCAN_THREADS / 64];
-    __shared__ __align__(16) uint16_t evs[2][FR_MAX_EV];
-    __shared__ __align__(8) uint8_t tab[2][(FR_W + 1) / 8];
-    const uint32_t tau = threadIdx.x, lane = tau & 63, wave = tau >> 6;
-    const uint32_t M = n - 1, top_mask = mask_of(M);
-    uint32_t last = 0;
-    for (;;) {
-        if (tau == 0) {   // wait for a post newer than the last one served, the end of the chain launch, a failure or 1 s
-            uint32_t cmd = 0, seq = 0;
-            const long long t0 = wall_clock64();
-            for (;;) {
-                seq = __hip_atomic_load(&ctl->seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-                if (seq != last) break;
-                if (__hip_atomic_load(&ctl->done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) >= launch_id ||
-                    __hip_atomic_load(st + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull ||
-                    wall_clock64() - t0 > PHI_WAIT_TICKS) { cmd = 1; break; }
-                __builtin_amdgcn_s_sleep(8);
-            }
-            unsigned long long b_ref = 0, S_ref = total_steps;
-            if (!cmd) {
-                b_ref = ctl->post_b[seq & 1u]; S_ref = ctl->post_S[seq & 1u];
-                if (__hip_atomic_load(&ctl->seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != seq) S_ref = total_steps;   // (overwritten meanwhile: next round)
-            }
-            shCmd = cmd; shSeq = seq; shBref = b_ref; shSref = S_ref;
-        }
-        __syncthreads();
-        if (shCmd) return;
-        {   // the guesses of the last FR_TAIL + 1 blocks of this permutation, one lane each (a guess is a dozen logarithms)
-            const unsigned long long b_ref = shBref, S_ref = shSref;
-            if (tau <= FR_TAIL && S_ref < total_steps) {
-                const uint32_t rem_ref = M - (uint32_t)(S_ref % M);
-                // the post is from the END of a permutation (rem_ref steps left); the tables are for the end of the NEXT one
-                const float q_end = phi_draws_to_finish(rem_ref), q_perm = phi_draws_to_finish(M);
-                const unsigned long long e = b_ref + (unsigned long long)((q_end + q_perm) / (float)SCAN_BLOCK);
-                // cell k: block e + 1 - k; its guess = the next permutation's end minus the steps expected to be left there
-                const unsigned long long bk = e + 1 - tau;
-                unsigned long long Gk = ~0ull;
-                const float q = (float)(bk - b_ref) * (float)SCAN_BLOCK - q_end;   // draws into the next permutation
-                if (e + 1 >= b_ref + tau && q > 0.f) {
-                    const uint32_t left = phi_rem_after(M, q);
-                    Gk = S_ref + rem_ref + M - left;     // (left == 0: at or beyond that permutation's end)
-                }
-                shGs[tau] = Gk;
-                if (tau == 0) shE = e;
-            }
-        }
-        __syncthreads();
-        for (uint32_t round = 0; round < FR_ROUNDS; ++round) {   // this helper's blocks of the post, latest first
-        if (tau == 0) {
-            unsigned long long bsel = ~0ull, Gsel = 0;
-            uint32_t wsel = 0, isel = 0;
-            const unsigned long long b_ref = shBref, S_ref = shSref;
-            if (S_ref < total_steps) {
-                // the clean-looking blocks among the last FR_TAIL of this permutation; this helper takes the
-                // (blockIdx.x)-th from the END (the late ones are never prepared by the first tier)
-                const uint32_t rem_ref = M - (uint32_t)(S_ref % M);
-                const unsigned long long perm_end = S_ref + rem_ref + M, e = shE;   // (the end of the NEXT permutation)
-                uint32_t taken = 0;
-                for (uint32_t k = 0; k < FR_TAIL; ++k) {
-                    if (e < b_ref + k) break;
-                    const unsigned long long b = e - k;
-                    if (b + 1 >= n_blocks) continue;
-                    const unsigned long long G = shGs[k + 1], Gnext = shGs[k];   // blocks e - k and e - k + 1
-                    if (G == ~0ull || G >= perm_end || Gnext >= perm_end || Gnext + SCAN_BLOCK >= total_steps) continue;
-                    const double dq = (double)(b - b_ref) * (double)SCAN_BLOCK;
-                    const uint32_t i_in = (uint32_t)(perm_end - G), i_out = (uint32_t)(perm_end - Gnext);
-                    const double wd = FR_WINDOW * sqrt(dq) + 32.0;
-                    const uint32_t w = wd < (double)FR_W ? (uint32_t)wd : (uint32_t)FR_W;
-                    const uint32_t m = mask_of(i_in), low = (m >> 1) + 1;
-                    if (i_out < low + w / 4 || i_in > FR_REM_MAX + SCAN_BLOCK) continue;   // a band change inside (or too early)
-                    if (taken++ == blockIdx.x + FR_HELPERS * round) { bsel = b; Gsel = G; wsel = w; isel = i_in; break; }
-                }
-                if (bsel != ~0ull && __hip_atomic_load(&fdesc[bsel % FR_RING].ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == bsel + 1)
-                    bsel = ~0ull;   // prepared already (an earlier post of the same permutation)
-            }
-            shB = bsel; shG = Gsel; shW = wsel; shIin = isel;
-            atomicAdd(&ctl->diag[0], 1ull);                                  // diagnostics: rounds, blocks attempted,
-            if (bsel != ~0ull) atomicAdd(&ctl->diag[1], 1ull);               // ... ticks from the post to the start of the work
-            atomicAdd(&ctl->diag[2], (unsigned long long)wall_clock64() - ctl->post_t[shSeq & 1u]);
-        }
-        __syncthreads();
-        if (round == 0) last = shSeq;
-        const unsigned long long b = shB, G = shG;
-        const uint32_t w = shW, i_in = shIin;
-        __syncthreads();     // (everybody has read the cells thread 0 rewrites next time)
-        if (b == ~0ull) continue;
-        // ---- the base trajectory from the fresh guess, as k_phi_events does it ----
-        uint32_t u[SCAN_D];
-        scan_load(raw, b * SCAN_BLOCK, tau, u);
-        ScanRes r;
-        uint32_t excl = 0, total_cnt = 0, parity = 0;
-        bool easy = block_fixed_point(u, G, i_in, M, top_mask, total_steps, sh, parity, r, excl, total_cnt) == 0;
-        const uint32_t mask = mask_of(i_in);
-        const uint32_t cap = mask < M ? mask : M, low = (mask >> 1) + 1;
-        uint32_t w_pos = 0, w_neg = 0;
-        if (easy && i_in >= total_cnt + low) {
-            const uint32_t i_out = i_in - total_cnt;
-            w_pos = w < i_out - low ? w : i_out - low;
-            w_neg = w < cap - i_in ? w : cap - i_in;
-        } else easy = false;
-        uint32_t totP = 0, totN = 0, offP = 0, offN = 0;
-        {
-            uint32_t thr = i_in - excl, np = 0, nn = 0;
-            if (easy) {
-#pragma unroll
-                for (int s = 0; s < SCAN_D; ++s) {
-                    const int32_t d = (int32_t)(thr - (u[s] & mask));
-                    if (d >= 0) { np += ((uint32_t)d < w_pos) ? 1u : 0u; --thr; }
-                    else nn += ((uint32_t)(-d - 1) < w_neg) ? 1u : 0u;
-                }
-            }
-            const uint32_t pk = np | (nn << 16);
-            const uint32_t incl = wave_inclusive_scan(pk);
-            if (lane == 63) wpk[wave] = incl;
-            __syncthreads();
-            uint32_t before = 0, all = 0;
-#pragma unroll
-            for (int k = 0; k < SCAN_THREADS / 64; ++k) {
-                const uint32_t t = wpk[k];
-                before += (k < (int)wave) ? t : 0u;
-                all += t;
-            }
-            const uint32_t ex = before + incl - pk;
-            offP = ex & 0xffffu; offN = ex >> 16;
-            totP = all & 0xffffu; totN = all >> 16;
-        }
-        if (totP > FR_MAX_EV || totN > FR_MAX_EV) easy = false;   // (uniform: totals are the same in every thread)
-        if (easy) {
-            uint32_t thr = i_in - excl;
-#pragma unroll
-            for (int s = 0; s < SCAN_D; ++s) {
-                const int32_t dd = (int32_t)(thr - (u[s] & mask));
-                if (dd >= 0) { if ((uint32_t)dd < w_pos) evs[0][offP++] = (uint16_t)dd; --thr; }
-                else if ((uint32_t)(-dd - 1) < w_neg) evs[1][offN++] = (uint16_t)(-dd - 1);
-            }
-        }
-        __syncthreads();
-        if (tau == 0) atomicAdd(&ctl->diag[easy ? 3 : 4], 1ull);   // diagnostics: base trajectories clean / not clean
-        if (!easy) continue;   // (uniform)
-        const uint64_t slot = b % FR_RING;
-        if (tau == 0) {   // the slot's old table is void from here on
-            __hip_atomic_store(&fdesc[slot].ready, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __threadfence();
-        }
-        // ---- the table: every entry gap of the window walked through the side's events (draw order) ----
-        // thread (side, t) of the first eight wavefronts owns the gaps 8 t .. 8 t + 8; an event of slack s takes one step
-        // off every gap above s: all of the thread's gaps (a counter), none, or -- rarely -- some of them.  Events are
-        // read eight at a time (a dependent LDS read per event was most of the walk's time)
-        if (tau < 512) {
-            const uint32_t side = tau >> 8, t = tau & 255u;
-            const uint32_t nev = side ? totN : totP;
-            uint32_t a[9], off = 0;
-#pragma unroll
-            for (int k = 0; k <= 8; ++k) a[k] = 8u * t + k;
-            const uint4 *ev8 = reinterpret_cast<const uint4 *>(evs[side]);
-            for (uint32_t e0 = 0; e0 < nev; e0 += 8) {
-                const uint4 pk = ev8[e0 >> 3];
-                const uint32_t wds[4] = {pk.x, pk.y, pk.z, pk.w};
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    if (e0 + j < nev) {   // (uniform per side: all threads of a wavefront belong to one side)
-                        const uint32_t lim = ((wds[j >> 1] >> (16 * (j & 1))) & 0xffffu) + off;   // gap > slack  <=>  a > slack + off
-                        if (a[0] > lim) ++off;
-                        else if (a[8] > lim) {
-#pragma unroll
-                            for (int k = 0; k <= 8; ++k) a[k] -= (a[k] > lim) ? 1u : 0u;
-                        }
-                    }
-                }
-            }
-            uint32_t bits = 0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) bits |= (a[k + 1] - a[k]) << k;   // surviving increments (gaps move together: 0 or 1)
-            tab[side][t] = (uint8_t)bits;
-        }
-        __syncthreads();
-        if (tau < 2 * FR_WORDS) {   // 2 x 32 words of 64 bits
-            const uint32_t side = tau / FR_WORDS, wd = tau % FR_WORDS;
-            ftbits[(slot * 2 + side) * FR_WORDS + wd] = *reinterpret_cast<const unsigned long long *>(&tab[side][8 * wd]);
-        }
-        __threadfence();
-        __syncthreads();
-        if (tau == 0) {
-            FreshDesc d;
-            d.G = G; d.cnt = total_cnt; d.i_in = i_in; d.w_pos = (uint16_t)w_pos; d.w_neg = (uint16_t)w_neg; d.pad_ = 0; d.ready = 0;
-            FreshDesc *dst = fdesc + slot;
-            dst->G = d.G; dst->cnt = d.cnt; dst->i_in = d.i_in; dst->w_pos = d.w_pos; dst->w_neg = d.w_neg;
-            __hip_atomic_store(&dst->ready, (unsigned long long)b + 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            atomicAdd(&ctl->diag[5], (unsigned long long)wall_clock64() - ctl->post_t[last & 1u]);   // diagnostics: ticks from the post to "ready"
-        }
-        }   // rounds
-    }
-}
-
-// The chain's side: resolve block bx, entered with S, from its fresh table if there is one that covers S (every thread of
-// the workgroup evaluates it: S stays uniform).  Returns false when there is none.
-// ready_known: the caller has seen ready == bx + 1 already (a relaxed load issued long before): only the acquire fence is
-// needed.  (A slot is rewritten only for a block FR_RING further on, i.e. after the chain has passed this one: no re-check.)
-__device__ __forceinline__ bool fresh_lookup(const FreshDesc *__restrict__ fdesc, const unsigned long long *__restrict__ ftbits,
-                                             uint64_t bx, uint64_t &S, uint32_t &rem, bool ready_known)
-{
-    const uint64_t slot = bx % FR_RING;
-    const FreshDesc *fd = fdesc + slot;
-    if (ready_known) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    else if (__hip_atomic_load(&fd->ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != bx + 1) return false;
-    const unsigned long long G = fd->G;
-    const uint32_t cnt = fd->cnt, i_in = fd->i_in, w_pos = fd->w_pos, w_neg = fd->w_neg;
-    const int64_t g = (int64_t)S - (int64_t)G;
-    const bool neg = g < 0;
-    const uint64_t idx = (uint64_t)(neg ? -g : g);
-    if (idx > (neg ? w_neg : w_pos)) return false;
-    uint32_t T = 0;
-    if (idx) {
-        const uint32_t lane = threadIdx.x & 63;
-        uint32_t c = 0;
-        if (lane < FR_WORDS && (uint64_t)lane * 64u < idx) {
-            const unsigned long long wd = ftbits[(slot * 2 + (neg ? 1 : 0)) * FR_WORDS + lane];
-            const uint32_t d = (uint32_t)idx - lane * 64u;
-            c = (uint32_t)__popcll(wd & sc_low_mask64(d < 64u ? d : 64u));
-        }
-        T = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan(c), 63);
-    }
-    S = G + cnt + (unsigned long long)(neg ? -(long long)T : (long long)T);
-    rem = i_in - (uint32_t)(S - G);
-    return true;
-}
-
 // Chain the exact states through blocks [b0, b1) (one workgroup): a SEGMENT of prepared blocks costs one lookup in
 // its (composed) table, which every thread evaluates for itself from LDS; the other blocks the full in-block fixed
 // point.  While a block is computed, the draws of the next block to compute and the tables of the run of segments
@@ -1711,16 +1129,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chain(const uint32_t *__restri
                                                         bits_t *__restrict__ acc_bits, uint32_t *__restrict__ enter,
                                                         unsigned long long *__restrict__ sblk,
                                                         unsigned long long *__restrict__ st, uint32_t *__restrict__ flags,
-                                                        uint32_t unit0, FreshCtl *__restrict__ fctl /* + descriptors + tables */,
-                                                        uint32_t launch_id)
+                                                        uint32_t unit0)
 {
     __shared__ BlockShared sh;
-#if PHI_TAIL_LDS
-    __shared__ TailShared tsh;
-    TailShared *const tshp = &tsh;
-#else
-    TailShared *const tshp = nullptr;
-#endif
     __shared__ uint32_t shReady;
     __shared__ __align__(8) PhiSeg sg[PHI_UNIT];
     __shared__ uint16_t nxt[PHI_UNIT + 2];  // first block >= i (relative to b0) the chain computes itself
@@ -1734,36 +1145,18 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chain(const uint32_t *__restri
     const uint32_t M = n - 1, top_mask = mask_of(M);
     uint64_t S = st[0];
     if (S >= total_steps || st[1] != B0 || B1 > n_blocks) {  // job complete, or an earlier launch gave up (uniform)
-        if (tau == 0) {
-            __hip_atomic_store(flags, 0xffffffffu, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);  // no gate waits for us
-            if (fctl) __hip_atomic_store(&fctl->done, launch_id, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);   // nor k_fresh
-        }
+        if (tau == 0) __hip_atomic_store(flags, 0xffffffffu, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);  // no gate waits for us
         return;
-    }
-    // the exact state S_ at the boundary IN FRONT OF block bx_, the first one seen with at most FR_POST_REM steps of the
-    // current permutation left: the reference for the fresh tables of the NEXT permutation's end (k_fresh has a whole
-    // permutation of chain time, ~100 us, to build them; the uncertainty grows only with the square root of the distance)
-#define PHI_POST(bx_, S_)                                                                                     \
-    if (fctl && tau == 0 && !cn[6]) {                                                                         \
-        cn[6] = 1;                                                                                            \
-        const uint32_t ps_ = ++cn[5];                                                                         \
-        fctl->post_b[ps_ & 1u] = (bx_);                                                                       \
-        fctl->post_S[ps_ & 1u] = (S_);                                                                        \
-        fctl->post_t[ps_ & 1u] = (unsigned long long)wall_clock64();                                          \
-        __hip_atomic_store(&fctl->seq, ps_, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);                      \
     }
     uint32_t parity = 0;
     int failed = 0;
     __shared__ unsigned long long shEnd;   // (raw position of the job's last step, seen by at most one thread of one launch)
     if (tau == 0) shEnd = 0;
     // counters of thread 0 live in LDS (the kernel sits at its 128-VGPR cap): [0] blocks by lookup, [1] computed, [2] segment
-    // lookups, [3] slow paths, [4] blocks by fresh table, [5] posts to k_fresh
-    __shared__ uint32_t cn[7];   // ... [6] the current permutation has been posted
-    if (tau < 7) cn[tau] = tau == 5 && fctl ? fctl->seq : 0u;
+    // lookups, [3] slow paths
+    __shared__ uint32_t cn[7];   // ([4] .. [6] served the fresh-table variant and stay zero: the kernel's LDS layout is unchanged)
+    if (tau < 7) cn[tau] = 0u;
     __syncthreads();
-#ifdef PHI_PROFILE
-    unsigned long long pf_easy = 0, pf_hard = 0;
-#endif
     uint32_t rem = M - (uint32_t)(S % M);  // steps left in the current permutation, carried along from here
     uint64_t b_next = B0;
     // one launch chains several launch units (each prepared by its own launches; the host waited for all of them)
@@ -1774,23 +1167,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chain(const uint32_t *__restri
     const uint64_t b1 = b0 + PHI_UNIT < B1 ? b0 + PHI_UNIT : B1;
     const uint32_t nb = (uint32_t)(b1 - b0);
     __syncthreads();  // the previous unit's readers of sg / nxt / tl are done
-#ifdef PHI_PROFILE
-    const long long pf_w0 = clock64();
-#endif
     if (tau == 0) shReady = (uint32_t)phi_wait_at_least(flags + 1 + unit % PHI_FLAG_SLOTS, unit + 1, st);
     __syncthreads();
-#ifdef PHI_PROFILE
-    if (tau == 0) {   // waiting for the unit's preparation: total, units that waited > 20 us, longest wait
-        const unsigned long long wt = (unsigned long long)(clock64() - pf_w0);
-        atomicAdd(&g_phi_prof[20], wt);
-        if (wt > 40000ull) {
-            const unsigned long long k = atomicAdd(&g_phi_prof[30], 1ull);
-            atomicAdd(&g_phi_prof[19], wt);
-            if (k < 128) { g_phi_prof[32 + 2 * k] = (unsigned long long)unit | ((unsigned long long)unit0 << 32); g_phi_prof[33 + 2 * k] = wt; }
-        }
-        atomicMax(&g_phi_prof[31], wt);
-    }
-#endif
     if (shReady) { gave_up = (int)shReady; break; }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // the unit's descriptors and tables, written by other kernels
     if (tau < nb) sg[tau] = seg[(b0 + tau) % PHI_RING];
@@ -1819,17 +1197,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chain(const uint32_t *__restri
     ulonglong2 treg;
     uint32_t un[SCAN_D];
     uint32_t rel = 0, h = nxt[0];   // rel: next block to resolve; h: the next block the chain computes itself (>= rel)
-    // the "ready" word (low half: block + 1) of block h's fresh table, asked for as soon as h is known -- one item (a
-    // fixed point, microseconds) before it is looked at: a table that is not there then costs nothing
-#if PHI_FRESH_TABLES
-#define PHI_FRESH_ASK(hh)                                                                                                    \
-    fr_ready = (fctl && (hh) < nb) ? __hip_atomic_load(reinterpret_cast<const uint32_t *>(                                   \
-                   &reinterpret_cast<const FreshDesc *>(fctl + 1)[(b0 + (hh)) % FR_RING].ready), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-    uint32_t fr_ready;
-#else
-#define PHI_FRESH_ASK(hh)
-#endif
-    PHI_FRESH_ASK(h)
     PHI_STAGE_LOAD(rel)
     if (h < nb) scan_load(raw, (b0 + h) * SCAN_BLOCK, tau, un);
     for (;;) {
@@ -1840,9 +1207,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chain(const uint32_t *__restri
             if (tau < PHI_NS * 2 * PHI_STAGE_PIECES) { tl[tau] = treg; tpre[tau] = upto - ones; }
         }
         __syncthreads();
-#ifdef PHI_PROFILE
-        const long long pf_t0 = clock64();
-#endif
         // ---- the staged segments, one lookup each, by wavefront 0 (sixteen wavefronts doing the same ~60 dependent
         // instructions take turns on the four SIMDs: four times the clocks of one) ----
         if (wave == 0) {
@@ -1872,24 +1236,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chain(const uint32_t *__restri
                 if (tau == 0) { cn[0] += sq.len; ++cn[2]; }
                 rel += sq.len;
             }
-            // ... and behind them a block the chain would compute itself: at the end of a permutation a FRESH table may
-            // cover it (k_fresh; wavefront 0 alone evaluates it: the lookup's registers are not live in the fixed point)
-#if PHI_FRESH_TABLES
-            while (fctl && !miss0 && rel < nb && sg[rel].kind == 0 && rem <= FR_REM_MAX && (rel != h || fr_ready == (uint32_t)(b0 + rel + 1))) {
-                const uint64_t S_in = S;
-                if (tau == 0) {   // diagnostics: lookups tried, ticks since the last post, how far its block is from the slot's
-                    atomicAdd(&fctl->diag[6], 1ull);
-                    atomicAdd(&fctl->diag[7], (unsigned long long)wall_clock64() - fctl->post_t[cn[5] & 1u]);
-                    const unsigned long long rd = reinterpret_cast<const FreshDesc *>(fctl + 1)[(b0 + rel) % FR_RING].ready;
-                    if (rd == b0 + rel + 1) atomicAdd(&fctl->diag[8], 1ull);   // a table for exactly this block exists
-                }
-                if (!fresh_lookup(reinterpret_cast<const FreshDesc *>(fctl + 1),
-                                  reinterpret_cast<const unsigned long long *>(reinterpret_cast<const FreshDesc *>(fctl + 1) + FR_RING),
-                                  b0 + rel, S, rem, rel == h)) break;
-                if (tau == 0) { sblk[b0 + rel] = S_in; hardmask[b0 + rel] = 0; ++cn[0]; ++cn[4]; }
-                ++rel;
-            }
-#endif
             if (tau == 0) { shS = S; shRem = rem; shRel = rel | (miss0 ? 0x80000000u : 0u); }
         }
         __syncthreads();
@@ -1897,17 +1243,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chain(const uint32_t *__restri
         rem = shRem;
         rel = shRel & 0x7fffffffu;
         const bool miss = (shRel >> 31) != 0;
-#if PHI_FRESH_TABLES
-        if (rem <= FR_POST_REM) PHI_POST(b0 + rel, S)
-#endif
-        if (rel > h) {   // a fresh table resolved the block whose draws were prefetched: the next one to compute, then
+        if (rel > h) {   // the block whose draws were prefetched is behind us: the next one to compute, then
             h = nxt[rel];
             if (h < nb) scan_load(raw, (b0 + h) * SCAN_BLOCK, tau, un);
-            PHI_FRESH_ASK(h)
         }
-#ifdef PHI_PROFILE
-        const long long pf_ts = clock64();
-#endif
         if (miss) {
             // The entry state lies outside the segment's window (a band edge narrowed it, or the guess was far off):
             // its blocks one by one -- the per-block tables from global memory where they cover the state, the fixed
@@ -1926,7 +1265,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chain(const uint32_t *__restri
                     rem = d.i_in - (uint32_t)(S - d.G);
                     if (tau == 0) ++cn[0];
                 } else {
-                    // (a fresh table is not consulted here: a second inlined copy of the lookup made the kernel spill)
                     uint32_t u[SCAN_D];
                     scan_load(raw, bx * SCAN_BLOCK, tau, u);
                     ScanRes r;
@@ -1937,30 +1275,16 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chain(const uint32_t *__restri
                     if (tau == 0) { sblk[bx] = S; hardmask[bx] = 1; }
                     if (r.end) shEnd = bx * SCAN_BLOCK + (uint64_t)tau * SCAN_D + r.end;
                     S += total_cnt;
-                    const uint32_t rem_new = rem_advance(rem, total_cnt, M);
-#if PHI_FRESH_TABLES
-                    if (rem_new > rem && tau == 0) cn[6] = 0;   // a new permutation: not posted yet
-#endif
-                    rem = rem_new;
+                    rem = rem_advance(rem, total_cnt, M);
                     if (tau == 0) ++cn[1];
                 }
             }
             if (tau == 0) { segmode[b0 + first] = 2; ++cn[3]; }   // k_seg_fill has nothing to add here
-#ifdef PHI_PROFILE
-            if (tau == 0) { atomicAdd(&g_phi_prof[21], (unsigned long long)(clock64() - pf_ts)); atomicAdd(&g_phi_prof[22], 1ull); }
-#endif
             if (failed || S >= total_steps) break;
         }
-#ifdef PHI_PROFILE
-        const long long pf_t1 = clock64();
-        pf_easy += (unsigned long long)(pf_t1 - pf_t0);
-#endif
         if (rel >= nb) { rel = nb; break; }
         if (sg[rel].kind == 1) {   // the run goes on (more segments than staged at once, or behind a slow path)
             PHI_STAGE_LOAD(rel)
-#ifdef PHI_PROFILE
-            if (tau == 0) atomicAdd(&g_phi_prof[23], 1ull);   // exposed table loads
-#endif
             continue;
         }
         // ---- block rel: computed by the chain itself ----
@@ -1976,39 +1300,17 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chain(const uint32_t *__restri
         // on their way while block x is computed: the tables of the run behind it and the draws of the block after that
         PHI_STAGE_LOAD(x + 1)
         if (x == h && hN < nb) scan_load(raw, (b0 + hN) * SCAN_BLOCK, tau, un);
-        PHI_FRESH_ASK(hN)     // (for the block after this one; this block's word has been used)
         ScanRes r;
         uint32_t excl, total_cnt;
-#ifdef PHI_PROFILE
-        const uint32_t pf_rem = rem;
-        int pf_rounds = 0;
-        if (block_fixed_point<PHI_TAIL>(u, S, rem, M, top_mask, total_steps, sh, parity, r, excl, total_cnt, &pf_rounds, tshp) > 0) { failed = 1; break; }
-        if (tau == 0) {   // computed blocks by the steps left in their permutation: count, clocks of the fixed point, rounds
-            const int cls = pf_rem > 98304u ? 0 : pf_rem > 49152u ? 1 : pf_rem > 24576u ? 2 : pf_rem > 12288u ? 3 : 4;
-            atomicAdd(&g_phi_prof[cls * 4], 1ull);
-            atomicAdd(&g_phi_prof[cls * 4 + 1], (unsigned long long)(clock64() - pf_t1));
-            atomicAdd(&g_phi_prof[cls * 4 + 2], (unsigned long long)pf_rounds);
-        }
-#else
-        if (block_fixed_point<PHI_TAIL>(u, S, rem, M, top_mask, total_steps, sh, parity, r, excl, total_cnt, nullptr, tshp) > 0) { failed = 1; break; }
-#endif
+        if (block_fixed_point(u, S, rem, M, top_mask, total_steps, sh, parity, r, excl, total_cnt) > 0) { failed = 1; break; }
         const uint64_t bx = b0 + x;
         acc_bits[bx * SCAN_THREADS + tau] = r.bits;
         enter[bx * SCAN_THREADS + tau] = excl;
         if (tau == 0) { sblk[bx] = S; hardmask[bx] = 1; }
         if (r.end) shEnd = bx * SCAN_BLOCK + (uint64_t)tau * SCAN_D + r.end;
         S += total_cnt;
-        {
-            const uint32_t rem_new = rem_advance(rem, total_cnt, M);
-#if PHI_FRESH_TABLES
-            if (rem_new > rem && tau == 0) cn[6] = 0;   // a new permutation: not posted yet
-#endif
-            rem = rem_new;
-        }
+        rem = rem_advance(rem, total_cnt, M);
         if (tau == 0) ++cn[1];
-#ifdef PHI_PROFILE
-        pf_hard += (unsigned long long)(clock64() - pf_t1);
-#endif
         rel = x + 1;
         h = hN;
         if (S >= total_steps) break;
@@ -2020,20 +1322,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chain(const uint32_t *__restri
     }
     }  // units
 #undef PHI_STAGE_LOAD
-#undef PHI_FRESH_ASK
-#undef PHI_POST
     __syncthreads();
     if (tau == 0) {
         if (shEnd) st[3] = shEnd;
         const uint64_t b = b_next;
         st[0] = S;
         st[1] = b;
-#ifdef PHI_PROFILE
-        st[6] += (pf_easy >> 6) | ((pf_hard >> 6) << 32);   // clocks / 64 of thread 0: lookup phases, computed blocks
-#else
         st[6] += cn[2];   // segment lookups
-#endif
-        st[7] += (unsigned long long)cn[3] | ((unsigned long long)cn[4] << 32);  // segments whose window missed the entry state | blocks resolved by a fresh table
+        st[7] += (unsigned long long)cn[3] | ((unsigned long long)cn[4] << 32);  // segments whose window missed the entry state (high half: zero)
         st[4] += cn[0];
         st[5] += cn[1];
         sblk[b] = S;  // entry state of the next block (sblk holds n_blocks + 1 entries)
@@ -2044,7 +1340,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_chain(const uint32_t *__restri
         if (f) atomicOr(st + 2, f);
         if (f || gave_up || S >= total_steps)  // nothing more will come from the chain: release every gate
             __hip_atomic_store(flags, 0xffffffffu, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        if (fctl) __hip_atomic_store(&fctl->done, launch_id, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);   // k_fresh of this launch ends
     }
 }
 
@@ -2136,9 +1431,7 @@ __global__ __launch_bounds__(64) void k_apply_swaps(const int32_t *__restrict__ 
 // keyed by the target: CAS insert with linear probing, minimum step index per key).  The longest prefix without
 // such a pair is applied in parallel; the round trip to L2 that bounds a round is paid once per ~SW_T steps.
 #define SW_T 512
-#ifndef SWAPS_WG_MIN_N
 #define SWAPS_WG_MIN_N 65536  // shorter permutations: conflicts are frequent, one wavefront per permutation is enough
-#endif
 #define SW_HASH 2048
 
 // ASC = false: the shuffle itself (steps i = n-1 .. 1), the table numpy returns.
@@ -2151,9 +1444,8 @@ __global__ __launch_bounds__(64) void k_apply_swaps(const int32_t *__restrict__ 
 // rounds do; only WHICH steps a round holds does, by up to SW_T), so a round's memory latency is one dependent access
 // (the values at the partners' slots) instead of two; (ii) in the ascending mode a step's own slot has never been touched
 // when its turn comes (every earlier step i' < i writes slots <= i'), so its value is i itself: no load, and no identity
-// fill of the row beyond slot 0.  -DSW_NO_PREFETCH: the r02 form (A/B builds).
+// fill of the row beyond slot 0.
 #define SW_RING 2048   // partners of steps [done, done + <= 1536) live here
-
 
 // r04: PW permutations per workgroup (PW x SW_T threads, each SW_T-thread half runs its own permutation with its own LDS
 // structures, the barriers are shared: a round is latency-bound, two of them in lockstep cost what one costs).  Why: a
@@ -2167,21 +1459,16 @@ __global__ __launch_bounds__(SW_T * PW) void k_apply_swaps_wg(const int32_t *__r
     __shared__ uint32_t hkey_[PW][SW_HASH], hmin_[PW][SW_HASH];
     __shared__ uint32_t first_conf_[PW][2];
     __shared__ uint32_t act[2];
-#ifndef SW_NO_PREFETCH
     __shared__ int32_t jring_[PW][SW_RING];
-#endif
     const uint32_t half = PW > 1 ? threadIdx.x / SW_T : 0u;
     const uint32_t l = PW > 1 ? threadIdx.x % SW_T : threadIdx.x;
     uint32_t *hkey = hkey_[half], *hmin = hmin_[half], *first_conf = first_conf_[half];
-#ifndef SW_NO_PREFETCH
     int32_t *jring = jring_[half];
-#endif
     const int64_t p = p0 + (int64_t)blockIdx.x * PW + half;
     const bool exists = p < n_perm;          // (an odd chunk: the last workgroup's second half has nothing to do but meet the barriers)
     const uint32_t M = n - 1;
     int32_t *A = perm + (exists ? p : p0) * pstride;
     const int32_t *Jp = J + (exists ? p : p0) * (int64_t)M;
-#ifndef SW_NO_PREFETCH
     // step k = 0 .. M - 1 of the processing order: i = 1 + k (ascending) or n - 1 - k; its partner is Jp[M - i]
     auto step_i = [&](int64_t k) -> int64_t { return ASC ? 1 + k : (int64_t)n - 1 - k; };
     if (exists) {
@@ -2193,9 +1480,6 @@ __global__ __launch_bounds__(SW_T * PW) void k_apply_swaps_wg(const int32_t *__r
         }
     }
     int64_t filled = 2 * SW_T;      // partners of steps [done, filled) are in the ring
-#else
-    if (exists) for (uint32_t x = l; x < n; x += SW_T) A[x] = (int32_t)x;
-#endif
     int64_t i_cur = ASC ? 1 : (int64_t)n - 1;  // first step of the round
     if (!exists) i_cur = ASC ? (int64_t)n : 0; // (done)
     if (l < 2) first_conf[l] = SW_T;
@@ -2208,7 +1492,6 @@ __global__ __launch_bounds__(SW_T * PW) void k_apply_swaps_wg(const int32_t *__r
     while (act[0] | act[1]) {       // (uniform: the words are rewritten in front of the round's last barrier)
         const int64_t i = ASC ? i_cur + l : i_cur - l;
         const bool valid = exists && (ASC ? (i_cur <= (int64_t)n - 1 && i <= (int64_t)n - 1) : (i_cur >= 1 && i >= 1));
-#ifndef SW_NO_PREFETCH
         const int64_t done = ASC ? i_cur - 1 : (int64_t)n - 1 - i_cur;   // steps applied so far
         int32_t j = valid ? jring[(done + l) & (SW_RING - 1)] : -1;
         // the ring's next SW_T partners are on their way while this round works (stored at its end)
@@ -2216,17 +1499,10 @@ __global__ __launch_bounds__(SW_T * PW) void k_apply_swaps_wg(const int32_t *__r
         const int64_t kf = filled + l;
         int32_t j_next = -1;
         if (top_up && kf < (int64_t)M) j_next = Jp[(int64_t)M - step_i(kf)];
-#else
-        int32_t j = valid ? Jp[(int64_t)M - i] : -1;
-#endif
         if (valid && (uint32_t)j > (uint32_t)i) j = (int32_t)i;  // never index outside [0, i], whatever J holds
         int32_t a_i = 0, a_j = 0;
         if (valid) {  // L1 is bypassed: the values the previous round stored are in L2 (vmcnt wait + barrier)
-#ifndef SW_NO_PREFETCH
             a_i = ASC ? (int32_t)i : __hip_atomic_load(&A[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-            a_i = __hip_atomic_load(&A[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
             a_j = (ASC && j == (int32_t)i) ? a_i : __hip_atomic_load(&A[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
 #pragma unroll
@@ -2262,9 +1538,7 @@ __global__ __launch_bounds__(SW_T * PW) void k_apply_swaps_wg(const int32_t *__r
             A[i] = a_j;
             if (j != (int32_t)i) A[j] = a_i;
         }
-#ifndef SW_NO_PREFETCH
         if (top_up) { jring[kf & (SW_RING - 1)] = j_next; filled += SW_T; }   // (uniform per half; slots of steps already applied)
-#endif
         i_cur += ASC ? (int64_t)count : -(int64_t)count;
         ++round;
         if (l == 0) act[half] = (exists && (ASC ? i_cur <= (int64_t)n - 1 : i_cur >= 1)) ? 1u : 0u;
@@ -2338,17 +1612,8 @@ __global__ __launch_bounds__(SF_T) void k_apply_swaps_full(const int32_t *__rest
     auto last_lt = [](uint32_t mn, uint32_t mx1, uint32_t k) -> uint32_t {
         return (mx1 != 0u && mx1 - 1u < k) ? mx1 - 1u : (mn < k ? mn : SF_NONE);
     };
-#ifdef SF_PROFILE
-    long long pf[6] = {0, 0, 0, 0, 0, 0};
-#define SF_MARK(x) { const long long t_ = clock64(); pf[x] += t_ - pf_t; pf_t = t_; }
-#else
-#define SF_MARK(x)
-#endif
     uint32_t round = 0;
     while (done < M) {
-#ifdef SF_PROFILE
-        long long pf_t = clock64();
-#endif
         const uint32_t i_cur = ASC ? 1u + done : n - 1u - done;   // the round's first step
         const uint32_t left = M - done;
         const uint32_t nvalid = left < SF_T ? left : SF_T;
@@ -2381,7 +1646,6 @@ __global__ __launch_bounds__(SF_T) void k_apply_swaps_full(const int32_t *__rest
             if (t < SF_T) { atomicMin(&omin[t], l); atomicMax(&omax[t], l + 1u); }
         }
         sf_lds_barrier();
-        SF_MARK(0)
         // ---- hazards: middle steps end the round; every step finds where its two values come from ----
         uint32_t mn = SF_NONE, mx1 = 0u, imn = SF_NONE, imx1 = 0u;   // of the key j / of the key i (my own slot as somebody's partner)
         uint32_t myptr = SF_NONE, p2 = SF_NONE;
@@ -2408,7 +1672,6 @@ __global__ __launch_bounds__(SF_T) void k_apply_swaps_full(const int32_t *__rest
         }
         if (l == 0) { first_conf[(round + 1) & 1] = SF_T; chains[(round + 1) & 1] = 0u; }
         sf_lds_barrier();
-        SF_MARK(1)
         uint32_t count = *fc;
         if (count > nvalid) count = nvalid;
         // chains: a step takes the value of an earlier one, which may itself be waiting (rare; usually no pointer at all;
@@ -2424,7 +1687,6 @@ __global__ __launch_bounds__(SF_T) void k_apply_swaps_full(const int32_t *__rest
                 if (!pending) break;
             }
         }
-        SF_MARK(2)
         if (valid && l < count) {
             const uint32_t my_last = (mx1 != 0u && mx1 - 1u < count) ? mx1 - 1u : (mn < count ? mn : SF_NONE);   // last processed step of key j
             if (!ASC) {
@@ -2446,12 +1708,7 @@ __global__ __launch_bounds__(SF_T) void k_apply_swaps_full(const int32_t *__rest
         done += count;
         ++round;
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        SF_MARK(3)
     }
-#ifdef SF_PROFILE
-    if (blockIdx.x == 0 && (l == 0 || l == 1000)) printf("swaps_full thread %u: %u rounds; clocks per round: loads issued + insert + barrier %lld, hazards + values + barrier %lld, chains %lld, stores + clear + wait + barrier %lld\n",
-                                  l, round, pf[0] / round, pf[1] / round, pf[2] / round, pf[3] / round);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2515,21 +1772,9 @@ int permgen_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, 
         SC_TRY(c->pg_ctbits.ensure(sizeof(unsigned long long) * (size_t)PHI_RING * 2 * PHI_WORDS, &c->mem));
         SC_TRY(c->pg_segmode.ensure((size_t)n_blocks + 1, &c->mem));
         SC_TRY(c->pg_seglist.ensure(sizeof(uint32_t) * (size_t)PHI_FLAG_SLOTS * (1 + PHI_UNIT), &c->mem));
-        // fresh tables: [control | descriptors | tables]
-        SC_TRY(c->pg_fresh.ensure(sizeof(FreshCtl) + sizeof(FreshDesc) * FR_RING + sizeof(unsigned long long) * FR_RING * 2 * FR_WORDS, &c->mem));
-        SC_HIP(hipMemsetAsync(c->pg_fresh.p, 0, sizeof(FreshCtl) + sizeof(FreshDesc) * FR_RING, s));
-        if (!c->stream_fr) SC_HIP(hipStreamCreateWithFlags(&c->stream_fr, hipStreamNonBlocking));
         SC_HIP(hipMemsetAsync(c->pg_segmode.p, 0, (size_t)n_blocks + 1, s));
-        int prio_lo = 0, prio_hi = 0;  // the generator is the critical path of its callers (plain streams if refused)
-        const bool prio = getenv("SC_STREAM_PRIORITY") && hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) == hipSuccess;
-        for (hipStream_t &sp : c->stream_pg) {
-            if (sp) continue;
-            if (!prio || hipStreamCreateWithPriority(&sp, hipStreamNonBlocking, prio_hi) != hipSuccess) {
-                (void)hipGetLastError();
-                sp = nullptr;
-                SC_HIP(hipStreamCreateWithFlags(&sp, hipStreamNonBlocking));
-            }
-        }
+        for (hipStream_t &sp : c->stream_pg)
+            if (!sp) SC_HIP(hipStreamCreateWithFlags(&sp, hipStreamNonBlocking));
     }
     for (hipEvent_t &e : c->pg_ev)
         if (!e) SC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -2637,24 +1882,12 @@ int permgen_scan_chunk(sc_ctx *c, PermJob *job, int64_t p1, hipStream_t s, hipSt
             job->B_done = b1;
             job->unit_no = u + 1;
         }
-        // the fresh-table helpers of this chain launch (their own stream; they end with the chain launch)
-        static const bool no_fresh = !PHI_FRESH_TABLES || getenv("SC_NO_FRESH") != nullptr;   // development build only; A/B switch
-        FreshCtl *fctl = no_fresh ? nullptr : reinterpret_cast<FreshCtl *>(c->pg_fresh.p);
-        FreshDesc *fdesc = no_fresh ? nullptr : reinterpret_cast<FreshDesc *>(reinterpret_cast<char *>(c->pg_fresh.p) + sizeof(FreshCtl));
-        unsigned long long *ftbits = no_fresh ? nullptr : reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(fdesc) + sizeof(FreshDesc) * FR_RING);
-        const uint32_t launch_id = (uint32_t)job->chunk_no + 1;
-        if (fctl) {
-            if (job->chunk_no == 0) SC_HIP(hipStreamWaitEvent(c->stream_fr, c->pg_ev[32], 0));   // (the raw stream and the zeroed control block)
-            hipLaunchKernelGGL(k_fresh, dim3(FR_HELPERS), dim3(SCAN_THREADS), 0, c->stream_fr, c->pg_raw.as<uint32_t>(), n_blocks,
-                               (uint32_t)job->n, job->total_steps, job->draws_per_perm, fctl, fdesc, ftbits, st, launch_id);
-        }
         hipLaunchKernelGGL(k_chain, dim3(1), dim3(SCAN_THREADS), 0, s, c->pg_raw.as<uint32_t>(), n_blocks,
                            (uint32_t)job->n, job->total_steps, g0, B_end, target,
                            c->pg_desc.as<PhiDesc>(), c->pg_tbits.as<unsigned long long>(), c->pg_seg.as<PhiSeg>(),
                            c->pg_ctbits.as<unsigned long long>(), c->pg_hard.as<uint8_t>(), c->pg_segmode.as<uint8_t>(),
                            (c->pg_mode == 2 && u_first == 0) ? 1 : 0, c->pg_bits.as<bits_t>(),
-                           c->pg_enter.as<uint32_t>(), c->pg_sblk.as<unsigned long long>(), st, flags, (uint32_t)u_first,
-                           fctl, launch_id);
+                           c->pg_enter.as<uint32_t>(), c->pg_sblk.as<unsigned long long>(), st, flags, (uint32_t)u_first);
         SC_HIP(hipGetLastError());
         // the verification / expansion of this chunk reads the entry states k_seg_fill leaves on the preparation streams
         for (unsigned q = 0; q < PHI_STREAMS; ++q)
@@ -2922,7 +2155,6 @@ static int perm_generate_once(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_
     SC_HIP(hipStreamSynchronize(c->stream));
     for (hipStream_t sp : c->stream_pg)
         if (sp) SC_HIP(hipStreamSynchronize(sp));
-    if (c->stream_fr) SC_HIP(hipStreamSynchronize(c->stream_fr));
     return permgen_finish(c, &job, state6);
 }
 

@@ -73,6 +73,24 @@ def test_product_never_imports_the_oracle():
     assert not bad, bad
 
 
+def test_native_code_reads_only_the_documented_environment_and_has_no_compiled_out_variants():
+    """The environment variables the native library reads are the four DESIGN.md lists, and the development variants that
+    were removed from sc_permgen.hip (clock-counter profiles, the r03 scan paths, the lane tail solver, the fresh tables)
+    do not come back as preprocessor arms."""
+    csrc = os.path.join(ROOT, "spatialcore_amd", "csrc")
+    variant = re.compile(r"^\s*#\s*if(n?def)?\s+.*\b(PHI_PROFILE|SF_PROFILE|SCAN_R03_PATHS|PHI_TAIL|PHI_FRESH_TABLES)\b")
+    names, arms = set(), []
+    sources = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert len(sources) >= 11
+    for f in sources:
+        text = open(os.path.join(csrc, f)).read()
+        names |= set(re.findall(r"getenv\(\s*\"([^\"]*)\"\s*\)", text))
+        assert len(re.findall(r"\bgetenv\b", text)) == len(re.findall(r"getenv\(\s*\"[^\"]*\"\s*\)", text)), f"{f}: getenv of a computed name"
+        arms += [f"{f}:{k + 1}: {line}" for k, line in enumerate(text.split("\n")) if variant.match(line)]
+    assert names == {"SC_SWAP_PW", "SC_SWAP_FULL_ROUNDS", "SC_LM_FLOAT_ROWS", "GPU_MAX_HW_QUEUES"}
+    assert not arms, arms
+
+
 def test_host_permutation_generator_matches_numpy():
     from spatialcore_amd import _lib
 
