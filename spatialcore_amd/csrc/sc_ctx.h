@@ -234,6 +234,7 @@ int permgen_scan_chunk(sc_ctx *c, PermJob *job, int64_t p1, hipStream_t s, hipSt
 int permgen_swap_chunk(sc_ctx *c, PermJob *job, int64_t p0, int64_t p1, hipStream_t s, bool inverse, int pw_req);
 bool permgen_can_swap_inverse(int64_t n);
 int sc_perm_forward_ensure(sc_ctx *c);  // materialise c->perm from c->inv after a pipeline that only made the inverse
+int sc_perm_table_is_bijective(sc_ctx *c, int64_t n_perm, bool *bijective);   // inverse rows of an uploaded table + the check
 int invert_rows(sc_ctx *c, int64_t p0, int64_t p1, hipStream_t s);   // inverse rows [p0, p1) of the active table on stream s
 int permgen_finish(sc_ctx *c, PermJob *job, uint64_t *state6);
 int sc_perm_alloc(sc_ctx *c, int64_t n, int64_t n_perm);
@@ -256,8 +257,18 @@ int sc_perm_pipeline(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_perm, int
 int permgen_rerun_on_failure(sc_ctx *c, const std::function<int()> &attempt, const std::function<int()> &undo);
 
 int sc_timer_collect(sc_ctx *c);
+// ---- expression tiles (sc_expr.hip), all enqueued on c->stream ----
+enum { OP_ID = 0, OP_SQ = 1, OP_MUL = 2, OP_NZ = 3, OP_SQC = 4 };   // what expr_colsum adds up (k_colsum_partial)
+int expr_colsum(sc_ctx *c, int op, const double *A, const double *B, double *out, double div, double *out_raw = nullptr);
+int expr_colsum_chunks(sc_ctx *c, const double *partial, int chunks, double *out, double div = 1.0, double *out_raw = nullptr);
+int expr_moments(sc_ctx *c);                       // mean (+ raw column sums), z2 = sum (X - mean)^2, var = z2 / n
+int expr_write_z(sc_ctx *c, const double *centre);   // Z = X - centre (per gene)
 int sc_expr_zscores(sc_ctx *c);  // Z = (X - mean) / population sd per gene (0 for zero variance), variances in g_var
-int sc_lag_tiles(sc_ctx *c, const DBuf &indptr, const DBuf &indices, const DBuf &data, const double *Z, double *out);
+int expr_gene_stats(sc_ctx *c);  // value classes and largest counts of the loaded genes into c->g_flags / c->g_xmax
+int expr_pack_narrow(sc_ctx *c, int bits);   // c->X32 = the raw values as uint8 / uint16 / float32 rows
+// Lag = W Z on any CSR over the cells; unit[gene] != 0 (optional): that gene's rows are summed with weight 1
+int sc_lag_tiles(sc_ctx *c, const DBuf &indptr, const DBuf &indices, const DBuf &data, const double *Z, double *out,
+                 const double *unit = nullptr);
 
 // 64-bit masks and per-lane variable shifts built from 32-bit instructions whose shift amounts are IN RANGE by
 // construction.  r02 finding (ISA diff in r03): the one instruction that produced wrong values
@@ -296,6 +307,11 @@ __device__ __forceinline__ uint64_t sc_shr64(uint64_t x, uint32_t pos)   // x >>
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t align_up64(int64_t a, int64_t b) { return ceil_div64(a, b) * b; }
+// the graph's processing order for kernels that walk n cells (nullptr: none captured for a graph of this size, input order)
+static inline const int32_t *sc_processing_order(const sc_ctx *c, int64_t n)
+{
+    return (c->g_order_captured && c->g_n == n && c->g_order.p) ? c->g_order.as<int32_t>() : nullptr;
+}
 
 // ---- implemented across translation units ----
 // bins the points for a neighbour search (sx / sy / sid / bin_start; bins of side >= min_h, about target_per_bin points each)

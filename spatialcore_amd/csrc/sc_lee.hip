@@ -13,6 +13,7 @@
 //     rows -- a fresh block of P per live pair, in pair order, zero-variance pairs draw nothing (AC:1129-1140) -- come
 //     out of the same generator pipeline as sc_moran_seeded and are scored chunk by chunk while the generator runs; the
 //     counts are reduced on the device (no host round trip per pair).
+// Behind the batched forms: Lee's L one pair at a time on the resident table (sc_lee), and local Lee (sc_lee_local*).
 #include <math.h>
 #include <string.h>
 
@@ -690,5 +691,382 @@ extern "C" int sc_lee_shared(sc_ctx *c, uint64_t *state6, const int32_t *genes_x
     SC_HIP(hipMemcpyAsync(cnt.data(), c->lee_cnt.p, sizeof(unsigned long long) * (size_t)per, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     for (int64_t q = 0; q < per; ++q) count_abs_ge_out[q] = (int64_t)cnt[(size_t)q];
+    return SC_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// A8: Lee's L, one pair at a time (sc_lee: the resident permutation table; tests and lees_l_local's global statistic)
+// ------------------------------------------------------------------------------------------------
+
+// out[i] = T[tile(g)][i][slot(g)]  -- pull one gene out of the tiles into a contiguous vector
+__global__ __launch_bounds__(256) void k_extract_col(const double *__restrict__ T, int64_t n, int64_t g,
+                                                     double *__restrict__ out)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = T[(g >> 4) * n * SC_TILE + i * SC_TILE + (g & 15)];
+}
+
+#define LEE_CELLS_PER_BLOCK 8192
+
+// partial[p][blk] = sum_{j in block range} a[j] * b[perm_p[j]]   (p == n_perm: identity perm with a2)
+__global__ __launch_bounds__(256) void k_vec_gather_dot(const double *__restrict__ a,
+                                                        const double *__restrict__ b,
+                                                        const int32_t *__restrict__ perm, int64_t pstride,
+                                                        int64_t n, double *__restrict__ partial)
+{
+    __shared__ double sh[256];
+    const int32_t *prow = perm + (int64_t)blockIdx.y * pstride;
+    int64_t j0 = (int64_t)blockIdx.x * LEE_CELLS_PER_BLOCK;
+    int64_t j1 = j0 + LEE_CELLS_PER_BLOCK < n ? j0 + LEE_CELLS_PER_BLOCK : n;
+    double acc = 0.0;
+    for (int64_t j = j0 + threadIdx.x; j < j1; j += 256) acc = fma(a[j], b[prow[j]], acc);
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
+}
+
+__global__ __launch_bounds__(256) void k_vec_dot(const double *__restrict__ a, const double *__restrict__ b,
+                                                 int64_t n, double *__restrict__ partial)
+{
+    __shared__ double sh[256];
+    int64_t j0 = (int64_t)blockIdx.x * LEE_CELLS_PER_BLOCK;
+    int64_t j1 = j0 + LEE_CELLS_PER_BLOCK < n ? j0 + LEE_CELLS_PER_BLOCK : n;
+    double acc = 0.0;
+    for (int64_t j = j0 + threadIdx.x; j < j1; j += 256) acc = fma(a[j], b[j], acc);
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+}
+
+// out[r] = sum_b partial[r][b]; one thread per row, ascending b
+__global__ void k_row_sum(const double *__restrict__ partial, int rows, int blocks, double *__restrict__ out)
+{
+    int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    double s = 0.0;
+    for (int b = 0; b < blocks; ++b) s += partial[(int64_t)r * blocks + b];
+    out[r] = s;
+}
+
+extern "C" int sc_lee(sc_ctx *c, const int32_t *pair_x, const int32_t *pair_y, const int64_t *perm_offset,
+                      int64_t n_pairs, int64_t n_perm, double *L_out, int64_t *count_abs_ge_out,
+                      double *L_perm_out)
+{
+    SC_REQUIRE(c && pair_x && pair_y && L_out, SC_ERR_INVALID, "sc_lee: null pointer");
+    SC_REQUIRE(n_pairs >= 0 && n_perm >= 0, SC_ERR_INVALID, "sc_lee: negative size");
+    SC_HIP(hipSetDevice(c->device));
+    if (n_perm > 0) SC_TRY(sc_perm_forward_ensure(c));
+    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_lee: no expression loaded");
+    SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_lee: graph missing or size mismatch");
+    SC_REQUIRE(n_perm == 0 || perm_offset, SC_ERR_INVALID, "sc_lee: perm_offset required when n_perm > 0");
+    const int64_t n = c->e_n, T = c->e_tiles;
+    const size_t tile_bytes = (size_t)n * SC_TILE * sizeof(double);
+    for (int64_t q = 0; q < n_pairs; ++q) {
+        SC_REQUIRE(pair_x[q] >= 0 && pair_x[q] < c->e_genes && pair_y[q] >= 0 && pair_y[q] < c->e_genes,
+                   SC_ERR_INVALID, "sc_lee: pair %lld references a gene outside the loaded set", (long long)q);
+        if (n_perm > 0 && perm_offset[q] >= 0)
+            SC_REQUIRE(c->p_n == n && perm_offset[q] + n_perm <= c->p_count, SC_ERR_STATE,
+                       "sc_lee: pair %lld needs permutation rows [%lld, %lld) but the table has %lld",
+                       (long long)q, (long long)perm_offset[q], (long long)(perm_offset[q] + n_perm),
+                       (long long)c->p_count);
+    }
+    // z-scores (population sd), lag = W z, u = W^T z
+    SC_TRY(sc_expr_zscores(c));
+    SC_TRY(c->Lag.ensure((size_t)T * tile_bytes, &c->mem));
+    SC_TRY(sc_lag_tiles(c, c->g_indptr, c->g_indices, c->g_data, c->Z.as<double>(), c->Lag.as<double>()));
+    std::vector<double> var((size_t)c->e_genes);
+    SC_HIP(hipMemcpyAsync(var.data(), c->g_var.p, sizeof(double) * var.size(), hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipStreamSynchronize(c->stream));
+
+    const int blocks = (int)ceil_div64(n, LEE_CELLS_PER_BLOCK);
+    // vectors: a = z_x, la = (W z_y), u = W^T z_x (via transposed graph on the extracted column), b = z_y
+    SC_TRY(c->lee_a.ensure(sizeof(double) * (size_t)n * 4, &c->mem));
+    double *va = c->lee_a.as<double>(), *vlag = va + n, *vu = va + 2 * n, *vb = va + 3 * n;
+    SC_TRY(c->lee_b.ensure(sizeof(double) * (size_t)blocks * (size_t)(n_perm + 1), &c->mem));
+    SC_TRY(c->lee_out.ensure(sizeof(double) * (size_t)(n_perm + 1 > T * SC_TILE ? n_perm + 1 : T * SC_TILE),
+                             &c->mem));
+    if (n_perm > 0) SC_TRY(sc_graph_ensure_transpose(c));
+    std::vector<double> host((size_t)n_perm + 1);
+    for (int64_t q = 0; q < n_pairs; ++q) {
+        bool degenerate = !(var[pair_x[q]] > 0.0) || !(var[pair_y[q]] > 0.0);
+        if (degenerate) {
+            L_out[q] = 0.0;
+            if (count_abs_ge_out) count_abs_ge_out[q] = n_perm;
+            if (L_perm_out)
+                for (int64_t p = 0; p < n_perm; ++p) L_perm_out[q * n_perm + p] = 0.0;
+            continue;
+        }
+        unsigned gcol = (unsigned)ceil_div64(n, 256);
+        hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n,
+                           (int64_t)pair_x[q], va);
+        hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Lag.as<double>(), n,
+                           (int64_t)pair_y[q], vlag);
+        hipLaunchKernelGGL(k_vec_dot, dim3(blocks), dim3(256), 0, c->stream, va, vlag, n,
+                           c->lee_b.as<double>() + (size_t)n_perm * blocks);
+        bool do_perm = n_perm > 0 && perm_offset[q] >= 0;
+        if (do_perm) {
+            hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n,
+                               (int64_t)pair_y[q], vb);
+            // u = W^T z_x : SpMV with the transposed graph on a single contiguous vector
+            sc_launch_spmv_vec(c, c->gt_indptr.as<int64_t>(), c->gt_indices.as<int32_t>(), c->gt_data.as<double>(),
+                               va, vu, n);
+            KernelTimerScope ts(c, SC_K_LEE_PERM);
+            hipLaunchKernelGGL(k_vec_gather_dot, dim3(blocks, (unsigned)n_perm), dim3(256), 0, c->stream, vu, vb,
+                               c->perm.as<int32_t>() + perm_offset[q] * c->p_stride, c->p_stride, n,
+                               c->lee_b.as<double>());
+        }
+        int rows = do_perm ? (int)n_perm + 1 : 1;
+        const double *src = c->lee_b.as<double>() + (do_perm ? 0 : (size_t)n_perm * blocks);
+        double *dst = c->lee_out.as<double>() + (do_perm ? 0 : n_perm);
+        hipLaunchKernelGGL(k_row_sum, dim3((unsigned)ceil_div64(rows, 256)), dim3(256), 0, c->stream, src, rows,
+                           blocks, dst);
+        SC_HIP(hipGetLastError());
+        SC_HIP(hipMemcpyAsync(host.data() + (do_perm ? 0 : n_perm), dst, sizeof(double) * (size_t)rows,
+                              hipMemcpyDeviceToHost, c->stream));
+        SC_HIP(hipStreamSynchronize(c->stream));
+        double L = host[(size_t)n_perm];
+        L_out[q] = L;
+        int64_t cnt = 0;
+        if (do_perm)
+            for (int64_t p = 0; p < n_perm; ++p) cnt += fabs(host[(size_t)p]) >= fabs(L) ? 1 : 0;
+        if (count_abs_ge_out) count_abs_ge_out[q] = do_perm ? cnt : 0;
+        if (L_perm_out)
+            for (int64_t p = 0; p < n_perm; ++p) L_perm_out[q * n_perm + p] = do_perm ? host[(size_t)p] : 0.0;
+    }
+    return SC_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// N2: Local Lee's L for one pair (AC:1394-1413): z-scores, lag = W z_y, L_local = z_x * lag, and the
+// optional per-cell permutation count  #{p : |float32(z_x[i] * (W z_y[perm_p])[i])| >= |L_local[i]|}
+// ------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void k_vec_mul(const double *__restrict__ a, const double *__restrict__ b,
+                                                 double *__restrict__ out, int64_t n)
+{
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = __dmul_rn(a[i], b[i]);
+}
+
+// The count in two phases per batch of permutations, in the graph's processing order (see k_lm_gather_sorted):
+// ys[p][r] = z_y[perm_p[order[r]]] once per permutation, then a LOCAL sparse product.  (A one-kernel form, r01,
+// fetched 900 GB for 999 permutations of 1M cells: 7 random 8-byte reads per cell and permutation, 128 bytes each.)
+#define LL_PERM_BATCH 16
+
+__global__ __launch_bounds__(256) void k_lee_local_gather(const double *__restrict__ zy, const int32_t *__restrict__ order,
+                                                          const int32_t *__restrict__ perm, int64_t pstride, int64_t n,
+                                                          double *__restrict__ ys)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    ys[(int64_t)blockIdx.y * n + r] = zy[perm[(int64_t)blockIdx.y * pstride + order[r]]];
+}
+
+__global__ __launch_bounds__(256) void k_lee_local_count_sorted(const long long *__restrict__ indptr,
+                                                                const int32_t *__restrict__ indices_r,
+                                                                const double *__restrict__ w, const int32_t *__restrict__ order,
+                                                                const double *__restrict__ zx,
+                                                                const double *__restrict__ ys,
+                                                                const double *__restrict__ Llocal, int n_batch,
+                                                                int32_t *__restrict__ count, int64_t n, int first)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const int64_t i = order[r];
+    const long long e0 = indptr[i], e1 = indptr[i + 1];
+    const double x = zx[i], obs = fabs(Llocal[i]);
+    double s[LL_PERM_BATCH];
+#pragma unroll
+    for (int p = 0; p < LL_PERM_BATCH; ++p) s[p] = 0.0;
+    for (long long e = e0; e < e1; ++e) {      // edge loop outside, permutations unrolled inside: independent loads in flight
+        const double ww = w[e];
+        const double *ye = ys + indices_r[e];
+#pragma unroll
+        for (int p = 0; p < LL_PERM_BATCH; ++p)
+            if (p < n_batch) s[p] = __dadd_rn(s[p], __dmul_rn(ww, ye[(int64_t)p * n]));
+    }
+    int cnt = 0;
+#pragma unroll
+    for (int p = 0; p < LL_PERM_BATCH; ++p)
+        if (p < n_batch) {
+            // the reference stores the permuted values in a float32 array before comparing (AC:1402,1408)
+            const double lp = (double)(float)__dmul_rn(x, s[p]);
+            cnt += fabs(lp) >= obs;
+        }
+    count[i] = first ? cnt : count[i] + cnt;
+}
+
+// The vectors of one local Lee job (sc_lee_local, sc_lee_local_seeded), n each
+struct LlJob { int64_t n = 0; double *zx = nullptr, *zy = nullptr, *lag = nullptr, *L = nullptr; int32_t *cnt = nullptr; };
+
+// z_x and z_y from the standardised tiles (c->Z), lag = W z_y, L_local = z_x * lag; and what the per-cell counts of
+// n_perm permutations need
+static int ll_prepare(sc_ctx *c, int32_t gene_x, int32_t gene_y, int64_t n_perm, const LlJob &j)
+{
+    const int64_t n = j.n;
+    const unsigned gcol = (unsigned)ceil_div64(n, 256);
+    hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_x, j.zx);
+    hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_y, j.zy);
+    sc_launch_spmv_vec(c, c->g_indptr.as<int64_t>(), c->g_indices.as<int32_t>(), c->g_data.as<double>(), j.zy, j.lag, n);
+    hipLaunchKernelGGL(k_vec_mul, dim3(gcol), dim3(256), 0, c->stream, j.zx, j.lag, j.L, n);
+    if (n_perm > 0) {
+        SC_TRY(sc_graph_ensure_order(c));
+        SC_TRY(c->lm_ys.ensure(sizeof(double) * (size_t)LL_PERM_BATCH * (size_t)n, &c->mem));
+    }
+    SC_HIP(hipGetLastError());
+    return SC_OK;
+}
+
+// counts of permutations [p0, p1) of the job (rows row0 + p of the forward table); p0 == 0 starts the counts
+static int ll_count(sc_ctx *c, const LlJob &j, int64_t row0, int64_t p0, int64_t p1)
+{
+    const int64_t n = j.n;
+    const unsigned gcol = (unsigned)ceil_div64(n, 256);
+    for (int64_t p = p0; p < p1; p += LL_PERM_BATCH) {
+        const int nb = (int)(p1 - p < LL_PERM_BATCH ? p1 - p : LL_PERM_BATCH);
+        hipLaunchKernelGGL(k_lee_local_gather, dim3(gcol, (unsigned)nb), dim3(256), 0, c->stream, j.zy,
+                           c->g_order.as<int32_t>(), c->perm.as<int32_t>() + (row0 + p) * c->p_stride, c->p_stride,
+                           n, c->lm_ys.as<double>());
+        hipLaunchKernelGGL(k_lee_local_count_sorted, dim3(gcol), dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
+                           c->g_indices_r.as<int32_t>(), c->g_data.as<double>(), c->g_order.as<int32_t>(), j.zx,
+                           c->lm_ys.as<double>(), j.L, nb, j.cnt, n, p == 0 ? 1 : 0);
+    }
+    SC_HIP(hipGetLastError());
+    return SC_OK;
+}
+
+extern "C" int sc_lee_local(sc_ctx *c, int32_t gene_x, int32_t gene_y, int64_t n_perm, int64_t perm_row0,
+                            double *zx_out, double *lag_out, double *L_local_out, int32_t *count_out)
+{
+    SC_REQUIRE(c && zx_out && lag_out && L_local_out, SC_ERR_INVALID, "sc_lee_local: null pointer");
+    SC_HIP(hipSetDevice(c->device));
+    if (n_perm > 0) SC_TRY(sc_perm_forward_ensure(c));
+    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_lee_local: no expression loaded");
+    SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_lee_local: graph missing or size mismatch");
+    SC_REQUIRE(gene_x >= 0 && gene_x < c->e_genes && gene_y >= 0 && gene_y < c->e_genes, SC_ERR_INVALID,
+               "sc_lee_local: gene index outside the loaded set");
+    if (n_perm > 0) {
+        SC_REQUIRE(count_out, SC_ERR_INVALID, "sc_lee_local: count_out required when n_perm > 0");
+        SC_REQUIRE(c->p_n == c->e_n && perm_row0 >= 0 && perm_row0 + n_perm <= c->p_count, SC_ERR_STATE,
+                   "sc_lee_local: needs permutation rows [%lld, %lld)", (long long)perm_row0,
+                   (long long)(perm_row0 + n_perm));
+    }
+    const int64_t n = c->e_n;
+    SC_TRY(sc_expr_zscores(c));
+    SC_TRY(c->lee_a.ensure(sizeof(double) * (size_t)n * 5, &c->mem));
+    LlJob j;
+    j.n = n; j.zx = c->lee_a.as<double>(); j.zy = j.zx + n; j.lag = j.zx + 2 * n; j.L = j.zx + 3 * n;
+    j.cnt = reinterpret_cast<int32_t *>(j.zx + 4 * n);
+    SC_TRY(ll_prepare(c, gene_x, gene_y, n_perm, j));
+    if (n_perm > 0) {
+        KernelTimerScope ts(c, SC_K_LEE_PERM);
+        SC_TRY(ll_count(c, j, perm_row0, 0, n_perm));
+    }
+    SC_HIP(hipMemcpyAsync(zx_out, j.zx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(lag_out, j.lag, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(L_local_out, j.L, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (n_perm > 0)
+        SC_HIP(hipMemcpyAsync(count_out, j.cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipStreamSynchronize(c->stream));
+    return SC_OK;
+}
+
+// r04: the pair body of lees_l_local as ONE pipeline (r03's verdict: a generator call and two device calls per pair, each
+// waiting for the one before).  Equal to
+//     sc_perm_generate(state6, n, n_perm_global + n_perm_local);  sc_lee(x, y, offset 0, n_perm_global);
+//     sc_lee_local(x, y, n_perm_local, perm_row0 = n_perm_global)
+// -- the same kernels on the same rows, results bit for bit, the generator state advanced by the same draws -- with the
+// permuted sums of the global statistic and the per-cell counts taken chunk by chunk behind the generator (which is 85 % of
+// the three calls' time at 10^6 cells), like sc_local_moran_seeded.
+// (sc_lee's pair body is written out again here, not shared: there one gather-dot launch covers all rows and the sums
+// come back per pair; here the rows arrive chunk by chunk between the local job's launches and z_x, z_y are the local
+// job's vectors -- one body for both would branch on its caller.)
+extern "C" int sc_lee_local_seeded(sc_ctx *c, uint64_t *state6, int32_t gene_x, int32_t gene_y, int64_t n_perm_global,
+                                   int64_t n_perm_local, double *L_out, int64_t *count_abs_ge_out, double *zx_out,
+                                   double *lag_out, double *L_local_out, int32_t *count_out)
+{
+    SC_REQUIRE(c && state6 && L_out && zx_out && lag_out && L_local_out, SC_ERR_INVALID, "sc_lee_local_seeded: null pointer");
+    SC_REQUIRE(n_perm_global >= 0 && n_perm_local >= 0 && n_perm_global + n_perm_local >= 1 &&
+               n_perm_global + n_perm_local <= (1 << 24), SC_ERR_INVALID, "sc_lee_local_seeded: permutation counts out of range");
+    SC_REQUIRE(n_perm_local == 0 || count_out, SC_ERR_INVALID, "sc_lee_local_seeded: count_out required when n_perm_local > 0");
+    SC_REQUIRE(n_perm_global == 0 || count_abs_ge_out, SC_ERR_INVALID, "sc_lee_local_seeded: count_abs_ge_out required when n_perm_global > 0");
+    SC_HIP(hipSetDevice(c->device));
+    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_lee_local_seeded: no expression loaded");
+    SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_lee_local_seeded: graph missing or size mismatch");
+    SC_REQUIRE(gene_x >= 0 && gene_x < c->e_genes && gene_y >= 0 && gene_y < c->e_genes, SC_ERR_INVALID,
+               "sc_lee_local_seeded: gene index outside the loaded set");
+    const int64_t n = c->e_n, T = c->e_tiles, Pg = n_perm_global, Pl = n_perm_local;
+    const int blocks = (int)ceil_div64(n, LEE_CELLS_PER_BLOCK);
+    const unsigned gcol = (unsigned)ceil_div64(n, 256);
+    double *vlag_g = nullptr, *vu = nullptr;
+    LlJob j;   // (z_x, z_y: sc_lee's operands too)
+    auto prepare = [&]() -> int {
+        // ---- sc_lee's operands: z-scores (population sd), Lag = W Z, u = W^T z_x ----
+        SC_TRY(sc_expr_zscores(c));
+        SC_TRY(c->Lag.ensure((size_t)T * (size_t)n * SC_TILE * sizeof(double), &c->mem));
+        SC_TRY(sc_lag_tiles(c, c->g_indptr, c->g_indices, c->g_data, c->Z.as<double>(), c->Lag.as<double>()));
+        double var[2];
+        SC_HIP(hipMemcpyAsync(&var[0], c->g_var.as<double>() + gene_x, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        SC_HIP(hipMemcpyAsync(&var[1], c->g_var.as<double>() + gene_y, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        SC_HIP(hipStreamSynchronize(c->stream));
+        SC_REQUIRE(var[0] > 0.0 && var[1] > 0.0, SC_ERR_INVALID, "sc_lee_local_seeded: a gene of the pair has zero variance");
+        SC_TRY(c->lee_a.ensure(sizeof(double) * (size_t)n * 8, &c->mem));
+        j.n = n; j.zx = c->lee_a.as<double>(); vlag_g = j.zx + n; vu = j.zx + 2 * n; j.zy = j.zx + 3 * n;
+        j.lag = j.zx + 4 * n; j.L = j.zx + 5 * n;
+        j.cnt = reinterpret_cast<int32_t *>(j.zx + 6 * n);
+        SC_TRY(c->lee_b.ensure(sizeof(double) * (size_t)blocks * (size_t)(Pg + 1), &c->mem));
+        SC_TRY(c->lee_out.ensure(sizeof(double) * (size_t)(Pg + 1 > T * SC_TILE ? Pg + 1 : T * SC_TILE), &c->mem));
+        if (Pg > 0) SC_TRY(sc_graph_ensure_transpose(c));
+        // ---- sc_lee_local's: z_x, z_y, lag = W z_y on the vector, L_local = z_x * lag ----
+        SC_TRY(ll_prepare(c, gene_x, gene_y, Pl, j));
+        // ---- sc_lee's: the observed sum and u = W^T z_x ----
+        hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Lag.as<double>(), n, (int64_t)gene_y, vlag_g);
+        hipLaunchKernelGGL(k_vec_dot, dim3(blocks), dim3(256), 0, c->stream, j.zx, vlag_g, n, c->lee_b.as<double>() + (size_t)Pg * blocks);
+        if (Pg > 0)
+            sc_launch_spmv_vec(c, c->gt_indptr.as<int64_t>(), c->gt_indices.as<int32_t>(), c->gt_data.as<double>(), j.zx, vu, n);
+        SC_HIP(hipGetLastError());
+        return SC_OK;
+    };
+    auto score = [&](int64_t p0, int64_t p1) -> int {
+        KernelTimerScope ts(c, SC_K_LEE_PERM);
+        const int64_t a1 = p1 < Pg ? p1 : Pg;
+        if (p0 < a1)   // rows of the global statistic
+            hipLaunchKernelGGL(k_vec_gather_dot, dim3(blocks, (unsigned)(a1 - p0)), dim3(256), 0, c->stream, vu, j.zy,
+                               c->perm.as<int32_t>() + p0 * c->p_stride, c->p_stride, n, c->lee_b.as<double>() + (size_t)p0 * blocks);
+        // rows of the per-cell counts: permutations [b0 - Pg, p1 - Pg) of the local job
+        const int64_t b0 = p0 > Pg ? p0 : Pg;
+        if (b0 < p1) SC_TRY(ll_count(c, j, Pg, b0 - Pg, p1 - Pg));
+        SC_HIP(hipGetLastError());
+        return SC_OK;
+    };
+    // a job that fails its verification is rerun with the sequential scan: everything restarts at permutation 0 (the
+    // first rows' flag restarts the counts)
+    SC_TRY(permgen_rerun_on_failure(c, [&]() { return sc_perm_pipeline(c, state6, n, Pg + Pl, 0, 2, prepare, score); }, nullptr));
+    std::vector<double> host((size_t)Pg + 1);
+    hipLaunchKernelGGL(k_row_sum, dim3((unsigned)ceil_div64(Pg + 1, 256)), dim3(256), 0, c->stream, c->lee_b.as<double>(),
+                       (int)(Pg + 1), blocks, c->lee_out.as<double>());
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipMemcpyAsync(host.data(), c->lee_out.p, sizeof(double) * (size_t)(Pg + 1), hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(zx_out, j.zx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(lag_out, j.lag, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(L_local_out, j.L, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (Pl > 0) SC_HIP(hipMemcpyAsync(count_out, j.cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipStreamSynchronize(c->stream));
+    const double L = host[(size_t)Pg];
+    *L_out = L;
+    if (count_abs_ge_out) {
+        int64_t cnt = 0;
+        for (int64_t p = 0; p < Pg; ++p) cnt += fabs(host[(size_t)p]) >= fabs(L) ? 1 : 0;
+        *count_abs_ge_out = cnt;
+    }
     return SC_OK;
 }

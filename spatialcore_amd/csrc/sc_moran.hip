@@ -1,453 +1,13 @@
-// Expression tiles, spatial lag, global Moran's I with permutations, Lee's L.  gfx950 only.
-//
-// Device layout (DESIGN.md "Data layout"): genes are grouped in tiles of SC_TILE = 16; a tile is
-// [cell][16] fp64, i.e. one 128-byte row per cell.  A permutation step `lag[perm[i]]` then gathers
-// one full cache line that serves 16 genes at once, and the contiguous operand z[i] is a coalesced
-// 128-byte row.  The permutation table is [perm][cell] int32 with a row stride that is a multiple
-// of 32 elements so that rows can be read as int4.
+// Global Moran's I with permutations: the scoring prelude, the scoring kernels, the finalisation.  gfx950 only.
+// (Tiles: sc_expr.hip.  The permutation table is [perm][cell] int32 with a row stride that is a multiple of 32 elements,
+// so that rows can be read as int4: sc_perm.hip.)
 #include <math.h>
 #include <stdlib.h>
 
 #include <functional>
-#include <optional>
-#include <thread>
 #include <vector>
 
 #include "sc_ctx.h"
-#include "sc_pairwise.h"
-
-// ------------------------------------------------------------------------------------------------
-// expression upload
-// ------------------------------------------------------------------------------------------------
-
-template <typename T>
-__global__ __launch_bounds__(256) void k_scatter_csr(const int64_t *__restrict__ indptr,
-                                                      const int32_t *__restrict__ indices,
-                                                      const T *__restrict__ data,
-                                                      const int32_t *__restrict__ colmap,
-                                                      double *__restrict__ X, int64_t rows,
-                                                      int64_t n, int64_t n_vars, int64_t row0)
-{
-    // one wavefront per matrix row; lanes stride over the row's stored entries.
-    // X points at the chunk's first row inside tile 0; n is the full cell count (tile stride).
-    int64_t row = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    int64_t e0 = indptr[row] - row0, e1 = indptr[row + 1] - row0;
-    for (int64_t e = e0 + lane; e < e1; e += 64) {
-        int32_t c = indices[e];
-        if ((uint32_t)c >= (uint64_t)n_vars) continue;
-        int32_t slot = colmap[c];
-        if (slot >= 0)
-            X[(int64_t)(slot >> 4) * n * SC_TILE + row * SC_TILE + (slot & 15)] = (double)data[e];
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void k_gather_dense(const T *__restrict__ data, int64_t ld,
-                                                       const int32_t *__restrict__ gene_cols,
-                                                       int64_t n_genes, double *__restrict__ X,
-                                                       int64_t n, int64_t row_lo, int64_t rows)
-{
-    // thread = (row, slot) of one tile (blockIdx.y); padded slots are written as 0
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t r = t >> 4;
-    int s = (int)(t & 15);
-    if (r >= rows) return;
-    int64_t g = (int64_t)blockIdx.y * SC_TILE + s;
-    double v = 0.0;
-    if (g < n_genes) v = (double)data[r * ld + gene_cols[g]];
-    X[(int64_t)blockIdx.y * n * SC_TILE + (row_lo + r) * SC_TILE + s] = v;
-}
-
-static int expr_alloc(sc_ctx *c, int64_t n, int64_t n_genes)
-{
-    SC_REQUIRE(n >= 1 && n <= 0x7fffffffLL, SC_ERR_INVALID, "n_cells=%lld out of range", (long long)n);
-    SC_REQUIRE(n_genes >= 1 && n_genes <= (1 << 24), SC_ERR_INVALID, "n_genes=%lld out of range",
-               (long long)n_genes);
-    int64_t tiles = ceil_div64(n_genes, SC_TILE);
-    size_t bytes = (size_t)tiles * n * SC_TILE * sizeof(double);
-    SC_TRY(c->X.ensure(bytes, &c->mem));
-    size_t gb = (size_t)align_up64(tiles, 8) * SC_TILE * sizeof(double);  // the narrow-source kernels read whole groups
-    SC_TRY(c->g_mean.ensure(gb, &c->mem));
-    SC_TRY(c->g_var.ensure(gb, &c->mem));
-    SC_TRY(c->g_z2.ensure(gb, &c->mem));
-    SC_TRY(c->g_scale.ensure(gb, &c->mem));
-    SC_TRY(c->g_Inum.ensure(gb, &c->mem));
-    SC_TRY(c->g_xsum.ensure(gb, &c->mem));
-    SC_TRY(c->g_meanc.ensure(gb, &c->mem));
-    SC_TRY(c->g_lat.ensure(gb, &c->mem));
-    c->e_n = n;
-    c->e_genes = n_genes;
-    c->e_tiles = tiles;
-    c->narrow_bits = 64;
-    c->lat_any = false;
-    c->lm_valid = false;
-    c->prep_early = false;
-    return SC_OK;
-}
-
-
-extern "C" int sc_expr_set_csr(sc_ctx *c, const int64_t *indptr, const int32_t *indices,
-                               const void *data, int dtype, int64_t n, int64_t n_vars,
-                               const int32_t *gene_cols, int64_t n_genes)
-{
-    SC_REQUIRE(c && indptr && gene_cols, SC_ERR_INVALID, "sc_expr_set_csr: null pointer");
-    SC_REQUIRE(dtype == SC_F32 || dtype == SC_F64, SC_ERR_INVALID, "sc_expr_set_csr: bad dtype %d", dtype);
-    SC_REQUIRE(n_vars >= 1 && n_vars <= 0x7fffffffLL, SC_ERR_INVALID, "n_vars out of range");
-    SC_HIP(hipSetDevice(c->device));
-    c->e_n = 0;
-    SC_TRY(expr_alloc(c, n, n_genes));
-    c->e_dtype = dtype;
-    SC_REQUIRE(indptr[0] == 0, SC_ERR_INVALID, "sc_expr_set_csr: indptr[0] must be 0");
-    for (int64_t i = 0; i < n; ++i)
-        SC_REQUIRE(indptr[i + 1] >= indptr[i], SC_ERR_INVALID, "sc_expr_set_csr: indptr not monotone at row %lld",
-                   (long long)i);
-    int64_t nnz = indptr[n];
-    SC_REQUIRE(nnz == 0 || (indices && data), SC_ERR_INVALID, "sc_expr_set_csr: null indices/data");
-    std::vector<int32_t> colmap((size_t)n_vars, -1);
-    for (int64_t g = 0; g < n_genes; ++g) {
-        SC_REQUIRE(gene_cols[g] >= 0 && gene_cols[g] < n_vars, SC_ERR_INVALID, "gene column %d out of range",
-                   gene_cols[g]);
-        SC_REQUIRE(colmap[gene_cols[g]] < 0, SC_ERR_INVALID, "gene column %d listed twice", gene_cols[g]);
-        colmap[gene_cols[g]] = (int32_t)g;
-    }
-    SC_TRY(c->e_colmap.ensure(sizeof(int32_t) * (size_t)n_vars, &c->mem));
-    SC_HIP(hipMemcpyAsync(c->e_colmap.p, colmap.data(), sizeof(int32_t) * (size_t)n_vars,
-                          hipMemcpyHostToDevice, c->stream));
-    SC_HIP(hipMemsetAsync(c->X.p, 0, (size_t)c->e_tiles * n * SC_TILE * sizeof(double), c->stream));
-    SC_TRY(c->e_tmp_indptr.ensure(sizeof(int64_t) * (size_t)(n + 1), &c->mem));
-    SC_HIP(hipMemcpyAsync(c->e_tmp_indptr.p, indptr, sizeof(int64_t) * (size_t)(n + 1),
-                          hipMemcpyHostToDevice, c->stream));
-    // stream the stored entries through the device in row chunks of <= 256 Mi entries
-    const int64_t max_chunk = (int64_t)1 << 28;
-    size_t esz = dtype == SC_F32 ? 4 : 8;
-    int64_t r0 = 0;
-    while (r0 < n) {
-        int64_t r1 = r0 + 1;
-        while (r1 < n && indptr[r1 + 1] - indptr[r0] <= max_chunk) ++r1;
-        int64_t e0 = indptr[r0], cnt = indptr[r1] - e0;
-        if (cnt > 0) {
-            SC_TRY(c->e_tmp_indices.ensure(sizeof(int32_t) * (size_t)cnt, &c->mem));
-            SC_TRY(c->e_tmp_data.ensure(esz * (size_t)cnt, &c->mem));
-            SC_HIP(hipMemcpyAsync(c->e_tmp_indices.p, indices + e0, sizeof(int32_t) * (size_t)cnt,
-                                  hipMemcpyHostToDevice, c->stream));
-            SC_HIP(hipMemcpyAsync(c->e_tmp_data.p, (const char *)data + esz * (size_t)e0, esz * (size_t)cnt,
-                                  hipMemcpyHostToDevice, c->stream));
-            int64_t rows = r1 - r0;
-            unsigned grid = (unsigned)ceil_div64(rows * 64, 256);
-            const int64_t *ip = c->e_tmp_indptr.as<int64_t>() + r0;
-            double *Xr = c->X.as<double>() + r0 * SC_TILE;
-            // Xr is offset by r0 rows inside every tile: tile stride stays n*16
-            if (dtype == SC_F32)
-                hipLaunchKernelGGL(k_scatter_csr<float>, dim3(grid), dim3(256), 0, c->stream, ip,
-                                   c->e_tmp_indices.as<int32_t>(), c->e_tmp_data.as<float>(),
-                                   c->e_colmap.as<int32_t>(), Xr, rows, n, n_vars, e0);
-            else
-                hipLaunchKernelGGL(k_scatter_csr<double>, dim3(grid), dim3(256), 0, c->stream, ip,
-                                   c->e_tmp_indices.as<int32_t>(), c->e_tmp_data.as<double>(),
-                                   c->e_colmap.as<int32_t>(), Xr, rows, n, n_vars, e0);
-            SC_HIP(hipGetLastError());
-            // the staging buffers are reused by the next chunk
-            SC_HIP(hipStreamSynchronize(c->stream));
-        }
-        r0 = r1;
-    }
-    SC_HIP(hipStreamSynchronize(c->stream));
-    return SC_OK;
-}
-
-extern "C" int sc_expr_set_dense(sc_ctx *c, const void *data, int dtype, int64_t n, int64_t n_vars,
-                                 const int32_t *gene_cols, int64_t n_genes)
-{
-    SC_REQUIRE(c && data && gene_cols, SC_ERR_INVALID, "sc_expr_set_dense: null pointer");
-    SC_REQUIRE(dtype == SC_F32 || dtype == SC_F64, SC_ERR_INVALID, "sc_expr_set_dense: bad dtype %d", dtype);
-    SC_REQUIRE(n_vars >= 1, SC_ERR_INVALID, "n_vars out of range");
-    SC_HIP(hipSetDevice(c->device));
-    c->e_n = 0;
-    SC_TRY(expr_alloc(c, n, n_genes));
-    c->e_dtype = dtype;
-    for (int64_t g = 0; g < n_genes; ++g)
-        SC_REQUIRE(gene_cols[g] >= 0 && gene_cols[g] < n_vars, SC_ERR_INVALID, "gene column %d out of range",
-                   gene_cols[g]);
-    SC_TRY(c->e_colmap.ensure(sizeof(int32_t) * (size_t)n_genes, &c->mem));
-    SC_HIP(hipMemcpyAsync(c->e_colmap.p, gene_cols, sizeof(int32_t) * (size_t)n_genes, hipMemcpyHostToDevice,
-                          c->stream));
-    size_t esz = dtype == SC_F32 ? 4 : 8;
-    // row chunks of <= 1 GiB of source data
-    int64_t rows_per = ((int64_t)1 << 30) / (int64_t)(esz * (size_t)n_vars);
-    if (rows_per < 1) rows_per = 1;
-    for (int64_t r0 = 0; r0 < n; r0 += rows_per) {
-        int64_t rows = (n - r0 < rows_per) ? n - r0 : rows_per;
-        size_t bytes = esz * (size_t)rows * (size_t)n_vars;
-        SC_TRY(c->e_tmp_data.ensure(bytes, &c->mem));
-        SC_HIP(hipMemcpyAsync(c->e_tmp_data.p, (const char *)data + esz * (size_t)r0 * (size_t)n_vars, bytes,
-                              hipMemcpyHostToDevice, c->stream));
-        dim3 grid((unsigned)ceil_div64(rows * SC_TILE, 256), (unsigned)c->e_tiles);
-        if (dtype == SC_F32)
-            hipLaunchKernelGGL(k_gather_dense<float>, grid, dim3(256), 0, c->stream, c->e_tmp_data.as<float>(),
-                               n_vars, c->e_colmap.as<int32_t>(), n_genes, c->X.as<double>(), n, r0, rows);
-        else
-            hipLaunchKernelGGL(k_gather_dense<double>, grid, dim3(256), 0, c->stream,
-                               c->e_tmp_data.as<double>(), n_vars, c->e_colmap.as<int32_t>(), n_genes,
-                               c->X.as<double>(), n, r0, rows);
-        SC_HIP(hipGetLastError());
-        SC_HIP(hipStreamSynchronize(c->stream));
-    }
-    return SC_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// per-gene column reductions over tiles (deterministic two-stage tree)
-// ------------------------------------------------------------------------------------------------
-
-enum { OP_ID = 0, OP_SQ = 1, OP_MUL = 2, OP_NZ = 3, OP_SQC = 4 };
-
-#define RED_ROWS_PER_BLOCK 4096
-
-// partial[tile][chunk][16] = sum over the chunk's rows of op(A[row][slot], B[row][slot])
-// (OP_SQC: (A[row][slot] - B[tile * 16 + slot])^2, B = the per-gene means: the squares of Z = X - mean without storing Z)
-template <int OP>
-__global__ __launch_bounds__(256) void k_colsum_partial(const double *__restrict__ A,
-                                                        const double *__restrict__ B,
-                                                        double *__restrict__ partial, int64_t n)
-{
-    __shared__ double sh[256];
-    const int64_t tile = blockIdx.y;
-    const int slot = threadIdx.x & 15, rg = threadIdx.x >> 4;  // 16 row groups
-    const double *a = A + tile * n * SC_TILE;
-    const double *b = (OP == OP_MUL) ? B + tile * n * SC_TILE : nullptr;
-    const double centre = (OP == OP_SQC) ? B[tile * SC_TILE + slot] : 0.0;
-    int64_t r0 = (int64_t)blockIdx.x * RED_ROWS_PER_BLOCK;
-    int64_t r1 = r0 + RED_ROWS_PER_BLOCK < n ? r0 + RED_ROWS_PER_BLOCK : n;
-    double acc = 0.0;
-    for (int64_t r = r0 + rg; r < r1; r += 16) {
-        double v = a[r * SC_TILE + slot];
-        if (OP == OP_SQC) v = v - centre;
-        if (OP == OP_SQ || OP == OP_SQC) v = v * v;
-        if (OP == OP_NZ) v = (v != 0.0) ? 1.0 : 0.0;
-        if (OP == OP_MUL) v = v * b[r * SC_TILE + slot];
-        acc += v;
-    }
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s >= 16; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x < 16) partial[(tile * gridDim.x + blockIdx.x) * SC_TILE + threadIdx.x] = sh[threadIdx.x];
-}
-
-// out[tile*16+slot] = (sum over chunks, ascending) / div; out_raw (optional) gets the sum itself.
-// A true division, as numpy's mean takes it: sum * (1/n) turns a constant column c into c(1 +- eps) for ~15 % of
-// the cell counts n, and a zero-variance gene would then look alive.
-__global__ void k_colsum_final(const double *__restrict__ partial, double *__restrict__ out,
-                               double *__restrict__ out_raw, int chunks, double div)
-{
-    int tile = blockIdx.x, slot = threadIdx.x;
-    double s = 0.0;
-    for (int ch = 0; ch < chunks; ++ch) s += partial[((int64_t)tile * chunks + ch) * SC_TILE + slot];
-    if (out_raw) out_raw[tile * SC_TILE + slot] = s;
-    out[tile * SC_TILE + slot] = s / div;
-}
-
-template <int OP>
-static int colsum(sc_ctx *c, const double *A, const double *B, double *out, double div, double *out_raw = nullptr)
-{
-    int64_t n = c->e_n;
-    int chunks = (int)ceil_div64(n, RED_ROWS_PER_BLOCK);
-    SC_TRY(c->red_tmp.ensure(sizeof(double) * (size_t)c->e_tiles * chunks * SC_TILE, &c->mem));
-    hipLaunchKernelGGL(k_colsum_partial<OP>, dim3(chunks, (unsigned)c->e_tiles), dim3(256), 0, c->stream, A, B,
-                       c->red_tmp.as<double>(), n);
-    hipLaunchKernelGGL(k_colsum_final, dim3((unsigned)c->e_tiles), dim3(SC_TILE), 0, c->stream,
-                       c->red_tmp.as<double>(), out, out_raw, chunks, div);
-    SC_HIP(hipGetLastError());
-    return SC_OK;
-}
-
-// Z = X - mean   (mode 0, scanpy's z)      |  Z = Z / sd  (mode 1, in place; Lee's z-score AC:1142)
-__global__ __launch_bounds__(256) void k_center(const double *__restrict__ X, const double *__restrict__ mean,
-                                                double *__restrict__ Z, int64_t n)
-{
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * SC_TILE) return;
-    int64_t tile = blockIdx.y;
-    int slot = (int)(t & 15);
-    Z[tile * n * SC_TILE + t] = X[tile * n * SC_TILE + t] - mean[tile * SC_TILE + slot];
-}
-
-__global__ __launch_bounds__(256) void k_div_sd(double *__restrict__ Z, const double *__restrict__ var,
-                                                int64_t n)
-{
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * SC_TILE) return;
-    int64_t tile = blockIdx.y;
-    int slot = (int)(t & 15);
-    double v = var[tile * SC_TILE + slot];
-    double sd = sqrt(v);
-    // zero-variance genes are standardised to 0 (AC:1357-1359)
-    Z[tile * n * SC_TILE + t] = (v > 0.0) ? Z[tile * n * SC_TILE + t] / sd : 0.0;
-}
-
-// mean (+ raw column sums), z2 = sum (X - mean)^2, var = z2 / n
-static int expr_moments(sc_ctx *c)
-{
-    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "no expression loaded (call sc_expr_set_* first)");
-    const int64_t n = c->e_n;
-    SC_TRY(colsum<OP_ID>(c, c->X.as<double>(), nullptr, c->g_mean.as<double>(), (double)n, c->g_xsum.as<double>()));
-    SC_TRY(colsum<OP_SQC>(c, c->X.as<double>(), c->g_mean.as<double>(), c->g_var.as<double>(), (double)n, c->g_z2.as<double>()));
-    return SC_OK;
-}
-
-// Z = X - centre (per gene)
-static int expr_write_z(sc_ctx *c, const double *centre)
-{
-    c->lm_valid = false;  // Z is about to be rewritten
-    const int64_t n = c->e_n;
-    SC_TRY(c->Z.ensure((size_t)c->e_tiles * n * SC_TILE * sizeof(double), &c->mem));
-    dim3 grid((unsigned)ceil_div64(n * SC_TILE, 256), (unsigned)c->e_tiles);
-    hipLaunchKernelGGL(k_center, grid, dim3(256), 0, c->stream, c->X.as<double>(), centre, c->Z.as<double>(), n);
-    SC_HIP(hipGetLastError());
-    return SC_OK;
-}
-
-// mean, Z = X - mean, z2 = sum Z^2, var = z2 / n
-static int expr_center(sc_ctx *c)
-{
-    SC_TRY(expr_moments(c));
-    return expr_write_z(c, c->g_mean.as<double>());
-}
-
-extern "C" int sc_expr_stats(sc_ctx *c, double *mean_out, double *var_out)
-{
-    SC_REQUIRE(c, SC_ERR_INVALID, "null context");
-    SC_HIP(hipSetDevice(c->device));
-    SC_TRY(expr_center(c));
-    if (mean_out)
-        SC_HIP(hipMemcpyAsync(mean_out, c->g_mean.p, sizeof(double) * (size_t)c->e_genes, hipMemcpyDeviceToHost,
-                              c->stream));
-    if (var_out)
-        SC_HIP(hipMemcpyAsync(var_out, c->g_var.p, sizeof(double) * (size_t)c->e_genes, hipMemcpyDeviceToHost,
-                              c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-    return SC_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// A3: spatial lag  Lag[i][g] = sum_e w[e] * Z[col[e]][g]   (row-sequential, mul and add rounded
-// separately, like scanpy's `(i_data * z[i_indices]).sum()` and scipy's csr_matvec)
-// ------------------------------------------------------------------------------------------------
-
-// unit[gene] != 0 (optional): the gene's rows are summed with weight 1 instead of w[e] -- the unweighted neighbour sums S
-// of an integer-lattice gene (Z holds its raw counts then), exact integers in fp64.
-//
-// Processing order (r03): thread groups walk the cells in the graph's spatially sorted order (`order`: the bin-sorted
-// order of the points the graph was built from; identity for a graph of unknown geometry) and each XCD -- blockIdx.x % 8
-// under round-robin placement, speed only -- takes one contiguous eighth of that order, so the neighbour rows a
-// workgroup gathers were fetched by its neighbours a moment ago and sit in THAT XCD's L2.  In input order (r02) every
-// neighbour row came from the Infinity Cache or HBM again: 12.5 ms and 8-16 x the compulsory fetch traffic per launch at
-// bench size.  The sums are per row, in edge order: the results do not depend on the processing order.
-__global__ __launch_bounds__(256) void k_lag(const int64_t *__restrict__ indptr,
-                                             const int32_t *__restrict__ indices,
-                                             const double *__restrict__ w, const double *__restrict__ Z,
-                                             double *__restrict__ Lag, int64_t n, const double *__restrict__ unit,
-                                             const int32_t *__restrict__ order)
-{
-    // 8 threads per cell, each owning 2 of the tile's 16 genes (one 16-byte slice of the row)
-    const int64_t per_xcd = (int64_t)(gridDim.x >> 3);                 // gridDim.x is a multiple of 8
-    const int64_t blk = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    const int64_t t = blk * blockDim.x + threadIdx.x;
-    const int64_t pos = t >> 3;
-    int q = (int)(t & 7);
-    if (pos >= n) return;
-    const int64_t i = order ? order[pos] : pos;
-    const double2 *Zt = reinterpret_cast<const double2 *>(Z + (int64_t)blockIdx.y * n * SC_TILE);
-    double2 *Lt = reinterpret_cast<double2 *>(Lag + (int64_t)blockIdx.y * n * SC_TILE);
-    const bool ux = unit && unit[(int64_t)blockIdx.y * SC_TILE + 2 * q] != 0.0;
-    const bool uy = unit && unit[(int64_t)blockIdx.y * SC_TILE + 2 * q + 1] != 0.0;
-    int64_t e0 = indptr[i], e1 = indptr[i + 1];
-    double sx = 0.0, sy = 0.0;
-    for (int64_t e = e0; e < e1; ++e) {
-        int32_t j = indices[e];
-        double ww = w[e];
-        double2 z = Zt[(int64_t)j * 8 + q];
-        sx = __dadd_rn(sx, __dmul_rn(ux ? 1.0 : ww, z.x));
-        sy = __dadd_rn(sy, __dmul_rn(uy ? 1.0 : ww, z.y));
-    }
-    Lt[i * 8 + q] = make_double2(sx, sy);
-}
-
-// The same lag from the float32 narrow rows (r04): a float32-source batch has its raw values as 32 genes per 128-byte row
-// (k_pack_narrow<32>: the lane's 16 bytes = genes {16 t + 2 q, + 1} of the group's two tiles), so a neighbour costs one
-// 16-byte piece per lane for FOUR genes instead of one per tile for two -- half the gathered bytes (what bounds k_lag is
-// the rows through the CUs' vector memory path, section 4.2 of DESIGN.md).  z = (double)x - centre is rebuilt in
-// registers, the very value the Z tile holds; products and sums rounded separately, edges in ascending order: Lag is
-// k_lag's bit for bit.
-__global__ __launch_bounds__(256) void k_lag_f32rows(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
-                                                     const double *__restrict__ w, const uint4 *__restrict__ narrow,
-                                                     const double *__restrict__ centre, double *__restrict__ Lag, int64_t n,
-                                                     int tiles16, const double *__restrict__ unit,
-                                                     const int32_t *__restrict__ order)
-{
-    const int64_t per_xcd = (int64_t)(gridDim.x >> 3);                 // gridDim.x is a multiple of 8
-    const int64_t blk = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
-    const int64_t t = blk * blockDim.x + threadIdx.x;
-    const int64_t pos = t >> 3;
-    const int q = (int)(t & 7);
-    if (pos >= n) return;
-    const int64_t i = order ? order[pos] : pos;
-    const int grp = blockIdx.y;                                        // 32 genes = tiles 2 grp, 2 grp + 1
-    const int tiles_left = tiles16 - 2 * grp;
-    const uint4 *Xg = narrow + (int64_t)grp * n * 8;
-    double cen[4];
-    bool un[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t g = (int64_t)(2 * grp + ((k >> 1) < tiles_left ? (k >> 1) : 0)) * SC_TILE + 2 * q + (k & 1);
-        cen[k] = centre[g];
-        un[k] = unit && unit[g] != 0.0;
-    }
-    const int64_t e0 = indptr[i], e1 = indptr[i + 1];
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t e = e0; e < e1; ++e) {
-        const uint4 v = Xg[(int64_t)indices[e] * 8 + q];
-        const double ww = w[e];
-        const double z[4] = {(double)__uint_as_float(v.x) - cen[0], (double)__uint_as_float(v.y) - cen[1],
-                             (double)__uint_as_float(v.z) - cen[2], (double)__uint_as_float(v.w) - cen[3]};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) s[k] = __dadd_rn(s[k], __dmul_rn(un[k] ? 1.0 : ww, z[k]));
-    }
-    reinterpret_cast<double2 *>(Lag + (int64_t)(2 * grp) * n * SC_TILE)[i * 8 + q] = make_double2(s[0], s[1]);
-    if (tiles_left > 1) reinterpret_cast<double2 *>(Lag + (int64_t)(2 * grp + 1) * n * SC_TILE)[i * 8 + q] = make_double2(s[2], s[3]);
-}
-
-static int launch_lag(sc_ctx *c, const DBuf &indptr, const DBuf &indices, const DBuf &data, const double *Z,
-                      double *out, const double *unit = nullptr)
-{
-    int64_t n = c->e_n;
-    const int32_t *order = (c->g_order_captured && c->g_n == n && c->g_order.p) ? c->g_order.as<int32_t>() : nullptr;
-    KernelTimerScope ts(c, SC_K_LAG);
-    hipLaunchKernelGGL(k_lag, dim3((unsigned)align_up64(ceil_div64(n * 8, 256), 8), (unsigned)c->e_tiles), dim3(256), 0,
-                       c->stream, indptr.as<int64_t>(), indices.as<int32_t>(), data.as<double>(), Z, out, n, unit, order);
-    SC_HIP(hipGetLastError());
-    return SC_OK;
-}
-
-// helpers for the other translation units (sc_lee.hip): population-sd z-scores of the loaded genes in c->Z
-// (zero-variance genes -> 0, AC:1357-1359; c->g_var holds the variances), and the lag kernel on any CSR
-int sc_expr_zscores(sc_ctx *c)
-{
-    SC_TRY(expr_center(c));
-    hipLaunchKernelGGL(k_div_sd, dim3((unsigned)ceil_div64(c->e_n * SC_TILE, 256), (unsigned)c->e_tiles), dim3(256), 0,
-                       c->stream, c->Z.as<double>(), c->g_var.as<double>(), c->e_n);
-    SC_HIP(hipGetLastError());
-    return SC_OK;
-}
-
-int sc_lag_tiles(sc_ctx *c, const DBuf &indptr, const DBuf &indices, const DBuf &data, const double *Z, double *out)
-{
-    return launch_lag(c, indptr, indices, data, Z, out);
-}
 
 // ------------------------------------------------------------------------------------------------
 // A5: the permutation kernel (the metric's dominant kernel)
@@ -633,47 +193,12 @@ __global__ __launch_bounds__(256) void k_moran_count(const double *__restrict__ 
 // group's TG 16-gene tiles (TG = 8 / 4 / 2 / 1), stored as the lane's 16 bytes [t][e]: a lane's lag operands are then TG
 // 16-byte LDS reads that are contiguous across q (no bank conflicts), one per lag tile.
 //
-// What bounds the uint8 form (r02, 1M cells, 128 genes x 128 permutations, 3.56 ms on 248 CUs; diagnostic builds
-// -DSC_DIAG=n give wrong sums on purpose): half the LDS reads of lag 3.40 ms, no int -> fp64 conversions 3.50, neither
-// byte extraction nor conversion 3.44 -- neither LDS nor VALU issue; the gathered rows alone are 4.6 TB/s, with the
-// lag rows and indices ~5.7 TB/s memory-side: the random 128-byte gather at what the fabric sustains.
+// What bounds the uint8 form (r02, 1M cells, 128 genes x 128 permutations, 3.56 ms on 248 CUs; measured with diagnostic
+// builds that gave wrong sums on purpose -- they are in history, commit 2d8ee49): half the LDS reads of lag 3.40 ms, no
+// int -> fp64 conversions 3.50, neither byte extraction nor conversion 3.44 -- neither LDS nor VALU issue; the gathered
+// rows alone are 4.6 TB/s, with the lag rows and indices ~5.7 TB/s memory-side: the random 128-byte gather at what the
+// fabric sustains.
 // ------------------------------------------------------------------------------------------------
-
-// Value class of every gene in one pass over the tiles: flags[g] bit 0 = some value is not an integer in [0, 255],
-// bit 1 = ... not an integer in [0, 65535], bit 2 = ... not a float32 (NaN included); xmax[g] = largest integer count
-// (0xffffffff as soon as a value is no integer in [0, 2^32))
-__global__ __launch_bounds__(256) void k_gene_stats(const double *__restrict__ X, int64_t n, uint32_t *__restrict__ flags,
-                                                    uint32_t *__restrict__ xmax)
-{
-    __shared__ uint32_t sh_f[256], sh_m[256];
-    const int64_t tile = blockIdx.y;
-    const int slot = threadIdx.x & 15, rg = threadIdx.x >> 4;
-    const double *a = X + tile * n * SC_TILE;
-    const int64_t r0 = (int64_t)blockIdx.x * RED_ROWS_PER_BLOCK;
-    const int64_t r1 = r0 + RED_ROWS_PER_BLOCK < n ? r0 + RED_ROWS_PER_BLOCK : n;
-    uint32_t f = 0u, m = 0u;
-    for (int64_t r = r0 + rg; r < r1; r += 16) {
-        const double v = a[r * SC_TILE + slot];
-        const bool isint = v >= 0.0 && v <= 4294967295.0 && (double)(uint32_t)v == v;
-        const uint32_t u = isint ? (uint32_t)v : 0xffffffffu;
-        f |= (u <= 255u ? 0u : 1u) | (u <= 65535u ? 0u : 2u) | ((double)(float)v == v ? 0u : 4u);
-        m = u > m ? u : m;
-    }
-    sh_f[threadIdx.x] = f;
-    sh_m[threadIdx.x] = m;
-    __syncthreads();
-    for (int s = 128; s >= 16; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            sh_f[threadIdx.x] |= sh_f[threadIdx.x + s];
-            sh_m[threadIdx.x] = sh_m[threadIdx.x] > sh_m[threadIdx.x + s] ? sh_m[threadIdx.x] : sh_m[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 16) {
-        if (sh_f[threadIdx.x]) atomicOr(&flags[tile * SC_TILE + threadIdx.x], sh_f[threadIdx.x]);
-        atomicMax(&xmax[tile * SC_TILE + threadIdx.x], sh_m[threadIdx.x]);
-    }
-}
 
 // centre[g] = lat[g] ? 0 : mean[g]
 __global__ void k_moran_centres(const double *__restrict__ mean, const double *__restrict__ lat, double *__restrict__ centre,
@@ -681,70 +206,6 @@ __global__ void k_moran_centres(const double *__restrict__ mean, const double *_
 {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g < total) centre[g] = lat[g] != 0.0 ? 0.0 : mean[g];
-}
-
-// Narrow[group][cell][q][t][e] = X[TG * group + t][cell][2 q + e] as uint8 / uint16 / float (every value fits: k_gene_stats)
-template <int BITS>
-__global__ __launch_bounds__(256) void k_pack_narrow(const double *__restrict__ X, uint4 *__restrict__ out, int64_t n,
-                                                     int64_t tiles16)
-{
-    constexpr int TG = BITS == 8 ? 8 : BITS == 16 ? 4 : 2;
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (cell, q)
-    if (t >= n * 8) return;
-    const int64_t cell = t >> 3;
-    const int q = (int)(t & 7);
-    uint32_t o[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int tt = 0; tt < TG; ++tt) {
-        const int64_t t16 = TG * (int64_t)blockIdx.y + tt;
-        if (t16 >= tiles16) continue;
-        const double2 v = reinterpret_cast<const double2 *>(X + t16 * n * SC_TILE + cell * SC_TILE)[q];
-        if (BITS == 8) {
-            const uint32_t a = (uint32_t)(v.x >= 0.0 && v.x <= 255.0 ? v.x : 0.0), b = (uint32_t)(v.y >= 0.0 && v.y <= 255.0 ? v.y : 0.0);
-            o[tt >> 1] |= (a | (b << 8)) << (16 * (tt & 1));
-        } else if (BITS == 16) {
-            const uint32_t a = (uint32_t)(v.x >= 0.0 && v.x <= 65535.0 ? v.x : 0.0), b = (uint32_t)(v.y >= 0.0 && v.y <= 65535.0 ? v.y : 0.0);
-            o[tt] = a | (b << 16);
-        } else {
-            const float a = (float)v.x, b = (float)v.y;
-            o[2 * tt] = __float_as_uint(a);
-            o[2 * tt + 1] = __float_as_uint(b);
-        }
-    }
-    out[((int64_t)blockIdx.y * n + cell) * 8 + q] = make_uint4(o[0], o[1], o[2], o[3]);
-}
-
-#define INV_BLOCKS_PER_ROW 64
-
-// inv[row][perm[row][i]] = i.  Blocks of one row share blockIdx % 8 (one XCD under round-robin placement,
-// speed only) so that the 4n-byte inverse row is assembled in one L2.
-__global__ __launch_bounds__(256) void k_invert_perm(const int32_t *__restrict__ perm, int32_t *__restrict__ inv,
-                                                     int64_t n, int64_t stride, int rows)
-{
-    const int id = blockIdx.x;
-    const int rest = id >> 3;
-    const int row = (rest / INV_BLOCKS_PER_ROW) * 8 + (id & 7);
-    const int part = rest % INV_BLOCKS_PER_ROW;
-    if (row >= rows) return;
-    const int64_t per = (n + INV_BLOCKS_PER_ROW - 1) / INV_BLOCKS_PER_ROW;
-    const int64_t i0 = (int64_t)part * per, i1 = i0 + per < n ? i0 + per : n;
-    const int32_t *src = perm + (int64_t)row * stride;
-    int32_t *dst = inv + (int64_t)row * stride;
-    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) dst[src[i]] = (int32_t)i;
-}
-
-__global__ __launch_bounds__(256) void k_check_inverse(const int32_t *__restrict__ perm,
-                                                       const int32_t *__restrict__ inv, int64_t n, int64_t stride,
-                                                       int64_t rows, int *__restrict__ flag)
-{
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t total = rows * n;
-    int bad = 0;
-    for (; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t r = t / n, i = t - r * n;
-        if (inv[r * stride + perm[r * stride + i]] != (int32_t)i) bad = 1;
-    }
-    if (bad) atomicOr(flag, 1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -780,6 +241,58 @@ __global__ __launch_bounds__(256) void k_check_inverse(const int32_t *__restrict
 // = S of genes (16 t + 2 q, + 1) as two uint16 in one word, 256 bytes per cell and 128-gene group instead of 1 KB of fp64
 // -- and becomes the same fp64 values when it is parked in LDS (integers: exact): a quarter of the streamed bytes.
 __device__ __forceinline__ double2 lag16_to_double2(uint32_t v) { return make_double2((double)(v & 0xffffu), (double)(v >> 16)); }
+
+// ---- what k_moran_score and k_moran_score_wg do alike, in their pipelined loops and in their ragged tails ----
+// (A task's operands come in by reference, and each kernel binds them once per task in a one-line lambda: passed by
+// value, or named at every call, hipcc orders the address arithmetic of several instantiations differently -- as it does
+// with the per-task set-up, centres and cleared accumulators, in a function: that stays written out in both kernels.
+// scripts/isa_diff.py compares the ISA.)
+
+// The lane's 16 bytes (qoff = 16 q) of row i of a group's table Xg, at byte offset 128 i: a 32-bit offset from a
+// wavefront-uniform base (n < 2^25 cells, else the host picks the BIG form), i.e. no 64-bit address arithmetic per gather
+template <bool BIG>
+__device__ __forceinline__ uint4 score_row(const char *const &Xg, const uint32_t &qoff, int32_t i)
+{
+    if constexpr (BIG) return *reinterpret_cast<const uint4 *>(Xg + ((uint64_t)(uint32_t)i * 128u + qoff));
+    else return *reinterpret_cast<const uint4 *>(Xg + ((uint32_t)i * 128u + qoff));
+}
+
+// the index vectors of block b of the nblk blocks of a split that begins at cell c0 of the inverse row irow
+template <int CB>
+__device__ __forceinline__ void score_load_idx(int4 (&id)[CB / 4], const int32_t *const &irow, const int64_t &c0, int64_t b, const int64_t &nblk)
+{
+    const int64_t bb = b < nblk ? b : nblk - 1;   // past the end: a harmless reload of the last block
+#pragma unroll
+    for (int k = 0; k < CB / 4; ++k) id[k] = *reinterpret_cast<const int4 *>(irow + c0 + bb * CB + 4 * k);
+}
+
+template <int CB, bool BIG>
+__device__ __forceinline__ void score_gather(uint4 (&x)[CB], const int4 (&id)[CB / 4], const char *const &Xg, const uint32_t &qoff)
+{
+#pragma unroll
+    for (int k = 0; k < CB / 4; ++k) {
+        x[4 * k + 0] = score_row<BIG>(Xg, qoff, id[k].x);
+        x[4 * k + 1] = score_row<BIG>(Xg, qoff, id[k].y);
+        x[4 * k + 2] = score_row<BIG>(Xg, qoff, id[k].z);
+        x[4 * k + 3] = score_row<BIG>(Xg, qoff, id[k].w);
+    }
+}
+
+// tile t of one gathered row (w: the lane's four words): the two values of the lane's gene pair, centred, times the lag pair l
+template <int BITS, bool CENTER>
+__device__ __forceinline__ void score_fma(const uint32_t (&w)[4], int t, double2 l, const double (&m)[2], double (&acc)[2])
+{
+    double v0, v1;
+    if (BITS == 8) {
+        const uint32_t h = w[t >> 1] >> (16 * (t & 1));
+        v0 = (double)(h & 0xffu); v1 = (double)((h >> 8) & 0xffu);
+    } else if (BITS == 16) { v0 = (double)(w[t] & 0xffffu); v1 = (double)(w[t] >> 16); }
+    else if (BITS == 32) { v0 = (double)__uint_as_float(w[2 * t]); v1 = (double)__uint_as_float(w[2 * t + 1]); }
+    else { v0 = __hiloint2double((int)w[1], (int)w[0]); v1 = __hiloint2double((int)w[3], (int)w[2]); }
+    if constexpr (CENTER) { v0 -= m[0]; v1 -= m[1]; }
+    acc[0] = fma(l.x, v0, acc[0]);
+    acc[1] = fma(l.y, v1, acc[1]);
+}
 
 template <int BITS, int CB, bool BIG, bool L16 = false>
 __global__ __launch_bounds__(SCORE_PRIVATE_WAVES * 64) void k_moran_score(
@@ -820,14 +333,8 @@ __global__ __launch_bounds__(SCORE_PRIVATE_WAVES * 64) void k_moran_score(
         int64_t c1 = c0 + cells_per_split;
         if (c1 > n) c1 = n;
         const int32_t *irow = inv + (int64_t)pc * pstride;
-        // row i of the group's table at byte offset 128 i (+ 16 q for this lane): a 32-bit offset from a
-        // wavefront-uniform base (n < 2^25 cells, else the host picks the BIG form), i.e. no 64-bit address arithmetic per gather
         const char *Xg = reinterpret_cast<const char *>(narrow + (int64_t)grp * n * 8);
         const uint32_t qoff = (uint32_t)q * 16u;
-        auto row_of = [&](int32_t i) {
-            if constexpr (BIG) return *reinterpret_cast<const uint4 *>(Xg + ((uint64_t)(uint32_t)i * 128u + qoff));
-            else return *reinterpret_cast<const uint4 *>(Xg + ((uint32_t)i * 128u + qoff));
-        };
         const int tiles_left = tiles16 - TG * grp;                                 // lag tiles this group really has
         const double *lag_g = Lag + (int64_t)TG * grp * tile_elems;
         // (a padded last group re-reads its first tile for the missing ones; those sums are never used)
@@ -850,11 +357,7 @@ __global__ __launch_bounds__(SCORE_PRIVATE_WAVES * 64) void k_moran_score(
         uint32_t lh0 = 0, lh1 = 0, lh2 = 0, lh3 = 0;   // ... as 16-bit pairs (L16)
         uint4 xa[CB], xb[CB];
 
-        auto load_idx = [&](int4 (&id)[NI], int64_t b) {
-            const int64_t bb = b < nblk ? b : nblk - 1;   // past the end: a harmless reload of the last block
-#pragma unroll
-            for (int k = 0; k < NI; ++k) id[k] = *reinterpret_cast<const int4 *>(irow + c0 + bb * CB + 4 * k);
-        };
+        auto load_idx = [&](int4 (&id)[NI], int64_t b) { score_load_idx<CB>(id, irow, c0, b, nblk); };
         auto load_lag = [&](int64_t b) {
             const int64_t bb = b < nblk ? b : nblk - 1;
             const int64_t row0 = c0 + bb * CB + lcell0;
@@ -868,15 +371,7 @@ __global__ __launch_bounds__(SCORE_PRIVATE_WAVES * 64) void k_moran_score(
                 if constexpr (NL > 2) { lg2 = lsrc[(row0 + 2 * CSTEP) * 8]; lg3 = lsrc[(row0 + 3 * CSTEP) * 8]; }
             }
         };
-        auto gather = [&](uint4 (&x)[CB], const int4 (&id)[NI]) {
-#pragma unroll
-            for (int k = 0; k < NI; ++k) {
-                x[4 * k + 0] = row_of(id[k].x);
-                x[4 * k + 1] = row_of(id[k].y);
-                x[4 * k + 2] = row_of(id[k].z);
-                x[4 * k + 3] = row_of(id[k].w);
-            }
-        };
+        auto gather = [&](uint4 (&x)[CB], const int4 (&id)[NI]) { score_gather<CB, BIG>(x, id, Xg, qoff); };
         auto park_lag = [&](int buf) {
             double2 *dst = lw + buf * (CB * ROW) + lane;
             if constexpr (L16) {
@@ -892,29 +387,7 @@ __global__ __launch_bounds__(SCORE_PRIVATE_WAVES * 64) void k_moran_score(
         auto mul_cell = [&](const uint4 &x, const double2 *lr) {
             const uint32_t w[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
-            for (int t = 0; t < TG; ++t) {
-#if defined(SC_DIAG) && SC_DIAG == 1   /* diagnostic builds (wrong results): which resource bounds the kernel */
-                const double2 l = lr[(t & ~1) * 8];
-#else
-                const double2 l = lr[t * 8];
-#endif
-                double v0, v1;
-                if (BITS == 8) {
-                    const uint32_t h = w[t >> 1] >> (16 * (t & 1));
-#if defined(SC_DIAG) && SC_DIAG == 2
-                    v0 = __hiloint2double(0x3ff00000, (int)(h & 0xffu)); v1 = __hiloint2double(0x3ff00000, (int)((h >> 8) & 0xffu));
-#elif defined(SC_DIAG) && SC_DIAG == 3
-                    v0 = __hiloint2double(0x3ff00000, (int)h); v1 = __hiloint2double(0x3ff00001, (int)h);
-#else
-                    v0 = (double)(h & 0xffu); v1 = (double)((h >> 8) & 0xffu);
-#endif
-                } else if (BITS == 16) { v0 = (double)(w[t] & 0xffffu); v1 = (double)(w[t] >> 16); }
-                else if (BITS == 32) { v0 = (double)__uint_as_float(w[2 * t]); v1 = (double)__uint_as_float(w[2 * t + 1]); }
-                else { v0 = __hiloint2double((int)w[1], (int)w[0]); v1 = __hiloint2double((int)w[3], (int)w[2]); }
-                if constexpr (CENTER) { v0 -= m[t][0]; v1 -= m[t][1]; }
-                acc[t][0] = fma(l.x, v0, acc[t][0]);
-                acc[t][1] = fma(l.y, v1, acc[t][1]);
-            }
+            for (int t = 0; t < TG; ++t) score_fma<BITS, CENTER>(w, t, lr[t * 8], m[CENTER ? t : 0], acc[t]);
         };
         auto multiply = [&](const uint4 (&x)[CB], int buf) {
             const double2 *lr = lw + buf * (CB * ROW) + q;
@@ -950,23 +423,14 @@ __global__ __launch_bounds__(SCORE_PRIVATE_WAVES * 64) void k_moran_score(
             if (b < nblk) stage(xa, xb, idb, b);
         }
         for (int64_t j = c0 + nblk * CB; j < c1; ++j) {   // ragged tail of the split: straight from global memory
-            const uint4 x = row_of(irow[j]);
+            const uint4 x = score_row<BIG>(Xg, qoff, irow[j]);
             const uint32_t w[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
             for (int t = 0; t < TG; ++t) {
                 double2 l;
                 if constexpr (L16) l = lag16_to_double2(lag16_g[j * ROW + t * 8 + q]);
                 else l = reinterpret_cast<const double2 *>(lag_g + (int64_t)(t < tiles_left ? t : 0) * tile_elems)[j * 8 + q];
-                double v0, v1;
-                if (BITS == 8) {
-                    const uint32_t h = w[t >> 1] >> (16 * (t & 1));
-                    v0 = (double)(h & 0xffu); v1 = (double)((h >> 8) & 0xffu);
-                } else if (BITS == 16) { v0 = (double)(w[t] & 0xffffu); v1 = (double)(w[t] >> 16); }
-                else if (BITS == 32) { v0 = (double)__uint_as_float(w[2 * t]); v1 = (double)__uint_as_float(w[2 * t + 1]); }
-                else { v0 = __hiloint2double((int)w[1], (int)w[0]); v1 = __hiloint2double((int)w[3], (int)w[2]); }
-                if constexpr (CENTER) { v0 -= m[t][0]; v1 -= m[t][1]; }
-                acc[t][0] = fma(l.x, v0, acc[t][0]);
-                acc[t][1] = fma(l.y, v1, acc[t][1]);
+                score_fma<BITS, CENTER>(w, t, l, m[CENTER ? t : 0], acc[t]);
             }
         }
         if (p < n_perm) {
@@ -1044,10 +508,6 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void k_moran_score_wg(
         const int32_t *irow = inv + (int64_t)pc * pstride;
         const char *Xg = reinterpret_cast<const char *>(narrow + (int64_t)grp * n * 8);
         const uint32_t qoff = (uint32_t)q * 16u;
-        auto row_of = [&](int32_t i) {
-            if constexpr (BIG) return *reinterpret_cast<const uint4 *>(Xg + ((uint64_t)(uint32_t)i * 128u + qoff));
-            else return *reinterpret_cast<const uint4 *>(Xg + ((uint32_t)i * 128u + qoff));
-        };
         const int tiles_left = tiles16 - TG * grp;
         const double *lag_g = Lag + (int64_t)TG * grp * tile_elems;
         // (a padded last group re-reads its first tile for the missing ones; those sums are never used)
@@ -1080,25 +540,13 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void k_moran_score_wg(
             else lds_lag[buf][pid] = lg;
         };
 
-        auto load_idx = [&](int4 (&id)[NI], int64_t b) {
-            const int64_t bb = b < nblk ? b : nblk - 1;   // past the end: a harmless reload of the last block
-#pragma unroll
-            for (int k = 0; k < NI; ++k) id[k] = *reinterpret_cast<const int4 *>(irow + c0 + bb * CB + 4 * k);
-        };
+        auto load_idx = [&](int4 (&id)[NI], int64_t b) { score_load_idx<CB>(id, irow, c0, b, nblk); };
         auto load_lag = [&](int64_t sb) {
             const int64_t ss = sb < nsb ? sb : nsb - 1;
             if constexpr (L16) lh = lsrc16[(c0 + ss * SCORE_SB + lcell) * ROW];
             else lg = lsrc[(c0 + ss * SCORE_SB + lcell) * LSTRIDE];
         };
-        auto gather = [&](uint4 (&x)[CB], const int4 (&id)[NI]) {
-#pragma unroll
-            for (int k = 0; k < NI; ++k) {
-                x[4 * k + 0] = row_of(id[k].x);
-                x[4 * k + 1] = row_of(id[k].y);
-                x[4 * k + 2] = row_of(id[k].z);
-                x[4 * k + 3] = row_of(id[k].w);
-            }
-        };
+        auto gather = [&](uint4 (&x)[CB], const int4 (&id)[NI]) { score_gather<CB, BIG>(x, id, Xg, qoff); };
         auto mul_cell = [&](const uint4 &x, const double2 *lr) {
             const uint32_t w[4] = {x.x, x.y, x.z, x.w};
             if constexpr (NIB) {
@@ -1113,19 +561,7 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void k_moran_score_wg(
                 return;
             }
 #pragma unroll
-            for (int t = 0; t < TG; ++t) {
-                const double2 l = lr[t * 8];
-                double v0, v1;
-                if (BITS == 8) {
-                    const uint32_t h = w[t >> 1] >> (16 * (t & 1));
-                    v0 = (double)(h & 0xffu); v1 = (double)((h >> 8) & 0xffu);
-                } else if (BITS == 16) { v0 = (double)(w[t] & 0xffffu); v1 = (double)(w[t] >> 16); }
-                else if (BITS == 32) { v0 = (double)__uint_as_float(w[2 * t]); v1 = (double)__uint_as_float(w[2 * t + 1]); }
-                else { v0 = __hiloint2double((int)w[1], (int)w[0]); v1 = __hiloint2double((int)w[3], (int)w[2]); }
-                if constexpr (CENTER) { v0 -= m[t][0]; v1 -= m[t][1]; }
-                acc[t][0] = fma(l.x, v0, acc[t][0]);
-                acc[t][1] = fma(l.y, v1, acc[t][1]);
-            }
+            for (int t = 0; t < TG; ++t) score_fma<BITS, CENTER>(w, t, lr[t * 8], m[CENTER ? t : 0], acc[t]);
         };
         // one stage for block b = sb * SPS + k: `cur` holds its gathered rows; `nxt` receives block b + 1; `id_next` holds
         // the indices of block b + 1 and is refilled with those of block b + 1 + SPS, i.e. every index vector is consumed in
@@ -1185,7 +621,7 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void k_moran_score_wg(
         }
         if (live) {
             for (int64_t j = c0 + nsb * SCORE_SB; j < c1; ++j) {   // ragged tail of the split (< 16 cells): straight from global memory
-                const uint4 x = row_of(irow[j]);
+                const uint4 x = score_row<BIG>(Xg, qoff, irow[j]);
                 const uint32_t w[4] = {x.x, x.y, x.z, x.w};
                 if constexpr (NIB) {
                     const uint4 *srow = reinterpret_cast<const uint4 *>(Lag) + ((int64_t)grp * n + j) * ROW + q;
@@ -1204,16 +640,7 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void k_moran_score_wg(
                     double2 l;
                     if constexpr (L16) l = lag16_to_double2(lag16_g[j * ROW + t * 8 + q]);
                     else l = reinterpret_cast<const double2 *>(lag_g + (int64_t)(t < tiles_left ? t : 0) * tile_elems)[j * 8 + q];
-                    double v0, v1;
-                    if (BITS == 8) {
-                        const uint32_t h = w[t >> 1] >> (16 * (t & 1));
-                        v0 = (double)(h & 0xffu); v1 = (double)((h >> 8) & 0xffu);
-                    } else if (BITS == 16) { v0 = (double)(w[t] & 0xffffu); v1 = (double)(w[t] >> 16); }
-                    else if (BITS == 32) { v0 = (double)__uint_as_float(w[2 * t]); v1 = (double)__uint_as_float(w[2 * t + 1]); }
-                    else { v0 = __hiloint2double((int)w[1], (int)w[0]); v1 = __hiloint2double((int)w[3], (int)w[2]); }
-                    if constexpr (CENTER) { v0 -= m[t][0]; v1 -= m[t][1]; }
-                    acc[t][0] = fma(l.x, v0, acc[t][0]);
-                    acc[t][1] = fma(l.y, v1, acc[t][1]);
+                    score_fma<BITS, CENTER>(w, t, l, m[CENTER ? t : 0], acc[t]);
                 }
             }
             if (p < n_perm) {
@@ -1288,6 +715,50 @@ static int moran_check(sc_ctx *c, int64_t n_perm, const double *I_out)
     SC_REQUIRE(c->g_n == c->e_n, SC_ERR_INVALID, "sc_moran: graph has %lld rows but expression has %lld cells",
                (long long)c->g_n, (long long)c->e_n);
     return SC_OK;
+}
+
+// The same lag from the float32 narrow rows (r04): a float32-source batch has its raw values as 32 genes per 128-byte row
+// (k_pack_narrow<32>: the lane's 16 bytes = genes {16 t + 2 q, + 1} of the group's two tiles), so a neighbour costs one
+// 16-byte piece per lane for FOUR genes instead of one per tile for two -- half the gathered bytes (what bounds k_lag is
+// the rows through the CUs' vector memory path, section 4.2 of DESIGN.md).  z = (double)x - centre is rebuilt in
+// registers, the very value the Z tile holds; products and sums rounded separately, edges in ascending order: Lag is
+// k_lag's bit for bit.
+__global__ __launch_bounds__(256) void k_lag_f32rows(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                     const double *__restrict__ w, const uint4 *__restrict__ narrow,
+                                                     const double *__restrict__ centre, double *__restrict__ Lag, int64_t n,
+                                                     int tiles16, const double *__restrict__ unit,
+                                                     const int32_t *__restrict__ order)
+{
+    const int64_t per_xcd = (int64_t)(gridDim.x >> 3);                 // gridDim.x is a multiple of 8
+    const int64_t blk = (int64_t)(blockIdx.x & 7) * per_xcd + (blockIdx.x >> 3);
+    const int64_t t = blk * blockDim.x + threadIdx.x;
+    const int64_t pos = t >> 3;
+    const int q = (int)(t & 7);
+    if (pos >= n) return;
+    const int64_t i = order ? order[pos] : pos;
+    const int grp = blockIdx.y;                                        // 32 genes = tiles 2 grp, 2 grp + 1
+    const int tiles_left = tiles16 - 2 * grp;
+    const uint4 *Xg = narrow + (int64_t)grp * n * 8;
+    double cen[4];
+    bool un[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t g = (int64_t)(2 * grp + ((k >> 1) < tiles_left ? (k >> 1) : 0)) * SC_TILE + 2 * q + (k & 1);
+        cen[k] = centre[g];
+        un[k] = unit && unit[g] != 0.0;
+    }
+    const int64_t e0 = indptr[i], e1 = indptr[i + 1];
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t e = e0; e < e1; ++e) {
+        const uint4 v = Xg[(int64_t)indices[e] * 8 + q];
+        const double ww = w[e];
+        const double z[4] = {(double)__uint_as_float(v.x) - cen[0], (double)__uint_as_float(v.y) - cen[1],
+                             (double)__uint_as_float(v.z) - cen[2], (double)__uint_as_float(v.w) - cen[3]};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s[k] = __dadd_rn(s[k], __dmul_rn(un[k] ? 1.0 : ww, z[k]));
+    }
+    reinterpret_cast<double2 *>(Lag + (int64_t)(2 * grp) * n * SC_TILE)[i * 8 + q] = make_double2(s[0], s[1]);
+    if (tiles_left > 1) reinterpret_cast<double2 *>(Lag + (int64_t)(2 * grp + 1) * n * SC_TILE)[i * 8 + q] = make_double2(s[2], s[3]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1554,14 +1025,7 @@ static int moran_prepare_early(sc_ctx *c)
     if (need_s0) SC_TRY(sc_graph_weight_sum_launch(c, h_s0));
     SC_TRY(sc_graph_moments_begin(c));   // s1, s2 (p_norm, z-scores): on the side stream, out of this serial prelude
     SC_TRY(expr_moments(c));
-    // ---- value classes ----
-    SC_TRY(c->g_flags.ensure(sizeof(uint32_t) * (size_t)Gpad, &c->mem));
-    SC_TRY(c->g_xmax.ensure(sizeof(uint32_t) * (size_t)Gpad, &c->mem));
-    SC_HIP(hipMemsetAsync(c->g_flags.p, 0, sizeof(uint32_t) * (size_t)Gpad, c->stream));
-    SC_HIP(hipMemsetAsync(c->g_xmax.p, 0, sizeof(uint32_t) * (size_t)Gpad, c->stream));
-    hipLaunchKernelGGL(k_gene_stats, dim3((unsigned)ceil_div64(n, RED_ROWS_PER_BLOCK), (unsigned)T), dim3(256), 0, c->stream,
-                       c->X.as<double>(), n, c->g_flags.as<uint32_t>(), c->g_xmax.as<uint32_t>());
-    SC_HIP(hipGetLastError());
+    SC_TRY(expr_gene_stats(c));   // value classes
     SC_HIP(hipMemcpyAsync(h_flags, c->g_flags.p, sizeof(uint32_t) * (size_t)Gpad, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipMemcpyAsync(h_xmax, c->g_xmax.p, sizeof(uint32_t) * (size_t)Gpad, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipMemcpyAsync(h_xsum, c->g_xsum.p, sizeof(double) * (size_t)(T * SC_TILE), hipMemcpyDeviceToHost, c->stream));
@@ -1650,7 +1114,7 @@ static int moran_prepare(sc_ctx *c, int64_t n_perm, bool allow_lattice)
         hipLaunchKernelGGL(k_pack_nib, dim3((unsigned)ceil_div64(n * 8, 256), (unsigned)nib_groups), dim3(256), 0, c->stream,
                            c->X.as<double>(), c->X32.as<uint4>(), n, G, nib_slots, wide);
         const int chunks = (int)ceil_div64(n, LAG8_CELLS_PER_BLOCK);
-        const int32_t *order = (c->g_order_captured && c->g_n == n && c->g_order.p) ? c->g_order.as<int32_t>() : nullptr;
+        const int32_t *order = sc_processing_order(c, n);
         {
             KernelTimerScope ts(c, SC_K_LAG);
             hipLaunchKernelGGL(k_lag_nib, dim3((unsigned)align_up64(chunks, 8), (unsigned)nib_groups), dim3(256), 0, c->stream,
@@ -1669,12 +1133,10 @@ static int moran_prepare(sc_ctx *c, int64_t n_perm, bool allow_lattice)
         SC_HIP(hipGetLastError());
     } else if (u8_prelude) {
         c->lm_valid = false;   // (Lag is about to be rewritten)
-        SC_TRY(c->X32.ensure(sizeof(float) * (size_t)((T + 1) / 2) * n * 32, &c->mem));
-        hipLaunchKernelGGL(k_pack_narrow<8>, dim3((unsigned)ceil_div64(n * 8, 256), (unsigned)ceil_div64(T, 8)), dim3(256), 0,
-                           c->stream, c->X.as<double>(), c->X32.as<uint4>(), n, T);
+        SC_TRY(expr_pack_narrow(c, 8));
         const int chunks = (int)ceil_div64(n, LAG8_CELLS_PER_BLOCK);
         SC_TRY(c->red_tmp.ensure(sizeof(double) * 2 * (size_t)T * chunks * SC_TILE, &c->mem));
-        const int32_t *order = (c->g_order_captured && c->g_n == n && c->g_order.p) ? c->g_order.as<int32_t>() : nullptr;
+        const int32_t *order = sc_processing_order(c, n);
         {
             KernelTimerScope ts(c, SC_K_LAG);
             hipLaunchKernelGGL(k_lag_u8, dim3((unsigned)align_up64(chunks, 8), (unsigned)ceil_div64(T, 8)), dim3(256), 0, c->stream,
@@ -1682,19 +1144,15 @@ static int moran_prepare(sc_ctx *c, int64_t n_perm, bool allow_lattice)
                                (int64_t)n * SC_TILE, c->Lag.as<double>(), lag16 ? c->Lag.as<uint32_t>() : nullptr,
                                c->red_tmp.as<double>(), chunks);
         }
-        hipLaunchKernelGGL(k_colsum_final, dim3((unsigned)T), dim3(SC_TILE), 0, c->stream, c->red_tmp.as<double>(),
-                           c->g_Inum.as<double>(), (double *)nullptr, chunks, 1.0);
-        hipLaunchKernelGGL(k_colsum_final, dim3((unsigned)T), dim3(SC_TILE), 0, c->stream,
-                           c->red_tmp.as<double>() + (size_t)T * chunks * SC_TILE, c->g_slag.as<double>(), (double *)nullptr, chunks, 1.0);
         SC_HIP(hipGetLastError());
+        SC_TRY(expr_colsum_chunks(c, c->red_tmp.as<double>(), chunks, c->g_Inum.as<double>()));
+        SC_TRY(expr_colsum_chunks(c, c->red_tmp.as<double>() + (size_t)T * chunks * SC_TILE, chunks, c->g_slag.as<double>()));
     } else {
         SC_TRY(expr_write_z(c, c->g_meanc.as<double>()));
         const bool lag_from_rows = n_perm > 0 && bits == 32;
         if (lag_from_rows) {   // the float32 narrow copy first, then the lag from ITS rows (half the gathered bytes of the fp64 tiles)
-            SC_TRY(c->X32.ensure(sizeof(float) * (size_t)((T + 1) / 2) * n * 32, &c->mem));
-            hipLaunchKernelGGL(k_pack_narrow<32>, dim3((unsigned)ceil_div64(n * 8, 256), (unsigned)ceil_div64(T, 2)), dim3(256), 0,
-                               c->stream, c->X.as<double>(), c->X32.as<uint4>(), n, T);
-            const int32_t *order = (c->g_order_captured && c->g_n == n && c->g_order.p) ? c->g_order.as<int32_t>() : nullptr;
+            SC_TRY(expr_pack_narrow(c, 32));
+            const int32_t *order = sc_processing_order(c, n);
             KernelTimerScope ts(c, SC_K_LAG);
             hipLaunchKernelGGL(k_lag_f32rows, dim3((unsigned)align_up64(ceil_div64(n * 8, 256), 8), (unsigned)ceil_div64(T, 2)),
                                dim3(256), 0, c->stream, c->g_indptr.as<int64_t>(), c->g_indices.as<int32_t>(),
@@ -1703,10 +1161,10 @@ static int moran_prepare(sc_ctx *c, int64_t n_perm, bool allow_lattice)
             SC_HIP(hipGetLastError());
             narrow_packed = true;
         } else
-        SC_TRY(launch_lag(c, c->g_indptr, c->g_indices, c->g_data, c->Z.as<double>(), c->Lag.as<double>(),
-                          lat_any ? c->g_lat.as<double>() : nullptr));
-        SC_TRY(colsum<OP_MUL>(c, c->Z.as<double>(), c->Lag.as<double>(), c->g_Inum.as<double>(), 1.0));
-        if (lat_any) SC_TRY(colsum<OP_ID>(c, c->Lag.as<double>(), nullptr, c->g_slag.as<double>(), 1.0));
+        SC_TRY(sc_lag_tiles(c, c->g_indptr, c->g_indices, c->g_data, c->Z.as<double>(), c->Lag.as<double>(),
+                            lat_any ? c->g_lat.as<double>() : nullptr));
+        SC_TRY(expr_colsum(c, OP_MUL, c->Z.as<double>(), c->Lag.as<double>(), c->g_Inum.as<double>(), 1.0));
+        if (lat_any) SC_TRY(expr_colsum(c, OP_ID, c->Lag.as<double>(), nullptr, c->g_slag.as<double>(), 1.0));
     }
     SC_TRY(c->sims.ensure(sizeof(double) * (size_t)(T * SC_TILE) * (size_t)(n_perm > 0 ? n_perm : 1), &c->mem));
     hipLaunchKernelGGL(k_moran_scale, dim3((unsigned)ceil_div64(T * SC_TILE, 256)), dim3(256), 0, c->stream,
@@ -1724,72 +1182,9 @@ static int moran_prepare(sc_ctx *c, int64_t n_perm, bool allow_lattice)
         if (nib && (size_t)score_splits * (size_t)nib_groups * 256 > narrow_rows) narrow_rows = (size_t)score_splits * (size_t)nib_groups * 256;
         const size_t wide_rows = (size_t)splits64 * SC_TILE;
         SC_TRY(c->partial.ensure(sizeof(double) * (size_t)n_perm * (narrow_rows > wide_rows ? narrow_rows : wide_rows), &c->mem));
-        if (bits < 64 && bits > 4 && !u8_prelude && !narrow_packed) {
-            // the gathered operand: the raw values in the narrowest type that holds every gene of the batch exactly
-            const int64_t T32 = (T + 1) / 2;
-            SC_TRY(c->X32.ensure(sizeof(float) * (size_t)T32 * n * 32, &c->mem));   // >= the uint16 / uint8 copies
-            const int tg = bits == 8 ? 8 : bits == 16 ? 4 : 2;
-            const dim3 grid((unsigned)ceil_div64(n * 8, 256), (unsigned)ceil_div64(T, tg));
-            auto pack = bits == 8 ? k_pack_narrow<8> : bits == 16 ? k_pack_narrow<16> : k_pack_narrow<32>;
-            hipLaunchKernelGGL(pack, grid, dim3(256), 0, c->stream, c->X.as<double>(), c->X32.as<uint4>(), n, T);
-            SC_HIP(hipGetLastError());
-        }
+        // the gathered operand: the raw values in the narrowest type that holds every gene of the batch exactly
+        if (bits < 64 && bits > 4 && !u8_prelude && !narrow_packed) SC_TRY(expr_pack_narrow(c, bits));
     }
-    return SC_OK;
-}
-
-// inverse rows [p0, p1) of the active table on stream s
-int invert_rows(sc_ctx *c, int64_t p0, int64_t p1, hipStream_t s)
-{
-    const int rows = (int)(p1 - p0);
-    if (rows <= 0) return SC_OK;
-    const int groups = (rows + 7) / 8;
-    // (the table's own length, not the expression's: a generator job may run before any expression is loaded)
-    hipLaunchKernelGGL(k_invert_perm, dim3((unsigned)(groups * INV_BLOCKS_PER_ROW * 8)), dim3(256), 0, s,
-                       c->perm.as<int32_t>() + p0 * c->p_stride, c->inv.as<int32_t>() + p0 * c->p_stride, c->p_n,
-                       c->p_stride, rows);
-    SC_HIP(hipGetLastError());
-    return SC_OK;
-}
-
-// After a seeded pipeline that only generated the inverse table: materialise the permutation table itself (the
-// inverse of the inverse) for callers that use the resident table afterwards.
-int sc_perm_forward_ensure(sc_ctx *c)
-{
-    if (c->perm_forward_valid || c->p_count <= 0) return SC_OK;
-    const int rows = (int)c->p_count;
-    const int groups = (rows + 7) / 8;
-    hipLaunchKernelGGL(k_invert_perm, dim3((unsigned)(groups * INV_BLOCKS_PER_ROW * 8)), dim3(256), 0, c->stream,
-                       c->inv.as<int32_t>(), c->perm.as<int32_t>(), c->p_n, c->p_stride, rows);
-    SC_HIP(hipGetLastError());
-    SC_HIP(hipStreamSynchronize(c->stream));
-    c->perm_forward_valid = true;
-    return SC_OK;
-}
-
-// The scoring kernels gather through the INVERSE rows, which exist only for true permutations: a table uploaded by
-// the caller is checked once (inverse of the inverse).  *bijective = false: its rows are arbitrary index maps and
-// take the index-row kernel (k_moran_perm).
-static int moran_table_is_bijective(sc_ctx *c, int64_t n_perm, bool *bijective)
-{
-    *bijective = false;
-    if (n_perm <= 0) return SC_OK;
-    const int64_t rows = c->p_count > n_perm ? c->p_count : n_perm;  // the WHOLE table is checked once
-    SC_TRY(c->inv.ensure(sizeof(int32_t) * (size_t)(c->p_stride * rows + 32), &c->mem));
-    if (!c->perm_bijective && !c->perm_checked) {
-        SC_TRY(invert_rows(c, 0, rows, c->stream));
-        SC_TRY(c->perm_flag.ensure(sizeof(unsigned long long), &c->mem));
-        SC_HIP(hipMemsetAsync(c->perm_flag.p, 0, sizeof(int), c->stream));
-        hipLaunchKernelGGL(k_check_inverse, dim3(2048), dim3(256), 0, c->stream, c->perm.as<int32_t>(),
-                           c->inv.as<int32_t>(), c->p_n, c->p_stride, rows, c->perm_flag.as<int>());
-        int bad = 0;
-        SC_HIP(hipMemcpyAsync(&bad, c->perm_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        SC_HIP(hipStreamSynchronize(c->stream));
-        c->perm_checked = true;
-        c->perm_bijective = (bad == 0);
-        if (c->perm_bijective) c->inv_rows_valid = rows;
-    }
-    *bijective = c->perm_bijective;
     return SC_OK;
 }
 
@@ -1947,7 +1342,7 @@ extern "C" int sc_moran(sc_ctx *c, int64_t n_perm, double *I_out, double *sims_o
     const bool inverse_suffices = n_perm > 0 && c->perm_bijective && c->inv_rows_valid >= n_perm;
     if (n_perm > 0 && !inverse_suffices) SC_TRY(sc_perm_forward_ensure(c));
     bool bijective = true;
-    SC_TRY(moran_table_is_bijective(c, n_perm, &bijective));
+    SC_TRY(sc_perm_table_is_bijective(c, n_perm, &bijective));
     SC_TRY(moran_prepare(c, n_perm < PERM_CHUNK ? n_perm : PERM_CHUNK, n_perm <= 0 || bijective));
     SC_TRY(moran_alloc_sims(c, n_perm));
     const int bits = bijective ? c->narrow_bits : 0;
@@ -2103,1244 +1498,3 @@ extern "C" int sc_moran_seeded_finish(sc_ctx *c, uint64_t *state6, double *I_out
     return rc;
 }
 
-// ------------------------------------------------------------------------------------------------
-// A8: Lee's L
-// ------------------------------------------------------------------------------------------------
-
-// out[i] = T[tile(g)][i][slot(g)]  -- pull one gene out of the tiles into a contiguous vector
-__global__ __launch_bounds__(256) void k_extract_col(const double *__restrict__ T, int64_t n, int64_t g,
-                                                     double *__restrict__ out)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = T[(g >> 4) * n * SC_TILE + i * SC_TILE + (g & 15)];
-}
-
-#define LEE_CELLS_PER_BLOCK 8192
-
-// partial[p][blk] = sum_{j in block range} a[j] * b[perm_p[j]]   (p == n_perm: identity perm with a2)
-__global__ __launch_bounds__(256) void k_vec_gather_dot(const double *__restrict__ a,
-                                                        const double *__restrict__ b,
-                                                        const int32_t *__restrict__ perm, int64_t pstride,
-                                                        int64_t n, double *__restrict__ partial)
-{
-    __shared__ double sh[256];
-    const int32_t *prow = perm + (int64_t)blockIdx.y * pstride;
-    int64_t j0 = (int64_t)blockIdx.x * LEE_CELLS_PER_BLOCK;
-    int64_t j1 = j0 + LEE_CELLS_PER_BLOCK < n ? j0 + LEE_CELLS_PER_BLOCK : n;
-    double acc = 0.0;
-    for (int64_t j = j0 + threadIdx.x; j < j1; j += 256) acc = fma(a[j], b[prow[j]], acc);
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
-}
-
-__global__ __launch_bounds__(256) void k_vec_dot(const double *__restrict__ a, const double *__restrict__ b,
-                                                 int64_t n, double *__restrict__ partial)
-{
-    __shared__ double sh[256];
-    int64_t j0 = (int64_t)blockIdx.x * LEE_CELLS_PER_BLOCK;
-    int64_t j1 = j0 + LEE_CELLS_PER_BLOCK < n ? j0 + LEE_CELLS_PER_BLOCK : n;
-    double acc = 0.0;
-    for (int64_t j = j0 + threadIdx.x; j < j1; j += 256) acc = fma(a[j], b[j], acc);
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
-}
-
-// out[r] = sum_b partial[r][b]; one thread per row, ascending b
-__global__ void k_row_sum(const double *__restrict__ partial, int rows, int blocks, double *__restrict__ out)
-{
-    int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    double s = 0.0;
-    for (int b = 0; b < blocks; ++b) s += partial[(int64_t)r * blocks + b];
-    out[r] = s;
-}
-
-extern "C" int sc_lee(sc_ctx *c, const int32_t *pair_x, const int32_t *pair_y, const int64_t *perm_offset,
-                      int64_t n_pairs, int64_t n_perm, double *L_out, int64_t *count_abs_ge_out,
-                      double *L_perm_out)
-{
-    SC_REQUIRE(c && pair_x && pair_y && L_out, SC_ERR_INVALID, "sc_lee: null pointer");
-    SC_REQUIRE(n_pairs >= 0 && n_perm >= 0, SC_ERR_INVALID, "sc_lee: negative size");
-    SC_HIP(hipSetDevice(c->device));
-    if (n_perm > 0) SC_TRY(sc_perm_forward_ensure(c));
-    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_lee: no expression loaded");
-    SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_lee: graph missing or size mismatch");
-    SC_REQUIRE(n_perm == 0 || perm_offset, SC_ERR_INVALID, "sc_lee: perm_offset required when n_perm > 0");
-    const int64_t n = c->e_n, T = c->e_tiles;
-    const size_t tile_bytes = (size_t)n * SC_TILE * sizeof(double);
-    for (int64_t q = 0; q < n_pairs; ++q) {
-        SC_REQUIRE(pair_x[q] >= 0 && pair_x[q] < c->e_genes && pair_y[q] >= 0 && pair_y[q] < c->e_genes,
-                   SC_ERR_INVALID, "sc_lee: pair %lld references a gene outside the loaded set", (long long)q);
-        if (n_perm > 0 && perm_offset[q] >= 0)
-            SC_REQUIRE(c->p_n == n && perm_offset[q] + n_perm <= c->p_count, SC_ERR_STATE,
-                       "sc_lee: pair %lld needs permutation rows [%lld, %lld) but the table has %lld",
-                       (long long)q, (long long)perm_offset[q], (long long)(perm_offset[q] + n_perm),
-                       (long long)c->p_count);
-    }
-    // z-scores (population sd), lag = W z, u = W^T z
-    SC_TRY(expr_center(c));
-    hipLaunchKernelGGL(k_div_sd, dim3((unsigned)ceil_div64(n * SC_TILE, 256), (unsigned)T), dim3(256), 0, c->stream,
-                       c->Z.as<double>(), c->g_var.as<double>(), n);
-    SC_TRY(c->Lag.ensure((size_t)T * tile_bytes, &c->mem));
-    SC_TRY(launch_lag(c, c->g_indptr, c->g_indices, c->g_data, c->Z.as<double>(), c->Lag.as<double>()));
-    std::vector<double> var((size_t)c->e_genes);
-    SC_HIP(hipMemcpyAsync(var.data(), c->g_var.p, sizeof(double) * var.size(), hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-
-    const int blocks = (int)ceil_div64(n, LEE_CELLS_PER_BLOCK);
-    // vectors: a = z_x, la = (W z_y), u = W^T z_x (via transposed graph on the extracted column), b = z_y
-    SC_TRY(c->lee_a.ensure(sizeof(double) * (size_t)n * 4, &c->mem));
-    double *va = c->lee_a.as<double>(), *vlag = va + n, *vu = va + 2 * n, *vb = va + 3 * n;
-    SC_TRY(c->lee_b.ensure(sizeof(double) * (size_t)blocks * (size_t)(n_perm + 1), &c->mem));
-    SC_TRY(c->lee_out.ensure(sizeof(double) * (size_t)(n_perm + 1 > T * SC_TILE ? n_perm + 1 : T * SC_TILE),
-                             &c->mem));
-    if (n_perm > 0) SC_TRY(sc_graph_ensure_transpose(c));
-    std::vector<double> host((size_t)n_perm + 1);
-    for (int64_t q = 0; q < n_pairs; ++q) {
-        bool degenerate = !(var[pair_x[q]] > 0.0) || !(var[pair_y[q]] > 0.0);
-        if (degenerate) {
-            L_out[q] = 0.0;
-            if (count_abs_ge_out) count_abs_ge_out[q] = n_perm;
-            if (L_perm_out)
-                for (int64_t p = 0; p < n_perm; ++p) L_perm_out[q * n_perm + p] = 0.0;
-            continue;
-        }
-        unsigned gcol = (unsigned)ceil_div64(n, 256);
-        hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n,
-                           (int64_t)pair_x[q], va);
-        hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Lag.as<double>(), n,
-                           (int64_t)pair_y[q], vlag);
-        hipLaunchKernelGGL(k_vec_dot, dim3(blocks), dim3(256), 0, c->stream, va, vlag, n,
-                           c->lee_b.as<double>() + (size_t)n_perm * blocks);
-        bool do_perm = n_perm > 0 && perm_offset[q] >= 0;
-        if (do_perm) {
-            hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n,
-                               (int64_t)pair_y[q], vb);
-            // u = W^T z_x : SpMV with the transposed graph on a single contiguous vector
-            sc_launch_spmv_vec(c, c->gt_indptr.as<int64_t>(), c->gt_indices.as<int32_t>(), c->gt_data.as<double>(),
-                               va, vu, n);
-            KernelTimerScope ts(c, SC_K_LEE_PERM);
-            hipLaunchKernelGGL(k_vec_gather_dot, dim3(blocks, (unsigned)n_perm), dim3(256), 0, c->stream, vu, vb,
-                               c->perm.as<int32_t>() + perm_offset[q] * c->p_stride, c->p_stride, n,
-                               c->lee_b.as<double>());
-        }
-        int rows = do_perm ? (int)n_perm + 1 : 1;
-        const double *src = c->lee_b.as<double>() + (do_perm ? 0 : (size_t)n_perm * blocks);
-        double *dst = c->lee_out.as<double>() + (do_perm ? 0 : n_perm);
-        hipLaunchKernelGGL(k_row_sum, dim3((unsigned)ceil_div64(rows, 256)), dim3(256), 0, c->stream, src, rows,
-                           blocks, dst);
-        SC_HIP(hipGetLastError());
-        SC_HIP(hipMemcpyAsync(host.data() + (do_perm ? 0 : n_perm), dst, sizeof(double) * (size_t)rows,
-                              hipMemcpyDeviceToHost, c->stream));
-        SC_HIP(hipStreamSynchronize(c->stream));
-        double L = host[(size_t)n_perm];
-        L_out[q] = L;
-        int64_t cnt = 0;
-        if (do_perm)
-            for (int64_t p = 0; p < n_perm; ++p) cnt += fabs(host[(size_t)p]) >= fabs(L) ? 1 : 0;
-        if (count_abs_ge_out) count_abs_ge_out[q] = do_perm ? cnt : 0;
-        if (L_perm_out)
-            for (int64_t p = 0; p < n_perm; ++p) L_perm_out[q * n_perm + p] = do_perm ? host[(size_t)p] : 0.0;
-    }
-    return SC_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// N1: Local Moran's I (AC:804-934) with the reference's float32 arithmetic
-//
-// The reference standardises in float32, takes lag = W32 @ Z32 with scipy's row-sequential float32
-// accumulation, and for every permutation recomputes Zs = Z[perm], lag_s = W @ Zs, I_perm = Zs * lag_s
-// into a (P, N, B) tensor before counting |I_perm| >= |I| per cell in a Python loop.  Here the count
-// is accumulated on the fly: thread = (cell, 4 genes of a 16-gene float tile), loop over permutations.
-// ------------------------------------------------------------------------------------------------
-
-// Z32[tile][cell][16] = (float(x) - mean32) / sd32  (two float32 roundings, AC:858); padded genes -> 0
-__global__ __launch_bounds__(256) void k_lm_standardize(const double *__restrict__ X, const float *__restrict__ mean32,
-                                                        const float *__restrict__ sd32, float *__restrict__ Z32,
-                                                        int64_t n)
-{
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * SC_TILE) return;
-    int64_t tile = blockIdx.y;
-    int slot = (int)(t & 15);
-    float x = (float)X[tile * n * SC_TILE + t];
-    float sd = sd32[tile * SC_TILE + slot];
-    // IEEE float division via double (innocuous double rounding for 24-bit operands)
-    float z = (float)__ddiv_rn((double)__fsub_rn(x, mean32[tile * SC_TILE + slot]), (double)sd);
-    Z32[tile * n * SC_TILE + t] = z;
-}
-
-// ---- numpy's float summation, reproduced ---------------------------------------------------------
-// The reference takes the per-gene mean and E[x^2] with scipy's sparse `.mean(axis=0)` (AC:79-80,
-// 102-107): (data * T(1/n)) summed per CSC column by np.add.reduceat, i.e. first stored entry +
-// numpy's PAIRWISE sum of the rest (blocks of <= 128 with 8 strided accumulators, halving above
-// that with the split rounded down to a multiple of 8), in the matrix dtype T.  On count data the
-// per-cell |I_perm| >= |I| test is full of exact ties that are decided by the last bit of z, so the
-// float32 mean and sd must be THE SAME floats; a more accurate sum is not good enough.
-// The summation tree is fixed by the element count alone, so it is evaluated in parallel with the same rounding:
-// (1) the stored (non-zero) values of every gene are compacted in cell order (k_npc_count / k_npc_offsets /
-// k_npc_scatter: wavefront ballots over 512-cell blocks), (2) one thread per gene lists the leaves of numpy's
-// recursion over elements 1.. (k_npc_leaves), (3) one thread per (gene, statistic, leaf) sums its <= 128 elements
-// with the 8 strided accumulators (k_npc_leafsum), (4) one thread per (gene, statistic) replays the recursion over
-// the leaf sums (k_npc_combine).  A sequential walk per gene took 1.15 s at 1M cells; this takes milliseconds.
-
-#define NPC_CELLS 512  // cells per wavefront block of the compaction
-
-// cnt[(tile * nblk + w) * 16 + g] = stored entries of gene slot g among the cells of block w
-__global__ __launch_bounds__(256) void k_npc_count(const double *__restrict__ X, int64_t n, int64_t nblk,
-                                                   uint32_t *__restrict__ cnt)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), tile = blockIdx.y;
-    if (w >= nblk) return;
-    const double *Xt = X + tile * n * SC_TILE;
-    uint32_t mine = 0;
-    for (int s = 0; s < NPC_CELLS / 64; ++s) {
-        const int64_t cell = w * NPC_CELLS + 64 * s + lane;
-        double v[16];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const double2 t = cell < n ? reinterpret_cast<const double2 *>(Xt + cell * SC_TILE)[k] : make_double2(0.0, 0.0);
-            v[2 * k] = t.x; v[2 * k + 1] = t.y;
-        }
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const uint32_t c = (uint32_t)__popcll(__ballot(v[g] != 0.0));
-            mine += (lane == g) ? c : 0u;
-        }
-    }
-    if (lane < 16) cnt[(tile * nblk + w) * 16 + lane] = mine;
-}
-
-// exclusive prefix over the blocks of one gene, in place (one thread per padded gene)
-__global__ void k_npc_offsets(uint32_t *__restrict__ cnt, int64_t nblk, int64_t genes_padded)
-{
-    const int64_t gp = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gp >= genes_padded) return;
-    uint32_t *c = cnt + (gp >> 4) * nblk * 16 + (gp & 15);
-    uint32_t run = 0;
-    for (int64_t w = 0; w < nblk; ++w) {
-        const uint32_t t = c[w * 16];
-        c[w * 16] = run;
-        run += t;
-    }
-}
-
-// comp[gene * n + k] = k-th stored value of the gene, in cell order, as T
-template <typename T>
-__global__ __launch_bounds__(256) void k_npc_scatter(const double *__restrict__ X, int64_t n, int64_t nblk,
-                                                     const uint32_t *__restrict__ off, T *__restrict__ comp)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), tile = blockIdx.y;
-    if (w >= nblk) return;
-    const double *Xt = X + tile * n * SC_TILE;
-    uint32_t base[16];
-#pragma unroll
-    for (int g = 0; g < 16; ++g) base[g] = off[(tile * nblk + w) * 16 + g];
-    for (int s = 0; s < NPC_CELLS / 64; ++s) {
-        const int64_t cell = w * NPC_CELLS + 64 * s + lane;
-        double v[16];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const double2 t = cell < n ? reinterpret_cast<const double2 *>(Xt + cell * SC_TILE)[k] : make_double2(0.0, 0.0);
-            v[2 * k] = t.x; v[2 * k + 1] = t.y;
-        }
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const bool nz = v[g] != 0.0;
-            const unsigned long long bal = __ballot(nz);
-            // set bits of the ballot below this lane: the hardware's own mask-below-lane count (no per-lane 64-bit shift)
-            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-            if (nz) comp[(tile * 16 + g) * n + base[g] + below] = (T)v[g];
-            base[g] += (uint32_t)__popcll(bal);
-        }
-    }
-}
-
-// leaves[gene][i] = (start, len) of the i-th leaf of the recursion over elements 1 .. nnz-1; nleaves[gene]
-__global__ void k_npc_leaves(const double *__restrict__ nnz, int64_t n_genes, int64_t max_leaves,
-                             uint2 *__restrict__ leaves, uint32_t *__restrict__ nleaves)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_genes) return;
-    const uint32_t cnt = (uint32_t)nnz[g];
-    uint32_t k = 0;
-    if (cnt >= 2) {
-        uint2 *out = leaves + g * max_leaves;
-        (void)pw_walk<float>(cnt - 1, [&](uint32_t start, uint32_t len) {
-            if ((int64_t)k < max_leaves) out[k] = make_uint2(start, len);
-            ++k;
-            return 0.f;
-        });
-    }
-    nleaves[g] = k;
-}
-
-// one leaf: numpy's unrolled block sum (8 strided accumulators, pairwise combine, then the tail) of
-// val(i) = x_i * inv_n (statistic 0) or (x_i * x_i) * inv_n (statistic 1) over compacted elements 1 + start ..
-template <typename T>
-__global__ __launch_bounds__(256) void k_npc_leafsum(const T *__restrict__ comp, int64_t n,
-                                                     const uint2 *__restrict__ leaves,
-                                                     const uint32_t *__restrict__ nleaves, int64_t max_leaves,
-                                                     T *__restrict__ leafsum)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t g = blockIdx.y;
-    const int square = blockIdx.z;
-    if (i >= (int64_t)nleaves[g] || i >= max_leaves) return;
-    const uint2 lf = leaves[g * max_leaves + i];
-    const T *a = comp + g * n + 1 + lf.x;
-    const T inv_n = (T)(1.0 / (double)n);
-    const uint32_t len = lf.y;
-    auto val = [&](uint32_t k) { T x = a[k]; if (square) x = x * x; return x * inv_n; };
-    T res;
-    if (len < 8) {
-        res = (T)(-0.0);
-        for (uint32_t k = 0; k < len; ++k) res += val(k);
-    } else {
-        T r0 = val(0), r1 = val(1), r2 = val(2), r3 = val(3), r4 = val(4), r5 = val(5), r6 = val(6), r7 = val(7);
-        uint32_t k = 8;
-        for (; k < len - (len % 8); k += 8) {
-            r0 += val(k); r1 += val(k + 1); r2 += val(k + 2); r3 += val(k + 3);
-            r4 += val(k + 4); r5 += val(k + 5); r6 += val(k + 6); r7 += val(k + 7);
-        }
-        res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-        for (; k < len; ++k) res += val(k);
-    }
-    leafsum[(g * 2 + square) * max_leaves + i] = res;
-}
-
-// out[2*g] = numpy mean, out[2*g+1] = numpy mean of squares, as T: first stored entry + pairwise sum of the rest
-template <typename T>
-__global__ void k_npc_combine(const T *__restrict__ comp, int64_t n, const double *__restrict__ nnz,
-                              const T *__restrict__ leafsum, int64_t max_leaves, int64_t n_genes,
-                              T *__restrict__ out)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t g = t >> 1;
-    if (g >= n_genes) return;
-    const int square = (int)(t & 1);
-    const uint32_t cnt = (uint32_t)nnz[g];
-    const T inv_n = (T)(1.0 / (double)n);
-    T res = (T)0;
-    if (cnt >= 1) {
-        T x = comp[g * n];
-        if (square) x = x * x;
-        res = x * inv_n;
-        if (cnt >= 2) {
-            const T *ls = leafsum + (g * 2 + square) * max_leaves;
-            uint32_t k = 0;
-            res = res + pw_walk<T>(cnt - 1, [&](uint32_t, uint32_t) { return ls[k++]; });
-        }
-    }
-    out[t] = res;
-}
-
-// mean32 / sd32 exactly as AC:821-830: var = sqmean - mean^2 and sqrt in the matrix dtype T, then float32
-template <typename T>
-__global__ void k_lm_stats(const T *__restrict__ stats, float *__restrict__ mean32, float *__restrict__ sd32,
-                           unsigned char *__restrict__ zero, int64_t n_genes, int64_t total)
-{
-    int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= total) return;
-    if (g >= n_genes) { mean32[g] = 0.f; sd32[g] = 1.f; zero[g] = 1; return; }
-    const T m = stats[2 * g], q = stats[2 * g + 1];
-    const T var = q - m * m;
-    // sqrt in double, rounded once: correctly rounded for a float operand (53 >= 2*24 + 2 bits); the
-    // hardware v_sqrt_f32 alone is a 1-ulp approximation
-    const float sd = (float)__dsqrt_rn((double)var);
-    const bool z = (sd == 0.0f);
-    mean32[g] = (float)m;
-    sd32[g] = z ? 1.0f : sd;
-    zero[g] = z ? 1 : 0;
-}
-
-// observed: lag = W32 @ Z32 (row-sequential float32, mul and add rounded separately), I = Z * lag
-__global__ __launch_bounds__(256) void k_lm_observed(const long long *__restrict__ indptr,
-                                                     const int32_t *__restrict__ indices,
-                                                     const double *__restrict__ w, const float *__restrict__ Z32,
-                                                     float *__restrict__ Lag32, float *__restrict__ I32, int64_t n)
-{
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int64_t i = t >> 2;
-    int q = (int)(t & 3);
-    if (i >= n) return;
-    const float4 *Zt = reinterpret_cast<const float4 *>(Z32 + (int64_t)blockIdx.y * n * SC_TILE) + q;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (long long e = indptr[i]; e < indptr[i + 1]; ++e) {
-        const float ww = (float)w[e];
-        const float4 z = Zt[(int64_t)indices[e] * 4];
-        s.x = __fadd_rn(s.x, __fmul_rn(ww, z.x)); s.y = __fadd_rn(s.y, __fmul_rn(ww, z.y));
-        s.z = __fadd_rn(s.z, __fmul_rn(ww, z.z)); s.w = __fadd_rn(s.w, __fmul_rn(ww, z.w));
-    }
-    const float4 zi = Zt[i * 4];
-    const int64_t o = (int64_t)blockIdx.y * n * 4 + i * 4 + q;
-    reinterpret_cast<float4 *>(Lag32)[o] = s;
-    reinterpret_cast<float4 *>(I32)[o] =
-        make_float4(__fmul_rn(zi.x, s.x), __fmul_rn(zi.y, s.y), __fmul_rn(zi.z, s.z), __fmul_rn(zi.w, s.w));
-}
-
-// ---- count[i][g] += #{p : |Z[perm_p[i]] * sum_e w_e Z[perm_p[col_e]]| >= |I[i]|}, in two phases per batch of
-// permutations, in the graph's processing order (r02) ----
-// A one-kernel form (r01) read, per permutation and cell, k + 1 permutation indices and k + 1 random 64-byte z rows
-// per gene tile.  Per cell i the permuted vector y = z[perm] is all that matters: I_perm[i] = y[i] * sum_e w_e y[col_e].
-// Phase A materialises y once per (permutation, tile) -- ONE random row per cell -- at the cell's position r in a
-// spatially sorted order (Ys[r] = Z[perm[order[r]]]); phase B is then a LOCAL sparse product: the neighbours of a cell
-// sit at nearby positions, their rows are served by L1 / L2.  The edges of a row keep their ascending-column order,
-// so every sum is the reference's row-sequential float32 sum, bit for bit.
-#define LM_PERM_BATCH 8
-
-// Ys[p][tile][r][16] = Z32[tile][perm_p[order[r]]][16]      thread = (r, q), grid.y = tile, grid.z = permutation of the batch
-__global__ __launch_bounds__(256) void k_lm_gather_sorted(const float *__restrict__ Z32, const int32_t *__restrict__ order,
-                                                          const int32_t *__restrict__ perm, int64_t pstride, int64_t n,
-                                                          int64_t tiles, float *__restrict__ Ys)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t r = t >> 2;
-    const int q = (int)(t & 3);
-    if (r >= n) return;
-    const int32_t src = perm[(int64_t)blockIdx.z * pstride + order[r]];
-    const float4 v = reinterpret_cast<const float4 *>(Z32 + (int64_t)blockIdx.y * n * SC_TILE)[(int64_t)src * 4 + q];
-    reinterpret_cast<float4 *>(Ys + ((int64_t)blockIdx.z * tiles + blockIdx.y) * n * SC_TILE)[r * 4 + q] = v;
-}
-
-// count[tile][cell][16] += #{p in batch : |y[r] * sum_e w_e y[rank(col_e)]| >= |I[cell]|},  cell = order[r]
-// The edge loop is the OUTER loop and the batch's permutations the (unrolled) inner one: the LM_PERM_BATCH row loads of
-// an edge are independent and in flight together (with the permutations outside, every row load waited for the
-// previous one: 6.4 ms per launch at 2.9 TB/s of fabric traffic, latency-bound), and an edge's index and weight are
-// read once per batch.  Per permutation the terms are still added in the row's edge order: the reference's sum.
-// (An XCD-contiguous block order was measured too: 7.6 ms instead of 6.4 with the old loop order; not kept.)
-__global__ __launch_bounds__(256) void k_lm_count_sorted(const long long *__restrict__ indptr,
-                                                         const int32_t *__restrict__ indices_r,
-                                                         const float *__restrict__ w32, const int32_t *__restrict__ order,
-                                                         const float *__restrict__ Ys, const float *__restrict__ I32,
-                                                         int n_batch, int64_t tiles, int32_t *__restrict__ count, int64_t n,
-                                                         int first)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t r = t >> 2;
-    const int q = (int)(t & 3);
-    if (r >= n) return;
-    const int64_t i = order[r];
-    const int64_t o = (int64_t)blockIdx.y * n * 4 + i * 4 + q;
-    const float4 obs = reinterpret_cast<const float4 *>(I32)[o];
-    const float ax = fabsf(obs.x), ay = fabsf(obs.y), az = fabsf(obs.z), aw = fabsf(obs.w);
-    const long long e0 = indptr[i], e1 = indptr[i + 1];
-    const int64_t pstep = tiles * n * 4;   // float4 stride between the permutations of the batch
-    const float4 *Y0 = reinterpret_cast<const float4 *>(Ys + (int64_t)blockIdx.y * n * SC_TILE) + q;
-    float4 s[LM_PERM_BATCH];
-#pragma unroll
-    for (int p = 0; p < LM_PERM_BATCH; ++p) s[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (long long e = e0; e < e1; ++e) {
-        const float ww = w32[e];
-        const float4 *Ye = Y0 + (int64_t)indices_r[e] * 4;
-#pragma unroll
-        for (int p = 0; p < LM_PERM_BATCH; ++p) {
-            if (p < n_batch) {
-                const float4 z = Ye[p * pstep];
-                s[p].x = __fadd_rn(s[p].x, __fmul_rn(ww, z.x)); s[p].y = __fadd_rn(s[p].y, __fmul_rn(ww, z.y));
-                s[p].z = __fadd_rn(s[p].z, __fmul_rn(ww, z.z)); s[p].w = __fadd_rn(s[p].w, __fmul_rn(ww, z.w));
-            }
-        }
-    }
-    int cx = 0, cy = 0, cz = 0, cw = 0;
-#pragma unroll
-    for (int p = 0; p < LM_PERM_BATCH; ++p) {
-        if (p < n_batch) {
-            const float4 zi = Y0[r * 4 + p * pstep];
-            cx += fabsf(__fmul_rn(zi.x, s[p].x)) >= ax; cy += fabsf(__fmul_rn(zi.y, s[p].y)) >= ay;
-            cz += fabsf(__fmul_rn(zi.z, s[p].z)) >= az; cw += fabsf(__fmul_rn(zi.w, s[p].w)) >= aw;
-        }
-    }
-    int4 *dst = reinterpret_cast<int4 *>(count) + o;
-    if (first) *dst = make_int4(cx, cy, cz, cw);
-    else { const int4 c0 = *dst; *dst = make_int4(c0.x + cx, c0.y + cy, c0.z + cz, c0.w + cw); }
-}
-
-// ---- the two phases over CODE rows (r03): count data, every value an integer in [0, LM_CODES) ----
-// A gene with few distinct values has few distinct z: z = table[gene][value].  The permuted matrix of a batch is then
-// moved around as the uint8 rows of the scoring kernel's narrow copy (128 genes per 128-byte row instead of 16 per
-// 64-byte float tile row: an eighth of the gathered, written and re-read bytes), and the float32 z of a neighbour is
-// looked up in LDS when it is used.  table[gene][v] is k_lm_standardize's own expression at x = v, so every product
-// and every sum is the float path's, bit for bit.  With all weights equal (a row-normalised kNN graph) a second table
-// holds w * z, the product the float path rounds before it adds.
-#define LM_CODES 32          // values 0 .. 31
-#define LM_TAB_STRIDE 36     // floats per table row: (q, value) pairs of one load land in different LDS banks for small values
-#define LM_U8_QUAD 4         // permutations in flight per thread
-#define LM_U8_BATCH_MAX 32   // permutations per launch (the counts are read and written once per launch)
-
-// table rows in the order the kernel's threads use them: row = 8 b + q holds the gene of byte b of lane q's 16 bytes
-// of a narrow row (k_pack_narrow<8>: tile 8 grp + b / 2, slot 2 q + b % 2);  tab[0] = z, tab[1] = w z
-__global__ __launch_bounds__(256) void k_lm_ztab(const float *__restrict__ mean32, const float *__restrict__ sd32,
-                                                 int64_t tiles16, float w, float *__restrict__ tab, int groups)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= groups * 128 * LM_TAB_STRIDE) return;
-    const int v = t % LM_TAB_STRIDE, row = (t / LM_TAB_STRIDE) % 128, grp = t / (LM_TAB_STRIDE * 128);
-    const int b = row >> 3, q = row & 7;
-    const int64_t tile = 8 * (int64_t)grp + (b >> 1);
-    float z = 0.f;
-    if (tile < tiles16 && v < LM_CODES) {
-        const int64_t g = tile * SC_TILE + 2 * q + (b & 1);
-        z = (float)__ddiv_rn((double)__fsub_rn((float)v, mean32[g]), (double)sd32[g]);
-    }
-    tab[t] = z;
-    tab[(size_t)groups * 128 * LM_TAB_STRIDE + t] = __fmul_rn(w, z);
-}
-
-// Ys8[p][grp][r] = X8[grp][perm_p[order[r]]]   thread = (r, q), grid.y = group, grid.z = permutation of the batch
-__global__ __launch_bounds__(256) void k_lm_gather_u8(const uint4 *__restrict__ X8, const int32_t *__restrict__ order,
-                                                      const int32_t *__restrict__ perm, int64_t pstride, int64_t n,
-                                                      int groups, uint4 *__restrict__ Ys8)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t r = t >> 3;
-    const int q = (int)(t & 7);
-    if (r >= n) return;
-    const int32_t src = perm[(int64_t)blockIdx.z * pstride + order[r]];
-    Ys8[(((int64_t)blockIdx.z * groups + blockIdx.y) * n + r) * 8 + q] = X8[((int64_t)blockIdx.y * n + src) * 8 + q];
-}
-
-// count[tile][cell][16] += #{p in batch : |y[r] * sum_e w_e y[rank(col_e)]| >= |I[cell]|}, y = table[code], cell = order[r]
-// thread = (r, q): the 16 genes of lane q's 16 bytes, LM_U8_QUAD permutations at a time; edges in the row's order.
-template <bool UNI>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UNI ? 4 : 3, 4))) void k_lm_count_u8(const long long *__restrict__ indptr,
-                                                     const int32_t *__restrict__ indices_r, const float *__restrict__ w32,
-                                                     const int32_t *__restrict__ order, const uint4 *__restrict__ Ys8,
-                                                     const float *__restrict__ I32, const float *__restrict__ tab,
-                                                     int n_batch, int64_t tiles, int groups, int32_t *__restrict__ count,
-                                                     int64_t n, int first)
-{
-    __shared__ float tz[128 * LM_TAB_STRIDE];
-    __shared__ float tw[UNI ? 128 * LM_TAB_STRIDE : 1];
-    const int grp = blockIdx.y;
-    for (int k = threadIdx.x; k < 128 * LM_TAB_STRIDE; k += 256) {
-        tz[k] = tab[(size_t)grp * 128 * LM_TAB_STRIDE + k];
-        if (UNI) tw[k] = tab[((size_t)groups + grp) * 128 * LM_TAB_STRIDE + k];
-    }
-    __syncthreads();
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t r = t >> 3;
-    const int q = (int)(t & 7);
-    if (r >= n) return;
-    const int64_t i = order[r];
-    float a[16];
-    uint32_t cnt[4] = {0u, 0u, 0u, 0u};   // 16 counts of <= LM_U8_BATCH_MAX, 8 bits each
-    static_assert(LM_U8_BATCH_MAX < 256, "packed per-launch counts");
-#pragma unroll
-    for (int b = 0; b < 16; ++b) {
-        const int64_t tile = 8 * (int64_t)grp + (b >> 1);
-        a[b] = tile < tiles ? fabsf(I32[tile * n * SC_TILE + i * SC_TILE + 2 * q + (b & 1)]) : 0.f;
-    }
-    const long long e0 = indptr[i], e1 = indptr[i + 1];
-    const int64_t pstep = (int64_t)groups * n * 8;   // uint4 stride between the permutations of the batch
-    const uint4 *Y0 = Ys8 + (int64_t)grp * n * 8 + q;
-    const float *zq = tz + q * LM_TAB_STRIDE;         // + b * 8 * LM_TAB_STRIDE + value
-    const float *wq = (UNI ? tw : tz) + q * LM_TAB_STRIDE;
-    typedef float v2f __attribute__((ext_vector_type(2)));   // two genes per v_pk_add_f32 / v_pk_mul_f32: IEEE per component
-    for (int p0 = 0; p0 < n_batch; p0 += LM_U8_QUAD) {
-        v2f s[LM_U8_QUAD][8];
-#pragma unroll
-        for (int p = 0; p < LM_U8_QUAD; ++p)
-#pragma unroll
-            for (int b = 0; b < 8; ++b) s[p][b] = (v2f){0.f, 0.f};
-        for (long long e = e0; e < e1; ++e) {
-            const float ww = w32[e];
-            const v2f ww2 = {ww, ww};
-            const uint4 *Ye = Y0 + (int64_t)indices_r[e] * 8 + (int64_t)p0 * pstep;
-            uint4 row[LM_U8_QUAD];
-#pragma unroll
-            for (int p = 0; p < LM_U8_QUAD; ++p) row[p] = p0 + p < n_batch ? Ye[p * pstep] : make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-            for (int p = 0; p < LM_U8_QUAD; ++p) {
-                const uint32_t wd[4] = {row[p].x, row[p].y, row[p].z, row[p].w};
-#pragma unroll
-                for (int b = 0; b < 16; b += 2) {
-                    const uint32_t v0 = (wd[b >> 2] >> (8 * (b & 3))) & 0xffu, v1 = (wd[b >> 2] >> (8 * (b & 3) + 8)) & 0xffu;
-                    v2f term = {wq[b * 8 * LM_TAB_STRIDE + v0], wq[(b + 1) * 8 * LM_TAB_STRIDE + v1]};
-                    if (!UNI) term = ww2 * term;          // (-ffp-contract=off: product and sum are rounded separately)
-                    s[p][b >> 1] = s[p][b >> 1] + term;
-                }
-            }
-        }
-#pragma unroll
-        for (int p = 0; p < LM_U8_QUAD; ++p) {
-            if (p0 + p < n_batch) {
-                const uint4 own = Y0[r * 8 + (int64_t)(p0 + p) * pstep];
-                const uint32_t wd[4] = {own.x, own.y, own.z, own.w};
-#pragma unroll
-                for (int b = 0; b < 16; b += 2) {
-                    const uint32_t v0 = (wd[b >> 2] >> (8 * (b & 3))) & 0xffu, v1 = (wd[b >> 2] >> (8 * (b & 3) + 8)) & 0xffu;
-                    const v2f zi = {zq[b * 8 * LM_TAB_STRIDE + v0], zq[(b + 1) * 8 * LM_TAB_STRIDE + v1]};
-                    const v2f ip = zi * s[p][b >> 1];
-                    cnt[b >> 2] += (fabsf(ip.x) >= a[b] ? 1u : 0u) << (8 * (b & 3));
-                    cnt[b >> 2] += (fabsf(ip.y) >= a[b + 1] ? 1u : 0u) << (8 * (b & 3) + 8);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int tt = 0; tt < 8; ++tt) {
-        const int64_t tile = 8 * (int64_t)grp + tt;
-        if (tile >= tiles) continue;
-        int2 *dst = reinterpret_cast<int2 *>(count + tile * n * SC_TILE + i * SC_TILE + 2 * q);
-        const int ca = (int)((cnt[tt >> 1] >> (16 * (tt & 1))) & 0xffu), cb = (int)((cnt[tt >> 1] >> (16 * (tt & 1) + 8)) & 0xffu);
-        if (first) *dst = make_int2(ca, cb);
-        else { const int2 c0 = *dst; *dst = make_int2(c0.x + ca, c0.y + cb); }
-    }
-}
-
-// tile layout [tile][cell][16] -> row-major [cell][n_genes]
-template <typename T>
-__global__ __launch_bounds__(256) void k_untile(const T *__restrict__ tiles, T *__restrict__ out, int64_t n,
-                                                int64_t n_genes)
-{
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * n_genes) return;
-    int64_t i = t / n_genes, g = t - i * n_genes;
-    out[t] = tiles[(g >> 4) * n * SC_TILE + i * SC_TILE + (g & 15)];
-}
-
-// Is every loaded value an integer in [0, LM_CODES)?  (one pass over the tiles + one synchronisation; SC_LM_FLOAT_ROWS
-// set: development switch, the float-row form for A/B runs and tests)
-static int lm_codes_ok(sc_ctx *c, bool *ok)
-{
-    *ok = false;
-    if (getenv("SC_LM_FLOAT_ROWS") || c->e_n >= ((int64_t)1 << 24)) return SC_OK;   // (16.7M cells: 2 GB of code rows per permutation and group)
-    const int64_t n = c->e_n, T = c->e_tiles, G = c->e_genes;
-    const int64_t Gpad = align_up64(T, 8) * SC_TILE;
-    SC_TRY(c->g_flags.ensure(sizeof(uint32_t) * (size_t)Gpad, &c->mem));
-    SC_TRY(c->g_xmax.ensure(sizeof(uint32_t) * (size_t)Gpad, &c->mem));
-    SC_HIP(hipMemsetAsync(c->g_flags.p, 0, sizeof(uint32_t) * (size_t)Gpad, c->stream));
-    SC_HIP(hipMemsetAsync(c->g_xmax.p, 0, sizeof(uint32_t) * (size_t)Gpad, c->stream));
-    hipLaunchKernelGGL(k_gene_stats, dim3((unsigned)ceil_div64(n, RED_ROWS_PER_BLOCK), (unsigned)T), dim3(256), 0, c->stream,
-                       c->X.as<double>(), n, c->g_flags.as<uint32_t>(), c->g_xmax.as<uint32_t>());
-    SC_HIP(hipGetLastError());
-    std::vector<uint32_t> flags((size_t)Gpad), xmax((size_t)Gpad);
-    SC_HIP(hipMemcpyAsync(flags.data(), c->g_flags.p, sizeof(uint32_t) * (size_t)Gpad, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(xmax.data(), c->g_xmax.p, sizeof(uint32_t) * (size_t)Gpad, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-    for (int64_t g = 0; g < G; ++g)
-        if ((flags[(size_t)g] & 1u) || xmax[(size_t)g] >= LM_CODES) return SC_OK;
-    *ok = true;
-    return SC_OK;
-}
-
-// One local Moran job: the operands of the per-cell permutation counts (sc_local_moran, sc_local_moran_seeded)
-struct LmJob {
-    int64_t n = 0, G = 0, T = 0;
-    size_t tile_f = 0;
-    float *mean32 = nullptr, *sd32 = nullptr, *Z32 = nullptr, *I32 = nullptr, *Lag32 = nullptr;
-    int32_t *cnt = nullptr;
-    unsigned char *zero = nullptr;
-    dim3 gc;
-    int mode = 2;        // 1: uint8 code rows, 2: float rows
-    int groups = 0;      // code rows: 128-gene groups
-    int64_t batch = 0;   // permutations per launch
-    bool uni = false;
-};
-
-// statistics in numpy's order, z, observed lag and I; then the form of the permutation counts and its buffers
-static int lm_prepare(sc_ctx *c, int64_t n_perm, LmJob &j)
-{
-    const int64_t n = c->e_n, G = c->e_genes, T = c->e_tiles;
-    c->lm_valid = false;
-    const size_t tile_f = (size_t)T * n * SC_TILE;
-    // per-gene mean and E[x^2] with numpy's own summation order, in the matrix dtype (see k_npc_*)
-    SC_TRY(colsum<OP_NZ>(c, c->X.as<double>(), nullptr, c->g_Inum.as<double>(), 1.0));
-    SC_TRY(c->lee_out.ensure(sizeof(double) * 2 * (size_t)(T * SC_TILE), &c->mem));
-    {
-        const int64_t nblk = ceil_div64(n, NPC_CELLS), max_leaves = n / 32 + 64;
-        const size_t tsz = c->e_dtype == SC_F32 ? sizeof(float) : sizeof(double);
-        SC_TRY(c->np_cnt.ensure(sizeof(uint32_t) * (size_t)(T * nblk * 16), &c->mem));
-        SC_TRY(c->np_comp.ensure(tsz * (size_t)(T * SC_TILE) * (size_t)n, &c->mem));
-        SC_TRY(c->np_leaves.ensure(sizeof(uint2) * (size_t)G * (size_t)max_leaves + sizeof(uint32_t) * (size_t)G, &c->mem));
-        SC_TRY(c->np_leafsum.ensure(tsz * 2 * (size_t)G * (size_t)max_leaves, &c->mem));
-        uint2 *leaves = c->np_leaves.as<uint2>();
-        uint32_t *nleaves = reinterpret_cast<uint32_t *>(leaves + (size_t)G * (size_t)max_leaves);
-        const dim3 gw((unsigned)ceil_div64(nblk, 4), (unsigned)T);
-        hipLaunchKernelGGL(k_npc_count, gw, dim3(256), 0, c->stream, c->X.as<double>(), n, nblk, c->np_cnt.as<uint32_t>());
-        hipLaunchKernelGGL(k_npc_offsets, dim3((unsigned)ceil_div64(T * SC_TILE, 64)), dim3(64), 0, c->stream,
-                           c->np_cnt.as<uint32_t>(), nblk, T * SC_TILE);
-        hipLaunchKernelGGL(k_npc_leaves, dim3((unsigned)ceil_div64(G, 64)), dim3(64), 0, c->stream,
-                           c->g_Inum.as<double>(), G, max_leaves, leaves, nleaves);
-        const dim3 gl((unsigned)ceil_div64(max_leaves, 256), (unsigned)G, 2);
-        if (c->e_dtype == SC_F32) {
-            hipLaunchKernelGGL(k_npc_scatter<float>, gw, dim3(256), 0, c->stream, c->X.as<double>(), n, nblk,
-                               c->np_cnt.as<uint32_t>(), c->np_comp.as<float>());
-            hipLaunchKernelGGL(k_npc_leafsum<float>, gl, dim3(256), 0, c->stream, c->np_comp.as<float>(), n, leaves,
-                               nleaves, max_leaves, c->np_leafsum.as<float>());
-            hipLaunchKernelGGL(k_npc_combine<float>, dim3((unsigned)ceil_div64(2 * G, 64)), dim3(64), 0, c->stream,
-                               c->np_comp.as<float>(), n, c->g_Inum.as<double>(), c->np_leafsum.as<float>(), max_leaves, G,
-                               c->lee_out.as<float>());
-        } else {
-            hipLaunchKernelGGL(k_npc_scatter<double>, gw, dim3(256), 0, c->stream, c->X.as<double>(), n, nblk,
-                               c->np_cnt.as<uint32_t>(), c->np_comp.as<double>());
-            hipLaunchKernelGGL(k_npc_leafsum<double>, gl, dim3(256), 0, c->stream, c->np_comp.as<double>(), n, leaves,
-                               nleaves, max_leaves, c->np_leafsum.as<double>());
-            hipLaunchKernelGGL(k_npc_combine<double>, dim3((unsigned)ceil_div64(2 * G, 64)), dim3(64), 0, c->stream,
-                               c->np_comp.as<double>(), n, c->g_Inum.as<double>(), c->np_leafsum.as<double>(), max_leaves,
-                               G, c->lee_out.as<double>());
-        }
-        SC_HIP(hipGetLastError());
-    }
-    // float work buffers: [mean32 | sd32] in g_scale (as float), zero flags in counts, Z32/Lag32/I32 in Z/Lag
-    SC_TRY(c->Z.ensure(tile_f * sizeof(double), &c->mem));    // Z32 (first half) + I32 (second half)
-    SC_TRY(c->Lag.ensure(tile_f * sizeof(double), &c->mem));  // Lag32 (first half) + counts (second half)
-    SC_TRY(c->counts.ensure((size_t)T * SC_TILE + 16, &c->mem));
-    float *mean32 = c->g_scale.as<float>(), *sd32 = mean32 + T * SC_TILE;
-    float *Z32 = c->Z.as<float>(), *I32 = Z32 + tile_f;
-    float *Lag32 = c->Lag.as<float>();
-    int32_t *cnt = reinterpret_cast<int32_t *>(Lag32 + tile_f);
-    unsigned char *zero = c->counts.as<unsigned char>();
-    if (c->e_dtype == SC_F32)
-        hipLaunchKernelGGL(k_lm_stats<float>, dim3((unsigned)ceil_div64(T * SC_TILE, 256)), dim3(256), 0, c->stream,
-                           c->lee_out.as<float>(), mean32, sd32, zero, G, T * SC_TILE);
-    else
-        hipLaunchKernelGGL(k_lm_stats<double>, dim3((unsigned)ceil_div64(T * SC_TILE, 256)), dim3(256), 0, c->stream,
-                           c->lee_out.as<double>(), mean32, sd32, zero, G, T * SC_TILE);
-    dim3 ge((unsigned)ceil_div64(n * SC_TILE, 256), (unsigned)T);
-    hipLaunchKernelGGL(k_lm_standardize, ge, dim3(256), 0, c->stream, c->X.as<double>(), mean32, sd32, Z32, n);
-    dim3 gc((unsigned)ceil_div64(n * 4, 256), (unsigned)T);
-    hipLaunchKernelGGL(k_lm_observed, gc, dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
-                       c->g_indices.as<int32_t>(), c->g_data.as<double>(), Z32, Lag32, I32, n);
-    SC_HIP(hipGetLastError());
-    j.n = n; j.G = G; j.T = T; j.tile_f = tile_f;
-    j.mean32 = mean32; j.sd32 = sd32; j.Z32 = Z32; j.I32 = I32; j.Lag32 = Lag32; j.cnt = cnt; j.zero = zero; j.gc = gc;
-    if (n_perm <= 0) return SC_OK;
-    SC_TRY(sc_graph_ensure_order(c));
-    bool codes = false;
-    SC_TRY(lm_codes_ok(c, &codes));
-    if (codes) {
-        // count data: the permuted matrix travels as uint8 code rows, z is looked up where it is used (k_lm_count_u8)
-        j.mode = 1;
-        j.groups = (int)ceil_div64(T, 8);
-        const size_t row_bytes = (size_t)j.groups * (size_t)n * 128;
-        SC_TRY(c->X32.ensure(sizeof(float) * (size_t)((T + 1) / 2) * n * 32, &c->mem));
-        SC_TRY(c->lm_tab.ensure(sizeof(float) * 2 * (size_t)j.groups * 128 * LM_TAB_STRIDE, &c->mem));
-        int64_t batch = (int64_t)(((size_t)4 << 30) / row_bytes) / LM_U8_QUAD * LM_U8_QUAD;
-        batch = batch < LM_U8_QUAD ? LM_U8_QUAD : batch > LM_U8_BATCH_MAX ? LM_U8_BATCH_MAX : batch;
-        if (batch > n_perm) batch = align_up64(n_perm, LM_U8_QUAD);
-        j.batch = batch;
-        SC_TRY(c->lm_ys.ensure(row_bytes * (size_t)batch, &c->mem));
-        hipLaunchKernelGGL(k_pack_narrow<8>, dim3((unsigned)ceil_div64(n * 8, 256), (unsigned)j.groups), dim3(256), 0, c->stream,
-                           c->X.as<double>(), c->X32.as<uint4>(), n, T);
-        j.uni = c->g_uniform_w > 0.0;
-        hipLaunchKernelGGL(k_lm_ztab, dim3((unsigned)ceil_div64((int64_t)j.groups * 128 * LM_TAB_STRIDE, 256)), dim3(256), 0, c->stream,
-                           mean32, sd32, T, j.uni ? (float)c->g_uniform_w : 0.f, c->lm_tab.as<float>(), j.groups);
-        SC_HIP(hipGetLastError());
-    } else {
-        j.mode = 2;
-        j.batch = LM_PERM_BATCH;
-        SC_TRY(c->lm_ys.ensure(sizeof(float) * (size_t)LM_PERM_BATCH * tile_f, &c->mem));
-    }
-    return SC_OK;
-}
-
-// counts of permutations [p0, p1) of the job (rows row0 + p of the forward table); p0 == 0 starts the counts
-static int lm_count(sc_ctx *c, const LmJob &j, int64_t row0, int64_t p0, int64_t p1)
-{
-    const int64_t n = j.n, T = j.T;
-    if (p1 <= p0) return SC_OK;
-    KernelTimerScope ts(c, SC_K_LEE_PERM);
-    if (j.mode == 1) {
-        const dim3 g8((unsigned)ceil_div64(n * 8, 256), (unsigned)j.groups);
-        auto count_u8 = j.uni ? k_lm_count_u8<true> : k_lm_count_u8<false>;
-        for (int64_t p = p0; p < p1; p += j.batch) {
-            const int nb = (int)(p1 - p < j.batch ? p1 - p : j.batch);
-            hipLaunchKernelGGL(k_lm_gather_u8, dim3(g8.x, g8.y, (unsigned)nb), dim3(256), 0, c->stream, c->X32.as<uint4>(),
-                               c->g_order.as<int32_t>(), c->perm.as<int32_t>() + (row0 + p) * c->p_stride, c->p_stride,
-                               n, j.groups, c->lm_ys.as<uint4>());
-            hipLaunchKernelGGL(count_u8, g8, dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
-                               c->g_indices_r.as<int32_t>(), c->g_w32.as<float>(), c->g_order.as<int32_t>(),
-                               c->lm_ys.as<uint4>(), j.I32, c->lm_tab.as<float>(), nb, T, j.groups, j.cnt, n, p == 0 ? 1 : 0);
-        }
-    } else {
-        for (int64_t p = p0; p < p1; p += j.batch) {
-            const int nb = (int)(p1 - p < j.batch ? p1 - p : j.batch);
-            hipLaunchKernelGGL(k_lm_gather_sorted, dim3(j.gc.x, (unsigned)T, (unsigned)nb), dim3(256), 0, c->stream, j.Z32,
-                               c->g_order.as<int32_t>(), c->perm.as<int32_t>() + (row0 + p) * c->p_stride, c->p_stride,
-                               n, T, c->lm_ys.as<float>());
-            hipLaunchKernelGGL(k_lm_count_sorted, j.gc, dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
-                               c->g_indices_r.as<int32_t>(), c->g_w32.as<float>(), c->g_order.as<int32_t>(),
-                               c->lm_ys.as<float>(), j.I32, nb, T, j.cnt, n, p == 0 ? 1 : 0);
-        }
-    }
-    SC_HIP(hipGetLastError());
-    return SC_OK;
-}
-
-// un-tile into row-major (cells x genes) staging and copy back
-static int lm_finish(sc_ctx *c, const LmJob &j, int64_t n_perm, float *z_out, float *lag_out, float *I_out,
-                     int32_t *count_out, uint8_t *zero_var_out, bool arrays_done = false)
-{
-    const int64_t n = j.n, G = j.G;
-    const bool counts = n_perm > 0 && count_out;
-    if (!arrays_done || counts) SC_TRY(c->lee_a.ensure(sizeof(float) * (size_t)n * (size_t)G, &c->mem));   // (staging)
-    unsigned gu = (unsigned)ceil_div64(n * G, 256);
-    struct { const float *src; float *dst; } outs[3] = {{j.Z32, z_out}, {j.Lag32, lag_out}, {j.I32, I_out}};
-    for (auto &o : outs) {
-        if (arrays_done) break;   // (a helper thread has copied them out beside the pipeline)
-        hipLaunchKernelGGL(k_untile<float>, dim3(gu), dim3(256), 0, c->stream, o.src, c->lee_a.as<float>(), n, G);
-        SC_HIP(hipMemcpyAsync(o.dst, c->lee_a.p, sizeof(float) * (size_t)n * (size_t)G, hipMemcpyDeviceToHost,
-                              c->stream));
-    }
-    if (counts) {
-        hipLaunchKernelGGL(k_untile<int32_t>, dim3(gu), dim3(256), 0, c->stream, j.cnt, c->lee_a.as<int32_t>(), n, G);
-        SC_HIP(hipMemcpyAsync(count_out, c->lee_a.p, sizeof(int32_t) * (size_t)n * (size_t)G, hipMemcpyDeviceToHost,
-                              c->stream));
-    }
-    if (zero_var_out)
-        SC_HIP(hipMemcpyAsync(zero_var_out, j.zero, (size_t)G, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipGetLastError());
-    SC_HIP(hipStreamSynchronize(c->stream));
-    c->lm_valid = true;  // z / lag / counts stay resident for sc_local_moran_hist / sc_local_moran_classify
-    c->lm_perms = n_perm;
-    return SC_OK;
-}
-
-extern "C" int sc_local_moran(sc_ctx *c, int64_t n_perm, int64_t perm_row0, float *z_out, float *lag_out,
-                              float *I_out, int32_t *count_out, uint8_t *zero_var_out)
-{
-    SC_REQUIRE(c && z_out && lag_out && I_out, SC_ERR_INVALID, "sc_local_moran: null pointer");
-    SC_REQUIRE(n_perm >= 0 && perm_row0 >= 0, SC_ERR_INVALID, "sc_local_moran: negative size");
-    SC_HIP(hipSetDevice(c->device));
-    if (n_perm > 0) SC_TRY(sc_perm_forward_ensure(c));
-    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_local_moran: no expression loaded");
-    SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_local_moran: graph missing or size mismatch");
-    c->lm_valid = false;
-    if (n_perm > 0) {
-        SC_REQUIRE(c->p_n == c->e_n && perm_row0 + n_perm <= c->p_count, SC_ERR_STATE,
-                   "sc_local_moran: needs permutation rows [%lld, %lld) of length %lld", (long long)perm_row0,
-                   (long long)(perm_row0 + n_perm), (long long)c->e_n);
-    }
-    LmJob j;
-    SC_TRY(lm_prepare(c, n_perm, j));
-    SC_TRY(lm_count(c, j, perm_row0, 0, n_perm));
-    return lm_finish(c, j, n_perm, z_out, lag_out, I_out, count_out, zero_var_out);
-}
-
-// A thread that is joined when it is destroyed (C++17 has no std::jthread)
-struct JoiningThread {
-    std::thread t;
-    ~JoiningThread() { if (t.joinable()) t.join(); }
-};
-
-// The same with the permutations drawn here: n_perm numpy-exact permutations of the cells from state6 (as
-// sc_perm_generate would draw them; state6 is advanced the same way, the table stays resident), generated chunk
-// by chunk while the per-cell counts of the finished chunks are taken -- the generator's chain is the longest part of
-// a local Moran call, and the counts hide behind it.  Same outputs as sc_perm_generate + sc_local_moran.
-extern "C" int sc_local_moran_seeded(sc_ctx *c, uint64_t *state6, int64_t n_perm, float *z_out, float *lag_out,
-                                     float *I_out, int32_t *count_out, uint8_t *zero_var_out)
-{
-    SC_REQUIRE(c && state6 && z_out && lag_out && I_out, SC_ERR_INVALID, "sc_local_moran_seeded: null pointer");
-    SC_REQUIRE(n_perm >= 1 && n_perm <= (1 << 24), SC_ERR_INVALID, "sc_local_moran_seeded: n_perm=%lld out of range", (long long)n_perm);
-    SC_HIP(hipSetDevice(c->device));
-    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_local_moran_seeded: no expression loaded");
-    SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_local_moran_seeded: graph missing or size mismatch");
-    c->lm_valid = false;
-    LmJob j;
-    // r04: z, lag and I are final once the preparation has run -- three (cells x genes) float arrays, 1.2 GB at 10^6 cells x
-    // 100 genes, that r03 copied to the caller's (pageable) arrays AFTER the last count, 0.1 s of a 0.5-s call.  A helper
-    // thread un-tiles and copies them out on a stream of its own while the generator and the counts run (neither uses
-    // the PCIe link); this thread keeps enqueuing the pipeline.
-    int copier_rc = SC_OK;
-    std::optional<JoiningThread> copier;   // (declared after what its thread writes; reset() joins)
-    bool copier_started = false;
-    auto prepare = [&]() -> int {
-        SC_TRY(lm_prepare(c, n_perm, j));
-        if (copier_started) return SC_OK;
-        if (!c->stream_out) SC_HIP(hipStreamCreateWithFlags(&c->stream_out, hipStreamNonBlocking));
-        SC_TRY(c->lm_out.ensure(sizeof(float) * (size_t)j.n * (size_t)j.G, &c->mem));
-        hipEvent_t ready;
-        SC_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-        SC_HIP(hipEventRecord(ready, c->stream));
-        SC_HIP(hipStreamWaitEvent(c->stream_out, ready, 0));
-        SC_HIP(hipEventDestroy(ready));
-        const LmJob jj = j;
-        try {   // (no thread to be had: the arrays are copied at the end, as in r03)
-            copier.emplace().t = std::thread([c, jj, z_out, lag_out, I_out, &copier_rc]() {
-            if (hipSetDevice(c->device) != hipSuccess) { copier_rc = SC_ERR_HIP; return; }
-            const unsigned gu = (unsigned)ceil_div64(jj.n * jj.G, 256);
-            const struct { const float *src; float *dst; } outs[3] = {{jj.Z32, z_out}, {jj.Lag32, lag_out}, {jj.I32, I_out}};
-            for (const auto &o : outs) {
-                hipLaunchKernelGGL(k_untile<float>, dim3(gu), dim3(256), 0, c->stream_out, o.src, c->lm_out.as<float>(), jj.n, jj.G);
-                if (hipMemcpyAsync(o.dst, c->lm_out.p, sizeof(float) * (size_t)jj.n * (size_t)jj.G, hipMemcpyDeviceToHost, c->stream_out) != hipSuccess ||
-                    hipStreamSynchronize(c->stream_out) != hipSuccess) {   // (the staging buffer is reused by the next array)
-                    copier_rc = SC_ERR_HIP;
-                    return;
-                }
-            }
-            });
-            copier_started = true;
-        } catch (...) {
-            copier_started = false;
-        }
-        return SC_OK;
-    };
-    auto count = [&](int64_t p0, int64_t p1) -> int { return lm_count(c, j, 0, p0, p1); };
-    // a job that fails its verification is rerun with the sequential scan: the counts restart at permutation 0, and the
-    // copier is joined first (the second preparation rewrites what it reads -- with the same values)
-    const int rc = permgen_rerun_on_failure(
-        c, [&]() { return sc_perm_pipeline(c, state6, c->e_n, n_perm, 0, 2, prepare, count); },
-        [&]() { copier.reset(); return SC_OK; });
-    copier.reset();
-    SC_TRY(rc);
-    if (copier_started && copier_rc != SC_OK) {
-        sc_set_error("sc_local_moran_seeded: the copy of z / lag / I to the host failed");
-        return copier_rc;
-    }
-    return lm_finish(c, j, n_perm, z_out, lag_out, I_out, count_out, zero_var_out, copier_started);
-}
-
-// hist[gene][c] = cells of the gene with permutation count c (LDS-private per workgroup while 16 genes' worth fits)
-#define LMH_LDS 12288
-__global__ __launch_bounds__(256) void k_lm_hist(const int32_t *__restrict__ cnt, int64_t n, int P1,
-                                                 unsigned long long *__restrict__ hist)
-{
-    __shared__ uint32_t h[LMH_LDS];
-    const int64_t tile = blockIdx.y;
-    const int32_t *ct = cnt + tile * n * SC_TILE;
-    unsigned long long *ht = hist + tile * SC_TILE * P1;
-    const bool priv = SC_TILE * P1 <= LMH_LDS;
-    if (priv) {
-        for (int k = threadIdx.x; k < SC_TILE * P1; k += 256) h[k] = 0;
-        __syncthreads();
-    }
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n * SC_TILE; t += (int64_t)gridDim.x * 256) {
-        int c = ct[t];
-        c = c < 0 ? 0 : (c >= P1 ? P1 - 1 : c);
-        const int slot = (int)(t & 15);
-        if (priv) atomicAdd(&h[slot * P1 + c], 1u);
-        else atomicAdd(&ht[slot * P1 + c], 1ull);
-    }
-    if (priv) {
-        __syncthreads();
-        for (int k = threadIdx.x; k < SC_TILE * P1; k += 256)
-            if (h[k]) atomicAdd(&ht[k], (unsigned long long)h[k]);
-    }
-}
-
-extern "C" int sc_local_moran_hist(sc_ctx *c, int64_t *hist_out)
-{
-    SC_REQUIRE(c && hist_out, SC_ERR_INVALID, "sc_local_moran_hist: null pointer");
-    SC_REQUIRE(c->lm_valid && c->lm_perms > 0, SC_ERR_STATE, "sc_local_moran_hist: no sc_local_moran result with permutations");
-    SC_HIP(hipSetDevice(c->device));
-    const int64_t n = c->e_n, G = c->e_genes, T = c->e_tiles;
-    const int P1 = (int)c->lm_perms + 1;
-    const size_t tile_f = (size_t)T * n * SC_TILE;
-    const int32_t *cnt = reinterpret_cast<const int32_t *>(c->Lag.as<float>() + tile_f);
-    SC_TRY(c->lee_b.ensure(sizeof(unsigned long long) * (size_t)(T * SC_TILE) * (size_t)P1, &c->mem));
-    SC_HIP(hipMemsetAsync(c->lee_b.p, 0, sizeof(unsigned long long) * (size_t)(T * SC_TILE) * (size_t)P1, c->stream));
-    hipLaunchKernelGGL(k_lm_hist, dim3(256, (unsigned)T), dim3(256), 0, c->stream, cnt, n, P1,
-                       c->lee_b.as<unsigned long long>());
-    SC_HIP(hipGetLastError());
-    SC_HIP(hipMemcpyAsync(hist_out, c->lee_b.p, sizeof(int64_t) * (size_t)G * (size_t)P1, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-    return SC_OK;
-}
-
-// p = p_tab[g][count], p_adj = padj_tab[g][count], LISA quadrant (AC:219-265): 1 HH, 2 LL, 3 HL, 4 LH from the signs of
-// z and lag, 0 where p_adj >= alpha or the gene is flagged; row-major outputs
-__global__ __launch_bounds__(256) void k_lm_classify(const float *__restrict__ Z32, const float *__restrict__ Lag32,
-                                                     const int32_t *__restrict__ cnt, int64_t n, int64_t G, int P1,
-                                                     const float *__restrict__ p_tab, const float *__restrict__ padj_tab,
-                                                     const unsigned char *__restrict__ force_ns, float alpha,
-                                                     float *__restrict__ p_out, float *__restrict__ padj_out,
-                                                     signed char *__restrict__ q_out)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * G) return;
-    const int64_t i = t / G, g = t - i * G;
-    const int64_t src = (g >> 4) * n * SC_TILE + i * SC_TILE + (g & 15);
-    const float z = Z32[src], lag = Lag32[src];
-    signed char q = 0;
-    if (z > 0.f && lag > 0.f) q = 1;
-    if (z < 0.f && lag < 0.f) q = 2;
-    if (z > 0.f && lag < 0.f) q = 3;
-    if (z < 0.f && lag > 0.f) q = 4;
-    if (P1 > 0) {
-        int c = cnt[src];
-        c = c < 0 ? 0 : (c >= P1 ? P1 - 1 : c);
-        const float pa = padj_tab[g * P1 + c];
-        p_out[t] = p_tab[g * P1 + c];
-        padj_out[t] = pa;
-        if (pa >= alpha) q = 0;
-    }
-    if (force_ns[g]) q = 0;
-    q_out[t] = q;
-}
-
-extern "C" int sc_local_moran_classify(sc_ctx *c, const float *p_tab, const float *padj_tab, const uint8_t *force_ns,
-                                       float alpha, float *p_out, float *padj_out, int8_t *quadrant_out)
-{
-    SC_REQUIRE(c && force_ns && quadrant_out, SC_ERR_INVALID, "sc_local_moran_classify: null pointer");
-    SC_REQUIRE(c->lm_valid, SC_ERR_STATE, "sc_local_moran_classify: no sc_local_moran result");
-    SC_HIP(hipSetDevice(c->device));
-    const int64_t n = c->e_n, G = c->e_genes, T = c->e_tiles;
-    const int P1 = c->lm_perms > 0 ? (int)c->lm_perms + 1 : 0;
-    if (P1 > 0) SC_REQUIRE(p_tab && padj_tab && p_out && padj_out, SC_ERR_INVALID, "sc_local_moran_classify: tables and outputs required with permutations");
-    const size_t tile_f = (size_t)T * n * SC_TILE, cells = (size_t)n * (size_t)G;
-    const float *Z32 = c->Z.as<float>(), *Lag32 = c->Lag.as<float>();
-    const int32_t *cnt = reinterpret_cast<const int32_t *>(Lag32 + tile_f);
-    // device staging: [p | p_adj | quadrant] row-major, tables, flags
-    SC_TRY(c->lee_a.ensure(sizeof(float) * 2 * cells + cells + 64, &c->mem));
-    SC_TRY(c->lee_b.ensure(sizeof(float) * 2 * (size_t)G * (size_t)(P1 > 0 ? P1 : 1) + (size_t)G + 64, &c->mem));
-    float *d_p = c->lee_a.as<float>(), *d_pa = d_p + cells;
-    signed char *d_q = reinterpret_cast<signed char *>(d_pa + cells);
-    float *d_pt = c->lee_b.as<float>(), *d_at = d_pt + (size_t)G * (size_t)(P1 > 0 ? P1 : 1);
-    unsigned char *d_f = reinterpret_cast<unsigned char *>(d_at + (size_t)G * (size_t)(P1 > 0 ? P1 : 1));
-    if (P1 > 0) {
-        SC_HIP(hipMemcpyAsync(d_pt, p_tab, sizeof(float) * (size_t)G * P1, hipMemcpyHostToDevice, c->stream));
-        SC_HIP(hipMemcpyAsync(d_at, padj_tab, sizeof(float) * (size_t)G * P1, hipMemcpyHostToDevice, c->stream));
-    }
-    SC_HIP(hipMemcpyAsync(d_f, force_ns, (size_t)G, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_lm_classify, dim3((unsigned)ceil_div64(n * G, 256)), dim3(256), 0, c->stream, Z32, Lag32, cnt, n,
-                       G, P1, d_pt, d_at, d_f, alpha, d_p, d_pa, d_q);
-    SC_HIP(hipGetLastError());
-    if (P1 > 0) {
-        SC_HIP(hipMemcpyAsync(p_out, d_p, sizeof(float) * cells, hipMemcpyDeviceToHost, c->stream));
-        SC_HIP(hipMemcpyAsync(padj_out, d_pa, sizeof(float) * cells, hipMemcpyDeviceToHost, c->stream));
-    }
-    SC_HIP(hipMemcpyAsync(quadrant_out, d_q, cells, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-    return SC_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// N2: Local Lee's L for one pair (AC:1394-1413): z-scores, lag = W z_y, L_local = z_x * lag, and the
-// optional per-cell permutation count  #{p : |float32(z_x[i] * (W z_y[perm_p])[i])| >= |L_local[i]|}
-// ------------------------------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256) void k_vec_mul(const double *__restrict__ a, const double *__restrict__ b,
-                                                 double *__restrict__ out, int64_t n)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = __dmul_rn(a[i], b[i]);
-}
-
-// The count in two phases per batch of permutations, in the graph's processing order (see k_lm_gather_sorted):
-// ys[p][r] = z_y[perm_p[order[r]]] once per permutation, then a LOCAL sparse product.  (A one-kernel form, r01,
-// fetched 900 GB for 999 permutations of 1M cells: 7 random 8-byte reads per cell and permutation, 128 bytes each.)
-#define LL_PERM_BATCH 16
-
-__global__ __launch_bounds__(256) void k_lee_local_gather(const double *__restrict__ zy, const int32_t *__restrict__ order,
-                                                          const int32_t *__restrict__ perm, int64_t pstride, int64_t n,
-                                                          double *__restrict__ ys)
-{
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    ys[(int64_t)blockIdx.y * n + r] = zy[perm[(int64_t)blockIdx.y * pstride + order[r]]];
-}
-
-__global__ __launch_bounds__(256) void k_lee_local_count_sorted(const long long *__restrict__ indptr,
-                                                                const int32_t *__restrict__ indices_r,
-                                                                const double *__restrict__ w, const int32_t *__restrict__ order,
-                                                                const double *__restrict__ zx,
-                                                                const double *__restrict__ ys,
-                                                                const double *__restrict__ Llocal, int n_batch,
-                                                                int32_t *__restrict__ count, int64_t n, int first)
-{
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const int64_t i = order[r];
-    const long long e0 = indptr[i], e1 = indptr[i + 1];
-    const double x = zx[i], obs = fabs(Llocal[i]);
-    double s[LL_PERM_BATCH];
-#pragma unroll
-    for (int p = 0; p < LL_PERM_BATCH; ++p) s[p] = 0.0;
-    for (long long e = e0; e < e1; ++e) {      // edge loop outside, permutations unrolled inside: independent loads in flight
-        const double ww = w[e];
-        const double *ye = ys + indices_r[e];
-#pragma unroll
-        for (int p = 0; p < LL_PERM_BATCH; ++p)
-            if (p < n_batch) s[p] = __dadd_rn(s[p], __dmul_rn(ww, ye[(int64_t)p * n]));
-    }
-    int cnt = 0;
-#pragma unroll
-    for (int p = 0; p < LL_PERM_BATCH; ++p)
-        if (p < n_batch) {
-            // the reference stores the permuted values in a float32 array before comparing (AC:1402,1408)
-            const double lp = (double)(float)__dmul_rn(x, s[p]);
-            cnt += fabs(lp) >= obs;
-        }
-    count[i] = first ? cnt : count[i] + cnt;
-}
-
-// The vectors of one local Lee job (sc_lee_local, sc_lee_local_seeded), n each
-struct LlJob { int64_t n = 0; double *zx = nullptr, *zy = nullptr, *lag = nullptr, *L = nullptr; int32_t *cnt = nullptr; };
-
-// z_x and z_y from the standardised tiles (c->Z), lag = W z_y, L_local = z_x * lag; and what the per-cell counts of
-// n_perm permutations need
-static int ll_prepare(sc_ctx *c, int32_t gene_x, int32_t gene_y, int64_t n_perm, const LlJob &j)
-{
-    const int64_t n = j.n;
-    const unsigned gcol = (unsigned)ceil_div64(n, 256);
-    hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_x, j.zx);
-    hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_y, j.zy);
-    sc_launch_spmv_vec(c, c->g_indptr.as<int64_t>(), c->g_indices.as<int32_t>(), c->g_data.as<double>(), j.zy, j.lag, n);
-    hipLaunchKernelGGL(k_vec_mul, dim3(gcol), dim3(256), 0, c->stream, j.zx, j.lag, j.L, n);
-    if (n_perm > 0) {
-        SC_TRY(sc_graph_ensure_order(c));
-        SC_TRY(c->lm_ys.ensure(sizeof(double) * (size_t)LL_PERM_BATCH * (size_t)n, &c->mem));
-    }
-    SC_HIP(hipGetLastError());
-    return SC_OK;
-}
-
-// counts of permutations [p0, p1) of the job (rows row0 + p of the forward table); p0 == 0 starts the counts
-static int ll_count(sc_ctx *c, const LlJob &j, int64_t row0, int64_t p0, int64_t p1)
-{
-    const int64_t n = j.n;
-    const unsigned gcol = (unsigned)ceil_div64(n, 256);
-    for (int64_t p = p0; p < p1; p += LL_PERM_BATCH) {
-        const int nb = (int)(p1 - p < LL_PERM_BATCH ? p1 - p : LL_PERM_BATCH);
-        hipLaunchKernelGGL(k_lee_local_gather, dim3(gcol, (unsigned)nb), dim3(256), 0, c->stream, j.zy,
-                           c->g_order.as<int32_t>(), c->perm.as<int32_t>() + (row0 + p) * c->p_stride, c->p_stride,
-                           n, c->lm_ys.as<double>());
-        hipLaunchKernelGGL(k_lee_local_count_sorted, dim3(gcol), dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
-                           c->g_indices_r.as<int32_t>(), c->g_data.as<double>(), c->g_order.as<int32_t>(), j.zx,
-                           c->lm_ys.as<double>(), j.L, nb, j.cnt, n, p == 0 ? 1 : 0);
-    }
-    SC_HIP(hipGetLastError());
-    return SC_OK;
-}
-
-extern "C" int sc_lee_local(sc_ctx *c, int32_t gene_x, int32_t gene_y, int64_t n_perm, int64_t perm_row0,
-                            double *zx_out, double *lag_out, double *L_local_out, int32_t *count_out)
-{
-    SC_REQUIRE(c && zx_out && lag_out && L_local_out, SC_ERR_INVALID, "sc_lee_local: null pointer");
-    SC_HIP(hipSetDevice(c->device));
-    if (n_perm > 0) SC_TRY(sc_perm_forward_ensure(c));
-    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_lee_local: no expression loaded");
-    SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_lee_local: graph missing or size mismatch");
-    SC_REQUIRE(gene_x >= 0 && gene_x < c->e_genes && gene_y >= 0 && gene_y < c->e_genes, SC_ERR_INVALID,
-               "sc_lee_local: gene index outside the loaded set");
-    if (n_perm > 0) {
-        SC_REQUIRE(count_out, SC_ERR_INVALID, "sc_lee_local: count_out required when n_perm > 0");
-        SC_REQUIRE(c->p_n == c->e_n && perm_row0 >= 0 && perm_row0 + n_perm <= c->p_count, SC_ERR_STATE,
-                   "sc_lee_local: needs permutation rows [%lld, %lld)", (long long)perm_row0,
-                   (long long)(perm_row0 + n_perm));
-    }
-    const int64_t n = c->e_n, T = c->e_tiles;
-    SC_TRY(expr_center(c));
-    hipLaunchKernelGGL(k_div_sd, dim3((unsigned)ceil_div64(n * SC_TILE, 256), (unsigned)T), dim3(256), 0, c->stream,
-                       c->Z.as<double>(), c->g_var.as<double>(), n);
-    SC_TRY(c->lee_a.ensure(sizeof(double) * (size_t)n * 5, &c->mem));
-    LlJob j;
-    j.n = n; j.zx = c->lee_a.as<double>(); j.zy = j.zx + n; j.lag = j.zx + 2 * n; j.L = j.zx + 3 * n;
-    j.cnt = reinterpret_cast<int32_t *>(j.zx + 4 * n);
-    SC_TRY(ll_prepare(c, gene_x, gene_y, n_perm, j));
-    if (n_perm > 0) {
-        KernelTimerScope ts(c, SC_K_LEE_PERM);
-        SC_TRY(ll_count(c, j, perm_row0, 0, n_perm));
-    }
-    SC_HIP(hipMemcpyAsync(zx_out, j.zx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(lag_out, j.lag, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(L_local_out, j.L, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (n_perm > 0)
-        SC_HIP(hipMemcpyAsync(count_out, j.cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-    return SC_OK;
-}
-
-// r04: the pair body of lees_l_local as ONE pipeline (r03's verdict: a generator call and two device calls per pair, each
-// waiting for the one before).  Equal to
-//     sc_perm_generate(state6, n, n_perm_global + n_perm_local);  sc_lee(x, y, offset 0, n_perm_global);
-//     sc_lee_local(x, y, n_perm_local, perm_row0 = n_perm_global)
-// -- the same kernels on the same rows, results bit for bit, the generator state advanced by the same draws -- with the
-// permuted sums of the global statistic and the per-cell counts taken chunk by chunk behind the generator (which is 85 % of
-// the three calls' time at 10^6 cells), like sc_local_moran_seeded.
-extern "C" int sc_lee_local_seeded(sc_ctx *c, uint64_t *state6, int32_t gene_x, int32_t gene_y, int64_t n_perm_global,
-                                   int64_t n_perm_local, double *L_out, int64_t *count_abs_ge_out, double *zx_out,
-                                   double *lag_out, double *L_local_out, int32_t *count_out)
-{
-    SC_REQUIRE(c && state6 && L_out && zx_out && lag_out && L_local_out, SC_ERR_INVALID, "sc_lee_local_seeded: null pointer");
-    SC_REQUIRE(n_perm_global >= 0 && n_perm_local >= 0 && n_perm_global + n_perm_local >= 1 &&
-               n_perm_global + n_perm_local <= (1 << 24), SC_ERR_INVALID, "sc_lee_local_seeded: permutation counts out of range");
-    SC_REQUIRE(n_perm_local == 0 || count_out, SC_ERR_INVALID, "sc_lee_local_seeded: count_out required when n_perm_local > 0");
-    SC_REQUIRE(n_perm_global == 0 || count_abs_ge_out, SC_ERR_INVALID, "sc_lee_local_seeded: count_abs_ge_out required when n_perm_global > 0");
-    SC_HIP(hipSetDevice(c->device));
-    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_lee_local_seeded: no expression loaded");
-    SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_lee_local_seeded: graph missing or size mismatch");
-    SC_REQUIRE(gene_x >= 0 && gene_x < c->e_genes && gene_y >= 0 && gene_y < c->e_genes, SC_ERR_INVALID,
-               "sc_lee_local_seeded: gene index outside the loaded set");
-    const int64_t n = c->e_n, T = c->e_tiles, Pg = n_perm_global, Pl = n_perm_local;
-    const int blocks = (int)ceil_div64(n, LEE_CELLS_PER_BLOCK);
-    const unsigned gcol = (unsigned)ceil_div64(n, 256);
-    double *vlag_g = nullptr, *vu = nullptr;
-    LlJob j;   // (z_x, z_y: sc_lee's operands too)
-    auto prepare = [&]() -> int {
-        // ---- sc_lee's operands: z-scores (population sd), Lag = W Z, u = W^T z_x ----
-        SC_TRY(expr_center(c));
-        hipLaunchKernelGGL(k_div_sd, dim3((unsigned)ceil_div64(n * SC_TILE, 256), (unsigned)T), dim3(256), 0, c->stream,
-                           c->Z.as<double>(), c->g_var.as<double>(), n);
-        SC_TRY(c->Lag.ensure((size_t)T * (size_t)n * SC_TILE * sizeof(double), &c->mem));
-        SC_TRY(launch_lag(c, c->g_indptr, c->g_indices, c->g_data, c->Z.as<double>(), c->Lag.as<double>()));
-        double var[2];
-        SC_HIP(hipMemcpyAsync(&var[0], c->g_var.as<double>() + gene_x, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        SC_HIP(hipMemcpyAsync(&var[1], c->g_var.as<double>() + gene_y, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        SC_HIP(hipStreamSynchronize(c->stream));
-        SC_REQUIRE(var[0] > 0.0 && var[1] > 0.0, SC_ERR_INVALID, "sc_lee_local_seeded: a gene of the pair has zero variance");
-        SC_TRY(c->lee_a.ensure(sizeof(double) * (size_t)n * 8, &c->mem));
-        j.n = n; j.zx = c->lee_a.as<double>(); vlag_g = j.zx + n; vu = j.zx + 2 * n; j.zy = j.zx + 3 * n;
-        j.lag = j.zx + 4 * n; j.L = j.zx + 5 * n;
-        j.cnt = reinterpret_cast<int32_t *>(j.zx + 6 * n);
-        SC_TRY(c->lee_b.ensure(sizeof(double) * (size_t)blocks * (size_t)(Pg + 1), &c->mem));
-        SC_TRY(c->lee_out.ensure(sizeof(double) * (size_t)(Pg + 1 > T * SC_TILE ? Pg + 1 : T * SC_TILE), &c->mem));
-        if (Pg > 0) SC_TRY(sc_graph_ensure_transpose(c));
-        // ---- sc_lee_local's: z_x, z_y, lag = W z_y on the vector, L_local = z_x * lag ----
-        SC_TRY(ll_prepare(c, gene_x, gene_y, Pl, j));
-        // ---- sc_lee's: the observed sum and u = W^T z_x ----
-        hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Lag.as<double>(), n, (int64_t)gene_y, vlag_g);
-        hipLaunchKernelGGL(k_vec_dot, dim3(blocks), dim3(256), 0, c->stream, j.zx, vlag_g, n, c->lee_b.as<double>() + (size_t)Pg * blocks);
-        if (Pg > 0)
-            sc_launch_spmv_vec(c, c->gt_indptr.as<int64_t>(), c->gt_indices.as<int32_t>(), c->gt_data.as<double>(), j.zx, vu, n);
-        SC_HIP(hipGetLastError());
-        return SC_OK;
-    };
-    auto score = [&](int64_t p0, int64_t p1) -> int {
-        KernelTimerScope ts(c, SC_K_LEE_PERM);
-        const int64_t a1 = p1 < Pg ? p1 : Pg;
-        if (p0 < a1)   // rows of the global statistic
-            hipLaunchKernelGGL(k_vec_gather_dot, dim3(blocks, (unsigned)(a1 - p0)), dim3(256), 0, c->stream, vu, j.zy,
-                               c->perm.as<int32_t>() + p0 * c->p_stride, c->p_stride, n, c->lee_b.as<double>() + (size_t)p0 * blocks);
-        // rows of the per-cell counts: permutations [b0 - Pg, p1 - Pg) of the local job
-        const int64_t b0 = p0 > Pg ? p0 : Pg;
-        if (b0 < p1) SC_TRY(ll_count(c, j, Pg, b0 - Pg, p1 - Pg));
-        SC_HIP(hipGetLastError());
-        return SC_OK;
-    };
-    // a job that fails its verification is rerun with the sequential scan: everything restarts at permutation 0 (the
-    // first rows' flag restarts the counts)
-    SC_TRY(permgen_rerun_on_failure(c, [&]() { return sc_perm_pipeline(c, state6, n, Pg + Pl, 0, 2, prepare, score); }, nullptr));
-    std::vector<double> host((size_t)Pg + 1);
-    hipLaunchKernelGGL(k_row_sum, dim3((unsigned)ceil_div64(Pg + 1, 256)), dim3(256), 0, c->stream, c->lee_b.as<double>(),
-                       (int)(Pg + 1), blocks, c->lee_out.as<double>());
-    SC_HIP(hipGetLastError());
-    SC_HIP(hipMemcpyAsync(host.data(), c->lee_out.p, sizeof(double) * (size_t)(Pg + 1), hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(zx_out, j.zx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(lag_out, j.lag, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(L_local_out, j.L, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (Pl > 0) SC_HIP(hipMemcpyAsync(count_out, j.cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-    const double L = host[(size_t)Pg];
-    *L_out = L;
-    if (count_abs_ge_out) {
-        int64_t cnt = 0;
-        for (int64_t p = 0; p < Pg; ++p) cnt += fabs(host[(size_t)p]) >= fabs(L) ? 1 : 0;
-        *count_abs_ge_out = cnt;
-    }
-    return SC_OK;
-}

@@ -341,3 +341,92 @@ int permgen_rerun_on_failure(sc_ctx *c, const std::function<int()> &attempt, con
     c->pg_mode = 1;
     return attempt();
 }
+
+// ---- inverse rows of the table (the Moran scoring kernels gather through them), and the forward table from them ----
+#define INV_BLOCKS_PER_ROW 64
+
+// inv[row][perm[row][i]] = i.  Blocks of one row share blockIdx % 8 (one XCD under round-robin placement,
+// speed only) so that the 4n-byte inverse row is assembled in one L2.
+__global__ __launch_bounds__(256) void k_invert_perm(const int32_t *__restrict__ perm, int32_t *__restrict__ inv,
+                                                     int64_t n, int64_t stride, int rows)
+{
+    const int id = blockIdx.x;
+    const int rest = id >> 3;
+    const int row = (rest / INV_BLOCKS_PER_ROW) * 8 + (id & 7);
+    const int part = rest % INV_BLOCKS_PER_ROW;
+    if (row >= rows) return;
+    const int64_t per = (n + INV_BLOCKS_PER_ROW - 1) / INV_BLOCKS_PER_ROW;
+    const int64_t i0 = (int64_t)part * per, i1 = i0 + per < n ? i0 + per : n;
+    const int32_t *src = perm + (int64_t)row * stride;
+    int32_t *dst = inv + (int64_t)row * stride;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) dst[src[i]] = (int32_t)i;
+}
+
+__global__ __launch_bounds__(256) void k_check_inverse(const int32_t *__restrict__ perm,
+                                                       const int32_t *__restrict__ inv, int64_t n, int64_t stride,
+                                                       int64_t rows, int *__restrict__ flag)
+{
+    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = rows * n;
+    int bad = 0;
+    for (; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = t / n, i = t - r * n;
+        if (inv[r * stride + perm[r * stride + i]] != (int32_t)i) bad = 1;
+    }
+    if (bad) atomicOr(flag, 1);
+}
+
+// inverse rows [p0, p1) of the active table on stream s
+int invert_rows(sc_ctx *c, int64_t p0, int64_t p1, hipStream_t s)
+{
+    const int rows = (int)(p1 - p0);
+    if (rows <= 0) return SC_OK;
+    const int groups = (rows + 7) / 8;
+    // (the table's own length, not the expression's: a generator job may run before any expression is loaded)
+    hipLaunchKernelGGL(k_invert_perm, dim3((unsigned)(groups * INV_BLOCKS_PER_ROW * 8)), dim3(256), 0, s,
+                       c->perm.as<int32_t>() + p0 * c->p_stride, c->inv.as<int32_t>() + p0 * c->p_stride, c->p_n,
+                       c->p_stride, rows);
+    SC_HIP(hipGetLastError());
+    return SC_OK;
+}
+
+// After a seeded pipeline that only generated the inverse table: materialise the permutation table itself (the
+// inverse of the inverse) for callers that use the resident table afterwards.
+int sc_perm_forward_ensure(sc_ctx *c)
+{
+    if (c->perm_forward_valid || c->p_count <= 0) return SC_OK;
+    const int rows = (int)c->p_count;
+    const int groups = (rows + 7) / 8;
+    hipLaunchKernelGGL(k_invert_perm, dim3((unsigned)(groups * INV_BLOCKS_PER_ROW * 8)), dim3(256), 0, c->stream,
+                       c->inv.as<int32_t>(), c->perm.as<int32_t>(), c->p_n, c->p_stride, rows);
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipStreamSynchronize(c->stream));
+    c->perm_forward_valid = true;
+    return SC_OK;
+}
+
+// The scoring kernels gather through the INVERSE rows, which exist only for true permutations: a table uploaded by
+// the caller is checked once (inverse of the inverse).  *bijective = false: its rows are arbitrary index maps and
+// take the index-row kernel (k_moran_perm).
+int sc_perm_table_is_bijective(sc_ctx *c, int64_t n_perm, bool *bijective)
+{
+    *bijective = false;
+    if (n_perm <= 0) return SC_OK;
+    const int64_t rows = c->p_count > n_perm ? c->p_count : n_perm;  // the WHOLE table is checked once
+    SC_TRY(c->inv.ensure(sizeof(int32_t) * (size_t)(c->p_stride * rows + 32), &c->mem));
+    if (!c->perm_bijective && !c->perm_checked) {
+        SC_TRY(invert_rows(c, 0, rows, c->stream));
+        SC_TRY(c->perm_flag.ensure(sizeof(unsigned long long), &c->mem));
+        SC_HIP(hipMemsetAsync(c->perm_flag.p, 0, sizeof(int), c->stream));
+        hipLaunchKernelGGL(k_check_inverse, dim3(2048), dim3(256), 0, c->stream, c->perm.as<int32_t>(),
+                           c->inv.as<int32_t>(), c->p_n, c->p_stride, rows, c->perm_flag.as<int>());
+        int bad = 0;
+        SC_HIP(hipMemcpyAsync(&bad, c->perm_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        SC_HIP(hipStreamSynchronize(c->stream));
+        c->perm_checked = true;
+        c->perm_bijective = (bad == 0);
+        if (c->perm_bijective) c->inv_rows_valid = rows;
+    }
+    *bijective = c->perm_bijective;
+    return SC_OK;
+}
