@@ -136,7 +136,9 @@ int sc_knn_fetch(sc_ctx *ctx, int32_t *idx_out, double *rdist_out);
 /* ---- A2: radius graph ---------------------------------------------------------------------
  * Replaces cKDTree.query_ball_point(coords, r) with self removed (NB:241-244): closed ball
  * fl(dx*dx+dy*dy) <= fl(r*r).  Two-pass: count fills indptr_out[n+1]; fill writes nnz indices,
- * ascending within each row.  The coordinates of the count call stay resident for the fill call. */
+ * ascending within each row.  The binned coordinates of the count call stay resident for the fill call until the next
+ * neighbour search of the context (sc_knn_2d, sc_radius_count_2d, sc_nearest_*, sc_ripley_build): after one of those
+ * the fill call returns SC_ERR_STATE. */
 int sc_radius_count_2d(sc_ctx *ctx, const double *xy, int64_t n, double radius, int64_t *indptr_out);
 int sc_radius_fill_2d(sc_ctx *ctx, int64_t nnz, int32_t *indices_out);
 

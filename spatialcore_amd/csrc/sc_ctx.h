@@ -96,8 +96,11 @@ struct sc_ctx {
     DBuf knn_idx, knn_rd;  // [n][k] device result of the last sc_knn_2d
     hipEvent_t knn_done = nullptr;      // ... recorded behind a search whose result was not fetched (sc_knn_fetch)
     DBuf knn_hd, knn_hi;   // k > 32: the per-query candidate heaps, [slot][query]
+    // the pending radius count: > 0 from a sc_radius_count_2d until the next sc_bin_points (any neighbour search), since
+    // the fill pass walks the bins the rows were counted on
     double radius = -1.0;
-    DBuf rad_indptr;  // [n+1] int64 of the last radius count
+    DBuf rad_indptr;  // [n+1] int64 of that count
+    long long rad_nnz = 0;   // ... and its last entry
     // ---- Ripley's K pair list (sc_labelperm.hip): the unordered pairs within the largest radius, kept BESIDE the graph ----
     // Positions are those of the bin-sorted order of the points (sid: position -> cell), so the list is valid exactly as
     // long as the bins are those it was built from: sc_bin_points clears rp_valid, and every neighbour search goes through it.
@@ -277,12 +280,6 @@ int sc_lag_tiles(sc_ctx *c, const DBuf &indptr, const DBuf &indices, const DBuf 
 // r itself, in the same kernel, never failed.  Device code therefore keeps per-lane 64-bit shifts out of the ISA: these
 // helpers compile to v_lshlrev_b32 / v_lshrrev_b32 / v_alignbit_b32 with amounts masked to [0, 31] in the source.
 #if defined(__HIPCC__)
-// bin of a coordinate on the neighbour searches' uniform grid (sc_graph.hip, sc_labelperm.hip), clamped to the grid
-__device__ __forceinline__ int bin_coord(double v, double v0, double inv_h, int nb)
-{
-    int b = (int)floor((v - v0) * inv_h);
-    return b < 0 ? 0 : (b >= nb ? nb - 1 : b);
-}
 __device__ __forceinline__ uint64_t sc_low_mask64(uint32_t d)   // the d low bits set, d in [0, 64]
 {
     const uint32_t part = (1u << (d & 31u)) - 1u;
@@ -314,8 +311,18 @@ static inline const int32_t *sc_processing_order(const sc_ctx *c, int64_t n)
 }
 
 // ---- implemented across translation units ----
-// bins the points for a neighbour search (sx / sy / sid / bin_start; bins of side >= min_h, about target_per_bin points each)
+// ---- neighbour searches (sc_search.hip) ----
+// bins the points for a neighbour search (sx / sy / sid / bin_start; bins of side >= min_h, about target_per_bin points each).
+// The only function that replaces the bins, so it invalidates what is only meaningful on the bins it replaces: the pending
+// radius count (radius, rad_indptr) and the Ripley pair list (rp_valid).
 int sc_bin_points(sc_ctx *c, const double *xy, int64_t n, double target_per_bin, double min_h);
+struct BinGrid;                         // sc_search.h
+BinGrid sc_bin_grid(const sc_ctx *c);   // the bins of the last sc_bin_points, as kernels take them
+int sc_window_rings(const sc_ctx *c, double radius);   // rings of bins around a point's own bin that cover its closed ball (window_walk)
+// offsets[0 .. n] = exclusive sums of counts[0 .. n] (counts[n] = 0), and *total = offsets[n]: enqueued on c->stream, the caller waits
+int sc_counts_to_offsets(sc_ctx *c, long long *counts, long long *offsets, int64_t n, long long *total);
+// ---- active graph (sc_graph.hip) ----
+void sc_graph_drop(sc_ctx *c);          // the active graph is gone (before its arrays are replaced or overwritten)
 int sc_graph_ensure_transpose(sc_ctx *c);
 int sc_graph_ensure_s0(sc_ctx *c);
 int sc_graph_weight_sum_blocks(const sc_ctx *c);

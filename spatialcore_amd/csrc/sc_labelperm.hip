@@ -12,7 +12,7 @@
 #include <hipcub/hipcub.hpp>
 #include <vector>
 
-#include "sc_ctx.h"
+#include "sc_search.h"
 
 // ------------------------------------------------------------------------------------------------
 // shared by both tests
@@ -389,46 +389,34 @@ struct RipleyR2 { double v[RIP_MAX_RADII]; };
 // FILL = false: counts[t] = pairs (t, s), s > t, within the largest radius; rank[cell at t] = t.
 // FILL = true: the pairs themselves at indptr[t] .., with their radius bins.  t, s: positions in bin order.
 template <bool FILL>
-__global__ __launch_bounds__(256) void k_ripley_pairs(const double *__restrict__ sx, const double *__restrict__ sy,
-                                                      const int32_t *__restrict__ sid, const int32_t *__restrict__ bin_start,
-                                                      int64_t n, RipleyR2 r2, int n_radii, int rings, double x0, double y0,
-                                                      double h, int nbx, int nby, long long *__restrict__ counts,
+__global__ __launch_bounds__(256) void k_ripley_pairs(BinGrid g, int64_t n, RipleyR2 r2, int n_radii, int rings,
+                                                      long long *__restrict__ counts,
                                                       const long long *__restrict__ indptr, int32_t *__restrict__ prow,
                                                       int32_t *__restrict__ pcol, unsigned char *__restrict__ pbin,
                                                       int32_t *__restrict__ rank)
 {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
-    const double qx = sx[t], qy = sy[t];
+    const double qx = g.sx[t], qy = g.sy[t];
     const double r2max = r2.v[n_radii - 1];
-    const double inv_h = 1.0 / h;
-    const int bx = bin_coord(qx, x0, inv_h, nbx), by = bin_coord(qy, y0, inv_h, nby);
-    const int yhi = by + rings >= nby ? nby - 1 : by + rings;
-    const int xlo = bx - rings < 0 ? 0 : bx - rings, xhi = bx + rings >= nbx ? nbx - 1 : bx + rings;
     long long cnt = 0;
     const long long base = FILL ? indptr[t] : 0;
-    for (int yy = by; yy <= yhi; ++yy) {
-        int s0 = bin_start[yy * nbx + xlo];
-        const int s1 = bin_start[yy * nbx + xhi + 1];
-        if (s0 <= t) s0 = (int)t + 1;   // (own row only: the rows above start behind t)
-        for (int s = s0; s < s1; ++s) {
-            const double dx = qx - sx[s], dy = qy - sy[s];
-            const double d = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
-            if (d <= r2max) {
-                if (FILL) {
-                    int b = 0;
-                    for (int j = 0; j < n_radii - 1; ++j) b += d > r2.v[j] ? 1 : 0;
-                    prow[base + cnt] = (int32_t)t;
-                    pcol[base + cnt] = s;
-                    pbin[base + cnt] = (unsigned char)b;
-                }
-                ++cnt;
+    window_walk<true>(g, qx, qy, rings, (int)t, [&](int s) {
+        const double d = BinGrid::dist2(qx, qy, g.sx[s], g.sy[s]);
+        if (d <= r2max) {
+            if (FILL) {
+                int b = 0;
+                for (int j = 0; j < n_radii - 1; ++j) b += d > r2.v[j] ? 1 : 0;
+                prow[base + cnt] = (int32_t)t;
+                pcol[base + cnt] = s;
+                pbin[base + cnt] = (unsigned char)b;
             }
+            ++cnt;
         }
-    }
+    });
     if (!FILL) {
         counts[t] = cnt;
-        rank[sid[t]] = (int32_t)t;
+        rank[g.sid[t]] = (int32_t)t;
     }
 }
 
@@ -450,29 +438,22 @@ extern "C" int sc_ripley_build(sc_ctx *c, const double *xy, int64_t n, const dou
     }
     SC_HIP(hipSetDevice(c->device));
     const double rmax = radii[n_radii - 1];
-    c->radius = -1.0;   // (a pending sc_radius_count_2d / _fill_2d pair loses its bins)
     // bins no smaller than the largest radius, as the radius graph takes them
     SC_TRY(sc_bin_points(c, xy, n, 4.0, rmax));
-    int rings = (int)ceil(rmax / c->gh * (1.0 + 1e-9));
-    if (rings < 1) rings = 1;
+    const int rings = sc_window_rings(c, rmax);
+    const BinGrid g = sc_bin_grid(c);
     SC_TRY(c->rp_cnt.ensure(sizeof(long long) * (size_t)(n + 1), &c->mem));
     SC_TRY(c->rp_indptr.ensure(sizeof(long long) * (size_t)(n + 1), &c->mem));
     SC_TRY(c->rp_rank.ensure(sizeof(int32_t) * (size_t)n, &c->mem));
     long long *counts = c->rp_cnt.as<long long>();
     SC_HIP(hipMemsetAsync(counts, 0, sizeof(long long) * (size_t)(n + 1), c->stream));
     const dim3 grid((unsigned)ceil_div64(n, 256));
-    hipLaunchKernelGGL(k_ripley_pairs<false>, grid, dim3(256), 0, c->stream, c->sx.as<double>(), c->sy.as<double>(),
-                       c->sid.as<int32_t>(), c->bin_start.as<int32_t>(), n, r2, (int)n_radii, rings, c->gx0, c->gy0, c->gh,
-                       c->nbx, c->nby, counts, (const long long *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr,
-                       (unsigned char *)nullptr, c->rp_rank.as<int32_t>());
+    hipLaunchKernelGGL(k_ripley_pairs<false>, grid, dim3(256), 0, c->stream, g, n, r2, (int)n_radii, rings, counts,
+                       (const long long *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (unsigned char *)nullptr,
+                       c->rp_rank.as<int32_t>());
     SC_HIP(hipGetLastError());
-    size_t tmp_bytes = 0;
-    SC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, counts, c->rp_indptr.as<long long>(), (int)(n + 1), c->stream));
-    SC_TRY(c->cub_tmp.ensure(tmp_bytes, &c->mem));
-    SC_HIP(hipcub::DeviceScan::ExclusiveSum(c->cub_tmp.p, tmp_bytes, counts, c->rp_indptr.as<long long>(), (int)(n + 1),
-                                            c->stream));
     long long total = 0;
-    SC_HIP(hipMemcpyAsync(&total, c->rp_indptr.as<long long>() + n, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    SC_TRY(sc_counts_to_offsets(c, counts, c->rp_indptr.as<long long>(), n, &total));
     SC_HIP(hipStreamSynchronize(c->stream));
     SC_REQUIRE(ceil_div64(total, RIP_PAIRS_PER_BLOCK) <= 65535, SC_ERR_INVALID,
                "sc_ripley_build: %lld unordered pairs within the largest radius, more than 4.2e9", total);
@@ -481,9 +462,8 @@ extern "C" int sc_ripley_build(sc_ctx *c, const double *xy, int64_t n, const dou
     SC_TRY(c->rp_col.ensure(sizeof(int32_t) * cap, &c->mem));
     SC_TRY(c->rp_bin.ensure(cap, &c->mem));
     if (total > 0) {
-        hipLaunchKernelGGL(k_ripley_pairs<true>, grid, dim3(256), 0, c->stream, c->sx.as<double>(), c->sy.as<double>(),
-                           c->sid.as<int32_t>(), c->bin_start.as<int32_t>(), n, r2, (int)n_radii, rings, c->gx0, c->gy0, c->gh,
-                           c->nbx, c->nby, (long long *)nullptr, c->rp_indptr.as<long long>(), c->rp_row.as<int32_t>(),
+        hipLaunchKernelGGL(k_ripley_pairs<true>, grid, dim3(256), 0, c->stream, g, n, r2, (int)n_radii, rings,
+                           (long long *)nullptr, c->rp_indptr.as<long long>(), c->rp_row.as<int32_t>(),
                            c->rp_col.as<int32_t>(), c->rp_bin.as<unsigned char>(), (int32_t *)nullptr);
         SC_HIP(hipGetLastError());
         SC_HIP(hipStreamSynchronize(c->stream));

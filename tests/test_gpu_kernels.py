@@ -251,6 +251,29 @@ def test_radius_graph(ctx, oracle, radius):
     np.testing.assert_array_equal(indices, wi)
 
 
+def test_radius_fill_refused_after_another_search(ctx, oracle):
+    """The count pass sizes the rows for the bins it ran on: any neighbour search in between replaces the bins, so the
+    fill pass must refuse (SC_ERR_STATE) instead of filling those rows from other bins.  Raw entry points, the same
+    coordinates in both searches; a fresh count + fill then works as ever."""
+    from spatialcore_amd import _lib
+
+    rng = np.random.default_rng(9)
+    xy = np.ascontiguousarray(rng.uniform(0, 400, (4000, 2)))
+    n, radius, k = xy.shape[0], 12.0, 6
+    lib = ctx._lib
+    indptr = np.empty(n + 1, dtype=np.int64)
+    _lib._check(lib.sc_radius_count_2d(ctx._h, _lib._ptr(xy), n, radius, _lib._ptr(indptr)))
+    idx = np.empty((n, k), dtype=np.int32)
+    _lib._check(lib.sc_knn_2d(ctx._h, _lib._ptr(xy), n, k, 0, _lib._ptr(idx), None))
+    indices = np.empty(int(indptr[-1]), dtype=np.int32)
+    with pytest.raises(_lib.SpatialCoreHipError, match="call sc_radius_count_2d first"):
+        _lib._check(lib.sc_radius_fill_2d(ctx._h, indices.size, _lib._ptr(indices)))
+    indptr, indices = ctx.radius_graph(xy, radius)
+    wp, wi = oracle.radius_neighbors(xy, radius)
+    np.testing.assert_array_equal(indptr, wp)
+    np.testing.assert_array_equal(indices, wi)
+
+
 def test_graph_moments(ctx, oracle):
     coords, _ = synth(3000, 1, 3)
     g = oracle.row_normalize_l1(oracle.squidpy_connectivities(coords, 6))
