@@ -137,7 +137,7 @@ int sc_knn_fetch(sc_ctx *ctx, int32_t *idx_out, double *rdist_out);
  * Replaces cKDTree.query_ball_point(coords, r) with self removed (NB:241-244): closed ball
  * fl(dx*dx+dy*dy) <= fl(r*r).  Two-pass: count fills indptr_out[n+1]; fill writes nnz indices,
  * ascending within each row.  The binned coordinates of the count call stay resident for the fill call until the next
- * neighbour search of the context (sc_knn_2d, sc_radius_count_2d, sc_nearest_*, sc_ripley_build): after one of those
+ * neighbour search of the context (sc_knn_2d, sc_radius_count_2d, sc_nearest_*, sc_ripley_build, sc_domains_2d): after one of those
  * the fill call returns SC_ERR_STATE. */
 int sc_radius_count_2d(sc_ctx *ctx, const double *xy, int64_t n, double radius, int64_t *indptr_out);
 int sc_radius_fill_2d(sc_ctx *ctx, int64_t nnz, int32_t *indices_out);
@@ -373,7 +373,7 @@ int sc_kmeans_fit(sc_ctx *ctx, const void *X, int dtype, int64_t n, int32_t C, i
  * sc_ripley_build: bins the points and builds, on the device, the list of pairs within r_R, each with one byte (the
  *   index of the smallest radius that contains it).  The list is kept beside the active graph (which it does not touch)
  *   and stays valid until the next neighbour search of the context (sc_knn_2d, sc_radius_count_2d, sc_nearest_*,
- *   sc_ripley_build): the counting entry points then return SC_ERR_STATE.  n_pairs_out = ordered pairs within r_R.
+ *   sc_ripley_build, sc_domains_2d): the counting entry points then return SC_ERR_STATE.  n_pairs_out = ordered pairs within r_R.
  *   More than 4.2e9 stored pairs: SC_ERR_INVALID.
  * sc_ripley_counts: counts_out[((p T + a) T + b) R + j] for the label vectors labels[perm_p], perm_p = rows
  *   [perm_row0, perm_row0 + n_perm) of the active permutation table; p = n_perm holds the observed counts.
@@ -389,6 +389,30 @@ int sc_ripley_counts(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_ty
                      int64_t *counts_out);
 int sc_ripley_counter(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_types, uint64_t seed, int64_t p_first,
                       int64_t n_perm, int64_t batch, int64_t *observed_out, int64_t *sums_out);
+
+/* ---- N7: spatial domains (make_spatial_domains, reference src/spatialcore/spatial/domains.py:289-732) ---------------
+ * The reference hands this step to R (domains.py:579-638, r_functions.R:34-124: st_buffer, st_union, negative
+ * st_buffer, concaveman, st_join).  Here buffer - union - shrink is taken in its continuous meaning over discs and
+ * computed from the points alone.  d = cell_dist, s = shrink (the caller's cell_dist - shrink_margin), 0 <= s < d.
+ *  - U = union of the closed discs of radius d about the targets.  Its polygons are the connected components of the
+ *    graph on the targets with an edge iff fl(fl(dx dx) + fl(dy dy)) <= fl((2d)(2d)) (fp64, no FMA; 2d is an exact
+ *    doubling).  target_component_out[i] = the smallest target index in i's component: a function of the input alone,
+ *    identical from run to run (integer atomics on a parent array, lock-free union-find with path halving).
+ *  - A query p lies in the shrunken region iff the closed disc of radius s about p is contained in U.
+ *    clearance_out[q] (nullable) = min(s, distance from p to the boundary of U) for p in U, and -1.0 when no target is
+ *    within d (p outside U).  The boundary point nearest to p, when closer than s, is a foot point
+ *    t_i + d (p - t_i) / |p - t_i| of a circle that contains p (targets on p's spot have none) or one of the two
+ *    intersection points of circles i and j, 0 < |t_i - t_j| <= 2d; either counts only if no other disc holds it
+ *    strictly inside (targets coincident with t_i or t_j are the same circle).  fp64 throughout.
+ *    query_component_out[q] = the component of the targets within d of p when clearance >= s (they are pairwise
+ *    within 2d, so it is unique), else -1.
+ *  - n_queries = 0: components only (xy_queries and the query outputs may be null).
+ * The targets are binned by the context's bin grid: like every neighbour search, the call ends a pending
+ * sc_radius_count_2d and the pair list of sc_ripley_build.  Bad sizes, a non-finite or non-positive cell_dist, a shrink
+ * outside [0, cell_dist) or a non-finite coordinate give SC_ERR_INVALID with the argument in the message. */
+int sc_domains_2d(sc_ctx *ctx, const double *xy_targets, int64_t n_targets, const double *xy_queries, int64_t n_queries,
+                  double cell_dist, double shrink, int32_t *target_component_out, int32_t *query_component_out,
+                  double *clearance_out);
 
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across

@@ -87,6 +87,7 @@ SYMBOLS = {
     "sc_ripley_build": [_P, _P, c_int64, _P, c_int32, _P],
     "sc_ripley_counts": [_P, _P, c_int64, c_int32, c_int64, c_int64, _P],
     "sc_ripley_counter": [_P, _P, c_int64, c_int32, ctypes.c_uint64, c_int64, c_int64, c_int64, _P, _P],
+    "sc_domains_2d": [_P, _P, c_int64, _P, c_int64, c_double, c_double, _P, _P, _P],
     "sc_kmeans_fit": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P,
                       POINTER(c_double), _P, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)],
     "sc_comm_unique_id": [_P],
@@ -626,6 +627,23 @@ class Context:
         mean, mn = c_double(0), c_double(0)
         _check(self._lib.sc_pairwise_2d(self._h, _ptr(a), a.shape[0], _ptr(b), b.shape[0], byref(mean), byref(mn)))
         return mean.value, mn.value
+
+    # ---- N7: spatial domains -----------------------------------------------------------------
+    def domains(self, targets, queries, cell_dist: float, shrink: float, return_clearance: bool = True):
+        """Buffer - union - shrink over discs (sc_domains_2d): (component id per target = smallest target index of its
+        component, component id per query or -1, clearance per query or None).  ``queries`` may be None or empty."""
+        t = _c(targets, np.float64)
+        if t.ndim != 2 or t.shape[1] != 2:
+            raise ValueError(f"targets must have shape (n, 2), got {t.shape}")
+        q = _c(queries if queries is not None else np.zeros((0, 2)), np.float64).reshape(-1, 2)
+        n_q = q.shape[0]
+        comp_t = np.empty(t.shape[0], dtype=np.int32)
+        comp_q = np.empty(n_q, dtype=np.int32)
+        clear = np.empty(n_q, dtype=np.float64) if return_clearance else None
+        _check(self._lib.sc_domains_2d(self._h, _ptr(t), t.shape[0], _ptr(q) if n_q else None, n_q, float(cell_dist),
+                                       float(shrink), _ptr(comp_t), _ptr(comp_q) if n_q else None,
+                                       _ptr(clear) if (n_q and return_clearance) else None))
+        return comp_t, comp_q, clear
 
     # ---- A9 ---------------------------------------------------------------------------------
     def profile_counts(self, labels, n_types: int) -> np.ndarray:

@@ -108,6 +108,8 @@ struct sc_ctx {
     int64_t rp_n = 0, rp_pairs = 0;   // cells, stored pairs (each unordered pair once: row position < column position)
     int rp_radii = 0;
     DBuf rp_cnt, rp_indptr, rp_row, rp_col, rp_bin, rp_rank;   // per-position counts / offsets, pair ends, radius bin (1 byte), cell -> position
+    // ---- spatial domains (sc_domains.hip): union-find parents by target index, per-query component and clearance ----
+    DBuf dm_parent, dm_qcomp, dm_clear;
 
     // ---- graph (CSR, rows sorted by column) + transpose ----
     int64_t g_n = 0, g_nnz = 0;

@@ -9,6 +9,7 @@ from spatialcore_amd.spatial.autocorrelation import (
     morans_i,
 )
 from spatialcore_amd.spatial.distance import calculate_domain_distances, get_distance_matrix
+from spatialcore_amd.spatial.domains import get_domain_summary, make_spatial_domains
 from spatialcore_amd.spatial.neighborhoods import (
     compute_neighborhood_profile,
     identify_niches,
@@ -26,6 +27,8 @@ __all__ = [
     "identify_niches",
     "neighborhood_enrichment",  # extension: not in the reference
     "ripley_k",  # extension: not in the reference
+    "make_spatial_domains",
+    "get_domain_summary",
     "calculate_domain_distances",
     "get_distance_matrix",
 ]
