@@ -1,4 +1,4 @@
-"""Rounds of the in-block fixed point (block_fixed_point, sc_permgen.hip) restated on the CPU, for blocks in which a
+"""Rounds of the in-block fixed point (block_fixed_point, sc_permgen.h) restated on the CPU, for blocks in which a
 permutation of 10^6 cells ends: where the exact prefix stands after each round, and what two accelerations would buy.
 
     python scripts/fixed_point_rounds_sim.py trace [seed]           the front (first thread with a wrong entering count) by round

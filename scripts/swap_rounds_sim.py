@@ -1,4 +1,4 @@
-"""The rule of k_apply_swaps_full (sc_permgen.hip), restated on the CPU: whole rounds of T Fisher-Yates steps, hazards
+"""The rule of k_apply_swaps_full (sc_swaps.hip), restated on the CPU: whole rounds of T Fisher-Yates steps, hazards
 resolved through the smallest / largest step index per partner slot, a round cut only at the first MIDDLE step of a slot.
 
     python scripts/swap_rounds_sim.py check [seed]     rounds form == sequential form, both directions, small n / T (many conflicts)

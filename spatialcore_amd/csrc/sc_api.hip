@@ -3,7 +3,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "sc_ctx.h"
+#include "sc_permgen.h"
 
 static thread_local char g_err[1024] = "";
 
@@ -92,9 +92,7 @@ int sc_timer_collect(sc_ctx *c)
     if (c->stream2) SC_HIP(hipStreamSynchronize(c->stream2));
     if (c->stream3) SC_HIP(hipStreamSynchronize(c->stream3));
     if (c->stream4) SC_HIP(hipStreamSynchronize(c->stream4));
-    for (hipStream_t sp : c->stream_pg)
-        if (sp) SC_HIP(hipStreamSynchronize(sp));
-    if (c->stream_px) SC_HIP(hipStreamSynchronize(c->stream_px));
+    SC_TRY(c->pg.sync());
     if (c->stream_out) SC_HIP(hipStreamSynchronize(c->stream_out));
     for (int k = 0; k < SC_K_COUNT_; ++k) {
         KTimer &t = c->timers[k];
@@ -177,12 +175,12 @@ int sc_ctx_destroy(sc_ctx *c)
                     &c->g_z2, &c->g_scale, &c->g_Inum, &c->g_I, &c->red_tmp, &c->perm, &c->perm_flag,
                     &c->partial, &c->sims, &c->counts, &c->sim_sum, &c->sim_sumsq, &c->lee_a,
                     &c->lee_b, &c->lee_out, &c->lee_pairs, &c->lee_U, &c->lee_Zc, &c->lee_Uc, &c->lee_part, &c->lee_obs, &c->lee_cnt,
-                    &c->lee_rowmap, &c->lee_lperm, &c->g_slag, &c->g_xsum, &c->g_flags, &c->g_xmax, &c->g_lat, &c->g_meanc, &c->g_seff, &c->g_corr, &c->g_thr, &c->sims_raw, &c->g_order, &c->g_rank, &c->g_indices_r, &c->g_w32, &c->g_erow_r, &c->lm_ys, &c->lm_out, &c->lm_tab, &c->s0_tmp, &c->pg_J, &c->pg_raw, &c->pg_out, &c->pg_flags, &c->pg_bits, &c->pg_enter, &c->pg_sblk,
-                    &c->pg_desc, &c->pg_tbits, &c->pg_events, &c->pg_hard, &c->pg_seg, &c->pg_ctbits, &c->pg_segmode, &c->pg_seglist, &c->nib_map,
+                    &c->lee_rowmap, &c->lee_lperm, &c->g_slag, &c->g_xsum, &c->g_flags, &c->g_xmax, &c->g_lat, &c->g_meanc, &c->g_seff, &c->g_corr, &c->g_thr, &c->sims_raw, &c->g_order, &c->g_rank, &c->g_indices_r, &c->g_w32, &c->g_erow_r, &c->lm_ys, &c->lm_out, &c->lm_tab, &c->s0_tmp, &c->nib_map,
                     &c->np_cnt, &c->np_comp, &c->np_leaves, &c->np_leafsum,
                     &c->rp_cnt, &c->rp_indptr, &c->rp_row, &c->rp_col, &c->rp_bin, &c->rp_rank,
                     &c->dm_parent, &c->dm_qcomp, &c->dm_clear};
     for (DBuf *b : bufs) b->release(&c->mem);
+    c->pg.release(&c->mem);
     for (int k = 0; k < SC_K_COUNT_; ++k) {
         for (auto &ev : c->timers[k].pending) {
             (void)hipEventDestroy(ev.first);
@@ -196,12 +194,7 @@ int sc_ctx_destroy(sc_ctx *c)
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->stream3) (void)hipStreamDestroy(c->stream3);
     if (c->stream4) (void)hipStreamDestroy(c->stream4);
-    for (hipStream_t sp : c->stream_pg)
-        if (sp) (void)hipStreamDestroy(sp);
-    if (c->stream_px) (void)hipStreamDestroy(c->stream_px);
     if (c->stream_out) (void)hipStreamDestroy(c->stream_out);
-    for (hipEvent_t e : c->pg_ev)
-        if (e) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
     delete c;
     return SC_OK;
@@ -220,7 +213,7 @@ int sc_debug_copy(sc_ctx *c, int which, int64_t offset, void *out, int64_t bytes
 {
     SC_REQUIRE(c && out && offset >= 0 && bytes >= 0, SC_ERR_INVALID, "sc_debug_copy: bad argument");
     SC_HIP(hipSetDevice(c->device));
-    const DBuf *bufs[] = {&c->pg_J, &c->pg_raw, &c->pg_bits, &c->pg_enter, &c->pg_sblk, &c->pg_out, &c->perm, &c->inv};
+    const DBuf *bufs[] = {&c->pg.J, &c->pg.raw, &c->pg.bits, &c->pg.enter, &c->pg.sblk, &c->pg.out, &c->perm, &c->inv};
     SC_REQUIRE(which >= 0 && which < (int)(sizeof(bufs) / sizeof(bufs[0])), SC_ERR_INVALID, "sc_debug_copy: unknown buffer %d", which);
     const DBuf *b = bufs[which];
     SC_REQUIRE((size_t)(offset + bytes) <= b->cap, SC_ERR_INVALID, "sc_debug_copy: range exceeds the buffer (%zu bytes)", b->cap);
@@ -261,19 +254,14 @@ int sc_ctx_set_permgen_mode(sc_ctx *c, int mode)
 {
     SC_REQUIRE(c, SC_ERR_INVALID, "null context");
     SC_REQUIRE(mode >= 0 && mode <= 2, SC_ERR_INVALID, "sc_ctx_set_permgen_mode: mode %d not in {0, 1, 2}", mode);
-    c->pg_mode = mode;
-    // re-arm: a context that fell back to the sequential scan after one stalled hand-over (a transient: GPU shared with
-    // another process, a profiler pass) probes its streams again and may return to the block-parallel form
-    c->pg_streams_serial = false;
-    c->pg_probed = false;
-    c->pg_note.clear();
+    c->pg.rearm(mode);
     return SC_OK;
 }
 
 int sc_ctx_permgen_note(sc_ctx *c, const char **message)
 {
     SC_REQUIRE(c && message, SC_ERR_INVALID, "null pointer");
-    *message = c->pg_note.c_str();   // "" while the block-parallel generator is in use; valid until the next generator call
+    *message = c->pg.note.c_str();   // "" while the block-parallel generator is in use; valid until the next generator call
     return SC_OK;
 }
 
@@ -312,11 +300,11 @@ int sc_ctx_permgen_stats(sc_ctx *c, int64_t *jobs_parallel, int64_t *jobs_sequen
                          int64_t *blocks_prepared, int64_t *blocks_chain)
 {
     SC_REQUIRE(c, SC_ERR_INVALID, "null context");
-    if (jobs_parallel) *jobs_parallel = c->pg_jobs_parallel;
-    if (jobs_sequential) *jobs_sequential = c->pg_jobs_sequential;
-    if (fallbacks) *fallbacks = c->pg_fallbacks;
-    if (blocks_prepared) *blocks_prepared = c->pg_blocks_prepared;
-    if (blocks_chain) *blocks_chain = c->pg_blocks_chain;
+    if (jobs_parallel) *jobs_parallel = c->pg.jobs_parallel;
+    if (jobs_sequential) *jobs_sequential = c->pg.jobs_sequential;
+    if (fallbacks) *fallbacks = c->pg.fallbacks;
+    if (blocks_prepared) *blocks_prepared = c->pg.blocks_prepared;
+    if (blocks_chain) *blocks_chain = c->pg.blocks_chain;
     return SC_OK;
 }
 

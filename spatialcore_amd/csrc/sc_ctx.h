@@ -57,7 +57,55 @@ struct KTimer {
     int64_t launches = 0;
 };
 
-struct PermPipe;   // a generator job in flight (sc_perm.hip; begun by sc_moran_seeded_begin, consumed by _finish)
+// The numpy-exact permutation generator's state in the context (sc_permgen.h): scratch, its own streams and events, its form, counters
+struct PermGen {
+    DBuf J, raw, out, bits, enter, sblk;  // accepted j per step, raw 32-bit stream, scan state + chunk ranges, per block: accept masks, entering counts, entry state
+    DBuf flags;       // hand-over words between the chain workgroup and the preparation launches (sc_permgen_phi.hip)
+    DBuf desc, tbits, events, hard;  // block-parallel scan: per-block descriptors + gap-transfer tables (ring), hard flags
+    DBuf seglist;                    // ... per unit in flight: [count | first blocks of the segments k_phi_compose builds]
+    DBuf seg, ctbits, segmode;       // ... segments of prepared blocks: descriptors + composed tables (ring), per-block mode
+    hipStream_t stream_pg[4] = {};   // block-parallel scan: the chip prepares blocks here ahead of the chain
+    hipStream_t stream_px = nullptr; // ... and verifies + expands a finished chunk here, beside the next chunk's chain
+    hipEvent_t ev[34] = {};          // [0 .. 3] k_seg_fill of a chunk done on preparation stream q, [32] raw stream written, [33] chain of a chunk done
+    int mode = 0;                    // 0 auto, 1 sequential scan only, 2 fault injection (tests)
+    bool streams_serial = false;     // a wait on a hand-over word gave up once: the streams of this process do not run concurrently (profiler
+                                     // that serialises kernels, shared hardware queues) -- later jobs take the sequential scan at once
+    bool probed = false;             // the stream-concurrency probe ran (once per context, before the first block-parallel job)
+    std::string note;                // why the generator left the block-parallel form, if it did (sc_ctx_permgen_note)
+    std::string form;                // scratch of sc_ctx_permgen_form
+    int64_t jobs_parallel = 0, jobs_sequential = 0, fallbacks = 0;  // generator jobs by scan form
+    int64_t blocks_prepared = 0, blocks_chain = 0;  // block-parallel jobs: blocks resolved by table lookup / by the chain workgroup
+    int ensure(bool preparation)     // create what is missing: the events, and (preparation) the preparation streams
+    {
+        if (preparation)
+            for (hipStream_t &sp : stream_pg)
+                if (!sp) SC_HIP(hipStreamCreateWithFlags(&sp, hipStreamNonBlocking));
+        for (hipEvent_t &e : ev)
+            if (!e) SC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        return SC_OK;
+    }
+    int sync()                       // wait for the generator's own streams
+    {
+        for (hipStream_t sp : {stream_pg[0], stream_pg[1], stream_pg[2], stream_pg[3], stream_px})
+            if (sp) SC_HIP(hipStreamSynchronize(sp));
+        return SC_OK;
+    }
+    // sc_ctx_set_permgen_mode.  Re-arms: a context that fell back to the sequential scan after one stalled hand-over (a transient: GPU
+    // shared with another process, a profiler pass) probes its streams again and may return to the block-parallel form
+    void rearm(int new_mode) { mode = new_mode; streams_serial = false; probed = false; note.clear(); }
+    void release(int64_t *acct)      // buffers, streams, events
+    {
+        (void)sync();
+        for (DBuf *b : {&J, &raw, &out, &bits, &enter, &sblk, &flags, &desc, &tbits, &events, &hard, &seglist, &seg, &ctbits, &segmode})
+            b->release(acct);
+        for (hipStream_t sp : {stream_pg[0], stream_pg[1], stream_pg[2], stream_pg[3], stream_px})
+            if (sp) (void)hipStreamDestroy(sp);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+struct PermPipe;   // a generator job in flight (sc_permgen.h, sc_perm.hip; begun by sc_moran_seeded_begin, consumed by _finish)
 
 struct sc_ctx {
     int device = 0;
@@ -66,19 +114,8 @@ struct sc_ctx {
     hipStream_t stream2 = nullptr;  // fused permutation/Moran pipeline: rejection scan runs ahead here
     hipStream_t stream3 = nullptr;  // ... and the Fisher-Yates swaps of the scanned chunk here
     hipStream_t stream4 = nullptr;  // ... alternating with this one
-    hipStream_t stream_pg[4] = {};    // block-parallel scan: the chip prepares blocks here ahead of the chain
-    hipStream_t stream_px = nullptr;     // ... and verifies + expands a finished chunk here, beside the next chunk's chain
     hipStream_t stream_out = nullptr;    // r04: result copies that run beside a pipeline, issued by a helper thread (sc_local_moran_seeded)
-    hipEvent_t pg_ev[34] = {};        // rings of events between the preparation and the chain launches + start marker
-    int pg_mode = 0;                  // 0 auto, 1 sequential scan only, 2 fault injection (tests)
-    bool pg_streams_serial = false;   // a wait on a hand-over word gave up once: the streams of this process do not run
-                                      // concurrently (profiler that serialises kernels, shared hardware queues) --
-                                      // later jobs take the sequential scan at once instead of waiting 10 s again
-    bool pg_probed = false;           // the stream-concurrency probe ran (once per context, before the first block-parallel job)
-    std::string pg_note;              // why the generator left the block-parallel form, if it did (sc_ctx_permgen_note)
-    std::string pg_form;              // scratch of sc_ctx_permgen_form
-    int64_t pg_jobs_parallel = 0, pg_jobs_sequential = 0, pg_fallbacks = 0;  // generator jobs by scan form
-    int64_t pg_blocks_prepared = 0, pg_blocks_chain = 0;  // block-parallel jobs: blocks resolved by table lookup / by the chain workgroup
+    PermGen pg;       // the numpy-exact permutation generator's state
     int64_t mem = 0;  // bytes allocated through DBuf
     bool timing = true;
     KTimer timers[SC_K_COUNT_];
@@ -169,11 +206,6 @@ struct sc_ctx {
     bool perm_forward_valid = true; // c->perm holds the active table (false: only its inverse, c->inv, was generated)
     bool perm_bijective = false;   // the active table is known to hold true permutations
     bool perm_checked = false;     // ... or was checked and is not
-    DBuf pg_J, pg_raw, pg_out, pg_bits, pg_enter, pg_sblk;  // device generator scratch: accepted j per step, raw 32-bit stream
-    DBuf pg_flags;       // hand-over words between the chain workgroup and the preparation launches (sc_permgen.hip)
-    DBuf pg_desc, pg_tbits, pg_events, pg_hard;  // block-parallel scan: per-block descriptors + gap-transfer tables (ring), hard flags
-    DBuf pg_seglist;                             // ... per unit in flight: [count | first blocks of the segments k_phi_compose builds]
-    DBuf pg_seg, pg_ctbits, pg_segmode;          // ... segments of prepared blocks: descriptors + composed tables (ring), per-block mode
 
     // ---- Moran / Lee work buffers ----
     DBuf partial, sims, counts, sim_sum, sim_sumsq;
@@ -202,49 +234,6 @@ struct KernelTimerScope {
     ~KernelTimerScope();
 };
 
-// One numpy-exact permutation job on the device (sc_permgen.hip): begin -> {scan, swap} per chunk
-// of permutations -> finish.  Scan state lives on the device so chunks chain without host syncs.
-struct PermJob {
-    int64_t n = 0, n_perm = 0;
-    uint64_t h = 0;            // 1 if the generator starts with a buffered 32-bit half
-    uint64_t st_hi = 0, st_lo = 0, inc_hi = 0, inc_lo = 0;
-    uint32_t buffered = 0;
-    uint64_t total_steps = 0;
-    uint64_t hi = 0;           // raw indices [0, hi) hold stream draws
-    bool trivial = false;      // n == 1
-    double draws_per_perm = 0; // expectation
-    int64_t p_done = 0;        // permutations covered by the scan launches so far
-    int64_t chunk_no = 0;
-    bool phi = false;          // block-parallel scan in use
-    uint64_t B_done = 0;       // blocks covered by the chain launches so far
-    uint64_t unit_start[8] = {};  // first block of the last launch units (ring)
-    int64_t unit_no = 0;
-    int64_t gate_seen[4] = {};   // per preparation stream: the "units completed by the chain" count its last gate waited for
-    int units_ahead = 1;       // launch units prepared ahead of the chain
-};
-// A generator job whose chunks are (being) enqueued on the generator's streams while the consumer catches up.
-struct PermPipe {
-    PermJob job;
-    std::vector<int64_t> bounds;       // chunk k = permutations [bounds[k], bounds[k + 1])
-    std::vector<hipEvent_t> ev;        // per chunk: scanned, swapped
-    int table = 0;                     // 0 rows, 1 inverse rows only, 2 both
-    int64_t n = 0, n_perm = 0, enqueued = 0;   // generator chunks enqueued so far
-    uint64_t state0[6] = {};           // the generator state the job started from (a sequential rerun starts there again)
-};
-#define SC_PERMGEN_RETRY 1000  // internal: the block-parallel scan failed its verification, rerun sequentially
-bool permgen_is_block_parallel(const sc_ctx *c, int64_t n);  // which scan form a job of length n takes
-// units_ahead: launch units the block-parallel scan's preparation runs ahead of its chain (clamped to [1, PHI_AHEAD_MAX])
-int permgen_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int units_ahead, PermJob *job, hipStream_t s);
-int permgen_scan_chunk(sc_ctx *c, PermJob *job, int64_t p1, hipStream_t s, hipStream_t post, hipEvent_t done);
-int permgen_swap_chunk(sc_ctx *c, PermJob *job, int64_t p0, int64_t p1, hipStream_t s, bool inverse, int pw_req);
-bool permgen_can_swap_inverse(int64_t n);
-int sc_perm_forward_ensure(sc_ctx *c);  // materialise c->perm from c->inv after a pipeline that only made the inverse
-int sc_perm_table_is_bijective(sc_ctx *c, int64_t n_perm, bool *bijective);   // inverse rows of an uploaded table + the check
-int invert_rows(sc_ctx *c, int64_t p0, int64_t p1, hipStream_t s);   // inverse rows [p0, p1) of the active table on stream s
-int permgen_finish(sc_ctx *c, PermJob *job, uint64_t *state6);
-int sc_perm_alloc(sc_ctx *c, int64_t n, int64_t n_perm);
-// rows [0, n_perm) of the allocated table <- counter-based permutations p_first .. (sc_permgen.hip), on stream s
-int sc_perm_counter_rows(sc_ctx *c, uint64_t seed, int64_t n, int64_t p_first, int64_t n_perm, hipStream_t s);
 // generator / consumer pipeline (sc_perm.hip): table 0 = permutation rows, 1 = inverse rows only, 2 = both
 constexpr int PIPE_AHEAD = 3;                      // launch units the generator's preparation runs ahead of its chain inside the pipeline
 constexpr int64_t PIPE_TAIL[] = {96, 48, 24};      // permutations of the tapering last chunks (sc_perm.hip: pipe_begin)
@@ -258,8 +247,14 @@ void sc_perm_pipe_abort(sc_ctx *c);    // drain and drop c->pipe (no results)
 int sc_perm_pipeline(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_perm, int table, int units_ahead,
                      const std::function<int()> &after_first, const std::function<int(int64_t, int64_t)> &score);
 // Runs attempt(); if the block-parallel scan failed its verification, runs undo() (may be empty) and then attempt() once
-// more with the sequential scan.  pg_mode is the caller's again on return, on every path.
+// more with the sequential scan.  The generator's mode is the caller's again on return, on every path.
 int permgen_rerun_on_failure(sc_ctx *c, const std::function<int()> &attempt, const std::function<int()> &undo);
+int sc_perm_forward_ensure(sc_ctx *c);  // materialise c->perm from c->inv after a pipeline that only made the inverse
+int sc_perm_table_is_bijective(sc_ctx *c, int64_t n_perm, bool *bijective);   // inverse rows of an uploaded table + the check
+int invert_rows(sc_ctx *c, int64_t p0, int64_t p1, hipStream_t s);   // inverse rows [p0, p1) of the active table on stream s
+int sc_perm_alloc(sc_ctx *c, int64_t n, int64_t n_perm);
+// rows [0, n_perm) of the allocated table <- counter-based permutations p_first .. (sc_perm_counter.hip), on stream s
+int sc_perm_counter_rows(sc_ctx *c, uint64_t seed, int64_t n, int64_t p_first, int64_t n_perm, hipStream_t s);
 
 int sc_timer_collect(sc_ctx *c);
 // ---- expression tiles (sc_expr.hip), all enqueued on c->stream ----

@@ -7,7 +7,7 @@
 #include <functional>
 #include <vector>
 
-#include "sc_ctx.h"
+#include "sc_permgen.h"
 
 // ------------------------------------------------------------------------------------------------
 // A5: the permutation kernel (the metric's dominant kernel)

@@ -10,15 +10,13 @@
 //
 // The stream is sequential (rejections make the draws per permutation data dependent).  The host
 // generator below is the simple exact form (sc_perm_numpy_host); the device table is produced by
-// the parallel exact generator of sc_permgen.hip.
+// the parallel exact generator of sc_permgen.hip (its units: sc_permgen.h).
 #include <stdlib.h>
 #include <string.h>
 
 #include <vector>
 
-#include "sc_ctx.h"
-
-typedef unsigned __int128 u128;
+#include "sc_permgen.h"
 
 namespace {
 
@@ -28,15 +26,10 @@ struct Pcg64 {
     uint32_t buf;
 };
 
-const u128 kMult = ((u128)0x2360ed051fc65da4ULL << 64) | 0x4385df649fccf645ULL;
-
 inline uint64_t next64(Pcg64 &g)
 {
-    g.state = g.state * kMult + g.inc;
-    uint64_t hi = (uint64_t)(g.state >> 64), lo = (uint64_t)g.state;
-    uint64_t x = hi ^ lo;
-    unsigned r = (unsigned)(hi >> 58);
-    return (x >> r) | (x << ((64 - r) & 63));
+    g.state = g.state * pcg_mult() + g.inc;
+    return xsl_rr(g.state);
 }
 
 inline uint32_t next32(Pcg64 &g)
@@ -81,8 +74,7 @@ void shuffle_one(Pcg64 &g, int32_t *a, int64_t n)
 {
     for (int64_t i = 0; i < n; ++i) a[i] = (int32_t)i;
     if (n < 2) return;
-    uint32_t mask = (uint32_t)(n - 1);
-    mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
+    uint32_t mask = smear_mask((uint32_t)(n - 1));
     for (int64_t i = n - 1; i >= 1; --i) {
         // the mask only shrinks when i drops below a power of two
         while ((mask >> 1) >= (uint32_t)i) mask >>= 1;
@@ -207,7 +199,7 @@ static int pipe_generate(sc_ctx *c, PermPipe &pp, int64_t k)
     hipStream_t sw = overlap ? c->stream4 : c->stream3;
     SC_HIP(hipEventCreateWithFlags(&scanned, hipEventDisableTiming));
     SC_HIP(hipEventCreateWithFlags(&swapped, hipEventDisableTiming));
-    SC_TRY(permgen_scan_chunk(c, &pp.job, pp.bounds[(size_t)k + 1], c->stream2, c->stream_px, scanned));
+    SC_TRY(permgen_scan_chunk(c, &pp.job, pp.bounds[(size_t)k + 1], c->stream2, c->pg.stream_px, scanned));
     SC_HIP(hipStreamWaitEvent(sw, scanned, 0));
     // Two permutations per swap workgroup while the chain still runs -- workgroups of the preparation kernels' own size --
     // but only beside the Moran scoring kernel (the one consumer that fills its CUs with wavefronts that live for
@@ -227,9 +219,7 @@ void pipe_drain(sc_ctx *c, PermPipe &pp)
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);
     if (c->stream3) (void)hipStreamSynchronize(c->stream3);
     if (c->stream4) (void)hipStreamSynchronize(c->stream4);
-    if (c->stream_px) (void)hipStreamSynchronize(c->stream_px);
-    for (hipStream_t sp : c->stream_pg)
-        if (sp) (void)hipStreamSynchronize(sp);
+    (void)c->pg.sync();
     (void)hipStreamSynchronize(c->stream);
     for (hipEvent_t e : pp.ev)
         if (e) (void)hipEventDestroy(e);
@@ -253,7 +243,7 @@ int pipe_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int
     c->inv_rows_valid = 0;
     c->perm_forward_valid = false;
     if (!c->stream2) SC_HIP(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-    if (!c->stream_px) SC_HIP(hipStreamCreateWithFlags(&c->stream_px, hipStreamNonBlocking));
+    if (!c->pg.stream_px) SC_HIP(hipStreamCreateWithFlags(&c->pg.stream_px, hipStreamNonBlocking));
     if (!c->stream3) SC_HIP(hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
     if (!c->stream4) SC_HIP(hipStreamCreateWithFlags(&c->stream4, hipStreamNonBlocking));
     // allocations first (hipMalloc synchronises the device), then the streams run freely
@@ -337,8 +327,8 @@ int permgen_rerun_on_failure(sc_ctx *c, const std::function<int()> &attempt, con
     int rc = attempt();
     if (rc != SC_PERMGEN_RETRY) return rc;
     if (undo) SC_TRY(undo());
-    struct ModeRestore { sc_ctx *c; int mode; ~ModeRestore() { c->pg_mode = mode; } } restore{c, c->pg_mode};
-    c->pg_mode = 1;
+    struct ModeRestore { sc_ctx *c; int mode; ~ModeRestore() { c->pg.mode = mode; } } restore{c, c->pg.mode};
+    c->pg.mode = 1;
     return attempt();
 }
 

@@ -181,7 +181,7 @@ def test_swap_rounds_rule_equals_the_sequential_shuffle():
 
 
 def test_fixed_point_rounds_restatement_is_exact():
-    """scripts/fixed_point_rounds_sim.py restates block_fixed_point (sc_permgen.hip) on the CPU to count its rounds; the
+    """scripts/fixed_point_rounds_sim.py restates block_fixed_point (sc_permgen.h) on the CPU to count its rounds; the
     entering counts it converges to must be those of a plain sequential scan of the block, for a block in which a
     permutation ends and for an ordinary one, in all three variants it compares."""
     import importlib.util
