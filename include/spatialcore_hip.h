@@ -297,7 +297,9 @@ int sc_lee_local_seeded(sc_ctx *ctx, uint64_t *state6, int32_t gene_x, int32_t g
  * 359-367): index (into the target array, lowest index on ties) and euclidean distance
  * sqrt(fl(fl(dx*dx)+fl(dy*dy))) of the nearest target for every query point.
  * sc_pairwise_2d replaces cdist(a, b).mean() / .min() (distance.py:269, 349, 397): LDS-tiled
- * brute force over all |a| x |b| pairs. */
+ * brute force over all |a| x |b| pairs.
+ * Like every entry point that reads coordinates, sc_pairwise_2d and sc_pair_table_2d refuse a non-finite one with
+ * SC_ERR_INVALID and its index in the message, on the host, before anything is enqueued. */
 int sc_nearest_2d(sc_ctx *ctx, const double *xy_targets, int64_t n_targets, const double *xy_queries,
                   int64_t n_queries, int32_t *idx_out, double *dist_out);
 int sc_pairwise_2d(sc_ctx *ctx, const double *xy_a, int64_t n_a, const double *xy_b, int64_t n_b,

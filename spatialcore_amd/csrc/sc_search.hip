@@ -556,6 +556,15 @@ extern "C" int sc_nearest_excluding_2d(sc_ctx *c, const double *xy_targets, cons
 // partial[block] = {sum of distances, min distance} for the block's A points.
 #define PW_BTILE 1024
 
+// (a NaN distance would be kept by `sum += d` and skipped by `d < mn`: a NaN mean beside a finite minimum)
+static int require_finite_points(const char *who, const char *set, const double *xy, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i)
+        SC_REQUIRE(isfinite(xy[2 * i]) && isfinite(xy[2 * i + 1]), SC_ERR_INVALID, "%s: %s coordinate %lld is not finite",
+                   who, set, (long long)i);
+    return SC_OK;
+}
+
 __global__ __launch_bounds__(256) void k_pairwise(const double *__restrict__ a, int64_t n_a,
                                                   const double *__restrict__ b, int64_t n_b,
                                                   double *__restrict__ partial)
@@ -600,6 +609,8 @@ extern "C" int sc_pairwise_2d(sc_ctx *c, const double *xy_a, int64_t n_a, const 
 {
     SC_REQUIRE(c && xy_a && xy_b, SC_ERR_INVALID, "sc_pairwise_2d: null pointer");
     SC_REQUIRE(n_a >= 1 && n_b >= 1, SC_ERR_INVALID, "sc_pairwise_2d: empty point set");
+    SC_TRY(require_finite_points("sc_pairwise_2d", "a", xy_a, n_a));
+    SC_TRY(require_finite_points("sc_pairwise_2d", "b", xy_b, n_b));
     SC_HIP(hipSetDevice(c->device));
     const int blocks = (int)ceil_div64(n_a, 256);
     SC_TRY(c->e_tmp_data.ensure(sizeof(double) * 2 * (size_t)(n_a + n_b), &c->mem));
@@ -679,6 +690,8 @@ extern "C" int sc_pair_table_2d(sc_ctx *c, const double *xy_a, const int64_t *a_
         SC_REQUIRE(b_off[g + 1] >= b_off[g], SC_ERR_INVALID, "sc_pair_table_2d: target offsets not monotone");
     const int64_t n_a = a_off[n_groups_a], n_b = b_off[n_groups_b];
     SC_REQUIRE(n_a >= 1 && n_b >= 1, SC_ERR_INVALID, "sc_pair_table_2d: empty point set");
+    SC_TRY(require_finite_points("sc_pair_table_2d", "source", xy_a, n_a));
+    SC_TRY(require_finite_points("sc_pair_table_2d", "target", xy_b, n_b));
     SC_HIP(hipSetDevice(c->device));
     std::vector<int64_t> ch0;
     std::vector<int32_t> chn, chg;
