@@ -45,7 +45,10 @@ extern "C" {
 #define SC_K_PERM_SWAP 6 /* Fisher-Yates application, one workgroup (or wavefront) per permutation */
 #define SC_K_KMEANS_SEED 7  /* centring + k-means++ seeding rounds of sc_kmeans_fit (all runs) */
 #define SC_K_KMEANS_LLOYD 8 /* Lloyd E-step + fixed-order centre reduction of sc_kmeans_fit, final E-step included */
-#define SC_K_COUNT_ 9
+#define SC_K_RANK_EMIT 9    /* sc_ranksum: counting + scatter of the non-zero (key, group) pairs */
+#define SC_K_RANK_SORT 10   /* ... the device-wide radix sort(s) of the pairs */
+#define SC_K_RANK_RUNS 11   /* ... tie runs -> rank sums and tie sums */
+#define SC_K_COUNT_ 12
 
 typedef struct sc_ctx sc_ctx;
 
@@ -415,6 +418,33 @@ int sc_ripley_counter(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_t
 int sc_domains_2d(sc_ctx *ctx, const double *xy_targets, int64_t n_targets, const double *xy_queries, int64_t n_queries,
                   double cell_dist, double shrink, int32_t *target_component_out, int32_t *query_component_out,
                   double *clearance_out);
+
+/* ---- N8 (extension; no reference site: the reference's domain vignette calls scanpy's rank_genes_groups) ----------
+ * Wilcoxon rank sums of the loaded genes (sc_expr_set_*: G genes, n cells) per group of cells, as exact integers.
+ * Definition:
+ *  - group_code[i] in [0, n_groups) places cell i in a group; -1 excludes the cell from the ranking altogether (the
+ *    two-group comparison `reference=<group>`); anything else is SC_ERR_INVALID with the cell index in the message.
+ *  - Per gene the ranked cells get average ranks, 1-based, ties sharing the mean of their positions:
+ *    scipy.stats.rankdata(x[code >= 0]).  Ties are decided on the loaded fp64 values; those represent a float32
+ *    matrix exactly, so float32 input has float32's tie structure.
+ *  - rank2_out[g][k] = sum over the ranked cells of group k of 2 * rank: an integer.
+ *  Only the non-zero values are sorted.  With N ranked cells, n_neg of them below zero, n_zero equal to zero, and a
+ *  run of equal non-zero values at sorted positions [a, b) among the gene's non-zeros:
+ *    a run of negative values has 2 * rank = a + b + 1, a run of positive values 2 * rank = 2 n_zero + a + b + 1,
+ *    every zero has 2 * rank = 2 n_neg + n_zero + 1 (added on the device from group_n - nnz).
+ *  - tie_out[g] = (hi, lo) words of the sum over the tie runs of NON-ZERO values of t^3 - t, exact for every accepted
+ *    n (128-bit).  The zero block's n_zero^3 - n_zero is NOT part of it: the caller adds it.
+ *  - nnz_out[g][k] = cells of group k with a non-zero value; sum_out[g][k] = sum of the group's values (per-workgroup
+ *    partials over at most 256 cells of one group, reduced in a fixed order: no floating-point atomics);
+ *    n_neg_out[g] = ranked cells with a negative value; group_n_out[k] = ranked cells of group k.
+ *  All integer outputs are exact, order-free and identical from run to run, and a gene's results do not depend on the
+ *  genes it is loaded with.  One device-wide radix sort per batch of pairs: genes whose values are all float32-exact
+ *  sort once on a 64-bit key (gene | ordered float32 bits); other batches sort by the ordered fp64 bits and then
+ *  stably by gene.
+ * n must equal the loaded cell count.  Envelope: 1 <= n_groups <= 4096 (SC_ERR_INVALID beyond, limit in the message).
+ * A non-finite expression value gives SC_ERR_INVALID and names the gene; no loaded expression gives SC_ERR_STATE. */
+int sc_ranksum(sc_ctx *ctx, const int32_t *group_code, int64_t n, int32_t n_groups, int64_t *rank2_out,
+               uint64_t *tie_out, int64_t *nnz_out, double *sum_out, int64_t *n_neg_out, int64_t *group_n_out);
 
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across

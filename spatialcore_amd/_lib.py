@@ -22,6 +22,7 @@ SC_OK, SC_ERR_INVALID, SC_ERR_STATE, SC_ERR_HIP, SC_ERR_NOMEM, SC_ERR_EMPTY = 0,
 SC_F32, SC_F64 = 0, 1
 K_MORAN_PERM, K_LAG, K_KNN, K_PERMGEN, K_LEE_PERM, K_PERM_SCAN, K_PERM_SWAP = 0, 1, 2, 3, 4, 5, 6
 K_KMEANS_SEED, K_KMEANS_LLOYD = 7, 8
+K_RANK_EMIT, K_RANK_SORT, K_RANK_RUNS = 9, 10, 11
 
 # every symbol include/spatialcore_hip.h declares: (name, argtypes); restype is always int
 _P = c_void_p
@@ -88,6 +89,7 @@ SYMBOLS = {
     "sc_ripley_counts": [_P, _P, c_int64, c_int32, c_int64, c_int64, _P],
     "sc_ripley_counter": [_P, _P, c_int64, c_int32, ctypes.c_uint64, c_int64, c_int64, c_int64, _P, _P],
     "sc_domains_2d": [_P, _P, c_int64, _P, c_int64, c_double, c_double, _P, _P, _P],
+    "sc_ranksum": [_P, _P, c_int64, c_int32, _P, _P, _P, _P, _P, _P],
     "sc_kmeans_fit": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P,
                       POINTER(c_double), _P, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)],
     "sc_comm_unique_id": [_P],
@@ -644,6 +646,29 @@ class Context:
                                        float(shrink), _ptr(comp_t), _ptr(comp_q) if n_q else None,
                                        _ptr(clear) if (n_q and return_clearance) else None))
         return comp_t, comp_q, clear
+
+    # ---- N8 (extension): rank sums ----------------------------------------------------------
+    def ranksum(self, group_code, n_groups: int) -> dict:
+        """Wilcoxon rank sums of the loaded genes per group (sc_ranksum): ``rank2`` (G, K) int64 = 2 * sum of the average
+        ranks of the group's cells among the cells with a code >= 0 (-1 excludes a cell), ``tie_nonzero`` (G,) Python ints
+        = sum of t^3 - t over the tie runs of non-zero values, ``nnz`` (G, K) int64, ``sums`` (G, K) float64, ``n_neg``
+        (G,) int64 and ``group_n`` (K,) int64.  Exact integers, identical from run to run."""
+        code = _c(group_code, np.int32)
+        if code.ndim != 1:
+            raise ValueError(f"group codes must be 1-D, got shape {code.shape}")
+        # (without a loaded expression the library refuses the call: the arrays only have to exist)
+        G, K = max(int(getattr(self, "_n_genes", 0)), 1), int(n_groups)
+        shape = (G, max(K, 1))
+        rank2 = np.zeros(shape, dtype=np.int64)
+        tie = np.zeros((G, 2), dtype=np.uint64)
+        nnz = np.zeros(shape, dtype=np.int64)
+        sums = np.zeros(shape, dtype=np.float64)
+        n_neg = np.zeros(G, dtype=np.int64)
+        group_n = np.zeros(max(K, 1), dtype=np.int64)
+        _check(self._lib.sc_ranksum(self._h, _ptr(code), code.size, K, _ptr(rank2), _ptr(tie), _ptr(nnz), _ptr(sums),
+                                    _ptr(n_neg), _ptr(group_n)))
+        tie_nonzero = np.array([(int(hi) << 64) | int(lo) for hi, lo in tie], dtype=object)
+        return {"rank2": rank2, "tie_nonzero": tie_nonzero, "nnz": nnz, "sums": sums, "n_neg": n_neg, "group_n": group_n}
 
     # ---- A9 ---------------------------------------------------------------------------------
     def profile_counts(self, labels, n_types: int) -> np.ndarray:

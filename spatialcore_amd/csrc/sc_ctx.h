@@ -147,6 +147,11 @@ struct sc_ctx {
     DBuf rp_cnt, rp_indptr, rp_row, rp_col, rp_bin, rp_rank;   // per-position counts / offsets, pair ends, radius bin (1 byte), cell -> position
     // ---- spatial domains (sc_domains.hip): union-find parents by target index, per-query component and clearance ----
     DBuf dm_parent, dm_qcomp, dm_clear;
+    // ---- rank sums (sc_ranksum.hip): group-sorted cell order in pieces, per-piece partials, the pair arrays (double
+    // buffered for the sort), per-gene offsets / negative counts / flags, the result tables ----
+    DBuf rs_order, rs_pstart, rs_pgroup, rs_gpiece, rs_groupn, rs_psum, rs_pnnz, rs_poff, rs_goff, rs_neg, rs_flag;
+    DBuf rs_keys, rs_keys2, rs_pay, rs_pay2, rs_gkey, rs_gkey2, rs_idx, rs_idx2, rs_tmp;
+    DBuf rs_rank2, rs_tie, rs_nnz, rs_sum;
 
     // ---- graph (CSR, rows sorted by column) + transpose ----
     int64_t g_n = 0, g_nnz = 0;

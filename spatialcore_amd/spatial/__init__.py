@@ -10,6 +10,7 @@ from spatialcore_amd.spatial.autocorrelation import (
 )
 from spatialcore_amd.spatial.distance import calculate_domain_distances, get_distance_matrix
 from spatialcore_amd.spatial.domains import get_domain_summary, make_spatial_domains
+from spatialcore_amd.spatial.markers import rank_genes_groups
 from spatialcore_amd.spatial.neighborhoods import (
     compute_neighborhood_profile,
     identify_niches,
@@ -31,4 +32,5 @@ __all__ = [
     "get_domain_summary",
     "calculate_domain_distances",
     "get_distance_matrix",
+    "rank_genes_groups",  # extension: scanpy's function, not in the reference
 ]
