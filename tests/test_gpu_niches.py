@@ -9,7 +9,7 @@ import pytest
 
 import kmeans_restated as kr
 from conftest import load_golden, make_adata
-from test_cpu_niches import CASES, LATTICE_TIES, ari
+from test_cpu_niches import BLOB_SHAPES, CASES, LATTICE_TIES, ari, blobs
 
 pytestmark = pytest.mark.gpu
 
@@ -70,36 +70,22 @@ def test_niches_match_reference(name):
     np.testing.assert_allclose(a.uns["niche_centroids"], G[f"{name}_centroids"], rtol=0, atol=1e-3)
 
 
-def _blobs(n, C, K, seed, dtype):
-    rng = np.random.default_rng(seed)
-    centres = rng.normal(0, 1.0, (K, C))
-    X = centres[rng.integers(0, K, n)] + rng.normal(0, 0.6, (n, C))
-    return X.astype(dtype)
-
-
-@pytest.mark.parametrize("n,C,K,n_init,max_iter,dtype,seed", [
-    (3000, 6, 5, 10, 300, np.float32, 1),
-    (3000, 6, 5, 10, 300, np.float64, 2),       # float64 input: no float32 rounding of D^2 or the potential
-    (2500, 3, 9, 4, 300, np.float32, 3),        # K > C
-    (2000, 100, 40, 2, 300, np.float32, 4),     # the general path (C > 64)
-    (5000, 8, 6, 1, 300, np.float32, 5),        # n_init = 1
-    (3000, 6, 5, 10, 1, np.float32, 6),         # max_iter = 1: no convergence, the final E-step
-    (9000, 5, 70, 2, 300, np.float64, 7),       # K > 64: the general path, several seeding groups
-])
+@pytest.mark.parametrize("n,C,K,n_init,max_iter,dtype,seed", BLOB_SHAPES)
 def test_kmeans_matches_restatement(n, C, K, n_init, max_iter, dtype, seed):
-    X = _blobs(n, C, K, seed, dtype)
+    """Equality throughout: the restatement sums in the kernels' own orders (kernel_order=True)."""
+    X = blobs(n, C, K, seed, dtype)
     fit, draws = _ctx_fit(X, K, n_init, max_iter, seed)
-    ref = kr.fit(X, K, n_init, max_iter, draws)
+    ref = kr.fit(X, K, n_init, max_iter, draws, kernel_order=True)
     np.testing.assert_array_equal(fit["seeds"], ref["seeds"])
     np.testing.assert_array_equal(fit["labels"], ref["labels"])
-    assert fit["inertia"] == pytest.approx(ref["inertia"], rel=1e-9)
-    assert fit["n_iter"] == ref["n_iter"] and fit["strict"] == ref["strict"]
+    assert fit["inertia"] == ref["inertia"]
+    assert fit["n_iter"] == ref["n_iter"] and fit["strict"] == ref["strict"] and fit["distinct"] == ref["distinct"]
     assert fit["centers"].dtype == X.dtype
-    np.testing.assert_allclose(fit["centers"], ref["centers"], rtol=0, atol=1e-5 if dtype == np.float32 else 1e-12)
+    np.testing.assert_array_equal(fit["centers"], ref["centers"])
 
 
 def test_kmeans_is_bit_reproducible():
-    X = _blobs(20000, 12, 8, 9, np.float32)
+    X = blobs(20000, 12, 8, 9, np.float32)
     a, _ = _ctx_fit(X, 8, 10, 300, 0)
     b, _ = _ctx_fit(X, 8, 10, 300, 0)
     for k in ("labels", "centers", "seeds"):
@@ -125,7 +111,7 @@ def test_profile_then_niches_end_to_end():
 
 
 def test_minibatch_is_answered_by_lloyd():
-    X = _blobs(4000, 6, 5, 11, np.float32)
+    X = blobs(4000, 6, 5, 11, np.float32)
     a, _ = _run(X, n_niches=5, method="kmeans")
     b, _ = _run(X, n_niches=5, method="minibatch_kmeans")
     np.testing.assert_array_equal(a.obs["niche"].cat.codes.to_numpy(), b.obs["niche"].cat.codes.to_numpy())
