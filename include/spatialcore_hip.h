@@ -6,7 +6,8 @@
  * (reference src/spatialcore/spatial/__init__.py:11-52); spatialcore_amd/spatial/ mirrors those
  * functions and reaches the GPU only through the entry points declared here (ctypes).
  * Each entry point names the reference call site(s) whose arithmetic it replaces;
- * AC = src/spatialcore/spatial/autocorrelation.py, NB = src/spatialcore/spatial/neighborhoods.py.
+ * AC = src/spatialcore/spatial/autocorrelation.py, NB = src/spatialcore/spatial/neighborhoods.py,
+ * CL = src/spatialcore/stats/classify.py, TH = src/spatialcore/stats/_thresholding.py.
  *
  * Conventions
  *  - plain pointers and sizes only; every function returns an int status (SC_OK = 0) and never
@@ -48,7 +49,12 @@ extern "C" {
 #define SC_K_RANK_EMIT 9    /* sc_ranksum: counting + scatter of the non-zero (key, group) pairs */
 #define SC_K_RANK_SORT 10   /* ... the device-wide radix sort(s) of the pairs */
 #define SC_K_RANK_RUNS 11   /* ... tie runs -> rank sums and tie sums */
-#define SC_K_COUNT_ 12
+#define SC_K_THRESH_SCORE 12 /* sc_metagene_score: per-cell score, mask and the fixed-order statistics */
+#define SC_K_THRESH_SORT 13  /* sc_ks_prepare: device-wide radix sort of the scores + background moments */
+#define SC_K_THRESH_KS 14    /* sc_ks_argmax / sc_ks_classify: D = ECDF - Phi, its argmax, deviation scores and labels */
+#define SC_K_GMM_EM 15       /* sc_gmm_fit: the fused E-step / M-sums pass and the per-run parameter stage, all runs */
+#define SC_K_GMM_POST 16     /* sc_gmm_posterior: P(high) and labels of every cell */
+#define SC_K_COUNT_ 17
 
 typedef struct sc_ctx sc_ctx;
 
@@ -445,6 +451,74 @@ int sc_domains_2d(sc_ctx *ctx, const double *xy_targets, int64_t n_targets, cons
  * A non-finite expression value gives SC_ERR_INVALID and names the gene; no loaded expression gives SC_ERR_STATE. */
 int sc_ranksum(sc_ctx *ctx, const int32_t *group_code, int64_t n, int32_t n_groups, int64_t *rank2_out,
                uint64_t *tie_out, int64_t *nnz_out, double *sum_out, int64_t *n_neg_out, int64_t *group_n_out);
+
+/* ---- T1-T4: classify_by_threshold (CL:419-894, TH:27-344) -----------------------------------------------------------
+ * Every floating-point sum of these entry points is taken in ONE order ("block order"): workgroup b owns the 2048
+ * consecutive points [2048 b, 2048 b + 2048), its thread t adds the points 2048 b + 256 j + t, j = 0 .. 7, in that order;
+ * the 256 thread values are added as a fixed tree (value[t] += value[t + h], h = 128, 64, .. 1); the workgroups are added
+ * in index order.  No floating-point atomics: each result is a function of the arguments alone, bit for bit.
+ * tests/threshold_restated.py states the same in numpy.
+ *
+ * T1 sc_metagene_score -- compute_metagene_score (TH:27-99) plus the mask and checks of CL:680-745.
+ *  - features: n x n_features, row-major, SC_F32 or SC_F64; 1 <= n_features <= 64.
+ *  - method: 0 shifted_geometric_mean (exp(mean(log(x + pseudocount))) - pseudocount), 1 geometric_mean (eps = 1e-10,
+ *    TH:82), 2 arithmetic_mean, 3 median, 4 minimum.  The mean over the features is numpy's pairwise sum of a
+ *    contiguous row (fewer than 8 terms: in order; otherwise 8 accumulators, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the
+ *    remainder in order).  Methods 2-4 compute in the input type and equal numpy bit for bit; methods 0 and 1 compute
+ *    in fp64 and round to the input type once.
+ *  - valid_out[n]: 1 where every feature of the row is finite (CL:680); score_out[n] in the input type, NaN on the
+ *    other rows.
+ *  - stats_out[3]: min, max and mean (fp64; block order over all rows, a row that is not valid adding nothing) of the
+ *    valid scores (CL:723-726);
+ *    counts_out[3]: valid rows, valid rows with a score < 1e-6 (1e-6 rounded to the input type as numpy compares it,
+ *    CL:732-733), valid rows with a negative feature (CL:702). */
+int sc_metagene_score(sc_ctx *ctx, const void *features, int dtype, int64_t n, int32_t n_features, int32_t method,
+                      double pseudocount, uint8_t *valid_out, void *score_out, double *stats_out, int64_t *counts_out);
+
+/* T2 threshold_ks (TH:102-198), in three calls around the host's two O(1) fallbacks (TH:158-165, 181-182).
+ * sc_ks_prepare: sorts the n scores (SC_F32 or SC_F64, all finite; n >= 10) with the device-wide radix sort of
+ *  sc_ranksum on the ordered bits of their fp64 values and keeps the sorted fp64 array in the context.
+ *  bg_out[2] = mean and POPULATION standard deviation (two passes, block order, fp64) of the first
+ *  max(int(n * background_quantile), 10) sorted scores (TH:151-155); rank_out[k] = sorted[ranks[k]] for the n_ranks
+ *  order statistics the host asks for; sorted_out[n] (may be NULL) = the whole sorted array.
+ * sc_ks_argmax: D_i = (i + 1) / n - Phi((s_i - mean) / std) (TH:168-177) over the sorted array of the last
+ *  sc_ks_prepare, Phi as scipy's ndtr (x = a / sqrt 2: 0.5 + 0.5 erf(x) for |x| < 1, else 0.5 erfc(|x|), mirrored for x > 0); out: the FIRST index of the largest D, its score and D itself.
+ * sc_ks_classify: deviation_out[i] = clip((score_i - threshold) / range, 0, 1) in fp64 with range = max(max_score -
+ *  threshold, 1e-10) (TH:185-190), labels_out[i] = score_i >= threshold (CL:770), *n_high_out = their number. */
+int sc_ks_prepare(sc_ctx *ctx, const void *scores, int dtype, int64_t n, double background_quantile,
+                  const int64_t *ranks, int32_t n_ranks, double *rank_out, double *bg_out, double *sorted_out);
+int sc_ks_argmax(sc_ctx *ctx, double bg_mean, double bg_std, int64_t *index_out, double *score_out, double *d_out);
+int sc_ks_classify(sc_ctx *ctx, const void *scores, int dtype, int64_t n, double threshold, double max_score,
+                   double *deviation_out, int32_t *labels_out, int64_t *n_high_out);
+
+/* T3 sc_gmm_fit -- GaussianMixture(n_components=K, n_init, covariance_type="full", random_state).fit on n x 1 scores
+ * (TH:271-277), sklearn 1.7.2 (mixture/_base.py, _gaussian_mixture.py) replayed with all n_init runs side by side.
+ *  - k-means labels: run r starts from KMeans(K, n_init=1, random_state=<the one shared RandomState>).fit(X).labels_;
+ *    the ten calls consume the stream consecutively, so `uniforms` is the layout of sc_kmeans_fit for n_init runs,
+ *    and km_tol / x_mean / km_max_iter are what that entry takes (C = 1).  The same seeding and Lloyd kernels run;
+ *    EVERY run's final labels are kept (km_labels_out[n_init][n], may be NULL).
+ *  - initialisation from one-hot responsibilities: nk = sum r + 10 eps (eps = 2^-52), mean = sum r x / nk, variance
+ *    = sum r (x - mean)^2 / nk + reg_covar in a second pass around that mean, weights = nk / n.
+ *  - one EM iteration = one launch over the scores serving every active run (log-probabilities, log-sum-exp as
+ *    max + log sum exp(. - max), lower-bound sum and the M-step sums S0 = sum r, S1 = sum r x, A = sum r (x - c),
+ *    B = sum r (x - c)^2 around the current mean c, block order) and one small launch per run: nk = S0 + 10 eps,
+ *    mean = S1 / nk, d = mean - c, variance = (B - 2 d A + d d S0) / nk + reg_covar (ONE pass, shifted; sklearn takes
+ *    a second pass around the new mean), weights = nk / sum nk, lower bound = mean log-likelihood; a run stops when
+ *    |change| < tol (converged) or after max_iter iterations, with the parameters of its last M-step.
+ *  - best run: strictly larger lower bound, so the first of equal runs wins.
+ * All arithmetic is fp64 whatever the score type.  Out, per run: weights / means / variances [n_init][K],
+ * lower_bound [n_init], n_iter and converged [n_init]; *best_out.  2 <= K <= 8, K <= n <= 2^31 - 1. */
+int sc_gmm_fit(sc_ctx *ctx, const void *scores, int dtype, int64_t n, int32_t K, int32_t n_init, int32_t km_max_iter,
+               double km_tol, const void *x_mean, const double *uniforms, int32_t max_iter, double tol, double reg_covar,
+               int32_t *km_labels_out, double *weights_out, double *means_out, double *variances_out,
+               double *lower_bound_out, int32_t *n_iter_out, int32_t *converged_out, int32_t *best_out);
+
+/* T4 sc_gmm_posterior -- predict_proba under given parameters (TH:308-331, CL:785-795): for every score the
+ * responsibilities as in T3, prob_out[i] = sum of those of the components high[0 .. n_high) in that order,
+ * labels_out[i] = prob > cutoff, *n_high_cells_out = their number.  The scores need not be those of the fit. */
+int sc_gmm_posterior(sc_ctx *ctx, const void *scores, int dtype, int64_t n, int32_t K, const double *weights,
+                     const double *means, const double *variances, const int32_t *high, int32_t n_high, double cutoff,
+                     double *prob_out, int32_t *labels_out, int64_t *n_high_cells_out);
 
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across

@@ -23,6 +23,8 @@ SC_F32, SC_F64 = 0, 1
 K_MORAN_PERM, K_LAG, K_KNN, K_PERMGEN, K_LEE_PERM, K_PERM_SCAN, K_PERM_SWAP = 0, 1, 2, 3, 4, 5, 6
 K_KMEANS_SEED, K_KMEANS_LLOYD = 7, 8
 K_RANK_EMIT, K_RANK_SORT, K_RANK_RUNS = 9, 10, 11
+K_THRESH_SCORE, K_THRESH_SORT, K_THRESH_KS, K_GMM_EM, K_GMM_POST = 12, 13, 14, 15, 16
+METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
 
 # every symbol include/spatialcore_hip.h declares: (name, argtypes); restype is always int
 _P = c_void_p
@@ -92,6 +94,13 @@ SYMBOLS = {
     "sc_ranksum": [_P, _P, c_int64, c_int32, _P, _P, _P, _P, _P, _P],
     "sc_kmeans_fit": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P,
                       POINTER(c_double), _P, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)],
+    "sc_metagene_score": [_P, _P, c_int, c_int64, c_int32, c_int32, c_double, _P, _P, _P, _P],
+    "sc_ks_prepare": [_P, _P, c_int, c_int64, c_double, _P, c_int32, _P, _P, _P],
+    "sc_ks_argmax": [_P, c_double, c_double, POINTER(c_int64), POINTER(c_double), POINTER(c_double)],
+    "sc_ks_classify": [_P, _P, c_int, c_int64, c_double, c_double, _P, _P, POINTER(c_int64)],
+    "sc_gmm_fit": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_double, _P, _P, c_int32, c_double, c_double,
+                   _P, _P, _P, _P, _P, _P, _P, POINTER(c_int32)],
+    "sc_gmm_posterior": [_P, _P, c_int, c_int64, c_int32, _P, _P, _P, _P, c_int32, c_double, _P, _P, POINTER(c_int64)],
     "sc_comm_unique_id": [_P],
     "sc_comm_create": [_P, _P, c_int, c_int, POINTER(c_void_p)],
     "sc_comm_destroy": [_P],
@@ -702,6 +711,102 @@ class Context:
                                        byref(distinct)))
         return {"labels": labels, "centers": centers, "inertia": inertia.value, "seeds": seeds,
                 "n_iter": n_iter.value, "strict": bool(strict.value), "distinct": distinct.value}
+
+    # ---- T1-T4: classify_by_threshold --------------------------------------------------------
+    @staticmethod
+    def _scores(a, what: str) -> np.ndarray:
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64) or a.ndim != 1:
+            raise ValueError(f"{what}: scores must be a 1-D float32 or float64 array, got {a.dtype} {a.shape}")
+        return a
+
+    def metagene_score(self, features, method: str, pseudocount: float = 0.1) -> dict:
+        """sc_metagene_score on a float32 or float64 (n, F) matrix: ``valid`` (n,) bool, ``score`` (n,) in the input type
+        (NaN where not valid), ``min`` / ``max`` / ``mean`` of the valid scores, ``n_valid``, ``n_below`` (valid scores
+        < 1e-6) and ``n_negative`` (valid rows with a negative feature)."""
+        F = np.ascontiguousarray(features)
+        if F.dtype not in (np.float32, np.float64) or F.ndim != 2:
+            raise ValueError(f"metagene_score: features must be a 2-D float32 or float64 array, got {F.dtype} {F.shape}")
+        n, nf = F.shape
+        valid = np.empty(n, dtype=np.uint8)
+        score = np.empty(n, dtype=F.dtype)
+        stats = np.empty(3, dtype=np.float64)
+        counts = np.empty(3, dtype=np.int64)
+        _check(self._lib.sc_metagene_score(self._h, _ptr(F), SC_F32 if F.dtype == np.float32 else SC_F64, n, nf,
+                                           METAGENE_METHODS.index(method), float(pseudocount), _ptr(valid), _ptr(score),
+                                           _ptr(stats), _ptr(counts)))
+        return {"valid": valid.astype(bool), "score": score, "min": float(stats[0]), "max": float(stats[1]),
+                "mean": float(stats[2]), "n_valid": int(counts[0]), "n_below": int(counts[1]),
+                "n_negative": int(counts[2])}
+
+    def ks_prepare(self, scores, background_quantile: float, ranks=(), return_sorted: bool = False) -> dict:
+        """sc_ks_prepare: sorts the scores on the device (they stay there for ks_argmax); ``bg_mean`` / ``bg_std`` of the
+        lowest max(int(n q), 10) of them, ``order`` = the order statistics at ``ranks``, ``sorted`` on request."""
+        x = self._scores(scores, "ks_prepare")
+        rk = _c(ranks, np.int64)
+        vals = np.empty(rk.size, dtype=np.float64)
+        bg = np.empty(2, dtype=np.float64)
+        srt = np.empty(x.size, dtype=np.float64) if return_sorted else None
+        _check(self._lib.sc_ks_prepare(self._h, _ptr(x), SC_F32 if x.dtype == np.float32 else SC_F64, x.size,
+                                       float(background_quantile), _ptr(rk) if rk.size else None, rk.size,
+                                       _ptr(vals) if rk.size else None, _ptr(bg), _ptr(srt)))
+        return {"bg_mean": float(bg[0]), "bg_std": float(bg[1]), "order": vals, "sorted": srt}
+
+    def ks_argmax(self, bg_mean: float, bg_std: float) -> Tuple[int, float, float]:
+        """(first index of the largest D, the sorted score there, D) over the scores of the last ks_prepare."""
+        i, sc, d = c_int64(0), c_double(0.0), c_double(0.0)
+        _check(self._lib.sc_ks_argmax(self._h, float(bg_mean), float(bg_std), byref(i), byref(sc), byref(d)))
+        return i.value, sc.value, d.value
+
+    def ks_classify(self, scores, threshold: float, max_score: float):
+        """(deviation scores float64, labels int32 = score >= threshold, their number)."""
+        x = self._scores(scores, "ks_classify")
+        dev = np.empty(x.size, dtype=np.float64)
+        lab = np.empty(x.size, dtype=np.int32)
+        nh = c_int64(0)
+        _check(self._lib.sc_ks_classify(self._h, _ptr(x), SC_F32 if x.dtype == np.float32 else SC_F64, x.size,
+                                        float(threshold), float(max_score), _ptr(dev), _ptr(lab), byref(nh)))
+        return dev, lab, nh.value
+
+    def gmm_fit(self, scores, n_components: int, n_init: int, km_max_iter: int, km_tol: float, x_mean, uniforms,
+                max_iter: int = 100, tol: float = 1e-3, reg_covar: float = 1e-6, return_km_labels: bool = False) -> dict:
+        """sc_gmm_fit: every run's ``weights`` / ``means`` / ``variances`` (n_init, K), ``lower_bound``, ``n_iter`` and
+        ``converged`` (n_init,), the index ``best``, and on request every run's k-means labels (n_init, n)."""
+        x = self._scores(scores, "gmm_fit")
+        K, R = int(n_components), int(n_init)
+        xm = np.ascontiguousarray(np.asarray(x_mean).reshape(-1), dtype=x.dtype)
+        u = _c(uniforms, np.float64)
+        L = 2 + int(np.log(K)) if K >= 1 else 0
+        if xm.size != 1 or u.size != R * (1 + (K - 1) * L):
+            raise ValueError("gmm_fit: x_mean must have one entry and uniforms n_init * (1 + (K - 1) * L)")
+        w, mu, var = (np.empty((R, K), dtype=np.float64) for _ in range(3))
+        lb = np.empty(R, dtype=np.float64)
+        n_iter = np.empty(R, dtype=np.int32)
+        conv = np.empty(R, dtype=np.int32)
+        km = np.empty((R, x.size), dtype=np.int32) if return_km_labels else None
+        best = c_int32(0)
+        _check(self._lib.sc_gmm_fit(self._h, _ptr(x), SC_F32 if x.dtype == np.float32 else SC_F64, x.size, K, R,
+                                    int(km_max_iter), float(km_tol), _ptr(xm), _ptr(u), int(max_iter), float(tol),
+                                    float(reg_covar), _ptr(km), _ptr(w), _ptr(mu), _ptr(var), _ptr(lb), _ptr(n_iter),
+                                    _ptr(conv), byref(best)))
+        return {"weights": w, "means": mu, "variances": var, "lower_bound": lb, "n_iter": n_iter,
+                "converged": conv.astype(bool), "best": best.value, "km_labels": km}
+
+    def gmm_posterior(self, scores, weights, means, variances, high, cutoff: float):
+        """(P(high) float64 = the responsibilities of the components ``high`` added in that order, labels int32 = P >
+        cutoff, their number) of every score under the given mixture."""
+        x = self._scores(scores, "gmm_posterior")
+        w, mu, var = _c(weights, np.float64), _c(means, np.float64), _c(variances, np.float64)
+        hi = _c(high, np.int32)
+        if not (w.size == mu.size == var.size):
+            raise ValueError("gmm_posterior: weights, means and variances must have one entry per component")
+        prob = np.empty(x.size, dtype=np.float64)
+        lab = np.empty(x.size, dtype=np.int32)
+        nh = c_int64(0)
+        _check(self._lib.sc_gmm_posterior(self._h, _ptr(x), SC_F32 if x.dtype == np.float32 else SC_F64, x.size, w.size,
+                                          _ptr(w), _ptr(mu), _ptr(var), _ptr(hi), hi.size, float(cutoff), _ptr(prob),
+                                          _ptr(lab), byref(nh)))
+        return prob, lab, nh.value
 
     # ---- N4 (extension) ---------------------------------------------------------------------
     def enrichment_counts(self, labels, n_types: int, n_perm: int, perm_row0: int = 0) -> np.ndarray:

@@ -181,7 +181,7 @@ int sc_ctx_destroy(sc_ctx *c)
                     &c->dm_parent, &c->dm_qcomp, &c->dm_clear,
                     &c->rs_order, &c->rs_pstart, &c->rs_pgroup, &c->rs_gpiece, &c->rs_groupn, &c->rs_psum, &c->rs_pnnz, &c->rs_poff,
                     &c->rs_goff, &c->rs_neg, &c->rs_flag, &c->rs_keys, &c->rs_keys2, &c->rs_pay, &c->rs_pay2, &c->rs_gkey, &c->rs_gkey2,
-                    &c->rs_idx, &c->rs_idx2, &c->rs_tmp, &c->rs_rank2, &c->rs_tie, &c->rs_nnz, &c->rs_sum};
+                    &c->rs_idx, &c->rs_idx2, &c->rs_tmp, &c->rs_rank2, &c->rs_tie, &c->rs_nnz, &c->rs_sum, &c->th_sorted};
     for (DBuf *b : bufs) b->release(&c->mem);
     c->pg.release(&c->mem);
     for (int k = 0; k < SC_K_COUNT_; ++k) {

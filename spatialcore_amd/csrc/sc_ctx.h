@@ -152,6 +152,9 @@ struct sc_ctx {
     DBuf rs_order, rs_pstart, rs_pgroup, rs_gpiece, rs_groupn, rs_psum, rs_pnnz, rs_poff, rs_goff, rs_neg, rs_flag;
     DBuf rs_keys, rs_keys2, rs_pay, rs_pay2, rs_gkey, rs_gkey2, rs_idx, rs_idx2, rs_tmp;
     DBuf rs_rank2, rs_tie, rs_nnz, rs_sum;
+    // ---- thresholds (sc_threshold.hip): the sorted fp64 scores of the last sc_ks_prepare, for sc_ks_argmax ----
+    DBuf th_sorted;
+    int64_t th_n = 0;
 
     // ---- graph (CSR, rows sorted by column) + transpose ----
     int64_t g_n = 0, g_nnz = 0;
@@ -335,5 +338,14 @@ void sc_graph_moments_drain(sc_ctx *c);  // wait for a begun computation (before
 int sc_graph_capture_order(sc_ctx *c, int64_t n);  // called by the graph setters
 int sc_graph_ensure_order(sc_ctx *c);           // rank / relabelled columns / float weights, built on first use
 int sc_perm_generate_device(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_perm);
+// ---- shared with sc_threshold.hip ----
+// device-wide radix sort of cnt (key, payload) pairs on the key bits [0, end_bit), on c->stream; scratch in c->rs_tmp
+// (sc_ranksum.hip, which instantiates the combinations in use)
+template <class K, class V>
+int rs_sort(sc_ctx *c, const K *k_in, K *k_out, const V *v_in, V *v_out, int64_t cnt, int end_bit);
+// sc_kmeans_fit's seeding and Lloyd passes for n_init runs (same arguments), keeping EVERY run's final labels:
+// labels_dev[n_init][n] is a device array, written on c->stream (sc_kmeans.hip)
+int sc_kmeans_run_labels(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t C, int32_t K, int32_t n_init,
+                         int32_t max_iter, double tol, const void *x_mean, const double *uniforms, int32_t *labels_dev);
 void sc_launch_spmv_vec(sc_ctx *c, const int64_t *indptr, const int32_t *indices, const double *w,
                         const double *x, double *y, int64_t n);

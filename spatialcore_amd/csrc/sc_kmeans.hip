@@ -479,7 +479,7 @@ std::vector<int64_t> first_centres(int64_t n, const double *u0, int64_t stride, 
 template <class T>
 int kmeans_fit(sc_ctx *c, const T *X, int64_t n, int C, int K, int R, int max_iter, double tol, const T *x_mean,
                const double *uniforms, int32_t *labels_out, T *centers_out, double *inertia_out, int64_t *seeds_out,
-               int32_t *n_iter_out, int32_t *strict_out, int32_t *distinct_out)
+               int32_t *n_iter_out, int32_t *strict_out, int32_t *distinct_out, int32_t *run_labels_dev = nullptr)
 {
     hipStream_t s = c->stream;
     const int L = 2 + (int)std::log((double)K);
@@ -640,6 +640,11 @@ int kmeans_fit(sc_ctx *c, const T *X, int64_t n, int C, int K, int R, int max_it
         estep(1);
     }
     SC_HIP(hipGetLastError());
+    if (run_labels_dev) {   // sc_kmeans_run_labels: every run's labels stay on the device; no best run is chosen
+        SC_HIP(hipMemcpyAsync(run_labels_dev, m.b[LAB].p, sz[LAB], hipMemcpyDeviceToDevice, s));
+        SC_HIP(hipStreamSynchronize(s));
+        return SC_OK;
+    }
     SC_HIP(hipMemcpyAsync(inert.data(), m.b[INERT].p, sz[INERT], hipMemcpyDeviceToHost, s));
     SC_HIP(hipMemcpyAsync(st.data(), m.b[STATE].p, sz[STATE], hipMemcpyDeviceToHost, s));
     SC_HIP(hipMemcpyAsync(seeds_out, m.b[SEEDS].p, sz[SEEDS], hipMemcpyDeviceToHost, s));
@@ -688,6 +693,16 @@ int kmeans_fit(sc_ctx *c, const T *X, int64_t n, int C, int K, int R, int max_it
 }
 
 }  // namespace
+
+int sc_kmeans_run_labels(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t C, int32_t K, int32_t n_init,
+                         int32_t max_iter, double tol, const void *x_mean, const double *uniforms, int32_t *labels_dev)
+{
+    if (dtype == SC_F32)
+        return kmeans_fit<float>(c, (const float *)X, n, C, K, n_init, max_iter, tol, (const float *)x_mean, uniforms,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, labels_dev);
+    return kmeans_fit<double>(c, (const double *)X, n, C, K, n_init, max_iter, tol, (const double *)x_mean, uniforms,
+                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, labels_dev);
+}
 
 extern "C" int sc_kmeans_fit(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t C, int32_t K, int32_t n_init,
                              int32_t max_iter, double tol, const void *x_mean, const double *uniforms,

@@ -335,7 +335,7 @@ __global__ __launch_bounds__(256) void k_rs_final(const double *__restrict__ psu
 // ------------------------------------------------------------------------------------------------
 
 template <class K, class V>
-static int rs_sort(sc_ctx *c, const K *k_in, K *k_out, const V *v_in, V *v_out, int64_t cnt, int end_bit)
+int rs_sort(sc_ctx *c, const K *k_in, K *k_out, const V *v_in, V *v_out, int64_t cnt, int end_bit)
 {
     size_t tmp = 0;
     SC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, k_in, k_out, v_in, v_out, (size_t)cnt, 0, end_bit, c->stream));
@@ -343,6 +343,8 @@ static int rs_sort(sc_ctx *c, const K *k_in, K *k_out, const V *v_in, V *v_out, 
     SC_HIP(hipcub::DeviceRadixSort::SortPairs(c->rs_tmp.p, tmp, k_in, k_out, v_in, v_out, (size_t)cnt, 0, end_bit, c->stream));
     return SC_OK;
 }
+
+template int rs_sort<u64, uint32_t>(sc_ctx *, const u64 *, u64 *, const uint32_t *, uint32_t *, int64_t, int);   // also sc_threshold.hip's
 
 static int bits_for(int64_t count)   // bits that hold 0 .. count - 1 (at least 1)
 {
