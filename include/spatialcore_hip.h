@@ -286,6 +286,36 @@ int sc_local_moran_hist(sc_ctx *ctx, int64_t *hist_out);
 int sc_local_moran_classify(sc_ctx *ctx, const float *p_tab, const float *padj_tab, const uint8_t *force_ns,
                             float alpha, float *p_out, float *padj_out, int8_t *quadrant_out);
 
+/* ---- N1b: Getis-Ord Gi / Gi* and local Geary's C (EXTENSION: the reference has neither) -------------
+ * The batch body of local_getis_ord / local_gearys_c for the loaded genes on the active graph.  z, lag, the zero-variance
+ * flags, the permutation rows and the code / float row forms are sc_local_moran's.  stat selects the statistic:
+ *   SC_LOCAL_GETIS  s_i = lag_i; stat_out = the standardised G_i in float64 stored as float32 -- star != 0: Gi*, the graph
+ *                   holds the self edges, G = lag / sqrt((n S1 - W^2) / (n - 1)); star == 0: Gi (Ord & Getis 1995 in z
+ *                   units), mi = -z / (n - 1), vi = (n - z^2) / (n - 1) - mi^2,
+ *                   G = (lag - W mi) / (sqrt(vi) sqrt(((n - 1) S1 - W^2) / (n - 2))); W = sum_e w_e, S1 = sum_e w_e^2 over the
+ *                   row; 0 where the denominator is 0 or not finite.
+ *   SC_LOCAL_GEARY  s_i = stat_out = C_i = sum_e fl(w_e fl(d d)), d = fl(z_i - z_col(e)), float32 in edge order.
+ * Per cell and gene count_ge_out = #{p : s_i(z[perm_p]) >= s_i(z)} and count_le_out = #{p : s_i(z[perm_p]) <= s_i(z)}
+ * (signed, float32, the observed value's own products and sums in the same order: a tie is a tie); n_perm <= 65535.
+ * Outputs are row-major [n_cells][n_genes]; the count outputs are optional. */
+#define SC_LOCAL_GETIS 1
+#define SC_LOCAL_GEARY 2
+int sc_local_stat(sc_ctx *ctx, int32_t stat, int32_t star, int64_t n_perm, int64_t perm_row0, float *z_out, float *lag_out,
+                  float *stat_out, int32_t *count_ge_out, int32_t *count_le_out, uint8_t *zero_var_out);
+/* The same batch with its permutations drawn here, as one pipeline behind the numpy-exact generator: equal in every
+ * output and in the state6 it leaves to sc_perm_generate + sc_local_stat (see sc_local_moran_seeded). */
+int sc_local_stat_seeded(sc_ctx *ctx, int32_t stat, int32_t star, uint64_t *state6, int64_t n_perm, float *z_out,
+                         float *lag_out, float *stat_out, int32_t *count_ge_out, int32_t *count_le_out, uint8_t *zero_var_out);
+/* Per-cell finalisation of the last sc_local_stat, as sc_local_moran_hist / sc_local_moran_classify with the permutation
+ * level m = min(ge, le) in the place of the count: hist[g][m], p = p_tab[g][m], p_adj = padj_tab[g][m].  class int8 --
+ * Getis-Ord: 1 hot (G > 0), 2 cold (G < 0); Geary, against E_i = 2n / (n - 1) sum_{e : col(e) != i} w_e (float64, summed in
+ * the kernel): C < E 1 high-high (z > 0, lag > 0), 2 low-low (z < 0, lag < 0), 3 other positive; C > E 4 negative.  0 where
+ * p_adj >= alpha, force_ns[g], or G == 0 / C == E.  A result of sc_local_moran does not satisfy these two calls, nor one
+ * of sc_local_stat sc_local_moran_hist / _classify: SC_ERR_STATE. */
+int sc_local_stat_hist(sc_ctx *ctx, int64_t *hist_out);
+int sc_local_stat_classify(sc_ctx *ctx, const float *p_tab, const float *padj_tab, const uint8_t *force_ns, float alpha,
+                           float *p_out, float *padj_out, int8_t *class_out);
+
 /* ---- N2: Local Lee's L -----------------------------------------------------------------------
  * Replaces the per-pair body of lees_l_local (AC:1373-1413): population-std z-scores of the two
  * loaded genes, lag = W z_y, L_local = z_x * lag, and (n_perm > 0) the per-cell count

@@ -27,6 +27,7 @@ K_THRESH_SCORE, K_THRESH_SORT, K_THRESH_KS, K_GMM_EM, K_GMM_POST = 12, 13, 14, 1
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
 
 # every symbol include/spatialcore_hip.h declares: (name, argtypes); restype is always int
+LOCAL_STATS = {"getis": 1, "geary": 2}   # SC_LOCAL_GETIS / SC_LOCAL_GEARY
 _P = c_void_p
 SYMBOLS = {
     "sc_version": [],
@@ -78,6 +79,10 @@ SYMBOLS = {
     "sc_local_moran_seeded": [_P, _P, c_int64, _P, _P, _P, _P, _P],
     "sc_local_moran_hist": [_P, _P],
     "sc_local_moran_classify": [_P, _P, _P, _P, c_float, _P, _P, _P],
+    "sc_local_stat": [_P, c_int32, c_int32, c_int64, c_int64, _P, _P, _P, _P, _P, _P],
+    "sc_local_stat_seeded": [_P, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P, _P, _P],
+    "sc_local_stat_hist": [_P, _P],
+    "sc_local_stat_classify": [_P, _P, _P, _P, c_float, _P, _P, _P],
     "sc_lee_local": [_P, c_int32, c_int32, c_int64, c_int64, _P, _P, _P, _P],
     "sc_lee_local_seeded": [_P, _P, c_int32, c_int32, c_int64, c_int64, _P, _P, _P, _P, _P, _P],
     "sc_nearest_2d": [_P, _P, c_int64, _P, c_int64, _P, _P],
@@ -574,6 +579,54 @@ class Context:
         f = _c(np.asarray(force_ns).astype(np.uint8), np.uint8)
         _check(self._lib.sc_local_moran_classify(self._h, _ptr(pt), _ptr(at), _ptr(f), c_float(float(np.float32(alpha))),
                                                  _ptr(p), _ptr(padj), _ptr(q)))
+        return p, padj, q
+
+    # ---- Getis-Ord Gi / Gi* and local Geary's C (extension) ------------------
+    def _local_stat_call(self, stat: str, n_cells: int, n_perm: int, fetch_counts: bool, call):
+        G = self._n_genes
+        z = np.empty((n_cells, G), dtype=np.float32)
+        lag = np.empty((n_cells, G), dtype=np.float32)
+        val = np.empty((n_cells, G), dtype=np.float32)
+        with_counts = n_perm > 0 and fetch_counts
+        ge = np.zeros((n_cells, G), dtype=np.int32) if with_counts else None
+        le = np.zeros((n_cells, G), dtype=np.int32) if with_counts else None
+        zero = np.zeros(G, dtype=np.uint8)
+        _check(call(LOCAL_STATS[stat], _ptr(z), _ptr(lag), _ptr(val), _ptr(ge), _ptr(le), _ptr(zero)))
+        return {"z": z, "lag": lag, "stat": val, "ge": ge, "le": le, "zero_var": zero.astype(bool)}
+
+    def local_stat(self, stat: str, n_cells: int, n_perm: int, perm_row0: int = 0, star: bool = False,
+                   fetch_counts: bool = True):
+        """z, lag, the statistic ("getis": G, Gi* with ``star`` on a graph with self edges; "geary": C) and the two-tail
+        counts ge / le of rows [perm_row0, perm_row0 + n_perm) of the active permutation table."""
+        return self._local_stat_call(stat, n_cells, n_perm, fetch_counts, lambda code, *out: self._lib.sc_local_stat(
+            self._h, code, int(bool(star)), int(n_perm), int(perm_row0), *out))
+
+    def local_stat_seeded(self, stat: str, words: np.ndarray, n_cells: int, n_perm: int, star: bool = False,
+                          fetch_counts: bool = True):
+        """local_stat with its n_perm permutations drawn from `words` (advanced in place) inside the call."""
+        r = self._local_stat_call(stat, n_cells, n_perm, fetch_counts, lambda code, *out: self._lib.sc_local_stat_seeded(
+            self._h, code, int(bool(star)), _ptr(words), int(n_perm), *out))
+        self.permgen_note()
+        return r
+
+    def local_stat_hist(self, n_perm: int) -> np.ndarray:
+        """hist[g][m] = cells of gene g whose permutation level min(ge, le) is m (of the last local_stat call)."""
+        hist = np.zeros((self._n_genes, n_perm + 1), dtype=np.int64)
+        _check(self._lib.sc_local_stat_hist(self._h, _ptr(hist)))
+        return hist
+
+    def local_stat_classify(self, n_cells: int, p_tab, padj_tab, force_ns, alpha):
+        """Per-cell p, adjusted p (table lookups by min(ge, le)) and the classes of the last local_stat."""
+        G = self._n_genes
+        with_p = p_tab is not None
+        p = np.empty((n_cells, G), dtype=np.float32) if with_p else None
+        padj = np.empty((n_cells, G), dtype=np.float32) if with_p else None
+        q = np.empty((n_cells, G), dtype=np.int8)
+        pt = _c(p_tab, np.float32) if with_p else None
+        at = _c(padj_tab, np.float32) if with_p else None
+        f = _c(np.asarray(force_ns).astype(np.uint8), np.uint8)
+        _check(self._lib.sc_local_stat_classify(self._h, _ptr(pt), _ptr(at), _ptr(f), c_float(float(np.float32(alpha))),
+                                                _ptr(p), _ptr(padj), _ptr(q)))
         return p, padj, q
 
     def lee_local(self, n_cells: int, gene_x: int, gene_y: int, n_perm: int = 0, perm_row0: int = 0):

@@ -221,6 +221,8 @@ struct sc_ctx {
     DBuf lee_U, lee_Zc, lee_Uc, lee_part, lee_obs, lee_cnt, lee_rowmap, lee_lperm;  // batched Lee (sc_lee.hip)
     bool lm_valid = false;   // z / lag / counts of the last sc_local_moran are still resident
     int64_t lm_perms = 0;
+    int lm_stat = 0;         // ... and belong to this statistic: 0 local Moran, SC_LOCAL_GETIS / SC_LOCAL_GEARY (sc_local_stats.hip)
+    bool lm_star = false;    // ... Getis-Ord: Gi* (the graph holds the self edges)
     DBuf lm_out;             // local Moran: row-major staging of one output array for the helper thread's device-to-host copies
     DBuf lm_ys;              // local Moran: the permuted z rows (or uint8 code rows) of a batch of permutations, in the graph's processing order
     DBuf lm_tab;             // local Moran, code rows: z and w z per (gene, value)

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "sc_ctx.h"
+#include "sc_local.h"
 #include "sc_pairwise.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(256) void k_lm_observed(const long long *__restrict
 // spatially sorted order (Ys[r] = Z[perm[order[r]]]); phase B is then a LOCAL sparse product: the neighbours of a cell
 // sit at nearby positions, their rows are served by L1 / L2.  The edges of a row keep their ascending-column order,
 // so every sum is the reference's row-sequential float32 sum, bit for bit.
-#define LM_PERM_BATCH 8
+// (LM_PERM_BATCH permutations per launch: sc_local.h)
 
 // Ys[p][tile][r][16] = Z32[tile][perm_p[order[r]]][16]      thread = (r, q), grid.y = tile, grid.z = permutation of the batch
 __global__ __launch_bounds__(256) void k_lm_gather_sorted(const float *__restrict__ Z32, const int32_t *__restrict__ order,
@@ -330,10 +331,7 @@ __global__ __launch_bounds__(256) void k_lm_count_sorted(const long long *__rest
 // looked up in LDS when it is used.  table[gene][v] is k_lm_standardize's own expression at x = v, so every product
 // and every sum is the float path's, bit for bit.  With all weights equal (a row-normalised kNN graph) a second table
 // holds w * z, the product the float path rounds before it adds.
-#define LM_CODES 32          // values 0 .. 31
-#define LM_TAB_STRIDE 36     // floats per table row: (q, value) pairs of one load land in different LDS banks for small values
-#define LM_U8_QUAD 4         // permutations in flight per thread
-#define LM_U8_BATCH_MAX 32   // permutations per launch (the counts are read and written once per launch)
+// (LM_CODES values, LM_TAB_STRIDE floats per table row, quads of LM_U8_QUAD and launches of LM_U8_BATCH_MAX permutations: sc_local.h)
 
 // table rows in the order the kernel's threads use them: row = 8 b + q holds the gene of byte b of lane q's 16 bytes
 // of a narrow row (k_pack_narrow<8>: tile 8 grp + b / 2, slot 2 q + b % 2);  tab[0] = z, tab[1] = w z
@@ -485,22 +483,8 @@ static int lm_codes_ok(sc_ctx *c, bool *ok)
     return SC_OK;
 }
 
-// One local Moran job: the operands of the per-cell permutation counts (sc_local_moran, sc_local_moran_seeded)
-struct LmJob {
-    int64_t n = 0, G = 0, T = 0;
-    size_t tile_f = 0;
-    float *mean32 = nullptr, *sd32 = nullptr, *Z32 = nullptr, *I32 = nullptr, *Lag32 = nullptr;
-    int32_t *cnt = nullptr;
-    unsigned char *zero = nullptr;
-    dim3 gc;
-    int mode = 2;        // 1: uint8 code rows, 2: float rows
-    int groups = 0;      // code rows: 128-gene groups
-    int64_t batch = 0;   // permutations per launch
-    bool uni = false;
-};
-
 // statistics in numpy's order, z, observed lag and I; then the form of the permutation counts and its buffers
-static int lm_prepare(sc_ctx *c, int64_t n_perm, LmJob &j)
+int lm_prepare(sc_ctx *c, int64_t n_perm, LmJob &j)
 {
     const int64_t n = c->e_n, G = c->e_genes, T = c->e_tiles;
     c->lm_valid = false;
@@ -594,41 +578,46 @@ static int lm_prepare(sc_ctx *c, int64_t n_perm, LmJob &j)
     return SC_OK;
 }
 
+// phase A of permutations [row, row + nb) of the forward table: the permuted rows of the batch, in the job's form
+void lm_gather(sc_ctx *c, const LmJob &j, int64_t row, int nb)
+{
+    const int64_t n = j.n;
+    if (j.mode == 1)
+        hipLaunchKernelGGL(k_lm_gather_u8, dim3((unsigned)ceil_div64(n * 8, 256), (unsigned)j.groups, (unsigned)nb), dim3(256), 0,
+                           c->stream, c->X32.as<uint4>(), c->g_order.as<int32_t>(), c->perm.as<int32_t>() + row * c->p_stride,
+                           c->p_stride, n, j.groups, c->lm_ys.as<uint4>());
+    else
+        hipLaunchKernelGGL(k_lm_gather_sorted, dim3(j.gc.x, (unsigned)j.T, (unsigned)nb), dim3(256), 0, c->stream, j.Z32,
+                           c->g_order.as<int32_t>(), c->perm.as<int32_t>() + row * c->p_stride, c->p_stride, n, j.T,
+                           c->lm_ys.as<float>());
+}
+
 // counts of permutations [p0, p1) of the job (rows row0 + p of the forward table); p0 == 0 starts the counts
 static int lm_count(sc_ctx *c, const LmJob &j, int64_t row0, int64_t p0, int64_t p1)
 {
     const int64_t n = j.n, T = j.T;
     if (p1 <= p0) return SC_OK;
     KernelTimerScope ts(c, SC_K_LEE_PERM);
-    if (j.mode == 1) {
-        const dim3 g8((unsigned)ceil_div64(n * 8, 256), (unsigned)j.groups);
-        auto count_u8 = j.uni ? k_lm_count_u8<true> : k_lm_count_u8<false>;
-        for (int64_t p = p0; p < p1; p += j.batch) {
-            const int nb = (int)(p1 - p < j.batch ? p1 - p : j.batch);
-            hipLaunchKernelGGL(k_lm_gather_u8, dim3(g8.x, g8.y, (unsigned)nb), dim3(256), 0, c->stream, c->X32.as<uint4>(),
-                               c->g_order.as<int32_t>(), c->perm.as<int32_t>() + (row0 + p) * c->p_stride, c->p_stride,
-                               n, j.groups, c->lm_ys.as<uint4>());
+    const dim3 g8((unsigned)ceil_div64(n * 8, 256), (unsigned)j.groups);
+    auto count_u8 = j.uni ? k_lm_count_u8<true> : k_lm_count_u8<false>;
+    for (int64_t p = p0; p < p1; p += j.batch) {
+        const int nb = (int)(p1 - p < j.batch ? p1 - p : j.batch);
+        lm_gather(c, j, row0 + p, nb);
+        if (j.mode == 1)
             hipLaunchKernelGGL(count_u8, g8, dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
                                c->g_indices_r.as<int32_t>(), c->g_w32.as<float>(), c->g_order.as<int32_t>(),
                                c->lm_ys.as<uint4>(), j.I32, c->lm_tab.as<float>(), nb, T, j.groups, j.cnt, n, p == 0 ? 1 : 0);
-        }
-    } else {
-        for (int64_t p = p0; p < p1; p += j.batch) {
-            const int nb = (int)(p1 - p < j.batch ? p1 - p : j.batch);
-            hipLaunchKernelGGL(k_lm_gather_sorted, dim3(j.gc.x, (unsigned)T, (unsigned)nb), dim3(256), 0, c->stream, j.Z32,
-                               c->g_order.as<int32_t>(), c->perm.as<int32_t>() + (row0 + p) * c->p_stride, c->p_stride,
-                               n, T, c->lm_ys.as<float>());
+        else
             hipLaunchKernelGGL(k_lm_count_sorted, j.gc, dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
                                c->g_indices_r.as<int32_t>(), c->g_w32.as<float>(), c->g_order.as<int32_t>(),
                                c->lm_ys.as<float>(), j.I32, nb, T, j.cnt, n, p == 0 ? 1 : 0);
-        }
     }
     SC_HIP(hipGetLastError());
     return SC_OK;
 }
 
 // z / lag / I of the job, each un-tiled into the row-major (cells x genes) staging buffer and copied out on stream s
-static int lm_copy_arrays(const LmJob &j, float *stage, hipStream_t s, bool sync_each, float *z_out, float *lag_out, float *I_out)
+int lm_copy_arrays(const LmJob &j, float *stage, hipStream_t s, bool sync_each, float *z_out, float *lag_out, float *I_out)
 {
     const unsigned gu = (unsigned)ceil_div64(j.n * j.G, 256);
     const struct { const float *src; float *dst; } outs[3] = {{j.Z32, z_out}, {j.Lag32, lag_out}, {j.I32, I_out}};
@@ -660,6 +649,7 @@ static int lm_finish(sc_ctx *c, const LmJob &j, int64_t n_perm, float *z_out, fl
     SC_HIP(hipGetLastError());
     SC_HIP(hipStreamSynchronize(c->stream));
     c->lm_valid = true;  // z / lag / counts stay resident for sc_local_moran_hist / sc_local_moran_classify
+    c->lm_stat = LM_STAT_MORAN;
     c->lm_perms = n_perm;
     return SC_OK;
 }
@@ -691,20 +681,15 @@ struct JoiningThread {
     ~JoiningThread() { if (t.joinable()) t.join(); }
 };
 
-// The same with the permutations drawn here: n_perm numpy-exact permutations of the cells from state6 (as
-// sc_perm_generate would draw them; state6 is advanced the same way, the table stays resident), generated chunk
-// by chunk while the per-cell counts of the finished chunks are taken -- the generator's chain is the longest part of
-// a local Moran call, and the counts hide behind it.  Same outputs as sc_perm_generate + sc_local_moran.
-extern "C" int sc_local_moran_seeded(sc_ctx *c, uint64_t *state6, int64_t n_perm, float *z_out, float *lag_out,
-                                     float *I_out, int32_t *count_out, uint8_t *zero_var_out)
+// A job as one pipeline behind the generator (sc_local.h): n_perm numpy-exact permutations of the cells from state6 (as
+// sc_perm_generate would draw them; state6 is advanced the same way, the table stays resident), generated chunk by chunk
+// while the per-cell counts of the finished chunks are taken -- the generator's chain is the longest part of a call, and
+// the counts hide behind it.
+int lm_seeded_pipeline(sc_ctx *c, const char *who, uint64_t *state6, int64_t n_perm, LmJob &j,
+                       const std::function<int(const LmJob &)> &observed,
+                       const std::function<int(const LmJob &, int64_t, int64_t)> &count, float *z_out, float *lag_out,
+                       float *I_out, bool *arrays_done)
 {
-    SC_REQUIRE(c && state6 && z_out && lag_out && I_out, SC_ERR_INVALID, "sc_local_moran_seeded: null pointer");
-    SC_REQUIRE(n_perm >= 1 && n_perm <= (1 << 24), SC_ERR_INVALID, "sc_local_moran_seeded: n_perm=%lld out of range", (long long)n_perm);
-    SC_HIP(hipSetDevice(c->device));
-    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_local_moran_seeded: no expression loaded");
-    SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_local_moran_seeded: graph missing or size mismatch");
-    c->lm_valid = false;
-    LmJob j;
     // r04: z, lag and I are final once the preparation has run -- three (cells x genes) float arrays, 1.2 GB at 10^6 cells x
     // 100 genes, that r03 copied to the caller's (pageable) arrays AFTER the last count, 0.1 s of a 0.5-s call.  A helper
     // thread un-tiles and copies them out on a stream of its own while the generator and the counts run (neither uses
@@ -712,8 +697,10 @@ extern "C" int sc_local_moran_seeded(sc_ctx *c, uint64_t *state6, int64_t n_perm
     int copier_rc = SC_OK;
     std::optional<JoiningThread> copier;   // (declared after what its thread writes; reset() joins)
     bool copier_started = false;
+    *arrays_done = false;
     auto prepare = [&]() -> int {
         SC_TRY(lm_prepare(c, n_perm, j));
+        if (observed) SC_TRY(observed(j));
         if (copier_started) return SC_OK;
         if (!c->stream_out) SC_HIP(hipStreamCreateWithFlags(&c->stream_out, hipStreamNonBlocking));
         SC_TRY(c->lm_out.ensure(sizeof(float) * (size_t)j.n * (size_t)j.G, &c->mem));
@@ -735,19 +722,38 @@ extern "C" int sc_local_moran_seeded(sc_ctx *c, uint64_t *state6, int64_t n_perm
         }
         return SC_OK;
     };
-    auto count = [&](int64_t p0, int64_t p1) -> int { return lm_count(c, j, 0, p0, p1); };
+    auto score = [&](int64_t p0, int64_t p1) -> int { return count(j, p0, p1); };
     // a job that fails its verification is rerun with the sequential scan: the counts restart at permutation 0, and the
     // copier is joined first (the second preparation rewrites what it reads -- with the same values)
     const int rc = permgen_rerun_on_failure(
-        c, [&]() { return sc_perm_pipeline(c, state6, c->e_n, n_perm, 0, 2, prepare, count); },
+        c, [&]() { return sc_perm_pipeline(c, state6, c->e_n, n_perm, 0, 2, prepare, score); },
         [&]() { copier.reset(); return SC_OK; });
     copier.reset();
     SC_TRY(rc);
     if (copier_started && copier_rc != SC_OK) {
-        sc_set_error("sc_local_moran_seeded: the copy of z / lag / I to the host failed");
+        sc_set_error("%s: the copy of z / lag / the statistic to the host failed", who);
         return copier_rc;
     }
-    return lm_finish(c, j, n_perm, z_out, lag_out, I_out, count_out, zero_var_out, copier_started);
+    *arrays_done = copier_started;
+    return SC_OK;
+}
+
+// sc_local_moran with the permutations drawn here, as one pipeline.  Same outputs as sc_perm_generate + sc_local_moran.
+extern "C" int sc_local_moran_seeded(sc_ctx *c, uint64_t *state6, int64_t n_perm, float *z_out, float *lag_out,
+                                     float *I_out, int32_t *count_out, uint8_t *zero_var_out)
+{
+    SC_REQUIRE(c && state6 && z_out && lag_out && I_out, SC_ERR_INVALID, "sc_local_moran_seeded: null pointer");
+    SC_REQUIRE(n_perm >= 1 && n_perm <= (1 << 24), SC_ERR_INVALID, "sc_local_moran_seeded: n_perm=%lld out of range", (long long)n_perm);
+    SC_HIP(hipSetDevice(c->device));
+    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_local_moran_seeded: no expression loaded");
+    SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_local_moran_seeded: graph missing or size mismatch");
+    c->lm_valid = false;
+    LmJob j;
+    bool arrays_done = false;
+    SC_TRY(lm_seeded_pipeline(c, "sc_local_moran_seeded", state6, n_perm, j, nullptr,
+                              [c](const LmJob &job, int64_t p0, int64_t p1) { return lm_count(c, job, 0, p0, p1); }, z_out,
+                              lag_out, I_out, &arrays_done));
+    return lm_finish(c, j, n_perm, z_out, lag_out, I_out, count_out, zero_var_out, arrays_done);
 }
 
 // hist[gene][c] = cells of the gene with permutation count c (LDS-private per workgroup while 16 genes' worth fits)
@@ -778,11 +784,8 @@ __global__ __launch_bounds__(256) void k_lm_hist(const int32_t *__restrict__ cnt
     }
 }
 
-extern "C" int sc_local_moran_hist(sc_ctx *c, int64_t *hist_out)
+int lm_hist_run(sc_ctx *c, int64_t *hist_out)
 {
-    SC_REQUIRE(c && hist_out, SC_ERR_INVALID, "sc_local_moran_hist: null pointer");
-    SC_REQUIRE(c->lm_valid && c->lm_perms > 0, SC_ERR_STATE, "sc_local_moran_hist: no sc_local_moran result with permutations");
-    SC_HIP(hipSetDevice(c->device));
     const int64_t n = c->e_n, G = c->e_genes, T = c->e_tiles;
     const int P1 = (int)c->lm_perms + 1;
     const size_t tile_f = (size_t)T * n * SC_TILE;
@@ -795,6 +798,15 @@ extern "C" int sc_local_moran_hist(sc_ctx *c, int64_t *hist_out)
     SC_HIP(hipMemcpyAsync(hist_out, c->lee_b.p, sizeof(int64_t) * (size_t)G * (size_t)P1, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     return SC_OK;
+}
+
+extern "C" int sc_local_moran_hist(sc_ctx *c, int64_t *hist_out)
+{
+    SC_REQUIRE(c && hist_out, SC_ERR_INVALID, "sc_local_moran_hist: null pointer");
+    SC_REQUIRE(c->lm_valid && c->lm_stat == LM_STAT_MORAN && c->lm_perms > 0, SC_ERR_STATE,
+               "sc_local_moran_hist: no sc_local_moran result with permutations");
+    SC_HIP(hipSetDevice(c->device));
+    return lm_hist_run(c, hist_out);
 }
 
 // p = p_tab[g][count], p_adj = padj_tab[g][count], LISA quadrant (AC:219-265): 1 HH, 2 LL, 3 HL, 4 LH from the signs of
@@ -828,19 +840,15 @@ __global__ __launch_bounds__(256) void k_lm_classify(const float *__restrict__ Z
     q_out[t] = q;
 }
 
-extern "C" int sc_local_moran_classify(sc_ctx *c, const float *p_tab, const float *padj_tab, const uint8_t *force_ns,
-                                       float alpha, float *p_out, float *padj_out, int8_t *quadrant_out)
+int lm_classify_run(sc_ctx *c, const float *p_tab, const float *padj_tab, const uint8_t *force_ns, float *p_out,
+                    float *padj_out, int8_t *class_out,
+                    const std::function<void(int, const float *, const float *, const unsigned char *, float *, float *,
+                                             signed char *)> &classify)
 {
-    SC_REQUIRE(c && force_ns && quadrant_out, SC_ERR_INVALID, "sc_local_moran_classify: null pointer");
-    SC_REQUIRE(c->lm_valid, SC_ERR_STATE, "sc_local_moran_classify: no sc_local_moran result");
-    SC_HIP(hipSetDevice(c->device));
-    const int64_t n = c->e_n, G = c->e_genes, T = c->e_tiles;
+    const int64_t n = c->e_n, G = c->e_genes;
     const int P1 = c->lm_perms > 0 ? (int)c->lm_perms + 1 : 0;
-    if (P1 > 0) SC_REQUIRE(p_tab && padj_tab && p_out && padj_out, SC_ERR_INVALID, "sc_local_moran_classify: tables and outputs required with permutations");
-    const size_t tile_f = (size_t)T * n * SC_TILE, cells = (size_t)n * (size_t)G;
-    const float *Z32 = c->Z.as<float>(), *Lag32 = c->Lag.as<float>();
-    const int32_t *cnt = reinterpret_cast<const int32_t *>(Lag32 + tile_f);
-    // device staging: [p | p_adj | quadrant] row-major, tables, flags
+    const size_t cells = (size_t)n * (size_t)G;
+    // device staging: [p | p_adj | class] row-major, tables, flags
     SC_TRY(c->lee_a.ensure(sizeof(float) * 2 * cells + cells + 64, &c->mem));
     SC_TRY(c->lee_b.ensure(sizeof(float) * 2 * (size_t)G * (size_t)(P1 > 0 ? P1 : 1) + (size_t)G + 64, &c->mem));
     float *d_p = c->lee_a.as<float>(), *d_pa = d_p + cells;
@@ -852,14 +860,32 @@ extern "C" int sc_local_moran_classify(sc_ctx *c, const float *p_tab, const floa
         SC_HIP(hipMemcpyAsync(d_at, padj_tab, sizeof(float) * (size_t)G * P1, hipMemcpyHostToDevice, c->stream));
     }
     SC_HIP(hipMemcpyAsync(d_f, force_ns, (size_t)G, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_lm_classify, dim3((unsigned)ceil_div64(n * G, 256)), dim3(256), 0, c->stream, Z32, Lag32, cnt, n,
-                       G, P1, d_pt, d_at, d_f, alpha, d_p, d_pa, d_q);
+    classify(P1, d_pt, d_at, d_f, d_p, d_pa, d_q);
     SC_HIP(hipGetLastError());
     if (P1 > 0) {
         SC_HIP(hipMemcpyAsync(p_out, d_p, sizeof(float) * cells, hipMemcpyDeviceToHost, c->stream));
         SC_HIP(hipMemcpyAsync(padj_out, d_pa, sizeof(float) * cells, hipMemcpyDeviceToHost, c->stream));
     }
-    SC_HIP(hipMemcpyAsync(quadrant_out, d_q, cells, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(class_out, d_q, cells, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     return SC_OK;
+}
+
+extern "C" int sc_local_moran_classify(sc_ctx *c, const float *p_tab, const float *padj_tab, const uint8_t *force_ns,
+                                       float alpha, float *p_out, float *padj_out, int8_t *quadrant_out)
+{
+    SC_REQUIRE(c && force_ns && quadrant_out, SC_ERR_INVALID, "sc_local_moran_classify: null pointer");
+    SC_REQUIRE(c->lm_valid && c->lm_stat == LM_STAT_MORAN, SC_ERR_STATE, "sc_local_moran_classify: no sc_local_moran result");
+    SC_HIP(hipSetDevice(c->device));
+    const int64_t n = c->e_n, G = c->e_genes, T = c->e_tiles;
+    if (c->lm_perms > 0) SC_REQUIRE(p_tab && padj_tab && p_out && padj_out, SC_ERR_INVALID, "sc_local_moran_classify: tables and outputs required with permutations");
+    const size_t tile_f = (size_t)T * n * SC_TILE;
+    const float *Z32 = c->Z.as<float>(), *Lag32 = c->Lag.as<float>();
+    const int32_t *cnt = reinterpret_cast<const int32_t *>(Lag32 + tile_f);
+    return lm_classify_run(c, p_tab, padj_tab, force_ns, p_out, padj_out, quadrant_out,
+                           [=](int P1, const float *d_pt, const float *d_at, const unsigned char *d_f, float *d_p, float *d_pa,
+                               signed char *d_q) {
+                               hipLaunchKernelGGL(k_lm_classify, dim3((unsigned)ceil_div64(n * G, 256)), dim3(256), 0, c->stream,
+                                                  Z32, Lag32, cnt, n, G, P1, d_pt, d_at, d_f, alpha, d_p, d_pa, d_q);
+                           });
 }

@@ -9,6 +9,7 @@ from spatialcore_amd.spatial.autocorrelation import (
     morans_i,
 )
 from spatialcore_amd.spatial.distance import calculate_domain_distances, get_distance_matrix
+from spatialcore_amd.spatial.local_stats import local_gearys_c, local_getis_ord
 from spatialcore_amd.spatial.domains import get_domain_summary, make_spatial_domains
 from spatialcore_amd.spatial.markers import rank_genes_groups
 from spatialcore_amd.spatial.neighborhoods import (
@@ -21,6 +22,8 @@ from spatialcore_amd.spatial.neighborhoods import (
 __all__ = [
     "morans_i",
     "local_morans_i",
+    "local_getis_ord",  # extension: not in the reference
+    "local_gearys_c",  # extension: not in the reference
     "lees_l",
     "lees_l_local",
     "build_spatial_weights",
