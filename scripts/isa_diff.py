@@ -1,12 +1,15 @@
 """Compare the gfx950 device code of two source trees kernel by kernel (no GPU needed).
 
-    python scripts/isa_diff.py OLD_CSRC [NEW_CSRC] [--keep DIR]
+    python scripts/isa_diff.py OLD_CSRC [NEW_CSRC] [--keep DIR] [--rename OLD_SYMBOL=NEW_SYMBOL ...]
 
 Every *.hip of both directories (NEW_CSRC defaults to spatialcore_amd/csrc; OLD_CSRC is e.g. the csrc/ of a
 `git worktree add` of the parent commit) is compiled to device assembly with the Makefile's code-generation flags,
 the assembly is cut per kernel symbol -- code, .amdhsa_kernel block and resource summary -- and the kernels are
 matched BY NAME across all units, so a kernel that moved to another file compares equal.  Reported: kernels that
 are missing, new or defined twice, and for every kernel whose text differs its resources, old -> new.
+--rename (repeatable) compares kernel OLD_SYMBOL of the old tree with kernel NEW_SYMBOL of the new one, the symbols as
+this tool prints them, with the symbol's own name replaced in both texts; between such a pair the section directive that
+differs only because a plain function became a template instantiation (.text vs its comdat .section) does not count.
 Exit status 0 only if both trees hold the same kernels with identical text.
 """
 import argparse
@@ -23,6 +26,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
          "-Wno-unused-command-line-argument"]
 BEGIN = re.compile(r"; -- Begin function (\S+)")
 LOCAL = re.compile(r"\.(LBB|Lfunc_end|Lfunc_begin|Ltmp|LJTI)\d+")   # labels numbered by position in the unit
+SECTION = re.compile(r'(?m)^\t(\.text|\.section\t\.text\.\S+,"axG",@progbits,\S+,comdat)$')
 FIELDS = (".amdhsa_next_free_vgpr", ".amdhsa_accum_offset", ".amdhsa_next_free_sgpr", ".amdhsa_group_segment_fixed_size",
           ".amdhsa_private_segment_fixed_size", "; Occupancy:", "; codeLenInByte")
 
@@ -68,10 +72,26 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new", nargs="?", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "spatialcore_amd", "csrc"))
     ap.add_argument("--keep", help="keep the assembly under this directory")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD_SYMBOL=NEW_SYMBOL",
+                    help="compare this kernel of the old tree with that kernel of the new one")
     a = ap.parse_args()
     tmp = a.keep or tempfile.mkdtemp(prefix="isa_diff_")
     old, new = kernels(a.old, os.path.join(tmp, "old")), kernels(a.new, os.path.join(tmp, "new"))
     bad = 0
+    renamed = [r.split("=", 1) for r in a.rename]
+    for o_name, n_name in renamed:
+        o, n = old.get(o_name, []), new.get(n_name, [])
+        if len(o) != 1 or len(n) != 1:
+            print("COUNT   %s -> %s: %d definition(s) before, %d after" % (o_name, n_name, len(o), len(n)))
+            bad += 1
+            continue
+        o_text, n_text = (SECTION.sub("\t.text", t.replace(name, "KERNEL")) for t, name in ((o[0], o_name), (n[0], n_name)))
+        if o_text != n_text:
+            print("DIFFERS %s -> %s\n    old: %s\n    new: %s" % (o_name, n_name, resources(o[0]), resources(n[0])))
+            bad += 1
+    for o_name, n_name in renamed:
+        old.pop(o_name, None)
+        new.pop(n_name, None)
     for name in sorted(set(old) | set(new)):
         o, n = old.get(name, []), new.get(name, [])
         if len(o) != len(n) or len(set(n)) != 1:   # (several equal copies: a header library's kernel in more than one unit)

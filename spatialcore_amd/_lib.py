@@ -535,40 +535,24 @@ class Context:
         _check(self._lib.sc_lee_observed_f32(self._h, _ptr(px), _ptr(py), px.size, _ptr(out), None, None))
         return out
 
-    # ---- N1 / N2 ----------------------------------------------------------------------------
-    def local_moran(self, n_cells: int, n_perm: int, perm_row0: int = 0, fetch_counts: bool = True):
+    # ---- N1 / N2, and Getis-Ord Gi / Gi* and local Geary's C (extension) ------
+    def _local_call(self, n_cells: int, value: str, counts, fetch: bool, call):
+        """One sc_local_* call: z, lag and the statistic (key ``value``), the int32 count arrays named in ``counts`` (null
+        pointers unless ``fetch``) and the zero-variance flags, in the order of the symbol's output arguments."""
         G = self._n_genes
-        z = np.empty((n_cells, G), dtype=np.float32)
-        lag = np.empty((n_cells, G), dtype=np.float32)
-        I = np.empty((n_cells, G), dtype=np.float32)
-        cnt = np.zeros((n_cells, G), dtype=np.int32) if (n_perm > 0 and fetch_counts) else None
+        r = {name: np.empty((n_cells, G), dtype=np.float32) for name in ("z", "lag", value)}
+        r.update({name: np.zeros((n_cells, G), dtype=np.int32) if fetch else None for name in counts})
         zero = np.zeros(G, dtype=np.uint8)
-        _check(self._lib.sc_local_moran(self._h, int(n_perm), int(perm_row0), _ptr(z), _ptr(lag), _ptr(I), _ptr(cnt),
-                                        _ptr(zero)))
-        return {"z": z, "lag": lag, "I": I, "count": cnt, "zero_var": zero.astype(bool)}
+        _check(call(*(_ptr(a) for a in r.values()), _ptr(zero)))
+        r["zero_var"] = zero.astype(bool)
+        return r
 
-    def local_moran_seeded(self, words: np.ndarray, n_cells: int, n_perm: int, fetch_counts: bool = True):
-        """local_moran with its n_perm permutations drawn from `words` (advanced in place) inside the call: generator and
-        per-cell counts run as one pipeline."""
-        G = self._n_genes
-        z = np.empty((n_cells, G), dtype=np.float32)
-        lag = np.empty((n_cells, G), dtype=np.float32)
-        I = np.empty((n_cells, G), dtype=np.float32)
-        cnt = np.zeros((n_cells, G), dtype=np.int32) if fetch_counts else None
-        zero = np.zeros(G, dtype=np.uint8)
-        _check(self._lib.sc_local_moran_seeded(self._h, _ptr(words), int(n_perm), _ptr(z), _ptr(lag), _ptr(I), _ptr(cnt),
-                                               _ptr(zero)))
-        self.permgen_note()
-        return {"z": z, "lag": lag, "I": I, "count": cnt, "zero_var": zero.astype(bool)}
-
-    def local_moran_hist(self, n_perm: int) -> np.ndarray:
-        """hist[g][c] = cells of gene g whose permutation count is c (of the last local_moran call)."""
+    def _local_hist(self, symbol, n_perm: int) -> np.ndarray:
         hist = np.zeros((self._n_genes, n_perm + 1), dtype=np.int64)
-        _check(self._lib.sc_local_moran_hist(self._h, _ptr(hist)))
+        _check(symbol(self._h, _ptr(hist)))
         return hist
 
-    def local_moran_classify(self, n_cells: int, p_tab, padj_tab, force_ns, alpha):
-        """Per-cell p, adjusted p (table lookups by permutation count) and LISA quadrants of the last local_moran."""
+    def _local_classify(self, symbol, n_cells: int, p_tab, padj_tab, force_ns, alpha):
         G = self._n_genes
         with_p = p_tab is not None
         p = np.empty((n_cells, G), dtype=np.float32) if with_p else None
@@ -577,57 +561,51 @@ class Context:
         pt = _c(p_tab, np.float32) if with_p else None
         at = _c(padj_tab, np.float32) if with_p else None
         f = _c(np.asarray(force_ns).astype(np.uint8), np.uint8)
-        _check(self._lib.sc_local_moran_classify(self._h, _ptr(pt), _ptr(at), _ptr(f), c_float(float(np.float32(alpha))),
-                                                 _ptr(p), _ptr(padj), _ptr(q)))
+        _check(symbol(self._h, _ptr(pt), _ptr(at), _ptr(f), c_float(float(np.float32(alpha))), _ptr(p), _ptr(padj), _ptr(q)))
         return p, padj, q
 
-    # ---- Getis-Ord Gi / Gi* and local Geary's C (extension) ------------------
-    def _local_stat_call(self, stat: str, n_cells: int, n_perm: int, fetch_counts: bool, call):
-        G = self._n_genes
-        z = np.empty((n_cells, G), dtype=np.float32)
-        lag = np.empty((n_cells, G), dtype=np.float32)
-        val = np.empty((n_cells, G), dtype=np.float32)
-        with_counts = n_perm > 0 and fetch_counts
-        ge = np.zeros((n_cells, G), dtype=np.int32) if with_counts else None
-        le = np.zeros((n_cells, G), dtype=np.int32) if with_counts else None
-        zero = np.zeros(G, dtype=np.uint8)
-        _check(call(LOCAL_STATS[stat], _ptr(z), _ptr(lag), _ptr(val), _ptr(ge), _ptr(le), _ptr(zero)))
-        return {"z": z, "lag": lag, "stat": val, "ge": ge, "le": le, "zero_var": zero.astype(bool)}
+    def local_moran(self, n_cells: int, n_perm: int, perm_row0: int = 0, fetch_counts: bool = True):
+        return self._local_call(n_cells, "I", ("count",), n_perm > 0 and fetch_counts, lambda *out: self._lib.sc_local_moran(
+            self._h, int(n_perm), int(perm_row0), *out))
+
+    def local_moran_seeded(self, words: np.ndarray, n_cells: int, n_perm: int, fetch_counts: bool = True):
+        """local_moran with its n_perm permutations drawn from `words` (advanced in place) inside the call: generator and
+        per-cell counts run as one pipeline."""
+        r = self._local_call(n_cells, "I", ("count",), fetch_counts, lambda *out: self._lib.sc_local_moran_seeded(
+            self._h, _ptr(words), int(n_perm), *out))
+        self.permgen_note()
+        return r
+
+    def local_moran_hist(self, n_perm: int) -> np.ndarray:
+        """hist[g][c] = cells of gene g whose permutation count is c (of the last local_moran call)."""
+        return self._local_hist(self._lib.sc_local_moran_hist, n_perm)
+
+    def local_moran_classify(self, n_cells: int, p_tab, padj_tab, force_ns, alpha):
+        """Per-cell p, adjusted p (table lookups by permutation count) and LISA quadrants of the last local_moran."""
+        return self._local_classify(self._lib.sc_local_moran_classify, n_cells, p_tab, padj_tab, force_ns, alpha)
 
     def local_stat(self, stat: str, n_cells: int, n_perm: int, perm_row0: int = 0, star: bool = False,
                    fetch_counts: bool = True):
         """z, lag, the statistic ("getis": G, Gi* with ``star`` on a graph with self edges; "geary": C) and the two-tail
         counts ge / le of rows [perm_row0, perm_row0 + n_perm) of the active permutation table."""
-        return self._local_stat_call(stat, n_cells, n_perm, fetch_counts, lambda code, *out: self._lib.sc_local_stat(
-            self._h, code, int(bool(star)), int(n_perm), int(perm_row0), *out))
+        return self._local_call(n_cells, "stat", ("ge", "le"), n_perm > 0 and fetch_counts, lambda *out: self._lib.sc_local_stat(
+            self._h, LOCAL_STATS[stat], int(bool(star)), int(n_perm), int(perm_row0), *out))
 
     def local_stat_seeded(self, stat: str, words: np.ndarray, n_cells: int, n_perm: int, star: bool = False,
                           fetch_counts: bool = True):
         """local_stat with its n_perm permutations drawn from `words` (advanced in place) inside the call."""
-        r = self._local_stat_call(stat, n_cells, n_perm, fetch_counts, lambda code, *out: self._lib.sc_local_stat_seeded(
-            self._h, code, int(bool(star)), _ptr(words), int(n_perm), *out))
+        r = self._local_call(n_cells, "stat", ("ge", "le"), n_perm > 0 and fetch_counts, lambda *out: self._lib.sc_local_stat_seeded(
+            self._h, LOCAL_STATS[stat], int(bool(star)), _ptr(words), int(n_perm), *out))
         self.permgen_note()
         return r
 
     def local_stat_hist(self, n_perm: int) -> np.ndarray:
         """hist[g][m] = cells of gene g whose permutation level min(ge, le) is m (of the last local_stat call)."""
-        hist = np.zeros((self._n_genes, n_perm + 1), dtype=np.int64)
-        _check(self._lib.sc_local_stat_hist(self._h, _ptr(hist)))
-        return hist
+        return self._local_hist(self._lib.sc_local_stat_hist, n_perm)
 
     def local_stat_classify(self, n_cells: int, p_tab, padj_tab, force_ns, alpha):
         """Per-cell p, adjusted p (table lookups by min(ge, le)) and the classes of the last local_stat."""
-        G = self._n_genes
-        with_p = p_tab is not None
-        p = np.empty((n_cells, G), dtype=np.float32) if with_p else None
-        padj = np.empty((n_cells, G), dtype=np.float32) if with_p else None
-        q = np.empty((n_cells, G), dtype=np.int8)
-        pt = _c(p_tab, np.float32) if with_p else None
-        at = _c(padj_tab, np.float32) if with_p else None
-        f = _c(np.asarray(force_ns).astype(np.uint8), np.uint8)
-        _check(self._lib.sc_local_stat_classify(self._h, _ptr(pt), _ptr(at), _ptr(f), c_float(float(np.float32(alpha))),
-                                                _ptr(p), _ptr(padj), _ptr(q)))
-        return p, padj, q
+        return self._local_classify(self._lib.sc_local_stat_classify, n_cells, p_tab, padj_tab, force_ns, alpha)
 
     def lee_local(self, n_cells: int, gene_x: int, gene_y: int, n_perm: int = 0, perm_row0: int = 0):
         zx = np.empty(n_cells, dtype=np.float64)

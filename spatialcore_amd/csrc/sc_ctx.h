@@ -114,7 +114,7 @@ struct sc_ctx {
     hipStream_t stream2 = nullptr;  // fused permutation/Moran pipeline: rejection scan runs ahead here
     hipStream_t stream3 = nullptr;  // ... and the Fisher-Yates swaps of the scanned chunk here
     hipStream_t stream4 = nullptr;  // ... alternating with this one
-    hipStream_t stream_out = nullptr;    // r04: result copies that run beside a pipeline, issued by a helper thread (sc_local_moran_seeded)
+    hipStream_t stream_out = nullptr;    // r04: result copies that run beside a pipeline, issued by a helper thread (sc_local_moran_seeded, sc_local_stat_seeded)
     PermGen pg;       // the numpy-exact permutation generator's state
     int64_t mem = 0;  // bytes allocated through DBuf
     bool timing = true;
@@ -219,13 +219,14 @@ struct sc_ctx {
     DBuf partial, sims, counts, sim_sum, sim_sumsq;
     DBuf lee_a, lee_b, lee_out, lee_pairs;
     DBuf lee_U, lee_Zc, lee_Uc, lee_part, lee_obs, lee_cnt, lee_rowmap, lee_lperm;  // batched Lee (sc_lee.hip)
-    bool lm_valid = false;   // z / lag / counts of the last sc_local_moran are still resident
-    int64_t lm_perms = 0;
-    int lm_stat = 0;         // ... and belong to this statistic: 0 local Moran, SC_LOCAL_GETIS / SC_LOCAL_GEARY (sc_local_stats.hip)
+    // the per-cell (LISA) statistics (sc_local_prepare.hip, sc_local_stats.hip)
+    bool lm_valid = false;   // z / lag / statistic / count words of the last sc_local_moran* or sc_local_stat* are still resident
+    int64_t lm_perms = 0;    // ... with this many permutations
+    int lm_stat = 0;         // ... and belong to this statistic: 0 local Moran, SC_LOCAL_GETIS / SC_LOCAL_GEARY
     bool lm_star = false;    // ... Getis-Ord: Gi* (the graph holds the self edges)
-    DBuf lm_out;             // local Moran: row-major staging of one output array for the helper thread's device-to-host copies
-    DBuf lm_ys;              // local Moran: the permuted z rows (or uint8 code rows) of a batch of permutations, in the graph's processing order
-    DBuf lm_tab;             // local Moran, code rows: z and w z per (gene, value)
+    DBuf lm_out;             // row-major staging of one output array for the helper thread's device-to-host copies (the _seeded calls)
+    DBuf lm_ys;              // the permuted z rows (or uint8 code rows) of a batch of permutations, in the graph's processing order (also sc_lee_local*)
+    DBuf lm_tab;             // code rows: z and w z per (gene, value)
     // first half of the Moran preparation, enqueued ahead of the generator by sc_moran_seeded_begin (sc_moran.hip)
     bool prep_early = false;         // ... is in flight / done for the resident expression and graph
     void *prep_host = nullptr;       // pinned: [weight-sum partials | xsum | flags | xmax]

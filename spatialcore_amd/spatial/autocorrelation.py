@@ -572,6 +572,168 @@ def _padj_tables(hist: np.ndarray, n_cells: int, n_permutations: int, method: st
     return np.clip(a, 0, 1).astype(np.float32)
 
 
+def _local_driver(adata, stat, label, function_name, value_suffix, class_suffix, class_word, log, genes, layer, spatial_key,
+                  n_neighbors, star, n_permutations, fdr_correction, alpha, seed, batch_size, key_added, copy, device,
+                  max_permutations=None, extra_params=None, extra_recorded=None):
+    """The batch driver of the LISA family: ``stat`` is "moran" (``Context.local_moran*``) or "getis" / "geary"
+    (``Context.local_stat*``).  ``max_permutations``: the extensions' bound, checked together with ``batch_size >= 1``
+    (the reference's function checks neither); ``extra_params`` / ``extra_recorded``: what they add to ``uns`` and to the
+    recorded parameters."""
+    start_time = time.time()
+    coords = _require_spatial(adata, spatial_key)
+    _check_counts(n_neighbors, n_permutations)
+    if max_permutations is not None and n_permutations > max_permutations:
+        raise ValueError(f"n_permutations must be <= {max_permutations}, got {n_permutations}")
+    if fdr_correction not in ["bonferroni", "fdr_bh", "none"]:
+        raise ValueError(f"Invalid fdr_correction: '{fdr_correction}'. Must be 'bonferroni', 'fdr_bh', or 'none'.")
+    if max_permutations is not None and batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+    adata = adata.copy() if copy else adata
+    gene_names = _resolve_genes(adata, genes, "This may be slow and memory-intensive.")
+    n_cells, n_genes = adata.n_obs, len(gene_names)
+    gene_indices = np.array([adata.var_names.get_loc(g) for g in gene_names])
+    log.info(f"Computing {label}: {n_cells:,} cells, {n_genes} genes, "
+             f"k={n_neighbors}, permutations={n_permutations}")
+
+    ctx = _lib.default_context(device)
+    _knn_weights_f32(ctx, coords, n_neighbors, include_self=bool(star))
+    X = _expression(adata, layer)
+    if sparse.issparse(X) and n_genes > batch_size:
+        X = X.tocsc()        # one conversion; every batch then ships only its own columns (AC:813-816 does the same)
+
+    moran = stat == "moran"
+    value = "I" if moran else "stat"
+    fields = ("z", "lag", value)
+    words = _lib.rng_state_words(np.random.default_rng(seed))
+    n_batches = (n_genes + batch_size - 1) // batch_size
+    log.info(f"Processing {n_genes} genes in {n_batches} batches")
+    levels = ((np.arange(n_permutations + 1) + 1) / (n_permutations + 1)).astype(np.float32)
+    single = n_batches == 1
+
+    def alloc(dtype):
+        return None if single else np.empty((n_cells, n_genes), dtype=dtype)   # (one batch: its own arrays become the outputs)
+
+    out = {name: alloc(np.float32) for name in fields}
+    p_values = alloc(np.float32) if n_permutations > 0 else None
+    p_adj = alloc(np.float32) if n_permutations > 0 else None
+    classes = alloc(np.int8)
+    zero_var_mask = np.zeros(n_genes, dtype=bool)
+
+    def put(dst, src, b0, b1, inv):
+        if inv is not None:
+            src = src[:, inv]
+        if single:
+            return np.ascontiguousarray(src)
+        dst[:, b0:b1] = src
+        return dst
+
+    def run():   # with permutations: continues the one stream; generator and per-cell counts run as one pipeline
+        if moran:
+            if n_permutations > 0:
+                return ctx.local_moran_seeded(words, n_cells, n_permutations, fetch_counts=False)
+            return ctx.local_moran(n_cells, 0, fetch_counts=False)
+        if n_permutations > 0:
+            return ctx.local_stat_seeded(stat, words, n_cells, n_permutations, star=star, fetch_counts=False)
+        return ctx.local_stat(stat, n_cells, 0, star=star, fetch_counts=False)
+
+    hist_of, classify = ((ctx.local_moran_hist, ctx.local_moran_classify) if moran
+                         else (ctx.local_stat_hist, ctx.local_stat_classify))
+    for batch_idx in range(n_batches):
+        b0, b1 = batch_idx * batch_size, min((batch_idx + 1) * batch_size, n_genes)
+        log.debug(f"Processing batch {batch_idx + 1}/{n_batches}")
+        cols, inv = np.unique(gene_indices[b0:b1], return_inverse=True)   # a gene named twice is loaded once
+        if inv.size == cols.size and np.array_equal(inv, np.arange(cols.size)):
+            inv = None                       # the usual case: distinct genes in ascending column order
+        if sparse.issparse(X) and n_batches > 1:
+            ctx.set_expression(X[:, cols], np.arange(cols.size, dtype=np.int32))
+        else:
+            ctx.set_expression(X, cols.astype(np.int32))
+        r = run()
+        zero = r["zero_var"]
+        # per-cell p, adjusted p and classes on the device: lookup tables per (gene, permutation count or level m) built
+        # here with the reference's expressions (AC:894-896, 912-920); zero-variance genes get p = p_adj = 1, class 0
+        if n_permutations > 0:
+            hist = hist_of(n_permutations)
+            hist[zero] = 0
+            hist[zero, n_permutations] = n_cells
+            p_tab = np.tile(levels, (cols.size, 1))
+            p_tab[zero] = 1.0
+            padj_tab = _padj_tables(hist, n_cells, n_permutations, fdr_correction)
+            padj_tab[zero] = 1.0
+            pb, ab, qb = classify(n_cells, p_tab, padj_tab, zero, alpha)
+            p_values = put(p_values, pb, b0, b1, inv)
+            p_adj = put(p_adj, ab, b0, b1, inv)
+        else:
+            _, _, qb = classify(n_cells, None, None, zero, alpha)
+        classes = put(classes, qb, b0, b1, inv)
+        for name in fields:
+            if zero.any():
+                r[name][:, zero] = 0.0
+            out[name] = put(out[name], r[name], b0, b1, inv)
+        zero_var_mask[b0:b1] = zero if inv is None else zero[inv]
+
+    zero_variance_genes = [gene_names[i] for i in np.where(zero_var_mask)[0]]
+    if zero_var_mask.any():
+        log.warning(f"{int(zero_var_mask.sum())} genes have zero variance and will be skipped: "
+                    f"{zero_variance_genes[:5]}")
+    if n_permutations > 0:
+        log.debug(f"Applied {fdr_correction} correction; {class_word} with significance filtering")
+    else:
+        log.warning("n_permutations=0: Quadrants classified by z/lag signs only, "
+                    "without significance filtering. Consider n_permutations>=99 for p-values.")
+        p_values = p_adj = np.ones((n_cells, n_genes), dtype=np.float32)
+
+    adata.obsm[f"{key_added}_{value_suffix}"] = out[value]
+    adata.obsm[f"{key_added}_z"] = out["z"]
+    adata.obsm[f"{key_added}_lag"] = out["lag"]
+    adata.obsm[f"{key_added}_p"] = p_values
+    adata.obsm[f"{key_added}_p_adj"] = p_adj
+    adata.obsm[f"{key_added}_{class_suffix}"] = classes
+
+    elapsed = time.time() - start_time
+    adata.uns[f"{key_added}_params"] = {
+        "genes": gene_names,
+        "n_neighbors": n_neighbors,
+        "n_permutations": n_permutations,
+        "fdr_correction": fdr_correction,
+        "alpha": alpha,
+        "n_cells": n_cells,
+        "n_genes": n_genes,
+        "seed": seed,
+        "computation_time_seconds": elapsed,
+        "zero_variance_genes": zero_variance_genes,
+        **(extra_params or {}),
+    }
+    n_significant = (classes != 0).sum(axis=0)
+    log.info(f"{label} completed in {elapsed:.1f}s. "
+             f"Significant cells per gene: min={n_significant.min()}, max={n_significant.max()}")
+    update_metadata(
+        adata,
+        function_name=function_name,
+        parameters={
+            "genes": gene_names[:10] if len(gene_names) > 10 else gene_names,
+            "n_genes": n_genes,
+            "n_neighbors": n_neighbors,
+            "n_permutations": n_permutations,
+            "fdr_correction": fdr_correction,
+            "alpha": alpha,
+            "seed": seed,
+            "permgen_form": ctx.permgen_form(n_cells) if n_permutations > 0 else None,
+            **(extra_recorded or {}),
+        },
+        outputs={
+            f"obsm_{value_suffix}": f"{key_added}_{value_suffix}",
+            "obsm_z": f"{key_added}_z",
+            "obsm_lag": f"{key_added}_lag",
+            "obsm_p": f"{key_added}_p",
+            "obsm_p_adj": f"{key_added}_p_adj",
+            f"obsm_{class_suffix}": f"{key_added}_{class_suffix}",
+            "uns_params": f"{key_added}_params",
+        },
+    )
+    return adata
+
+
 def local_morans_i(
     adata,
     genes: Optional[Union[str, List[str]]] = None,
@@ -596,150 +758,9 @@ def local_morans_i(
     ``n_permutations`` permutations from ONE numpy-exact stream (AC:839-879).  The per-cell counts
     are accumulated on the GPU instead of materialising the reference's ``(P, N, B)`` tensor.
     """
-    start_time = time.time()
-    coords = _require_spatial(adata, spatial_key)
-    _check_counts(n_neighbors, n_permutations)
-    if fdr_correction not in ["bonferroni", "fdr_bh", "none"]:
-        raise ValueError(f"Invalid fdr_correction: '{fdr_correction}'. Must be 'bonferroni', 'fdr_bh', or 'none'.")
-    adata = adata.copy() if copy else adata
-    gene_names = _resolve_genes(adata, genes, "This may be slow and memory-intensive.")
-    n_cells, n_genes = adata.n_obs, len(gene_names)
-    gene_indices = np.array([adata.var_names.get_loc(g) for g in gene_names])
-    logger.info(f"Computing Local Moran's I: {n_cells:,} cells, {n_genes} genes, "
-                f"k={n_neighbors}, permutations={n_permutations}")
-
-    ctx = _lib.default_context(device)
-    _knn_weights_f32(ctx, coords, n_neighbors)
-    X = _expression(adata, layer)
-    if sparse.issparse(X) and n_genes > batch_size:
-        X = X.tocsc()        # one conversion; every batch then ships only its own columns (AC:813-816 does the same)
-
-    words = _lib.rng_state_words(np.random.default_rng(seed))
-    n_batches = (n_genes + batch_size - 1) // batch_size
-    logger.info(f"Processing {n_genes} genes in {n_batches} batches")
-    levels = ((np.arange(n_permutations + 1) + 1) / (n_permutations + 1)).astype(np.float32)
-    single = n_batches == 1
-
-    def alloc(dtype, fill=None):
-        if single:
-            return None                      # the batch's own arrays become the outputs
-        a = np.empty((n_cells, n_genes), dtype=dtype)
-        if fill is not None:
-            a.fill(fill)
-        return a
-
-    local_I, z_values, lag_values = alloc(np.float32), alloc(np.float32), alloc(np.float32)
-    p_values = alloc(np.float32) if n_permutations > 0 else None
-    p_adj = alloc(np.float32) if n_permutations > 0 else None
-    quadrants = alloc(np.int8)
-    zero_var_mask = np.zeros(n_genes, dtype=bool)
-
-    def put(dst, src, b0, b1, inv):
-        if inv is not None:
-            src = src[:, inv]
-        if single:
-            return np.ascontiguousarray(src)
-        dst[:, b0:b1] = src
-        return dst
-
-    for batch_idx in range(n_batches):
-        b0, b1 = batch_idx * batch_size, min((batch_idx + 1) * batch_size, n_genes)
-        logger.debug(f"Processing batch {batch_idx + 1}/{n_batches}")
-        cols, inv = np.unique(gene_indices[b0:b1], return_inverse=True)
-        if inv.size == cols.size and np.array_equal(inv, np.arange(cols.size)):
-            inv = None                       # the usual case: distinct genes in ascending column order
-        if sparse.issparse(X) and n_batches > 1:
-            ctx.set_expression(X[:, cols], np.arange(cols.size, dtype=np.int32))
-        else:
-            ctx.set_expression(X, cols.astype(np.int32))
-        if n_permutations > 0:   # continues the one stream; generator and per-cell counts run as one pipeline
-            r = ctx.local_moran_seeded(words, n_cells, n_permutations, fetch_counts=False)
-        else:
-            r = ctx.local_moran(n_cells, 0, fetch_counts=False)
-        zero = r["zero_var"]
-        # per-cell p, adjusted p and quadrants on the device: lookup tables per (gene, permutation count) built here
-        # with the reference's expressions (AC:894-896, 912-920); zero-variance genes get p = p_adj = 1, quadrant 0
-        if n_permutations > 0:
-            hist = ctx.local_moran_hist(n_permutations)
-            hist[zero] = 0
-            hist[zero, n_permutations] = n_cells
-            p_tab = np.tile(levels, (cols.size, 1))
-            p_tab[zero] = 1.0
-            padj_tab = _padj_tables(hist, n_cells, n_permutations, fdr_correction)
-            padj_tab[zero] = 1.0
-            pb, ab, qb = ctx.local_moran_classify(n_cells, p_tab, padj_tab, zero, alpha)
-            p_values = put(p_values, pb, b0, b1, inv)
-            p_adj = put(p_adj, ab, b0, b1, inv)
-        else:
-            _, _, qb = ctx.local_moran_classify(n_cells, None, None, zero, alpha)
-        quadrants = put(quadrants, qb, b0, b1, inv)
-        for name in ("z", "lag", "I"):
-            if zero.any():
-                r[name][:, zero] = 0.0
-        z_values = put(z_values, r["z"], b0, b1, inv)
-        lag_values = put(lag_values, r["lag"], b0, b1, inv)
-        local_I = put(local_I, r["I"], b0, b1, inv)
-        zero_var_mask[b0:b1] = zero if inv is None else zero[inv]
-
-    zero_variance_genes = [gene_names[i] for i in np.where(zero_var_mask)[0]]
-    if zero_var_mask.any():
-        logger.warning(f"{int(zero_var_mask.sum())} genes have zero variance and will be skipped: "
-                       f"{zero_variance_genes[:5]}")
-    if n_permutations > 0:
-        logger.debug(f"Applied {fdr_correction} correction; LISA quadrants with significance filtering")
-    else:
-        logger.warning("n_permutations=0: Quadrants classified by z/lag signs only, "
-                       "without significance filtering. Consider n_permutations>=99 for p-values.")
-        p_values = np.ones((n_cells, n_genes), dtype=np.float32)
-        p_adj = p_values
-
-    adata.obsm[f"{key_added}_I"] = local_I
-    adata.obsm[f"{key_added}_z"] = z_values
-    adata.obsm[f"{key_added}_lag"] = lag_values
-    adata.obsm[f"{key_added}_p"] = p_values
-    adata.obsm[f"{key_added}_p_adj"] = p_adj
-    adata.obsm[f"{key_added}_quadrant"] = quadrants
-
-    elapsed = time.time() - start_time
-    adata.uns[f"{key_added}_params"] = {
-        "genes": gene_names,
-        "n_neighbors": n_neighbors,
-        "n_permutations": n_permutations,
-        "fdr_correction": fdr_correction,
-        "alpha": alpha,
-        "n_cells": n_cells,
-        "n_genes": n_genes,
-        "seed": seed,
-        "computation_time_seconds": elapsed,
-        "zero_variance_genes": zero_variance_genes,
-    }
-    n_significant = (quadrants != 0).sum(axis=0)
-    logger.info(f"Local Moran's I completed in {elapsed:.1f}s. "
-                f"Significant cells per gene: min={n_significant.min()}, max={n_significant.max()}")
-    update_metadata(
-        adata,
-        function_name="local_morans_i",
-        parameters={
-            "genes": gene_names[:10] if len(gene_names) > 10 else gene_names,
-            "n_genes": n_genes,
-            "n_neighbors": n_neighbors,
-            "n_permutations": n_permutations,
-            "fdr_correction": fdr_correction,
-            "alpha": alpha,
-            "seed": seed,
-            "permgen_form": ctx.permgen_form(n_cells) if n_permutations > 0 else None,
-        },
-        outputs={
-            "obsm_I": f"{key_added}_I",
-            "obsm_z": f"{key_added}_z",
-            "obsm_lag": f"{key_added}_lag",
-            "obsm_p": f"{key_added}_p",
-            "obsm_p_adj": f"{key_added}_p_adj",
-            "obsm_quadrant": f"{key_added}_quadrant",
-            "uns_params": f"{key_added}_params",
-        },
-    )
-    return adata
+    return _local_driver(adata, "moran", "Local Moran's I", "local_morans_i", "I", "quadrant", "LISA quadrants", logger, genes,
+                         layer, spatial_key, n_neighbors, False, n_permutations, fdr_correction, alpha, seed, batch_size,
+                         key_added, copy, device)
 
 
 # =============================================================================================

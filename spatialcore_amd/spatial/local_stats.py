@@ -10,180 +10,16 @@ cell whose null mostly EQUALS the observed value significant; on count data that
 
 from __future__ import annotations
 
-import time
 from typing import List, Optional, Union
 
-import numpy as np
-from scipy import sparse
-
-from spatialcore_amd import _lib
 from spatialcore_amd._logging import get_logger
-from spatialcore_amd._metadata import update_metadata
-from spatialcore_amd.spatial.autocorrelation import (
-    _check_counts,
-    _expression,
-    _knn_weights_f32,
-    _padj_tables,
-    _require_spatial,
-    _resolve_genes,
-)
+from spatialcore_amd.spatial.autocorrelation import _local_driver
 
 logger = get_logger("spatial.local_stats")
 
 MAX_PERMUTATIONS = 65535      # the two tails of a cell share one 32-bit word on the device
 SPOT_CODES = {"NS": 0, "hot": 1, "cold": 2}          # name -> int8 code (string keys: uns must survive an h5ad round trip)
 GEARY_CODES = {"NS": 0, "high-high": 1, "low-low": 2, "other-positive": 3, "negative": 4}
-
-
-def _local_stat(adata, stat, label, function_name, value_suffix, class_suffix, class_codes, genes, layer, spatial_key,
-                n_neighbors, star, n_permutations, fdr_correction, alpha, seed, batch_size, key_added, copy, device):
-    """The driver both functions share: local_morans_i's batch loop around Context.local_stat*."""
-    start_time = time.time()
-    coords = _require_spatial(adata, spatial_key)
-    _check_counts(n_neighbors, n_permutations)
-    if n_permutations > MAX_PERMUTATIONS:
-        raise ValueError(f"n_permutations must be <= {MAX_PERMUTATIONS}, got {n_permutations}")
-    if fdr_correction not in ["bonferroni", "fdr_bh", "none"]:
-        raise ValueError(f"Invalid fdr_correction: '{fdr_correction}'. Must be 'bonferroni', 'fdr_bh', or 'none'.")
-    if batch_size < 1:
-        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
-    adata = adata.copy() if copy else adata
-    gene_names = _resolve_genes(adata, genes, "This may be slow and memory-intensive.")
-    n_cells, n_genes = adata.n_obs, len(gene_names)
-    gene_indices = np.array([adata.var_names.get_loc(g) for g in gene_names])
-    logger.info(f"Computing {label}: {n_cells:,} cells, {n_genes} genes, k={n_neighbors}, permutations={n_permutations}")
-
-    ctx = _lib.default_context(device)
-    _knn_weights_f32(ctx, coords, n_neighbors, include_self=bool(star))
-    X = _expression(adata, layer)
-    if sparse.issparse(X) and n_genes > batch_size:
-        X = X.tocsc()        # one conversion; every batch then ships only its own columns
-
-    words = _lib.rng_state_words(np.random.default_rng(seed))
-    n_batches = (n_genes + batch_size - 1) // batch_size
-    logger.info(f"Processing {n_genes} genes in {n_batches} batches")
-    levels = ((np.arange(n_permutations + 1) + 1) / (n_permutations + 1)).astype(np.float32)
-    single = n_batches == 1
-
-    def alloc(dtype):
-        return None if single else np.empty((n_cells, n_genes), dtype=dtype)   # (one batch: its own arrays become the outputs)
-
-    out = {name: alloc(np.float32) for name in ("z", "lag", "stat")}
-    classes = alloc(np.int8)
-    p_values = alloc(np.float32) if n_permutations > 0 else None
-    p_adj = alloc(np.float32) if n_permutations > 0 else None
-    zero_var_mask = np.zeros(n_genes, dtype=bool)
-
-    def put(dst, src, b0, b1, inv):
-        if inv is not None:
-            src = src[:, inv]
-        if single:
-            return np.ascontiguousarray(src)
-        dst[:, b0:b1] = src
-        return dst
-
-    for batch_idx in range(n_batches):
-        b0, b1 = batch_idx * batch_size, min((batch_idx + 1) * batch_size, n_genes)
-        logger.debug(f"Processing batch {batch_idx + 1}/{n_batches}")
-        cols, inv = np.unique(gene_indices[b0:b1], return_inverse=True)   # a gene named twice is loaded once
-        if inv.size == cols.size and np.array_equal(inv, np.arange(cols.size)):
-            inv = None                       # the usual case: distinct genes in ascending column order
-        if sparse.issparse(X) and n_batches > 1:
-            ctx.set_expression(X[:, cols], np.arange(cols.size, dtype=np.int32))
-        else:
-            ctx.set_expression(X, cols.astype(np.int32))
-        if n_permutations > 0:   # continues the one stream; generator and per-cell counts run as one pipeline
-            r = ctx.local_stat_seeded(stat, words, n_cells, n_permutations, star=star, fetch_counts=False)
-        else:
-            r = ctx.local_stat(stat, n_cells, 0, star=star, fetch_counts=False)
-        zero = r["zero_var"]
-        # per-cell p, adjusted p and classes on the device, from lookup tables per (gene, level m); zero-variance genes
-        # get p = p_adj = 1 and class 0
-        if n_permutations > 0:
-            hist = ctx.local_stat_hist(n_permutations)
-            hist[zero] = 0
-            hist[zero, n_permutations] = n_cells
-            p_tab = np.tile(levels, (cols.size, 1))
-            p_tab[zero] = 1.0
-            padj_tab = _padj_tables(hist, n_cells, n_permutations, fdr_correction)
-            padj_tab[zero] = 1.0
-            pb, ab, qb = ctx.local_stat_classify(n_cells, p_tab, padj_tab, zero, alpha)
-            p_values = put(p_values, pb, b0, b1, inv)
-            p_adj = put(p_adj, ab, b0, b1, inv)
-        else:
-            _, _, qb = ctx.local_stat_classify(n_cells, None, None, zero, alpha)
-        classes = put(classes, qb, b0, b1, inv)
-        for name in ("z", "lag", "stat"):
-            if zero.any():
-                r[name][:, zero] = 0.0
-            out[name] = put(out[name], r[name], b0, b1, inv)
-        zero_var_mask[b0:b1] = zero if inv is None else zero[inv]
-    if n_permutations == 0:
-        p_values = p_adj = np.ones((n_cells, n_genes), dtype=np.float32)
-
-    zero_variance_genes = [gene_names[i] for i in np.where(zero_var_mask)[0]]
-    if zero_var_mask.any():
-        logger.warning(f"{int(zero_var_mask.sum())} genes have zero variance and will be skipped: "
-                       f"{zero_variance_genes[:5]}")
-    if n_permutations > 0:
-        logger.debug(f"Applied {fdr_correction} correction; classes with significance filtering")
-    else:
-        logger.warning("n_permutations=0: Quadrants classified by z/lag signs only, "
-                       "without significance filtering. Consider n_permutations>=99 for p-values.")
-
-    adata.obsm[f"{key_added}_{value_suffix}"] = out["stat"]
-    adata.obsm[f"{key_added}_z"] = out["z"]
-    adata.obsm[f"{key_added}_lag"] = out["lag"]
-    adata.obsm[f"{key_added}_p"] = p_values
-    adata.obsm[f"{key_added}_p_adj"] = p_adj
-    adata.obsm[f"{key_added}_{class_suffix}"] = classes
-
-    elapsed = time.time() - start_time
-    params = {
-        "genes": gene_names,
-        "n_neighbors": n_neighbors,
-        "n_permutations": n_permutations,
-        "fdr_correction": fdr_correction,
-        "alpha": alpha,
-        "n_cells": n_cells,
-        "n_genes": n_genes,
-        "seed": seed,
-        "computation_time_seconds": elapsed,
-        "zero_variance_genes": zero_variance_genes,
-        "class_codes": dict(class_codes),
-    }
-    recorded = {
-        "genes": gene_names[:10] if len(gene_names) > 10 else gene_names,
-        "n_genes": n_genes,
-        "n_neighbors": n_neighbors,
-        "n_permutations": n_permutations,
-        "fdr_correction": fdr_correction,
-        "alpha": alpha,
-        "seed": seed,
-        "permgen_form": ctx.permgen_form(n_cells) if n_permutations > 0 else None,
-    }
-    if stat == "getis":
-        params["star"] = bool(star)
-        recorded["star"] = bool(star)
-    adata.uns[f"{key_added}_params"] = params
-    n_significant = (classes != 0).sum(axis=0)
-    logger.info(f"{label} completed in {elapsed:.1f}s. "
-                f"Significant cells per gene: min={n_significant.min()}, max={n_significant.max()}")
-    update_metadata(
-        adata,
-        function_name=function_name,
-        parameters=recorded,
-        outputs={
-            f"obsm_{value_suffix}": f"{key_added}_{value_suffix}",
-            "obsm_z": f"{key_added}_z",
-            "obsm_lag": f"{key_added}_lag",
-            "obsm_p": f"{key_added}_p",
-            "obsm_p_adj": f"{key_added}_p_adj",
-            f"obsm_{class_suffix}": f"{key_added}_{class_suffix}",
-            "uns_params": f"{key_added}_params",
-        },
-    )
-    return adata
 
 
 def local_getis_ord(
@@ -213,9 +49,10 @@ def local_getis_ord(
     value fixed.  Both tails are counted, ``p = float32((min(ge, le) + 1) / (P + 1))``, so a permuted sum that ties the
     observed one never counts as evidence (see the module docstring).
     """
-    return _local_stat(adata, "getis", "Getis-Ord Gi*" if star else "Getis-Ord Gi", "local_getis_ord", "G", "spot",
-                       SPOT_CODES, genes, layer, spatial_key, n_neighbors, bool(star), n_permutations, fdr_correction, alpha,
-                       seed, batch_size, key_added, copy, device)
+    return _local_driver(adata, "getis", "Getis-Ord Gi*" if star else "Getis-Ord Gi", "local_getis_ord", "G", "spot", "classes",
+                         logger, genes, layer, spatial_key, n_neighbors, bool(star), n_permutations, fdr_correction, alpha,
+                         seed, batch_size, key_added, copy, device, max_permutations=MAX_PERMUTATIONS,
+                         extra_params={"class_codes": dict(SPOT_CODES), "star": bool(star)}, extra_recorded={"star": bool(star)})
 
 
 def local_gearys_c(
@@ -241,6 +78,6 @@ def local_gearys_c(
     positive association (1 high-high, 2 low-low, 3 other positive), ``C > E`` 4 negative, 0 not significant;
     ``uns[{key}_params]``.  Both tails are counted, ``p = float32((min(ge, le) + 1) / (P + 1))``.
     """
-    return _local_stat(adata, "geary", "Local Geary's C", "local_gearys_c", "C", "cluster", GEARY_CODES, genes, layer,
-                       spatial_key, n_neighbors, False, n_permutations, fdr_correction, alpha, seed, batch_size, key_added,
-                       copy, device)
+    return _local_driver(adata, "geary", "Local Geary's C", "local_gearys_c", "C", "cluster", "classes", logger, genes, layer,
+                         spatial_key, n_neighbors, False, n_permutations, fdr_correction, alpha, seed, batch_size, key_added,
+                         copy, device, max_permutations=MAX_PERMUTATIONS, extra_params={"class_codes": dict(GEARY_CODES)})

@@ -878,7 +878,7 @@ def test_numpy_order_column_sums_large(ctx, dtype):
 @pytest.mark.parametrize("uniform", [True, False])
 def test_local_moran_code_rows_equal_float_rows(ctx, monkeypatch, uniform):
     """Count data (every value an integer below 32) travels through the per-cell permutation counts as uint8 code rows
-    with z looked up per (gene, value) (k_lm_gather_u8 / k_lm_count_u8; with equal weights also w * z from a table).  The
+    with z looked up per (gene, value) (k_lm_gather_u8 / k_local_count_u8; with equal weights also w * z from a table).  The
     counts must be those of the float-row form (SC_LM_FLOAT_ROWS), cell for cell: 150 genes = two 128-gene groups with a
     ragged second one, 37 permutations = a ragged last quad, on a row-normalised kNN graph and on a graph with unequal
     weights.  A value of 32 or a non-integer sends the call to the float rows by itself (same counts again)."""

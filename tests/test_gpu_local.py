@@ -6,7 +6,8 @@ stream plus hand-made rows, uploaded with ``set_permutations``), so the expected
 The edges: 16-gene tiles and 128-gene code-row groups; the quads of 4 and launches of 32 permutations of the code-row
 kernels and the batches of 8 of the float-row kernels; 32 / 64 cells per workgroup and the 512-cell blocks of the
 column compaction; unequal weights, unequal degrees, empty rows, negative values; the value 31 / 32 switch between the
-two forms; the LDS switch of the histogram between 767 and 768 permutations; the batches of 16 of local Lee.
+two forms; the LDS switch of the histogram between 767 and 768 permutations; a count above 65535 in its 32-bit word; the
+batches of 16 of local Lee.
 """
 import numpy as np
 import pytest
@@ -116,7 +117,7 @@ def test_permutation_edges_code_rows(ctx, oracle, P):
 @pytest.mark.parametrize("data", ["lognorm", "counts"])
 @pytest.mark.parametrize("P", [1, 7, 8, 9, 17])
 def test_permutation_edges_float_rows(ctx, oracle, monkeypatch, P, data):
-    """Batches of 8 permutations; on the count matrix the exact ties reach k_lm_count_sorted too."""
+    """Batches of 8 permutations; on the count matrix the exact ties reach k_local_count_sorted too."""
     n, G = 1500, 17
     if data == "counts":
         monkeypatch.setenv("SC_LM_FLOAT_ROWS", "1")
@@ -149,7 +150,7 @@ GRAPHS = {"unequal": dict(), "equal-weights-unequal-degrees": dict(equal_weights
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("kind", sorted(GRAPHS))
 def test_weights_and_rows(ctx, oracle, kind, dtype):
-    """Graphs through set_graph_csr: unequal weights (k_lm_count_u8<false>), one weight with unequal degrees, rows
+    """Graphs through set_graph_csr: unequal weights (k_local_count_u8<MORAN, false>), one weight with unequal degrees, rows
     without edges; count data and a matrix with negative non-integer values."""
     n, G, P = 700, 17, 9
     coords = lr.uniform_coords(n, 3)
@@ -235,6 +236,35 @@ def test_perm_row0(ctx, oracle, monkeypatch):
     want = restated(X, graph, perms[5:5 + P])
     for form in both_forms(monkeypatch):
         assert_same(native(ctx, X, perms, P, 5), want, form)
+
+
+def test_counts_above_16_bits(ctx, oracle, monkeypatch):
+    """A local Moran count is one whole 32-bit word: 20 rows of numpy's stream tiled 3277 times are P = 65540
+    permutations -- 2048 full code-row launches and one of 4, 8192 full float-row batches and one of 4.  Counts are
+    additive over rows, so the expected counts are the restatement's of the 20 rows times 3277.  On a row without edges
+    lag = I = 0 and every permutation satisfies |0| >= |0|: those counts are P itself, above 65535.  The histogram and the
+    p of the classification read the same words."""
+    n, G, rows, reps = 40, 2, 20, 3277
+    P = rows * reps
+    assert P == 65540
+    X = lr.count_matrix(n, G, 23)
+    idx = ctx.knn(lr.uniform_coords(n, 5), K)
+    graph = csr_graph(ctx, lr.thinned_csr(idx, seed=6, empty_every=17), n)
+    empty = np.diff(graph[0]) == 0
+    assert empty[8] and empty[25]
+    base = table(oracle, n, rows)
+    want = restated(X, graph, base)
+    want["count"] = want["count"] * reps
+    assert want["count"].dtype == np.int32 and not want["zero_var"].any()
+    assert (want["count"][empty] == P).all() and P > 65535
+    assert ((want["count"] > 0) & (want["count"] < P)).any()
+    perms = np.tile(base, (reps, 1))
+    levels = np.tile(lr.pvalue32(np.arange(P + 1), P), (G, 1))
+    for form in both_forms(monkeypatch):
+        assert_same(native(ctx, X, perms), want, form)
+        np.testing.assert_array_equal(ctx.local_moran_hist(P), lr.count_hist(want["count"], P), err_msg=form)
+        p, _, _ = ctx.local_moran_classify(n, levels, levels, np.zeros(G, dtype=bool), 0.05)
+        np.testing.assert_array_equal(p, levels[np.arange(G)[None, :], want["count"]], err_msg=form)
 
 
 # ---- local_moran_hist and local_moran_classify -----------------------------------------------------------------------

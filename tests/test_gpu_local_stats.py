@@ -5,7 +5,8 @@ Every comparison is ``==``: z, lag, the statistic, both tails of the counts and 
 permutation tables are the tests' own (rows of numpy's stream plus hand-made rows, uploaded with ``set_permutations``).
 The edges are those of tests/test_gpu_local.py, whose structure this file follows: 16-gene tiles and 128-gene code-row
 groups; quads of 4 (Geary: pairs) and launches of 32 permutations of the code-row kernels, batches of 8 of the float-row
-kernels; 32 / 64 cells per workgroup; unequal weights, unequal degrees, empty rows, negative values; the self edge of Gi*.
+kernels; 32 / 64 cells per workgroup; unequal weights, unequal degrees, empty rows, negative values; the self edge of Gi*;
+both tails at 65535, the packed word full.
 """
 import numpy as np
 import pytest
@@ -219,6 +220,34 @@ def test_seeded_equals_generate_then_count(ctx, stat, data):
     np.testing.assert_array_equal(w1, w2)
     assert_same(got, want)
     assert want["ge"].max() <= P and ((want["ge"] + want["le"]) >= P).all()
+
+
+@pytest.mark.parametrize("stat", ["getis", "geary"])
+def test_both_tails_full(ctx, oracle, monkeypatch, stat):
+    """The largest P the two tails accept: 15 rows of numpy's stream tiled 4369 times are 65535 permutations.  Counts are
+    additive over rows, so the expected tails are the restatement's of the 15 rows times 4369.  On a row without edges the
+    statistic and every permuted value are the empty sum 0: ge = le = 65535, all 32 bits of the packed word set.  The
+    histogram of m = min(ge, le) and the p of the classification read the folded words."""
+    n, G, rows, reps = 40, 2, 15, 4369
+    P = rows * reps
+    assert P == 65535
+    X = lr.count_matrix(n, G, 23)
+    graph = thinned_graph(ctx, stat, lr.uniform_coords(n, 5), n, seed=6, empty_every=17)
+    empty = np.diff(graph[0]) == 0
+    assert empty[8] and empty[25]
+    base = table(oracle, n, rows)
+    want = ls.restated(stat, X, graph, base)
+    want["ge"], want["le"] = want["ge"] * reps, want["le"] * reps
+    assert want["ge"].dtype == np.int32 and not want["zero_var"].any()
+    assert (want["ge"][empty] == P).all() and (want["le"][empty] == P).all()
+    perms = np.tile(base, (reps, 1))
+    levels = np.tile(lr.pvalue32(np.arange(P + 1), P), (G, 1))
+    m = np.minimum(want["ge"], want["le"])
+    for form in both_forms(monkeypatch):
+        assert_same(native(ctx, stat, X, perms), want, form)
+        np.testing.assert_array_equal(ctx.local_stat_hist(P), level_hist(want, P), err_msg=form)
+        p, _, _ = ctx.local_stat_classify(n, levels, levels, np.zeros(G, dtype=bool), 0.05)
+        np.testing.assert_array_equal(p, levels[np.arange(G)[None, :], m], err_msg=form)
 
 
 def test_state_hygiene(ctx, oracle):
