@@ -173,8 +173,8 @@ int sc_ctx_destroy(sc_ctx *c)
                     &c->gt_data, &c->gt_cursor, &c->gt_tmp, &c->mom_dev, &c->X, &c->Z, &c->Lag, &c->X32, &c->inv, &c->e_tmp_indptr,
                     &c->e_tmp_indices, &c->e_tmp_data, &c->e_colmap, &c->g_mean, &c->g_var,
                     &c->g_z2, &c->g_scale, &c->g_Inum, &c->g_I, &c->red_tmp, &c->perm, &c->perm_flag,
-                    &c->partial, &c->sims, &c->counts, &c->sim_sum, &c->sim_sumsq, &c->lee_a,
-                    &c->lee_b, &c->lee_out, &c->lee_pairs, &c->lee_U, &c->lee_Zc, &c->lee_Uc, &c->lee_part, &c->lee_obs, &c->lee_cnt,
+                    &c->partial, &c->sims, &c->counts, &c->sim_sum, &c->sim_sumsq, &c->scratch_a,
+                    &c->scratch_b, &c->scratch_out, &c->scratch_idx, &c->lee_U, &c->lee_Zc, &c->lee_Uc, &c->lee_part, &c->lee_obs, &c->lee_cnt,
                     &c->lee_rowmap, &c->lee_lperm, &c->g_slag, &c->g_xsum, &c->g_flags, &c->g_xmax, &c->g_lat, &c->g_meanc, &c->g_seff, &c->g_corr, &c->g_thr, &c->sims_raw, &c->g_order, &c->g_rank, &c->g_indices_r, &c->g_w32, &c->g_erow_r, &c->lm_ys, &c->lm_out, &c->lm_tab, &c->s0_tmp, &c->nib_map,
                     &c->np_cnt, &c->np_comp, &c->np_leaves, &c->np_leafsum,
                     &c->rp_cnt, &c->rp_indptr, &c->rp_row, &c->rp_col, &c->rp_bin, &c->rp_rank,

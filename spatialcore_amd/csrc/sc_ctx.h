@@ -217,8 +217,10 @@ struct sc_ctx {
 
     // ---- Moran / Lee work buffers ----
     DBuf partial, sims, counts, sim_sum, sim_sumsq;
-    DBuf lee_a, lee_b, lee_out, lee_pairs;
-    DBuf lee_U, lee_Zc, lee_Uc, lee_part, lee_obs, lee_cnt, lee_rowmap, lee_lperm;  // batched Lee (sc_lee.hip)
+    // everybody's scratch (Lee, the label-permutation tests, the graph builders, the per-cell statistics): an entry point
+    // lays them out as it likes, and their contents are not kept from one entry point to the next
+    DBuf scratch_a, scratch_b, scratch_out, scratch_idx;
+    DBuf lee_U, lee_Zc, lee_Uc, lee_part, lee_obs, lee_cnt, lee_rowmap, lee_lperm;  // Lee's own (sc_lee*.hip)
     // the per-cell (LISA) statistics (sc_local_prepare.hip, sc_local_stats.hip)
     bool lm_valid = false;   // z / lag / statistic / count words of the last sc_local_moran* or sc_local_stat* are still resident
     int64_t lm_perms = 0;    // ... with this many permutations

@@ -568,18 +568,18 @@ extern "C" int sc_profile_counts(sc_ctx *c, const int32_t *labels, int64_t n, in
         SC_REQUIRE(labels[i] >= 0 && labels[i] < n_types, SC_ERR_INVALID, "label %d of cell %lld out of range",
                    labels[i], (long long)i);
     size_t cbytes = sizeof(float) * (size_t)n * (size_t)n_types;
-    SC_TRY(c->lee_a.ensure(cbytes, &c->mem));
-    SC_TRY(c->lee_pairs.ensure(sizeof(int32_t) * (size_t)n + 16, &c->mem));
+    SC_TRY(c->scratch_a.ensure(cbytes, &c->mem));
+    SC_TRY(c->scratch_idx.ensure(sizeof(int32_t) * (size_t)n + 16, &c->mem));
     SC_TRY(c->perm_flag.ensure(sizeof(unsigned long long), &c->mem));
-    SC_HIP(hipMemcpyAsync(c->lee_pairs.p, labels, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    SC_HIP(hipMemsetAsync(c->lee_a.p, 0, cbytes, c->stream));
+    SC_HIP(hipMemcpyAsync(c->scratch_idx.p, labels, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    SC_HIP(hipMemsetAsync(c->scratch_a.p, 0, cbytes, c->stream));
     SC_HIP(hipMemsetAsync(c->perm_flag.p, 0, sizeof(unsigned long long), c->stream));
     hipLaunchKernelGGL(k_profile, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, c->stream,
-                       c->g_indptr.as<long long>(), c->g_indices.as<int32_t>(), c->lee_pairs.as<int32_t>(), n,
-                       (int)n_types, c->lee_a.as<float>(), c->perm_flag.as<unsigned long long>());
+                       c->g_indptr.as<long long>(), c->g_indices.as<int32_t>(), c->scratch_idx.as<int32_t>(), n,
+                       (int)n_types, c->scratch_a.as<float>(), c->perm_flag.as<unsigned long long>());
     SC_HIP(hipGetLastError());
     unsigned long long empty = 0;
-    SC_HIP(hipMemcpyAsync(counts_out, c->lee_a.p, cbytes, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(counts_out, c->scratch_a.p, cbytes, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipMemcpyAsync(&empty, c->perm_flag.p, sizeof(empty), hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     if (n_empty_out) *n_empty_out = (int64_t)empty;

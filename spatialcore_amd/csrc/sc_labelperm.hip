@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void k_lp_sums(const unsigned long long *__res
 
 namespace {
 
-// the labels, checked to lie in [0, n_types), as one byte per cell into lee_pairs (waited for: the bytes are staged in a
+// the labels, checked to lie in [0, n_types), as one byte per cell into scratch_idx (waited for: the bytes are staged in a
 // local vector)
 int lp_upload_labels(sc_ctx *c, const int32_t *labels, int64_t n, int32_t n_types)
 {
@@ -100,8 +100,8 @@ int lp_upload_labels(sc_ctx *c, const int32_t *labels, int64_t n, int32_t n_type
                    (long long)i);
         lab8[(size_t)i] = (unsigned char)labels[i];
     }
-    SC_TRY(c->lee_pairs.ensure((size_t)n + 16, &c->mem));
-    SC_HIP(hipMemcpyAsync(c->lee_pairs.p, lab8.data(), (size_t)n, hipMemcpyHostToDevice, c->stream));
+    SC_TRY(c->scratch_idx.ensure((size_t)n + 16, &c->mem));
+    SC_HIP(hipMemcpyAsync(c->scratch_idx.p, lab8.data(), (size_t)n, hipMemcpyHostToDevice, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     return SC_OK;
 }
@@ -217,25 +217,25 @@ extern "C" int sc_enrichment_counts(sc_ctx *c, const int32_t *labels, int64_t n,
     const size_t tt = (size_t)n_types * n_types;
     const size_t out_bytes = sizeof(unsigned long long) * tt * (size_t)(n_perm + 1);
     const int64_t lstride = align_up64(n, 16);
-    SC_TRY(c->lee_b.ensure(out_bytes, &c->mem));
-    SC_TRY(c->lee_a.ensure((size_t)lstride * (size_t)(n_perm + 1), &c->mem));   // permuted label vectors
-    SC_HIP(hipMemsetAsync(c->lee_b.p, 0, out_bytes, c->stream));
+    SC_TRY(c->scratch_b.ensure(out_bytes, &c->mem));
+    SC_TRY(c->scratch_a.ensure((size_t)lstride * (size_t)(n_perm + 1), &c->mem));   // permuted label vectors
+    SC_HIP(hipMemsetAsync(c->scratch_b.p, 0, out_bytes, c->stream));
     SC_TRY(sc_graph_ensure_order(c));
     hipLaunchKernelGGL(k_enrich_relabel, dim3((unsigned)ceil_div64(n, 1024), (unsigned)(n_perm + 1)), dim3(256), 0, c->stream,
-                       c->lee_pairs.as<unsigned char>(), c->g_order.as<int32_t>(),
+                       c->scratch_idx.as<unsigned char>(), c->g_order.as<int32_t>(),
                        c->perm.as<int32_t>() + perm_row0 * c->p_stride, c->p_stride, (int)n_perm, n, lstride,
-                       c->lee_a.as<unsigned char>());
+                       c->scratch_a.as<unsigned char>());
     if (c->g_nnz > 0) {
         int copies = 16;
         const int cstride = (int)tt | 1;   // odd: copy c starts at a different LDS bank
         while (copies > 1 && (size_t)copies * cstride > 12288) copies >>= 1;   // <= 48 KB of LDS per workgroup
         dim3 grid((unsigned)(n_perm + 1), (unsigned)ceil_div64(c->g_nnz, ENR_EDGES_PER_BLOCK));
         hipLaunchKernelGGL(k_enrich, grid, dim3(256), sizeof(unsigned int) * cstride * copies, c->stream,
-                           c->g_erow_r.as<int32_t>(), c->g_indices_r.as<int32_t>(), c->g_nnz, c->lee_a.as<unsigned char>(),
-                           lstride, (int)n_types, copies, cstride, c->lee_b.as<unsigned long long>());
+                           c->g_erow_r.as<int32_t>(), c->g_indices_r.as<int32_t>(), c->g_nnz, c->scratch_a.as<unsigned char>(),
+                           lstride, (int)n_types, copies, cstride, c->scratch_b.as<unsigned long long>());
     }
     SC_HIP(hipGetLastError());
-    SC_HIP(hipMemcpyAsync(counts_out, c->lee_b.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(counts_out, c->scratch_b.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     return SC_OK;
 }
@@ -301,9 +301,9 @@ extern "C" int sc_enrichment_counter(sc_ctx *c, const int32_t *labels, int64_t n
     const int tt = n_types * n_types;
     const int64_t lstride = align_up64(n, 16);
     const size_t cnt_bytes = sizeof(unsigned long long) * (size_t)tt * (size_t)batch;
-    SC_TRY(c->lee_b.ensure(cnt_bytes + sizeof(unsigned long long) * (size_t)tt * 4, &c->mem));   // counts | observed | 3 sums
-    SC_TRY(c->lee_a.ensure((size_t)lstride * (size_t)align_up64(batch, 16), &c->mem));   // (also the 16-wide form: n x 16 B per 16 rows)
-    unsigned long long *d_cnt = c->lee_b.as<unsigned long long>(), *d_obs = d_cnt + (size_t)tt * batch;
+    SC_TRY(c->scratch_b.ensure(cnt_bytes + sizeof(unsigned long long) * (size_t)tt * 4, &c->mem));   // counts | observed | 3 sums
+    SC_TRY(c->scratch_a.ensure((size_t)lstride * (size_t)align_up64(batch, 16), &c->mem));   // (also the 16-wide form: n x 16 B per 16 rows)
+    unsigned long long *d_cnt = c->scratch_b.as<unsigned long long>(), *d_obs = d_cnt + (size_t)tt * batch;
     long long *d_sums = reinterpret_cast<long long *>(d_obs + tt);
     SC_TRY(sc_graph_ensure_order(c));
     SC_HIP(hipMemsetAsync(d_obs, 0, sizeof(unsigned long long) * (size_t)tt * 4, c->stream));
@@ -316,22 +316,22 @@ extern "C" int sc_enrichment_counter(sc_ctx *c, const int32_t *labels, int64_t n
     auto relabel = [&](int rows, const int32_t *table) {
         if (wide && table)
             hipLaunchKernelGGL(k_enrich_relabel16, dim3((unsigned)ceil_div64(n, 256), (unsigned)((rows + 15) / 16)), dim3(256), 0,
-                               c->stream, c->lee_pairs.as<unsigned char>(), c->g_rank.as<int32_t>(), table, c->p_stride, rows, n,
-                               c->lee_a.as<uint4>());
+                               c->stream, c->scratch_idx.as<unsigned char>(), c->g_rank.as<int32_t>(), table, c->p_stride, rows, n,
+                               c->scratch_a.as<uint4>());
         else
             hipLaunchKernelGGL(k_enrich_relabel, dim3((unsigned)ceil_div64(n, 1024), (unsigned)rows), dim3(256), 0, c->stream,
-                               c->lee_pairs.as<unsigned char>(), c->g_order.as<int32_t>(), table, c->p_stride, table ? rows : 0, n,
-                               lstride, c->lee_a.as<unsigned char>());
+                               c->scratch_idx.as<unsigned char>(), c->g_order.as<int32_t>(), table, c->p_stride, table ? rows : 0, n,
+                               lstride, c->scratch_a.as<unsigned char>());
     };
     auto edges = [&](int rows, unsigned long long *out, bool from_table) {
         if (c->g_nnz <= 0) return;
         if (wide && from_table)
             hipLaunchKernelGGL(k_enrich16, dim3((unsigned)((rows + 15) / 16), eblocks), dim3(256), sizeof(unsigned int) * 16 * hstride,
-                               c->stream, c->g_erow_r.as<int32_t>(), c->g_indices_r.as<int32_t>(), c->g_nnz, c->lee_a.as<uint4>(), n,
+                               c->stream, c->g_erow_r.as<int32_t>(), c->g_indices_r.as<int32_t>(), c->g_nnz, c->scratch_a.as<uint4>(), n,
                                (int)n_types, hstride, rows, out);
         else
             hipLaunchKernelGGL(k_enrich, dim3((unsigned)rows, eblocks), dim3(256), sizeof(unsigned int) * cstride * copies, c->stream,
-                               c->g_erow_r.as<int32_t>(), c->g_indices_r.as<int32_t>(), c->g_nnz, c->lee_a.as<unsigned char>(),
+                               c->g_erow_r.as<int32_t>(), c->g_indices_r.as<int32_t>(), c->g_nnz, c->scratch_a.as<unsigned char>(),
                                lstride, (int)n_types, copies, cstride, out);
     };
     // observed labels: one "permutation" without a table
@@ -579,7 +579,7 @@ struct RipPlan {
     unsigned pblocks = 0;
 };
 
-// what both counting entry points check: the pair list, the labels (uploaded to lee_pairs), the shape
+// what both counting entry points check: the pair list, the labels (uploaded to scratch_idx), the shape
 int rip_prepare(sc_ctx *c, const char *who, const int32_t *labels, int64_t n, int32_t n_types, RipPlan *plan)
 {
     SC_REQUIRE(n_types >= 1 && n_types <= 96, SC_ERR_INVALID, "%s: n_types must be 1..96, got %d", who, (int)n_types);
@@ -608,7 +608,7 @@ int rip_prepare(sc_ctx *c, const char *who, const int32_t *labels, int64_t n, in
 void rip_observed(sc_ctx *c, const RipPlan &pl, int64_t n, unsigned char *labp, unsigned long long *out)
 {
     hipLaunchKernelGGL(k_enrich_relabel, dim3((unsigned)ceil_div64(n, 1024), 1u), dim3(256), 0, c->stream,
-                       c->lee_pairs.as<unsigned char>(), c->sid.as<int32_t>(), (const int32_t *)nullptr, (int64_t)0, 0, n,
+                       c->scratch_idx.as<unsigned char>(), c->sid.as<int32_t>(), (const int32_t *)nullptr, (int64_t)0, 0, n,
                        align_up64(n, 16), labp);
     if (c->rp_pairs > 0)
         hipLaunchKernelGGL(k_ripley<1>, dim3(1u, pl.pblocks), dim3(RIP_THREADS), sizeof(unsigned int) * (size_t)pl.cells, c->stream,
@@ -616,12 +616,12 @@ void rip_observed(sc_ctx *c, const RipPlan &pl, int64_t n, unsigned char *labp, 
                            (int64_t)0, 1, pl.T, pl.R, pl.cells, 1, out);
 }
 
-// `rows` rows of the permutation table -> 16-byte label words in lee_a
+// `rows` rows of the permutation table -> 16-byte label words in scratch_a
 void rip_relabel_words(sc_ctx *c, int64_t n, const int32_t *table, int rows)
 {
     hipLaunchKernelGGL(k_enrich_relabel16, dim3((unsigned)ceil_div64(n, 256), (unsigned)((rows + 15) / 16)), dim3(256), 0,
-                       c->stream, c->lee_pairs.as<unsigned char>(), c->rp_rank.as<int32_t>(), table, c->p_stride, rows, n,
-                       c->lee_a.as<uint4>());
+                       c->stream, c->scratch_idx.as<unsigned char>(), c->rp_rank.as<int32_t>(), table, c->p_stride, rows, n,
+                       c->scratch_a.as<uint4>());
 }
 
 // ... -> out[rows][cells], NP permutations per pass over the pairs
@@ -632,7 +632,7 @@ void rip_count_words(sc_ctx *c, const RipPlan &pl, int64_t n, int rows, unsigned
     const size_t lds = sizeof(unsigned int) * (size_t)pl.np * pl.hstride;
 #define RIP_LAUNCH(NP)                                                                                                  \
     hipLaunchKernelGGL(k_ripley<NP>, grid, dim3(RIP_THREADS), lds, c->stream, c->rp_row.as<int32_t>(), c->rp_col.as<int32_t>(), \
-                       c->rp_bin.as<unsigned char>(), c->rp_pairs, c->lee_a.as<unsigned char>(), (int64_t)n * 16, 16, pl.T, pl.R, \
+                       c->rp_bin.as<unsigned char>(), c->rp_pairs, c->scratch_a.as<unsigned char>(), (int64_t)n * 16, 16, pl.T, pl.R, \
                        pl.hstride, rows, out)
     switch (pl.np) {
     case 16: RIP_LAUNCH(16); break;
@@ -680,17 +680,17 @@ extern "C" int sc_ripley_counts(sc_ctx *c, const int32_t *labels, int64_t n, int
     }
     const size_t words = (size_t)pl.cells * (size_t)(n_perm + 1);
     const int64_t lstride = align_up64(n, 16);
-    SC_TRY(c->lee_b.ensure(sizeof(unsigned long long) * words, &c->mem));
+    SC_TRY(c->scratch_b.ensure(sizeof(unsigned long long) * words, &c->mem));
     // [16-byte label words of the table rows | observed labels by position]
     const size_t word_bytes = (size_t)n * 16 * (size_t)((n_perm + 15) / 16);
-    SC_TRY(c->lee_a.ensure(word_bytes + (size_t)lstride, &c->mem));
-    unsigned long long *d_cnt = c->lee_b.as<unsigned long long>();
+    SC_TRY(c->scratch_a.ensure(word_bytes + (size_t)lstride, &c->mem));
+    unsigned long long *d_cnt = c->scratch_b.as<unsigned long long>();
     SC_HIP(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long) * words, c->stream));
     if (n_perm > 0) {
         rip_relabel_words(c, n, c->perm.as<int32_t>() + perm_row0 * c->p_stride, (int)n_perm);
         rip_count_words(c, pl, n, (int)n_perm, d_cnt);
     }
-    rip_observed(c, pl, n, c->lee_a.as<unsigned char>() + word_bytes, d_cnt + (size_t)pl.cells * (size_t)n_perm);
+    rip_observed(c, pl, n, c->scratch_a.as<unsigned char>() + word_bytes, d_cnt + (size_t)pl.cells * (size_t)n_perm);
     SC_HIP(hipGetLastError());
     std::vector<unsigned long long> host(words);
     SC_HIP(hipMemcpyAsync(host.data(), d_cnt, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, c->stream));
@@ -712,13 +712,13 @@ extern "C" int sc_ripley_counter(sc_ctx *c, const int32_t *labels, int64_t n, in
     const int cells = pl.cells;
     const int64_t lstride = align_up64(n, 16);
     const size_t cnt_bytes = sizeof(unsigned long long) * (size_t)cells * (size_t)batch;
-    SC_TRY(c->lee_b.ensure(cnt_bytes + sizeof(unsigned long long) * (size_t)cells * 5, &c->mem));   // counts | observed | 4 sums
+    SC_TRY(c->scratch_b.ensure(cnt_bytes + sizeof(unsigned long long) * (size_t)cells * 5, &c->mem));   // counts | observed | 4 sums
     const size_t word_bytes = (size_t)n * 16 * (size_t)((batch + 15) / 16);
-    SC_TRY(c->lee_a.ensure(word_bytes > (size_t)lstride ? word_bytes : (size_t)lstride, &c->mem));
-    unsigned long long *d_cnt = c->lee_b.as<unsigned long long>(), *d_obs = d_cnt + (size_t)cells * batch;
+    SC_TRY(c->scratch_a.ensure(word_bytes > (size_t)lstride ? word_bytes : (size_t)lstride, &c->mem));
+    unsigned long long *d_cnt = c->scratch_b.as<unsigned long long>(), *d_obs = d_cnt + (size_t)cells * batch;
     long long *d_sums = reinterpret_cast<long long *>(d_obs + cells);
     SC_HIP(hipMemsetAsync(d_obs, 0, sizeof(unsigned long long) * (size_t)cells * 5, c->stream));
-    rip_observed(c, pl, n, c->lee_a.as<unsigned char>(), d_obs);   // (the label words of batch 0 follow on the same stream)
+    rip_observed(c, pl, n, c->scratch_a.as<unsigned char>(), d_obs);   // (the label words of batch 0 follow on the same stream)
     SC_HIP(hipGetLastError());
     SC_TRY(lp_counter_batches(
         c, "sc_ripley_counter", seed, n, p_first, n_perm, batch, [&](int rows) { rip_relabel_words(c, n, c->perm.as<int32_t>(), rows); },

@@ -13,14 +13,15 @@
 //     rows -- a fresh block of P per live pair, in pair order, zero-variance pairs draw nothing (AC:1129-1140) -- come
 //     out of the same generator pipeline as sc_moran_seeded and are scored chunk by chunk while the generator runs; the
 //     counts are reduced on the device (no host round trip per pair).
-// Behind the batched forms: Lee's L one pair at a time on the resident table (sc_lee), and local Lee (sc_lee_local*).
+// Behind the batched forms: Lee's L one pair at a time on the resident table (sc_lee), at the end of this file.  The
+// float32-faithful observed value is in sc_lee_f32.hip, local Lee in sc_lee_local.hip; sc_lee.h is what they share.
 #include <math.h>
 #include <string.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "sc_ctx.h"
+#include "sc_lee.h"
 
 // out[k][cell] = T[tile(genes[k])][cell][slot(genes[k])]: gene-major contiguous copies of the genes a kernel gathers from
 __global__ __launch_bounds__(256) void k_gene_major(const double *__restrict__ T, int64_t n, const int32_t *__restrict__ genes,
@@ -82,22 +83,27 @@ __global__ __launch_bounds__(256) void k_lee_observed_pick(const double *__restr
     obs[q] = s;
 }
 
-// ---- permutation statistic of a chunk of rows: partial[row][block] = sum_{j in block} U[x(row)][j] * Zy[y(row)][perm_row[j]] ----
-#define LEE_PERM_CELLS 8192
+// ---- the per-pair permutation statistic: partial[row][block] = sum_{j in block} u[j] * z[perm_row[j]] ----
+// Row r of a launch belongs to pair (row0 + r) / rows_per_pair of the slot table: (slot of u_x in Uc, slot of z_y in Zc),
+// n doubles per slot; 32-bit, a generator job has fewer than 2^32 rows.  A single pair (lee_pair_*) is a one-entry table
+// over its own vectors.  PERMUTED = false is the identity permutation: sc_lee's observed L.
+#define LEE_ROW_CELLS 8192   // cells per workgroup.  sc_lee and sc_lee_seeded agree bit for bit because they add the same blocks.
 
+template <bool PERMUTED>
 __global__ __launch_bounds__(256) void k_lee_rows(const double *__restrict__ Uc, const double *__restrict__ Zc, int64_t n,
                                                   const int32_t *__restrict__ perm, int64_t pstride,
-                                                  const int2 *__restrict__ row_slots, double *__restrict__ partial)
+                                                  const int2 *__restrict__ pair_slots, unsigned row0, unsigned rows_per_pair,
+                                                  double *__restrict__ partial)
 {
     __shared__ double sh[256];
     const int row = blockIdx.y;
-    const int2 sl = row_slots[row];          // (slot of u_x in Uc, slot of z_y in Zc)
+    const int2 sl = pair_slots[(row0 + row) / rows_per_pair];
     const double *u = Uc + (int64_t)sl.x * n, *z = Zc + (int64_t)sl.y * n;
     const int32_t *prow = perm + (int64_t)row * pstride;
-    const int64_t j0 = (int64_t)blockIdx.x * LEE_PERM_CELLS;
-    const int64_t j1 = j0 + LEE_PERM_CELLS < n ? j0 + LEE_PERM_CELLS : n;
+    const int64_t j0 = (int64_t)blockIdx.x * LEE_ROW_CELLS;
+    const int64_t j1 = j0 + LEE_ROW_CELLS < n ? j0 + LEE_ROW_CELLS : n;
     double acc = 0.0;
-    for (int64_t j = j0 + threadIdx.x; j < j1; j += 256) acc = fma(u[j], z[prow[j]], acc);
+    for (int64_t j = j0 + threadIdx.x; j < j1; j += 256) acc = fma(u[j], z[PERMUTED ? prow[j] : j], acc);
     sh[threadIdx.x] = acc;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
@@ -107,20 +113,117 @@ __global__ __launch_bounds__(256) void k_lee_rows(const double *__restrict__ Uc,
     if (threadIdx.x == 0) partial[(int64_t)row * gridDim.x + blockIdx.x] = sh[0];
 }
 
-// L_perm[row] = sum_b partial[row][b] (ascending); count[pair(row)] += |L_perm| >= |obs[pair]| (integer: exact, order-free)
-__global__ __launch_bounds__(256) void k_lee_rows_count(const double *__restrict__ partial, int blocks, int rows,
-                                                        const int32_t *__restrict__ row_pair,
-                                                        const double *__restrict__ obs,
-                                                        unsigned long long *__restrict__ count,
-                                                        double *__restrict__ lperm_out)
+// sum[row] = sum_b partial[row][b] (ascending) into out (optional).  COUNT: count[pair(row)] += |sum| >= |obs[pair]|
+// (integer: exact, order-free), the pair being pair_of[(row0 + row) / rows_per_pair]
+template <bool COUNT>
+__global__ __launch_bounds__(256) void k_lee_row_sums(const double *__restrict__ partial, int blocks, int rows,
+                                                      const int32_t *__restrict__ pair_of, unsigned row0, unsigned rows_per_pair,
+                                                      const double *__restrict__ obs, unsigned long long *__restrict__ count,
+                                                      double *__restrict__ out)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows) return;
     double s = 0.0;
     for (int b = 0; b < blocks; ++b) s += partial[(int64_t)r * blocks + b];
-    const int q = row_pair[r];
-    if (fabs(s) >= fabs(obs[q])) atomicAdd(&count[q], 1ull);
-    if (lperm_out) lperm_out[r] = s;
+    if (COUNT) {
+        const int q = pair_of[(row0 + r) / rows_per_pair];
+        if (fabs(s) >= fabs(obs[q])) atomicAdd(&count[q], 1ull);
+    }
+    if (out) out[r] = s;
+}
+
+// ---- what the entry points share ----
+
+int lee_check_genes(const sc_ctx *c, const char *name, const char *fmt, const int32_t *a, const int32_t *b, int64_t k)
+{
+    const int64_t G = c->e_genes;
+    for (int64_t q = 0; q < k; ++q)
+        SC_REQUIRE(a[q] >= 0 && a[q] < G && (!b || (b[q] >= 0 && b[q] < G)), SC_ERR_INVALID, fmt, name, (long long)q);
+    return SC_OK;
+}
+
+int lee_operands(sc_ctx *c, int transposed, std::vector<double> *var)
+{
+    const size_t tiles_bytes = (size_t)c->e_tiles * (size_t)c->e_n * SC_TILE * sizeof(double);
+    SC_TRY(sc_expr_zscores(c));
+    SC_TRY(c->Lag.ensure(tiles_bytes, &c->mem));
+    SC_TRY(sc_lag_tiles(c, c->g_indptr, c->g_indices, c->g_data, c->Z.as<double>(), c->Lag.as<double>()));
+    if (transposed >= 1) SC_TRY(sc_graph_ensure_transpose(c));
+    if (transposed >= 2) {
+        SC_TRY(c->lee_U.ensure(tiles_bytes, &c->mem));
+        SC_TRY(sc_lag_tiles(c, c->gt_indptr, c->gt_indices, c->gt_data, c->Z.as<double>(), c->lee_U.as<double>()));
+    }
+    if (var) {
+        var->resize((size_t)c->e_genes);
+        SC_HIP(hipMemcpyAsync(var->data(), c->g_var.p, sizeof(double) * var->size(), hipMemcpyDeviceToHost, c->stream));
+        SC_HIP(hipStreamSynchronize(c->stream));
+    }
+    return SC_OK;
+}
+
+void lee_gene_major(sc_ctx *c, const double *T, const int32_t *d_genes, int k, double *out)
+{
+    hipLaunchKernelGGL(k_gene_major, dim3((unsigned)ceil_div64(c->e_n, 256), (unsigned)k), dim3(256), 0, c->stream, T, c->e_n,
+                       d_genes, out);
+}
+
+// The observed stage of the batched forms.  L of n_pairs pairs into c->lee_obs and their counts zeroed (c->lee_cnt, with
+// room for lee_counted_pipeline's copy): one MFMA contraction of Zt against Lagt per tile pair of tps, then pair q picks
+// element (px[q] & 15, py[q] & 15) of tile pair tp[q] (tp[q] < 0: L = 0).  The host arrays are read until c->stream is
+// next synchronised.
+static int lee_observed(sc_ctx *c, const double *Zt, const double *Lagt, const std::vector<int2> &tps, const int32_t *tp,
+                        const int32_t *px, const int32_t *py, int64_t n_pairs)
+{
+    const int64_t n = c->e_n;
+    const int oblocks = (int)ceil_div64(n, LEE_OBS_CELLS);
+    SC_TRY(c->lee_obs.ensure(sizeof(double) * (size_t)n_pairs, &c->mem));
+    SC_TRY(c->lee_cnt.ensure(sizeof(unsigned long long) * (size_t)n_pairs * 2, &c->mem));
+    SC_HIP(hipMemsetAsync(c->lee_cnt.p, 0, sizeof(unsigned long long) * (size_t)n_pairs, c->stream));
+    // small index arrays: [tp | px | py] then the tile pairs
+    SC_TRY(c->scratch_idx.ensure(sizeof(int32_t) * (size_t)(3 * n_pairs) + sizeof(int2) * (tps.size() + 1), &c->mem));
+    int32_t *d_tp = c->scratch_idx.as<int32_t>(), *d_px = d_tp + n_pairs, *d_py = d_px + n_pairs;
+    int2 *d_tps = reinterpret_cast<int2 *>(d_py + n_pairs + (n_pairs & 1));
+    SC_HIP(hipMemcpyAsync(d_tp, tp, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
+    SC_HIP(hipMemcpyAsync(d_px, px, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
+    SC_HIP(hipMemcpyAsync(d_py, py, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
+    if (!tps.empty()) {
+        SC_HIP(hipMemcpyAsync(d_tps, tps.data(), sizeof(int2) * tps.size(), hipMemcpyHostToDevice, c->stream));
+        SC_TRY(c->lee_part.ensure(sizeof(double) * tps.size() * (size_t)oblocks * 256, &c->mem));
+        hipLaunchKernelGGL(k_lee_observed_mfma, dim3((unsigned)oblocks, (unsigned)tps.size()), dim3(256), 0, c->stream, Zt, Lagt,
+                           n, d_tps, c->lee_part.as<double>());
+    }
+    hipLaunchKernelGGL(k_lee_observed_pick, dim3((unsigned)ceil_div64(n_pairs, 256)), dim3(256), 0, c->stream,
+                       c->lee_part.as<double>(), oblocks, d_tp, d_px, d_py, n_pairs, c->lee_obs.as<double>());
+    SC_HIP(hipGetLastError());
+    return SC_OK;
+}
+
+// A generator job of `rows` permutations scored chunk by chunk into the n_cnt counts of c->lee_cnt.  The block-parallel
+// scan verifies itself at the end of a job; if that fails (never seen without the fault injection mode) the counts are
+// rolled back to what they were before the job and it is rerun with the sequential scan.
+static int lee_counted_pipeline(sc_ctx *c, uint64_t *state6, int64_t rows, int64_t n_cnt,
+                                const std::function<int(int64_t, int64_t)> &score)
+{
+    unsigned long long *cnt = c->lee_cnt.as<unsigned long long>(), *backup = cnt + n_cnt;
+    const size_t bytes = sizeof(unsigned long long) * (size_t)n_cnt;
+    SC_HIP(hipMemcpyAsync(backup, cnt, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return permgen_rerun_on_failure(
+        c, [&]() { return sc_perm_pipeline(c, state6, c->e_n, rows, 0, 2, nullptr, score); },
+        [&]() -> int {
+            SC_HIP(hipMemcpyAsync(cnt, backup, bytes, hipMemcpyDeviceToDevice, c->stream));
+            return SC_OK;
+        });
+}
+
+// L and the counts (widened to int64) of n_pairs pairs to the host
+static int lee_download(sc_ctx *c, int64_t n_pairs, double *L_out, int64_t *count_abs_ge_out)
+{
+    std::vector<unsigned long long> cnt((size_t)n_pairs);
+    SC_HIP(hipMemcpyAsync(L_out, c->lee_obs.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(cnt.data(), c->lee_cnt.p, sizeof(unsigned long long) * (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipStreamSynchronize(c->stream));
+    for (int64_t q = 0; q < n_pairs; ++q) count_abs_ge_out[q] = (int64_t)cnt[(size_t)q];
+    return SC_OK;
 }
 
 extern "C" int sc_lee_seeded(sc_ctx *c, uint64_t *state6, const int32_t *pair_x, const int32_t *pair_y, int64_t n_pairs,
@@ -133,19 +236,10 @@ extern "C" int sc_lee_seeded(sc_ctx *c, uint64_t *state6, const int32_t *pair_x,
     SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_lee_seeded: no expression loaded");
     SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_lee_seeded: graph missing or size mismatch");
     const int64_t n = c->e_n, T = c->e_tiles, G = c->e_genes;
-    for (int64_t q = 0; q < n_pairs; ++q)
-        SC_REQUIRE(pair_x[q] >= 0 && pair_x[q] < G && pair_y[q] >= 0 && pair_y[q] < G, SC_ERR_INVALID,
-                   "sc_lee_seeded: pair %lld references a gene outside the loaded set", (long long)q);
+    SC_TRY(lee_check_genes(c, "sc_lee_seeded", "%s: pair %lld references a gene outside the loaded set", pair_x, pair_y, n_pairs));
     if (n_pairs == 0) return SC_OK;
-    const size_t tile_bytes = (size_t)n * SC_TILE * sizeof(double);
-
-    // z-scores, lag = W Z, U = W^T Z for every loaded gene
-    SC_TRY(sc_expr_zscores(c));
-    SC_TRY(c->Lag.ensure((size_t)T * tile_bytes, &c->mem));
-    SC_TRY(sc_lag_tiles(c, c->g_indptr, c->g_indices, c->g_data, c->Z.as<double>(), c->Lag.as<double>()));
-    std::vector<double> var((size_t)G);
-    SC_HIP(hipMemcpyAsync(var.data(), c->g_var.p, sizeof(double) * var.size(), hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
+    std::vector<double> var;
+    SC_TRY(lee_operands(c, n_perm > 0 ? 2 : 0, &var));
 
     // ---- observed L of every pair: MFMA contraction per distinct (x tile, y tile) ----
     std::vector<int32_t> pair_tp((size_t)n_pairs, -1), live;
@@ -165,101 +259,60 @@ extern "C" int sc_lee_seeded(sc_ctx *c, uint64_t *state6, const int32_t *pair_x,
             pair_tp[(size_t)live[i]] = (int32_t)(std::lower_bound(uniq.begin(), uniq.end(), keys[i]) - uniq.begin());
     }
     const int64_t n_live = (int64_t)live.size();
-    SC_TRY(c->lee_obs.ensure(sizeof(double) * (size_t)n_pairs, &c->mem));
-    SC_TRY(c->lee_cnt.ensure(sizeof(unsigned long long) * (size_t)n_pairs * 2, &c->mem));   // counts + roll-back copy
-    unsigned long long *d_cnt_backup = c->lee_cnt.as<unsigned long long>() + n_pairs;
-    SC_HIP(hipMemsetAsync(c->lee_cnt.p, 0, sizeof(unsigned long long) * (size_t)n_pairs, c->stream));
-    // small index arrays: [pair_tp | pair_x | pair_y] then the tile pairs
-    SC_TRY(c->lee_pairs.ensure(sizeof(int32_t) * (size_t)(3 * n_pairs) + sizeof(int2) * (tps.size() + 1), &c->mem));
-    int32_t *d_tp = c->lee_pairs.as<int32_t>(), *d_px = d_tp + n_pairs, *d_py = d_px + n_pairs;
-    int2 *d_tps = reinterpret_cast<int2 *>(d_py + n_pairs + (n_pairs & 1));
-    SC_HIP(hipMemcpyAsync(d_tp, pair_tp.data(), sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
-    SC_HIP(hipMemcpyAsync(d_px, pair_x, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
-    SC_HIP(hipMemcpyAsync(d_py, pair_y, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
-    const int oblocks = (int)ceil_div64(n, LEE_OBS_CELLS);
-    if (!tps.empty()) {
-        SC_HIP(hipMemcpyAsync(d_tps, tps.data(), sizeof(int2) * tps.size(), hipMemcpyHostToDevice, c->stream));
-        SC_TRY(c->lee_part.ensure(sizeof(double) * tps.size() * (size_t)oblocks * 256, &c->mem));
-        hipLaunchKernelGGL(k_lee_observed_mfma, dim3((unsigned)oblocks, (unsigned)tps.size()), dim3(256), 0, c->stream,
-                           c->Z.as<double>(), c->Lag.as<double>(), n, d_tps, c->lee_part.as<double>());
-    }
-    hipLaunchKernelGGL(k_lee_observed_pick, dim3((unsigned)ceil_div64(n_pairs, 256)), dim3(256), 0, c->stream,
-                       c->lee_part.as<double>(), oblocks, d_tp, d_px, d_py, n_pairs, c->lee_obs.as<double>());
-    SC_HIP(hipGetLastError());
+    SC_TRY(lee_observed(c, c->Z.as<double>(), c->Lag.as<double>(), tps, pair_tp.data(), pair_x, pair_y, n_pairs));
 
     if (n_perm > 0 && n_live > 0) {
-        // ---- U = W^T Z (tiles), gene-major copies of the u_x / z_y vectors the permutation kernel reads ----
-        SC_TRY(sc_graph_ensure_transpose(c));
-        SC_TRY(c->lee_U.ensure((size_t)T * tile_bytes, &c->mem));
-        SC_TRY(sc_lag_tiles(c, c->gt_indptr, c->gt_indices, c->gt_data, c->Z.as<double>(), c->lee_U.as<double>()));
+        // ---- gene-major copies of the u_x / z_y vectors the permutation kernel reads; per live pair its slots and its index ----
         std::vector<int32_t> xs, ys, slot_x((size_t)G, -1), slot_y((size_t)G, -1);
+        std::vector<int2> slots;
         for (int32_t q : live) {
             if (slot_x[(size_t)pair_x[q]] < 0) { slot_x[(size_t)pair_x[q]] = (int32_t)xs.size(); xs.push_back(pair_x[q]); }
             if (slot_y[(size_t)pair_y[q]] < 0) { slot_y[(size_t)pair_y[q]] = (int32_t)ys.size(); ys.push_back(pair_y[q]); }
+            slots.push_back(make_int2(slot_x[(size_t)pair_x[q]], slot_y[(size_t)pair_y[q]]));
         }
         SC_TRY(c->lee_Uc.ensure(sizeof(double) * xs.size() * (size_t)n, &c->mem));
         SC_TRY(c->lee_Zc.ensure(sizeof(double) * ys.size() * (size_t)n, &c->mem));
-        SC_TRY(c->lee_a.ensure(sizeof(int32_t) * (xs.size() + ys.size()), &c->mem));
-        int32_t *d_xs = c->lee_a.as<int32_t>(), *d_ys = d_xs + xs.size();
+        SC_TRY(c->scratch_a.ensure(sizeof(int32_t) * (xs.size() + ys.size()), &c->mem));
+        SC_TRY(c->lee_rowmap.ensure((sizeof(int2) + sizeof(int32_t)) * (size_t)n_live, &c->mem));
+        int32_t *d_xs = c->scratch_a.as<int32_t>(), *d_ys = d_xs + xs.size();
+        int2 *d_slots = c->lee_rowmap.as<int2>();
+        int32_t *d_live = reinterpret_cast<int32_t *>(d_slots + n_live);
         SC_HIP(hipMemcpyAsync(d_xs, xs.data(), sizeof(int32_t) * xs.size(), hipMemcpyHostToDevice, c->stream));
         SC_HIP(hipMemcpyAsync(d_ys, ys.data(), sizeof(int32_t) * ys.size(), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_gene_major, dim3((unsigned)ceil_div64(n, 256), (unsigned)xs.size()), dim3(256), 0, c->stream,
-                           c->lee_U.as<double>(), n, d_xs, c->lee_Uc.as<double>());
-        hipLaunchKernelGGL(k_gene_major, dim3((unsigned)ceil_div64(n, 256), (unsigned)ys.size()), dim3(256), 0, c->stream,
-                           c->Z.as<double>(), n, d_ys, c->lee_Zc.as<double>());
+        SC_HIP(hipMemcpyAsync(d_slots, slots.data(), sizeof(int2) * (size_t)n_live, hipMemcpyHostToDevice, c->stream));
+        SC_HIP(hipMemcpyAsync(d_live, live.data(), sizeof(int32_t) * (size_t)n_live, hipMemcpyHostToDevice, c->stream));
+        lee_gene_major(c, c->lee_U.as<double>(), d_xs, (int)xs.size(), c->lee_Uc.as<double>());
+        lee_gene_major(c, c->Z.as<double>(), d_ys, (int)ys.size(), c->lee_Zc.as<double>());
         SC_HIP(hipGetLastError());
-        SC_HIP(hipStreamSynchronize(c->stream));  // xs / ys / tps are host vectors
+        SC_HIP(hipStreamSynchronize(c->stream));  // the index arrays are host vectors
 
-        // ---- permutations: sub-jobs of whole pairs, each a generator / scoring pipeline that continues the stream ----
+        // ---- permutations: sub-jobs of whole pairs, each a generator / scoring pipeline that continues the stream.
+        // Live pair l0 + i owns rows [i n_perm, (i + 1) n_perm) of its job ----
         const int64_t max_rows = std::max<int64_t>(n_perm, (int64_t)(2.2e9 / (double)n));   // ~40 GB of generator scratch
         const int64_t pairs_per_job = std::max<int64_t>(1, max_rows / n_perm);
-        const int pblocks = (int)ceil_div64(n, LEE_PERM_CELLS);
+        const int pblocks = (int)ceil_div64(n, LEE_ROW_CELLS);
         const int64_t job_rows_max = std::min(n_live, pairs_per_job) * n_perm;
-        SC_TRY(c->lee_rowmap.ensure((sizeof(int2) + sizeof(int32_t)) * (size_t)job_rows_max, &c->mem));
-        SC_TRY(c->lee_b.ensure(sizeof(double) * (size_t)PERM_CHUNK * (size_t)pblocks, &c->mem));
+        SC_TRY(c->scratch_b.ensure(sizeof(double) * (size_t)PERM_CHUNK * (size_t)pblocks, &c->mem));
         if (L_perm_out) SC_TRY(c->lee_lperm.ensure(sizeof(double) * (size_t)job_rows_max, &c->mem));
-        int2 *d_slots = c->lee_rowmap.as<int2>();
-        int32_t *d_rowpair = reinterpret_cast<int32_t *>(d_slots + job_rows_max);
         for (int64_t l0 = 0; l0 < n_live; l0 += pairs_per_job) {
             const int64_t l1 = std::min(n_live, l0 + pairs_per_job), rows = (l1 - l0) * n_perm;
-            std::vector<int2> slots((size_t)rows);
-            std::vector<int32_t> rowpair((size_t)rows);
-            for (int64_t l = l0; l < l1; ++l)
-                for (int64_t p = 0; p < n_perm; ++p) {
-                    const int32_t q = live[(size_t)l];
-                    slots[(size_t)((l - l0) * n_perm + p)] = make_int2(slot_x[(size_t)pair_x[q]], slot_y[(size_t)pair_y[q]]);
-                    rowpair[(size_t)((l - l0) * n_perm + p)] = q;
-                }
-            SC_HIP(hipMemcpyAsync(d_slots, slots.data(), sizeof(int2) * (size_t)rows, hipMemcpyHostToDevice, c->stream));
-            SC_HIP(hipMemcpyAsync(d_rowpair, rowpair.data(), sizeof(int32_t) * (size_t)rows, hipMemcpyHostToDevice, c->stream));
-            SC_HIP(hipStreamSynchronize(c->stream));
             auto score = [&](int64_t p0, int64_t p1) -> int {
                 const int cnt = (int)(p1 - p0);
                 {
                     KernelTimerScope ts(c, SC_K_LEE_PERM);
-                    hipLaunchKernelGGL(k_lee_rows, dim3((unsigned)pblocks, (unsigned)cnt), dim3(256), 0, c->stream,
+                    hipLaunchKernelGGL(k_lee_rows<true>, dim3((unsigned)pblocks, (unsigned)cnt), dim3(256), 0, c->stream,
                                        c->lee_Uc.as<double>(), c->lee_Zc.as<double>(), n,
-                                       c->perm.as<int32_t>() + p0 * c->p_stride, c->p_stride, d_slots + p0,
-                                       c->lee_b.as<double>());
+                                       c->perm.as<int32_t>() + p0 * c->p_stride, c->p_stride, d_slots + l0, (unsigned)p0, (unsigned)n_perm,
+                                       c->scratch_b.as<double>());
                 }
-                hipLaunchKernelGGL(k_lee_rows_count, dim3((unsigned)ceil_div64(cnt, 256)), dim3(256), 0, c->stream,
-                                   c->lee_b.as<double>(), pblocks, cnt, d_rowpair + p0, c->lee_obs.as<double>(),
-                                   c->lee_cnt.as<unsigned long long>(),
+                hipLaunchKernelGGL(k_lee_row_sums<true>, dim3((unsigned)ceil_div64(cnt, 256)), dim3(256), 0, c->stream,
+                                   c->scratch_b.as<double>(), pblocks, cnt, d_live + l0, (unsigned)p0, (unsigned)n_perm,
+                                   c->lee_obs.as<double>(), c->lee_cnt.as<unsigned long long>(),
                                    L_perm_out ? c->lee_lperm.as<double>() + p0 : (double *)nullptr);
                 SC_HIP(hipGetLastError());
                 return SC_OK;
             };
-            // the block-parallel scan verifies itself at the end of a job; if that fails (never seen without the fault
-            // injection mode) the sub-job's counts are rolled back and it is rerun with the sequential scan
-            SC_HIP(hipMemcpyAsync(d_cnt_backup, c->lee_cnt.p, sizeof(unsigned long long) * (size_t)n_pairs,
-                                  hipMemcpyDeviceToDevice, c->stream));
-            SC_TRY(permgen_rerun_on_failure(
-                c, [&]() { return sc_perm_pipeline(c, state6, n, rows, 0, 2, nullptr, score); },
-                [&]() -> int {
-                    SC_HIP(hipMemcpyAsync(c->lee_cnt.p, d_cnt_backup, sizeof(unsigned long long) * (size_t)n_pairs,
-                                          hipMemcpyDeviceToDevice, c->stream));
-                    return SC_OK;
-                }));
+            SC_TRY(lee_counted_pipeline(c, state6, rows, n_pairs, score));
             if (L_perm_out) {
                 std::vector<double> lp((size_t)rows);
                 SC_HIP(hipMemcpy(lp.data(), c->lee_lperm.p, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost));
@@ -269,223 +322,14 @@ extern "C" int sc_lee_seeded(sc_ctx *c, uint64_t *state6, const int32_t *pair_x,
             }
         }
     }
-    // ---- results ----
-    std::vector<unsigned long long> cnt((size_t)n_pairs);
-    SC_HIP(hipMemcpyAsync(L_out, c->lee_obs.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(cnt.data(), c->lee_cnt.p, sizeof(unsigned long long) * (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
+    SC_TRY(lee_download(c, n_pairs, L_out, count_abs_ge_out));
     for (int64_t q = 0; q < n_pairs; ++q) {
-        const bool dead = pair_tp[(size_t)q] < 0;
-        if (dead) L_out[q] = 0.0;
-        count_abs_ge_out[q] = dead ? n_perm : (int64_t)cnt[(size_t)q];
-        if (dead && L_perm_out)
+        if (pair_tp[(size_t)q] >= 0) continue;   // a zero-variance pair: L = 0, every L_perm = 0, p = 1
+        L_out[q] = 0.0;
+        count_abs_ge_out[q] = n_perm;
+        if (L_perm_out)
             for (int64_t p = 0; p < n_perm; ++p) L_perm_out[q * n_perm + p] = 0.0;
     }
-    return SC_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Float32-faithful observed L.  For a float32 matrix the reference computes everything in float32 with numpy's
-// summation order (AC:1118-1146, 307-315): mean = S(x) / n, std = sqrt(S(d * d) / n) with d = x - mean, z = d / std,
-// lag = W32 @ z_y (scipy csr_matvec: row-sequential, multiply and add rounded separately), L = float(S(z_x * lag)),
-// where S is numpy's sum of a contiguous float32 vector: the vector is cut into chunks of 8192 elements (the ufunc
-// buffer size), every chunk is summed PAIRWISE (blocks of <= 128 with 8 strided accumulators, halving above that with
-// the split rounded down to a multiple of 8) and the chunk sums are accumulated in order (numpy 2.2, verified against
-// numpy itself up to 10^6 elements).  A sum of 10^6 signed float32 terms carries ~1e-5 relative rounding noise, so an
-// fp64 L differs from the reference's by that much; to hand back the reference's OWN number the same tree is
-// evaluated here with the same float roundings -- in parallel: the tree's shape depends on n alone, so one thread sums
-// one leaf and one thread per vector replays the recursion over the leaf sums (sc_pairwise.h).  The permutation
-// statistics stay fp64 (the p-values of the reference's goldens are reproduced exactly that way).
-// ------------------------------------------------------------------------------------------------
-
-#include "sc_pairwise.h"
-
-#define NP_SUM_CHUNK 8192u   // numpy's ufunc buffer size in elements
-
-// leaves[i] = (start, len) of the i-th leaf of numpy's sum over m elements (chunk after chunk); *nleaves
-__global__ void k32_leaves(uint32_t m, uint2 *__restrict__ leaves, uint32_t max_leaves, uint32_t *__restrict__ nleaves)
-{
-    uint32_t k = 0;
-    for (uint32_t c0 = 0; c0 < m; c0 += NP_SUM_CHUNK) {
-        const uint32_t len_c = m - c0 < NP_SUM_CHUNK ? m - c0 : NP_SUM_CHUNK;
-        (void)pw_walk<float>(len_c, [&](uint32_t start, uint32_t len) {
-            if (k < max_leaves) leaves[k] = make_uint2(c0 + start, len);
-            ++k;
-            return 0.f;
-        });
-    }
-    *nleaves = k;
-}
-
-// numpy's sum of m float32 terms from the leaf sums `ls` (in leaf order): chunk sums accumulated in order
-__device__ __forceinline__ float np_sum_from_leaves(uint32_t m, const float *__restrict__ ls)
-{
-    uint32_t i = 0;
-    float acc = 0.f;
-    for (uint32_t c0 = 0; c0 < m; c0 += NP_SUM_CHUNK) {
-        const uint32_t len_c = m - c0 < NP_SUM_CHUNK ? m - c0 : NP_SUM_CHUNK;
-        const float part = pw_walk<float>(len_c, [&](uint32_t, uint32_t) { return ls[i++]; });
-        acc = c0 == 0 ? part : __fadd_rn(acc, part);
-    }
-    return acc;
-}
-
-// STAT 0: leaf sums of x over cells start ..; STAT 1: of fl(d * d), d = fl(x - mean).  thread = (leaf, gene)
-template <int STAT>
-__global__ __launch_bounds__(256) void k32_gene_leafsum(const double *__restrict__ X, int64_t n,
-                                                        const int32_t *__restrict__ genes,
-                                                        const float *__restrict__ mean32, const uint2 *__restrict__ leaves,
-                                                        uint32_t nleaves, float *__restrict__ leafsum)
-{
-    const uint32_t leaf = blockIdx.x * blockDim.x + threadIdx.x;
-    if (leaf >= nleaves) return;
-    const int32_t g = genes[blockIdx.y];
-    const double *col = X + (int64_t)(g >> 4) * n * SC_TILE + (g & 15);
-    const uint2 lf = leaves[leaf];
-    const float mu = STAT ? mean32[blockIdx.y] : 0.f;
-    leafsum[(int64_t)blockIdx.y * nleaves + leaf] = pw_block<float>(lf.y, [&](uint32_t k) {
-        const float x = (float)col[(int64_t)(lf.x + k) * SC_TILE];
-        if (!STAT) return x;
-        const float d = __fsub_rn(x, mu);
-        return __fmul_rn(d, d);
-    });
-}
-
-// STAT 0: mean32[k] = S(x) / n;  STAT 1: sd32[k] = sqrt(S(d * d) / n)   (IEEE float division / sqrt)
-template <int STAT>
-__global__ void k32_gene_combine(int64_t n, int n_genes, const float *__restrict__ leafsum, uint32_t nleaves,
-                                 float *__restrict__ out)
-{
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_genes) return;
-    float res = np_sum_from_leaves((uint32_t)n, leafsum + (int64_t)k * nleaves);
-    res = (float)__ddiv_rn((double)res, (double)(float)n);   // correctly rounded float division (53 >= 2 * 24 + 2)
-    out[k] = STAT ? (float)__dsqrt_rn((double)res) : res;
-}
-
-// z32[k][cell] = fl(fl(x - mean) / sd)
-__global__ __launch_bounds__(256) void k32_zscore(const double *__restrict__ X, int64_t n, const int32_t *__restrict__ genes,
-                                                  const float *__restrict__ mean32, const float *__restrict__ sd32,
-                                                  float *__restrict__ z32)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t g = genes[blockIdx.y];
-    const float x = (float)X[(int64_t)(g >> 4) * n * SC_TILE + i * SC_TILE + (g & 15)];
-    z32[(int64_t)blockIdx.y * n + i] = (float)__ddiv_rn((double)__fsub_rn(x, mean32[blockIdx.y]), (double)sd32[blockIdx.y]);
-}
-
-// lag32[k][i] = scipy's float32 csr_matvec row i of W32 @ z32[k]
-__global__ __launch_bounds__(256) void k32_lag(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
-                                               const double *__restrict__ w, const float *__restrict__ z32, int64_t n,
-                                               float *__restrict__ lag32)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float *z = z32 + (int64_t)blockIdx.y * n;
-    float s = 0.f;
-    for (int64_t e = indptr[i]; e < indptr[i + 1]; ++e) s = __fadd_rn(s, __fmul_rn((float)w[e], z[indices[e]]));
-    lag32[(int64_t)blockIdx.y * n + i] = s;
-}
-
-// leaf sums of p = fl(zx * lag_y) over cells start ..   thread = (leaf, pair)
-__global__ __launch_bounds__(256) void k32_pair_leafsum(const float *__restrict__ z32, const float *__restrict__ lag32,
-                                                        int64_t n, const int2 *__restrict__ pair_slots,
-                                                        const uint2 *__restrict__ leaves, uint32_t nleaves,
-                                                        float *__restrict__ leafsum)
-{
-    const uint32_t leaf = blockIdx.x * blockDim.x + threadIdx.x;
-    if (leaf >= nleaves) return;
-    const int2 sl = pair_slots[blockIdx.y];
-    if (sl.x < 0) return;
-    const float *zx = z32 + (int64_t)sl.x * n, *ly = lag32 + (int64_t)sl.y * n;
-    const uint2 lf = leaves[leaf];
-    leafsum[(int64_t)blockIdx.y * nleaves + leaf] =
-        pw_block<float>(lf.y, [&](uint32_t k) { return __fmul_rn(zx[lf.x + k], ly[lf.x + k]); });
-}
-
-__global__ void k32_pair_combine(int64_t n, const int2 *__restrict__ pair_slots, int64_t n_pairs,
-                                 const float *__restrict__ leafsum, uint32_t nleaves, float *__restrict__ out)
-{
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= n_pairs) return;
-    out[q] = pair_slots[q].x < 0 ? 0.f : np_sum_from_leaves((uint32_t)n, leafsum + q * nleaves);
-}
-
-extern "C" int sc_lee_observed_f32(sc_ctx *c, const int32_t *pair_x, const int32_t *pair_y, int64_t n_pairs,
-                                   float *L32_out, float *mean32_out, float *sd32_out)
-{
-    SC_REQUIRE(c && pair_x && pair_y && L32_out, SC_ERR_INVALID, "sc_lee_observed_f32: null pointer");
-    SC_HIP(hipSetDevice(c->device));
-    SC_REQUIRE(c->e_n > 0 && c->g_n == c->e_n, SC_ERR_STATE, "sc_lee_observed_f32: expression / graph missing");
-    SC_REQUIRE(c->e_dtype == SC_F32, SC_ERR_STATE, "sc_lee_observed_f32: the loaded matrix is not float32");
-    const int64_t n = c->e_n, G = c->e_genes;
-    SC_REQUIRE(n < ((int64_t)1 << 31), SC_ERR_INVALID, "sc_lee_observed_f32: too many cells");
-    if (n_pairs == 0) return SC_OK;
-    // distinct genes of the pair list (first-seen order)
-    std::vector<int32_t> genes, slot((size_t)G, -1);
-    for (int64_t q = 0; q < n_pairs; ++q) {
-        SC_REQUIRE(pair_x[q] >= 0 && pair_x[q] < G && pair_y[q] >= 0 && pair_y[q] < G, SC_ERR_INVALID,
-                   "sc_lee_observed_f32: pair %lld references a gene outside the loaded set", (long long)q);
-        for (int32_t g : {pair_x[q], pair_y[q]})
-            if (slot[(size_t)g] < 0) { slot[(size_t)g] = (int32_t)genes.size(); genes.push_back(g); }
-    }
-    const int K = (int)genes.size();
-    const uint32_t m = (uint32_t)n;
-    const uint32_t max_leaves = m / 64 + 66;  // leaves hold >= 64 elements each, except in a ragged last chunk
-    // layout of one scratch buffer: [genes K i32][mean K f32][sd K f32][nleaves u32 + pad][leaves][z32 K n][lag32 K n]
-    SC_TRY(c->lee_a.ensure(sizeof(int32_t) * (size_t)K * 3 + 16 + sizeof(uint2) * (size_t)max_leaves +
-                           sizeof(float) * 2 * (size_t)K * (size_t)n, &c->mem));
-    int32_t *d_genes = c->lee_a.as<int32_t>();
-    float *d_mean = reinterpret_cast<float *>(d_genes + K), *d_sd = d_mean + K;
-    uint32_t *d_nl = reinterpret_cast<uint32_t *>(d_sd + K + (K & 1));
-    uint2 *d_leaves = reinterpret_cast<uint2 *>(d_nl + 4);
-    float *d_z = reinterpret_cast<float *>(d_leaves + max_leaves), *d_lag = d_z + (int64_t)K * n;
-    SC_HIP(hipMemcpyAsync(d_genes, genes.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k32_leaves, dim3(1), dim3(1), 0, c->stream, m, d_leaves, max_leaves, d_nl);
-    uint32_t nleaves = 0;
-    SC_HIP(hipMemcpyAsync(&nleaves, d_nl, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-    SC_REQUIRE(nleaves <= max_leaves, SC_ERR_STATE, "sc_lee_observed_f32: leaf table overflow");
-    const size_t ls_elems = (size_t)std::max<int64_t>(K, n_pairs) * (size_t)(nleaves ? nleaves : 1);
-    SC_TRY(c->lee_b.ensure(sizeof(float) * ls_elems, &c->mem));
-    float *d_ls = c->lee_b.as<float>();
-    const dim3 lgrid((unsigned)ceil_div64(nleaves ? nleaves : 1, 256), (unsigned)K), cgrid((unsigned)ceil_div64(n, 256), (unsigned)K);
-    const double *X = c->X.as<double>();
-    if (nleaves) hipLaunchKernelGGL(k32_gene_leafsum<0>, lgrid, dim3(256), 0, c->stream, X, n, d_genes, d_mean, d_leaves, nleaves, d_ls);
-    hipLaunchKernelGGL(k32_gene_combine<0>, dim3((unsigned)ceil_div64(K, 64)), dim3(64), 0, c->stream, n, K, d_ls, nleaves, d_mean);
-    if (nleaves) hipLaunchKernelGGL(k32_gene_leafsum<1>, lgrid, dim3(256), 0, c->stream, X, n, d_genes, d_mean, d_leaves, nleaves, d_ls);
-    hipLaunchKernelGGL(k32_gene_combine<1>, dim3((unsigned)ceil_div64(K, 64)), dim3(64), 0, c->stream, n, K, d_ls, nleaves, d_sd);
-    hipLaunchKernelGGL(k32_zscore, cgrid, dim3(256), 0, c->stream, X, n, d_genes, d_mean, d_sd, d_z);
-    hipLaunchKernelGGL(k32_lag, cgrid, dim3(256), 0, c->stream, c->g_indptr.as<int64_t>(), c->g_indices.as<int32_t>(),
-                       c->g_data.as<double>(), d_z, n, d_lag);
-    SC_HIP(hipGetLastError());
-    // pairs: (slot of x, slot of y), or (-1, -1) when a gene has zero float32 variance (AC:1129: x_std == 0)
-    std::vector<float> sd((size_t)K), mean((size_t)K);
-    SC_HIP(hipMemcpyAsync(sd.data(), d_sd, sizeof(float) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(mean.data(), d_mean, sizeof(float) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-    std::vector<int2> ps((size_t)n_pairs);
-    for (int64_t q = 0; q < n_pairs; ++q) {
-        const int sx = slot[(size_t)pair_x[q]], sy = slot[(size_t)pair_y[q]];
-        ps[(size_t)q] = (sd[(size_t)sx] == 0.f || sd[(size_t)sy] == 0.f) ? make_int2(-1, -1) : make_int2(sx, sy);
-        if (mean32_out) { mean32_out[2 * q] = mean[(size_t)sx]; mean32_out[2 * q + 1] = mean[(size_t)sy]; }
-        if (sd32_out) { sd32_out[2 * q] = sd[(size_t)sx]; sd32_out[2 * q + 1] = sd[(size_t)sy]; }
-    }
-    SC_TRY(c->lee_rowmap.ensure(sizeof(int2) * (size_t)n_pairs + sizeof(float) * (size_t)n_pairs, &c->mem));
-    int2 *d_ps = c->lee_rowmap.as<int2>();
-    float *d_out = reinterpret_cast<float *>(d_ps + n_pairs);
-    SC_HIP(hipMemcpyAsync(d_ps, ps.data(), sizeof(int2) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
-    for (int64_t q0 = 0; nleaves && q0 < n_pairs; q0 += 32768) {   // gridDim.y limit
-        const int64_t qn = std::min<int64_t>(32768, n_pairs - q0);
-        hipLaunchKernelGGL(k32_pair_leafsum, dim3((unsigned)ceil_div64(nleaves, 256), (unsigned)qn), dim3(256), 0, c->stream,
-                           d_z, d_lag, n, d_ps + q0, d_leaves, nleaves, d_ls + q0 * nleaves);
-    }
-    hipLaunchKernelGGL(k32_pair_combine, dim3((unsigned)ceil_div64(n_pairs, 64)), dim3(64), 0, c->stream, n, d_ps, n_pairs,
-                       d_ls, nleaves, d_out);
-    SC_HIP(hipGetLastError());
-    SC_HIP(hipMemcpyAsync(L32_out, d_out, sizeof(float) * (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
     return SC_OK;
 }
 
@@ -590,24 +434,19 @@ extern "C" int sc_lee_shared(sc_ctx *c, uint64_t *state6, const int32_t *genes_x
     // state6 == NULL: the shared block is rows [0, n_perm) of the RESIDENT table (e.g. sc_perm_generate_counter's)
     SC_REQUIRE(n_perm == 0 || state6 || (c->p_count >= n_perm && c->p_n == c->e_n), SC_ERR_STATE,
                "sc_lee_shared: no generator state and no resident table of %lld rows", (long long)n_perm);
-    const int64_t n = c->e_n, T = c->e_tiles, G = c->e_genes;
-    for (int k = 0; k < n_x; ++k) SC_REQUIRE(genes_x[k] >= 0 && genes_x[k] < G, SC_ERR_INVALID, "sc_lee_shared: x gene out of range");
-    for (int k = 0; k < n_y; ++k) SC_REQUIRE(genes_y[k] >= 0 && genes_y[k] < G, SC_ERR_INVALID, "sc_lee_shared: y gene out of range");
+    const int64_t n = c->e_n;
+    SC_TRY(lee_check_genes(c, "sc_lee_shared", "%s: x gene out of range", genes_x, nullptr, n_x));
+    SC_TRY(lee_check_genes(c, "sc_lee_shared", "%s: y gene out of range", genes_y, nullptr, n_y));
     const size_t tile_bytes = (size_t)n * SC_TILE * sizeof(double);
     const int XT = (n_x + 15) / 16, YT = (n_y + 15) / 16;
     const int64_t per = (int64_t)n_x * n_y;
     // z-scores (zero-variance genes -> 0: their L and every L_perm are 0, count = n_perm, p = 1), lag, U
-    SC_TRY(sc_expr_zscores(c));
-    SC_TRY(c->Lag.ensure((size_t)T * tile_bytes, &c->mem));
-    SC_TRY(sc_lag_tiles(c, c->g_indptr, c->g_indices, c->g_data, c->Z.as<double>(), c->Lag.as<double>()));
-    SC_TRY(sc_graph_ensure_transpose(c));
-    SC_TRY(c->lee_U.ensure((size_t)T * tile_bytes, &c->mem));
-    SC_TRY(sc_lag_tiles(c, c->gt_indptr, c->gt_indices, c->gt_data, c->Z.as<double>(), c->lee_U.as<double>()));
+    SC_TRY(lee_operands(c, 2, nullptr));
     // compact tile sets: Zx (observed), Ux (permutations) over the x genes; LagY (observed), Zy (permutations) over the y genes
     SC_TRY(c->lee_Uc.ensure((size_t)(2 * XT) * tile_bytes, &c->mem));
     SC_TRY(c->lee_Zc.ensure((size_t)(2 * YT) * tile_bytes, &c->mem));
-    SC_TRY(c->lee_a.ensure(sizeof(int32_t) * (size_t)(n_x + n_y), &c->mem));
-    int32_t *d_gx = c->lee_a.as<int32_t>(), *d_gy = d_gx + n_x;
+    SC_TRY(c->scratch_a.ensure(sizeof(int32_t) * (size_t)(n_x + n_y), &c->mem));
+    int32_t *d_gx = c->scratch_a.as<int32_t>(), *d_gy = d_gx + n_x;
     SC_HIP(hipMemcpyAsync(d_gx, genes_x, sizeof(int32_t) * (size_t)n_x, hipMemcpyHostToDevice, c->stream));
     SC_HIP(hipMemcpyAsync(d_gy, genes_y, sizeof(int32_t) * (size_t)n_y, hipMemcpyHostToDevice, c->stream));
     double *Zx = c->lee_Uc.as<double>(), *Ux = Zx + (size_t)XT * n * SC_TILE;
@@ -617,42 +456,23 @@ extern "C" int sc_lee_shared(sc_ctx *c, uint64_t *state6, const int32_t *genes_x
     hipLaunchKernelGGL(k_repack_tiles, dim3(gcell, (unsigned)XT), dim3(256), 0, c->stream, c->lee_U.as<double>(), n, d_gx, (int)n_x, Ux);
     hipLaunchKernelGGL(k_repack_tiles, dim3(gcell, (unsigned)YT), dim3(256), 0, c->stream, c->Lag.as<double>(), n, d_gy, (int)n_y, LagY);
     hipLaunchKernelGGL(k_repack_tiles, dim3(gcell, (unsigned)YT), dim3(256), 0, c->stream, c->Z.as<double>(), n, d_gy, (int)n_y, Zy);
-    // observed grid: the identity "permutation" through the same contraction kernel shape (k_lee_observed_mfma)
+    // observed grid: every tile pair of the compact sets; pair (x, y) of the grid reads tile pair (x >> 4) * YT + (y >> 4)
     std::vector<int2> tps;
     for (int a = 0; a < XT; ++a) for (int b = 0; b < YT; ++b) tps.push_back(make_int2(a, b));
-    const int oblocks = (int)ceil_div64(n, LEE_OBS_CELLS);
-    SC_TRY(c->lee_pairs.ensure(sizeof(int2) * tps.size(), &c->mem));
-    SC_HIP(hipMemcpyAsync(c->lee_pairs.p, tps.data(), sizeof(int2) * tps.size(), hipMemcpyHostToDevice, c->stream));
+    std::vector<int32_t> tp((size_t)per), px((size_t)per), py((size_t)per);
+    for (int x = 0; x < n_x; ++x)
+        for (int y = 0; y < n_y; ++y) {
+            tp[(size_t)x * n_y + y] = (x >> 4) * YT + (y >> 4);
+            px[(size_t)x * n_y + y] = x;
+            py[(size_t)x * n_y + y] = y;
+        }
+    // (c->lee_part holds the observed partials, then a chunk's: sized for both before the first kernel writes it)
     const int sblocks = (int)ceil_div64(n, LEE_SH_CELLS);
     const int64_t chunk_max = n_perm < PERM_CHUNK ? (n_perm > 0 ? n_perm : 1) : PERM_CHUNK;
-    const size_t part_obs = tps.size() * (size_t)oblocks * 256, part_perm = (size_t)chunk_max * YT * XT * sblocks * 256;
+    const size_t part_obs = tps.size() * (size_t)ceil_div64(n, LEE_OBS_CELLS) * 256, part_perm = (size_t)chunk_max * YT * XT * sblocks * 256;
     SC_TRY(c->lee_part.ensure(sizeof(double) * std::max(part_obs, part_perm), &c->mem));
-    SC_TRY(c->lee_obs.ensure(sizeof(double) * (size_t)per, &c->mem));
-    SC_TRY(c->lee_cnt.ensure(sizeof(unsigned long long) * (size_t)per * 2, &c->mem));
-    unsigned long long *d_cnt_backup = c->lee_cnt.as<unsigned long long>() + per;
-    SC_HIP(hipMemsetAsync(c->lee_cnt.p, 0, sizeof(unsigned long long) * (size_t)per, c->stream));
-    hipLaunchKernelGGL(k_lee_observed_mfma, dim3((unsigned)oblocks, (unsigned)tps.size()), dim3(256), 0, c->stream, Zx, LagY, n,
-                       c->lee_pairs.as<int2>(), c->lee_part.as<double>());
-    // pick: obs[x][y] from tile pair (x >> 4) * YT + (y >> 4): reuse k_lee_shared_count's addressing with one "permutation"
-    // whose partial layout is [yt][xt] -- the observed kernel wrote [tile pair = xt * YT + yt]; a tiny dedicated pick instead:
-    {
-        std::vector<int32_t> tp((size_t)per), px((size_t)per), py((size_t)per);
-        for (int x = 0; x < n_x; ++x)
-            for (int y = 0; y < n_y; ++y) {
-                tp[(size_t)x * n_y + y] = (x >> 4) * YT + (y >> 4);
-                px[(size_t)x * n_y + y] = x;
-                py[(size_t)x * n_y + y] = y;
-            }
-        SC_TRY(c->lee_rowmap.ensure(sizeof(int32_t) * 3 * (size_t)per, &c->mem));
-        int32_t *d_tp = c->lee_rowmap.as<int32_t>();
-        SC_HIP(hipMemcpyAsync(d_tp, tp.data(), sizeof(int32_t) * (size_t)per, hipMemcpyHostToDevice, c->stream));
-        SC_HIP(hipMemcpyAsync(d_tp + per, px.data(), sizeof(int32_t) * (size_t)per, hipMemcpyHostToDevice, c->stream));
-        SC_HIP(hipMemcpyAsync(d_tp + 2 * per, py.data(), sizeof(int32_t) * (size_t)per, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_lee_observed_pick, dim3((unsigned)ceil_div64(per, 256)), dim3(256), 0, c->stream,
-                           c->lee_part.as<double>(), oblocks, d_tp, d_tp + per, d_tp + 2 * per, per, c->lee_obs.as<double>());
-        SC_HIP(hipGetLastError());
-        SC_HIP(hipStreamSynchronize(c->stream));   // host vectors
-    }
+    SC_TRY(lee_observed(c, Zx, LagY, tps, tp.data(), px.data(), py.data(), per));
+    SC_HIP(hipStreamSynchronize(c->stream));   // the index arrays are host vectors
     if (n_perm > 0) {
         if (L_perm_out) SC_TRY(c->lee_lperm.ensure(sizeof(double) * (size_t)per * (size_t)n_perm, &c->mem));
         auto score = [&](int64_t p0, int64_t p1) -> int {
@@ -674,86 +494,77 @@ extern "C" int sc_lee_shared(sc_ctx *c, uint64_t *state6, const int32_t *genes_x
         if (!state6) {   // the resident table, chunk by chunk
             SC_TRY(sc_perm_forward_ensure(c));
             for (int64_t p0 = 0; p0 < n_perm; p0 += PERM_CHUNK) SC_TRY(score(p0, p0 + PERM_CHUNK < n_perm ? p0 + PERM_CHUNK : n_perm));
-        } else {   // a job that fails its verification is rerun with the sequential scan, its counts rolled back
-            SC_HIP(hipMemcpyAsync(d_cnt_backup, c->lee_cnt.p, sizeof(unsigned long long) * (size_t)per, hipMemcpyDeviceToDevice, c->stream));
-            SC_TRY(permgen_rerun_on_failure(
-                c, [&]() { return sc_perm_pipeline(c, state6, n, n_perm, 0, 2, nullptr, score); },
-                [&]() -> int {
-                    SC_HIP(hipMemcpyAsync(c->lee_cnt.p, d_cnt_backup, sizeof(unsigned long long) * (size_t)per, hipMemcpyDeviceToDevice, c->stream));
-                    return SC_OK;
-                }));
+        } else {
+            SC_TRY(lee_counted_pipeline(c, state6, n_perm, per, score));
         }
         if (L_perm_out)
             SC_HIP(hipMemcpyAsync(L_perm_out, c->lee_lperm.p, sizeof(double) * (size_t)per * (size_t)n_perm, hipMemcpyDeviceToHost, c->stream));
     }
-    std::vector<unsigned long long> cnt((size_t)per);
-    SC_HIP(hipMemcpyAsync(L_out, c->lee_obs.p, sizeof(double) * (size_t)per, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(cnt.data(), c->lee_cnt.p, sizeof(unsigned long long) * (size_t)per, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-    for (int64_t q = 0; q < per; ++q) count_abs_ge_out[q] = (int64_t)cnt[(size_t)q];
+    return lee_download(c, per, L_out, count_abs_ge_out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// A8: Lee's L, one pair at a time on contiguous vectors (sc_lee: the resident permutation table; sc_lee_local_seeded's
+// global statistic).  The observed L is the fma dot product of k_lee_rows, not the MFMA contraction.
+// ------------------------------------------------------------------------------------------------
+
+int lee_pair_alloc(sc_ctx *c, const int32_t *xy, int64_t n_pairs, int64_t P_max, size_t extra, LeePair &j)
+{
+    const int64_t n = j.n = c->e_n;
+    SC_TRY(c->scratch_a.ensure(sizeof(double) * ((size_t)n * 4 + extra), &c->mem));
+    j.zx = c->scratch_a.as<double>(); j.zy = j.zx + n; j.lagy = j.zx + 2 * n; j.u = j.zx + 3 * n;
+    SC_TRY(c->scratch_b.ensure(sizeof(double) * (size_t)ceil_div64(n, LEE_ROW_CELLS) * (size_t)(P_max + 1), &c->mem));   // [row][block]
+    SC_TRY(c->scratch_out.ensure(sizeof(double) * (size_t)(P_max + 1), &c->mem));
+    SC_TRY(c->lee_rowmap.ensure(sizeof(int2) + sizeof(int32_t) * 2 * (size_t)n_pairs, &c->mem));
+    j.d_slot = c->lee_rowmap.as<int2>();
+    j.d_xy = reinterpret_cast<const int32_t *>(j.d_slot + 1);
+    SC_HIP(hipMemsetAsync(c->lee_rowmap.p, 0, sizeof(int2), c->stream));
+    SC_HIP(hipMemcpyAsync(c->lee_rowmap.as<int2>() + 1, xy, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
     return SC_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// A8: Lee's L, one pair at a time (sc_lee: the resident permutation table; tests and lees_l_local's global statistic)
-// ------------------------------------------------------------------------------------------------
-
-// out[i] = T[tile(g)][i][slot(g)]  -- pull one gene out of the tiles into a contiguous vector
-__global__ __launch_bounds__(256) void k_extract_col(const double *__restrict__ T, int64_t n, int64_t g,
-                                                     double *__restrict__ out)
+// (every row of the job, the observed one at index P included, is pair 0 of the one-entry table)
+int lee_pair_prepare(sc_ctx *c, LeePair &j, int64_t q, int64_t P)
 {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = T[(g >> 4) * n * SC_TILE + i * SC_TILE + (g & 15)];
+    const int64_t n = j.n;
+    const int blocks = (int)ceil_div64(n, LEE_ROW_CELLS);
+    j.P = P;
+    lee_gene_major(c, c->Z.as<double>(), j.d_xy + 2 * q, 2, j.zx);   // z_x | z_y
+    lee_gene_major(c, c->Lag.as<double>(), j.d_xy + 2 * q + 1, 1, j.lagy);
+    hipLaunchKernelGGL(k_lee_rows<false>, dim3((unsigned)blocks), dim3(256), 0, c->stream, j.zx, j.lagy, n, (const int32_t *)nullptr,
+                       (int64_t)0, j.d_slot, (unsigned)P, (unsigned)P + 1, c->scratch_b.as<double>() + (size_t)P * blocks);
+    if (P > 0)   // u = W^T z_x: SpMV with the transposed graph on the contiguous vector
+        sc_launch_spmv_vec(c, c->gt_indptr.as<int64_t>(), c->gt_indices.as<int32_t>(), c->gt_data.as<double>(), j.zx, j.u, n);
+    SC_HIP(hipGetLastError());
+    return SC_OK;
 }
 
-#define LEE_CELLS_PER_BLOCK 8192
-
-// partial[p][blk] = sum_{j in block range} a[j] * b[perm_p[j]]   (p == n_perm: identity perm with a2)
-__global__ __launch_bounds__(256) void k_vec_gather_dot(const double *__restrict__ a,
-                                                        const double *__restrict__ b,
-                                                        const int32_t *__restrict__ perm, int64_t pstride,
-                                                        int64_t n, double *__restrict__ partial)
+int lee_pair_score(sc_ctx *c, const LeePair &j, int64_t row0, int64_t p0, int64_t p1)
 {
-    __shared__ double sh[256];
-    const int32_t *prow = perm + (int64_t)blockIdx.y * pstride;
-    int64_t j0 = (int64_t)blockIdx.x * LEE_CELLS_PER_BLOCK;
-    int64_t j1 = j0 + LEE_CELLS_PER_BLOCK < n ? j0 + LEE_CELLS_PER_BLOCK : n;
-    double acc = 0.0;
-    for (int64_t j = j0 + threadIdx.x; j < j1; j += 256) acc = fma(a[j], b[prow[j]], acc);
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = sh[0];
+    const int blocks = (int)ceil_div64(j.n, LEE_ROW_CELLS);
+    hipLaunchKernelGGL(k_lee_rows<true>, dim3((unsigned)blocks, (unsigned)(p1 - p0)), dim3(256), 0, c->stream, j.u, j.zy, j.n,
+                       c->perm.as<int32_t>() + (row0 + p0) * c->p_stride, c->p_stride, j.d_slot, (unsigned)p0, (unsigned)j.P + 1,
+                       c->scratch_b.as<double>() + (size_t)p0 * blocks);
+    SC_HIP(hipGetLastError());
+    return SC_OK;
 }
 
-__global__ __launch_bounds__(256) void k_vec_dot(const double *__restrict__ a, const double *__restrict__ b,
-                                                 int64_t n, double *__restrict__ partial)
+int lee_pair_finish(sc_ctx *c, LeePair &j, double *L, int64_t *count_abs_ge, double *L_perm)
 {
-    __shared__ double sh[256];
-    int64_t j0 = (int64_t)blockIdx.x * LEE_CELLS_PER_BLOCK;
-    int64_t j1 = j0 + LEE_CELLS_PER_BLOCK < n ? j0 + LEE_CELLS_PER_BLOCK : n;
-    double acc = 0.0;
-    for (int64_t j = j0 + threadIdx.x; j < j1; j += 256) acc = fma(a[j], b[j], acc);
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
-}
-
-// out[r] = sum_b partial[r][b]; one thread per row, ascending b
-__global__ void k_row_sum(const double *__restrict__ partial, int rows, int blocks, double *__restrict__ out)
-{
-    int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    double s = 0.0;
-    for (int b = 0; b < blocks; ++b) s += partial[(int64_t)r * blocks + b];
-    out[r] = s;
+    const int rows = (int)j.P + 1;
+    j.sums.resize((size_t)rows);
+    hipLaunchKernelGGL(k_lee_row_sums<false>, dim3((unsigned)ceil_div64(rows, 256)), dim3(256), 0, c->stream,
+                       c->scratch_b.as<double>(), (int)ceil_div64(j.n, LEE_ROW_CELLS), rows, (const int32_t *)nullptr, 0u,
+                       1u, (const double *)nullptr, (unsigned long long *)nullptr, c->scratch_out.as<double>());
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipMemcpyAsync(j.sums.data(), c->scratch_out.p, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipStreamSynchronize(c->stream));
+    *L = j.sums[(size_t)j.P];
+    int64_t cnt = 0;
+    for (int64_t p = 0; p < j.P; ++p) cnt += fabs(j.sums[(size_t)p]) >= fabs(*L) ? 1 : 0;
+    if (count_abs_ge) *count_abs_ge = cnt;
+    if (L_perm) memcpy(L_perm, j.sums.data(), sizeof(double) * (size_t)j.P);
+    return SC_OK;
 }
 
 extern "C" int sc_lee(sc_ctx *c, const int32_t *pair_x, const int32_t *pair_y, const int64_t *perm_offset,
@@ -767,306 +578,37 @@ extern "C" int sc_lee(sc_ctx *c, const int32_t *pair_x, const int32_t *pair_y, c
     SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_lee: no expression loaded");
     SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_lee: graph missing or size mismatch");
     SC_REQUIRE(n_perm == 0 || perm_offset, SC_ERR_INVALID, "sc_lee: perm_offset required when n_perm > 0");
-    const int64_t n = c->e_n, T = c->e_tiles;
-    const size_t tile_bytes = (size_t)n * SC_TILE * sizeof(double);
-    for (int64_t q = 0; q < n_pairs; ++q) {
-        SC_REQUIRE(pair_x[q] >= 0 && pair_x[q] < c->e_genes && pair_y[q] >= 0 && pair_y[q] < c->e_genes,
-                   SC_ERR_INVALID, "sc_lee: pair %lld references a gene outside the loaded set", (long long)q);
+    SC_TRY(lee_check_genes(c, "sc_lee", "%s: pair %lld references a gene outside the loaded set", pair_x, pair_y, n_pairs));
+    for (int64_t q = 0; q < n_pairs; ++q)
         if (n_perm > 0 && perm_offset[q] >= 0)
-            SC_REQUIRE(c->p_n == n && perm_offset[q] + n_perm <= c->p_count, SC_ERR_STATE,
+            SC_REQUIRE(c->p_n == c->e_n && perm_offset[q] + n_perm <= c->p_count, SC_ERR_STATE,
                        "sc_lee: pair %lld needs permutation rows [%lld, %lld) but the table has %lld",
                        (long long)q, (long long)perm_offset[q], (long long)(perm_offset[q] + n_perm),
                        (long long)c->p_count);
-    }
-    // z-scores (population sd), lag = W z, u = W^T z
-    SC_TRY(sc_expr_zscores(c));
-    SC_TRY(c->Lag.ensure((size_t)T * tile_bytes, &c->mem));
-    SC_TRY(sc_lag_tiles(c, c->g_indptr, c->g_indices, c->g_data, c->Z.as<double>(), c->Lag.as<double>()));
-    std::vector<double> var((size_t)c->e_genes);
-    SC_HIP(hipMemcpyAsync(var.data(), c->g_var.p, sizeof(double) * var.size(), hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-
-    const int blocks = (int)ceil_div64(n, LEE_CELLS_PER_BLOCK);
-    // vectors: a = z_x, la = (W z_y), u = W^T z_x (via transposed graph on the extracted column), b = z_y
-    SC_TRY(c->lee_a.ensure(sizeof(double) * (size_t)n * 4, &c->mem));
-    double *va = c->lee_a.as<double>(), *vlag = va + n, *vu = va + 2 * n, *vb = va + 3 * n;
-    SC_TRY(c->lee_b.ensure(sizeof(double) * (size_t)blocks * (size_t)(n_perm + 1), &c->mem));
-    SC_TRY(c->lee_out.ensure(sizeof(double) * (size_t)(n_perm + 1 > T * SC_TILE ? n_perm + 1 : T * SC_TILE),
-                             &c->mem));
-    if (n_perm > 0) SC_TRY(sc_graph_ensure_transpose(c));
-    std::vector<double> host((size_t)n_perm + 1);
+    std::vector<double> var;
+    SC_TRY(lee_operands(c, n_perm > 0 ? 1 : 0, &var));
+    if (n_pairs == 0) return SC_OK;
+    std::vector<int32_t> xy((size_t)(2 * n_pairs));
+    for (int64_t q = 0; q < n_pairs; ++q) { xy[(size_t)(2 * q)] = pair_x[q]; xy[(size_t)(2 * q + 1)] = pair_y[q]; }
+    LeePair j;
+    SC_TRY(lee_pair_alloc(c, xy.data(), n_pairs, n_perm, 0, j));
     for (int64_t q = 0; q < n_pairs; ++q) {
-        bool degenerate = !(var[pair_x[q]] > 0.0) || !(var[pair_y[q]] > 0.0);
-        if (degenerate) {
+        const bool live = var[(size_t)pair_x[q]] > 0.0 && var[(size_t)pair_y[q]] > 0.0;
+        const bool do_perm = live && n_perm > 0 && perm_offset[q] >= 0;
+        if (!do_perm && L_perm_out)
+            for (int64_t p = 0; p < n_perm; ++p) L_perm_out[q * n_perm + p] = 0.0;
+        if (!live) {   // a zero-variance pair: L = 0, p = 1
             L_out[q] = 0.0;
             if (count_abs_ge_out) count_abs_ge_out[q] = n_perm;
-            if (L_perm_out)
-                for (int64_t p = 0; p < n_perm; ++p) L_perm_out[q * n_perm + p] = 0.0;
             continue;
         }
-        unsigned gcol = (unsigned)ceil_div64(n, 256);
-        hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n,
-                           (int64_t)pair_x[q], va);
-        hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Lag.as<double>(), n,
-                           (int64_t)pair_y[q], vlag);
-        hipLaunchKernelGGL(k_vec_dot, dim3(blocks), dim3(256), 0, c->stream, va, vlag, n,
-                           c->lee_b.as<double>() + (size_t)n_perm * blocks);
-        bool do_perm = n_perm > 0 && perm_offset[q] >= 0;
+        SC_TRY(lee_pair_prepare(c, j, q, do_perm ? n_perm : 0));
         if (do_perm) {
-            hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n,
-                               (int64_t)pair_y[q], vb);
-            // u = W^T z_x : SpMV with the transposed graph on a single contiguous vector
-            sc_launch_spmv_vec(c, c->gt_indptr.as<int64_t>(), c->gt_indices.as<int32_t>(), c->gt_data.as<double>(),
-                               va, vu, n);
             KernelTimerScope ts(c, SC_K_LEE_PERM);
-            hipLaunchKernelGGL(k_vec_gather_dot, dim3(blocks, (unsigned)n_perm), dim3(256), 0, c->stream, vu, vb,
-                               c->perm.as<int32_t>() + perm_offset[q] * c->p_stride, c->p_stride, n,
-                               c->lee_b.as<double>());
+            SC_TRY(lee_pair_score(c, j, perm_offset[q], 0, n_perm));
         }
-        int rows = do_perm ? (int)n_perm + 1 : 1;
-        const double *src = c->lee_b.as<double>() + (do_perm ? 0 : (size_t)n_perm * blocks);
-        double *dst = c->lee_out.as<double>() + (do_perm ? 0 : n_perm);
-        hipLaunchKernelGGL(k_row_sum, dim3((unsigned)ceil_div64(rows, 256)), dim3(256), 0, c->stream, src, rows,
-                           blocks, dst);
-        SC_HIP(hipGetLastError());
-        SC_HIP(hipMemcpyAsync(host.data() + (do_perm ? 0 : n_perm), dst, sizeof(double) * (size_t)rows,
-                              hipMemcpyDeviceToHost, c->stream));
-        SC_HIP(hipStreamSynchronize(c->stream));
-        double L = host[(size_t)n_perm];
-        L_out[q] = L;
-        int64_t cnt = 0;
-        if (do_perm)
-            for (int64_t p = 0; p < n_perm; ++p) cnt += fabs(host[(size_t)p]) >= fabs(L) ? 1 : 0;
-        if (count_abs_ge_out) count_abs_ge_out[q] = do_perm ? cnt : 0;
-        if (L_perm_out)
-            for (int64_t p = 0; p < n_perm; ++p) L_perm_out[q * n_perm + p] = do_perm ? host[(size_t)p] : 0.0;
-    }
-    return SC_OK;
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// N2: Local Lee's L for one pair (AC:1394-1413): z-scores, lag = W z_y, L_local = z_x * lag, and the
-// optional per-cell permutation count  #{p : |float32(z_x[i] * (W z_y[perm_p])[i])| >= |L_local[i]|}
-// ------------------------------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256) void k_vec_mul(const double *__restrict__ a, const double *__restrict__ b,
-                                                 double *__restrict__ out, int64_t n)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = __dmul_rn(a[i], b[i]);
-}
-
-// The count in two phases per batch of permutations, in the graph's processing order (see k_lm_gather_sorted):
-// ys[p][r] = z_y[perm_p[order[r]]] once per permutation, then a LOCAL sparse product.  (A one-kernel form, r01,
-// fetched 900 GB for 999 permutations of 1M cells: 7 random 8-byte reads per cell and permutation, 128 bytes each.)
-#define LL_PERM_BATCH 16
-
-__global__ __launch_bounds__(256) void k_lee_local_gather(const double *__restrict__ zy, const int32_t *__restrict__ order,
-                                                          const int32_t *__restrict__ perm, int64_t pstride, int64_t n,
-                                                          double *__restrict__ ys)
-{
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    ys[(int64_t)blockIdx.y * n + r] = zy[perm[(int64_t)blockIdx.y * pstride + order[r]]];
-}
-
-__global__ __launch_bounds__(256) void k_lee_local_count_sorted(const long long *__restrict__ indptr,
-                                                                const int32_t *__restrict__ indices_r,
-                                                                const double *__restrict__ w, const int32_t *__restrict__ order,
-                                                                const double *__restrict__ zx,
-                                                                const double *__restrict__ ys,
-                                                                const double *__restrict__ Llocal, int n_batch,
-                                                                int32_t *__restrict__ count, int64_t n, int first)
-{
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const int64_t i = order[r];
-    const long long e0 = indptr[i], e1 = indptr[i + 1];
-    const double x = zx[i], obs = fabs(Llocal[i]);
-    double s[LL_PERM_BATCH];
-#pragma unroll
-    for (int p = 0; p < LL_PERM_BATCH; ++p) s[p] = 0.0;
-    for (long long e = e0; e < e1; ++e) {      // edge loop outside, permutations unrolled inside: independent loads in flight
-        const double ww = w[e];
-        const double *ye = ys + indices_r[e];
-#pragma unroll
-        for (int p = 0; p < LL_PERM_BATCH; ++p)
-            if (p < n_batch) s[p] = __dadd_rn(s[p], __dmul_rn(ww, ye[(int64_t)p * n]));
-    }
-    int cnt = 0;
-#pragma unroll
-    for (int p = 0; p < LL_PERM_BATCH; ++p)
-        if (p < n_batch) {
-            // the reference stores the permuted values in a float32 array before comparing (AC:1402,1408)
-            const double lp = (double)(float)__dmul_rn(x, s[p]);
-            cnt += fabs(lp) >= obs;
-        }
-    count[i] = first ? cnt : count[i] + cnt;
-}
-
-// The vectors of one local Lee job (sc_lee_local, sc_lee_local_seeded), n each
-struct LlJob { int64_t n = 0; double *zx = nullptr, *zy = nullptr, *lag = nullptr, *L = nullptr; int32_t *cnt = nullptr; };
-
-// z_x and z_y from the standardised tiles (c->Z), lag = W z_y, L_local = z_x * lag; and what the per-cell counts of
-// n_perm permutations need
-static int ll_prepare(sc_ctx *c, int32_t gene_x, int32_t gene_y, int64_t n_perm, const LlJob &j)
-{
-    const int64_t n = j.n;
-    const unsigned gcol = (unsigned)ceil_div64(n, 256);
-    hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_x, j.zx);
-    hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Z.as<double>(), n, (int64_t)gene_y, j.zy);
-    sc_launch_spmv_vec(c, c->g_indptr.as<int64_t>(), c->g_indices.as<int32_t>(), c->g_data.as<double>(), j.zy, j.lag, n);
-    hipLaunchKernelGGL(k_vec_mul, dim3(gcol), dim3(256), 0, c->stream, j.zx, j.lag, j.L, n);
-    if (n_perm > 0) {
-        SC_TRY(sc_graph_ensure_order(c));
-        SC_TRY(c->lm_ys.ensure(sizeof(double) * (size_t)LL_PERM_BATCH * (size_t)n, &c->mem));
-    }
-    SC_HIP(hipGetLastError());
-    return SC_OK;
-}
-
-// counts of permutations [p0, p1) of the job (rows row0 + p of the forward table); p0 == 0 starts the counts
-static int ll_count(sc_ctx *c, const LlJob &j, int64_t row0, int64_t p0, int64_t p1)
-{
-    const int64_t n = j.n;
-    const unsigned gcol = (unsigned)ceil_div64(n, 256);
-    for (int64_t p = p0; p < p1; p += LL_PERM_BATCH) {
-        const int nb = (int)(p1 - p < LL_PERM_BATCH ? p1 - p : LL_PERM_BATCH);
-        hipLaunchKernelGGL(k_lee_local_gather, dim3(gcol, (unsigned)nb), dim3(256), 0, c->stream, j.zy,
-                           c->g_order.as<int32_t>(), c->perm.as<int32_t>() + (row0 + p) * c->p_stride, c->p_stride,
-                           n, c->lm_ys.as<double>());
-        hipLaunchKernelGGL(k_lee_local_count_sorted, dim3(gcol), dim3(256), 0, c->stream, c->g_indptr.as<long long>(),
-                           c->g_indices_r.as<int32_t>(), c->g_data.as<double>(), c->g_order.as<int32_t>(), j.zx,
-                           c->lm_ys.as<double>(), j.L, nb, j.cnt, n, p == 0 ? 1 : 0);
-    }
-    SC_HIP(hipGetLastError());
-    return SC_OK;
-}
-
-extern "C" int sc_lee_local(sc_ctx *c, int32_t gene_x, int32_t gene_y, int64_t n_perm, int64_t perm_row0,
-                            double *zx_out, double *lag_out, double *L_local_out, int32_t *count_out)
-{
-    SC_REQUIRE(c && zx_out && lag_out && L_local_out, SC_ERR_INVALID, "sc_lee_local: null pointer");
-    SC_HIP(hipSetDevice(c->device));
-    if (n_perm > 0) SC_TRY(sc_perm_forward_ensure(c));
-    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_lee_local: no expression loaded");
-    SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_lee_local: graph missing or size mismatch");
-    SC_REQUIRE(gene_x >= 0 && gene_x < c->e_genes && gene_y >= 0 && gene_y < c->e_genes, SC_ERR_INVALID,
-               "sc_lee_local: gene index outside the loaded set");
-    if (n_perm > 0) {
-        SC_REQUIRE(count_out, SC_ERR_INVALID, "sc_lee_local: count_out required when n_perm > 0");
-        SC_REQUIRE(c->p_n == c->e_n && perm_row0 >= 0 && perm_row0 + n_perm <= c->p_count, SC_ERR_STATE,
-                   "sc_lee_local: needs permutation rows [%lld, %lld)", (long long)perm_row0,
-                   (long long)(perm_row0 + n_perm));
-    }
-    const int64_t n = c->e_n;
-    SC_TRY(sc_expr_zscores(c));
-    SC_TRY(c->lee_a.ensure(sizeof(double) * (size_t)n * 5, &c->mem));
-    LlJob j;
-    j.n = n; j.zx = c->lee_a.as<double>(); j.zy = j.zx + n; j.lag = j.zx + 2 * n; j.L = j.zx + 3 * n;
-    j.cnt = reinterpret_cast<int32_t *>(j.zx + 4 * n);
-    SC_TRY(ll_prepare(c, gene_x, gene_y, n_perm, j));
-    if (n_perm > 0) {
-        KernelTimerScope ts(c, SC_K_LEE_PERM);
-        SC_TRY(ll_count(c, j, perm_row0, 0, n_perm));
-    }
-    SC_HIP(hipMemcpyAsync(zx_out, j.zx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(lag_out, j.lag, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(L_local_out, j.L, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (n_perm > 0)
-        SC_HIP(hipMemcpyAsync(count_out, j.cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-    return SC_OK;
-}
-
-// r04: the pair body of lees_l_local as ONE pipeline (r03's verdict: a generator call and two device calls per pair, each
-// waiting for the one before).  Equal to
-//     sc_perm_generate(state6, n, n_perm_global + n_perm_local);  sc_lee(x, y, offset 0, n_perm_global);
-//     sc_lee_local(x, y, n_perm_local, perm_row0 = n_perm_global)
-// -- the same kernels on the same rows, results bit for bit, the generator state advanced by the same draws -- with the
-// permuted sums of the global statistic and the per-cell counts taken chunk by chunk behind the generator (which is 85 % of
-// the three calls' time at 10^6 cells), like sc_local_moran_seeded.
-// (sc_lee's pair body is written out again here, not shared: there one gather-dot launch covers all rows and the sums
-// come back per pair; here the rows arrive chunk by chunk between the local job's launches and z_x, z_y are the local
-// job's vectors -- one body for both would branch on its caller.)
-extern "C" int sc_lee_local_seeded(sc_ctx *c, uint64_t *state6, int32_t gene_x, int32_t gene_y, int64_t n_perm_global,
-                                   int64_t n_perm_local, double *L_out, int64_t *count_abs_ge_out, double *zx_out,
-                                   double *lag_out, double *L_local_out, int32_t *count_out)
-{
-    SC_REQUIRE(c && state6 && L_out && zx_out && lag_out && L_local_out, SC_ERR_INVALID, "sc_lee_local_seeded: null pointer");
-    SC_REQUIRE(n_perm_global >= 0 && n_perm_local >= 0 && n_perm_global + n_perm_local >= 1 &&
-               n_perm_global + n_perm_local <= (1 << 24), SC_ERR_INVALID, "sc_lee_local_seeded: permutation counts out of range");
-    SC_REQUIRE(n_perm_local == 0 || count_out, SC_ERR_INVALID, "sc_lee_local_seeded: count_out required when n_perm_local > 0");
-    SC_REQUIRE(n_perm_global == 0 || count_abs_ge_out, SC_ERR_INVALID, "sc_lee_local_seeded: count_abs_ge_out required when n_perm_global > 0");
-    SC_HIP(hipSetDevice(c->device));
-    SC_REQUIRE(c->e_n > 0, SC_ERR_STATE, "sc_lee_local_seeded: no expression loaded");
-    SC_REQUIRE(c->g_n == c->e_n, SC_ERR_STATE, "sc_lee_local_seeded: graph missing or size mismatch");
-    SC_REQUIRE(gene_x >= 0 && gene_x < c->e_genes && gene_y >= 0 && gene_y < c->e_genes, SC_ERR_INVALID,
-               "sc_lee_local_seeded: gene index outside the loaded set");
-    const int64_t n = c->e_n, T = c->e_tiles, Pg = n_perm_global, Pl = n_perm_local;
-    const int blocks = (int)ceil_div64(n, LEE_CELLS_PER_BLOCK);
-    const unsigned gcol = (unsigned)ceil_div64(n, 256);
-    double *vlag_g = nullptr, *vu = nullptr;
-    LlJob j;   // (z_x, z_y: sc_lee's operands too)
-    auto prepare = [&]() -> int {
-        // ---- sc_lee's operands: z-scores (population sd), Lag = W Z, u = W^T z_x ----
-        SC_TRY(sc_expr_zscores(c));
-        SC_TRY(c->Lag.ensure((size_t)T * (size_t)n * SC_TILE * sizeof(double), &c->mem));
-        SC_TRY(sc_lag_tiles(c, c->g_indptr, c->g_indices, c->g_data, c->Z.as<double>(), c->Lag.as<double>()));
-        double var[2];
-        SC_HIP(hipMemcpyAsync(&var[0], c->g_var.as<double>() + gene_x, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        SC_HIP(hipMemcpyAsync(&var[1], c->g_var.as<double>() + gene_y, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        SC_HIP(hipStreamSynchronize(c->stream));
-        SC_REQUIRE(var[0] > 0.0 && var[1] > 0.0, SC_ERR_INVALID, "sc_lee_local_seeded: a gene of the pair has zero variance");
-        SC_TRY(c->lee_a.ensure(sizeof(double) * (size_t)n * 8, &c->mem));
-        j.n = n; j.zx = c->lee_a.as<double>(); vlag_g = j.zx + n; vu = j.zx + 2 * n; j.zy = j.zx + 3 * n;
-        j.lag = j.zx + 4 * n; j.L = j.zx + 5 * n;
-        j.cnt = reinterpret_cast<int32_t *>(j.zx + 6 * n);
-        SC_TRY(c->lee_b.ensure(sizeof(double) * (size_t)blocks * (size_t)(Pg + 1), &c->mem));
-        SC_TRY(c->lee_out.ensure(sizeof(double) * (size_t)(Pg + 1 > T * SC_TILE ? Pg + 1 : T * SC_TILE), &c->mem));
-        if (Pg > 0) SC_TRY(sc_graph_ensure_transpose(c));
-        // ---- sc_lee_local's: z_x, z_y, lag = W z_y on the vector, L_local = z_x * lag ----
-        SC_TRY(ll_prepare(c, gene_x, gene_y, Pl, j));
-        // ---- sc_lee's: the observed sum and u = W^T z_x ----
-        hipLaunchKernelGGL(k_extract_col, dim3(gcol), dim3(256), 0, c->stream, c->Lag.as<double>(), n, (int64_t)gene_y, vlag_g);
-        hipLaunchKernelGGL(k_vec_dot, dim3(blocks), dim3(256), 0, c->stream, j.zx, vlag_g, n, c->lee_b.as<double>() + (size_t)Pg * blocks);
-        if (Pg > 0)
-            sc_launch_spmv_vec(c, c->gt_indptr.as<int64_t>(), c->gt_indices.as<int32_t>(), c->gt_data.as<double>(), j.zx, vu, n);
-        SC_HIP(hipGetLastError());
-        return SC_OK;
-    };
-    auto score = [&](int64_t p0, int64_t p1) -> int {
-        KernelTimerScope ts(c, SC_K_LEE_PERM);
-        const int64_t a1 = p1 < Pg ? p1 : Pg;
-        if (p0 < a1)   // rows of the global statistic
-            hipLaunchKernelGGL(k_vec_gather_dot, dim3(blocks, (unsigned)(a1 - p0)), dim3(256), 0, c->stream, vu, j.zy,
-                               c->perm.as<int32_t>() + p0 * c->p_stride, c->p_stride, n, c->lee_b.as<double>() + (size_t)p0 * blocks);
-        // rows of the per-cell counts: permutations [b0 - Pg, p1 - Pg) of the local job
-        const int64_t b0 = p0 > Pg ? p0 : Pg;
-        if (b0 < p1) SC_TRY(ll_count(c, j, Pg, b0 - Pg, p1 - Pg));
-        SC_HIP(hipGetLastError());
-        return SC_OK;
-    };
-    // a job that fails its verification is rerun with the sequential scan: everything restarts at permutation 0 (the
-    // first rows' flag restarts the counts)
-    SC_TRY(permgen_rerun_on_failure(c, [&]() { return sc_perm_pipeline(c, state6, n, Pg + Pl, 0, 2, prepare, score); }, nullptr));
-    std::vector<double> host((size_t)Pg + 1);
-    hipLaunchKernelGGL(k_row_sum, dim3((unsigned)ceil_div64(Pg + 1, 256)), dim3(256), 0, c->stream, c->lee_b.as<double>(),
-                       (int)(Pg + 1), blocks, c->lee_out.as<double>());
-    SC_HIP(hipGetLastError());
-    SC_HIP(hipMemcpyAsync(host.data(), c->lee_out.p, sizeof(double) * (size_t)(Pg + 1), hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(zx_out, j.zx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(lag_out, j.lag, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipMemcpyAsync(L_local_out, j.L, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (Pl > 0) SC_HIP(hipMemcpyAsync(count_out, j.cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    SC_HIP(hipStreamSynchronize(c->stream));
-    const double L = host[(size_t)Pg];
-    *L_out = L;
-    if (count_abs_ge_out) {
-        int64_t cnt = 0;
-        for (int64_t p = 0; p < Pg; ++p) cnt += fabs(host[(size_t)p]) >= fabs(L) ? 1 : 0;
-        *count_abs_ge_out = cnt;
+        SC_TRY(lee_pair_finish(c, j, L_out + q, count_abs_ge_out ? count_abs_ge_out + q : nullptr,
+                               do_perm && L_perm_out ? L_perm_out + q * n_perm : nullptr));
     }
     return SC_OK;
 }

@@ -348,7 +348,7 @@ int lm_prepare(sc_ctx *c, int64_t n_perm, LmJob &j)
     const size_t tile_f = (size_t)T * n * SC_TILE;
     // per-gene mean and E[x^2] with numpy's own summation order, in the matrix dtype (see k_npc_*)
     SC_TRY(expr_colsum(c, OP_NZ, c->X.as<double>(), nullptr, c->g_Inum.as<double>(), 1.0));
-    SC_TRY(c->lee_out.ensure(sizeof(double) * 2 * (size_t)(T * SC_TILE), &c->mem));
+    SC_TRY(c->scratch_out.ensure(sizeof(double) * 2 * (size_t)(T * SC_TILE), &c->mem));
     {
         const int64_t nblk = ceil_div64(n, NPC_CELLS), max_leaves = n / 32 + 64;
         const size_t tsz = c->e_dtype == SC_F32 ? sizeof(float) : sizeof(double);
@@ -372,7 +372,7 @@ int lm_prepare(sc_ctx *c, int64_t n_perm, LmJob &j)
                                nleaves, max_leaves, c->np_leafsum.as<float>());
             hipLaunchKernelGGL(k_npc_combine<float>, dim3((unsigned)ceil_div64(2 * G, 64)), dim3(64), 0, c->stream,
                                c->np_comp.as<float>(), n, c->g_Inum.as<double>(), c->np_leafsum.as<float>(), max_leaves, G,
-                               c->lee_out.as<float>());
+                               c->scratch_out.as<float>());
         } else {
             hipLaunchKernelGGL(k_npc_scatter<double>, gw, dim3(256), 0, c->stream, c->X.as<double>(), n, nblk,
                                c->np_cnt.as<uint32_t>(), c->np_comp.as<double>());
@@ -380,7 +380,7 @@ int lm_prepare(sc_ctx *c, int64_t n_perm, LmJob &j)
                                nleaves, max_leaves, c->np_leafsum.as<double>());
             hipLaunchKernelGGL(k_npc_combine<double>, dim3((unsigned)ceil_div64(2 * G, 64)), dim3(64), 0, c->stream,
                                c->np_comp.as<double>(), n, c->g_Inum.as<double>(), c->np_leafsum.as<double>(), max_leaves,
-                               G, c->lee_out.as<double>());
+                               G, c->scratch_out.as<double>());
         }
         SC_HIP(hipGetLastError());
     }
@@ -395,10 +395,10 @@ int lm_prepare(sc_ctx *c, int64_t n_perm, LmJob &j)
     unsigned char *zero = c->counts.as<unsigned char>();
     if (c->e_dtype == SC_F32)
         hipLaunchKernelGGL(k_lm_stats<float>, dim3((unsigned)ceil_div64(T * SC_TILE, 256)), dim3(256), 0, c->stream,
-                           c->lee_out.as<float>(), mean32, sd32, zero, G, T * SC_TILE);
+                           c->scratch_out.as<float>(), mean32, sd32, zero, G, T * SC_TILE);
     else
         hipLaunchKernelGGL(k_lm_stats<double>, dim3((unsigned)ceil_div64(T * SC_TILE, 256)), dim3(256), 0, c->stream,
-                           c->lee_out.as<double>(), mean32, sd32, zero, G, T * SC_TILE);
+                           c->scratch_out.as<double>(), mean32, sd32, zero, G, T * SC_TILE);
     dim3 ge((unsigned)ceil_div64(n * SC_TILE, 256), (unsigned)T);
     hipLaunchKernelGGL(k_lm_standardize, ge, dim3(256), 0, c->stream, c->X.as<double>(), mean32, sd32, Z32, n);
     dim3 gc((unsigned)ceil_div64(n * 4, 256), (unsigned)T);

@@ -461,17 +461,17 @@ static int local_finish(sc_ctx *c, const LmJob &j, int stat, int star, int64_t n
     const size_t cells = (size_t)n * (size_t)G;
     const bool moran = stat == LM_STAT_MORAN;
     const bool counts = n_perm > 0 && (ge_out || le_out);
-    if (!arrays_done || counts) SC_TRY(c->lee_a.ensure(sizeof(float) * cells, &c->mem));   // (staging)
+    if (!arrays_done || counts) SC_TRY(c->scratch_a.ensure(sizeof(float) * cells, &c->mem));   // (staging)
     const unsigned gu = (unsigned)ceil_div64(n * G, 256);
     // (arrays_done: a helper thread has copied them out beside the pipeline)
-    if (!arrays_done) SC_TRY(lm_copy_arrays(j, c->lee_a.as<float>(), c->stream, false, z_out, lag_out, stat_out));
+    if (!arrays_done) SC_TRY(lm_copy_arrays(j, c->scratch_a.as<float>(), c->stream, false, z_out, lag_out, stat_out));
     if (n_perm > 0) {
         int32_t *const outs[2] = {ge_out, le_out};
         for (int h = 0; h < 2; ++h) {
             if (!outs[h]) continue;
-            hipLaunchKernelGGL(k_local_untile_field, dim3(gu), dim3(256), 0, c->stream, j.cnt, c->lee_a.as<int32_t>(), n, G,
+            hipLaunchKernelGGL(k_local_untile_field, dim3(gu), dim3(256), 0, c->stream, j.cnt, c->scratch_a.as<int32_t>(), n, G,
                                16 * h, moran ? 0xffffffffu : 0xffffu);
-            SC_HIP(hipMemcpyAsync(outs[h], c->lee_a.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+            SC_HIP(hipMemcpyAsync(outs[h], c->scratch_a.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
         }
         if (!moran)
             hipLaunchKernelGGL(k_ls_fold, dim3((unsigned)ceil_div64((int64_t)j.tile_f, 256)), dim3(256), 0, c->stream, j.cnt,
@@ -584,12 +584,12 @@ static int local_hist(sc_ctx *c, const char *family, bool moran, int64_t *hist_o
     const int P1 = (int)c->lm_perms + 1;
     const size_t tile_f = (size_t)T * n * SC_TILE;
     const int32_t *cnt = reinterpret_cast<const int32_t *>(c->Lag.as<float>() + tile_f);
-    SC_TRY(c->lee_b.ensure(sizeof(unsigned long long) * (size_t)(T * SC_TILE) * (size_t)P1, &c->mem));
-    SC_HIP(hipMemsetAsync(c->lee_b.p, 0, sizeof(unsigned long long) * (size_t)(T * SC_TILE) * (size_t)P1, c->stream));
+    SC_TRY(c->scratch_b.ensure(sizeof(unsigned long long) * (size_t)(T * SC_TILE) * (size_t)P1, &c->mem));
+    SC_HIP(hipMemsetAsync(c->scratch_b.p, 0, sizeof(unsigned long long) * (size_t)(T * SC_TILE) * (size_t)P1, c->stream));
     hipLaunchKernelGGL(k_lm_hist, dim3(256, (unsigned)T), dim3(256), 0, c->stream, cnt, n, P1,
-                       c->lee_b.as<unsigned long long>());
+                       c->scratch_b.as<unsigned long long>());
     SC_HIP(hipGetLastError());
-    SC_HIP(hipMemcpyAsync(hist_out, c->lee_b.p, sizeof(int64_t) * (size_t)G * (size_t)P1, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(hist_out, c->scratch_b.p, sizeof(int64_t) * (size_t)G * (size_t)P1, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     return SC_OK;
 }
@@ -611,11 +611,11 @@ static int local_classify(sc_ctx *c, const char *family, bool moran, const float
     const float *Z32 = c->Z.as<float>(), *S32 = Z32 + tile_f, *Lag32 = c->Lag.as<float>();
     const uint32_t *cnt = reinterpret_cast<const uint32_t *>(Lag32 + tile_f);
     // device staging: [p | p_adj | class] row-major, tables, flags
-    SC_TRY(c->lee_a.ensure(sizeof(float) * 2 * cells + cells + 64, &c->mem));
-    SC_TRY(c->lee_b.ensure(sizeof(float) * 2 * (size_t)G * (size_t)(P1 > 0 ? P1 : 1) + (size_t)G + 64, &c->mem));
-    float *d_p = c->lee_a.as<float>(), *d_pa = d_p + cells;
+    SC_TRY(c->scratch_a.ensure(sizeof(float) * 2 * cells + cells + 64, &c->mem));
+    SC_TRY(c->scratch_b.ensure(sizeof(float) * 2 * (size_t)G * (size_t)(P1 > 0 ? P1 : 1) + (size_t)G + 64, &c->mem));
+    float *d_p = c->scratch_a.as<float>(), *d_pa = d_p + cells;
     signed char *d_q = reinterpret_cast<signed char *>(d_pa + cells);
-    float *d_pt = c->lee_b.as<float>(), *d_at = d_pt + (size_t)G * (size_t)(P1 > 0 ? P1 : 1);
+    float *d_pt = c->scratch_b.as<float>(), *d_at = d_pt + (size_t)G * (size_t)(P1 > 0 ? P1 : 1);
     unsigned char *d_f = reinterpret_cast<unsigned char *>(d_at + (size_t)G * (size_t)(P1 > 0 ? P1 : 1));
     if (P1 > 0) {
         SC_HIP(hipMemcpyAsync(d_pt, p_tab, sizeof(float) * (size_t)G * P1, hipMemcpyHostToDevice, c->stream));

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 from scipy.sparse import csr_matrix
 
+import lee_restated as le
 from conftest import load_golden, synth
 
 pytestmark = pytest.mark.gpu
@@ -1093,6 +1094,57 @@ def test_lee_shared_permutation_grid_mfma(ctx, oracle):
     want = (np.abs(Lp) >= np.abs(L)[None]).sum(axis=0)
     np.testing.assert_array_equal(out["count_abs_ge"], want)
     assert (out["count_abs_ge"][1] == P).all() and (out["L"][1] == 0).all()      # the constant gene: p = 1
+
+
+def _lee_graph_and_genes(ctx, case):
+    ctx.knn(case["coords"], le.K, fetch=False)
+    ctx.graph_from_knn(float(np.float32(1.0) / np.float32(le.K)))
+    ctx.set_expression(case["X"], np.arange(case["X"].shape[1]))
+
+
+def _assert_lee_is_restated(out, case):
+    """The tolerances of test_lee_shared_permutation_grid_mfma; the counts exactly (no near tie: test_cpu_lee_restated.py)."""
+    np.testing.assert_allclose(out["L"], case["L"], rtol=1e-10, atol=1e-9)
+    np.testing.assert_allclose(out["L_perm"], case["L_perm"], rtol=1e-9, atol=1e-8)
+    np.testing.assert_array_equal(out["count_abs_ge"], case["count"])
+
+
+@pytest.mark.parametrize("n", le.ROW_SIZES)
+def test_lee_rows_and_observed_at_block_and_wave_edges(ctx, oracle, n):
+    """k_lee_rows / k_lee_row_sums and k_lee_observed_mfma one cell past a wavefront's range, past the 8192-cell row
+    block and past the 16384-cell observed block (a ragged MFMA quad each time): sc_lee_seeded, then sc_perm_generate +
+    sc_lee on the same stream, both against the float64 numpy restatement -- pairs in one tile, across tiles, sharing a
+    gene, and a dead one between live ones (so a live pair's index is not its position among the live)."""
+    from spatialcore_amd._lib import rng_state_words
+
+    case = le.rows_case(oracle, n)
+    _lee_graph_and_genes(ctx, case)
+    px, py, P = le.ROW_PAIRS[:, 0], le.ROW_PAIRS[:, 1], le.ROW_P
+    dead = ~case["live"]
+    w = rng_state_words(np.random.default_rng(le.ROW_SEED))
+    out = ctx.lee_seeded(w, px, py, P, return_perms=True)
+    np.testing.assert_array_equal(w, case["words"])
+    _assert_lee_is_restated(out, case)
+    assert (out["count_abs_ge"][dead] == P).all() and (out["L"][dead] == 0).all()
+    w = rng_state_words(np.random.default_rng(le.ROW_SEED))
+    ctx.generate_permutations(w, n, int(case["live"].sum()) * P)
+    np.testing.assert_array_equal(w, case["words"])
+    out = ctx.lee(px, py, case["offset"], P, return_perms=True)
+    _assert_lee_is_restated(out, case)
+    assert (out["count_abs_ge"][dead] == P).all() and (out["L"][dead] == 0).all()
+
+
+def test_lee_shared_two_x_passes(ctx, oracle):
+    """k_lee_shared_mfma with nine x tiles: a full pass of LEE_SH_XT = 8 and a pass of one ragged tile (2 genes), 17 y
+    genes (a ragged second y tile), 4099 cells (a ragged quad), against the float64 numpy restatement."""
+    from spatialcore_amd._lib import rng_state_words
+
+    case = le.grid_case(oracle)
+    _lee_graph_and_genes(ctx, case)
+    w = rng_state_words(np.random.default_rng(le.GRID_SEED))
+    out = ctx.lee_shared(w, case["gx"], case["gy"], le.GRID_P, return_perms=True)
+    np.testing.assert_array_equal(w, case["words"])
+    _assert_lee_is_restated(out, case)
 
 
 def test_profile_counts_golden(ctx):
