@@ -54,7 +54,8 @@ extern "C" {
 #define SC_K_THRESH_KS 14    /* sc_ks_argmax / sc_ks_classify: D = ECDF - Phi, its argmax, deviation scores and labels */
 #define SC_K_GMM_EM 15       /* sc_gmm_fit: the fused E-step / M-sums pass and the per-run parameter stage, all runs */
 #define SC_K_GMM_POST 16     /* sc_gmm_posterior: P(high) and labels of every cell */
-#define SC_K_COUNT_ 17
+#define SC_K_COOCCUR 17      /* sc_cooccurrence_2d: the all-pairs distance-bin histogram */
+#define SC_K_COUNT_ 18
 
 typedef struct sc_ctx sc_ctx;
 
@@ -430,6 +431,28 @@ int sc_ripley_counts(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_ty
                      int64_t *counts_out);
 int sc_ripley_counter(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_types, uint64_t seed, int64_t p_first,
                       int64_t n_perm, int64_t batch, int64_t *observed_out, int64_t *sums_out);
+
+/* ---- N9 (extension; no reference site: squidpy's co_occurrence, the third cell-type pattern statistic beside ------
+ * neighbourhood enrichment and Ripley's K) -- cell-type co-occurrence by distance: pair counts per type pair and
+ * distance bin over ALL pairs of cells, one streaming pass, no pair list (the default looks out to half the tissue's
+ * extent: 10^12 ordered pairs at 10^6 cells).
+ * Inputs: n points in 2-D (fp64) SORTED BY TYPE with offsets type_off[n_types + 1] (the convention of sc_pair_table_2d;
+ * empty types allowed, their rows and columns are zero), thresholds t_0 < t_1 < ... < t_R (fp64, finite, t_0 >= 0),
+ * n_thresholds = R + 1, 2 <= n_thresholds <= 128.
+ * Counts: for an ordered pair (i, i'), i != i', d2 = fl(fl(dx dx) + fl(dy dy)) (fp64, no FMA: the distance of every
+ * search here); the pair's bin is the smallest j with d2 <= fl(t_j t_j), the closed-ball predicate of
+ * sc_radius_count_2d and sc_ripley_build; a pair with d2 > fl(t_R t_R) is dropped.  counts_out, row-major
+ * [n_types][n_types][n_thresholds] int64: count[a][b][j] = ordered pairs of types (a, b) in bin j -- bin 0 the pairs
+ * within t_0, bins 1 .. R the annuli (t_{j-1}, t_j].  So count[a][b][j] == count[b][a][j]; the prefix sum over j,
+ * summed over a and b, is the nnz of the radius graph at t_j; coincident points (d2 == 0) are in bin 0; the table is
+ * identical from run to run and does not depend on the order of the cells (integer adds only).  The co-occurrence
+ * ratio is host arithmetic on these integers (spatialcore_amd.spatial.co_occurrence).
+ * Validated on the host before anything is enqueued (SC_ERR_INVALID with the argument in the message): null pointers,
+ * offsets that do not start at 0 or are not monotone, n_types outside 1 .. 65535, thresholds outside the above, a
+ * non-finite coordinate (with its index).  The call uses neither the bin grid nor the active graph: both, a pending
+ * radius count and a built Ripley pair list are left as they were. */
+int sc_cooccurrence_2d(sc_ctx *ctx, const double *xy, const int64_t *type_off, int32_t n_types,
+                       const double *thresholds, int32_t n_thresholds, int64_t *counts_out);
 
 /* ---- N7: spatial domains (make_spatial_domains, reference src/spatialcore/spatial/domains.py:289-732) ---------------
  * The reference hands this step to R (domains.py:579-638, r_functions.R:34-124: st_buffer, st_union, negative

@@ -24,6 +24,7 @@ K_MORAN_PERM, K_LAG, K_KNN, K_PERMGEN, K_LEE_PERM, K_PERM_SCAN, K_PERM_SWAP = 0,
 K_KMEANS_SEED, K_KMEANS_LLOYD = 7, 8
 K_RANK_EMIT, K_RANK_SORT, K_RANK_RUNS = 9, 10, 11
 K_THRESH_SCORE, K_THRESH_SORT, K_THRESH_KS, K_GMM_EM, K_GMM_POST = 12, 13, 14, 15, 16
+K_COOCCUR = 17
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
 
 # every symbol include/spatialcore_hip.h declares: (name, argtypes); restype is always int
@@ -95,6 +96,7 @@ SYMBOLS = {
     "sc_ripley_build": [_P, _P, c_int64, _P, c_int32, _P],
     "sc_ripley_counts": [_P, _P, c_int64, c_int32, c_int64, c_int64, _P],
     "sc_ripley_counter": [_P, _P, c_int64, c_int32, ctypes.c_uint64, c_int64, c_int64, c_int64, _P, _P],
+    "sc_cooccurrence_2d": [_P, _P, _P, c_int32, _P, c_int32, _P],
     "sc_domains_2d": [_P, _P, c_int64, _P, c_int64, c_double, c_double, _P, _P, _P],
     "sc_ranksum": [_P, _P, c_int64, c_int32, _P, _P, _P, _P, _P, _P],
     "sc_kmeans_fit": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P,
@@ -886,6 +888,25 @@ class Context:
         _check(self._lib.sc_ripley_counter(self._h, _ptr(lab), lab.size, int(n_types), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                            int(p_first), int(n_perm), int(batch), _ptr(obs), _ptr(sums)))
         return obs, sums
+
+    # ---- N9 (extension): co-occurrence ------------------------------------------------------
+    def cooccurrence_counts(self, coords_sorted, type_off, thresholds) -> np.ndarray:
+        """(T, T, len(thresholds)) int64 ordered pair counts by type pair and distance bin over ALL pairs of cells
+        (sc_cooccurrence_2d): the cells arrive sorted by type with offsets ``type_off`` (T + 1 entries); bin 0 holds the
+        pairs within thresholds[0], bin j the annulus (thresholds[j - 1], thresholds[j]], pairs beyond the last threshold
+        are dropped.  Leaves the bin grid, the active graph and a built Ripley pair list as they were."""
+        xy = _c(coords_sorted, np.float64)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError(f"coordinates must have shape (n, 2), got {xy.shape}")
+        off = _c(type_off, np.int64)
+        t = _c(thresholds, np.float64)
+        if off.ndim != 1 or off.size < 2 or t.ndim != 1:
+            raise ValueError("type offsets and thresholds must be 1-D, with at least one type")
+        if off[-1] != xy.shape[0]:
+            raise ValueError("type offsets do not cover the point array")
+        out = np.empty((off.size - 1, off.size - 1, t.size), dtype=np.int64)
+        _check(self._lib.sc_cooccurrence_2d(self._h, _ptr(xy), _ptr(off), off.size - 1, _ptr(t), t.size, _ptr(out)))
+        return out
 
 
 class RcclComm:

@@ -331,6 +331,9 @@ BinGrid sc_bin_grid(const sc_ctx *c);   // the bins of the last sc_bin_points, a
 int sc_window_rings(const sc_ctx *c, double radius);   // rings of bins around a point's own bin that cover its closed ball (window_walk)
 // offsets[0 .. n] = exclusive sums of counts[0 .. n] (counts[n] = 0), and *total = offsets[n]: enqueued on c->stream, the caller waits
 int sc_counts_to_offsets(sc_ctx *c, long long *counts, long long *offsets, int64_t n, long long *total);
+// the all-pairs entry points' host check (sc_pairwise_2d, sc_pair_table_2d, sc_cooccurrence_2d): SC_ERR_INVALID naming
+// the entry point, the point set and the index of the first coordinate that is not finite
+int require_finite_points(const char *who, const char *set, const double *xy, int64_t n);
 // ---- active graph (sc_graph.hip) ----
 void sc_graph_drop(sc_ctx *c);          // the active graph is gone (before its arrays are replaced or overwritten)
 int sc_graph_ensure_transpose(sc_ctx *c);

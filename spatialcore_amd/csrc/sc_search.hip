@@ -557,7 +557,7 @@ extern "C" int sc_nearest_excluding_2d(sc_ctx *c, const double *xy_targets, cons
 #define PW_BTILE 1024
 
 // (a NaN distance would be kept by `sum += d` and skipped by `d < mn`: a NaN mean beside a finite minimum)
-static int require_finite_points(const char *who, const char *set, const double *xy, int64_t n)
+int require_finite_points(const char *who, const char *set, const double *xy, int64_t n)
 {
     for (int64_t i = 0; i < n; ++i)
         SC_REQUIRE(isfinite(xy[2 * i]) && isfinite(xy[2 * i + 1]), SC_ERR_INVALID, "%s: %s coordinate %lld is not finite",

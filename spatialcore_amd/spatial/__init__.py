@@ -13,6 +13,7 @@ from spatialcore_amd.spatial.local_stats import local_gearys_c, local_getis_ord
 from spatialcore_amd.spatial.domains import get_domain_summary, make_spatial_domains
 from spatialcore_amd.spatial.markers import rank_genes_groups
 from spatialcore_amd.spatial.neighborhoods import (
+    co_occurrence,
     compute_neighborhood_profile,
     identify_niches,
     neighborhood_enrichment,
@@ -31,6 +32,7 @@ __all__ = [
     "identify_niches",
     "neighborhood_enrichment",  # extension: not in the reference
     "ripley_k",  # extension: not in the reference
+    "co_occurrence",  # extension: squidpy's function, not in the reference
     "make_spatial_domains",
     "get_domain_summary",
     "calculate_domain_distances",

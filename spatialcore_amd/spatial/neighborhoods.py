@@ -6,6 +6,8 @@ outputs (``adata.obsm[key_added]`` float32, ``adata.uns[key_added + '_celltypes'
 Neighbour search (exact kNN or closed-ball radius) and the per-cell label counting run in HIP
 kernels.  ``identify_niches`` (NB:299-522) clusters the profiles with sklearn's k-means (k-means++ seeding, Lloyd
 iterations, best of ``n_init`` runs) replayed step for step in HIP (``sc_kmeans_fit``).
+``neighborhood_enrichment``, ``ripley_k`` and ``co_occurrence`` are extensions: the three cell-type pattern statistics
+squidpy users run on an annotated section, as exact integer pair counts.
 """
 
 from __future__ import annotations
@@ -411,6 +413,176 @@ def ripley_k(
                     "permgen_form": (ctx.permgen_form(n_cells) if rng == "numpy" else "counter-based (philox)")
                                     if n_permutations > 0 else None},
         outputs={"uns": key_added, "n_celltypes": T, "n_cells": n_cells, "n_radii": R, "n_pairs": n_pairs},
+    )
+    return adata
+
+
+CO_OCCURRENCE_MAX_THRESHOLDS = 128     # sc_cooccurrence_2d's envelope
+
+
+def _interval_problem(interval) -> Optional[str]:
+    """What is wrong with ``co_occurrence``'s ``interval`` as given (an integer number of thresholds, or the thresholds
+    themselves), else None."""
+    if isinstance(interval, (bool, np.bool_)):
+        return f"interval must be an integer or a 1-D sequence of thresholds, got {interval!r}"
+    if isinstance(interval, (int, np.integer)):
+        if not 2 <= interval <= CO_OCCURRENCE_MAX_THRESHOLDS:
+            return f"interval must give 2 to {CO_OCCURRENCE_MAX_THRESHOLDS} thresholds, got {interval}"
+        return None
+    try:
+        t = np.asarray(interval, dtype=np.float64)
+    except (TypeError, ValueError):
+        return f"interval must be an integer or a 1-D sequence of thresholds, got {interval!r}"
+    if t.ndim != 1:
+        return f"interval must be an integer or a 1-D sequence of thresholds, got shape {t.shape}"
+    t = np.sort(t)
+    if not 2 <= t.size <= CO_OCCURRENCE_MAX_THRESHOLDS:
+        return f"interval must give 2 to {CO_OCCURRENCE_MAX_THRESHOLDS} thresholds, got {t.size}"
+    if not np.all(np.isfinite(t)):
+        return f"interval must be finite, got {t[~np.isfinite(t)][0]}"
+    if t[0] < 0:
+        return f"interval must be non-negative, got {t[0]}"
+    if np.any(np.diff(t) <= 0):
+        j = int(np.argmax(np.diff(t) <= 0))
+        return f"interval must be strictly increasing, got {t[j + 1]} after {t[j]}"
+    with np.errstate(over="ignore"):
+        if not np.isfinite(t[-1] * t[-1]):
+            return f"interval must have a finite square, got {t[-1]}"
+    return None
+
+
+def _co_occurrence_request_problem(adata, cluster_key, spatial_key, interval) -> Optional[str]:
+    """The first thing wrong with a ``co_occurrence`` request (checked before any device work), else None."""
+    if spatial_key not in adata.obsm:
+        return (f"adata.obsm['{spatial_key}'] not found. "
+                "Spatial coordinates are required for co-occurrence.")
+    if cluster_key not in adata.obs.columns:
+        return (f"Column '{cluster_key}' not found in adata.obs. "
+                f"Available columns: {list(adata.obs.columns)[:10]}...")
+    shape = np.shape(adata.obsm[spatial_key])
+    if len(shape) != 2 or shape[1] != 2:
+        return ("only 2-D coordinates are supported by the MI355X path "
+                f"(adata.obsm['{spatial_key}'] has shape {tuple(shape)})")
+    n_missing = int(adata.obs[cluster_key].isna().sum())
+    if n_missing:
+        return (f"{n_missing} cells have missing labels in '{cluster_key}'. "
+                "Fill or remove missing labels before computing co-occurrence.")
+    return _interval_problem(interval)
+
+
+def co_occurrence_thresholds(coords, interval) -> np.ndarray:
+    """The float64 thresholds of ``co_occurrence``.  An array ``interval`` is sorted and returned.  An integer
+    ``interval = m`` is squidpy's ``_find_min_max`` rule (restated from memory, not read): with ``s = x + y``, ``a`` and
+    ``b`` the two cells of smallest ``s`` (stable order: ties go to the lowest index) and ``c`` the first cell of largest
+    ``s``, ``t_min = dist(a, b)``, ``t_max = dist(a, c) / 2`` and the thresholds are ``np.linspace(t_min, t_max, m)`` --
+    in float64, where squidpy works in float32.  ``ValueError`` when they do not come out strictly increasing."""
+    if not isinstance(interval, (int, np.integer)):
+        return np.sort(np.asarray(interval, dtype=np.float64))
+    xy = np.asarray(coords, dtype=np.float64)
+    if xy.shape[0] < 2:
+        raise ValueError(f"interval={interval} derives the thresholds from the cells: at least 2 cells are needed, got {xy.shape[0]}")
+    s = xy[:, 0] + xy[:, 1]
+    a, b = np.argsort(s, kind="stable")[:2]
+    c = int(np.argmax(s))
+
+    def dist(p, q):
+        dx, dy = xy[p, 0] - xy[q, 0], xy[p, 1] - xy[q, 1]
+        return float(np.sqrt(dx * dx + dy * dy))
+
+    t_min, t_max = dist(a, b), dist(a, c) / 2
+    t = np.linspace(t_min, t_max, int(interval))
+    if not (np.all(np.isfinite(t)) and np.all(np.diff(t) > 0)):
+        raise ValueError(f"the thresholds derived from the cells are not strictly increasing: t_min = {t_min}, "
+                         f"t_max = {t_max}; pass interval= as an array")
+    return t
+
+
+def co_occurrence_ratio(count) -> np.ndarray:
+    """``occ`` (T, T, R) float32 from the (T, T, R + 1) integer table (pure host arithmetic, no device): for annulus
+    ``r = 1 .. R`` with ``co = count[:, :, r]``, ``occ[a, b, r - 1] = co[a, b] * co.sum() / (co[a, :].sum() *
+    co[:, b].sum())`` in float64, ``0 / 0`` giving NaN.  Bin 0, the pairs within the first threshold, has no ratio."""
+    co = np.asarray(count, dtype=np.int64)[:, :, 1:]
+    total = co.sum(axis=(0, 1)).astype(np.float64)
+    rows = co.sum(axis=1).astype(np.float64)          # [a, r] = co[a, :].sum()
+    cols = co.sum(axis=0).astype(np.float64)          # [b, r] = co[:, b].sum()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        occ = co.astype(np.float64) * total[None, None, :] / (rows[:, None, :] * cols[None, :, :])
+    return occ.astype(np.float32)
+
+
+def co_occurrence(
+    adata,
+    cluster_key: str,
+    spatial_key: str = "spatial",
+    interval=50,
+    copy: bool = False,
+    n_splits: Optional[int] = None,
+    n_jobs: Optional[int] = None,
+    backend: str = "loky",
+    show_progress_bar: bool = True,
+    *,
+    device: int = 0,
+):
+    """Cell-type co-occurrence by distance: squidpy's ``gr.co_occurrence``, every pair of cells in one pass on the GPU.
+
+    EXTENSION -- the reference has no such function; the name, the keywords and the stored key are squidpy's.
+    ``n_splits``, ``n_jobs``, ``backend`` and ``show_progress_bar`` are accepted and IGNORED: squidpy uses them to
+    split its O(N^2) CPU loop, and there is nothing to split here.
+
+    Semantics (include/spatialcore_hip.h, N9).  Thresholds ``t_0 < ... < t_R``: ``interval`` itself when it is an array
+    (sorted; finite, non-negative, strictly increasing, 2 to 128 entries), else ``co_occurrence_thresholds``' rule for
+    an integer ``interval`` (default 50 thresholds).  For an ordered pair of distinct cells
+    ``d2 = fl(fl(dx dx) + fl(dy dy))`` in fp64, its bin is the smallest ``j`` with ``d2 <= fl(t_j t_j)`` (the closed
+    ball of the radius graph and of ``ripley_k``), and a pair beyond ``t_R`` is dropped.  ``count[a, b, j]`` is the
+    number of ordered pairs of types (a, b) in bin j: bin 0 the pairs within ``t_0``, bins 1 .. R the annuli
+    ``(t_{j-1}, t_j]``.  ``occ[a, b, r - 1] = co[a, b] * co.sum() / (co[a, :].sum() * co[:, b].sum())`` with
+    ``co = count[:, :, r]``, float64 arithmetic on the integers stored as float32, NaN for ``0 / 0``: squidpy's
+    conditional-over-marginal ratio.  Two stated differences from squidpy, whose code was restated from memory and not
+    read: the coordinates and thresholds stay in float64 (squidpy casts them to float32), and the formula is the one
+    above.  The types are the categories of a categorical column, unused ones kept as all-zero rows (NaN in ``occ``),
+    else the sorted unique labels.
+
+    Stored in ``adata.uns[f"{cluster_key}_co_occurrence"]``: ``occ`` (T, T, R) float32, ``interval`` (R + 1,) float64,
+    ``count`` (T, T, R + 1) int64, ``celltypes``, ``n_per_type``.  ``copy=True`` returns ``(occ, interval)`` and writes
+    nothing to ``adata`` -- squidpy's convention, unlike this package's own functions, whose ``copy`` returns a copied
+    AnnData.  With ``copy=False`` the function returns ``adata``, as its siblings here do.
+    """
+    problem = _co_occurrence_request_problem(adata, cluster_key, spatial_key, interval)
+    if problem:
+        raise ValueError(problem)
+    labels = adata.obs[cluster_key]
+    if isinstance(labels.dtype, pd.CategoricalDtype):
+        celltypes, codes = list(labels.cat.categories), np.asarray(labels.cat.codes, dtype=np.int32)
+    else:
+        celltypes, codes = _label_codes(adata, cluster_key)
+    coords = _coordinates(adata, spatial_key)
+    thresholds = co_occurrence_thresholds(coords, interval)
+    n_cells, T, R = adata.n_obs, len(celltypes), thresholds.size - 1
+    if n_cells < 1 or T < 1:
+        raise ValueError("co_occurrence needs at least one cell")
+    logger.info(f"Computing co-occurrence: {n_cells:,} cells, {T} cell types, {R} intervals from {thresholds[0]:g} "
+                f"to {thresholds[-1]:g}")
+
+    order = np.argsort(codes, kind="stable")
+    n_per_type = np.bincount(codes, minlength=T).astype(np.int64)
+    type_off = np.concatenate([[0], np.cumsum(n_per_type)]).astype(np.int64)
+    ctx = _lib.default_context(device)
+    count = ctx.cooccurrence_counts(coords[order], type_off, thresholds)
+    occ = co_occurrence_ratio(count)
+    logger.debug(f"{int(count.sum()):,} of {n_cells * (n_cells - 1):,} ordered pairs lie within {thresholds[-1]:g}")
+    if copy:
+        return occ, thresholds
+    key_added = f"{cluster_key}_co_occurrence"
+    adata.uns[key_added] = {"occ": occ, "interval": thresholds, "count": count, "celltypes": celltypes,
+                            "n_per_type": n_per_type}
+    logger.info(f"Stored co-occurrence in adata.uns['{key_added}'] (occ shape: {occ.shape})")
+    update_metadata(
+        adata,
+        function_name="co_occurrence",
+        parameters={"cluster_key": cluster_key, "spatial_key": spatial_key,
+                    "interval": int(interval) if isinstance(interval, (int, np.integer)) else [float(t) for t in thresholds]},
+        outputs={"uns": key_added, "n_celltypes": T, "n_cells": n_cells, "n_intervals": R,
+                 "n_pairs": int(count.sum())},
     )
     return adata
 
