@@ -55,7 +55,8 @@ extern "C" {
 #define SC_K_GMM_EM 15       /* sc_gmm_fit: the fused E-step / M-sums pass and the per-run parameter stage, all runs */
 #define SC_K_GMM_POST 16     /* sc_gmm_posterior: P(high) and labels of every cell */
 #define SC_K_COOCCUR 17      /* sc_cooccurrence_2d: the all-pairs distance-bin histogram */
-#define SC_K_COUNT_ 18
+#define SC_K_LIGREC 18       /* sc_ligrec_*: expression summed by (permuted) cluster label, observed pass included */
+#define SC_K_COUNT_ 19
 
 typedef struct sc_ctx sc_ctx;
 
@@ -453,6 +454,46 @@ int sc_ripley_counter(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_t
  * radius count and a built Ripley pair list are left as they were. */
 int sc_cooccurrence_2d(sc_ctx *ctx, const double *xy, const int64_t *type_off, int32_t n_types,
                        const double *thresholds, int32_t n_thresholds, int64_t *counts_out);
+
+/* ---- N10 (extension; no reference site: squidpy's gr.ligrec, the CellPhoneDB permutation test) ----------------------
+ * Ligand-receptor test over ordered cluster pairs: for every interaction (L, R) of two loaded genes and every ordered
+ * pair of clusters (a, b), how many label permutations give a mean of L in a plus a mean of R in b at least as large as
+ * the observed one.  Exact integers, order-free.
+ * Definition, on the G genes and n cells of sc_expr_set_* and labels[i] in [0, n_types):
+ *  - gene g carries the shift s_g = shift[g]; a value x enters as the integer q = rint(x 2^s_g) (fp64 scaling by a power
+ *    of two, round half to even), which must satisfy |q| < 2^32.  The caller chooses the shifts: 0 for a gene of integer
+ *    counts in [0, 2^32) (raw counts are summed as they are), else 32 - e_g with e_g the smallest integer such that
+ *    max |x| < 2^e_g.
+ *  - S[c][g] = sum of q over the cells of cluster c (int64: n < 2^31), N[c][g] = #{cells of c with x > 0},
+ *    n_c = cells of c.  sum_out and nnz_out are [n_types][G], group_n_out is [n_types].
+ *  - A label permutation keeps every n_c.  With S_p the table under the labels labels[perm_p], the comparison
+ *    "(mean_L,a + mean_R,b) / 2 under p >= observed" is decided as
+ *        2^s_R n_b (S_p[a][L] - S[a][L]) + 2^s_L n_a (S_p[b][R] - S[b][R]) >= 0
+ *    in 128-bit integer arithmetic (both powers divided by the smaller: |s_L - s_R| <= 30 is required, SC_ERR_INVALID
+ *    naming the two genes otherwise).  count_ge_out[(i n_types + a) n_types + b] = #{p : the comparison holds} for
+ *    interaction i = (pair_l[i], pair_r[i]), indices into the loaded genes; a gene may pair with itself and appear in
+ *    any number of interactions.
+ *  The result is a function of the inputs alone: it does not depend on batching, on the genes loaded together, on the
+ *  rank count or on the run (integer adds and compares only; no floating-point atomics).  Means and p-values are host
+ *  arithmetic on these integers (spatialcore_amd.spatial.ligrec).
+ * sc_ligrec_counts: perm_p = rows [perm_row0, perm_row0 + n_perm) of the active permutation table.  null_sums_out
+ *   (nullable): S_p for every row, [n_perm][n_types][G].
+ * sc_ligrec_counter: ONE RANK'S RANGE [p_first, p_first + n_perm) of counter-based permutations
+ *   (sc_perm_generate_counter's definition), `batch` rows at a time, batch b + 1 generated on a second stream beside the
+ *   sums of batch b; ranks add their count_ge (sc_allreduce_sum_i64).  Like sc_ripley_counter it leaves no permutation
+ *   table later calls may rely on.
+ * Envelope: 1 <= n_types <= 96 (SC_ERR_INVALID beyond, limit in the message), n equal to the loaded cell count, every
+ * label in range, pair indices within the loaded genes, 1 <= n_pairs <= 2^24, at most 65534 rows per call or batch;
+ * n_perm = 0 is legal and gives the observed tables and zeros.  A value that is not finite, or whose rint(x 2^s) leaves
+ * (-2^32, 2^32), gives SC_ERR_INVALID naming the gene; no loaded expression gives SC_ERR_STATE.  The call leaves the active
+ * graph, the bin grid, a Ripley pair list and the loaded expression as they were. */
+int sc_ligrec_counts(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_types, const int32_t *shift,
+                     const int32_t *pair_l, const int32_t *pair_r, int64_t n_pairs, int64_t n_perm, int64_t perm_row0,
+                     int64_t *sum_out, int64_t *nnz_out, int64_t *group_n_out, int64_t *null_sums_out, int64_t *count_ge_out);
+int sc_ligrec_counter(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_types, const int32_t *shift,
+                      const int32_t *pair_l, const int32_t *pair_r, int64_t n_pairs, uint64_t seed, int64_t p_first,
+                      int64_t n_perm, int64_t batch, int64_t *sum_out, int64_t *nnz_out, int64_t *group_n_out,
+                      int64_t *count_ge_out);
 
 /* ---- N7: spatial domains (make_spatial_domains, reference src/spatialcore/spatial/domains.py:289-732) ---------------
  * The reference hands this step to R (domains.py:579-638, r_functions.R:34-124: st_buffer, st_union, negative

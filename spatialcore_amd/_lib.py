@@ -25,6 +25,7 @@ K_KMEANS_SEED, K_KMEANS_LLOYD = 7, 8
 K_RANK_EMIT, K_RANK_SORT, K_RANK_RUNS = 9, 10, 11
 K_THRESH_SCORE, K_THRESH_SORT, K_THRESH_KS, K_GMM_EM, K_GMM_POST = 12, 13, 14, 15, 16
 K_COOCCUR = 17
+K_LIGREC = 18
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
 
 # every symbol include/spatialcore_hip.h declares: (name, argtypes); restype is always int
@@ -97,6 +98,8 @@ SYMBOLS = {
     "sc_ripley_counts": [_P, _P, c_int64, c_int32, c_int64, c_int64, _P],
     "sc_ripley_counter": [_P, _P, c_int64, c_int32, ctypes.c_uint64, c_int64, c_int64, c_int64, _P, _P],
     "sc_cooccurrence_2d": [_P, _P, _P, c_int32, _P, c_int32, _P],
+    "sc_ligrec_counts": [_P, _P, c_int64, c_int32, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P],
+    "sc_ligrec_counter": [_P, _P, c_int64, c_int32, _P, _P, _P, c_int64, ctypes.c_uint64, c_int64, c_int64, c_int64, _P, _P, _P, _P],
     "sc_domains_2d": [_P, _P, c_int64, _P, c_int64, c_double, c_double, _P, _P, _P],
     "sc_ranksum": [_P, _P, c_int64, c_int32, _P, _P, _P, _P, _P, _P],
     "sc_kmeans_fit": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P, _P,
@@ -906,6 +909,44 @@ class Context:
             raise ValueError("type offsets do not cover the point array")
         out = np.empty((off.size - 1, off.size - 1, t.size), dtype=np.int64)
         _check(self._lib.sc_cooccurrence_2d(self._h, _ptr(xy), _ptr(off), off.size - 1, _ptr(t), t.size, _ptr(out)))
+        return out
+
+    # ---- N10 (extension): ligand-receptor permutation test ----------------------------------
+    def _ligrec_args(self, labels, n_types: int, shift, pair_l, pair_r):
+        lab, sh = _c(labels, np.int32), _c(shift, np.int32)
+        pl, pr = _c(pair_l, np.int32), _c(pair_r, np.int32)
+        G = int(getattr(self, "_n_genes", 0))
+        if lab.ndim != 1 or pl.ndim != 1 or pl.shape != pr.shape:
+            raise ValueError("labels must be 1-D and the two ends of the interactions 1-D arrays of one length")
+        if G and sh.shape != (G,):   # (without a loaded expression the library refuses the call: the arrays only have to exist)
+            raise ValueError(f"one shift per loaded gene is required: {G} genes, shift has shape {sh.shape}")
+        K, Gs = max(int(n_types), 1), max(G, 1)
+        out = {"sum": np.zeros((K, Gs), dtype=np.int64), "nnz": np.zeros((K, Gs), dtype=np.int64),
+               "group_n": np.zeros(K, dtype=np.int64), "count_ge": np.zeros((max(pl.size, 1), K, K), dtype=np.int64)}
+        return lab, sh, pl, pr, out
+
+    def ligrec_counts(self, labels, n_types: int, shift, pair_l, pair_r, n_perm: int, perm_row0: int = 0,
+                      return_null_sums: bool = False) -> dict:
+        """sc_ligrec_counts on the loaded genes: ``sum`` (K, G) int64 = the quantised expression ``rint(x * 2**shift[g])``
+        summed per cluster, ``nnz`` (K, G) = cells with x > 0, ``group_n`` (K,), ``count_ge`` (I, K, K) = permutations (rows
+        [perm_row0, perm_row0 + n_perm) of the resident table) whose ligand-in-a plus receptor-in-b mean is >= the observed
+        one, decided exactly, and on request ``null_sums`` (n_perm, K, G), the sums under every row."""
+        lab, sh, pl, pr, out = self._ligrec_args(labels, n_types, shift, pair_l, pair_r)
+        nul = np.zeros((int(n_perm),) + out["sum"].shape, dtype=np.int64) if return_null_sums else None
+        _check(self._lib.sc_ligrec_counts(self._h, _ptr(lab), lab.size, int(n_types), _ptr(sh), _ptr(pl), _ptr(pr), pl.size,
+                                          int(n_perm), int(perm_row0), _ptr(out["sum"]), _ptr(out["nnz"]), _ptr(out["group_n"]),
+                                          _ptr(nul), _ptr(out["count_ge"])))
+        out["null_sums"] = nul
+        return out
+
+    def ligrec_counter(self, labels, n_types: int, shift, pair_l, pair_r, seed: int, p_first: int, n_perm: int,
+                       batch: int = 512) -> dict:
+        """ligrec_counts over the counter-based label permutations p_first .. p_first + n_perm - 1 (sc_ligrec_counter),
+        generation overlapped with the sums; no ``null_sums``."""
+        lab, sh, pl, pr, out = self._ligrec_args(labels, n_types, shift, pair_l, pair_r)
+        _check(self._lib.sc_ligrec_counter(self._h, _ptr(lab), lab.size, int(n_types), _ptr(sh), _ptr(pl), _ptr(pr), pl.size,
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(p_first), int(n_perm), int(batch),
+                                           _ptr(out["sum"]), _ptr(out["nnz"]), _ptr(out["group_n"]), _ptr(out["count_ge"])))
         return out
 
 

@@ -12,6 +12,7 @@
 #include <hipcub/hipcub.hpp>
 #include <vector>
 
+#include "sc_labelperm.h"
 #include "sc_search.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -41,7 +42,8 @@ __global__ __launch_bounds__(256) void k_enrich_relabel(const unsigned char *__r
     else for (int k = 0; r0 + k < n; ++k) dst[r0 + k] = (unsigned char)(v >> (8 * k));
 }
 
-// lab16[g][rank[cell]] = the labels of `cell` under permutations 16 g .. 16 g + 15 (rows clamped to rows - 1)
+// lab16[g][rank[cell]] = the labels of `cell` under permutations 16 g .. 16 g + 15 (rows clamped to rows - 1); rank may be
+// null: the identity
 __global__ __launch_bounds__(256) void k_enrich_relabel16(const unsigned char *__restrict__ lab,
                                                           const int32_t *__restrict__ rank,
                                                           const int32_t *__restrict__ perm, int64_t pstride, int rows,
@@ -56,7 +58,7 @@ __global__ __launch_bounds__(256) void k_enrich_relabel16(const unsigned char *_
         const int row = 16 * g + p < rows ? 16 * g + p : rows - 1;
         w[p >> 2] |= (uint32_t)lab[perm[(int64_t)row * pstride + cell]] << (8 * (p & 3));
     }
-    lab16[(int64_t)g * n + rank[cell]] = make_uint4(w[0], w[1], w[2], w[3]);
+    lab16[(int64_t)g * n + (rank ? rank[cell] : cell)] = make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 // The integer sums of the null over a batch of n_perm tables counts[p][cells], one thread per (type pair, radius) of
@@ -88,10 +90,8 @@ __global__ __launch_bounds__(256) void k_lp_sums(const unsigned long long *__res
     if (n_rows > 3) sums[3 * cells + k] += le;
 }
 
-namespace {
+// ---- declared in sc_labelperm.h ----
 
-// the labels, checked to lie in [0, n_types), as one byte per cell into scratch_idx (waited for: the bytes are staged in a
-// local vector)
 int lp_upload_labels(sc_ctx *c, const int32_t *labels, int64_t n, int32_t n_types)
 {
     std::vector<unsigned char> lab8((size_t)n);
@@ -106,16 +106,12 @@ int lp_upload_labels(sc_ctx *c, const int32_t *labels, int64_t n, int32_t n_type
     return SC_OK;
 }
 
-// The batches of one rank's range of counter-based permutations p_first .. p_first + n_perm - 1, `batch` rows at a time
-// (the observed pass is the caller's).  Batch b's rows are generated into the permutation table on stream3; then, on
-// c->stream, relabel(rows) turns them into label words, count(rows) zeroes the per-batch table and counts the words into
-// it, and accumulate(rows) adds that table to the device sums.  The label words are the only thing the counting reads,
-// so the table is free again as soon as the relabel pass is through, and batch b + 1 is generated beside the counting
-// of batch b:
-//  * the first generation waits for c->stream (the table may still be read by an earlier call's kernels);
-//  * the generation of b + 1 waits for the relabel of b;
-//  * the counting of b waits for the generation of b.
-// Returns with both streams synchronised and every event destroyed, on every path.
+void lp_relabel_words(sc_ctx *c, int64_t n, const int32_t *rank, const int32_t *table, int rows, uint4 *lab16)
+{
+    hipLaunchKernelGGL(k_enrich_relabel16, dim3((unsigned)ceil_div64(n, 256), (unsigned)((rows + 15) / 16)), dim3(256), 0,
+                       c->stream, c->scratch_idx.as<unsigned char>(), rank, table, c->p_stride, rows, n, lab16);
+}
+
 int lp_counter_batches(sc_ctx *c, const char *who, uint64_t seed, int64_t n, int64_t p_first, int64_t n_perm, int64_t batch,
                        const std::function<void(int)> &relabel, const std::function<int(int)> &count,
                        const std::function<void(int)> &accumulate)
@@ -157,8 +153,6 @@ int lp_counter_batches(sc_ctx *c, const char *who, uint64_t seed, int64_t n, int
     if (n_perm > 0) c->p_count = 0;   // the table holds the last batch only: not a table later calls may rely on
     return SC_OK;
 }
-
-}   // namespace
 
 // ------------------------------------------------------------------------------------------------
 // N4 (extension, no reference counterpart): cell-type pair counts over the graph's edges under label
@@ -315,9 +309,7 @@ extern "C" int sc_enrichment_counter(sc_ctx *c, const int32_t *labels, int64_t n
     const int hstride = tt | 1;
     auto relabel = [&](int rows, const int32_t *table) {
         if (wide && table)
-            hipLaunchKernelGGL(k_enrich_relabel16, dim3((unsigned)ceil_div64(n, 256), (unsigned)((rows + 15) / 16)), dim3(256), 0,
-                               c->stream, c->scratch_idx.as<unsigned char>(), c->g_rank.as<int32_t>(), table, c->p_stride, rows, n,
-                               c->scratch_a.as<uint4>());
+            lp_relabel_words(c, n, c->g_rank.as<int32_t>(), table, rows, c->scratch_a.as<uint4>());
         else
             hipLaunchKernelGGL(k_enrich_relabel, dim3((unsigned)ceil_div64(n, 1024), (unsigned)rows), dim3(256), 0, c->stream,
                                c->scratch_idx.as<unsigned char>(), c->g_order.as<int32_t>(), table, c->p_stride, table ? rows : 0, n,
@@ -619,9 +611,7 @@ void rip_observed(sc_ctx *c, const RipPlan &pl, int64_t n, unsigned char *labp, 
 // `rows` rows of the permutation table -> 16-byte label words in scratch_a
 void rip_relabel_words(sc_ctx *c, int64_t n, const int32_t *table, int rows)
 {
-    hipLaunchKernelGGL(k_enrich_relabel16, dim3((unsigned)ceil_div64(n, 256), (unsigned)((rows + 15) / 16)), dim3(256), 0,
-                       c->stream, c->scratch_idx.as<unsigned char>(), c->rp_rank.as<int32_t>(), table, c->p_stride, rows, n,
-                       c->scratch_a.as<uint4>());
+    lp_relabel_words(c, n, c->rp_rank.as<int32_t>(), table, rows, c->scratch_a.as<uint4>());
 }
 
 // ... -> out[rows][cells], NP permutations per pass over the pairs

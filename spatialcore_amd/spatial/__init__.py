@@ -16,6 +16,7 @@ from spatialcore_amd.spatial.neighborhoods import (
     co_occurrence,
     compute_neighborhood_profile,
     identify_niches,
+    ligrec,
     neighborhood_enrichment,
     ripley_k,
 )
@@ -33,6 +34,7 @@ __all__ = [
     "neighborhood_enrichment",  # extension: not in the reference
     "ripley_k",  # extension: not in the reference
     "co_occurrence",  # extension: squidpy's function, not in the reference
+    "ligrec",  # extension: squidpy's function, not in the reference
     "make_spatial_domains",
     "get_domain_summary",
     "calculate_domain_distances",

@@ -7,7 +7,9 @@ Neighbour search (exact kNN or closed-ball radius) and the per-cell label counti
 kernels.  ``identify_niches`` (NB:299-522) clusters the profiles with sklearn's k-means (k-means++ seeding, Lloyd
 iterations, best of ``n_init`` runs) replayed step for step in HIP (``sc_kmeans_fit``).
 ``neighborhood_enrichment``, ``ripley_k`` and ``co_occurrence`` are extensions: the three cell-type pattern statistics
-squidpy users run on an annotated section, as exact integer pair counts.
+squidpy users run on an annotated section, as exact integer pair counts.  ``ligrec`` is the
+fourth extension under squidpy's name: the ligand-receptor permutation test over cluster pairs, expression summed by
+permuted label as exact integers.
 """
 
 from __future__ import annotations
@@ -583,6 +585,372 @@ def co_occurrence(
                     "interval": int(interval) if isinstance(interval, (int, np.integer)) else [float(t) for t in thresholds]},
         outputs={"uns": key_added, "n_celltypes": T, "n_cells": n_cells, "n_intervals": R,
                  "n_pairs": int(count.sum())},
+    )
+    return adata
+
+
+LIGREC_MAX_CLUSTERS = 96        # sc_ligrec_*'s envelope
+LIGREC_MAX_SHIFT_SPREAD = 30    # |s_L - s_R| of an interaction at most: the comparison stays inside 128 bits
+
+
+def ligrec_shifts(X) -> np.ndarray:
+    """The shift ``s_g`` of every column of the host matrix ``X`` (cells x genes, dense or scipy sparse), int32: 0 for a
+    gene whose values are all integers in [0, 2^32) -- raw counts are summed as they are -- else ``32 - e_g`` with ``e_g``
+    the smallest integer such that ``max |x| < 2^e_g`` (``np.frexp``'s exponent).  A value enters the test as the integer
+    ``rint(x * 2**s_g)``.  ``ValueError`` naming the columns that hold a non-finite value."""
+    from scipy import sparse
+
+    if sparse.issparse(X):
+        Xc = X.tocsc()
+        columns = (Xc.data[Xc.indptr[g]:Xc.indptr[g + 1]] for g in range(Xc.shape[1]))
+    else:
+        A = np.asarray(X)
+        columns = (A[:, g] for g in range(A.shape[1]))
+    shifts, bad = [], []
+    for g, col in enumerate(columns):
+        col = np.asarray(col, dtype=np.float64)
+        if not np.all(np.isfinite(col)):
+            bad.append(g)
+            shifts.append(0)
+            continue
+        top = float(np.abs(col).max()) if col.size else 0.0
+        counts = col.size == 0 or (col.min() >= 0 and top < 4294967296.0 and bool(np.all(col == np.floor(col))))
+        shifts.append(0 if counts else 32 - int(np.frexp(top)[1]))
+    if bad:
+        raise ValueError(f"non-finite expression values in columns {bad[:10]}{'...' if len(bad) > 10 else ''}")
+    return np.asarray(shifts, dtype=np.int32)
+
+
+def _ligrec_interactions(interactions, var_names):
+    """``(pairs, metadata, n_unknown)``: the distinct (source, target) name pairs whose two genes are in ``var_names``, in
+    the order given; the other columns of an interactions frame for those pairs (None when there are none); how many
+    distinct pairs were dropped for an unknown name.  A string means the request is malformed."""
+    if isinstance(interactions, pd.DataFrame):
+        if "source" not in interactions.columns or "target" not in interactions.columns:
+            return "interactions must have the columns 'source' and 'target'"
+        frame = interactions.reset_index(drop=True)
+    else:
+        try:
+            rows = [tuple(p) for p in interactions]
+        except TypeError:
+            return "interactions must be a DataFrame with 'source' and 'target' columns or a sequence of (source, target) pairs"
+        if any(len(p) != 2 for p in rows):
+            return "interactions must be a DataFrame with 'source' and 'target' columns or a sequence of (source, target) pairs"
+        frame = pd.DataFrame(rows, columns=["source", "target"])
+    frame = frame.assign(source=frame["source"].astype(str), target=frame["target"].astype(str))
+    frame = frame.drop_duplicates(subset=["source", "target"], keep="first")
+    known = frame["source"].isin(var_names) & frame["target"].isin(var_names)
+    n_unknown = int((~known).sum())
+    frame = frame[known].reset_index(drop=True)
+    pairs = list(zip(frame["source"], frame["target"]))
+    extra = frame.drop(columns=["source", "target"])
+    metadata = None
+    if extra.shape[1]:
+        extra.index = pd.MultiIndex.from_tuples(pairs, names=["source", "target"])
+        metadata = extra
+    return pairs, metadata, n_unknown
+
+
+def _ligrec_cluster_pairs(clusters, categories):
+    """The ordered cluster pairs (as positions in ``categories``) that ``clusters`` asks for: all K^2 for None, every
+    ordered pair of a subset of categories, or the listed pairs themselves.  A string names what is wrong."""
+    where = {c: k for k, c in enumerate(categories)}
+    K = len(categories)
+    if clusters is None:
+        return [(a, b) for a in range(K) for b in range(K)]
+    items = list(clusters)
+    if not items:
+        return "clusters must not be empty"
+    if all(isinstance(it, (tuple, list)) and len(it) == 2 for it in items):
+        flat = [c for it in items for c in it]
+        pairs = [tuple(it) for it in items]
+    else:
+        flat = items
+        pairs = [(a, b) for a in items for b in items]
+    unknown = [c for c in flat if not isinstance(c, (str, int, float, np.generic)) or c not in where]
+    if unknown:
+        return f"clusters {unknown[:5]} are not categories of the cluster column (categories: {list(categories)[:10]}...)"
+    return list(dict.fromkeys((where[a], where[b]) for a, b in pairs))
+
+
+def _ligrec_request_problem(adata, cluster_key, interactions, clusters, n_perms, threshold, corr_method, corr_axis, rng,
+                            comm, perm_batch, gene_batch) -> Optional[str]:
+    """The first thing wrong with a ``ligrec`` request (checked before any device work), else None."""
+    if cluster_key not in adata.obs.columns:
+        return (f"Column '{cluster_key}' not found in adata.obs. "
+                f"Available columns: {list(adata.obs.columns)[:10]}...")
+    n_missing = int(adata.obs[cluster_key].isna().sum())
+    if n_missing:
+        return (f"{n_missing} cells have missing labels in '{cluster_key}'. "
+                "Fill or remove missing labels before running ligrec.")
+    if interactions is None:
+        return "interactions is required: no database is fetched (pass a DataFrame with 'source' and 'target' columns)"
+    parsed = _ligrec_interactions(interactions, adata.var_names)
+    if isinstance(parsed, str):
+        return parsed
+    if not parsed[0]:
+        return (f"no interaction is left: none of the given (source, target) pairs has both genes in adata.var_names "
+                f"({parsed[2]} dropped)")
+    if n_perms < 0:
+        return f"n_perms must be >= 0, got {n_perms}"
+    if not 0 <= threshold <= 1:
+        return f"threshold must lie in [0, 1], got {threshold}"
+    if corr_method not in (None, "fdr_bh", "bonferroni"):
+        return f"corr_method must be None, 'fdr_bh' or 'bonferroni', got '{corr_method}'"
+    if corr_axis not in ("clusters", "interactions"):
+        return f"corr_axis must be 'clusters' or 'interactions', got '{corr_axis}'"
+    if rng not in ("numpy", "philox"):
+        return f"rng must be 'numpy' or 'philox', got '{rng}'"
+    if comm is not None and comm.world > 1 and rng != "philox":
+        return "permutations can only be sharded over ranks (comm=) with rng='philox': the numpy stream is sequential"
+    if perm_batch < 1:
+        return f"perm_batch must be >= 1, got {perm_batch}"
+    if gene_batch is not None and gene_batch < 2:
+        return f"gene_batch must be >= 2 (an interaction needs its two genes in one batch), got {gene_batch}"
+    labels = adata.obs[cluster_key]
+    categories = list(labels.cat.categories) if isinstance(labels.dtype, pd.CategoricalDtype) else sorted(set(labels.values))
+    if not 1 <= len(categories) <= LIGREC_MAX_CLUSTERS:
+        return f"ligrec supports 1 to {LIGREC_MAX_CLUSTERS} clusters, '{cluster_key}' has {len(categories)}"
+    picked = _ligrec_cluster_pairs(clusters, categories)
+    if isinstance(picked, str):
+        return picked
+    return None
+
+
+def _ligrec_gene_batch(n_cells: int, requested: Optional[int]) -> int:
+    """Genes per device batch of ``ligrec``, sized like ``morans_i``'s: the fp64 tiles are 8 bytes per (cell, gene), and
+    half of a 128 GB budget is left to the permutation table, the label words and the null tables."""
+    if requested is not None:
+        return int(requested)
+    fit = int((64 << 30) // (8 * max(n_cells, 1)))
+    return max(64, fit // 64 * 64)
+
+
+def _ligrec_batches(pairs_idx, gene_batch: int):
+    """The interactions (pairs of gene positions) cut, in order, into batches whose distinct genes number at most
+    ``gene_batch``: ``[(genes, rows)]`` with ``genes`` sorted and ``rows`` the batch's interaction numbers.  A gene may be
+    loaded with several batches; its integers do not depend on its company."""
+    batches, genes, rows = [], set(), []
+    for i, (l, r) in enumerate(pairs_idx):
+        if rows and len(genes | {l, r}) > gene_batch:
+            batches.append((sorted(genes), rows))
+            genes, rows = set(), []
+        genes |= {l, r}
+        rows.append(i)
+    batches.append((sorted(genes), rows))
+    return batches
+
+
+def ligrec_adjust(pvalues: np.ndarray, method: Optional[str], axis: str) -> np.ndarray:
+    """``pvalues`` (interactions x cluster pairs, NaN = not tested) corrected over the non-NaN entries of every cluster-pair
+    COLUMN (``axis="clusters"``: one family per cluster pair, its interactions) or of every interaction ROW
+    (``axis="interactions"``), in float64.  ``"bonferroni"``: ``min(p m, 1)`` with m the family's size; ``"fdr_bh"``:
+    Benjamini-Hochberg, ``min over ranks j >= k of p_(j) m / j``, clipped at 1 (the step-up form of the tables in
+    ``autocorrelation._padj_tables``, on values instead of permutation-count levels).  NaN stays NaN."""
+    p = np.array(pvalues, dtype=np.float64)
+    if method is None:
+        return p
+    fam = p if axis == "interactions" else p.T      # (a view: families are rows)
+    for row in fam:
+        ok = ~np.isnan(row)
+        m = int(ok.sum())
+        if m == 0:
+            continue
+        v = row[ok]
+        if method == "bonferroni":
+            row[ok] = np.minimum(v * m, 1.0)
+            continue
+        order = np.argsort(v, kind="stable")
+        adj = v[order] * m / np.arange(1, m + 1)
+        adj = np.minimum(np.minimum.accumulate(adj[::-1])[::-1], 1.0)
+        out = np.empty(m, dtype=np.float64)
+        out[order] = adj
+        row[ok] = out
+    return p
+
+
+def ligrec_statistics(sums, nnz, group_n, shifts, pairs_idx, cluster_pairs, count_ge, n_perms: int, threshold: float):
+    """``(means, pvalues)`` (interactions x cluster pairs, float64) from the integer tables alone (pure host arithmetic):
+    ``m[c, g] = float(S[c, g]) * 2**-s_g / n_c`` (0 for an empty cluster), ``means = (m[a, L] + m[b, R]) / 2`` and 0 where
+    either mean is <= 0; ``pvalues = count_ge / n_perms``, NaN where ``N[a, L] / n_a < threshold`` or
+    ``N[b, R] / n_b < threshold`` (float64 division; an empty cluster is never kept); None for ``n_perms = 0``."""
+    S, N = np.asarray(sums, dtype=np.int64), np.asarray(nnz, dtype=np.int64)
+    n_c = np.asarray(group_n, dtype=np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m = np.ldexp(S.astype(np.float64), -np.asarray(shifts, dtype=np.int64)[None, :]) / n_c[:, None].astype(np.float64)
+        frac = N.astype(np.float64) / n_c[:, None].astype(np.float64)
+    m[n_c == 0, :] = 0.0
+    L = np.asarray([l for l, _ in pairs_idx], dtype=np.intp)
+    R = np.asarray([r for _, r in pairs_idx], dtype=np.intp)
+    A = np.asarray([a for a, _ in cluster_pairs], dtype=np.intp)
+    B = np.asarray([b for _, b in cluster_pairs], dtype=np.intp)
+    mL, mR = m[A[None, :], L[:, None]], m[B[None, :], R[:, None]]
+    means = np.where((mL > 0) & (mR > 0), (mL + mR) / 2, 0.0)
+    if n_perms <= 0:
+        return means, None
+    keep = (frac[A[None, :], L[:, None]] >= threshold) & (frac[B[None, :], R[:, None]] >= threshold)
+    pvalues = np.where(keep, np.asarray(count_ge, dtype=np.int64) / n_perms, np.nan)
+    return means, pvalues
+
+
+def ligrec(
+    adata,
+    cluster_key: str,
+    interactions=None,
+    clusters=None,
+    n_perms: int = 1000,
+    threshold: float = 0.01,
+    corr_method: Optional[str] = None,
+    corr_axis: str = "clusters",
+    alpha: float = 0.05,
+    seed: int = 0,
+    key_added: Optional[str] = None,
+    copy: bool = False,
+    *,
+    device: int = 0,
+    perm_batch: int = 512,
+    gene_batch: Optional[int] = None,
+    rng: str = "numpy",
+    comm=None,
+):
+    """Ligand-receptor permutation test over ordered cluster pairs: squidpy's ``gr.ligrec`` (the CellPhoneDB test) on the GPU.
+
+    EXTENSION -- the reference has no such function; the name and the keywords are squidpy's, the semantics are defined
+    here (include/spatialcore_hip.h, N10).  For every interaction (L, R) and every ordered pair of
+    clusters (a, b): is the mean of L in a plus the mean of R in b higher than under shuffled cluster labels?
+
+    Inputs.  ``adata.X`` (cells x genes, CSR or dense, float32 or float64); ``cluster_key``, a column with K <= 96
+    categories (those of a categorical column, unused ones kept; else the sorted unique labels); ``interactions``, a
+    DataFrame with ``source`` and ``target`` columns or a sequence of ``(source, target)`` names.  NO DATABASE IS FETCHED:
+    ``interactions`` is required.  Duplicate pairs are dropped, a pair with a name that is not in ``var_names`` is dropped
+    (one log line gives the count), and nothing left is a ``ValueError``.  Complexes (``A_B``) and ``use_raw`` are out of
+    scope: ``SimpleAnnData`` has no ``.raw``, and a name is looked up as it stands.
+
+    Arithmetic: exact integers, order-free.  Gene g carries a shift ``s_g`` (``ligrec_shifts``: 0 for integer counts in
+    [0, 2^32), else ``32 - e_g`` with ``max |x| < 2^e_g``) and every value enters as ``q = rint(x * 2**s_g)``, |q| < 2^32.
+    ``S[c, g]`` = sum of q over cluster c (int64), ``N[c, g]`` = cells of c with x > 0, ``n_c`` = cells of c.  A label
+    permutation keeps every ``n_c``, so "permuted ``(mean_L,a + mean_R,b) / 2`` >= observed" is decided as
+    ``2^s_R n_b (S_p[a, L] - S[a, L]) + 2^s_L n_a (S_p[b, R] - S[b, R]) >= 0`` in 128-bit integers on the device; an
+    interaction whose two shifts differ by more than 30 is a ``ValueError`` naming the genes.  The result is a function of
+    the inputs alone: it does not depend on ``perm_batch``, ``gene_batch``, the rank count or the run.
+
+    Stored in ``adata.uns[key_added or f"{cluster_key}_ligrec"]``, rows a MultiIndex ``(source, target)``, columns a
+    MultiIndex ``(cluster_1, cluster_2)``: ``means`` = ``(m_L,a + m_R,b) / 2`` with ``m = float(S) * 2**-s / n_c`` in
+    float64, 0 where either mean is <= 0; ``count_ge`` (int64); ``pvalues = count_ge / n_perms`` -- squidpy's and
+    CellPhoneDB's form, WITHOUT the +1 in numerator and denominator that this package's other permutation tests use --
+    NaN where ``N[a, L] / n_a < threshold`` or ``N[b, R] / n_b < threshold`` (``>=`` keeps), absent for ``n_perms = 0``;
+    ``metadata``, the interactions frame's other columns, if any; and ``n_perms``, ``seed``, ``rng``, ``clusters`` (the
+    categories), ``threshold``, ``alpha`` (recorded only), ``corr_method``, ``corr_axis``.  ``corr_method`` (None,
+    ``"fdr_bh"``, ``"bonferroni"``) corrects the non-NaN p-values along ``corr_axis`` (``ligrec_adjust``:
+    ``"clusters"`` = every cluster-pair column over its interactions, ``"interactions"`` = every interaction row over its
+    cluster pairs).  ``clusters``: a subset of categories (all their ordered pairs) or a list of ordered pairs; default
+    all K^2.  It selects columns only: the null always permutes the labels of ALL cells.
+
+    Null: ``labels[perm_p]``, the sources and rules of ``neighborhood_enrichment``.  ``rng="numpy"`` (default):
+    ``default_rng(seed).permutation(n)`` continued batch after batch on one GPU; every gene batch sees the same
+    permutations (a permutation batch is generated once and all gene batches run against it).  ``rng="philox"``:
+    counter-based, and with ``comm`` sharded by ``shard_bounds`` and merged with one ``sum_over_ranks_i64`` of
+    ``count_ge``.  Sharding with ``rng="numpy"`` is a ``ValueError``.  ``copy=True`` works on, and returns, a copy.
+    """
+    problem = _ligrec_request_problem(adata, cluster_key, interactions, clusters, n_perms, threshold, corr_method, corr_axis,
+                                      rng, comm, perm_batch, gene_batch)
+    if problem:
+        raise ValueError(problem)
+    if copy:
+        adata = adata.copy()
+    n_cells = adata.n_obs
+    labels = adata.obs[cluster_key]
+    if isinstance(labels.dtype, pd.CategoricalDtype):
+        categories, codes = list(labels.cat.categories), np.asarray(labels.cat.codes, dtype=np.int32)
+    else:
+        categories, codes = _label_codes(adata, cluster_key)
+    K = len(categories)
+    cluster_pairs = _ligrec_cluster_pairs(clusters, categories)
+    pairs, metadata, n_unknown = _ligrec_interactions(interactions, adata.var_names)
+    if n_unknown:
+        logger.info(f"Dropped {n_unknown} interactions with a gene that is not in adata.var_names")
+    names = list(dict.fromkeys(g for pair in pairs for g in pair))            # the G distinct genes, first-seen order
+    var_pos = np.asarray([adata.var_names.get_loc(g) for g in names], dtype=np.int64)
+    at = {g: j for j, g in enumerate(names)}
+    pairs_idx = [(at[l], at[r]) for l, r in pairs]
+    X = adata.X
+    shifts = ligrec_shifts(X[:, var_pos])
+    for l, r in pairs_idx:
+        if abs(int(shifts[l]) - int(shifts[r])) > LIGREC_MAX_SHIFT_SPREAD:
+            raise ValueError(f"interaction ({names[l]}, {names[r]}): the value ranges of the two genes are too far apart for "
+                             f"the exact comparison (shifts {int(shifts[l])} and {int(shifts[r])} differ by more than "
+                             f"{LIGREC_MAX_SHIFT_SPREAD}); rescale one of them")
+    G, I = len(names), len(pairs)
+    logger.info(f"Computing ligrec: {n_cells:,} cells, {K} clusters, {I} interactions of {G} genes, permutations={n_perms}")
+
+    ctx = _lib.default_context(device)
+    batches = _ligrec_batches(pairs_idx, _ligrec_gene_batch(n_cells, gene_batch))
+    S, N = np.zeros((K, G), dtype=np.int64), np.zeros((K, G), dtype=np.int64)
+    count_ge = np.zeros((I, K, K), dtype=np.int64)
+    group_n = np.bincount(codes, minlength=K).astype(np.int64)
+    lo, hi = 0, n_perms
+    if comm is not None and comm.world > 1:
+        from spatialcore_amd.parallel import shard_bounds
+
+        lo, hi = shard_bounds(n_perms, comm.world, comm.rank)
+    resident = [None]
+
+    def run(batch, call):
+        """One device call on a gene batch (loaded unless it is the resident one); its integers into S, N, count_ge."""
+        genes, rows = batch
+        if resident[0] is not batch:
+            ctx.set_expression(X, var_pos[genes])
+            resident[0] = batch
+        local = {g: j for j, g in enumerate(genes)}
+        r = call(codes, K, shifts[genes], [local[pairs_idx[i][0]] for i in rows], [local[pairs_idx[i][1]] for i in rows])
+        S[:, genes], N[:, genes] = r["sum"], r["nnz"]
+        count_ge[rows] += r["count_ge"]
+
+    if rng == "philox":
+        for batch in batches:     # permutation p is a function of (seed, p): every gene batch sees the same ones
+            run(batch, lambda *a: ctx.ligrec_counter(*a, seed, lo, hi - lo, perm_batch))
+    else:
+        words = _lib.rng_state_words(np.random.default_rng(seed))
+        done = lo
+        while True:
+            rows_now = min(perm_batch, hi - done)
+            if rows_now > 0:
+                ctx.generate_permutations(words, n_cells, rows_now)   # one stream, continued batch after batch ...
+            for batch in batches:                                     # ... and every gene batch against the same rows
+                run(batch, lambda *a: ctx.ligrec_counts(*a, rows_now))
+            done += rows_now
+            if done >= hi:
+                break
+    if comm is not None and comm.world > 1:
+        count_ge = comm.sum_over_ranks_i64(count_ge)     # the one collective of this path
+
+    A = [a for a, _ in cluster_pairs]
+    B = [b for _, b in cluster_pairs]
+    picked_ge = count_ge[:, A, B]
+    means, pvalues = ligrec_statistics(S, N, group_n, shifts, pairs_idx, cluster_pairs, picked_ge, n_perms, threshold)
+    index = pd.MultiIndex.from_tuples(pairs, names=["source", "target"])
+    columns = pd.MultiIndex.from_tuples([(categories[a], categories[b]) for a, b in cluster_pairs],
+                                        names=["cluster_1", "cluster_2"])
+    result = {"means": pd.DataFrame(means, index=index, columns=columns),
+              "count_ge": pd.DataFrame(picked_ge, index=index, columns=columns)}
+    if pvalues is not None:
+        result["pvalues"] = pd.DataFrame(ligrec_adjust(pvalues, corr_method, corr_axis), index=index, columns=columns)
+    if metadata is not None:
+        result["metadata"] = metadata
+    result.update({"n_perms": n_perms, "seed": seed, "rng": rng, "clusters": list(categories), "threshold": threshold,
+                   "alpha": alpha, "corr_method": corr_method, "corr_axis": corr_axis})
+    key_added = key_added or f"{cluster_key}_ligrec"
+    adata.uns[key_added] = result
+    logger.info(f"Stored ligrec results in adata.uns['{key_added}'] ({I} interactions x {len(cluster_pairs)} cluster pairs)")
+    update_metadata(
+        adata,
+        function_name="ligrec",
+        parameters={"cluster_key": cluster_key, "n_perms": n_perms, "threshold": threshold, "corr_method": corr_method,
+                    "corr_axis": corr_axis, "alpha": alpha, "seed": seed, "rng": rng,
+                    "permgen_form": (ctx.permgen_form(n_cells) if rng == "numpy" else "counter-based (philox)")
+                                    if n_perms > 0 else None},
+        outputs={"uns": key_added, "n_clusters": K, "n_cells": n_cells, "n_interactions": I, "n_genes": G,
+                 "n_cluster_pairs": len(cluster_pairs), "n_dropped_interactions": n_unknown},
     )
     return adata
 
