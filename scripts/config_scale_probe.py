@@ -1,7 +1,7 @@
 """At-size runs of the remaining BASELINE shapes through the public API (GPU box; not a test):
   local   local_morans_i, 1M cells x 100 genes x 999 permutations (N1) + lees_l_local, 2 pairs with per-cell p-values (N2)
-  enrich  neighborhood_enrichment, 1M cells, k = 30, ~20 cell types, 10 000 label permutations (BASELINE configs[4])
-usage: python scripts/config_scale_probe.py local|enrich [n_perm] [numpy|philox]"""
+  enrich  neighborhood_enrichment, 1M cells, k = 30, 20 cell types (or n_types), 10 000 label permutations (BASELINE configs[4])
+usage: python scripts/config_scale_probe.py local|enrich [n_perm] [numpy|philox] [n_types]"""
 import json, logging, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -30,8 +30,9 @@ if what == "local":
     out["lees_l_local"] = f"2 pairs, k=6, {P} permutations for the global p + {P} for the per-cell p-values each"
 else:
     P = int(sys.argv[2]) if len(sys.argv) > 2 else 10_000
-    w = rng.dirichlet(np.full(20, 0.7))
-    labels = rng.choice(20, N, p=w)
+    T = int(sys.argv[4]) if len(sys.argv) > 4 else 20
+    w = rng.dirichlet(np.full(T, 0.7))
+    labels = rng.choice(T, N, p=w)
     ad = make_adata(coords, np.zeros((N, 1), dtype=np.float32), labels)
     sp.neighborhood_enrichment(ad, "cell_type", k=30, n_permutations=8)           # warm-up
     source = sys.argv[3] if len(sys.argv) > 3 else "numpy"

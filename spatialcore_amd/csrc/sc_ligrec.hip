@@ -14,11 +14,11 @@
 // k_ligrec_sums, the hot path.  A workgroup owns LIG_CELLS cells of one 16-gene tile and NP permutations.  The 16 lanes
 // of a quarter-wavefront read one cell's 128-byte row of the fp64 tile, one gene each, LIG_ROWS rows ahead; a lane whose
 // value is zero does nothing more (expression is mostly zeros).  The others quantise, read the cell's label word (NP label bytes: the 16-byte
-// words of k_enrich_relabel16, one load per 16 permutations) and add q into the LDS table [NP][K][16] of int64 with one
+// words of k_lp_relabel_words, one load per 16 permutations) and add q into the LDS table [NP][K][16] of int64 with one
 // 64-bit LDS integer atomic per permutation.  The lanes of a wavefront are 4 cells x 16 genes, so two lanes meet on an
 // address only when their cells share a label under that permutation.  The workgroup leaves with 64-bit global integer
 // atomics into [p][K][genes].  NP = 16, 8 or 4 by K, so that the table stays within 64 KB and two workgroups share a
-// compute unit's LDS (RipPlan's rule).  The observed pass is the same kernel on the identity labels (NP = 1); it also
+// compute unit's LDS (the rule of k_lp_pairs' plan).  The observed pass is the same kernel on the identity labels (NP = 1); it also
 // counts N and flags the genes with a value that cannot be quantised.  No floating-point atomics, no matrix cores (a
 // one-hot x X product would spend K times the arithmetic on zeros).
 //
@@ -35,26 +35,10 @@
 #define LIG_MAX_SPREAD 30     // |s_L - s_R| of an interaction at most: keeps the comparison inside 128 bits
 #define LIG_MAX_SHIFT 1200    // |s_g| at most (fp64 exponents: 32 - e_g lies in [-992, 1106])
 
-template <int NP> struct LigWord;
-template <> struct LigWord<16> { typedef uint4 type; };
-template <> struct LigWord<8> { typedef uint2 type; };
-template <> struct LigWord<4> { typedef uint32_t type; };
-template <> struct LigWord<1> { typedef unsigned char type; };
-
-// label byte s of a word, s a compile-time constant after unrolling (no per-lane indexing of a register array)
-__device__ __forceinline__ int lig_label(const uint4 &w, int s)
-{
-    const uint32_t v = (s >> 2) == 0 ? w.x : (s >> 2) == 1 ? w.y : (s >> 2) == 2 ? w.z : w.w;
-    return (int)((v >> (8 * (s & 3))) & 0xffu);
-}
-__device__ __forceinline__ int lig_label(const uint2 &w, int s) { return (int)((((s >> 2) ? w.y : w.x) >> (8 * (s & 3))) & 0xffu); }
-__device__ __forceinline__ int lig_label(const uint32_t &w, int s) { return (int)((w >> (8 * (s & 3))) & 0xffu); }
-__device__ __forceinline__ int lig_label(const unsigned char &w, int) { return (int)w; }
-
 // sums[q NP + p][c][tile 16 + slot] += sum of q over the workgroup's cells with label c under permutation q NP + p of the
 // pass.  Workgroup (cell block x pass q, tile): blockIdx.x = cell block * groups + q, the passes of one cell block side by
 // side (the counters show every pass fetching its rows from the memory side all the same: DESIGN.md 4.6j).  The labels of a cell are NP consecutive bytes at lab + group
-// stride * (q NP / 16) + cell * cell_bytes + (q NP) % 16: the 16-byte words of k_enrich_relabel16 (cell_bytes = 16), or
+// stride * (q NP / 16) + cell * cell_bytes + (q NP) % 16: the 16-byte words of k_lp_relabel_words (cell_bytes = 16), or
 // the label bytes themselves (OBS: NP = 1, cell_bytes = 1, one pass).  OBS also counts nnz[c][gene] = #{x > 0} and sets
 // bad[gene] when a value is not finite or its rint(x 2^s) leaves (-2^32, 2^32); such a value is added nowhere.
 template <int NP, bool OBS>
@@ -64,7 +48,7 @@ __global__ __launch_bounds__(256) void k_ligrec_sums(const double *__restrict__ 
                                                      unsigned long long *__restrict__ sums, unsigned long long *__restrict__ nnz,
                                                      uint32_t *__restrict__ bad)
 {
-    typedef typename LigWord<NP>::type word_t;
+    typedef typename LpWord<NP>::type word_t;
     extern __shared__ unsigned long long tab[];   // [NP][n_types][16], then (OBS) uint32 nz[n_types][16]
     const int words = NP * n_types * SC_TILE;
     uint32_t *nz = reinterpret_cast<uint32_t *>(tab + words);
@@ -92,10 +76,10 @@ __global__ __launch_bounds__(256) void k_ligrec_sums(const double *__restrict__ 
         }
         const unsigned long long qv = (unsigned long long)(long long)y;
         const word_t w = *reinterpret_cast<const word_t *>(lp + cell * cell_bytes);
-        if (OBS && x > 0.0) atomicAdd(&nz[lig_label(w, 0) * SC_TILE + slot], 1u);
+        if (OBS && x > 0.0) atomicAdd(&nz[lp_label(w, 0) * SC_TILE + slot], 1u);
         if (qv != 0ull) {
 #pragma unroll
-            for (int s = 0; s < NP; ++s) atomicAdd(&tab[(s * n_types + lig_label(w, s)) * SC_TILE + slot], qv);
+            for (int s = 0; s < NP; ++s) atomicAdd(&tab[(s * n_types + lp_label(w, s)) * SC_TILE + slot], qv);
         }
     };
     // LIG_ROWS rows per lane are loaded before the first is looked at: with one load in flight per lane the kernel ran at
@@ -308,17 +292,10 @@ extern "C" int sc_ligrec_counts(sc_ctx *c, const int32_t *labels, int64_t n, int
 {
     SC_REQUIRE(c && labels && shift && pair_l && pair_r && sum_out && nnz_out && group_n_out && count_ge_out, SC_ERR_INVALID,
                "sc_ligrec_counts: null pointer");
-    SC_REQUIRE(n_perm >= 0 && perm_row0 >= 0, SC_ERR_INVALID, "sc_ligrec_counts: negative size");
-    SC_REQUIRE(n_perm <= 65534, SC_ERR_INVALID,
-               "sc_ligrec_counts: at most 65534 permutations per call (got %lld); call it per batch of the table", (long long)n_perm);
     SC_HIP(hipSetDevice(c->device));
     LigPlan pl;
     SC_TRY(lig_prepare(c, "sc_ligrec_counts", labels, n, n_types, shift, pair_l, pair_r, n_pairs, n_perm, group_n_out, &pl));
-    if (n_perm > 0) {
-        SC_TRY(sc_perm_forward_ensure(c));
-        SC_REQUIRE(c->p_n == n && perm_row0 + n_perm <= c->p_count, SC_ERR_STATE,
-                   "sc_ligrec_counts: needs permutation rows [%lld, %lld)", (long long)perm_row0, (long long)(perm_row0 + n_perm));
-    }
+    SC_TRY(lp_counts_rows(c, "sc_ligrec_counts", n, n_perm, perm_row0));
     const size_t tw = pl.table();
     SC_TRY(c->scratch_b.ensure(sizeof(unsigned long long) * tw * (size_t)(n_perm + 2), &c->mem));
     unsigned long long *d_obs = c->scratch_b.as<unsigned long long>(), *d_nnz = d_obs + tw, *d_tab = d_nnz + tw;
@@ -349,9 +326,8 @@ extern "C" int sc_ligrec_counter(sc_ctx *c, const int32_t *labels, int64_t n, in
 {
     SC_REQUIRE(c && labels && shift && pair_l && pair_r && sum_out && nnz_out && group_n_out && count_ge_out, SC_ERR_INVALID,
                "sc_ligrec_counter: null pointer");
-    SC_REQUIRE(n_perm >= 0 && p_first >= 0 && batch >= 1 && batch <= 65534, SC_ERR_INVALID, "sc_ligrec_counter: bad sizes");
+    SC_TRY(lp_counter_sizes("sc_ligrec_counter", p_first, n_perm, &batch));
     SC_HIP(hipSetDevice(c->device));
-    if (batch > n_perm) batch = n_perm > 0 ? n_perm : 1;
     LigPlan pl;
     SC_TRY(lig_prepare(c, "sc_ligrec_counter", labels, n, n_types, shift, pair_l, pair_r, n_pairs, batch, group_n_out, &pl));
     const size_t tw = pl.table();

@@ -61,6 +61,34 @@ def _label_codes(adata, celltype_column: str):
     return list(kinds), codes.astype(np.int32)
 
 
+def _category_codes(adata, column: str):
+    """The categories of a categorical column (unused ones kept), else ``_label_codes``' sorted unique labels, and the
+    int32 code of every cell."""
+    labels = adata.obs[column]
+    if isinstance(labels.dtype, pd.CategoricalDtype):
+        return list(labels.cat.categories), np.asarray(labels.cat.codes, dtype=np.int32)
+    return _label_codes(adata, column)
+
+
+def _point_pattern_request_problem(adata, column, spatial_key, what) -> Optional[str]:
+    """What ``ripley_k`` and ``co_occurrence`` (``what``) check first: the spatial key, the column, 2-D coordinates."""
+    if spatial_key not in adata.obsm:
+        return (f"adata.obsm['{spatial_key}'] not found. "
+                f"Spatial coordinates are required for {what}.")
+    if column not in adata.obs.columns:
+        return (f"Column '{column}' not found in adata.obs. "
+                f"Available columns: {list(adata.obs.columns)[:10]}...")
+    shape = np.shape(adata.obsm[spatial_key])
+    if len(shape) != 2 or shape[1] != 2:
+        return ("only 2-D coordinates are supported by the MI355X path "
+                f"(adata.obsm['{spatial_key}'] has shape {tuple(shape)})")
+    return None
+
+
+def _rng_problem(rng) -> Optional[str]:
+    return None if rng in ("numpy", "philox") else f"rng must be 'numpy' or 'philox', got '{rng}'"
+
+
 def _coordinates(adata, spatial_key: str) -> np.ndarray:
     xy = np.asarray(adata.obsm[spatial_key])
     if xy.ndim != 2 or xy.shape[1] != 2:
@@ -81,37 +109,32 @@ def _activate_neighbour_graph(ctx, coords: np.ndarray, method: str, k: int, radi
         ctx.set_graph_csr(indptr, indices, np.ones(indices.size), coords.shape[0])
 
 
-def _label_permutation_null(ctx, counts, counter, codes, n_types: int, n_sums: int, n_permutations: int, seed: int,
-                            perm_batch: int, rng: str, comm):
-    """The observed table and the integer sums of the label-permutation null of ``neighborhood_enrichment`` and
-    ``ripley_k``: sum of (null - observed), sum of (null - observed)^2, #{null >= observed} and, with ``n_sums = 4``,
-    #{null <= observed}.  They are exact and order-free, so the permutation shards of the ranks of ``comm`` merge with
-    one integer all-reduce.  ``counts(codes, T, batch)``: the tables of the resident permutation rows, then the observed
-    one (``rng="numpy"``); ``counter(codes, T, seed, lo, n, batch)``: the observed table and the sums over the
-    counter-based permutations lo .. lo + n - 1 (``rng="philox"``)."""
+def _label_permutation_null(ctx, n_cells: int, n_permutations: int, seed: int, perm_batch: int, rng: str, comm,
+                            resident, counter):
+    """The null of a label-permutation test over this rank's share of the ``n_permutations`` permutations:
+    ``(observed, sums)``.  ``resident(rows)`` -> ``(observed, sums)`` over the first ``rows`` rows of the resident
+    permutation table (``rng="numpy"``: the stream ``default_rng(seed).permutation(n_cells)``, generated ``perm_batch``
+    rows at a time and continued batch after batch; one pass with ``rows = 0`` still runs when there is nothing to
+    permute, for the observed tables).  ``counter(lo, n)`` -> the same over the counter-based permutations
+    lo .. lo + n - 1 (``rng="philox"``), one call for the whole range.  ``sums`` is an int64 array, exact and order-free:
+    batches add theirs, and the permutation shards of the ranks of ``comm`` merge with one integer all-reduce;
+    ``observed`` is whatever the last call gave."""
     lo, hi = 0, n_permutations
     if comm is not None and comm.world > 1:
         from spatialcore_amd.parallel import shard_bounds
 
         lo, hi = shard_bounds(n_permutations, comm.world, comm.rank)
     if rng == "philox":
-        # one device call for this rank's whole range: generation of batch b + 1 beside the counting of batch b,
-        # integer sums accumulated on the device
-        observed, sums = counter(codes, n_types, seed, lo, hi - lo, perm_batch)
+        observed, sums = counter(lo, hi - lo)
     else:
         words = _lib.rng_state_words(np.random.default_rng(seed))
         sums, done = 0, lo
         while True:
             batch = min(perm_batch, hi - done)
             if batch > 0:
-                ctx.generate_permutations(words, codes.size, batch)   # one stream, continued batch after batch
-            cnt = counts(codes, n_types, batch)
-            observed = cnt[batch]
-            dev = cnt[:batch] - observed
-            rows = [dev.sum(axis=0), (dev * dev).sum(axis=0), (dev >= 0).sum(axis=0)]
-            if n_sums > 3:
-                rows.append((dev <= 0).sum(axis=0))
-            sums = sums + np.stack(rows)
+                ctx.generate_permutations(words, n_cells, batch)   # one stream, continued batch after batch
+            observed, part = resident(batch)
+            sums = sums + part
             done += batch
             if done >= hi:
                 break
@@ -120,9 +143,36 @@ def _label_permutation_null(ctx, counts, counter, codes, n_types: int, n_sums: i
     return observed, sums
 
 
+def _pair_count_null(ctx, counts, counter, codes, n_types: int, n_sums: int, n_permutations: int, seed: int,
+                     perm_batch: int, rng: str, comm):
+    """``_label_permutation_null`` of ``neighborhood_enrichment`` and ``ripley_k``: the observed table and the integer
+    sums of the null: sum of (null - observed), sum of (null - observed)^2, #{null >= observed} and, with
+    ``n_sums = 4``, #{null <= observed}.  ``counts(codes, T, rows)``: the tables of the resident permutation rows, then
+    the observed one; ``counter(codes, T, seed, lo, n, batch)``: the observed table and the sums, from one device call
+    (generation of batch b + 1 beside the counting of batch b, integer sums accumulated on the device)."""
+    def resident(rows):
+        cnt = counts(codes, n_types, rows)
+        observed = cnt[rows]
+        dev = cnt[:rows] - observed
+        sums = [dev.sum(axis=0), (dev * dev).sum(axis=0), (dev >= 0).sum(axis=0)]
+        if n_sums > 3:
+            sums.append((dev <= 0).sum(axis=0))
+        return observed, np.stack(sums)
+
+    return _label_permutation_null(ctx, codes.size, n_permutations, seed, perm_batch, rng, comm, resident,
+                                   lambda lo, n: counter(codes, n_types, seed, lo, n, perm_batch))
+
+
+def _permgen_form(ctx, n_cells: int, rng: str, n_permutations: int) -> Optional[str]:
+    """The ``permgen_form`` provenance entry of a call that draws label permutations."""
+    if n_permutations <= 0:
+        return None
+    return ctx.permgen_form(n_cells) if rng == "numpy" else "counter-based (philox)"
+
+
 def _null_statistics(count, sums, n_permutations: int) -> dict:
     """``mean``, ``std`` (population), ``zscore = (count - mean) / std`` and ``p_value = (#{>=} + 1) / (P + 1)`` from the
-    integer sums of ``_label_permutation_null`` over P = ``n_permutations`` > 0 null tables, and
+    integer sums of ``_pair_count_null`` over P = ``n_permutations`` > 0 null tables, and
     ``p_value_less = (#{<=} + 1) / (P + 1)`` when the sums have that fourth row."""
     s1, s2, ge, *le = (np.asarray(x, dtype=np.int64) for x in sums)
     mean_dev = s1 / n_permutations
@@ -240,8 +290,8 @@ def neighborhood_enrichment(
         raise ValueError(problem)
     if n_permutations < 0:
         raise ValueError(f"n_permutations must be >= 0, got {n_permutations}")
-    if rng not in ("numpy", "philox"):
-        raise ValueError(f"rng must be 'numpy' or 'philox', got '{rng}'")
+    if _rng_problem(rng):
+        raise ValueError(_rng_problem(rng))
     if comm is not None and comm.world > 1 and rng != "philox":
         raise ValueError("permutations can only be sharded over ranks with rng='philox': the numpy stream is sequential")
     if copy:
@@ -256,8 +306,8 @@ def neighborhood_enrichment(
     ctx = _lib.default_context(device)
     _activate_neighbour_graph(ctx, coords, method, k, radius)
 
-    observed, sums = _label_permutation_null(ctx, ctx.enrichment_counts, ctx.enrichment_counter, codes, T, 3, n_permutations,
-                                             seed, perm_batch, rng, comm)
+    observed, sums = _pair_count_null(ctx, ctx.enrichment_counts, ctx.enrichment_counter, codes, T, 3, n_permutations, seed,
+                                      perm_batch, rng, comm)
     result = {"count": observed, "celltypes": list(celltypes), "n_permutations": n_permutations, "seed": seed, "rng": rng}
     if n_permutations > 0:
         result.update(_null_statistics(observed, sums, n_permutations))
@@ -268,8 +318,7 @@ def neighborhood_enrichment(
         parameters={"celltype_column": celltype_column, "method": method, "k": k if method == "knn" else None,
                     "radius": radius if method == "radius" else None, "n_permutations": n_permutations,
                     "seed": seed, "spatial_key": spatial_key, "rng": rng,
-                    "permgen_form": (ctx.permgen_form(n_cells) if rng == "numpy" else "counter-based (philox)")
-                                    if n_permutations > 0 else None},
+                    "permgen_form": _permgen_form(ctx, n_cells, rng, n_permutations)},
         outputs={"uns": key_added, "n_celltypes": T, "n_cells": n_cells},
     )
     return adata
@@ -277,16 +326,9 @@ def neighborhood_enrichment(
 
 def _ripley_request_problem(adata, celltype_column, radii, n_permutations, area, spatial_key, rng, comm) -> Optional[str]:
     """The first thing wrong with a ``ripley_k`` request (checked before any device work), else None."""
-    if spatial_key not in adata.obsm:
-        return (f"adata.obsm['{spatial_key}'] not found. "
-                "Spatial coordinates are required for Ripley's K.")
-    if celltype_column not in adata.obs.columns:
-        return (f"Column '{celltype_column}' not found in adata.obs. "
-                f"Available columns: {list(adata.obs.columns)[:10]}...")
-    shape = np.shape(adata.obsm[spatial_key])
-    if len(shape) != 2 or shape[1] != 2:
-        return ("only 2-D coordinates are supported by the MI355X path "
-                f"(adata.obsm['{spatial_key}'] has shape {tuple(shape)})")
+    problem = _point_pattern_request_problem(adata, celltype_column, spatial_key, "Ripley's K")
+    if problem:
+        return problem
     try:
         r = np.asarray(radii, dtype=np.float64)
     except (TypeError, ValueError):
@@ -308,8 +350,8 @@ def _ripley_request_problem(adata, celltype_column, radii, n_permutations, area,
         return f"radii must have a finite square, got {r[-1]}"
     if n_permutations < 0:
         return f"n_permutations must be >= 0, got {n_permutations}"
-    if rng not in ("numpy", "philox"):
-        return f"rng must be 'numpy' or 'philox', got '{rng}'"
+    if _rng_problem(rng):
+        return _rng_problem(rng)
     if comm is not None and rng != "philox":
         return "permutations can only be sharded over ranks (comm=) with rng='philox': the numpy stream is sequential"
     if area is not None and not (np.isfinite(area) and area > 0):
@@ -400,8 +442,8 @@ def ripley_k(
     n_pairs = ctx.ripley_build(coords, radii)
     logger.debug(f"{n_pairs:,} ordered pairs within r={radii[-1]:g}")
 
-    observed, sums = _label_permutation_null(ctx, ctx.ripley_counts, ctx.ripley_counter, codes, T, 4, n_permutations, seed,
-                                             perm_batch, rng, comm)
+    observed, sums = _pair_count_null(ctx, ctx.ripley_counts, ctx.ripley_counter, codes, T, 4, n_permutations, seed,
+                                      perm_batch, rng, comm)
     n_per_type = np.bincount(codes, minlength=T).astype(np.int64)
     result = {"radii": radii, "celltypes": list(celltypes), "n_per_type": n_per_type, "area": float(area), "count": observed}
     result.update(ripley_statistics(observed, n_per_type, area, sums, n_permutations))
@@ -412,8 +454,7 @@ def ripley_k(
         function_name="ripley_k",
         parameters={"celltype_column": celltype_column, "radii": [float(r) for r in radii], "n_permutations": n_permutations,
                     "seed": seed, "area": float(area), "spatial_key": spatial_key, "rng": rng,
-                    "permgen_form": (ctx.permgen_form(n_cells) if rng == "numpy" else "counter-based (philox)")
-                                    if n_permutations > 0 else None},
+                    "permgen_form": _permgen_form(ctx, n_cells, rng, n_permutations)},
         outputs={"uns": key_added, "n_celltypes": T, "n_cells": n_cells, "n_radii": R, "n_pairs": n_pairs},
     )
     return adata
@@ -455,16 +496,9 @@ def _interval_problem(interval) -> Optional[str]:
 
 def _co_occurrence_request_problem(adata, cluster_key, spatial_key, interval) -> Optional[str]:
     """The first thing wrong with a ``co_occurrence`` request (checked before any device work), else None."""
-    if spatial_key not in adata.obsm:
-        return (f"adata.obsm['{spatial_key}'] not found. "
-                "Spatial coordinates are required for co-occurrence.")
-    if cluster_key not in adata.obs.columns:
-        return (f"Column '{cluster_key}' not found in adata.obs. "
-                f"Available columns: {list(adata.obs.columns)[:10]}...")
-    shape = np.shape(adata.obsm[spatial_key])
-    if len(shape) != 2 or shape[1] != 2:
-        return ("only 2-D coordinates are supported by the MI355X path "
-                f"(adata.obsm['{spatial_key}'] has shape {tuple(shape)})")
+    problem = _point_pattern_request_problem(adata, cluster_key, spatial_key, "co-occurrence")
+    if problem:
+        return problem
     n_missing = int(adata.obs[cluster_key].isna().sum())
     if n_missing:
         return (f"{n_missing} cells have missing labels in '{cluster_key}'. "
@@ -552,11 +586,7 @@ def co_occurrence(
     problem = _co_occurrence_request_problem(adata, cluster_key, spatial_key, interval)
     if problem:
         raise ValueError(problem)
-    labels = adata.obs[cluster_key]
-    if isinstance(labels.dtype, pd.CategoricalDtype):
-        celltypes, codes = list(labels.cat.categories), np.asarray(labels.cat.codes, dtype=np.int32)
-    else:
-        celltypes, codes = _label_codes(adata, cluster_key)
+    celltypes, codes = _category_codes(adata, cluster_key)
     coords = _coordinates(adata, spatial_key)
     thresholds = co_occurrence_thresholds(coords, interval)
     n_cells, T, R = adata.n_obs, len(celltypes), thresholds.size - 1
@@ -699,8 +729,8 @@ def _ligrec_request_problem(adata, cluster_key, interactions, clusters, n_perms,
         return f"corr_method must be None, 'fdr_bh' or 'bonferroni', got '{corr_method}'"
     if corr_axis not in ("clusters", "interactions"):
         return f"corr_axis must be 'clusters' or 'interactions', got '{corr_axis}'"
-    if rng not in ("numpy", "philox"):
-        return f"rng must be 'numpy' or 'philox', got '{rng}'"
+    if _rng_problem(rng):
+        return _rng_problem(rng)
     if comm is not None and comm.world > 1 and rng != "philox":
         return "permutations can only be sharded over ranks (comm=) with rng='philox': the numpy stream is sequential"
     if perm_batch < 1:
@@ -859,11 +889,7 @@ def ligrec(
     if copy:
         adata = adata.copy()
     n_cells = adata.n_obs
-    labels = adata.obs[cluster_key]
-    if isinstance(labels.dtype, pd.CategoricalDtype):
-        categories, codes = list(labels.cat.categories), np.asarray(labels.cat.codes, dtype=np.int32)
-    else:
-        categories, codes = _label_codes(adata, cluster_key)
+    categories, codes = _category_codes(adata, cluster_key)
     K = len(categories)
     cluster_pairs = _ligrec_cluster_pairs(clusters, categories)
     pairs, metadata, n_unknown = _ligrec_interactions(interactions, adata.var_names)
@@ -885,44 +911,31 @@ def ligrec(
 
     ctx = _lib.default_context(device)
     batches = _ligrec_batches(pairs_idx, _ligrec_gene_batch(n_cells, gene_batch))
-    S, N = np.zeros((K, G), dtype=np.int64), np.zeros((K, G), dtype=np.int64)
-    count_ge = np.zeros((I, K, K), dtype=np.int64)
     group_n = np.bincount(codes, minlength=K).astype(np.int64)
-    lo, hi = 0, n_perms
-    if comm is not None and comm.world > 1:
-        from spatialcore_amd.parallel import shard_bounds
-
-        lo, hi = shard_bounds(n_perms, comm.world, comm.rank)
     resident = [None]
 
-    def run(batch, call):
-        """One device call on a gene batch (loaded unless it is the resident one); its integers into S, N, count_ge."""
-        genes, rows = batch
-        if resident[0] is not batch:
-            ctx.set_expression(X, var_pos[genes])
-            resident[0] = batch
-        local = {g: j for j, g in enumerate(genes)}
-        r = call(codes, K, shifts[genes], [local[pairs_idx[i][0]] for i in rows], [local[pairs_idx[i][1]] for i in rows])
-        S[:, genes], N[:, genes] = r["sum"], r["nnz"]
-        count_ge[rows] += r["count_ge"]
+    def all_gene_batches(call):
+        """One device call per gene batch (loaded unless it is the resident one), all against the same permutations:
+        the observed integers ``(S, N)``, and ``count_ge`` of those permutations."""
+        S, N = np.zeros((K, G), dtype=np.int64), np.zeros((K, G), dtype=np.int64)
+        count_ge = np.zeros((I, K, K), dtype=np.int64)
+        for batch in batches:
+            genes, rows = batch
+            if resident[0] is not batch:
+                ctx.set_expression(X, var_pos[genes])
+                resident[0] = batch
+            local = {g: j for j, g in enumerate(genes)}
+            r = call(codes, K, shifts[genes], [local[pairs_idx[i][0]] for i in rows], [local[pairs_idx[i][1]] for i in rows])
+            S[:, genes], N[:, genes] = r["sum"], r["nnz"]
+            count_ge[rows] += r["count_ge"]
+        return (S, N), count_ge
 
-    if rng == "philox":
-        for batch in batches:     # permutation p is a function of (seed, p): every gene batch sees the same ones
-            run(batch, lambda *a: ctx.ligrec_counter(*a, seed, lo, hi - lo, perm_batch))
-    else:
-        words = _lib.rng_state_words(np.random.default_rng(seed))
-        done = lo
-        while True:
-            rows_now = min(perm_batch, hi - done)
-            if rows_now > 0:
-                ctx.generate_permutations(words, n_cells, rows_now)   # one stream, continued batch after batch ...
-            for batch in batches:                                     # ... and every gene batch against the same rows
-                run(batch, lambda *a: ctx.ligrec_counts(*a, rows_now))
-            done += rows_now
-            if done >= hi:
-                break
-    if comm is not None and comm.world > 1:
-        count_ge = comm.sum_over_ranks_i64(count_ge)     # the one collective of this path
+    # a batch of the numpy stream is generated once and every gene batch runs against those rows; counter-based
+    # permutation p is a function of (seed, p), so there too every gene batch sees the same ones
+    (S, N), count_ge = _label_permutation_null(
+        ctx, n_cells, n_perms, seed, perm_batch, rng, comm,
+        lambda rows: all_gene_batches(lambda *a: ctx.ligrec_counts(*a, rows)),
+        lambda lo, n: all_gene_batches(lambda *a: ctx.ligrec_counter(*a, seed, lo, n, perm_batch)))
 
     A = [a for a, _ in cluster_pairs]
     B = [b for _, b in cluster_pairs]
@@ -947,8 +960,7 @@ def ligrec(
         function_name="ligrec",
         parameters={"cluster_key": cluster_key, "n_perms": n_perms, "threshold": threshold, "corr_method": corr_method,
                     "corr_axis": corr_axis, "alpha": alpha, "seed": seed, "rng": rng,
-                    "permgen_form": (ctx.permgen_form(n_cells) if rng == "numpy" else "counter-based (philox)")
-                                    if n_perms > 0 else None},
+                    "permgen_form": _permgen_form(ctx, n_cells, rng, n_perms)},
         outputs={"uns": key_added, "n_clusters": K, "n_cells": n_cells, "n_interactions": I, "n_genes": G,
                  "n_cluster_pairs": len(cluster_pairs), "n_dropped_interactions": n_unknown},
     )

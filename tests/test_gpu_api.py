@@ -433,9 +433,10 @@ def _knn_graph_and_codes(seed, n, T, k, extent):
 
 
 def test_enrichment_counter_narrow_form_at_30_types(oracle):
-    """T = 30: T x T = 900 bins do not fit the sixteen-permutations-per-edge form (at most 768), so sc_enrichment_counter
-    counts with k_enrich, one permutation per edge pass.  21 counter-based permutations in batches of 8 (the last batch
-    ragged): the observed table and every sum row equal the oracle's restatement of the definition, exactly."""
+    """T = 30: T x T = 900 bins, sixteen histograms of which (odd stride 901) still fit the 16384 LDS words of the pair
+    kernel, so sc_enrichment_counter counts sixteen permutations per edge pass here (a second, one-permutation kernel took
+    over above 768 bins once).  21 counter-based permutations in batches of 8 (the last batch ragged): the observed
+    table and every sum row equal the oracle's restatement of the definition, exactly."""
     n, T, k, P, seed = 4000, 30, 8, 21, 91
     ctx, coords, codes = _knn_graph_and_codes(30, n, T, k, 700.0)
     obs, sums = ctx.enrichment_counter(codes, T, seed, 0, P, batch=8)
@@ -444,6 +445,69 @@ def test_enrichment_counter_narrow_form_at_30_types(oracle):
     dev = want[:-1] - want[-1]
     np.testing.assert_array_equal(obs, want[-1])
     np.testing.assert_array_equal(sums, np.stack([dev.sum(axis=0), (dev * dev).sum(axis=0), (dev >= 0).sum(axis=0)]))
+
+
+_NP_EDGE = dict(n=1500, k=4, P=37, seed=17, graph_seed=31, extent=400.0)
+_np_edge_shared = {}
+
+
+def _np_edge_case(oracle, T):
+    """The kNN graph of the NP-edge tests as the active graph, codes that use every one of T types, and (computed once,
+    shared, never written to) the graph's CSR by brute force and the first P counter-based permutations."""
+    c = _NP_EDGE
+    ctx, coords, codes = _knn_graph_and_codes(c["graph_seed"], c["n"], T, c["k"], c["extent"])
+    codes[:T] = np.arange(T)
+    if not _np_edge_shared:
+        _np_edge_shared["indices"] = oracle.knn_bruteforce(coords, c["k"]).reshape(-1)
+        _np_edge_shared["perms"] = np.stack([oracle.counter_permutation(c["seed"], c["n"], p) for p in range(c["P"])])
+    return ctx, codes, np.arange(0, c["n"] * c["k"] + 1, c["k"]), _np_edge_shared["indices"], _np_edge_shared["perms"]
+
+
+@pytest.mark.parametrize("T", [1, 2, 31, 32, 45, 46, 63, 64, 90, 91, 96])
+def test_enrichment_counter_at_the_np_steps_of_the_ordered_form(oracle, T):
+    """The ordered form of the pair kernel runs NP = 16 / 8 / 4 / 2 / 1 permutations per edge pass, the largest NP with
+    NP * (T T | 1) <= 16384 LDS words: 31 | 32, 45 | 46, 63 | 64 and 90 | 91 straddle its steps, 96 is the end of the
+    envelope.  37 counter-based permutations as one batch (64, clamped to 37: three 16-row word groups, the last with 5
+    rows, so passes start in later word groups) and as batches of 16 (the last with 5 rows): both give the observed table
+    and the three sum rows of the oracle's restatement, exactly."""
+    P, seed = _NP_EDGE["P"], _NP_EDGE["seed"]
+    ctx, codes, indptr, indices, perms = _np_edge_case(oracle, T)
+    want = oracle.enrichment_counts(indptr, indices, codes, T, perms)
+    dev = want[:-1] - want[-1]
+    sums = np.stack([dev.sum(axis=0), (dev * dev).sum(axis=0), (dev >= 0).sum(axis=0)])
+    for batch in (64, 16):
+        got_obs, got_sums = ctx.enrichment_counter(codes, T, seed, 0, P, batch=batch)
+        np.testing.assert_array_equal(got_obs, want[-1], err_msg=f"batch={batch}")
+        np.testing.assert_array_equal(got_sums, sums, err_msg=f"batch={batch}")
+
+
+@pytest.mark.parametrize("T", [5, 46, 91])
+def test_enrichment_counts_of_table_rows_at_an_offset(oracle, T):
+    """The table form goes through the label words too: 40 rows of the numpy stream are resident, and
+    enrichment_counts(codes, T, 33, perm_row0=3) gives the 33 tables of rows 3 .. 35 (word groups that start inside the
+    table, the last with one row) and then the observed one, at NP = 16, 4 and 1."""
+    from spatialcore_amd import _lib
+
+    ctx, codes, indptr, indices, _ = _np_edge_case(oracle, T)
+    ctx.generate_permutations(_lib.rng_state_words(np.random.default_rng(8)), _NP_EDGE["n"], 40)
+    got = ctx.enrichment_counts(codes, T, 33, perm_row0=3)
+    perms, _ = oracle.perm_table(8, _NP_EDGE["n"], 40)
+    np.testing.assert_array_equal(got, oracle.enrichment_counts(indptr, indices, codes, T, perms[3:36]))
+
+
+def test_enrichment_of_a_type_without_cells_is_a_zero_row(oracle):
+    """A type that no cell carries never appears at either end of an edge: its row and its column of every table are
+    zero, in the observed pass, the word path of the table form and the sums of the counter form."""
+    T, P, seed = 7, _NP_EDGE["P"], _NP_EDGE["seed"]
+    ctx, codes, indptr, indices, perms = _np_edge_case(oracle, T - 1)       # the codes use 0 .. T - 2
+    want = oracle.enrichment_counts(indptr, indices, codes, T, perms)
+    assert not want[:, T - 1].any() and not want[:, :, T - 1].any()
+    obs, sums = ctx.enrichment_counter(codes, T, seed, 0, P, batch=16)
+    dev = want[:-1] - want[-1]
+    np.testing.assert_array_equal(obs, want[-1])
+    np.testing.assert_array_equal(sums, np.stack([dev.sum(axis=0), (dev * dev).sum(axis=0), (dev >= 0).sum(axis=0)]))
+    ctx.set_permutations(perms)
+    np.testing.assert_array_equal(ctx.enrichment_counts(codes, T, P), want)
 
 
 def test_enrichment_counter_without_permutations_keeps_the_resident_table(oracle):

@@ -378,10 +378,10 @@ def test_config2_at_size_per_pair_permutations_lee_seeded(big, oracle):
 
 
 def test_config4_at_size_enrichment_k30(big, oracle):
-    """BASELINE configs[4] AT SIZE through k_enrich: 1M cells, k = 30 neighbour graph, 20 cell types, 600 label
-    permutations through the public neighborhood_enrichment (two generator batches), and the raw T x T count tables
-    of the observed labels and of three sampled permutations against the oracle's restatement on the host generator's
-    rows (exact integers)."""
+    """BASELINE configs[4] AT SIZE through the ordered form of k_lp_pairs: 1M cells, k = 30 neighbour graph, 20 cell
+    types, 600 label permutations through the public neighborhood_enrichment (two generator batches), and the raw
+    T x T count tables of the observed labels and of three sampled permutations against the oracle's restatement on
+    the host generator's rows (exact integers)."""
     from scipy.spatial import cKDTree
 
     from conftest import make_adata

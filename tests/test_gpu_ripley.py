@@ -206,6 +206,31 @@ def test_null_philox_source_and_disjoint_halves(oracle):
     np.testing.assert_array_equal(ctx.ripley_counts(c32, len(cats), 2, perm_row0=3)[:2], null[3:5])
 
 
+@pytest.mark.parametrize("T", [23, 32, 45, 64])
+def test_null_at_every_permutations_per_pass(oracle, T):
+    """Four radii and T = 23 / 32 / 45 / 64 give histograms of 2 T (T + 1) = 1104 / 2112 / 4140 / 8320 words: the
+    smallest T at which the pair kernel runs 8, 4, 2 and 1 permutations per pass (the largest NP with
+    NP * (words | 1) <= 16384; the tests above run 16).  21 counter-based permutations in batches of 8, the last ragged:
+    the observed table and the four sum rows equal the restatement, exactly; so do table rows at an offset."""
+    from spatialcore_amd import _lib
+
+    n, P, seed, radii = 1200, 21, 41, [4.0, 8.0, 13.0, 20.0]
+    rng = np.random.default_rng(16)
+    coords = rng.uniform(0, 250, (n, 2))
+    codes = rng.integers(0, T, n).astype(np.int32)
+    perms = np.stack([oracle.counter_permutation(seed, n, p) for p in range(P)])
+    null = null_tables(coords, codes, T, radii, perms)
+    obs = brute_counts(coords, codes, T, radii)
+    ctx = _lib.default_context(0)
+    ctx.ripley_build(coords, radii)
+    got_obs, got_sums = ctx.ripley_counter(codes, T, seed, 0, P, 8)
+    dev = null - obs
+    np.testing.assert_array_equal(got_obs, obs)
+    np.testing.assert_array_equal(got_sums, np.stack([dev.sum(0), (dev * dev).sum(0), (dev >= 0).sum(0), (dev <= 0).sum(0)]))
+    ctx.set_permutations(perms)
+    np.testing.assert_array_equal(ctx.ripley_counts(codes, T, 17, perm_row0=2), np.concatenate([null[2:19], obs[None]]))
+
+
 def test_run_to_run_identical_and_no_stale_state():
     from spatialcore_amd import _lib
     from spatialcore_amd.spatial import morans_i
