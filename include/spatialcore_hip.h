@@ -56,7 +56,10 @@ extern "C" {
 #define SC_K_GMM_POST 16     /* sc_gmm_posterior: P(high) and labels of every cell */
 #define SC_K_COOCCUR 17      /* sc_cooccurrence_2d: the all-pairs distance-bin histogram */
 #define SC_K_LIGREC 18       /* sc_ligrec_*: expression summed by (permuted) cluster label, observed pass included */
-#define SC_K_COUNT_ 19
+#define SC_K_RIPLEY_G_LIST 19    /* sc_ripley_g_build: count and fill passes of the ordered neighbour lists */
+#define SC_K_RIPLEY_G_RELABEL 20 /* sc_ripley_g_*: permutation rows -> label words at the cells' positions */
+#define SC_K_RIPLEY_G_COUNT 21   /* sc_ripley_g_*: the per-cell first-contact counting kernel, observed pass included */
+#define SC_K_COUNT_ 22
 
 typedef struct sc_ctx sc_ctx;
 
@@ -148,7 +151,7 @@ int sc_knn_fetch(sc_ctx *ctx, int32_t *idx_out, double *rdist_out);
  * Replaces cKDTree.query_ball_point(coords, r) with self removed (NB:241-244): closed ball
  * fl(dx*dx+dy*dy) <= fl(r*r).  Two-pass: count fills indptr_out[n+1]; fill writes nnz indices,
  * ascending within each row.  The binned coordinates of the count call stay resident for the fill call until the next
- * neighbour search of the context (sc_knn_2d, sc_radius_count_2d, sc_nearest_*, sc_ripley_build, sc_domains_2d): after one of those
+ * neighbour search of the context (sc_knn_2d, sc_radius_count_2d, sc_nearest_*, sc_ripley_build, sc_ripley_g_build, sc_domains_2d): after one of those
  * the fill call returns SC_ERR_STATE. */
 int sc_radius_count_2d(sc_ctx *ctx, const double *xy, int64_t n, double radius, int64_t *indptr_out);
 int sc_radius_fill_2d(sc_ctx *ctx, int64_t nnz, int32_t *indices_out);
@@ -416,7 +419,7 @@ int sc_kmeans_fit(sc_ctx *ctx, const void *X, int dtype, int64_t n, int32_t C, i
  * sc_ripley_build: bins the points and builds, on the device, the list of pairs within r_R, each with one byte (the
  *   index of the smallest radius that contains it).  The list is kept beside the active graph (which it does not touch)
  *   and stays valid until the next neighbour search of the context (sc_knn_2d, sc_radius_count_2d, sc_nearest_*,
- *   sc_ripley_build, sc_domains_2d): the counting entry points then return SC_ERR_STATE.  n_pairs_out = ordered pairs within r_R.
+ *   sc_ripley_build, sc_ripley_g_build, sc_domains_2d): the counting entry points then return SC_ERR_STATE.  n_pairs_out = ordered pairs within r_R.
  *   More than 4.2e9 stored pairs: SC_ERR_INVALID.
  * sc_ripley_counts: counts_out[((p T + a) T + b) R + j] for the label vectors labels[perm_p], perm_p = rows
  *   [perm_row0, perm_row0 + n_perm) of the active permutation table; p = n_perm holds the observed counts.
@@ -432,6 +435,39 @@ int sc_ripley_counts(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_ty
                      int64_t *counts_out);
 int sc_ripley_counter(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_types, uint64_t seed, int64_t p_first,
                       int64_t n_perm, int64_t batch, int64_t *observed_out, int64_t *sums_out);
+
+/* ---- N11 (extension; no reference site: spatstat's Gcross, squidpy's ripley(mode="G")) ----------------------------------
+ * Cross-type nearest-neighbour distance distribution G: cells with a neighbour of a type within a radius, by cell-type
+ * pair and radius, observed and under label permutations.
+ * Definition: for radii r_1 < ... < r_R (1 <= R <= 32) and T cell types,
+ *   count[a][b][j] = number of cells i of type a that have at least one OTHER cell i' != i of type b with
+ *                    fl(fl(dx dx) + fl(dy dy)) <= fl(r_j r_j)   (fp64, no FMA: the closed ball and the exact distance rule
+ *                    of sc_ripley_build / sc_radius_count_2d).  "Other" is decided by index: a coincident cell counts.
+ * The table is cumulative in j, count[a][b][j] <= n_a, and NOT symmetric in (a, b).  Integer arithmetic, exact,
+ * run-to-run identical.  G[a][b][j] = count / n_a (NaN where n_a = 0), the Poisson curve and the p-values are host
+ * arithmetic on these integers (spatialcore_amd.spatial.ripley_g).  No edge correction, as for N6: it cancels in the
+ * permutation null.  G is a minimum per cell, not a sum over pairs: none of the pair-count kernels can produce it.
+ *
+ * sc_ripley_g_build: bins the points (bins no smaller than r_R) and builds, on the device, the ORDERED neighbour lists
+ *   within r_R of every cell in bin-position order: per cell a row of (int32 column position, one byte = the index of the
+ *   smallest radius that contains the pair), the bytes of a row non-decreasing, with int64 offsets per row.  The lists
+ *   never visit the host.  They are kept beside the active graph and beside the pair list of sc_ripley_build (neither is
+ *   touched) and stay valid until the next neighbour search of the context (sc_knn_2d, sc_radius_count_2d, sc_nearest_*,
+ *   sc_ripley_build, sc_ripley_g_build, sc_domains_2d): the counting entry points then return SC_ERR_STATE ("no list").
+ *   n_entries_out = ordered pairs within r_R, the value sc_ripley_build reports.  More than 4.2e9 entries: SC_ERR_INVALID.
+ * sc_ripley_g_counts: counts_out[((p T + a) T + b) R + j] for the label vectors labels[perm_p], perm_p = rows
+ *   [perm_row0, perm_row0 + n_perm) of the active permutation table; p = n_perm holds the observed table.
+ * sc_ripley_g_counter: the same test for ONE RANK'S RANGE [p_first, p_first + n_perm) of counter-based permutations
+ *   (sc_perm_generate_counter's definition) in one call: batch b + 1 is generated on a second stream beside the counting
+ *   of batch b, and only integer sums come back -- observed_out[T*T*R]; sums_out[4][T*T*R], the four rows of
+ *   sc_ripley_counter: exact and order-free, ranks add theirs (sc_allreduce_sum_i64).
+ * Envelope: T <= 64 (one bit per type in the per-cell mask of types already seen) and T T R <= 16384 (one histogram of
+ * the ordered type pairs in 64 KB of LDS); beyond it SC_ERR_INVALID with the limit and the shape in the message. */
+int sc_ripley_g_build(sc_ctx *ctx, const double *xy, int64_t n, const double *radii, int32_t n_radii, int64_t *n_entries_out);
+int sc_ripley_g_counts(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_types, int64_t n_perm, int64_t perm_row0,
+                       int64_t *counts_out);
+int sc_ripley_g_counter(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_types, uint64_t seed, int64_t p_first,
+                        int64_t n_perm, int64_t batch, int64_t *observed_out, int64_t *sums_out);
 
 /* ---- N9 (extension; no reference site: squidpy's co_occurrence, the third cell-type pattern statistic beside ------
  * neighbourhood enrichment and Ripley's K) -- cell-type co-occurrence by distance: pair counts per type pair and
@@ -513,7 +549,7 @@ int sc_ligrec_counter(sc_ctx *ctx, const int32_t *labels, int64_t n, int32_t n_t
  *    within 2d, so it is unique), else -1.
  *  - n_queries = 0: components only (xy_queries and the query outputs may be null).
  * The targets are binned by the context's bin grid: like every neighbour search, the call ends a pending
- * sc_radius_count_2d and the pair list of sc_ripley_build.  Bad sizes, a non-finite or non-positive cell_dist, a shrink
+ * sc_radius_count_2d and the lists of sc_ripley_build and sc_ripley_g_build.  Bad sizes, a non-finite or non-positive cell_dist, a shrink
  * outside [0, cell_dist) or a non-finite coordinate give SC_ERR_INVALID with the argument in the message. */
 int sc_domains_2d(sc_ctx *ctx, const double *xy_targets, int64_t n_targets, const double *xy_queries, int64_t n_queries,
                   double cell_dist, double shrink, int32_t *target_component_out, int32_t *query_component_out,

@@ -26,6 +26,7 @@ K_RANK_EMIT, K_RANK_SORT, K_RANK_RUNS = 9, 10, 11
 K_THRESH_SCORE, K_THRESH_SORT, K_THRESH_KS, K_GMM_EM, K_GMM_POST = 12, 13, 14, 15, 16
 K_COOCCUR = 17
 K_LIGREC = 18
+K_RIPLEY_G_LIST, K_RIPLEY_G_RELABEL, K_RIPLEY_G_COUNT = 19, 20, 21
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
 
 # every symbol include/spatialcore_hip.h declares: (name, argtypes); restype is always int
@@ -97,6 +98,9 @@ SYMBOLS = {
     "sc_ripley_build": [_P, _P, c_int64, _P, c_int32, _P],
     "sc_ripley_counts": [_P, _P, c_int64, c_int32, c_int64, c_int64, _P],
     "sc_ripley_counter": [_P, _P, c_int64, c_int32, ctypes.c_uint64, c_int64, c_int64, c_int64, _P, _P],
+    "sc_ripley_g_build": [_P, _P, c_int64, _P, c_int32, _P],
+    "sc_ripley_g_counts": [_P, _P, c_int64, c_int32, c_int64, c_int64, _P],
+    "sc_ripley_g_counter": [_P, _P, c_int64, c_int32, ctypes.c_uint64, c_int64, c_int64, c_int64, _P, _P],
     "sc_cooccurrence_2d": [_P, _P, _P, c_int32, _P, c_int32, _P],
     "sc_ligrec_counts": [_P, _P, c_int64, c_int32, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P],
     "sc_ligrec_counter": [_P, _P, c_int64, c_int32, _P, _P, _P, c_int64, ctypes.c_uint64, c_int64, c_int64, c_int64, _P, _P, _P, _P],
@@ -229,6 +233,7 @@ class Context:
         self._h = h
         self.device = int(device)
         self._ripley_radii = 0   # radii of the resident Ripley pair list (shape of ripley_counts / ripley_counter results)
+        self._ripley_g_radii = 0   # ... and of the resident Ripley's G neighbour lists
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -890,6 +895,36 @@ class Context:
         sums = np.empty((4, n_types, n_types, self._ripley_radii), dtype=np.int64)
         _check(self._lib.sc_ripley_counter(self._h, _ptr(lab), lab.size, int(n_types), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                            int(p_first), int(n_perm), int(batch), _ptr(obs), _ptr(sums)))
+        return obs, sums
+
+    # ---- N11 (extension): Ripley's G --------------------------------------------------------
+    def ripley_g_build(self, coords, radii) -> int:
+        """Builds the device-resident ordered neighbour lists within radii[-1], one row per cell, each entry tagged with
+        the smallest radius that contains the pair; returns the number of entries (ORDERED pairs: nnz of the radius graph
+        at radii[-1], the value ``ripley_build`` returns).  The active graph and a Ripley pair list are untouched."""
+        xy = _c(coords, np.float64)
+        r = _c(radii, np.float64)
+        n_entries = c_int64(0)
+        _check(self._lib.sc_ripley_g_build(self._h, _ptr(xy), xy.shape[0], _ptr(r), r.size, byref(n_entries)))
+        self._ripley_g_radii = int(r.size)
+        return n_entries.value
+
+    def ripley_g_counts(self, labels, n_types: int, n_perm: int, perm_row0: int = 0) -> np.ndarray:
+        """(n_perm + 1, T, T, R) cumulative counts of cells of type a with a cell of type b within r_j, under rows
+        [perm_row0, perm_row0 + n_perm) of the resident permutation table; the last slice is the observed table."""
+        lab = _c(labels, np.int32)
+        out = np.empty((n_perm + 1, n_types, n_types, self._ripley_g_radii), dtype=np.int64)
+        _check(self._lib.sc_ripley_g_counts(self._h, _ptr(lab), lab.size, int(n_types), int(n_perm), int(perm_row0), _ptr(out)))
+        return out
+
+    def ripley_g_counter(self, labels, n_types: int, seed: int, p_first: int, n_perm: int, batch: int = 512):
+        """Observed (T, T, R) table and the four integer sum rows (deviation, squared deviation, #{>=}, #{<=}) over the
+        counter-based label permutations p_first .. p_first + n_perm - 1, generation overlapped with counting."""
+        lab = _c(labels, np.int32)
+        obs = np.empty((n_types, n_types, self._ripley_g_radii), dtype=np.int64)
+        sums = np.empty((4, n_types, n_types, self._ripley_g_radii), dtype=np.int64)
+        _check(self._lib.sc_ripley_g_counter(self._h, _ptr(lab), lab.size, int(n_types), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                             int(p_first), int(n_perm), int(batch), _ptr(obs), _ptr(sums)))
         return obs, sums
 
     # ---- N9 (extension): co-occurrence ------------------------------------------------------

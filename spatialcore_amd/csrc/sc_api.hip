@@ -178,6 +178,7 @@ int sc_ctx_destroy(sc_ctx *c)
                     &c->lee_rowmap, &c->lee_lperm, &c->g_slag, &c->g_xsum, &c->g_flags, &c->g_xmax, &c->g_lat, &c->g_meanc, &c->g_seff, &c->g_corr, &c->g_thr, &c->sims_raw, &c->g_order, &c->g_rank, &c->g_indices_r, &c->g_w32, &c->g_erow_r, &c->lm_ys, &c->lm_out, &c->lm_tab, &c->s0_tmp, &c->nib_map,
                     &c->np_cnt, &c->np_comp, &c->np_leaves, &c->np_leafsum,
                     &c->rp_cnt, &c->rp_indptr, &c->rp_row, &c->rp_col, &c->rp_bin, &c->rp_rank,
+                    &c->rg_cnt, &c->rg_indptr, &c->rg_col, &c->rg_bin, &c->rg_rank,
                     &c->dm_parent, &c->dm_qcomp, &c->dm_clear,
                     &c->rs_order, &c->rs_pstart, &c->rs_pgroup, &c->rs_gpiece, &c->rs_groupn, &c->rs_psum, &c->rs_pnnz, &c->rs_poff,
                     &c->rs_goff, &c->rs_neg, &c->rs_flag, &c->rs_keys, &c->rs_keys2, &c->rs_pay, &c->rs_pay2, &c->rs_gkey, &c->rs_gkey2,

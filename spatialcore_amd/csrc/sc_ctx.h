@@ -145,6 +145,12 @@ struct sc_ctx {
     int64_t rp_n = 0, rp_pairs = 0;   // cells, stored pairs (each unordered pair once: row position < column position)
     int rp_radii = 0;
     DBuf rp_cnt, rp_indptr, rp_row, rp_col, rp_bin, rp_rank;   // per-position counts / offsets, pair ends, radius bin (1 byte), cell -> position
+    // ---- Ripley's G neighbour lists (sc_ripley_g.hip): the ORDERED pairs within the largest radius as one row per position,
+    // kept beside the graph and beside the pair list above, valid exactly as long as the bins are (sc_bin_points clears rg_valid)
+    bool rg_valid = false;
+    int64_t rg_n = 0, rg_entries = 0;   // cells, stored entries (every ordered pair once)
+    int rg_radii = 0;
+    DBuf rg_cnt, rg_indptr, rg_col, rg_bin, rg_rank;   // per-position counts / row offsets, column position, radius bin (1 byte, non-decreasing within a row), cell -> position
     // ---- spatial domains (sc_domains.hip): union-find parents by target index, per-query component and clearance ----
     DBuf dm_parent, dm_qcomp, dm_clear;
     // ---- rank sums (sc_ranksum.hip): group-sorted cell order in pieces, per-piece partials, the pair arrays (double
@@ -324,7 +330,7 @@ static inline const int32_t *sc_processing_order(const sc_ctx *c, int64_t n)
 // ---- neighbour searches (sc_search.hip) ----
 // bins the points for a neighbour search (sx / sy / sid / bin_start; bins of side >= min_h, about target_per_bin points each).
 // The only function that replaces the bins, so it invalidates what is only meaningful on the bins it replaces: the pending
-// radius count (radius, rad_indptr) and the Ripley pair list (rp_valid).
+// radius count (radius, rad_indptr), the Ripley pair list (rp_valid) and the Ripley's G neighbour lists (rg_valid).
 int sc_bin_points(sc_ctx *c, const double *xy, int64_t n, double target_per_bin, double min_h);
 struct BinGrid;                         // sc_search.h
 BinGrid sc_bin_grid(const sc_ctx *c);   // the bins of the last sc_bin_points, as kernels take them

@@ -1,5 +1,5 @@
 // What the label-permutation tests share across translation units (sc_labelperm.hip: enrichment and Ripley's K, where
-// these are defined; sc_ligrec.hip: the ligand-receptor test).  gfx950 only.
+// these are defined; sc_ligrec.hip: the ligand-receptor test; sc_ripley_g.hip: Ripley's G).  gfx950 only.
 #pragma once
 
 #include <functional>
@@ -34,6 +34,16 @@ int lp_upload_labels(sc_ctx *c, const int32_t *labels, int64_t n, int32_t n_type
 // of `table` (row stride c->p_stride; rows clamped to rows - 1), one 16-byte word per cell and group of 16 rows.
 // rank = nullptr: the identity, the words stay in cell order (a test without a graph)
 void lp_relabel_words(sc_ctx *c, int64_t n, const int32_t *rank, const int32_t *table, int rows, uint4 *lab16);
+
+// k_lp_labels_by_position on c->stream: labp[r] = the label (scratch_idx) of the cell at position r, order[r]: the
+// observed labels as the one-byte "words" of a pass without a table (NP = 1, cell_bytes = 1)
+void lp_labels_by_position(sc_ctx *c, const int32_t *order, int64_t n, unsigned char *labp);
+
+// k_lp_sums on c->stream: the integer sums of the null over a batch of `rows` NON-cumulative tables counts[p][cells],
+// cells = type pairs x n_radii, against the observed one: sums[0 .. n_rows - 1][cells] += sum_p (u_p - u_obs),
+// sum_p (u_p - u_obs)^2, #{p : u_p >= u_obs} and (n_rows = 4) #{p : u_p <= u_obs} on the counts cumulated over the radii
+void lp_sums(sc_ctx *c, const unsigned long long *counts, const unsigned long long *obs, int rows, int cells, int n_radii,
+             int n_rows, long long *sums);
 
 // The batches of one rank's range of counter-based permutations p_first .. p_first + n_perm - 1, `batch` rows at a time
 // (the observed pass is the caller's).  Batch b's rows are generated into the permutation table on stream3; then, on

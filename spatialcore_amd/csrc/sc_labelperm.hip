@@ -5,7 +5,8 @@
 // under label permutations, with ONE counting kernel that differs only in how it indexes the histogram.  They share that
 // kernel with its plan and host helpers, the relabel kernels, the label upload, the kernel that adds a batch of tables to
 // the integer sums of the null, and the host driver of the counter-based batches (generation of batch b + 1 beside the
-// counting of batch b); each keeps its own checks of the graph or the pair list.
+// counting of batch b); each keeps its own checks of the graph or the pair list.  Ripley's G (sc_ripley_g.hip) takes a
+// minimum per cell, not a sum over pairs: it has its own lists and kernel and shares the helpers of sc_labelperm.h.
 #include <math.h>
 #include <stdlib.h>
 
@@ -97,6 +98,19 @@ int lp_upload_labels(sc_ctx *c, const int32_t *labels, int64_t n, int32_t n_type
     SC_HIP(hipMemcpyAsync(c->scratch_idx.p, lab8.data(), (size_t)n, hipMemcpyHostToDevice, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     return SC_OK;
+}
+
+void lp_labels_by_position(sc_ctx *c, const int32_t *order, int64_t n, unsigned char *labp)
+{
+    hipLaunchKernelGGL(k_lp_labels_by_position, dim3((unsigned)ceil_div64(n, 1024)), dim3(256), 0, c->stream,
+                       c->scratch_idx.as<unsigned char>(), order, n, labp);
+}
+
+void lp_sums(sc_ctx *c, const unsigned long long *counts, const unsigned long long *obs, int rows, int cells, int n_radii,
+             int n_rows, long long *sums)
+{
+    hipLaunchKernelGGL(k_lp_sums, dim3((unsigned)ceil_div64(cells, 256)), dim3(256), 0, c->stream, counts, obs, rows, cells,
+                       n_radii, n_rows, sums);
 }
 
 void lp_relabel_words(sc_ctx *c, int64_t n, const int32_t *rank, const int32_t *table, int rows, uint4 *lab16)
@@ -304,8 +318,7 @@ void lp_launch(sc_ctx *c, const LpPlan &pl, const LpPairs &pr, int np, int hstri
 // the observed labels by position into labp, their pair counts into out (one "permutation" without a table)
 void lp_observed(sc_ctx *c, const LpPlan &pl, const LpPairs &pr, int64_t n, unsigned char *labp, unsigned long long *out)
 {
-    hipLaunchKernelGGL(k_lp_labels_by_position, dim3((unsigned)ceil_div64(n, 1024)), dim3(256), 0, c->stream,
-                       c->scratch_idx.as<unsigned char>(), pr.order, n, labp);
+    lp_labels_by_position(c, pr.order, n, labp);
     lp_launch(c, pl, pr, 1, pl.cells, labp, 0, 1, 1, out);
 }
 
@@ -367,10 +380,7 @@ int lp_counter_sums(sc_ctx *c, const char *who, const LpPlan &pl, const LpPairs 
             lp_count_words(c, pl, pr, n, rows, d_cnt);
             return SC_OK;
         },
-        [&](int rows) {
-            hipLaunchKernelGGL(k_lp_sums, dim3((unsigned)ceil_div64(cells, 256)), dim3(256), 0, c->stream, d_cnt, d_obs, rows, cells,
-                               pl.R, n_rows, d_sums);
-        }));
+        [&](int rows) { lp_sums(c, d_cnt, d_obs, rows, cells, pl.R, n_rows, d_sums); }));
     SC_HIP(hipMemcpy(host, d_obs, res_bytes, hipMemcpyDeviceToHost));
     return SC_OK;
 }

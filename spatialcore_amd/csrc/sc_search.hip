@@ -68,6 +68,7 @@ int sc_bin_points(sc_ctx *c, const double *xy, int64_t n, double target_per_bin,
     // what is only meaningful on the bins this call replaces: the Ripley pair list holds positions of their order, and
     // the fill pass of a pending radius count walks them with rows sized by the count pass
     c->rp_valid = false;
+    c->rg_valid = false;
     c->radius = -1.0;
     SC_REQUIRE(n >= 1 && n <= 0x7fffffffLL, SC_ERR_INVALID, "n=%lld out of range", (long long)n);
     double xmin = DBL_MAX, xmax = -DBL_MAX, ymin = DBL_MAX, ymax = -DBL_MAX;

@@ -18,6 +18,7 @@ from spatialcore_amd.spatial.neighborhoods import (
     identify_niches,
     ligrec,
     neighborhood_enrichment,
+    ripley_g,
     ripley_k,
 )
 
@@ -35,6 +36,7 @@ __all__ = [
     "ripley_k",  # extension: not in the reference
     "co_occurrence",  # extension: squidpy's function, not in the reference
     "ligrec",  # extension: squidpy's function, not in the reference
+    "ripley_g",  # extension: not in the reference
     "make_spatial_domains",
     "get_domain_summary",
     "calculate_domain_distances",

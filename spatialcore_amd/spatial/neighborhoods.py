@@ -7,7 +7,8 @@ Neighbour search (exact kNN or closed-ball radius) and the per-cell label counti
 kernels.  ``identify_niches`` (NB:299-522) clusters the profiles with sklearn's k-means (k-means++ seeding, Lloyd
 iterations, best of ``n_init`` runs) replayed step for step in HIP (``sc_kmeans_fit``).
 ``neighborhood_enrichment``, ``ripley_k`` and ``co_occurrence`` are extensions: the three cell-type pattern statistics
-squidpy users run on an annotated section, as exact integer pair counts.  ``ligrec`` is the
+squidpy users run on an annotated section, as exact integer pair counts; ``ripley_g`` is the
+nearest-neighbour counterpart of ``ripley_k``, a minimum per cell where those are sums over pairs.  ``ligrec`` is the
 fourth extension under squidpy's name: the ligand-receptor permutation test over cluster pairs, expression summed by
 permuted label as exact integers.
 """
@@ -145,7 +146,7 @@ def _label_permutation_null(ctx, n_cells: int, n_permutations: int, seed: int, p
 
 def _pair_count_null(ctx, counts, counter, codes, n_types: int, n_sums: int, n_permutations: int, seed: int,
                      perm_batch: int, rng: str, comm):
-    """``_label_permutation_null`` of ``neighborhood_enrichment`` and ``ripley_k``: the observed table and the integer
+    """``_label_permutation_null`` of ``neighborhood_enrichment``, ``ripley_k`` and ``ripley_g``: the observed table and the integer
     sums of the null: sum of (null - observed), sum of (null - observed)^2, #{null >= observed} and, with
     ``n_sums = 4``, #{null <= observed}.  ``counts(codes, T, rows)``: the tables of the resident permutation rows, then
     the observed one; ``counter(codes, T, seed, lo, n, batch)``: the observed table and the sums, from one device call
@@ -324,9 +325,11 @@ def neighborhood_enrichment(
     return adata
 
 
-def _ripley_request_problem(adata, celltype_column, radii, n_permutations, area, spatial_key, rng, comm) -> Optional[str]:
-    """The first thing wrong with a ``ripley_k`` request (checked before any device work), else None."""
-    problem = _point_pattern_request_problem(adata, celltype_column, spatial_key, "Ripley's K")
+def _ripley_request_problem(adata, celltype_column, radii, n_permutations, area, spatial_key, rng, comm,
+                            what: str = "Ripley's K") -> Optional[str]:
+    """The first thing wrong with a ``ripley_k`` or ``ripley_g`` (``what``) request (checked before any device work),
+    else None."""
+    problem = _point_pattern_request_problem(adata, celltype_column, spatial_key, what)
     if problem:
         return problem
     try:
@@ -456,6 +459,114 @@ def ripley_k(
                     "seed": seed, "area": float(area), "spatial_key": spatial_key, "rng": rng,
                     "permgen_form": _permgen_form(ctx, n_cells, rng, n_permutations)},
         outputs={"uns": key_added, "n_celltypes": T, "n_cells": n_cells, "n_radii": R, "n_pairs": n_pairs},
+    )
+    return adata
+
+
+def ripley_g_statistics(count, n_per_type, area: float, sums=None, n_permutations: int = 0, *, radii=None) -> dict:
+    """G, its Poisson curve and the permutation statistics from the integer tables alone (pure host arithmetic, no device).
+
+    ``count``: (T, T, R) cumulative counts of the cells of type a with at least one other cell of type b within ``r_j``;
+    ``n_per_type``: (T,) cells per type.  ``G[a, b, j] = count[a, b, j] / n_a``, NaN where ``n_a = 0``.  With ``radii``
+    (the R radii), ``G_poisson[a, b, j] = 1 - exp(-lambda pi r_j^2)`` with ``lambda = n_b / area``, and
+    ``(n_a - 1) / area`` on the diagonal (a cell is not its own neighbour): the curve of complete spatial randomness at
+    the types' densities, for plotting only -- the inference is the permutation null.  ``sums``: (4, T, T, R) integers
+    over the ``n_permutations`` null tables -- sum of (null - count), sum of (null - count)^2, #{null >= count},
+    #{null <= count} -- giving ``mean``, ``std`` (population), ``zscore = (count - mean) / std``,
+    ``p_value = (#{>=} + 1) / (P + 1)`` (attraction: b nearer to a than under random labelling) and
+    ``p_value_less = (#{<=} + 1) / (P + 1)``.
+    """
+    count = np.asarray(count, dtype=np.int64)
+    n_t = np.asarray(n_per_type, dtype=np.int64)
+    n_a = np.where(n_t > 0, n_t, 1).astype(np.float64)
+    out = {"G": np.where((n_t > 0)[:, None, None], count / n_a[:, None, None], np.nan)}
+    if radii is not None:
+        r = np.asarray(radii, dtype=np.float64)
+        others = np.broadcast_to(n_t[None, :], (n_t.size, n_t.size)).astype(np.float64)   # [a, b] = n_b ...
+        others[np.diag_indices(n_t.size)] = np.maximum(n_t - 1, 0)                          # ... and n_a - 1 for b = a
+        out["G_poisson"] = 1.0 - np.exp(-(others / float(area))[:, :, None] * (np.pi * r * r)[None, None, :])
+    if n_permutations > 0:
+        out.update(_null_statistics(count, sums, n_permutations))
+    return out
+
+
+def ripley_g(
+    adata,
+    celltype_column: str,
+    radii,
+    n_permutations: int = 0,
+    seed: int = 0,
+    area: Optional[float] = None,
+    spatial_key: str = "spatial",
+    key_added: str = "ripley_g",
+    copy: bool = False,
+    *,
+    device: int = 0,
+    perm_batch: int = 512,
+    rng: str = "numpy",
+    comm=None,
+):
+    """Cross-type nearest-neighbour distance distribution G at several radii, with a label-permutation null.
+
+    EXTENSION -- spatstat's ``Gcross``, squidpy's ``ripley(mode="G")``: how far is a cell of type a from its nearest
+    cell of type b, and is that nearer or farther than random labelling would give?  ``ripley_k`` and this function are
+    read together: K is a sum over pairs and is dominated by dense clumps, G is a minimum per cell and speaks for the
+    typical cell.  Semantics defined here (include/spatialcore_hip.h, N11): for radii ``r_1 < ... < r_R`` (at most 32),
+    ``count[a, b, j]`` = number of cells i of type a with at least one OTHER cell i' of type b at squared distance
+    ``fl(fl(dx dx) + fl(dy dy)) <= fl(r_j r_j)`` (fp64, the closed ball of the radius graph and of ``ripley_k``; "other"
+    is decided by index, so a coincident cell counts).  The table is cumulative in j, ``count[a, b, j] <= n_a`` and NOT
+    symmetric in (a, b).  ``G[a, b, j] = count / n_a`` (NaN where ``n_a = 0``); ``G_poisson`` is the curve of complete
+    spatial randomness at the types' densities (``ripley_g_statistics``), for plotting; ``area`` defaults to the
+    bounding box of all cells and enters ``G_poisson`` only.  NO EDGE CORRECTION is applied: it cancels in the
+    permutation null, which is the inference this function offers.
+
+    Null: the label vector permuted ``n_permutations`` times exactly as ``ripley_k`` does it (``rng="numpy"``:
+    ``default_rng(seed).permutation(n)`` continued across batches; ``rng="philox"``: counter-based, and with ``comm``
+    sharded over the ranks and merged by one integer all-reduce).  Stored in ``adata.uns[key_added]``: ``radii``,
+    ``celltypes``, ``n_per_type``, ``area``, ``count`` (T, T, R int64), ``G``, ``G_poisson`` and, with permutations,
+    ``mean``, ``std`` (population), ``zscore``, ``p_value = (#{null >= count} + 1) / (P + 1)`` (attraction),
+    ``p_value_less = (#{null <= count} + 1) / (P + 1)``, plus ``n_permutations``, ``seed``, ``rng``.
+
+    The ordered neighbour lists within ``r_R`` are built on the device once and never visit the host; every batch of
+    permutations is one pass over them.  Envelope: at most 64 cell types and ``T * T * R <= 16384``.
+    """
+    problem = _ripley_request_problem(adata, celltype_column, radii, n_permutations, area, spatial_key, rng, comm,
+                                      "Ripley's G")
+    if problem:
+        raise ValueError(problem)
+    if copy:
+        adata = adata.copy()
+    n_cells = adata.n_obs
+    celltypes, codes = _label_codes(adata, celltype_column)
+    coords = _coordinates(adata, spatial_key)
+    radii = np.ascontiguousarray(radii, dtype=np.float64)
+    T, R = len(celltypes), radii.size
+    if area is None:
+        ext = coords.max(axis=0) - coords.min(axis=0) if n_cells else np.zeros(2)
+        area = float(ext[0] * ext[1])
+        if not area > 0:
+            raise ValueError(f"the bounding box of the cells has area {area}; pass area= explicitly")
+    logger.info(f"Computing Ripley's G: {n_cells:,} cells, {T} cell types, {R} radii up to {radii[-1]:g}, "
+                f"permutations={n_permutations}")
+
+    ctx = _lib.default_context(device)
+    n_entries = ctx.ripley_g_build(coords, radii)
+    logger.debug(f"{n_entries:,} list entries (ordered pairs) within r={radii[-1]:g}")
+
+    observed, sums = _pair_count_null(ctx, ctx.ripley_g_counts, ctx.ripley_g_counter, codes, T, 4, n_permutations, seed,
+                                      perm_batch, rng, comm)
+    n_per_type = np.bincount(codes, minlength=T).astype(np.int64)
+    result = {"radii": radii, "celltypes": list(celltypes), "n_per_type": n_per_type, "area": float(area), "count": observed}
+    result.update(ripley_g_statistics(observed, n_per_type, area, sums, n_permutations, radii=radii))
+    result.update({"n_permutations": n_permutations, "seed": seed, "rng": rng})
+    adata.uns[key_added] = result
+    update_metadata(
+        adata,
+        function_name="ripley_g",
+        parameters={"celltype_column": celltype_column, "radii": [float(r) for r in radii], "n_permutations": n_permutations,
+                    "seed": seed, "area": float(area), "spatial_key": spatial_key, "rng": rng,
+                    "permgen_form": _permgen_form(ctx, n_cells, rng, n_permutations)},
+        outputs={"uns": key_added, "n_celltypes": T, "n_cells": n_cells, "n_radii": R, "n_entries": n_entries},
     )
     return adata
 
