@@ -502,3 +502,53 @@ def test_config4_at_size_philox_enrichment_2048_permutations(big, oracle):
     np.testing.assert_array_equal(res["p_value"], (sums[2] + 1) / (P + 1))
     np.testing.assert_allclose(res["mean"], obs + sums[0] / P, rtol=1e-12)
     assert ad.uns["spatialcore_metadata"]["operations"][-1]["parameters"]["permgen_form"] == "counter-based (philox)"
+
+
+# ---- sc_ranksum: the second sort batch, at the smallest size that has one ---------------------------------------------------
+
+@pytest.fixture(scope="module")
+def two_batches():
+    """4.2M cells x 32 genes of tests/test_cpu_markers.py::closed_form_gene as float64 (every value 0 .. 1,399,999 three
+    times per gene): a tile of 16 genes holds 67,199,952 pairs <= 2^27 and two tiles hold more, so sc_ranksum sorts the
+    two tiles in two batches.  The expected tables are closed forms (closed_form_tables, checked against the rankdata
+    restatement at 4,200 cells on the CPU): nothing is sorted on the host."""
+    from test_cpu_markers import closed_form_gene, closed_form_tables
+    from test_gpu_markers import _codes
+
+    n = 4_200_000
+    code = _codes(n, 12)
+    X = np.empty((n, 32), dtype=np.float64)
+    for g in range(32):
+        X[:, g] = closed_form_gene(n, g)
+    yield X, code, closed_form_tables(n, code, 5)
+
+
+@pytest.mark.parametrize("scaled", ["second tile", "first tile"])
+def test_ranksum_second_sort_batch(two_batches, scaled):
+    """The batch at base = 67,199,952, gene0 = 16, tile0 = 1 of sc_ranksum: every `- base`, `gene0 +` and `tile0 +` of
+    its kernels.  The scaled tile (v * 0.1: not float32-exact) takes the two-pass fp64 sort, the integer tile the
+    one-pass float32 sort; "second tile" runs the two-pass form in the second batch, "first tile" the one-pass form.
+    Ranks do not change under the monotone scaling, so every integer output is the closed form of both tiles.  sums:
+    == for the integer tile; the scaled tile at rtol 1e-12 against 0.1 * (the exact integer sum), which is the sum of
+    the rounded products fl(0.1 v) to 2^-53 relative (every term is positive and rounded once).
+    The other split condition of the batches, more than 2^20 genes in one batch, is out of reach at any size a test can
+    have and is not covered."""
+    import time
+
+    from test_gpu_markers import INT_KEYS, _ranksum
+
+    X, code, want = two_batches
+    tile = slice(16, 32) if scaled == "second tile" else slice(0, 16)
+    whole = slice(0, 16) if scaled == "second tile" else slice(16, 32)
+    Xs = X.copy()
+    Xs[:, tile] *= 0.1
+    assert (Xs[:1000, tile].astype(np.float32).astype(np.float64) != Xs[:1000, tile]).any()
+    t0 = time.perf_counter()
+    got = _ranksum(Xs, code, 5)
+    print(f"sc_ranksum with set_expression, 4.2M x 32, scaled {scaled}: {time.perf_counter() - t0:.2f} s")
+    del Xs
+    for k in INT_KEYS:
+        np.testing.assert_array_equal(got[k], want[k], err_msg=k)
+    assert [int(t) for t in got["tie_nonzero"]] == [24 * 1_399_999] * 32
+    np.testing.assert_array_equal(got["sums"][whole], want["sums"][whole])
+    np.testing.assert_allclose(got["sums"][tile], 0.1 * want["sums"][tile], rtol=1e-12, atol=0.0)

@@ -37,6 +37,43 @@ def integer_tables(X, code, n_groups):
             "n_neg": (Xr < 0).sum(axis=0).astype(np.int64), "group_n": np.bincount(cr, minlength=n_groups).astype(np.int64)}
 
 
+def integer_tables_bincount(X, code, n_groups):
+    """integer_tables for many groups: the same dict, one np.bincount per gene and table instead of a mask per (gene,
+    group).  The weights of ``rank2`` are the integers 2 * rank, and every partial sum of them stays below
+    N (N + 1) < 2^53, so the float64 accumulator of bincount is exact.  ``sums`` is not taken with bincount: its running
+    sum in cell order is up to n_k * eps * sum |x| away from the pairwise x[sel].sum() of integer_tables, which is no
+    relative bound at all once a group's values cancel.  The cells are sorted by group once (stably: cell order inside a
+    group) and every occupied group's slice is summed as integer_tables sums it."""
+    X = dense(X).astype(np.float64)
+    code = np.asarray(code)
+    ranked = code >= 0
+    Xr, cr = X[ranked], code[ranked].astype(np.int64)
+    N, G = Xr.shape
+    assert N * (N + 1) < 2 ** 53
+    group_n = np.bincount(cr, minlength=n_groups).astype(np.int64)
+    by_group = np.argsort(cr, kind="stable")
+    ends = np.cumsum(group_n)
+    occupied = [(k, int(ends[k] - group_n[k]), int(ends[k])) for k in np.flatnonzero(group_n)]
+    rank2 = np.zeros((G, n_groups), dtype=np.int64)
+    nnz = np.zeros((G, n_groups), dtype=np.int64)
+    sums = np.zeros((G, n_groups), dtype=np.float64)
+    tie_nonzero, tie_all = [], []
+    for g in range(G):
+        x = Xr[:, g]
+        r2 = 2.0 * rankdata(x) if x.size else np.zeros(0)
+        assert (r2 == np.rint(r2)).all()
+        rank2[g] = np.bincount(cr, weights=r2, minlength=n_groups).astype(np.int64)
+        nnz[g] = np.bincount(cr[x != 0], minlength=n_groups)
+        xs = x[by_group]
+        for k, a, b in occupied:
+            sums[g, k] = xs[a:b].sum()
+        vals, counts = np.unique(x, return_counts=True)
+        tie_all.append(sum(int(t) ** 3 - int(t) for t in counts))
+        tie_nonzero.append(sum(int(t) ** 3 - int(t) for v, t in zip(vals, counts) if v != 0))
+    return {"rank2": rank2, "tie_nonzero": np.array(tie_nonzero, dtype=object), "tie_all": tie_all, "nnz": nnz, "sums": sums,
+            "n_neg": (Xr < 0).sum(axis=0).astype(np.int64), "group_n": group_n}
+
+
 def benjamini_hochberg(p):
     m = len(p)
     order = sorted(range(m), key=lambda i: (p[i], i))
