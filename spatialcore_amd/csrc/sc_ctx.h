@@ -105,6 +105,16 @@ struct PermGen {
     }
 };
 
+// Moran's partial sums as a ring of slices (sc_moran.hip): scoring launch k of a job writes slice k % MORAN_RING on the
+// context stream, and its finalise reads that slice on the side stream (sc_ctx::stream_out) beside launch k + 1
+constexpr int MORAN_RING = 3;
+struct MoranRing {
+    size_t slice = 0;                   // doubles per slice: one chunk's partial sums (sized by moran_prepare)
+    int64_t launches = 0;               // scoring launches of the job so far (0 again once moran_finish has waited for them)
+    hipEvent_t scored[MORAN_RING] = {}; // behind the scoring launch that last wrote the slice
+    hipEvent_t done[MORAN_RING] = {};   // behind the finalise that last read it
+};
+
 struct PermPipe;   // a generator job in flight (sc_permgen.h, sc_perm.hip; begun by sc_moran_seeded_begin, consumed by _finish)
 
 struct sc_ctx {
@@ -114,7 +124,8 @@ struct sc_ctx {
     hipStream_t stream2 = nullptr;  // fused permutation/Moran pipeline: rejection scan runs ahead here
     hipStream_t stream3 = nullptr;  // ... and the Fisher-Yates swaps of the scanned chunk here
     hipStream_t stream4 = nullptr;  // ... alternating with this one
-    hipStream_t stream_out = nullptr;    // r04: result copies that run beside a pipeline, issued by a helper thread (sc_local_moran_seeded, sc_local_stat_seeded)
+    hipStream_t stream_out = nullptr;    // r04: what leaves a pipeline beside it: result copies issued by a helper thread (sc_local_moran_seeded,
+                                         // sc_local_stat_seeded); Moran's finalise launches, beside the next chunk's scoring (sc_moran.hip: MoranRing)
     PermGen pg;       // the numpy-exact permutation generator's state
     int64_t mem = 0;  // bytes allocated through DBuf
     bool timing = true;
@@ -222,7 +233,8 @@ struct sc_ctx {
     bool perm_checked = false;     // ... or was checked and is not
 
     // ---- Moran / Lee work buffers ----
-    DBuf partial, sims, counts, sim_sum, sim_sumsq;
+    DBuf partial, sims, counts, sim_sum, sim_sumsq;   // partial: MORAN_RING slices
+    MoranRing ring;
     // everybody's scratch (Lee, the label-permutation tests, the graph builders, the per-cell statistics): an entry point
     // lays them out as it likes, and their contents are not kept from one entry point to the next
     DBuf scratch_a, scratch_b, scratch_out, scratch_idx;
@@ -259,12 +271,14 @@ constexpr int64_t PIPE_TAIL[] = {96, 48, 24};      // permutations of the taperi
 constexpr int64_t PIPE_TAIL_TOTAL = 96 + 48 + 24;
 int pipe_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int table, int units_ahead, PermPipe &pp,
                int64_t chunks_ahead, const std::function<int()> &after_first_chunk = nullptr);
-int pipe_consume(sc_ctx *c, PermPipe &pp, uint64_t *state6, const std::function<int()> &after_first,
-                 const std::function<int(int64_t, int64_t)> &score);
+// the consumer's set-up in two callbacks (either may be empty): `enqueue` must not wait for the device, `complete` may
+int pipe_consume(sc_ctx *c, PermPipe &pp, uint64_t *state6, const std::function<int()> &enqueue,
+                 const std::function<int()> &complete, const std::function<int(int64_t, int64_t)> &score);
 void pipe_drain(sc_ctx *c, PermPipe &pp);
 void sc_perm_pipe_abort(sc_ctx *c);    // drain and drop c->pipe (no results)
 int sc_perm_pipeline(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_perm, int table, int units_ahead,
-                     const std::function<int()> &after_first, const std::function<int(int64_t, int64_t)> &score);
+                     const std::function<int()> &enqueue, const std::function<int()> &complete,
+                     const std::function<int(int64_t, int64_t)> &score);
 // Runs attempt(); if the block-parallel scan failed its verification, runs undo() (may be empty) and then attempt() once
 // more with the sequential scan.  The generator's mode is the caller's again on return, on every path.
 int permgen_rerun_on_failure(sc_ctx *c, const std::function<int()> &attempt, const std::function<int()> &undo);

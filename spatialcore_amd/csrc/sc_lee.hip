@@ -208,7 +208,7 @@ static int lee_counted_pipeline(sc_ctx *c, uint64_t *state6, int64_t rows, int64
     const size_t bytes = sizeof(unsigned long long) * (size_t)n_cnt;
     SC_HIP(hipMemcpyAsync(backup, cnt, bytes, hipMemcpyDeviceToDevice, c->stream));
     return permgen_rerun_on_failure(
-        c, [&]() { return sc_perm_pipeline(c, state6, c->e_n, rows, 0, 2, nullptr, score); },
+        c, [&]() { return sc_perm_pipeline(c, state6, c->e_n, rows, 0, 2, nullptr, nullptr, score); },
         [&]() -> int {
             SC_HIP(hipMemcpyAsync(cnt, backup, bytes, hipMemcpyDeviceToDevice, c->stream));
             return SC_OK;

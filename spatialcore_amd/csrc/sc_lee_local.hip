@@ -189,7 +189,7 @@ extern "C" int sc_lee_local_seeded(sc_ctx *c, uint64_t *state6, int32_t gene_x, 
     };
     // a job that fails its verification is rerun with the sequential scan: everything restarts at permutation 0 (the
     // first rows' flag restarts the counts)
-    SC_TRY(permgen_rerun_on_failure(c, [&]() { return sc_perm_pipeline(c, state6, n, Pg + Pl, 0, 2, prepare, score); }, nullptr));
+    SC_TRY(permgen_rerun_on_failure(c, [&]() { return sc_perm_pipeline(c, state6, n, Pg + Pl, 0, 2, nullptr, prepare, score); }, nullptr));
     SC_TRY(ll_download(c, j, zx_out, lag_out, L_local_out, Pl > 0 ? count_out : nullptr));
     return lee_pair_finish(c, g, L_out, count_abs_ge_out, nullptr);
 }

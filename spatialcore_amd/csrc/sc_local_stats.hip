@@ -562,7 +562,7 @@ static int local_run_seeded(sc_ctx *c, const char *who, int stat, int star, uint
     // a job that fails its verification is rerun with the sequential scan: the counts restart at permutation 0, and the
     // copier is joined first (the second preparation rewrites what it reads -- with the same values)
     const int rc = permgen_rerun_on_failure(
-        c, [&]() { return sc_perm_pipeline(c, state6, c->e_n, n_perm, 0, 2, prepare, score); },
+        c, [&]() { return sc_perm_pipeline(c, state6, c->e_n, n_perm, 0, 2, nullptr, prepare, score); },
         [&]() { copier.reset(); return SC_OK; });
     copier.reset();
     SC_TRY(rc);

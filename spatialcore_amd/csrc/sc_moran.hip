@@ -993,6 +993,70 @@ __global__ __launch_bounds__(256) void k_moran_finalize_nib(const double *__rest
     sims[(p0 + p) * n_genes + g] = seff[g] * (s - corr[g]);
 }
 
+// ---- the ring of partial-sum slices (MoranRing, sc_ctx.h) ----
+// Nothing reads sims before k_moran_count at the end of the job, so a chunk's finalise need not sit between two scoring
+// launches on the context stream (bench size: eleven finalise launches of 0.2-1.25 ms, each re-reading up to 256 MB while
+// the scoring's CUs wait, and a launch boundary more each).  With one slice per launch in flight the finalise runs on the
+// side stream beside the NEXT scoring launch.  Its kernels and their order of summation are unchanged: every output is
+// bit-identical to the in-line form.  What the step gains (it is bound by the generator until its last chunks, so only
+// the launches behind those count): DESIGN.md sections 4.3 and 5.
+
+// a new job: R slices of `slice` doubles, no launch yet
+static int moran_ring_begin(sc_ctx *c, size_t slice)
+{
+    MoranRing &r = c->ring;
+    if (!c->stream_out) SC_HIP(hipStreamCreateWithFlags(&c->stream_out, hipStreamNonBlocking));
+    // (a job that ended in an error may have left finalise launches behind: they read what this job's set-up rewrites)
+    if (r.launches > 0) SC_HIP(hipStreamSynchronize(c->stream_out));
+    for (int k = 0; k < MORAN_RING; ++k) {
+        if (!r.scored[k]) SC_HIP(hipEventCreateWithFlags(&r.scored[k], hipEventDisableTiming));
+        if (!r.done[k]) SC_HIP(hipEventCreateWithFlags(&r.done[k], hipEventDisableTiming));
+    }
+    SC_TRY(c->partial.ensure(sizeof(double) * slice * MORAN_RING, &c->mem));
+    r.slice = slice;
+    r.launches = 0;
+    return SC_OK;
+}
+
+// the slice of the job's next scoring launch; the context stream waits for the finalise that read it MORAN_RING
+// launches ago (long done in practice: the finalise takes a tenth of a scoring launch)
+static int moran_ring_slice(sc_ctx *c, double **slice)
+{
+    MoranRing &r = c->ring;
+    const int k = (int)(r.launches % MORAN_RING);
+    if (r.launches >= MORAN_RING) SC_HIP(hipStreamWaitEvent(c->stream, r.done[k], 0));
+    *slice = c->partial.as<double>() + (size_t)k * r.slice;
+    return SC_OK;
+}
+
+// behind the scoring launch: the side stream, ready for that launch's finalise
+static int moran_ring_scored(sc_ctx *c)
+{
+    MoranRing &r = c->ring;
+    const int k = (int)(r.launches % MORAN_RING);
+    SC_HIP(hipEventRecord(r.scored[k], c->stream));
+    SC_HIP(hipStreamWaitEvent(c->stream_out, r.scored[k], 0));
+    return SC_OK;
+}
+
+// behind the finalise launch
+static int moran_ring_finalised(sc_ctx *c)
+{
+    MoranRing &r = c->ring;
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipEventRecord(r.done[r.launches % MORAN_RING], c->stream_out));
+    r.launches += 1;
+    return SC_OK;
+}
+
+// the context stream waits for every finalise of the job (the side stream runs them in order)
+static int moran_ring_join(sc_ctx *c)
+{
+    MoranRing &r = c->ring;
+    if (r.launches > 0) SC_HIP(hipStreamWaitEvent(c->stream, r.done[(r.launches - 1) % MORAN_RING], 0));
+    return SC_OK;
+}
+
 // Everything the permutation kernels need, from the loaded tiles and the active graph:
 //   value class + lattice decision per gene (one pass + one host sync), Z = X - centre, Lag = W Z (lattice genes: the
 //   unweighted neighbour sums of the raw counts), I, the per-gene finalisation constants, the narrow copy of the batch.
@@ -1173,15 +1237,15 @@ static int moran_prepare(sc_ctx *c, int64_t n_perm, bool allow_lattice)
                        c->g_I.as<double>(), (double)n / c->s0, c->g_uniform_w, T * SC_TILE);
     SC_HIP(hipGetLastError());
     if (n_perm > 0) {
-        // partial sums for one chunk of permutations (<= PERM_CHUNK): the persistent kernel keeps one row per
-        // (128-gene-padded gene, split, permutation); the index-row kernel one per (16 genes, split, permutation)
+        // partial sums for one chunk of permutations (<= PERM_CHUNK), one slice of the ring: the persistent kernel keeps one row
+        // per (128-gene-padded gene, split, permutation); the index-row kernel one per (16 genes, split, permutation)
         int64_t cps = 0;
         const int splits64 = pick_splits(n, 1, &cps);  // upper bound on the index-row kernel's split count
         const int64_t score_splits = ceil_div64(n, score_cells_per_split(n));
         size_t narrow_rows = (size_t)score_splits * (size_t)align_up64(T * SC_TILE, 128);
         if (nib && (size_t)score_splits * (size_t)nib_groups * 256 > narrow_rows) narrow_rows = (size_t)score_splits * (size_t)nib_groups * 256;
         const size_t wide_rows = (size_t)splits64 * SC_TILE;
-        SC_TRY(c->partial.ensure(sizeof(double) * (size_t)n_perm * (narrow_rows > wide_rows ? narrow_rows : wide_rows), &c->mem));
+        SC_TRY(moran_ring_begin(c, (size_t)n_perm * (narrow_rows > wide_rows ? narrow_rows : wide_rows)));
         // the gathered operand: the raw values in the narrowest type that holds every gene of the batch exactly
         if (bits < 64 && bits > 4 && !u8_prelude && !narrow_packed) SC_TRY(expr_pack_narrow(c, bits));
     }
@@ -1189,7 +1253,7 @@ static int moran_prepare(sc_ctx *c, int64_t n_perm, bool allow_lattice)
 }
 
 template <int BITS, int CB, bool BIG, bool L16 = false>
-static void launch_score(sc_ctx *c, int wgs, const uint4 *rows, int64_t p0, int cnt, int64_t cps, int splits, int groups)
+static void launch_score(sc_ctx *c, int wgs, const uint4 *rows, double *partial, int64_t p0, int cnt, int64_t cps, int splits, int groups)
 {
     // the workgroup form scores 128 permutations per task; wavefronts beyond a short chunk's permutations only help with
     // the lag rows.  Below SCORE_WG_MIN_PERMS live permutations a compute unit has too few gathers in flight: such chunks
@@ -1203,7 +1267,7 @@ static void launch_score(sc_ctx *c, int wgs, const uint4 *rows, int64_t p0, int 
         // fewer, the step the same within its noise either way, and with 151 as well.  Not kept.)
         hipLaunchKernelGGL((k_moran_score_wg<BITS, CB, BIG, L16>), dim3((unsigned)wgs), dim3(SCORE_WAVES * 64), 0, c->stream, rows,
                            c->Lag.as<double>(), (int64_t)c->e_n * SC_TILE, (int)c->e_tiles, c->g_meanc.as<double>(),
-                           c->inv.as<int32_t>() + p0 * c->p_stride, c->partial.as<double>(), c->e_n, c->p_stride, cnt, cps,
+                           c->inv.as<int32_t>() + p0 * c->p_stride, partial, c->e_n, c->p_stride, cnt, cps,
                            splits, groups);
         return;
     }
@@ -1211,11 +1275,11 @@ static void launch_score(sc_ctx *c, int wgs, const uint4 *rows, int64_t p0, int 
     hipLaunchKernelGGL((k_moran_score<BITS, CB, BIG, L16>), dim3((unsigned)(wgs * (SCORE_WAVES / SCORE_PRIVATE_WAVES))),
                        dim3(SCORE_PRIVATE_WAVES * 64), 0, c->stream, rows,
                        c->Lag.as<double>(), (int64_t)c->e_n * SC_TILE, (int)c->e_tiles, c->g_meanc.as<double>(),
-                       c->inv.as<int32_t>() + p0 * c->p_stride, c->partial.as<double>(), c->e_n, c->p_stride, cnt, cps,
+                       c->inv.as<int32_t>() + p0 * c->p_stride, partial, c->e_n, c->p_stride, cnt, cps,
                        splits, groups);
 }
 
-// score permutations [p0, p1) of the active table for every gene (on the context stream).
+// score permutations [p0, p1) of the active table for every gene (on the context stream; the finalise beside it).
 // bits: 8 / 16 / 32 / 64 = the persistent kernel gathers rows of that element width through the INVERSE permutation
 // (needs inverse rows [p0, p1); invert_here launches that inversion first); 0 = the table's rows are arbitrary index
 // maps: the index-row kernel over the fp64 tiles.
@@ -1243,48 +1307,52 @@ static int moran_perm_range(sc_ctx *c, int64_t p0, int64_t p1, int bits, bool in
         int wgs = c->n_cus - (c->score_leave_cus > 0 && c->score_leave_cus < c->n_cus ? c->score_leave_cus : 0);
         const int64_t tasks = (int64_t)groups * splits * ((cnt + 7) / 8);
         if ((int64_t)wgs * SCORE_WAVES > tasks) wgs = (int)ceil_div64(tasks, SCORE_WAVES);
+        double *partial = nullptr;
+        SC_TRY(moran_ring_slice(c, &partial));
         {
-            KernelTimerScope ts(c, SC_K_MORAN_PERM);
+            KernelTimerScope ts(c, SC_K_MORAN_PERM);   // (the scoring launch alone: neither the ring's wait nor the finalise)
             // (8 cells per stage were measured for the narrow sources too: under the 128-VGPR cap of the 1024-thread form they spill)
-            if (bits == 4) launch_score<4, 4, false>(c, wgs, c->X32.as<uint4>(), p0, cnt, cps, splits, groups);
-            else if (bits == 8 && c->lag_u16) launch_score<8, 4, false, true>(c, wgs, c->X32.as<uint4>(), p0, cnt, cps, splits, groups);
-            else if (bits == 8) launch_score<8, 4, false>(c, wgs, c->X32.as<uint4>(), p0, cnt, cps, splits, groups);
-            else if (bits == 16) launch_score<16, 4, false>(c, wgs, c->X32.as<uint4>(), p0, cnt, cps, splits, groups);
-            else if (bits == 32) launch_score<32, 4, false>(c, wgs, c->X32.as<uint4>(), p0, cnt, cps, splits, groups);
-            else if (!big) launch_score<64, 8, false>(c, wgs, c->Z.as<uint4>(), p0, cnt, cps, splits, groups);
-            else launch_score<64, 8, true>(c, wgs, c->Z.as<uint4>(), p0, cnt, cps, splits, groups);
+            if (bits == 4) launch_score<4, 4, false>(c, wgs, c->X32.as<uint4>(), partial, p0, cnt, cps, splits, groups);
+            else if (bits == 8 && c->lag_u16) launch_score<8, 4, false, true>(c, wgs, c->X32.as<uint4>(), partial, p0, cnt, cps, splits, groups);
+            else if (bits == 8) launch_score<8, 4, false>(c, wgs, c->X32.as<uint4>(), partial, p0, cnt, cps, splits, groups);
+            else if (bits == 16) launch_score<16, 4, false>(c, wgs, c->X32.as<uint4>(), partial, p0, cnt, cps, splits, groups);
+            else if (bits == 32) launch_score<32, 4, false>(c, wgs, c->X32.as<uint4>(), partial, p0, cnt, cps, splits, groups);
+            else if (!big) launch_score<64, 8, false>(c, wgs, c->Z.as<uint4>(), partial, p0, cnt, cps, splits, groups);
+            else launch_score<64, 8, true>(c, wgs, c->Z.as<uint4>(), partial, p0, cnt, cps, splits, groups);
         }
+        SC_TRY(moran_ring_scored(c));
         if (bits == 4) {
-            hipLaunchKernelGGL(k_moran_finalize_nib, dim3((unsigned)ceil_div64((int64_t)cnt * G, 256)), dim3(256), 0, c->stream,
-                               c->partial.as<double>(), c->g_seff.as<double>(), c->g_corr.as<double>(), c->nib_map.as<int32_t>(),
+            hipLaunchKernelGGL(k_moran_finalize_nib, dim3((unsigned)ceil_div64((int64_t)cnt * G, 256)), dim3(256), 0, c->stream_out,
+                               partial, c->g_seff.as<double>(), c->g_corr.as<double>(), c->nib_map.as<int32_t>(),
                                c->sims.as<double>(), c->sims_raw.as<double>(), cnt, splits, G, p0);
-            SC_HIP(hipGetLastError());
-            return SC_OK;
+            return moran_ring_finalised(c);
         }
         const dim3 fgrid((unsigned)ceil_div64((int64_t)cnt * GP, 256), (unsigned)groups);
         auto fin = bits == 8 ? k_moran_finalize_groups<128> : bits == 16 ? k_moran_finalize_groups<64>
                  : bits == 32 ? k_moran_finalize_groups<32> : k_moran_finalize_groups<16>;
-        hipLaunchKernelGGL(fin, fgrid, dim3(256), 0, c->stream, c->partial.as<double>(), c->g_seff.as<double>(),
+        hipLaunchKernelGGL(fin, fgrid, dim3(256), 0, c->stream_out, partial, c->g_seff.as<double>(),
                            c->g_corr.as<double>(), c->sims.as<double>(), c->sims_raw.as<double>(), cnt, splits, G, p0);
-        SC_HIP(hipGetLastError());
-        return SC_OK;
+        return moran_ring_finalised(c);
     }
     const int ptiles = (int)ceil_div64(cnt, MP_PERMS_PER_BLOCK);
     int64_t cps = 0;
     const int splits = pick_splits(n, ptiles, &cps);
-    for (int64_t t = 0; t < T; ++t) {
+    for (int64_t t = 0; t < T; ++t) {   // (every tile's launch takes the ring's next slice)
+        double *partial = nullptr;
+        SC_TRY(moran_ring_slice(c, &partial));
         {
             KernelTimerScope ts(c, SC_K_MORAN_PERM);
             hipLaunchKernelGGL(k_moran_perm, dim3((unsigned)splits, (unsigned)ptiles), dim3(256), 0, c->stream,
                                c->Z.as<double>() + t * tile_elems, c->Lag.as<double>() + t * tile_elems,
-                               c->perm.as<int32_t>() + p0 * c->p_stride, c->partial.as<double>(), n, c->p_stride,
+                               c->perm.as<int32_t>() + p0 * c->p_stride, partial, n, c->p_stride,
                                cnt, cps);
         }
+        SC_TRY(moran_ring_scored(c));
         hipLaunchKernelGGL(k_moran_finalize, dim3((unsigned)ceil_div64((int64_t)cnt * SC_TILE, 256)), dim3(256), 0,
-                           c->stream, c->partial.as<double>(), c->g_seff.as<double>(), c->g_corr.as<double>(),
+                           c->stream_out, partial, c->g_seff.as<double>(), c->g_corr.as<double>(),
                            c->sims.as<double>(), c->sims_raw.as<double>(), cnt, splits, G, t * SC_TILE, p0);
+        SC_TRY(moran_ring_finalised(c));
     }
-    SC_HIP(hipGetLastError());
     return SC_OK;
 }
 
@@ -1304,6 +1372,7 @@ static int moran_finish(sc_ctx *c, int64_t n_perm, double *I_out, double *sims_o
         SC_TRY(c->counts.ensure(sizeof(long long) * (size_t)G, &c->mem));
         SC_TRY(c->sim_sum.ensure(sizeof(double) * (size_t)G, &c->mem));
         SC_TRY(c->sim_sumsq.ensure(sizeof(double) * (size_t)G, &c->mem));
+        SC_TRY(moran_ring_join(c));   // sims are complete behind the last finalise
         hipLaunchKernelGGL(k_moran_count, dim3((unsigned)G), dim3(256), 0, c->stream, c->sims.as<double>(),
                            c->sims_raw.as<double>(), c->g_thr.as<double>(), c->g_lat.as<double>(), c->g_z2.as<double>(),
                            (int)n_perm, G, c->counts.as<long long>(), c->sim_sum.as<double>(),
@@ -1324,6 +1393,7 @@ static int moran_finish(sc_ctx *c, int64_t n_perm, double *I_out, double *sims_o
     }
     SC_HIP(hipMemcpyAsync(I_out, c->g_I.p, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
+    c->ring.launches = 0;   // (the side stream is idle: the context stream waited for its last launch)
     return SC_OK;
 }
 
@@ -1370,6 +1440,9 @@ static int moran_seeded_once(sc_ctx *c, uint64_t *state6, int64_t n_perm, double
     // transpositions in ascending order: no permutation rows, no scatter pass)
     const bool inverse_only = permgen_can_swap_inverse(n);
     int bits = 64;
+    // the set-up in two halves: what only enqueues, then -- with the generator topped up in between (pipe_consume) -- the
+    // synchronisation, the host's decisions and the rest
+    auto prepare_early = [&]() -> int { return moran_prepare_early(c); };
     auto prepare = [&]() -> int {
         SC_TRY(moran_prepare(c, n_perm < PERM_CHUNK ? n_perm : PERM_CHUNK, true));
         bits = c->narrow_bits;
@@ -1395,8 +1468,8 @@ static int moran_seeded_once(sc_ctx *c, uint64_t *state6, int64_t n_perm, double
         c->score_leave_cus = keep;
         return rc;
     };
-    if (begun) SC_TRY(pipe_consume(c, *begun, state6, prepare, score));   // the generator has been running since _begin
-    else SC_TRY(sc_perm_pipeline(c, state6, n, n_perm, inverse_only ? 1 : 2, PIPE_AHEAD, prepare, score));
+    if (begun) SC_TRY(pipe_consume(c, *begun, state6, prepare_early, prepare, score));   // the generator has been running since _begin
+    else SC_TRY(sc_perm_pipeline(c, state6, n, n_perm, inverse_only ? 1 : 2, PIPE_AHEAD, prepare_early, prepare, score));
     return moran_finish(c, n_perm, I_out, sims_out, count_ge_out, sim_sum_out, sim_sumsq_out);
 }
 

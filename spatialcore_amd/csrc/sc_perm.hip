@@ -173,6 +173,7 @@ extern "C" int sc_perm_generate(sc_ctx *c, uint64_t *state6, int64_t n, int64_t 
 // ---- the generator / consumer pipeline of the seeded statistics ----
 #define PIPE_FIRST 32        // permutations of the first pipeline chunk
 #define PIPE_SWAP_STREAMS 2  // swap chunks in flight (they are latency-bound: two overlap almost for free)
+#define PIPE_LOOKAHEAD 3     // chunks enqueued beyond the one whose scoring is enqueued next (pipe_consume)
 // The job ends with what is left once the generator's chain has finished: the swaps of its last chunk (~10 ms whatever
 // its size: one workgroup per permutation, latency-bound) and the consumption of every chunk not consumed yet.  Behind
 // a 128-permutation chunk that is its swaps AND its 10-ms consumption; tapering chunks (PIPE_TAIL) leave a few milliseconds (bench
@@ -183,8 +184,8 @@ extern "C" int sc_perm_generate(sc_ctx *c, uint64_t *state6, int64_t n, int64_t 
 // stream_pg: its preparation, stream_px: verification + expansion, stream3/4: Fisher-Yates swaps) while
 // `score(p0, p1)` consumes finished chunks on the context stream.  table: 0 = permutation rows (c->perm),
 // 1 = inverse rows only (c->inv; the same transpositions in ascending order), 2 = both (rows + k_invert_perm).
-// `after_first` runs on the host right after the first chunk of the generator has been enqueued (the generator is
-// the longest chain and depends on nothing else; everything host-blocking of the consumer's set-up goes here).
+// The consumer's set-up (`enqueue`, `complete`: pipe_consume) runs on the host after the first chunks of the generator
+// have been enqueued (the generator is the longest chain and depends on nothing else).
 static int pipe_generate(sc_ctx *c, PermPipe &pp, int64_t k)
 {
     hipEvent_t &scanned = pp.ev[(size_t)(2 * k)], &swapped = pp.ev[(size_t)(2 * k + 1)];
@@ -221,6 +222,7 @@ void pipe_drain(sc_ctx *c, PermPipe &pp)
     if (c->stream4) (void)hipStreamSynchronize(c->stream4);
     (void)c->pg.sync();
     (void)hipStreamSynchronize(c->stream);
+    if (c->stream_out) (void)hipStreamSynchronize(c->stream_out);   // (a consumer's launches beside its scoring: Moran's finalise)
     for (hipEvent_t e : pp.ev)
         if (e) (void)hipEventDestroy(e);
     pp.ev.clear();
@@ -278,19 +280,28 @@ int pipe_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int
     return rc;
 }
 
-// Consume: `after_first` (the consumer's host-blocking set-up) runs once, then `score(p0, p1)` behind every chunk's
+// Consume: the consumer's set-up runs once, then `score(p0, p1)` behind every chunk's
 // swaps on the context stream, with the generator kept TWO chunks ahead in the host's enqueue order (r03 timeline: with
 // one chunk ahead the chain sat idle for 5 ms behind the consumer's set-up; a chunk is some 250 API calls).
-int pipe_consume(sc_ctx *c, PermPipe &pp, uint64_t *state6, const std::function<int()> &after_first,
-                 const std::function<int(int64_t, int64_t)> &score)
+// The set-up is two callbacks.  `enqueue` only enqueues; `complete` is everything that waits for the device (and all of
+// the set-up for a consumer that has no such split: it passes no `enqueue` and is run exactly as before).  Between the
+// two the generator is topped up to PIPE_LOOKAHEAD + 1 chunks, what the loop below asks for as soon as it has enqueued the
+// first chunk's scoring (k = 1), so that those launches are in their queues before the host waits and before the first
+// scoring launch: DESIGN.md 4.3 for where that pays (a process whose streams share hardware queues) and where it does not.
+int pipe_consume(sc_ctx *c, PermPipe &pp, uint64_t *state6, const std::function<int()> &enqueue,
+                 const std::function<int()> &complete, const std::function<int(int64_t, int64_t)> &score)
 {
     const int64_t chunks = (int64_t)pp.bounds.size() - 1;
     int rc = SC_OK;
-    if (after_first) rc = after_first();
+    if (enqueue) {
+        rc = enqueue();
+        while (rc == SC_OK && pp.enqueued < chunks && pp.enqueued < PIPE_LOOKAHEAD + 1) rc = pipe_generate(c, pp, pp.enqueued);
+    }
+    if (rc == SC_OK && complete) rc = complete();
     c->perm_bijective = true;  // device-generated rows are permutations by construction
     c->perm_forward_valid = pp.table != 1;
     for (int64_t k = 0; k < chunks && rc == SC_OK; ++k) {
-        while (rc == SC_OK && pp.enqueued < chunks && pp.enqueued < k + 3) rc = pipe_generate(c, pp, pp.enqueued);
+        while (rc == SC_OK && pp.enqueued < chunks && pp.enqueued < k + PIPE_LOOKAHEAD) rc = pipe_generate(c, pp, pp.enqueued);
         if (rc == SC_OK && hipStreamWaitEvent(c->stream, pp.ev[(size_t)(2 * k + 1)], 0) != hipSuccess) {
             sc_set_error("permutation pipeline: event plumbing failed");
             rc = SC_ERR_HIP;
@@ -314,12 +325,13 @@ void sc_perm_pipe_abort(sc_ctx *c)
 }
 
 int sc_perm_pipeline(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_perm, int table, int units_ahead,
-                     const std::function<int()> &after_first, const std::function<int(int64_t, int64_t)> &score)
+                     const std::function<int()> &enqueue, const std::function<int()> &complete,
+                     const std::function<int(int64_t, int64_t)> &score)
 {
     sc_perm_pipe_abort(c);   // (a job begun with sc_moran_seeded_begin and never finished)
     PermPipe pp;
     SC_TRY(pipe_begin(c, state6, n, n_perm, table, units_ahead, pp, 2));
-    return pipe_consume(c, pp, state6, after_first, score);
+    return pipe_consume(c, pp, state6, enqueue, complete, score);
 }
 
 int permgen_rerun_on_failure(sc_ctx *c, const std::function<int()> &attempt, const std::function<int()> &undo)

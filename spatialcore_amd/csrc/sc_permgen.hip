@@ -301,7 +301,7 @@ static int perm_generate_once(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_
         // a long job: the chunked pipeline of the seeded statistics with nothing to consume -- the Fisher-Yates swaps of
         // chunk k run (on their own streams) beside the rejection scan of chunk k + 1 instead of all behind the scan
         // (r03, 999 permutations of 1M cells: 55 ms of swaps out of the call's critical path)
-        const int rc = sc_perm_pipeline(c, state6, n, n_perm, 0, 2, nullptr, [](int64_t, int64_t) -> int { return SC_OK; });
+        const int rc = sc_perm_pipeline(c, state6, n, n_perm, 0, 2, nullptr, nullptr, [](int64_t, int64_t) -> int { return SC_OK; });
         if (rc == SC_OK) c->perm_forward_valid = true;
         return rc;
     }
