@@ -59,7 +59,11 @@ extern "C" {
 #define SC_K_RIPLEY_G_LIST 19    /* sc_ripley_g_build: count and fill passes of the ordered neighbour lists */
 #define SC_K_RIPLEY_G_RELABEL 20 /* sc_ripley_g_*: permutation rows -> label words at the cells' positions */
 #define SC_K_RIPLEY_G_COUNT 21   /* sc_ripley_g_*: the per-cell first-contact counting kernel, observed pass included */
-#define SC_K_COUNT_ 22
+#define SC_K_NMF_SETUP 22  /* sc_nmf_fit: fp64 values, the column-sorted copy (stable device sort) and its chunk table */
+#define SC_K_NMF_W 23      /* ... H H^T / rowsum(H) and the W pass over the rows */
+#define SC_K_NMF_H 24      /* ... W^T W / colsum(W), the H pass over the column chunks and its finish */
+#define SC_K_NMF_ERR 25    /* ... an error evaluation (the initial one, every tenth iteration, the final one) */
+#define SC_K_COUNT_ 26
 
 typedef struct sc_ctx sc_ctx;
 
@@ -649,6 +653,35 @@ int sc_gmm_fit(sc_ctx *ctx, const void *scores, int dtype, int64_t n, int32_t K,
 int sc_gmm_posterior(sc_ctx *ctx, const void *scores, int dtype, int64_t n, int32_t K, const double *weights,
                      const double *means, const double *variances, const int32_t *high, int32_t n_high, double cutoff,
                      double *prob_out, int32_t *labels_out, int64_t *n_high_cells_out);
+
+/* ---- N12 (extension): sc_nmf_fit -- NMF(solver="mu") of a sparse cells x genes matrix ------------------------------
+ * Replays sklearn 1.7.2 decomposition/_nmf.py, _fit_multiplicative_update with gamma = 1 and no regularisation, for
+ * beta_loss "frobenius" (loss = 2) and "kullback-leibler" (loss = 1).  X is a CANONICAL CSR (indptr[n + 1] int64 from 0,
+ * columns int32 strictly ascending inside a row, values SC_F32 or SC_F64, finite and >= 0; stored zeros are legal and
+ * add nothing); anything else gives SC_ERR_INVALID.  All arithmetic is fp64 whatever the value type; EPS = 2^-23.
+ *  - per iteration, first W, then (update_H != 0) H with the new W:
+ *    Frobenius: W <- W o ((X H^T) / (W (H H^T))), H <- H o ((W^T X) / ((W^T W) H)), a denominator of exactly 0 -> EPS;
+ *    Kullback-Leibler: q = x / max((W H)_ig, EPS) at every stored entry, W <- W o ((Q H^T) / rowsum(H)) (0 -> EPS), q again
+ *    with the new W, H <- H o ((W^T Q) / colsum(W)) (0 -> 1), then H[H < 2^-52] = 0.  W H is formed at stored entries only.
+ *    update_H = 0 keeps H (NMF.transform); H H^T / rowsum(H) are then computed once.
+ *  - error(W, H) = sqrt(2 max(D, 0)); Frobenius: D = ((sum x^2 + tr((W^T W)(H H^T))) - 2 sum_ig x_ig (W H)_ig) / 2;
+ *    Kullback-Leibler: D = sum x log(x / max((W H)_ig, EPS)) + (colsum(W) . rowsum(H) - sum x), both sums over the stored
+ *    entries with x > EPS only.
+ *  - e0 = error(W0, H0), prev = e0; if tol > 0 the error is evaluated after every iteration whose number is a multiple
+ *    of 10: stop if (prev - e) / e0 < tol, else prev = e.  *n_iter_out = iterations done (<= max_iter).
+ *  - summation order (no floating-point atomics; the result is a function of the arguments alone, bit for bit, whatever
+ *    the grid): sums over a row's stored entries, over genes and over components run in index order from 0; the K-term
+ *    dot (W H)_ig is the adjacent-pair tree over the K products padded with zeros to the next power of two; a gene
+ *    column's stored entries (rows ascending) are added in chunks of 512 entries and the cells (W^T W, colsum(W), the
+ *    per-cell error terms) in chunks of 1024 cells, each chunk in index order from 0 and the chunk sums in chunk order;
+ *    sum x^2 and sum x run over the stored entries in index order.  The factors involve + x / only.
+ * In / out: W[n][K] = W0 -> W, H[K][n_genes] = H0 -> H (H0 is returned as it came with update_H = 0), both finite, >= 0.
+ * Out: err_trace_out[1 + max_iter / 10] = e0 and the error of every check, *n_checks_out = their number,
+ * *recon_err_out = the error of the returned factors.
+ * 1 <= K <= 64, 1 <= n <= 2^31 - 1, 1 <= n_genes <= 32768, 1 <= stored entries <= 2^32 - 1, max_iter >= 1, tol >= 0. */
+int sc_nmf_fit(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
+               int32_t n_genes, int32_t K, int32_t loss, int32_t update_H, int32_t max_iter, double tol, double *W, double *H,
+               double *err_trace_out, int32_t *n_checks_out, int32_t *n_iter_out, double *recon_err_out);
 
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across

@@ -27,6 +27,8 @@ K_THRESH_SCORE, K_THRESH_SORT, K_THRESH_KS, K_GMM_EM, K_GMM_POST = 12, 13, 14, 1
 K_COOCCUR = 17
 K_LIGREC = 18
 K_RIPLEY_G_LIST, K_RIPLEY_G_RELABEL, K_RIPLEY_G_COUNT = 19, 20, 21
+K_NMF_SETUP, K_NMF_W, K_NMF_H, K_NMF_ERR = 22, 23, 24, 25
+NMF_LOSSES = {"frobenius": 2, "kullback-leibler": 1}   # sc_nmf_fit's codes (sklearn's beta)
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
 
 # every symbol include/spatialcore_hip.h declares: (name, argtypes); restype is always int
@@ -115,6 +117,8 @@ SYMBOLS = {
     "sc_gmm_fit": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_double, _P, _P, c_int32, c_double, c_double,
                    _P, _P, _P, _P, _P, _P, _P, POINTER(c_int32)],
     "sc_gmm_posterior": [_P, _P, c_int, c_int64, c_int32, _P, _P, _P, _P, c_int32, c_double, _P, _P, POINTER(c_int64)],
+    "sc_nmf_fit": [_P, _P, _P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P,
+                   POINTER(c_int32), POINTER(c_int32), POINTER(c_double)],
     "sc_comm_unique_id": [_P],
     "sc_comm_create": [_P, _P, c_int, c_int, POINTER(c_void_p)],
     "sc_comm_destroy": [_P],
@@ -848,6 +852,31 @@ class Context:
                                           _ptr(w), _ptr(mu), _ptr(var), _ptr(hi), hi.size, float(cutoff), _ptr(prob),
                                           _ptr(lab), byref(nh)))
         return prob, lab, nh.value
+
+    # ---- N12 (extension): NMF ---------------------------------------------------------------
+    def nmf_fit(self, indptr, indices, data, n_genes: int, W0, H0, loss: str, update_H: bool = True, max_iter: int = 200,
+                tol: float = 1e-4) -> dict:
+        """sc_nmf_fit on a canonical CSR (values float32 or float64) from the starting factors ``W0`` (n, K) and ``H0``
+        (K, n_genes): ``W`` / ``H`` float64, ``n_iter``, ``reconstruction_err`` and ``error_trace`` (the error at the start
+        and at every check)."""
+        data = np.ascontiguousarray(data)
+        if data.dtype not in (np.float32, np.float64):
+            raise ValueError(f"nmf_fit: values must be float32 or float64, got {data.dtype}")
+        indptr, indices = _c(indptr, np.int64), _c(indices, np.int32)
+        W, H = np.array(W0, dtype=np.float64, order="C"), np.array(H0, dtype=np.float64, order="C")
+        n, G = indptr.size - 1, int(n_genes)
+        if W.ndim != 2 or H.ndim != 2 or W.shape[0] != n or H.shape != (W.shape[1], G):
+            raise ValueError(f"nmf_fit: W0 must be (n, K) and H0 (K, n_genes), got {W.shape} and {H.shape}")
+        if indices.size != data.size or n < 1 or indptr[-1] != data.size:
+            raise ValueError("nmf_fit: indptr, indices and values do not describe one CSR matrix")
+        trace = np.zeros(2 + max(int(max_iter), 0) // 10, dtype=np.float64)
+        checks, n_iter, err = c_int32(0), c_int32(0), c_double(0.0)
+        _check(self._lib.sc_nmf_fit(self._h, _ptr(indptr), _ptr(indices), _ptr(data),
+                                    SC_F32 if data.dtype == np.float32 else SC_F64, n, G, W.shape[1], NMF_LOSSES[loss],
+                                    int(bool(update_H)), int(max_iter), float(tol), _ptr(W), _ptr(H), _ptr(trace),
+                                    byref(checks), byref(n_iter), byref(err)))
+        return {"W": W, "H": H, "n_iter": n_iter.value, "reconstruction_err": err.value,
+                "error_trace": trace[:checks.value].copy()}
 
     # ---- N4 (extension) ---------------------------------------------------------------------
     def enrichment_counts(self, labels, n_types: int, n_perm: int, perm_row0: int = 0) -> np.ndarray:

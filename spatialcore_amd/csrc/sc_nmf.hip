@@ -1,0 +1,642 @@
+// sc_nmf.hip -- sc_nmf_fit: sklearn 1.7.2 NMF(solver="mu") on a sparse cells x genes matrix, Frobenius and
+// Kullback-Leibler losses (decomposition/_nmf.py: _fit_multiplicative_update with gamma = 1, no regularisation).
+// DESIGN.md 4.6l; restated in the same order by tests/nmf_restated.py.
+//
+// fp64 throughout, -ffp-contract=off, no floating-point atomics: the factors involve + x / only and are a function of
+// the arguments alone.  ONE summation order per sum:
+//  - over a row's stored entries, over a column chunk's stored entries, over genes and over components: index order
+//    (a running sum that starts at 0);
+//  - the K-term dot (W H)_ig of the Kullback-Leibler quotient and of the errors: the K products W_ik H_kg, padded with
+//    zeros to Kp = K rounded up to a power of two, added as the adjacent-pair tree (lane l takes lane l ^ 1, then
+//    l ^ 2, ...: every lane of the group ends with the same bits, since a + b = b + a);
+//  - over a gene column's stored entries: chunks of NMF_COL_CHUNK = 512 entries (rows ascending), each in index order
+//    from 0, the chunk sums added in chunk order;
+//  - over cells (W^T W, colsum(W), the per-cell error terms): chunks of NMF_CELL_CHUNK = 1024 cells, each in index
+//    order from 0, the chunk sums added in chunk order;
+//  - sum x^2 and sum x over the stored entries: on the host, in index order.
+// None of this depends on the grid or on how many workgroups are resident.
+//
+// Lanes = components: a group of Kp lanes serves one row (W pass, error pass), one column chunk (H pass) or one gene
+// (H finish); a workgroup of 256 threads holds 256 / Kp groups.
+#include <cmath>
+#include <vector>
+
+#include "sc_ctx.h"
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int NMF_TPB = 256;
+constexpr int NMF_KMAX = 64;
+constexpr int NMF_COL_CHUNK = 512;     // stored entries of a gene column per work item of the H pass
+constexpr int NMF_CELL_CHUNK = 1024;   // cells per partial of the sums over cells
+constexpr int NMF_TILE = 64;           // cells of W staged in LDS at a time by k_nmf_cellsums
+constexpr double NMF_EPS = 1.1920928955078125e-07;   // 2^-23: sklearn's EPSILON (float32 eps)
+constexpr double NMF_TINY = 2.220446049250313e-16;   // 2^-52: the Kullback-Leibler floor of H
+enum { NMF_KL = 1, NMF_FRO = 2 };
+
+// the adjacent-pair tree over the kp lanes of a group (kp a power of two, groups aligned to kp)
+__device__ __forceinline__ double nmf_group_sum(double v, int kp)
+{
+    for (int h = 1; h < kp; h <<= 1) v = v + __shfl_xor(v, h, 64);
+    return v;
+}
+
+// ---- set-up ------------------------------------------------------------------------------------------------------
+// per stored entry: fp64 value, sort key = its column, payload = its position; per row (one thread): the row id of its entries
+template <class T>
+__global__ __launch_bounds__(256) void k_nmf_entries(const T *__restrict__ data, const int32_t *__restrict__ indices, int64_t nnz,
+                                                     double *__restrict__ val, u64 *__restrict__ keys, uint32_t *__restrict__ pos)
+{
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nnz) return;
+    val[p] = (double)data[p];
+    keys[p] = (u64)indices[p];
+    pos[p] = (uint32_t)p;
+}
+__global__ __launch_bounds__(256) void k_nmf_rowids(const int64_t *__restrict__ indptr, int64_t n, int32_t *__restrict__ rowid)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int64_t p = indptr[i]; p < indptr[i + 1]; ++p) rowid[p] = (int32_t)i;
+}
+// the column-sorted copy (the sort is stable, so rows ascend inside a column)
+__global__ __launch_bounds__(256) void k_nmf_csc_fill(const uint32_t *__restrict__ pos, const int32_t *__restrict__ rowid,
+                                                      const double *__restrict__ val, int64_t nnz, int32_t *__restrict__ crow,
+                                                      double *__restrict__ cval)
+{
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nnz) return;
+    const uint32_t q = pos[p];
+    crow[p] = rowid[q];
+    cval[p] = val[q];
+}
+// colptr[g] = first sorted position whose column is >= g, g = 0 .. G
+__global__ __launch_bounds__(256) void k_nmf_colptr(const u64 *__restrict__ keys, int64_t nnz, int G, int64_t *__restrict__ colptr)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g > G) return;
+    int64_t lo = 0, hi = nnz;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (keys[mid] < (u64)g) lo = mid + 1; else hi = mid;
+    }
+    colptr[g] = lo;
+}
+// cptr[g] = first chunk of gene g (cptr[G] = number of chunks): one thread, G <= 32768
+__global__ void k_nmf_chunk_scan(const int64_t *__restrict__ colptr, int G, int64_t *__restrict__ cptr)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int64_t c = 0;
+    for (int g = 0; g < G; ++g) {
+        cptr[g] = c;
+        c += (colptr[g + 1] - colptr[g] + NMF_COL_CHUNK - 1) / NMF_COL_CHUNK;
+    }
+    cptr[G] = c;
+}
+__global__ __launch_bounds__(256) void k_nmf_chunk_fill(const int64_t *__restrict__ cptr, int G, int32_t *__restrict__ cgene)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    for (int64_t c = cptr[g]; c < cptr[g + 1]; ++c) cgene[c] = g;
+}
+__global__ __launch_bounds__(256) void k_nmf_transpose(const double *__restrict__ H, int K, int G, double *__restrict__ Ht)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (int64_t)K * G) return;
+    const int g = (int)(t / K), k = (int)(t % K);
+    Ht[t] = H[(int64_t)k * G + g];
+}
+
+// ---- per iteration -----------------------------------------------------------------------------------------------
+// grid K, 64 threads: HHt[k][k'] = sum_g H[k][g] H[k'][g] and Hsum[k] = sum_g H[k][g], genes in index order (reads H^T)
+__global__ __launch_bounds__(64) void k_nmf_hprep(const double *__restrict__ Ht, int K, int G, double *__restrict__ HHt,
+                                                  double *__restrict__ Hsum)
+{
+    const int k = blockIdx.x, k2 = threadIdx.x;
+    if (k2 >= K) return;
+    double s = 0.0, r = 0.0;
+    for (int g = 0; g < G; ++g) {
+        const double a = Ht[(int64_t)g * K + k];
+        s = s + a * Ht[(int64_t)g * K + k2];
+        r = r + a;
+    }
+    HHt[k * K + k2] = s;
+    if (k2 == 0) Hsum[k] = r;
+}
+
+// W pass: one group per row.  Frobenius: W_ik <- W_ik ((X H^T)_ik / (W (H H^T))_ik); Kullback-Leibler: W_ik <- W_ik
+// ((Q H^T)_ik / rowsum(H)_k), q = x / max((W H)_ig, EPS) at the row's stored entries.  A denominator of 0 becomes EPS.
+// Dynamic LDS: Frobenius K * K (H H^T) + 256 (the workgroup's W rows) doubles.
+template <int LOSS>
+__global__ __launch_bounds__(256) void k_nmf_w(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                               const double *__restrict__ val, int64_t n, int K, int kp,
+                                               const double *__restrict__ Ht, const double *__restrict__ HHt,
+                                               const double *__restrict__ Hsum, double *__restrict__ W)
+{
+    extern __shared__ double nmf_lds[];
+    const int t = threadIdx.x, grp = t / kp, k = t % kp;
+    const int64_t i = (int64_t)blockIdx.x * (NMF_TPB / kp) + grp;
+    const bool live = i < n && k < K;
+    const double w = live ? W[i * K + k] : 0.0;
+    if (LOSS == NMF_FRO) {
+        for (int q = t; q < K * K; q += NMF_TPB) nmf_lds[q] = HHt[q];
+        nmf_lds[K * K + t] = w;
+        __syncthreads();
+    }
+    double num = 0.0;
+    if (i < n) {   // uniform over the group, whose lanes walk the row together
+        auto add = [&](double x, double h) {
+            if (LOSS == NMF_FRO) {
+                num = num + x * h;
+            } else {
+                double d = nmf_group_sum(w * h, kp);
+                d = d < NMF_EPS ? NMF_EPS : d;
+                num = num + (x / d) * h;
+            }
+        };
+        auto row_of = [&](int32_t g) { return k < K ? Ht[(int64_t)g * K + k] : 0.0; };
+        // the group fetches kp entries at once (lane j holds entry base + j) and hands them round, four H^T rows in flight;
+        // the entries are still added one by one in index order
+        const int64_t p1 = indptr[i + 1];
+        for (int64_t base = indptr[i]; base < p1; base += kp) {
+            const int cnt = (int)(p1 - base < kp ? p1 - base : kp);
+            const int32_t g_mine = k < cnt ? indices[base + k] : 0;
+            const double x_mine = k < cnt ? val[base + k] : 0.0;
+            int j = 0;
+            for (; j + 4 <= cnt; j += 4) {
+                const double h0 = row_of(__shfl(g_mine, j, kp)), h1 = row_of(__shfl(g_mine, j + 1, kp));
+                const double h2 = row_of(__shfl(g_mine, j + 2, kp)), h3 = row_of(__shfl(g_mine, j + 3, kp));
+                add(__shfl(x_mine, j, kp), h0);
+                add(__shfl(x_mine, j + 1, kp), h1);
+                add(__shfl(x_mine, j + 2, kp), h2);
+                add(__shfl(x_mine, j + 3, kp), h3);
+            }
+            for (; j < cnt; ++j) add(__shfl(x_mine, j, kp), row_of(__shfl(g_mine, j, kp)));
+        }
+    }
+    if (!live) return;
+    double den;
+    if (LOSS == NMF_FRO) {
+        const double *wrow = nmf_lds + K * K + grp * kp;
+        den = 0.0;
+        for (int j = 0; j < K; ++j) den = den + wrow[j] * nmf_lds[j * K + k];
+    } else {
+        den = Hsum[k];
+    }
+    if (den == 0.0) den = NMF_EPS;
+    W[i * K + k] = w * (num / den);
+}
+
+// Sums over cells, one workgroup per chunk of 1024 cells: part[chunk][P], P = K * K entries (k, k') of W^T W (Frobenius) or
+// P = K entries of colsum(W) (Kullback-Leibler); cells in index order.  Thread t owns the entries t, t + 256, ...
+template <int LOSS>
+__global__ __launch_bounds__(256) void k_nmf_cellsums(const double *__restrict__ W, int64_t n, int K, double *__restrict__ part)
+{
+    __shared__ double tile[NMF_TILE * NMF_KMAX];
+    const int t = threadIdx.x;
+    const int P = LOSS == NMF_FRO ? K * K : K;
+    const int64_t c0 = (int64_t)blockIdx.x * NMF_CELL_CHUNK;
+    const int64_t c1 = c0 + NMF_CELL_CHUNK < n ? c0 + NMF_CELL_CHUNK : n;
+    double acc[NMF_KMAX * NMF_KMAX / NMF_TPB];
+#pragma unroll
+    for (int j = 0; j < NMF_KMAX * NMF_KMAX / NMF_TPB; ++j) acc[j] = 0.0;
+    for (int64_t b = c0; b < c1; b += NMF_TILE) {
+        const int cells = (int)(c1 - b < NMF_TILE ? c1 - b : NMF_TILE);
+        __syncthreads();
+        for (int q = t; q < cells * K; q += NMF_TPB) tile[q] = W[b * K + q];
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < NMF_KMAX * NMF_KMAX / NMF_TPB; ++j) {
+            const int e = t + j * NMF_TPB;
+            if (e < P) {
+                const int ka = LOSS == NMF_FRO ? e / K : e, kb = LOSS == NMF_FRO ? e % K : 0;
+                double a = acc[j];
+                for (int cc = 0; cc < cells; ++cc)
+                    a = LOSS == NMF_FRO ? a + tile[cc * K + ka] * tile[cc * K + kb] : a + tile[cc * K + ka];
+                acc[j] = a;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NMF_KMAX * NMF_KMAX / NMF_TPB; ++j) {
+        const int e = t + j * NMF_TPB;
+        if (e < P) part[(int64_t)blockIdx.x * P + e] = acc[j];
+    }
+}
+// out[e] = part[chunk][e] added in chunk order
+__global__ __launch_bounds__(256) void k_nmf_chunk_add(const double *__restrict__ part, int64_t chunks, int P, double *__restrict__ out)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= P) return;
+    double s = 0.0;
+    for (int64_t c = 0; c < chunks; ++c) s = s + part[c * P + e];
+    out[e] = s;
+}
+
+// H pass: one group per column chunk; part[chunk][k] = sum over the chunk's entries of W_ik x (Frobenius: W^T X) or
+// W_ik q with q = x / max((W H)_ig, EPS) (Kullback-Leibler: W^T Q), W the updated one, H the current one
+template <int LOSS>
+__global__ __launch_bounds__(256) void k_nmf_h(const int64_t *__restrict__ colptr, const int32_t *__restrict__ crow,
+                                               const double *__restrict__ cval, const int64_t *__restrict__ cptr,
+                                               const int32_t *__restrict__ cgene, int64_t chunks, int K, int kp,
+                                               const double *__restrict__ W, const double *__restrict__ Ht,
+                                               double *__restrict__ part)
+{
+    const int t = threadIdx.x, grp = t / kp, k = t % kp;
+    const int64_t c = (int64_t)blockIdx.x * (NMF_TPB / kp) + grp;
+    if (c >= chunks) return;   // the whole group leaves
+    const int32_t g = cgene[c];
+    const int64_t p0 = colptr[g] + (c - cptr[g]) * NMF_COL_CHUNK;
+    const int64_t pe = colptr[g + 1];
+    const int64_t p1 = p0 + NMF_COL_CHUNK < pe ? p0 + NMF_COL_CHUNK : pe;
+    const double h = (LOSS == NMF_KL && k < K) ? Ht[(int64_t)g * K + k] : 0.0;
+    double acc = 0.0;
+    auto add = [&](double x, double w) {
+        if (LOSS == NMF_FRO) {
+            acc = acc + w * x;
+        } else {
+            double d = nmf_group_sum(w * h, kp);
+            d = d < NMF_EPS ? NMF_EPS : d;
+            acc = acc + w * (x / d);
+        }
+    };
+    auto row_of = [&](int32_t i) { return k < K ? W[(int64_t)i * K + k] : 0.0; };
+    // as the W pass: kp entries fetched at once, four W rows in flight, added one by one in index order
+    for (int64_t base = p0; base < p1; base += kp) {
+        const int cnt = (int)(p1 - base < kp ? p1 - base : kp);
+        const int32_t i_mine = k < cnt ? crow[base + k] : 0;
+        const double x_mine = k < cnt ? cval[base + k] : 0.0;
+        int j = 0;
+        for (; j + 4 <= cnt; j += 4) {
+            const double w0 = row_of(__shfl(i_mine, j, kp)), w1 = row_of(__shfl(i_mine, j + 1, kp));
+            const double w2 = row_of(__shfl(i_mine, j + 2, kp)), w3 = row_of(__shfl(i_mine, j + 3, kp));
+            add(__shfl(x_mine, j, kp), w0);
+            add(__shfl(x_mine, j + 1, kp), w1);
+            add(__shfl(x_mine, j + 2, kp), w2);
+            add(__shfl(x_mine, j + 3, kp), w3);
+        }
+        for (; j < cnt; ++j) add(__shfl(x_mine, j, kp), row_of(__shfl(i_mine, j, kp)));
+    }
+    if (k < K) part[c * K + k] = acc;
+}
+
+// H finish: one group per gene.  Numerator = the gene's chunk sums in chunk order; Frobenius: H_kg <- H_kg (num /
+// ((W^T W) H)_kg), 0 -> EPS; Kullback-Leibler: H_kg <- H_kg (num / colsum(W)_k), 0 -> 1, then values < 2^-52 become 0.
+// Reads H (K x G), writes the other H buffer and its transpose.
+template <int LOSS>
+__global__ __launch_bounds__(256) void k_nmf_h_finish(const int64_t *__restrict__ cptr, const double *__restrict__ part, int G,
+                                                      int K, int kp, const double *__restrict__ cellsum,
+                                                      const double *__restrict__ H, double *__restrict__ Hn,
+                                                      double *__restrict__ Htn)
+{
+    const int t = threadIdx.x, grp = t / kp, k = t % kp;
+    const int64_t g = (int64_t)blockIdx.x * (NMF_TPB / kp) + grp;
+    if (g >= G || k >= K) return;
+    double num = 0.0;
+    for (int64_t c = cptr[g]; c < cptr[g + 1]; ++c) num = num + part[c * K + k];
+    double den;
+    if (LOSS == NMF_FRO) {
+        den = 0.0;
+        for (int j = 0; j < K; ++j) den = den + cellsum[k * K + j] * H[(int64_t)j * G + g];
+        if (den == 0.0) den = NMF_EPS;
+    } else {
+        den = cellsum[k];
+        if (den == 0.0) den = 1.0;
+    }
+    double hn = H[(int64_t)k * G + g] * (num / den);
+    if (LOSS == NMF_KL && hn < NMF_TINY) hn = 0.0;
+    Hn[(int64_t)k * G + g] = hn;
+    Htn[g * K + k] = hn;
+}
+
+// ---- error -------------------------------------------------------------------------------------------------------
+// rowerr[i] = sum over the row's stored entries, in index order, of x (W H)_ig (Frobenius: the cross term) or, for x > EPS
+// only, x log(x / max((W H)_ig, EPS)) (Kullback-Leibler)
+template <int LOSS>
+__global__ __launch_bounds__(256) void k_nmf_rowerr(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
+                                                    const double *__restrict__ val, int64_t n, int K, int kp,
+                                                    const double *__restrict__ Ht, const double *__restrict__ W,
+                                                    double *__restrict__ rowerr)
+{
+    const int t = threadIdx.x, grp = t / kp, k = t % kp;
+    const int64_t i = (int64_t)blockIdx.x * (NMF_TPB / kp) + grp;
+    if (i >= n) return;   // the whole group leaves
+    const double w = k < K ? W[i * K + k] : 0.0;
+    double s = 0.0;
+    const int64_t p1 = indptr[i + 1];
+    for (int64_t p = indptr[i]; p < p1; ++p) {
+        const int32_t g = indices[p];
+        const double x = val[p];
+        const double h = k < K ? Ht[(int64_t)g * K + k] : 0.0;
+        const double d = nmf_group_sum(w * h, kp);
+        if (LOSS == NMF_FRO) {
+            s = s + x * d;
+        } else if (x > NMF_EPS) {
+            s = s + x * log(x / (d < NMF_EPS ? NMF_EPS : d));
+        }
+    }
+    if (k == 0) rowerr[i] = s;
+}
+// part[chunk] = the chunk's 1024 cells in index order (one thread per chunk)
+__global__ __launch_bounds__(64) void k_nmf_rowerr_chunks(const double *__restrict__ rowerr, int64_t n, int64_t chunks,
+                                                          double *__restrict__ part)
+{
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= chunks) return;
+    const int64_t c0 = c * NMF_CELL_CHUNK;
+    const int64_t c1 = c0 + NMF_CELL_CHUNK < n ? c0 + NMF_CELL_CHUNK : n;
+    double s = 0.0;
+    for (int64_t i = c0; i < c1; ++i) s = s + rowerr[i];
+    part[c] = s;
+}
+// *out = sqrt(2 max(D, 0)).  Frobenius: D = ((sum x^2 + tr((W^T W)(H H^T))) - 2 cross) / 2; Kullback-Leibler: D = sum x
+// log(x / WH) + (colsum(W) . rowsum(H) - sum x).  One thread; cellsum = W^T W or colsum(W), hsum = H H^T or rowsum(H).
+template <int LOSS>
+__global__ void k_nmf_err_final(const double *__restrict__ part, int64_t chunks, int K, const double *__restrict__ cellsum,
+                                const double *__restrict__ hsum, double xconst, double *__restrict__ out)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = 0.0;
+    for (int64_t c = 0; c < chunks; ++c) s = s + part[c];
+    double D;
+    if (LOSS == NMF_FRO) {
+        double tr = 0.0;
+        for (int k = 0; k < K; ++k)
+            for (int j = 0; j < K; ++j) tr = tr + cellsum[k * K + j] * hsum[j * K + k];
+        D = ((xconst + tr) - 2.0 * s) / 2.0;
+    } else {
+        double sw = 0.0;
+        for (int k = 0; k < K; ++k) sw = sw + cellsum[k] * hsum[k];
+        D = s + (sw - xconst);
+    }
+    *out = sqrt(2.0 * (D > 0.0 ? D : 0.0));
+}
+
+struct NmfBufs {
+    sc_ctx *c;
+    enum { INDPTR, INDICES, RAW, VAL, KEYS, KEYS2, POS, POS2, ROWID, CROW, CVAL, COLPTR, CPTR, CGENE, W, H0, H1, HT0, HT1, HHT,
+           HSUM, CELLPART, CELLSUM, HPART, ROWERR, ERRPART, ERR, COUNT };
+    DBuf b[COUNT];
+    explicit NmfBufs(sc_ctx *ctx) : c(ctx) {}
+    ~NmfBufs()
+    {
+        for (DBuf &d : b) d.release(&c->mem);
+    }
+    int get(int which, size_t bytes) { return b[which].ensure(bytes ? bytes : 8, &c->mem); }
+    template <class T> T *as(int which) const { return b[which].as<T>(); }
+};
+
+struct NmfState {
+    sc_ctx *c;
+    NmfBufs *m;
+    int64_t n, chunks, cell_chunks;
+    int G, K, kp, loss;
+    int cur = 0;   // which of the two H / H^T buffers is current
+    double xconst; // sum x^2 (Frobenius) or sum of the x > EPS (Kullback-Leibler)
+    unsigned groups_grid(int64_t items) const { return (unsigned)ceil_div64(items, NMF_TPB / kp); }
+    double *H() const { return m->as<double>(cur ? NmfBufs::H1 : NmfBufs::H0); }
+    double *Ht() const { return m->as<double>(cur ? NmfBufs::HT1 : NmfBufs::HT0); }
+    double *Hother() const { return m->as<double>(cur ? NmfBufs::H0 : NmfBufs::H1); }
+    double *Htother() const { return m->as<double>(cur ? NmfBufs::HT0 : NmfBufs::HT1); }
+
+    void hprep() const
+    {
+        hipLaunchKernelGGL(k_nmf_hprep, dim3((unsigned)K), dim3(64), 0, c->stream, Ht(), K, G, m->as<double>(NmfBufs::HHT),
+                           m->as<double>(NmfBufs::HSUM));
+    }
+    void cellsums() const   // W^T W or colsum(W) of the current W into CELLSUM
+    {
+        const int P = loss == NMF_FRO ? K * K : K;
+        double *part = m->as<double>(NmfBufs::CELLPART);
+        if (loss == NMF_FRO) hipLaunchKernelGGL(k_nmf_cellsums<NMF_FRO>, dim3((unsigned)cell_chunks), dim3(NMF_TPB), 0, c->stream, m->as<double>(NmfBufs::W), n, K, part);
+        else hipLaunchKernelGGL(k_nmf_cellsums<NMF_KL>, dim3((unsigned)cell_chunks), dim3(NMF_TPB), 0, c->stream, m->as<double>(NmfBufs::W), n, K, part);
+        hipLaunchKernelGGL(k_nmf_chunk_add, dim3((unsigned)ceil_div64(P, NMF_TPB)), dim3(NMF_TPB), 0, c->stream, part, cell_chunks, P,
+                           m->as<double>(NmfBufs::CELLSUM));
+    }
+    void w_pass() const
+    {
+        const dim3 grid(groups_grid(n)), block(NMF_TPB);
+        const int64_t *indptr = m->as<int64_t>(NmfBufs::INDPTR);
+        const int32_t *indices = m->as<int32_t>(NmfBufs::INDICES);
+        const double *val = m->as<double>(NmfBufs::VAL);
+        if (loss == NMF_FRO)
+            hipLaunchKernelGGL(k_nmf_w<NMF_FRO>, grid, block, sizeof(double) * (size_t)(K * K + NMF_TPB), c->stream, indptr, indices, val, n,
+                               K, kp, Ht(), m->as<double>(NmfBufs::HHT), m->as<double>(NmfBufs::HSUM), m->as<double>(NmfBufs::W));
+        else
+            hipLaunchKernelGGL(k_nmf_w<NMF_KL>, grid, block, 0, c->stream, indptr, indices, val, n, K, kp, Ht(),
+                               m->as<double>(NmfBufs::HHT), m->as<double>(NmfBufs::HSUM), m->as<double>(NmfBufs::W));
+    }
+    void h_pass()   // needs cellsums() of the updated W; flips the current H
+    {
+        const dim3 block(NMF_TPB);
+        const int64_t *colptr = m->as<int64_t>(NmfBufs::COLPTR), *cptr = m->as<int64_t>(NmfBufs::CPTR);
+        const int32_t *crow = m->as<int32_t>(NmfBufs::CROW), *cgene = m->as<int32_t>(NmfBufs::CGENE);
+        const double *cval = m->as<double>(NmfBufs::CVAL), *W = m->as<double>(NmfBufs::W), *cs = m->as<double>(NmfBufs::CELLSUM);
+        double *part = m->as<double>(NmfBufs::HPART);
+        if (loss == NMF_FRO) {
+            if (chunks) hipLaunchKernelGGL(k_nmf_h<NMF_FRO>, dim3(groups_grid(chunks)), block, 0, c->stream, colptr, crow, cval, cptr, cgene, chunks, K, kp, W, Ht(), part);
+            hipLaunchKernelGGL(k_nmf_h_finish<NMF_FRO>, dim3(groups_grid(G)), block, 0, c->stream, cptr, part, G, K, kp, cs, H(), Hother(), Htother());
+        } else {
+            if (chunks) hipLaunchKernelGGL(k_nmf_h<NMF_KL>, dim3(groups_grid(chunks)), block, 0, c->stream, colptr, crow, cval, cptr, cgene, chunks, K, kp, W, Ht(), part);
+            hipLaunchKernelGGL(k_nmf_h_finish<NMF_KL>, dim3(groups_grid(G)), block, 0, c->stream, cptr, part, G, K, kp, cs, H(), Hother(), Htother());
+        }
+        cur ^= 1;
+    }
+    // the error of the current (W, H): enqueues everything, waits, returns the value
+    int error(double *out) const
+    {
+        {
+            KernelTimerScope ts(c, SC_K_NMF_ERR);
+            hprep();
+            cellsums();
+            const dim3 grid(groups_grid(n)), block(NMF_TPB);
+            const int64_t *indptr = m->as<int64_t>(NmfBufs::INDPTR);
+            const int32_t *indices = m->as<int32_t>(NmfBufs::INDICES);
+            const double *val = m->as<double>(NmfBufs::VAL), *W = m->as<double>(NmfBufs::W);
+            double *rowerr = m->as<double>(NmfBufs::ROWERR), *part = m->as<double>(NmfBufs::ERRPART);
+            const double *cs = m->as<double>(NmfBufs::CELLSUM);
+            double *err = m->as<double>(NmfBufs::ERR);
+            if (loss == NMF_FRO) hipLaunchKernelGGL(k_nmf_rowerr<NMF_FRO>, grid, block, 0, c->stream, indptr, indices, val, n, K, kp, Ht(), W, rowerr);
+            else hipLaunchKernelGGL(k_nmf_rowerr<NMF_KL>, grid, block, 0, c->stream, indptr, indices, val, n, K, kp, Ht(), W, rowerr);
+            hipLaunchKernelGGL(k_nmf_rowerr_chunks, dim3((unsigned)ceil_div64(cell_chunks, 64)), dim3(64), 0, c->stream, rowerr, n, cell_chunks, part);
+            if (loss == NMF_FRO) hipLaunchKernelGGL(k_nmf_err_final<NMF_FRO>, dim3(1), dim3(64), 0, c->stream, part, cell_chunks, K, cs, m->as<double>(NmfBufs::HHT), xconst, err);
+            else hipLaunchKernelGGL(k_nmf_err_final<NMF_KL>, dim3(1), dim3(64), 0, c->stream, part, cell_chunks, K, cs, m->as<double>(NmfBufs::HSUM), xconst, err);
+        }
+        SC_HIP(hipGetLastError());
+        SC_HIP(hipMemcpyAsync(out, m->as<double>(NmfBufs::ERR), sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        SC_HIP(hipStreamSynchronize(c->stream));
+        return SC_OK;
+    }
+};
+
+template <class T>
+int nmf_check_values(const T *data, int64_t nnz, double *sumsq, double *sumpos)
+{
+    double a = 0.0, b = 0.0;
+    for (int64_t p = 0; p < nnz; ++p) {
+        const double x = (double)data[p];
+        SC_REQUIRE(std::isfinite(x), SC_ERR_INVALID, "sc_nmf_fit: stored value %lld is not finite", (long long)p);
+        SC_REQUIRE(x >= 0.0, SC_ERR_INVALID, "sc_nmf_fit: stored value %lld is negative", (long long)p);
+        a = a + x * x;
+        if (x > NMF_EPS) b = b + x;
+    }
+    *sumsq = a;
+    *sumpos = b;
+    return SC_OK;
+}
+
+}  // namespace
+
+extern "C" int sc_nmf_fit(sc_ctx *c, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
+                          int32_t n_genes, int32_t K, int32_t loss, int32_t update_H, int32_t max_iter, double tol, double *W,
+                          double *H, double *err_trace_out, int32_t *n_checks_out, int32_t *n_iter_out, double *recon_err_out)
+{
+    SC_REQUIRE(c && indptr && W && H && err_trace_out && n_checks_out && n_iter_out && recon_err_out, SC_ERR_INVALID,
+               "sc_nmf_fit: null pointer");
+    SC_REQUIRE(dtype == SC_F32 || dtype == SC_F64, SC_ERR_INVALID, "sc_nmf_fit: dtype must be SC_F32 or SC_F64");
+    SC_REQUIRE(n >= 1 && n <= INT32_MAX, SC_ERR_INVALID, "sc_nmf_fit: need 1 <= n <= 2^31 - 1, got %lld", (long long)n);
+    SC_REQUIRE(n_genes >= 1 && n_genes <= 32768, SC_ERR_INVALID, "sc_nmf_fit: need 1 <= n_genes <= 32768, got %d", n_genes);
+    SC_REQUIRE(K >= 1 && K <= NMF_KMAX, SC_ERR_INVALID, "sc_nmf_fit: need 1 <= K <= %d, got %d", NMF_KMAX, K);
+    SC_REQUIRE(loss == NMF_FRO || loss == NMF_KL, SC_ERR_INVALID,
+               "sc_nmf_fit: loss must be 2 (frobenius) or 1 (kullback-leibler), got %d", loss);
+    SC_REQUIRE(max_iter >= 1, SC_ERR_INVALID, "sc_nmf_fit: max_iter must be >= 1, got %d", max_iter);
+    SC_REQUIRE(std::isfinite(tol) && tol >= 0.0, SC_ERR_INVALID, "sc_nmf_fit: tol must be finite and >= 0");
+    // canonical CSR: offsets from 0, non-decreasing; columns strictly ascending inside a row and inside [0, n_genes)
+    SC_REQUIRE(indptr[0] == 0, SC_ERR_INVALID, "sc_nmf_fit: indptr[0] must be 0");
+    for (int64_t i = 0; i < n; ++i)
+        SC_REQUIRE(indptr[i + 1] >= indptr[i], SC_ERR_INVALID, "sc_nmf_fit: indptr decreases at row %lld", (long long)i);
+    const int64_t nnz = indptr[n];
+    SC_REQUIRE(nnz >= 1 && nnz <= (int64_t)UINT32_MAX, SC_ERR_INVALID,
+               "sc_nmf_fit: need 1 <= stored entries <= 2^32 - 1, got %lld", (long long)nnz);
+    SC_REQUIRE(indices && data, SC_ERR_INVALID, "sc_nmf_fit: null pointer");
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t p = indptr[i]; p < indptr[i + 1]; ++p)
+            SC_REQUIRE(indices[p] >= 0 && indices[p] < n_genes && (p == indptr[i] || indices[p] > indices[p - 1]), SC_ERR_INVALID,
+                       "sc_nmf_fit: row %lld is not canonical (columns must ascend strictly inside [0, n_genes))", (long long)i);
+    double sumsq = 0.0, sumpos = 0.0;
+    if (dtype == SC_F32) SC_TRY(nmf_check_values((const float *)data, nnz, &sumsq, &sumpos));
+    else SC_TRY(nmf_check_values((const double *)data, nnz, &sumsq, &sumpos));
+    for (int64_t q = 0; q < n * K; ++q)
+        SC_REQUIRE(std::isfinite(W[q]) && W[q] >= 0.0, SC_ERR_INVALID, "sc_nmf_fit: W0 must be finite and >= 0");
+    for (int64_t q = 0; q < (int64_t)K * n_genes; ++q)
+        SC_REQUIRE(std::isfinite(H[q]) && H[q] >= 0.0, SC_ERR_INVALID, "sc_nmf_fit: H0 must be finite and >= 0");
+
+    SC_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int G = n_genes;
+    int kp = 1;
+    while (kp < K) kp <<= 1;
+    NmfBufs m(c);
+    NmfState st{c, &m, n, 0, ceil_div64(n, NMF_CELL_CHUNK), G, (int)K, kp, (int)loss};
+    st.xconst = loss == NMF_FRO ? sumsq : sumpos;
+    const size_t es = dtype == SC_F32 ? sizeof(float) : sizeof(double);
+    const size_t nW = sizeof(double) * (size_t)n * K, nH = sizeof(double) * (size_t)K * G;
+    const int P = K * K;
+
+    // ---- upload, fp64 values, the column-sorted copy and its chunks -------------------------------------------------
+    SC_TRY(m.get(NmfBufs::INDPTR, sizeof(int64_t) * (size_t)(n + 1)));
+    SC_TRY(m.get(NmfBufs::INDICES, sizeof(int32_t) * (size_t)nnz));
+    SC_TRY(m.get(NmfBufs::RAW, es * (size_t)nnz));
+    SC_TRY(m.get(NmfBufs::VAL, sizeof(double) * (size_t)nnz));
+    SC_TRY(m.get(NmfBufs::KEYS, sizeof(u64) * (size_t)nnz));
+    SC_TRY(m.get(NmfBufs::KEYS2, sizeof(u64) * (size_t)nnz));
+    SC_TRY(m.get(NmfBufs::POS, sizeof(uint32_t) * (size_t)nnz));
+    SC_TRY(m.get(NmfBufs::POS2, sizeof(uint32_t) * (size_t)nnz));
+    SC_TRY(m.get(NmfBufs::ROWID, sizeof(int32_t) * (size_t)nnz));
+    SC_TRY(m.get(NmfBufs::CROW, sizeof(int32_t) * (size_t)nnz));
+    SC_TRY(m.get(NmfBufs::CVAL, sizeof(double) * (size_t)nnz));
+    SC_TRY(m.get(NmfBufs::COLPTR, sizeof(int64_t) * (size_t)(G + 1)));
+    SC_TRY(m.get(NmfBufs::CPTR, sizeof(int64_t) * (size_t)(G + 1)));
+    SC_TRY(m.get(NmfBufs::W, nW));
+    SC_TRY(m.get(NmfBufs::H0, nH));
+    SC_TRY(m.get(NmfBufs::H1, nH));
+    SC_TRY(m.get(NmfBufs::HT0, nH));
+    SC_TRY(m.get(NmfBufs::HT1, nH));
+    SC_TRY(m.get(NmfBufs::HHT, sizeof(double) * (size_t)P));
+    SC_TRY(m.get(NmfBufs::HSUM, sizeof(double) * (size_t)K));
+    SC_TRY(m.get(NmfBufs::CELLPART, sizeof(double) * (size_t)st.cell_chunks * P));
+    SC_TRY(m.get(NmfBufs::CELLSUM, sizeof(double) * (size_t)P));
+    SC_TRY(m.get(NmfBufs::ROWERR, sizeof(double) * (size_t)n));
+    SC_TRY(m.get(NmfBufs::ERRPART, sizeof(double) * (size_t)st.cell_chunks));
+    SC_TRY(m.get(NmfBufs::ERR, sizeof(double)));
+    SC_HIP(hipMemcpyAsync(m.b[NmfBufs::INDPTR].p, indptr, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(m.b[NmfBufs::INDICES].p, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(m.b[NmfBufs::RAW].p, data, es * (size_t)nnz, hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(m.b[NmfBufs::W].p, W, nW, hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(m.b[NmfBufs::H0].p, H, nH, hipMemcpyHostToDevice, s));
+    int64_t chunks = 0;
+    {
+        KernelTimerScope ts(c, SC_K_NMF_SETUP);
+        const dim3 per_entry((unsigned)ceil_div64(nnz, 256)), per_gene((unsigned)ceil_div64(G + 1, 256)), tpb(256);
+        if (dtype == SC_F32)
+            hipLaunchKernelGGL(k_nmf_entries<float>, per_entry, tpb, 0, s, m.as<float>(NmfBufs::RAW), m.as<int32_t>(NmfBufs::INDICES), nnz,
+                               m.as<double>(NmfBufs::VAL), m.as<u64>(NmfBufs::KEYS), m.as<uint32_t>(NmfBufs::POS));
+        else
+            hipLaunchKernelGGL(k_nmf_entries<double>, per_entry, tpb, 0, s, m.as<double>(NmfBufs::RAW), m.as<int32_t>(NmfBufs::INDICES), nnz,
+                               m.as<double>(NmfBufs::VAL), m.as<u64>(NmfBufs::KEYS), m.as<uint32_t>(NmfBufs::POS));
+        hipLaunchKernelGGL(k_nmf_rowids, dim3((unsigned)ceil_div64(n, 256)), tpb, 0, s, m.as<int64_t>(NmfBufs::INDPTR), n, m.as<int32_t>(NmfBufs::ROWID));
+        int end_bit = 1;
+        while ((1 << end_bit) < G) ++end_bit;
+        SC_TRY((rs_sort<u64, uint32_t>(c, m.as<u64>(NmfBufs::KEYS), m.as<u64>(NmfBufs::KEYS2), m.as<uint32_t>(NmfBufs::POS),
+                                        m.as<uint32_t>(NmfBufs::POS2), nnz, end_bit)));
+        hipLaunchKernelGGL(k_nmf_csc_fill, per_entry, tpb, 0, s, m.as<uint32_t>(NmfBufs::POS2), m.as<int32_t>(NmfBufs::ROWID),
+                           m.as<double>(NmfBufs::VAL), nnz, m.as<int32_t>(NmfBufs::CROW), m.as<double>(NmfBufs::CVAL));
+        hipLaunchKernelGGL(k_nmf_colptr, per_gene, tpb, 0, s, m.as<u64>(NmfBufs::KEYS2), nnz, G, m.as<int64_t>(NmfBufs::COLPTR));
+        hipLaunchKernelGGL(k_nmf_chunk_scan, dim3(1), dim3(64), 0, s, m.as<int64_t>(NmfBufs::COLPTR), G, m.as<int64_t>(NmfBufs::CPTR));
+        hipLaunchKernelGGL(k_nmf_transpose, dim3((unsigned)ceil_div64((int64_t)K * G, 256)), tpb, 0, s, m.as<double>(NmfBufs::H0), (int)K, G,
+                           m.as<double>(NmfBufs::HT0));
+    }
+    SC_HIP(hipGetLastError());
+    SC_HIP(hipMemcpyAsync(&chunks, m.as<int64_t>(NmfBufs::CPTR) + G, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    SC_REQUIRE(chunks >= 1 && chunks <= nnz / NMF_COL_CHUNK + G, SC_ERR_HIP, "sc_nmf_fit: column chunk count %lld out of range",
+               (long long)chunks);
+    st.chunks = chunks;
+    SC_TRY(m.get(NmfBufs::CGENE, sizeof(int32_t) * (size_t)chunks));
+    SC_TRY(m.get(NmfBufs::HPART, sizeof(double) * (size_t)chunks * K));
+    {
+        KernelTimerScope ts(c, SC_K_NMF_SETUP);
+        hipLaunchKernelGGL(k_nmf_chunk_fill, dim3((unsigned)ceil_div64(G, 256)), dim3(256), 0, s, m.as<int64_t>(NmfBufs::CPTR), G,
+                           m.as<int32_t>(NmfBufs::CGENE));
+    }
+    SC_HIP(hipGetLastError());
+
+    // ---- sklearn's loop: one scalar comes back per check, nothing else waits for the host -------------------------------
+    double e0 = 0.0, e = 0.0;
+    SC_TRY(st.error(&e0));
+    int checks = 0;
+    err_trace_out[checks++] = e0;
+    double prev = e0;
+    int n_iter = 0, last_checked = 0;
+    for (int it = 1; it <= max_iter; ++it) {
+        {
+            KernelTimerScope ts(c, SC_K_NMF_W);
+            if (update_H || it == 1) st.hprep();
+            st.w_pass();
+        }
+        if (update_H) {
+            KernelTimerScope ts(c, SC_K_NMF_H);
+            st.cellsums();
+            st.h_pass();
+        }
+        SC_HIP(hipGetLastError());
+        n_iter = it;
+        if (tol > 0.0 && it % 10 == 0) {
+            SC_TRY(st.error(&e));
+            err_trace_out[checks++] = e;
+            last_checked = it;
+            if ((prev - e) / e0 < tol) break;
+            prev = e;
+        }
+    }
+    if (last_checked != n_iter) SC_TRY(st.error(&e));
+    SC_HIP(hipMemcpyAsync(W, m.b[NmfBufs::W].p, nW, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(H, st.H(), nH, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    *n_checks_out = checks;
+    *n_iter_out = n_iter;
+    *recon_err_out = e;
+    return SC_OK;
+}
