@@ -63,7 +63,11 @@ extern "C" {
 #define SC_K_NMF_W 23      /* ... H H^T / rowsum(H) and the W pass over the rows */
 #define SC_K_NMF_H 24      /* ... W^T W / colsum(W), the H pass over the column chunks and its finish */
 #define SC_K_NMF_ERR 25    /* ... an error evaluation (the initial one, every tenth iteration, the final one) */
-#define SC_K_COUNT_ 26
+#define SC_K_DIFF_KNN 26   /* sc_knn_dense: the brute-force search kernel and the merge of the candidate splits */
+#define SC_K_DIFF_GRAPH 27 /* sc_diffmap_graph*: scales, union (sort), kernel weights, normalisation, components */
+#define SC_K_DIFF_SPMV 28  /* sc_lanczos_run: the sparse matrix-vector products */
+#define SC_K_DIFF_ORTH 29  /* ... the two Gram-Schmidt passes, the norm and the scaling of every step */
+#define SC_K_COUNT_ 30
 
 typedef struct sc_ctx sc_ctx;
 
@@ -81,6 +85,8 @@ int sc_ctx_reset_timers(sc_ctx *ctx);
 /* Enable/disable per-launch HIP-event timing (default on; events are recorded on the ctx stream). */
 int sc_ctx_set_timing(sc_ctx *ctx, int enabled);
 int sc_ctx_device_mem(sc_ctx *ctx, int64_t *bytes_in_use);
+/* Free memory of the context's device as the runtime reports it now (hipMemGetInfo). */
+int sc_ctx_device_free(sc_ctx *ctx, int64_t *bytes_free);
 /* Development aid (scripts/concurrency_probe4.py, scripts/pipeline_soak.py): raw bytes of one of the generator's device buffers
  * (0 J, 1 raw stream, 2 accept masks, 3 entering counts, 4 block states, 5 scan state, 6 table, 7 inverse table). */
 int sc_debug_copy(sc_ctx *ctx, int which, int64_t offset_bytes, void *out, int64_t bytes);
@@ -682,6 +688,48 @@ int sc_gmm_posterior(sc_ctx *ctx, const void *scores, int dtype, int64_t n, int3
 int sc_nmf_fit(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
                int32_t n_genes, int32_t K, int32_t loss, int32_t update_H, int32_t max_iter, double tol, double *W, double *H,
                double *err_trace_out, int32_t *n_checks_out, int32_t *n_iter_out, double *recon_err_out);
+
+/* ---- N13 (extension): diffusion maps (Haghverdi et al. 2016) -- spatialcore_amd.diffusion -----------------------------
+ * All arithmetic fp64, every product and sum rounded separately, no floating-point atomics: every result is a function
+ * of the arguments alone, bit for bit.  The calls leave their results on the device for the next one:
+ *   sc_knn_dense -> sc_diffmap_graph   (or sc_diffmap_graph_csr alone) -> sc_lanczos_begin -> sc_lanczos_run ... ->
+ *   sc_lanczos_ritz -> sc_lanczos_end.
+ * sc_knn_dense: exact brute-force k nearest neighbours in d dimensions.  X[n][d] row-major SC_F32 (widened exactly) or
+ *   SC_F64, finite, |x| < 2^500.  d2(i, j) = sum_c (x_ic - x_jc)^2 added in column order from the c = 0 term; the neighbours of i are the
+ *   k cells j != i smallest in (d2, j).  idx_out[n][k] / d2_out[n][k] may be NULL (results stay on the device).
+ *   1 <= d <= 64, 2 <= k <= 32, k < n <= 2^31 - 1, n * k <= 2^29.  `splits` = 0 lets the library split the candidates over
+ *   workgroups for small n (any value gives the same bits); splits >= 1 forces that many (tests).
+ * sc_diffmap_graph: from the kept lists.  s2_i = median of row i's k squared distances ((a + b) / 2 for k even); a zero
+ *   scale is SC_ERR_INVALID.  Edges = symmetric union; w_ij = sqrt(2 sqrt(s2_i) sqrt(s2_j) / (s2_i + s2_j)) *
+ *   exp(-d2(i, j) / (s2_i + s2_j)); CSR rows sorted by column.  q_i = sum_j w_ij (column order, from 0), K'_ij = w_ij /
+ *   (q_i q_j), D_i = sum_j K'_ij, T_ij = K'_ij / (sqrt(D_i) sqrt(D_j)).  *n_components_out = connected components of the
+ *   edge set.  s2_out[n] may be NULL.
+ * sc_diffmap_graph_csr: the same from a caller's symmetric kernel matrix (canonical CSR, n x n, values finite and > 0,
+ *   every row non-empty; symmetry is the caller's to check).
+ * sc_diffmap_graph_get: indptr[n + 1], indices[nnz], w[nnz] (kernel weights) and, if not NULL, T[nnz].
+ * sc_lanczos_begin: v_0 = start / ||start|| (start[n], non-zero, finite); room for max_basis steps (1 <= max_basis <= n).
+ * sc_lanczos_run: `steps` more steps of Lanczos with full reorthogonalisation (classical Gram-Schmidt twice against
+ *   v_0 .. v_j); alpha_out[m], beta_out[m + 1] (beta[0] = ||start||, beta[j + 1] = norm after step j) for all m steps so
+ *   far, *m_out = m.  A beta below n 2^-52 is SC_ERR_STATE ("Krylov breakdown").
+ *   Step j: w = T v_j (row sums in column order from 0); pass 1: c_l = v_l . w for l = 0 .. j, then w_i <- w_i - v_li c_l
+ *   for l ascending; pass 2 the same with c'; alpha_j = c_j + c'_j; beta_{j+1} = sqrt(w . w); v_{j+1} = w / beta_{j+1}.
+ *   Every dot product: the index range in chunks of 1024; inside a chunk element e = r * 64 + lane, each lane adds its 16
+ *   products for r ascending from the first, the 64 lane sums meet in the adjacent-pair tree, a short last chunk is
+ *   padded with zero products; the chunk sums are added in chunk order from 0.
+ * sc_lanczos_ritz: y_l = sum_j v_j S[j][l] (j ascending from the first product; S is m x c row-major, c <= 64), scaled to
+ *   unit norm; vecs_out[c][n]; resid_out[l] = ||T y_l - lambda[l] y_l||_2, dots as above.
+ * sc_lanczos_end releases the basis. */
+int sc_knn_dense(sc_ctx *ctx, const void *X, int dtype, int64_t n, int32_t d, int32_t k, int32_t splits, int32_t *idx_out,
+                 double *d2_out);
+int sc_diffmap_graph(sc_ctx *ctx, double *s2_out, int64_t *n_edges_out, int64_t *n_components_out);
+int sc_diffmap_graph_csr(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const double *w, int64_t n,
+                         int64_t *n_components_out);
+int sc_diffmap_graph_get(sc_ctx *ctx, int64_t *indptr, int32_t *indices, double *w, double *T);
+int sc_lanczos_begin(sc_ctx *ctx, const double *start, int64_t max_basis);
+int sc_lanczos_run(sc_ctx *ctx, int32_t steps, double *alpha_out, double *beta_out, int64_t *m_out);
+int sc_lanczos_ritz(sc_ctx *ctx, const double *S, int64_t m, int32_t c, const double *lambda, double *vecs_out,
+                    double *resid_out);
+int sc_lanczos_end(sc_ctx *ctx);
 
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across

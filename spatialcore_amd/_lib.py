@@ -28,6 +28,7 @@ K_COOCCUR = 17
 K_LIGREC = 18
 K_RIPLEY_G_LIST, K_RIPLEY_G_RELABEL, K_RIPLEY_G_COUNT = 19, 20, 21
 K_NMF_SETUP, K_NMF_W, K_NMF_H, K_NMF_ERR = 22, 23, 24, 25
+K_DIFF_KNN, K_DIFF_GRAPH, K_DIFF_SPMV, K_DIFF_ORTH = 26, 27, 28, 29
 NMF_LOSSES = {"frobenius": 2, "kullback-leibler": 1}   # sc_nmf_fit's codes (sklearn's beta)
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
 
@@ -53,6 +54,7 @@ SYMBOLS = {
     "sc_ctx_moran_row_groups": [_P, _P],
     "sc_ctx_permgen_stats": [_P, _P, _P, _P, _P, _P],
     "sc_ctx_device_mem": [_P, POINTER(c_int64)],
+    "sc_ctx_device_free": [_P, POINTER(c_int64)],
     "sc_debug_copy": [_P, c_int, c_int64, _P, c_int64],   # buffers: 0 J, 1 raw stream, 2 accept masks, 3 entering counts, 4 block states, 5 scan state, 6 table, 7 inverse table
     "sc_knn_2d": [_P, _P, c_int64, c_int, c_int, _P, _P],
     "sc_knn_fetch": [_P, _P, _P],
@@ -119,6 +121,14 @@ SYMBOLS = {
     "sc_gmm_posterior": [_P, _P, c_int, c_int64, c_int32, _P, _P, _P, _P, c_int32, c_double, _P, _P, POINTER(c_int64)],
     "sc_nmf_fit": [_P, _P, _P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P,
                    POINTER(c_int32), POINTER(c_int32), POINTER(c_double)],
+    "sc_knn_dense": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, _P, _P],
+    "sc_diffmap_graph": [_P, _P, POINTER(c_int64), POINTER(c_int64)],
+    "sc_diffmap_graph_csr": [_P, _P, _P, _P, c_int64, POINTER(c_int64)],
+    "sc_diffmap_graph_get": [_P, _P, _P, _P, _P],
+    "sc_lanczos_begin": [_P, _P, c_int64],
+    "sc_lanczos_run": [_P, c_int32, _P, _P, POINTER(c_int64)],
+    "sc_lanczos_ritz": [_P, _P, c_int64, c_int32, _P, _P, _P],
+    "sc_lanczos_end": [_P],
     "sc_comm_unique_id": [_P],
     "sc_comm_create": [_P, _P, c_int, c_int, POINTER(c_void_p)],
     "sc_comm_destroy": [_P],
@@ -238,6 +248,7 @@ class Context:
         self.device = int(device)
         self._ripley_radii = 0   # radii of the resident Ripley pair list (shape of ripley_counts / ripley_counter results)
         self._ripley_g_radii = 0   # ... and of the resident Ripley's G neighbour lists
+        self._diff_n = self._diff_nnz = self._lanczos_cap = 0   # cells / stored entries of the resident diffusion graph, Lanczos basis cap
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -341,6 +352,12 @@ class Context:
     def device_mem(self) -> int:
         v = c_int64(0)
         _check(self._lib.sc_ctx_device_mem(self._h, byref(v)))
+        return v.value
+
+    def device_mem_free(self) -> int:
+        """Free memory of the device right now, in bytes."""
+        v = c_int64(0)
+        _check(self._lib.sc_ctx_device_free(self._h, byref(v)))
         return v.value
 
     # ---- A1 / A2 ----------------------------------------------------------------------------
@@ -877,6 +894,83 @@ class Context:
                                     byref(checks), byref(n_iter), byref(err)))
         return {"W": W, "H": H, "n_iter": n_iter.value, "reconstruction_err": err.value,
                 "error_trace": trace[:checks.value].copy()}
+
+    # ---- N13 (extension): diffusion maps ------------------------------------------------------
+    def knn_dense(self, X, k: int, fetch: bool = True, splits: int = 0):
+        """sc_knn_dense: the exact k nearest neighbours of every row of ``X`` (n, d), float32 or float64, by (squared
+        distance, index).  The lists stay on the device for ``diffmap_graph``; ``fetch`` also returns (indices, squared
+        distances).  ``splits`` forces a number of candidate splits (0: the library's choice; the result never differs)."""
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            raise ValueError(f"knn_dense: features must be float32 or float64, got {X.dtype}")
+        if X.ndim != 2:
+            raise ValueError(f"knn_dense: features must have shape (n, d), got {X.shape}")
+        n, d = X.shape
+        idx = np.empty((n, int(k)), dtype=np.int32) if fetch else None
+        d2 = np.empty((n, int(k)), dtype=np.float64) if fetch else None
+        _check(self._lib.sc_knn_dense(self._h, _ptr(X), SC_F32 if X.dtype == np.float32 else SC_F64, n, d, int(k), int(splits),
+                                      _ptr(idx), _ptr(d2)))
+        self._diff_n = n
+        return (idx, d2) if fetch else None
+
+    def diffmap_graph(self) -> dict:
+        """sc_diffmap_graph on the lists of the last ``knn_dense``: ``s2`` (local scales), ``n_edges`` (stored entries of
+        the symmetric kernel matrix), ``n_components``.  A zero scale raises ValueError."""
+        s2 = np.empty(self._diff_n, dtype=np.float64)
+        ne, nc = c_int64(0), c_int64(0)
+        _check(self._lib.sc_diffmap_graph(self._h, _ptr(s2), byref(ne), byref(nc)))
+        self._diff_nnz = ne.value
+        return {"s2": s2, "n_edges": ne.value, "n_components": nc.value}
+
+    def diffmap_graph_csr(self, indptr, indices, w) -> int:
+        """sc_diffmap_graph_csr: a caller's symmetric kernel matrix (canonical CSR) becomes the resident graph; returns
+        the number of connected components."""
+        indptr, indices, w = _c(indptr, np.int64), _c(indices, np.int32), _c(w, np.float64)
+        n = indptr.size - 1
+        if n < 1 or indices.size != w.size or indptr[-1] != w.size:
+            raise ValueError("diffmap_graph_csr: indptr, indices and values do not describe one CSR matrix")
+        nc = c_int64(0)
+        _check(self._lib.sc_diffmap_graph_csr(self._h, _ptr(indptr), _ptr(indices), _ptr(w), n, byref(nc)))
+        self._diff_n, self._diff_nnz = n, int(w.size)
+        return nc.value
+
+    def diffmap_graph_get(self, transition: bool = False):
+        """(indptr, indices, w) of the resident kernel matrix, rows sorted by column; with ``transition`` also T."""
+        indptr = np.empty(self._diff_n + 1, dtype=np.int64)
+        indices = np.empty(self._diff_nnz, dtype=np.int32)
+        w = np.empty(self._diff_nnz, dtype=np.float64)
+        T = np.empty(self._diff_nnz, dtype=np.float64) if transition else None
+        _check(self._lib.sc_diffmap_graph_get(self._h, _ptr(indptr), _ptr(indices), _ptr(w), _ptr(T)))
+        return (indptr, indices, w, T) if transition else (indptr, indices, w)
+
+    def lanczos_begin(self, start, max_basis: int) -> None:
+        v = _c(start, np.float64)
+        if v.shape != (self._diff_n,):
+            raise ValueError(f"lanczos_begin: the start vector must have shape ({self._diff_n},), got {v.shape}")
+        _check(self._lib.sc_lanczos_begin(self._h, _ptr(v), int(max_basis)))
+        self._lanczos_cap = int(max_basis)
+
+    def lanczos_run(self, steps: int):
+        """``steps`` more Lanczos steps; returns (alpha[m], beta[m + 1]) of all m steps so far (beta[0] = the start
+        vector's norm).  A Krylov breakdown raises RuntimeError."""
+        alpha = np.zeros(self._lanczos_cap, dtype=np.float64)
+        beta = np.zeros(self._lanczos_cap + 1, dtype=np.float64)
+        m = c_int64(0)
+        _check(self._lib.sc_lanczos_run(self._h, int(steps), _ptr(alpha), _ptr(beta), byref(m)))
+        return alpha[:m.value].copy(), beta[:m.value + 1].copy()
+
+    def lanczos_ritz(self, S, lam):
+        """Ritz vectors V S (S: m x c) scaled to unit norm, as (n, c), and their true residuals ||T y - lam y||."""
+        S, lam = _c(S, np.float64), _c(lam, np.float64)
+        if S.ndim != 2 or lam.shape != (S.shape[1],):
+            raise ValueError(f"lanczos_ritz: S must be (m, c) and lam (c,), got {S.shape} and {lam.shape}")
+        vecs = np.empty((S.shape[1], self._diff_n), dtype=np.float64)
+        res = np.empty(S.shape[1], dtype=np.float64)
+        _check(self._lib.sc_lanczos_ritz(self._h, _ptr(S), S.shape[0], S.shape[1], _ptr(lam), _ptr(vecs), _ptr(res)))
+        return np.ascontiguousarray(vecs.T), res
+
+    def lanczos_end(self) -> None:
+        _check(self._lib.sc_lanczos_end(self._h))
 
     # ---- N4 (extension) ---------------------------------------------------------------------
     def enrichment_counts(self, labels, n_types: int, n_perm: int, perm_row0: int = 0) -> np.ndarray:

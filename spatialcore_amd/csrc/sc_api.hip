@@ -184,6 +184,7 @@ int sc_ctx_destroy(sc_ctx *c)
                     &c->rs_goff, &c->rs_neg, &c->rs_flag, &c->rs_keys, &c->rs_keys2, &c->rs_pay, &c->rs_pay2, &c->rs_gkey, &c->rs_gkey2,
                     &c->rs_idx, &c->rs_idx2, &c->rs_tmp, &c->rs_rank2, &c->rs_tie, &c->rs_nnz, &c->rs_sum, &c->th_sorted};
     for (DBuf *b : bufs) b->release(&c->mem);
+    for (DBuf *b : c->df.bufs()) b->release(&c->mem);
     c->pg.release(&c->mem);
     for (int k = 0; k < SC_K_COUNT_; ++k) {
         for (auto &ev : c->timers[k].pending) {
@@ -316,6 +317,16 @@ int sc_ctx_device_mem(sc_ctx *c, int64_t *bytes)
 {
     SC_REQUIRE(c && bytes, SC_ERR_INVALID, "null pointer");
     *bytes = c->mem;
+    return SC_OK;
+}
+
+int sc_ctx_device_free(sc_ctx *c, int64_t *bytes_free)
+{
+    SC_REQUIRE(c && bytes_free, SC_ERR_INVALID, "null pointer");
+    SC_HIP(hipSetDevice(c->device));
+    size_t free_b = 0, total_b = 0;
+    SC_HIP(hipMemGetInfo(&free_b, &total_b));
+    *bytes_free = (int64_t)free_b;
     return SC_OK;
 }
 

@@ -172,6 +172,22 @@ struct sc_ctx {
     // ---- thresholds (sc_threshold.hip): the sorted fp64 scores of the last sc_ks_prepare, for sc_ks_argmax ----
     DBuf th_sorted;
     int64_t th_n = 0;
+    // ---- diffusion maps (sc_diffusion.hip): what one call leaves for the next -- the fp64 features and neighbour lists of
+    // the last sc_knn_dense, the kernel / transition matrix of the last sc_diffmap_graph*, the Lanczos basis ----
+    struct Diffusion {
+        int64_t n = 0, nnz = 0, m = 0, max_basis = 0;   // cells, stored entries, Lanczos steps taken, basis vectors allocated for
+        int d = 0, k = 0;                               // columns of X (the features padded to a multiple of 8), list length
+        bool knn_valid = false, graph_valid = false, lanczos_valid = false;
+        DBuf X, raw, idx, d2, pidx, pd2;        // [n][d] fp64, the upload, [n][k] result, [split][n][k] partial lists
+        DBuf s2, keys, keys2, pay, pay2, cnt, off;   // local scales; (row << 32 | column) keys, the sort's payload, first-of-run flags and offsets
+        DBuf indptr, indices, w, T, q, parent, flag;   // CSR (rows sorted by column): kernel weights, transition matrix; row sums; union-find
+        DBuf V, wv, part, coef, ab, Y, S, res;   // basis [max_basis + 1][n], work vector, chunk partials, coefficients, alpha | beta, Ritz vectors, their coefficients, residuals
+        std::vector<DBuf *> bufs()
+        {
+            return {&X, &raw, &idx, &d2, &pidx, &pd2, &s2, &keys, &keys2, &pay, &pay2, &cnt, &off, &indptr, &indices, &w, &T, &q,
+                    &parent, &flag, &V, &wv, &part, &coef, &ab, &Y, &S, &res};
+        }
+    } df;
 
     // ---- graph (CSR, rows sorted by column) + transpose ----
     int64_t g_n = 0, g_nnz = 0;

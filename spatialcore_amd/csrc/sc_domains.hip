@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "sc_search.h"
+#include "sc_unionfind.h"
 
 // ------------------------------------------------------------------------------------------------
 // components
@@ -27,32 +28,6 @@ __global__ __launch_bounds__(256) void k_dom_init(int32_t *__restrict__ parent, 
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) parent[i] = (int32_t)i;
-}
-
-__device__ __forceinline__ int32_t uf_load(const int32_t *a) { return __atomic_load_n(a, __ATOMIC_RELAXED); }
-
-// root of x, halving the path on the way: parent[x] <- its grandparent.  atomicMin: a parent only ever moves towards the
-// root, whatever other lanes write meanwhile.
-__device__ __forceinline__ int32_t uf_find(int32_t *parent, int32_t x)
-{
-    for (;;) {
-        const int32_t p = uf_load(parent + x);
-        if (p == x) return x;
-        const int32_t gp = uf_load(parent + p);
-        if (gp != p) atomicMin(parent + x, gp);
-        x = gp;
-    }
-}
-
-__device__ __forceinline__ void uf_union(int32_t *parent, int32_t a, int32_t b)
-{
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        if (atomicCAS(parent + hi, hi, lo) == hi) return;   // hi was still a root: hooked.  Otherwise look again.
-    }
 }
 
 __global__ __launch_bounds__(256) void k_dom_link(BinGrid g, int64_t n, double link2, int rings,

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "sc_search.h"
+#include "sc_topk.h"
 
 // ------------------------------------------------------------------------------------------------
 // binning
@@ -150,44 +151,6 @@ int sc_counts_to_offsets(sc_ctx *c, long long *counts, long long *offsets, int64
 // ------------------------------------------------------------------------------------------------
 // A1: exact kNN
 // ------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ bool cand_better(double d, int id, double ed, int eid)
-{
-    return d < ed || (d == ed && id < eid);
-}
-
-template <int K>
-struct TopK {
-    double d[K];
-    int id[K];
-    __device__ __forceinline__ void init()
-    {
-#pragma unroll
-        for (int j = 0; j < K; ++j) { d[j] = DBL_MAX; id[j] = 0x7fffffff; }
-    }
-    // sorted insert of a candidate known to beat the last entry
-    __device__ __forceinline__ void insert(double cd, int cid)
-    {
-        bool b_hi = cand_better(cd, cid, d[K - 1], id[K - 1]);  // vs entry j
-#pragma unroll
-        for (int j = K - 1; j > 0; --j) {
-            bool b_lo = cand_better(cd, cid, d[j - 1], id[j - 1]);  // vs entry j-1
-            double nd = b_lo ? d[j - 1] : (b_hi ? cd : d[j]);
-            int ni = b_lo ? id[j - 1] : (b_hi ? cid : id[j]);
-            d[j] = nd;
-            id[j] = ni;
-            b_hi = b_lo;
-        }
-        if (b_hi) { d[0] = cd; id[0] = cid; }
-    }
-    __device__ __forceinline__ double kth(int k) const
-    {
-        double v = d[K - 1];
-#pragma unroll
-        for (int j = 0; j < K; ++j) v = (j == k - 1) ? d[j] : v;
-        return v;
-    }
-};
 
 template <int K>
 __global__ __launch_bounds__(256) void k_knn(BinGrid g, int64_t n, int k, int include_self,
