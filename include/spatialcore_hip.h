@@ -118,17 +118,22 @@ int sc_ctx_set_permgen_mode(sc_ctx *ctx, int mode);
 /* Why the generator is not using its block-parallel form, "" when it is.  The form orders its kernels through words in
  * device memory and needs its streams on different hardware queues (the library asks for GPU_MAX_HW_QUEUES=24 when it is
  * loaded before the HIP runtime initialises -- a host application that initialised HIP first keeps its own setting);
- * the context probes that once (5 rounds of 5-ms waits at worst), falls back to the sequential scan with identical
- * results, and leaves the reason here.  sc_ctx_set_permgen_mode re-arms the probe. */
+ * the context finds out once: plain streams and a probe where the environment's value holds its eleven streams; its
+ * streams spread over the three stream priority levels (the runtime's limit is per level) and a probe of all eleven
+ * where the value is smaller but at least 4, or the plain probe failed; else the sequential scan with identical results,
+ * and the reason here.  The spread placement is no degradation and leaves "" here (sc_ctx_permgen_form names it).
+ * Every probe wait is bounded (20 ms).  sc_ctx_set_permgen_mode re-arms the whole ladder. */
 int sc_ctx_permgen_note(sc_ctx *ctx, const char **message);
-/* The same question asked up front instead of discovered inside the first job (spatialcore_amd.init()): probe the
- * context's generator streams now; *concurrent = 1 when they overlap (the block-parallel form is available),
+/* The same question asked up front instead of discovered inside the first job (spatialcore_amd.init()): place and probe
+ * the context's streams now (not while a job begun by sc_moran_seeded_begin is in flight: the streams may be
+ * re-created); *concurrent = 1 when they overlap (the block-parallel form is available),
  * *hw_queues_requested = the GPU_MAX_HW_QUEUES value in this process's environment (0: unset).  The reference has no
  * counterpart (single process, no device: AC:580 n_jobs=1); SURVEY section 5 "failure detection": a degradation must
  * surface like an error does. */
 int sc_ctx_probe_streams(sc_ctx *ctx, int *concurrent, int *hw_queues_requested);
 /* The scan form a permutation job of length n takes on this context right now, in words -- "block-parallel",
- * "sequential (...)" or "sequential: <reason>" -- for the provenance entry the drop-in functions append
+ * "block-parallel; streams spread over three priority levels (GPU_MAX_HW_QUEUES=4)", "sequential (...)" or
+ * "sequential: <reason>" -- for the provenance entry the drop-in functions append
  * (src/spatialcore/core/metadata.py:49-77).  Valid until the next call of this function on the context. */
 int sc_ctx_permgen_form(sc_ctx *ctx, int64_t n, const char **form);
 /* Completed generator jobs by scan form, how often the block-parallel form failed its verification and the

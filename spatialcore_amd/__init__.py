@@ -24,8 +24,10 @@ def init(device: int = 0) -> dict:
         report = spatialcore_amd.init()
         # {'device': 0, 'hw_queues_requested': 24, 'streams_concurrent': True, 'generator': 'block-parallel'}
 
-    ``streams_concurrent`` is MEASURED (a five-round stream probe, a few milliseconds); a ``False`` comes with a warning
-    on the ``spatialcore_amd`` logger and ``generator`` = ``"sequential: <reason>"``.  Every drop-in function also records the
+    ``streams_concurrent`` is MEASURED (a stream probe, a few milliseconds); a ``False`` comes with a warning
+    on the ``spatialcore_amd`` logger and ``generator`` = ``"sequential: <reason>"``.  A process held to fewer queues (a
+    launcher that exports 4, HIP initialised first) gets ``"block-parallel; streams spread over three priority levels
+    (GPU_MAX_HW_QUEUES=4)"``: same form, same speed, no warning.  Every drop-in function also records the
     form it ran with as ``permgen_form`` in its ``adata.uns["spatialcore_metadata"]`` entry.  Raises without a gfx950 GPU
     (there is no CPU fallback)."""
     from spatialcore_amd import _lib

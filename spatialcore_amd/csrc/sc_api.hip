@@ -9,12 +9,13 @@ static thread_local char g_err[1024] = "";
 
 // The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and kernels of
 // streams that share a hardware queue run strictly one after the other.  The generator / scoring pipeline of
-// sc_moran_seeded uses nine streams whose kernels should overlap (a 25-ms scoring launch in front of the generator's
+// sc_moran_seeded uses eleven streams whose kernels should overlap (a 25-ms scoring launch in front of the generator's
 // sub-millisecond chain launches doubles the step), so the library asks for one hardware queue per stream -- before
 // the runtime initialises, i.e. when the library is loaded, and only if the user has not set the variable.  It is a
 // REQUEST, not a requirement: a host application that initialised HIP earlier (or set a smaller value) keeps its
-// setting; the generator probes its streams before its first block-parallel job (permgen_probe_streams), uses the
-// sequential scan when they cannot overlap, and says so through sc_ctx_permgen_note (logged once by the Python layer).
+// setting; the context then spreads its streams over the stream priority levels, each of which has the setting's
+// worth of queues, probes them before its first block-parallel job (permgen_place_streams), uses the sequential scan
+// when they still cannot overlap, and says so through sc_ctx_permgen_note (logged once by the Python layer).
 // 24 = two contexts' worth: a context creates up to 11 streams, and once a process's streams outnumber the setting the
 // runtime lets them SHARE queues (r03: with 16, a second context in one process found its generator streams on shared
 // queues and fell back; 24 and 32 were measured: same bench step as 16, every test with two live contexts green).
@@ -60,6 +61,65 @@ void DBuf::release(int64_t *acct)
     cap = 0;
 }
 
+sc_ctx::sc_ctx() { pg.streams = &streams; }
+sc_ctx::~sc_ctx() = default;
+
+// ---- the context's streams (sc_ctx.h: StreamTable) ----
+int StreamTable::ensure(int role)
+{
+    if (s[role]) return SC_OK;
+    if (placement != SC_PLACE_SPREAD) {
+        SC_HIP(hipStreamCreateWithFlags(&s[role], hipStreamNonBlocking));
+        return SC_OK;
+    }
+    int least = 0, greatest = 0;   // numerically: greatest priority <= normal (0) <= least priority
+    SC_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    const int prio = level[role] == SL_HIGH ? greatest : level[role] == SL_LOW ? least : 0;
+    SC_HIP(hipStreamCreateWithPriority(&s[role], hipStreamNonBlocking, prio));
+    return SC_OK;
+}
+
+int StreamTable::sync(unsigned roles)
+{
+    for (int r = 0; r < SR_COUNT; ++r)
+        if ((roles >> r & 1u) && s[r]) SC_HIP(hipStreamSynchronize(s[r]));
+    return SC_OK;
+}
+
+int StreamTable::replace(int new_placement, const int *new_level)
+{
+    bool same = new_placement == placement;
+    for (int r = 0; r < SR_COUNT && same && placement == SC_PLACE_SPREAD; ++r) same = level[r] == new_level[r];
+    if (same) return SC_OK;
+    // The context stream stays what it is: a timer scope around the caller holds its handle, and a stream of the normal
+    // level is a plain stream -- which is why sc_streams.h keeps SR_SCORE's group there.
+    SC_REQUIRE(new_placement != SC_PLACE_SPREAD || new_level[SR_SCORE] == SL_NORMAL, SC_ERR_STATE,
+               "stream placement: the context stream belongs on the normal level");
+    bool had[SR_COUNT];
+    for (int r = 0; r < SR_COUNT; ++r) {
+        had[r] = s[r] != nullptr;
+        if (s[r]) SC_HIP(hipStreamSynchronize(s[r]));
+    }
+    for (int r = 0; r < SR_COUNT; ++r) {
+        level[r] = new_placement == SC_PLACE_SPREAD ? new_level[r] : SL_NORMAL;
+        if (r == SR_SCORE) continue;
+        if (s[r]) (void)hipStreamDestroy(s[r]);
+        s[r] = nullptr;
+    }
+    placement = new_placement;
+    for (int r = 0; r < SR_COUNT; ++r)
+        if (had[r]) SC_TRY(ensure(r));
+    return SC_OK;
+}
+
+void StreamTable::release()
+{
+    for (hipStream_t &sp : s) {
+        if (sp) (void)hipStreamDestroy(sp);
+        sp = nullptr;
+    }
+}
+
 KernelTimerScope::KernelTimerScope(sc_ctx *ctx, int kid, hipStream_t on) : c(ctx), id(kid), s(on ? on : ctx->stream)
 {
     if (!c->timing) return;
@@ -88,12 +148,7 @@ KernelTimerScope::~KernelTimerScope()
 
 int sc_timer_collect(sc_ctx *c)
 {
-    SC_HIP(hipStreamSynchronize(c->stream));
-    if (c->stream2) SC_HIP(hipStreamSynchronize(c->stream2));
-    if (c->stream3) SC_HIP(hipStreamSynchronize(c->stream3));
-    if (c->stream4) SC_HIP(hipStreamSynchronize(c->stream4));
-    SC_TRY(c->pg.sync());
-    if (c->stream_out) SC_HIP(hipStreamSynchronize(c->stream_out));
+    SC_TRY(c->streams.sync(SR_MASK_PIPELINE));
     for (int k = 0; k < SC_K_COUNT_; ++k) {
         KTimer &t = c->timers[k];
         for (auto &ev : t.pending) {
@@ -144,11 +199,10 @@ int sc_ctx_create(int device, sc_ctx **out)
     }
     sc_ctx *c = new sc_ctx();
     c->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
+    const int rc = c->streams.ensure(SR_SCORE);
+    if (rc != SC_OK) {
         delete c;
-        sc_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
-        return SC_ERR_HIP;
+        return rc;
     }
     *out = c;
     return SC_OK;
@@ -164,7 +218,6 @@ int sc_ctx_destroy(sc_ctx *c)
     if (c->prep_host) (void)hipHostFree(c->prep_host);
     if (c->mom_ready) (void)hipEventDestroy(c->mom_ready);
     if (c->mom_done) (void)hipEventDestroy(c->mom_done);
-    if (c->stream_m) (void)hipStreamDestroy(c->stream_m);
     if (c->knn_done) (void)hipEventDestroy(c->knn_done);
     (void)hipStreamSynchronize(c->stream);
     DBuf *bufs[] = {&c->px, &c->py, &c->sx, &c->sy, &c->sid, &c->bin_start, &c->bin_keys,
@@ -196,11 +249,7 @@ int sc_ctx_destroy(sc_ctx *c)
             (void)hipEventDestroy(ev.second);
         }
     }
-    if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    if (c->stream3) (void)hipStreamDestroy(c->stream3);
-    if (c->stream4) (void)hipStreamDestroy(c->stream4);
-    if (c->stream_out) (void)hipStreamDestroy(c->stream_out);
-    (void)hipStreamDestroy(c->stream);
+    c->streams.release();
     delete c;
     return SC_OK;
 }

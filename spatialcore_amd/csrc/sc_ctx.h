@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/spatialcore_hip.h"
+#include "sc_streams.h"
 
 #define SC_TILE 16  // genes per tile: one 128-byte fp64 row per cell and tile
 #define PERM_CHUNK 128  // permutations per pipeline stage (generator scan -> swaps -> scoring)
@@ -57,49 +58,57 @@ struct KTimer {
     int64_t launches = 0;
 };
 
-// The numpy-exact permutation generator's state in the context (sc_permgen.h): scratch, its own streams and events, its form, counters
+// The one owner of a context's streams (sc_streams.h: roles, placements; sc_api.hip).  A role's stream is created on
+// demand, the way the placement says: plain = hipStreamNonBlocking on the normal level, priority-spread = the same flag
+// on the role's level.  The placement is chosen once per context by permgen_place_streams (sc_permgen_phi.hip).
+constexpr unsigned SR_MASK_GENERATOR = (1u << SR_EXPAND) | (1u << SR_PREP0) | (1u << SR_PREP1) | (1u << SR_PREP2) | (1u << SR_PREP3);
+constexpr unsigned SR_MASK_PIPELINE = ((1u << SR_COUNT) - 1u) & ~(1u << SR_MOMENTS);   // what a pipeline's drain waits for
+struct StreamTable {
+    hipStream_t s[SR_COUNT] = {};
+    int placement = SC_PLACE_PLAIN;
+    int level[SR_COUNT] = {};            // priority-spread: StreamLevel per role
+    int ensure(int role);                // create the role's stream if it does not exist yet
+    int sync(unsigned roles);            // wait for the existing streams among `roles` (bit r = role r)
+    // Take another placement.  Existing streams must be idle: they are destroyed and created again where they belong.
+    int replace(int new_placement, const int *new_level);
+    void release();
+};
+
+// The numpy-exact permutation generator's state in the context (sc_permgen.h): scratch, its events, its form, counters
 struct PermGen {
     DBuf J, raw, out, bits, enter, sblk;  // accepted j per step, raw 32-bit stream, scan state + chunk ranges, per block: accept masks, entering counts, entry state
     DBuf flags;       // hand-over words between the chain workgroup and the preparation launches (sc_permgen_phi.hip)
     DBuf desc, tbits, events, hard;  // block-parallel scan: per-block descriptors + gap-transfer tables (ring), hard flags
     DBuf seglist;                    // ... per unit in flight: [count | first blocks of the segments k_phi_compose builds]
     DBuf seg, ctbits, segmode;       // ... segments of prepared blocks: descriptors + composed tables (ring), per-block mode
-    hipStream_t stream_pg[4] = {};   // block-parallel scan: the chip prepares blocks here ahead of the chain
-    hipStream_t stream_px = nullptr; // ... and verifies + expands a finished chunk here, beside the next chunk's chain
+    StreamTable *streams = nullptr;  // the context's table: SR_PREP0 .. 3 (the chip prepares blocks there ahead of the chain), SR_EXPAND
     hipEvent_t ev[34] = {};          // [0 .. 3] k_seg_fill of a chunk done on preparation stream q, [32] raw stream written, [33] chain of a chunk done
     int mode = 0;                    // 0 auto, 1 sequential scan only, 2 fault injection (tests)
     bool streams_serial = false;     // a wait on a hand-over word gave up once: the streams of this process do not run concurrently (profiler
                                      // that serialises kernels, shared hardware queues) -- later jobs take the sequential scan at once
-    bool probed = false;             // the stream-concurrency probe ran (once per context, before the first block-parallel job)
+    bool probed = false;             // the placement ladder and its probe ran (once per context, before the first block-parallel job)
     std::string note;                // why the generator left the block-parallel form, if it did (sc_ctx_permgen_note)
+    std::string placement_note;      // the block-parallel form on another placement than plain streams (sc_ctx_permgen_form; no degradation)
     std::string form;                // scratch of sc_ctx_permgen_form
     int64_t jobs_parallel = 0, jobs_sequential = 0, fallbacks = 0;  // generator jobs by scan form
     int64_t blocks_prepared = 0, blocks_chain = 0;  // block-parallel jobs: blocks resolved by table lookup / by the chain workgroup
     int ensure(bool preparation)     // create what is missing: the events, and (preparation) the preparation streams
     {
         if (preparation)
-            for (hipStream_t &sp : stream_pg)
-                if (!sp) SC_HIP(hipStreamCreateWithFlags(&sp, hipStreamNonBlocking));
+            for (int r = SR_PREP0; r <= SR_PREP3; ++r) SC_TRY(streams->ensure(r));
         for (hipEvent_t &e : ev)
             if (!e) SC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         return SC_OK;
     }
-    int sync()                       // wait for the generator's own streams
-    {
-        for (hipStream_t sp : {stream_pg[0], stream_pg[1], stream_pg[2], stream_pg[3], stream_px})
-            if (sp) SC_HIP(hipStreamSynchronize(sp));
-        return SC_OK;
-    }
+    int sync() { return streams->sync(SR_MASK_GENERATOR); }   // wait for the generator's own streams
     // sc_ctx_set_permgen_mode.  Re-arms: a context that fell back to the sequential scan after one stalled hand-over (a transient: GPU
-    // shared with another process, a profiler pass) probes its streams again and may return to the block-parallel form
-    void rearm(int new_mode) { mode = new_mode; streams_serial = false; probed = false; note.clear(); }
-    void release(int64_t *acct)      // buffers, streams, events
+    // shared with another process, a profiler pass) goes through the placement ladder again and may return to the block-parallel form
+    void rearm(int new_mode) { mode = new_mode; streams_serial = false; probed = false; note.clear(); placement_note.clear(); }
+    void release(int64_t *acct)      // buffers, events (the streams are the table's)
     {
         (void)sync();
         for (DBuf *b : {&J, &raw, &out, &bits, &enter, &sblk, &flags, &desc, &tbits, &events, &hard, &seglist, &seg, &ctbits, &segmode})
             b->release(acct);
-        for (hipStream_t sp : {stream_pg[0], stream_pg[1], stream_pg[2], stream_pg[3], stream_px})
-            if (sp) (void)hipStreamDestroy(sp);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
     }
@@ -120,13 +129,19 @@ struct PermPipe;   // a generator job in flight (sc_permgen.h, sc_perm.hip; begu
 struct sc_ctx {
     int device = 0;
     std::unique_ptr<PermPipe> pipe;  // the generator / consumer pipeline begun by sc_moran_seeded_begin, until _finish
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;  // fused permutation/Moran pipeline: rejection scan runs ahead here
-    hipStream_t stream3 = nullptr;  // ... and the Fisher-Yates swaps of the scanned chunk here
-    hipStream_t stream4 = nullptr;  // ... alternating with this one
-    hipStream_t stream_out = nullptr;    // r04: what leaves a pipeline beside it: result copies issued by a helper thread (sc_local_moran_seeded,
-                                         // sc_local_stat_seeded); Moran's finalise launches, beside the next chunk's scoring (sc_moran.hip: MoranRing)
+    StreamTable streams;            // every stream of the context, by role; the names below are its entries
+    hipStream_t &stream = streams.s[SR_SCORE];
+    hipStream_t &stream2 = streams.s[SR_CHAIN];   // fused permutation/Moran pipeline: rejection scan runs ahead here
+    hipStream_t &stream3 = streams.s[SR_SWAP_A];  // ... and the Fisher-Yates swaps of the scanned chunk here
+    hipStream_t &stream4 = streams.s[SR_SWAP_B];  // ... alternating with this one
+    hipStream_t &stream_out = streams.s[SR_FINALISE];  // r04: what leaves a pipeline beside it: result copies issued by a helper thread (sc_local_moran_seeded,
+                                                       // sc_local_stat_seeded); Moran's finalise launches, beside the next chunk's scoring (sc_moran.hip: MoranRing)
+    hipStream_t &stream_px = streams.s[SR_EXPAND];     // the generator verifies + expands a finished chunk here, beside the next chunk's chain
+    hipStream_t *const stream_pg = streams.s + SR_PREP0;   // [4]: its preparation streams
     PermGen pg;       // the numpy-exact permutation generator's state
+    sc_ctx();         // (sc_api.hip, where PermPipe is complete)
+    ~sc_ctx();
+    sc_ctx(const sc_ctx &) = delete;
     int64_t mem = 0;  // bytes allocated through DBuf
     bool timing = true;
     KTimer timers[SC_K_COUNT_];
@@ -199,7 +214,7 @@ struct sc_ctx {
     DBuf gt_indptr, gt_indices, gt_data, gt_cursor;
     // the full moments (transpose + reverse-edge search: 6 ms at 1M x 15) may be in flight on a side stream, begun by the
     // scoring's set-up so that they leave its serial prelude (sc_graph.hip: graph_moments_begin / graph_moments)
-    hipStream_t stream_m = nullptr;
+    hipStream_t &stream_m = streams.s[SR_MOMENTS];
     hipEvent_t mom_ready = nullptr, mom_done = nullptr;
     bool mom_pending = false;
     double *mom_host = nullptr;      // pinned: per-block partials of k_moments

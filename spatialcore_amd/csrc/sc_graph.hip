@@ -382,7 +382,7 @@ int sc_graph_moments_begin(sc_ctx *c)
     SC_REQUIRE(c->g_n > 0, SC_ERR_STATE, "no graph set");
     const int64_t n = c->g_n;
     const int blocks = (int)ceil_div64(n, MOM_ROWS_PER_BLOCK);
-    if (!c->stream_m) SC_HIP(hipStreamCreateWithFlags(&c->stream_m, hipStreamNonBlocking));
+    SC_TRY(c->streams.ensure(SR_MOMENTS));
     if (!c->mom_ready) SC_HIP(hipEventCreateWithFlags(&c->mom_ready, hipEventDisableTiming));
     if (!c->mom_done) SC_HIP(hipEventCreateWithFlags(&c->mom_done, hipEventDisableTiming));
     if (blocks > c->mom_blocks) {

@@ -124,7 +124,7 @@ int lp_counter_batches(sc_ctx *c, const char *who, uint64_t seed, int64_t n, int
                        const std::function<void(int)> &accumulate)
 {
     if (n_perm > 0) SC_TRY(sc_perm_alloc(c, n, batch));
-    if (!c->stream3) SC_HIP(hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
+    SC_TRY(c->streams.ensure(SR_SWAP_A));
     const int64_t batches = n_perm > 0 ? ceil_div64(n_perm, batch) : 0;
     auto rows = [&](int64_t b) { return (int)(b * batch + batch < n_perm ? batch : n_perm - b * batch); };
     std::vector<hipEvent_t> ev((size_t)batches * 2, nullptr);   // per batch: generated, relabelled

@@ -538,7 +538,7 @@ static int local_run_seeded(sc_ctx *c, const char *who, int stat, int star, uint
         SC_TRY(lm_prepare(c, n_perm, j));
         SC_TRY(local_observed(c, j, stat, star));
         if (copier_started) return SC_OK;
-        if (!c->stream_out) SC_HIP(hipStreamCreateWithFlags(&c->stream_out, hipStreamNonBlocking));
+        SC_TRY(c->streams.ensure(SR_FINALISE));
         SC_TRY(c->lm_out.ensure(sizeof(float) * (size_t)j.n * (size_t)j.G, &c->mem));
         hipEvent_t ready;
         SC_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));

@@ -1005,7 +1005,7 @@ __global__ __launch_bounds__(256) void k_moran_finalize_nib(const double *__rest
 static int moran_ring_begin(sc_ctx *c, size_t slice)
 {
     MoranRing &r = c->ring;
-    if (!c->stream_out) SC_HIP(hipStreamCreateWithFlags(&c->stream_out, hipStreamNonBlocking));
+    SC_TRY(c->streams.ensure(SR_FINALISE));
     // (a job that ended in an error may have left finalise launches behind: they read what this job's set-up rewrites)
     if (r.launches > 0) SC_HIP(hipStreamSynchronize(c->stream_out));
     for (int k = 0; k < MORAN_RING; ++k) {

@@ -200,7 +200,7 @@ static int pipe_generate(sc_ctx *c, PermPipe &pp, int64_t k)
     hipStream_t sw = overlap ? c->stream4 : c->stream3;
     SC_HIP(hipEventCreateWithFlags(&scanned, hipEventDisableTiming));
     SC_HIP(hipEventCreateWithFlags(&swapped, hipEventDisableTiming));
-    SC_TRY(permgen_scan_chunk(c, &pp.job, pp.bounds[(size_t)k + 1], c->stream2, c->pg.stream_px, scanned));
+    SC_TRY(permgen_scan_chunk(c, &pp.job, pp.bounds[(size_t)k + 1], c->stream2, c->stream_px, scanned));
     SC_HIP(hipStreamWaitEvent(sw, scanned, 0));
     // Two permutations per swap workgroup while the chain still runs -- workgroups of the preparation kernels' own size --
     // but only beside the Moran scoring kernel (the one consumer that fills its CUs with wavefronts that live for
@@ -217,12 +217,7 @@ static int pipe_generate(sc_ctx *c, PermPipe &pp, int64_t k)
 
 void pipe_drain(sc_ctx *c, PermPipe &pp)
 {
-    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-    if (c->stream3) (void)hipStreamSynchronize(c->stream3);
-    if (c->stream4) (void)hipStreamSynchronize(c->stream4);
-    (void)c->pg.sync();
-    (void)hipStreamSynchronize(c->stream);
-    if (c->stream_out) (void)hipStreamSynchronize(c->stream_out);   // (a consumer's launches beside its scoring: Moran's finalise)
+    (void)c->streams.sync(SR_MASK_PIPELINE);   // (SR_FINALISE: a consumer's launches beside its scoring, Moran's finalise)
     for (hipEvent_t e : pp.ev)
         if (e) (void)hipEventDestroy(e);
     pp.ev.clear();
@@ -244,10 +239,10 @@ int pipe_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int
     c->p_count = 0;
     c->inv_rows_valid = 0;
     c->perm_forward_valid = false;
-    if (!c->stream2) SC_HIP(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-    if (!c->pg.stream_px) SC_HIP(hipStreamCreateWithFlags(&c->pg.stream_px, hipStreamNonBlocking));
-    if (!c->stream3) SC_HIP(hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
-    if (!c->stream4) SC_HIP(hipStreamCreateWithFlags(&c->stream4, hipStreamNonBlocking));
+    // (the pipeline's streams first, the preparation streams behind them: the order the runtime has always seen them in)
+    for (int r : {SR_CHAIN, SR_EXPAND, SR_SWAP_A, SR_SWAP_B}) SC_TRY(c->streams.ensure(r));
+    // first block-parallel job of the context only.  May replace the streams: they are taken from the table below here
+    if (permgen_is_block_parallel(c, n)) SC_TRY(permgen_place_streams(c, SR_CHAIN));
     // allocations first (hipMalloc synchronises the device), then the streams run freely
     if (table >= 1) SC_TRY(c->inv.ensure(sizeof(int32_t) * (size_t)(c->p_stride * n_perm + 32), &c->mem));
     // chunk schedule: a short first chunk so that the consumer starts early, PERM_CHUNK each in the middle, a short

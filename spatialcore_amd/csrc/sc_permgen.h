@@ -368,13 +368,19 @@ struct PermPipe {
 };
 #define SC_PERMGEN_RETRY 1000  // internal: the block-parallel scan failed its verification, rerun sequentially
 bool permgen_is_block_parallel(const sc_ctx *c, int64_t n);  // (sc_permgen_phi.hip) which scan form a job of length n takes
+// Once per context (again after sc_ctx_set_permgen_mode), before the first block-parallel job and before the job takes
+// any stream from the table: choose the placement of the context's streams -- plain, priority-spread or neither, ended
+// by a probe -- and with it the scan form.  May destroy and re-create every stream of the context (all idle: it waits
+// for the device first), so no stream handle taken before the call may be used after it.  chain_role: where this job's
+// chain will run (SR_CHAIN in a pipeline, SR_SCORE for a short job on the context stream).
+int permgen_place_streams(sc_ctx *c, int chain_role);
 // units_ahead: launch units the block-parallel scan's preparation runs ahead of its chain (clamped to [1, PHI_AHEAD_MAX])
 int permgen_begin(sc_ctx *c, const uint64_t *state6, int64_t n, int64_t n_perm, int units_ahead, PermJob *job, hipStream_t s);
 int permgen_scan_chunk(sc_ctx *c, PermJob *job, int64_t p1, hipStream_t s, hipStream_t post, hipEvent_t done);
 int permgen_swap_chunk(sc_ctx *c, PermJob *job, int64_t p0, int64_t p1, hipStream_t s, bool inverse, int pw_req);
 bool permgen_can_swap_inverse(int64_t n);
 int permgen_finish(sc_ctx *c, PermJob *job, uint64_t *state6);
-// ---- the block-parallel form's share of a job (sc_permgen_phi.hip); phi_begin: the form (probing the streams), buffers, hand-over words
+// ---- the block-parallel form's share of a job (sc_permgen_phi.hip); phi_begin: the form (placed and probed by the caller), buffers, hand-over words
 int phi_begin(sc_ctx *c, PermJob *job, int units_ahead, uint64_t n_blocks, hipStream_t s);
 // the *blocks granted to permutations [0, p1): prepared on the preparation streams (*fill_streams: those the verification waits for)
 // and chained by ONE launch on s; then, on sp, the verification of the chunk

@@ -306,6 +306,7 @@ static int perm_generate_once(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_
         return rc;
     }
     PermJob job;
+    if (permgen_is_block_parallel(c, n)) SC_TRY(permgen_place_streams(c, SR_SCORE));   // (first such job of the context only)
     SC_TRY(permgen_begin(c, state6, n, n_perm, 1, &job, c->stream));
     for (int64_t p0 = 0; p0 < n_perm; p0 += PERM_CHUNK) {
         const int64_t p1 = p0 + PERM_CHUNK < n_perm ? p0 + PERM_CHUNK : n_perm;

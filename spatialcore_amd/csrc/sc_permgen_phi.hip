@@ -822,17 +822,33 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_block_exact(const uint32_t *__
     if (tau == 0 && (failed || r.end || S + total_cnt != sblk[b + 1])) atomicOr(st + 2, 4ull);
 }
 
+// k_probe_wait's question for ALL streams of a context at once (the priority-spread placement, permgen_probe_all_roles): one
+// such kernel per stream adds 1 to a counter and waits until all `want` have arrived.  Streams that share a queue never
+// meet: the kernel in front gives up after the same 20 ms and says so.
+// (Kept BEHIND the generator's kernels.  Defined beside k_probe_wait it moved k_chain in the code object, and the chain
+// -- one workgroup, bound by instruction latency -- took 2.3 ms longer per bench step: DESIGN.md 4.3.)
+__global__ void k_probe_meet(uint32_t *count, uint32_t want, uint32_t *timed_out)
+{
+    if (threadIdx.x != 0) return;
+    __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    const long long t0 = wall_clock64();
+    while (__hip_atomic_load(count, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < want) {
+        if (wall_clock64() - t0 > 2000000ll) { atomicOr(timed_out, 1u); return; }   // 20 ms
+        __builtin_amdgcn_s_sleep(8);
+    }
+}
+
 // ---- host: the stream probe, and the block-parallel form's share of a job (called by sc_permgen.hip) ----
 bool permgen_is_block_parallel(const sc_ctx *c, int64_t n) { return c->pg.mode != 1 && !c->pg.streams_serial && n >= PHI_MIN_N; }
 
-static int permgen_probe_streams(sc_ctx *c, hipStream_t chain_stream)
+// The probe of the plain placement: the chain's stream and the four preparation streams, in five rounds (k_probe_wait).
+static int permgen_probe_generator(sc_ctx *c, int chain_role, bool *concurrent)
 {
-    if (c->pg.probed) return SC_OK;
-    c->pg.probed = true;
     std::vector<hipStream_t> ss;
-    ss.push_back(chain_stream);
-    for (hipStream_t sp : c->pg.stream_pg)
-        if (sp && sp != chain_stream) ss.push_back(sp);
+    SC_TRY(c->streams.ensure(chain_role));
+    SC_TRY(c->pg.ensure(true));
+    ss.push_back(c->streams.s[chain_role]);
+    for (int q = 0; q < 4; ++q) ss.push_back(c->stream_pg[q]);
     SC_TRY(c->perm_flag.ensure(sizeof(unsigned long long), &c->mem));
     uint32_t *words = c->perm_flag.as<uint32_t>();
     SC_HIP(hipDeviceSynchronize());
@@ -849,9 +865,72 @@ static int permgen_probe_streams(sc_ctx *c, hipStream_t chain_stream)
     }
     uint32_t host[2] = {0, 0};
     SC_HIP(hipMemcpy(host, words, sizeof(host), hipMemcpyDeviceToHost));
-    if (host[1]) {
+    *concurrent = host[1] == 0;
+    return SC_OK;
+}
+
+// The probe of the priority-spread placement, which fills its queue pools exactly: one foreign stream on a level (a host
+// application's, a collective library's, a second context's) makes two of ours share a queue, whichever they are.  So
+// every role's stream is created and all of them meet in one round (k_probe_meet).
+static int permgen_probe_all_roles(sc_ctx *c, bool *concurrent)
+{
+    for (int r = 0; r < SR_COUNT; ++r) SC_TRY(c->streams.ensure(r));
+    SC_TRY(c->pg.ensure(true));
+    SC_TRY(c->perm_flag.ensure(sizeof(unsigned long long), &c->mem));
+    uint32_t *words = c->perm_flag.as<uint32_t>();
+    SC_HIP(hipDeviceSynchronize());
+    SC_HIP(hipMemset(words, 0, 2 * sizeof(uint32_t)));
+    for (hipStream_t sp : c->streams.s) hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, sp, words, 0u, 0u);   // (warm-up, as above)
+    SC_TRY(c->streams.sync((1u << SR_COUNT) - 1u));
+    for (hipStream_t sp : c->streams.s) hipLaunchKernelGGL(k_probe_meet, dim3(1), dim3(64), 0, sp, words, (uint32_t)SR_COUNT, words + 1);
+    SC_TRY(c->streams.sync((1u << SR_COUNT) - 1u));
+    uint32_t host[2] = {0, 0};
+    SC_HIP(hipMemcpy(host, words, sizeof(host), hipMemcpyDeviceToHost));
+    *concurrent = host[1] == 0 && host[0] == (uint32_t)SR_COUNT;
+    return SC_OK;
+}
+
+// The placement ladder.  Step 1: the environment's GPU_MAX_HW_QUEUES holds every role -- plain streams, probed.  Step 2:
+// it does not, or the plain probe failed (a runtime that initialised before the library could ask: the environment
+// shows 24, the runtime never saw it) -- the priority-spread placement, if its groups fit the limit, probed over all
+// roles.  Step 3: neither -- plain streams and the sequential scan, with the note.
+int permgen_place_streams(sc_ctx *c, int chain_role)
+{
+    if (c->pg.probed) return SC_OK;
+    c->pg.probed = true;
+    c->pg.placement_note.clear();
+    const char *q = getenv("GPU_MAX_HW_QUEUES");
+    const int limit = q && atoi(q) > 0 ? atoi(q) : 4;   // (unset: the runtime's default)
+    int least = 0, greatest = 0;
+    SC_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    const bool three_levels = greatest < 0 && least > 0;
+    SC_HIP(hipDeviceSynchronize());   // (the streams may be replaced below: all idle from here)
+    int level[SR_COUNT] = {};
+    bool concurrent = false, plain_failed = false;
+    for (int step = 1; step <= 2 && !concurrent; ++step) {
+        const int place = sc_place_streams(limit, plain_failed, SC_ROLE_GROUP, SR_COUNT, SC_GROUP_LEVEL, SG_COUNT, level);
+        if (place == SC_PLACE_NONE || (place == SC_PLACE_SPREAD && !three_levels)) break;
+        SC_TRY(c->streams.replace(place, level));
+        if (place == SC_PLACE_PLAIN) {
+            SC_TRY(permgen_probe_generator(c, chain_role, &concurrent));
+            plain_failed = !concurrent;
+        } else {
+            SC_TRY(permgen_probe_all_roles(c, &concurrent));
+            if (concurrent) {
+                char buf[120];
+                snprintf(buf, sizeof(buf), "streams spread over three priority levels (GPU_MAX_HW_QUEUES=%s)", q ? q : "unset");
+                c->pg.placement_note = buf;
+            }
+            break;
+        }
+    }
+    if (concurrent) return SC_OK;
+    // step 3.  Neither placement tried (fewer queues per level than the largest group needs): the plain probe decides, as
+    // it always did -- a runtime that runs the streams concurrently all the same keeps the block-parallel form
+    SC_TRY(c->streams.replace(SC_PLACE_PLAIN, level));
+    if (!plain_failed) SC_TRY(permgen_probe_generator(c, chain_role, &concurrent));
+    if (!concurrent) {
         c->pg.streams_serial = true;
-        const char *q = getenv("GPU_MAX_HW_QUEUES");
         char buf[320];
         snprintf(buf, sizeof(buf), "the HIP streams of this process do not run concurrently (GPU_MAX_HW_QUEUES=%s; the library "
                  "asks for 24 when it is loaded BEFORE the HIP runtime initialises, or a profiler serialises kernels): the "
@@ -868,9 +947,8 @@ extern "C" int sc_ctx_probe_streams(sc_ctx *c, int *concurrent, int *hw_queues_r
 {
     SC_REQUIRE(c && concurrent, SC_ERR_INVALID, "sc_ctx_probe_streams: null pointer");
     SC_HIP(hipSetDevice(c->device));
-    if (!c->stream2) SC_HIP(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-    SC_TRY(c->pg.ensure(true));
-    SC_TRY(permgen_probe_streams(c, c->stream2));
+    SC_REQUIRE(c->pg.probed || !c->pipe, SC_ERR_STATE, "sc_ctx_probe_streams: a job begun by sc_moran_seeded_begin is in flight");
+    SC_TRY(permgen_place_streams(c, SR_CHAIN));
     *concurrent = c->pg.streams_serial ? 0 : 1;
     if (hw_queues_requested) {
         const char *q = getenv("GPU_MAX_HW_QUEUES");
@@ -886,8 +964,11 @@ extern "C" int sc_ctx_permgen_form(sc_ctx *c, int64_t n, const char **form)
     if (n < PHI_MIN_N) c->pg.form = "sequential (permutations shorter than 131072: every block holds a band change)";
     else if (c->pg.mode == 1) c->pg.form = "sequential (sc_ctx_set_permgen_mode 1)";
     else if (c->pg.streams_serial) c->pg.form = "sequential: " + c->pg.note;
-    else if (!c->pg.note.empty()) c->pg.form = "block-parallel; " + c->pg.note;
-    else c->pg.form = "block-parallel";
+    else {
+        c->pg.form = "block-parallel";
+        for (const std::string *s : {&c->pg.placement_note, &c->pg.note})
+            if (!s->empty()) c->pg.form += "; " + *s;
+    }
     *form = c->pg.form.c_str();
     return SC_OK;
 }
@@ -896,11 +977,9 @@ int phi_begin(sc_ctx *c, PermJob *job, int units_ahead, uint64_t n_blocks, hipSt
 {
     job->phi = permgen_is_block_parallel(c, job->n);   // (a job starts from a fresh PermJob: no unit, no gate yet)
     job->units_ahead = units_ahead >= 1 && units_ahead <= PHI_AHEAD_MAX ? units_ahead : 1;
+    // (the caller took `s` from the table after permgen_place_streams, which may replace every stream)
+    SC_REQUIRE(!job->phi || c->pg.probed, SC_ERR_STATE, "permutation generator: block-parallel job on streams that were never placed");
     SC_TRY(c->pg.ensure(job->phi));
-    if (job->phi && !c->pg.probed) {   // first block-parallel job of this context: can its streams overlap at all?
-        SC_TRY(permgen_probe_streams(c, s));
-        job->phi = permgen_is_block_parallel(c, job->n);
-    }
     if (job->phi) {
         SC_TRY(c->pg.desc.ensure(sizeof(PhiDesc) * (size_t)PHI_RING, &c->mem));
         SC_TRY(c->pg.tbits.ensure(sizeof(unsigned long long) * (size_t)PHI_RING * 2 * PHI_WORDS, &c->mem));
@@ -942,7 +1021,7 @@ int phi_chain_chunk(sc_ctx *c, PermJob *job, int64_t p1, hipStream_t s, uint64_t
         const uint64_t b0 = job->B_done;
         const uint64_t b1 = b0 + PHI_UNIT < B_end ? b0 + PHI_UNIT : B_end;
         const int64_t u = job->unit_no;
-        hipStream_t sp = c->pg.stream_pg[(size_t)(u % PHI_STREAMS)];
+        hipStream_t sp = c->stream_pg[(size_t)(u % PHI_STREAMS)];
         // The guess of unit u uses the exact state at the start of unit u - ahead, which the chain leaves when it
         // completes unit u - ahead - 1; that unit also is the last reader of the ring slots unit u overwrites.
         const int64_t dep = u - job->units_ahead - 1;
@@ -980,7 +1059,7 @@ int phi_chain_chunk(sc_ctx *c, PermJob *job, int64_t p1, hipStream_t s, uint64_t
     SC_HIP(hipGetLastError());
     // the verification / expansion of this chunk reads the entry states k_seg_fill leaves on the preparation streams
     for (unsigned q = 0; q < PHI_STREAMS; ++q)
-        if (*fill_streams & (1u << q)) SC_HIP(hipEventRecord(c->pg.ev[q], c->pg.stream_pg[q]));
+        if (*fill_streams & (1u << q)) SC_HIP(hipEventRecord(c->pg.ev[q], c->stream_pg[q]));
     *blocks = B_end > g0 ? B_end - g0 : 1;
     return SC_OK;
 }

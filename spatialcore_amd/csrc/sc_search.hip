@@ -318,7 +318,7 @@ extern "C" int sc_knn_fetch(sc_ctx *c, int32_t *idx_out, double *rdist_out)
     // the side stream of the graph moments serves as the copy stream (a stream more per context would be a hardware queue
     // more: a process whose streams outnumber GPU_MAX_HW_QUEUES has them share queues, which the generator must avoid)
     sc_graph_moments_drain(c);
-    if (!c->stream_m) SC_HIP(hipStreamCreateWithFlags(&c->stream_m, hipStreamNonBlocking));
+    SC_TRY(c->streams.ensure(SR_MOMENTS));
     const size_t nk = (size_t)c->knn_n * (size_t)c->knn_k;
     SC_HIP(hipStreamWaitEvent(c->stream_m, c->knn_done, 0));
     if (idx_out) SC_HIP(hipMemcpyAsync(idx_out, c->knn_idx.p, sizeof(int32_t) * nk, hipMemcpyDeviceToHost, c->stream_m));
