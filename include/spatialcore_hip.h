@@ -67,7 +67,13 @@ extern "C" {
 #define SC_K_DIFF_GRAPH 27 /* sc_diffmap_graph*: scales, union (sort), kernel weights, normalisation, components */
 #define SC_K_DIFF_SPMV 28  /* sc_lanczos_run: the sparse matrix-vector products */
 #define SC_K_DIFF_ORTH 29  /* ... the two Gram-Schmidt passes, the norm and the scaling of every step */
-#define SC_K_COUNT_ 30
+#define SC_K_ANNOT_SETUP 30   /* sc_annot_*: normalisation, scaler statistics, the D values, the column-sorted copy */
+#define SC_K_ANNOT_ROWS 31    /* ... the row pass as a training forward pass (scores or direction product) */
+#define SC_K_ANNOT_GRAD 32    /* ... residuals, their cell-chunk sums, the column-chunk gradient pass and its finish */
+#define SC_K_ANNOT_LINE 33    /* ... one evaluation of the line search's derivatives */
+#define SC_K_ANNOT_PREDICT 34 /* sc_annot_predict / sc_annot_transform: the row pass with the fused per-cell epilogue */
+#define SC_K_ANNOT_STEP 35    /* sc_annot_train_step: the score update S <- S + alpha Dir */
+#define SC_K_COUNT_ 36
 
 typedef struct sc_ctx sc_ctx;
 
@@ -735,6 +741,49 @@ int sc_lanczos_run(sc_ctx *ctx, int32_t steps, double *alpha_out, double *beta_o
 int sc_lanczos_ritz(sc_ctx *ctx, const double *S, int64_t m, int32_t c, const double *lambda, double *vecs_out,
                     double *resid_out);
 int sc_lanczos_end(sc_ctx *ctx);
+
+/* ---- N14 (extension): CellTypist-style annotation -- spatialcore_amd.annotation ----------------------
+ * The model is a StandardScaler, a clip at 10 and one-vs-rest L2 logistic regression.  X is a CANONICAL CSR as for
+ * sc_nmf_fit (values SC_F32 or SC_F64, finite, >= 0) over the genes in use.  mode 0: counts, normalised on the device to
+ * log1p(x / rowsum * 1e4), the row sum over the stored entries in index order; mode 1: log1p values, taken as they are;
+ * mode 2: log1p values of a larger gene set: expm1, then as mode 0.  Stored zeros are legal; a row whose stored values are
+ * all 0 (row sum 0 in modes 0 and 2) is an empty row.  All arithmetic is fp64, every product and sum
+ * rounded separately, no floating-point atomics: every result is a function of the arguments alone, bit for bit.
+ * z_ig = min((x_ig - mean_g) / scale_g, 10); a zero entry gives z0_g = -mean_g / scale_g; d_ig = z_ig - z0_g at the stored
+ * entries.  A product with a table: row_it = (bias_t + sum_g z0_g w_tg, genes in index order from 0, formed on the host)
+ * + d_ig w_tg over the row's stored entries in index order.
+ * sc_annot_predict: scores = the product with coef[T][n_genes] and intercept[T].  labels_out[i] = first argmax of the fp64
+ *   scores; conf_out[5][n] = expit(max score), then the four transforms below of the row rounded to float32;
+ *   scores_out[n][T] (may be NULL) = the float32 scores.
+ * sc_annot_transform: the reference's transform_confidence of any n x T matrix (SC_F32 is widened), conf_out[4][n] = raw
+ *   (the maximum m), zscore = expit((m - mean) / sd) with the population sd (sd < 1e-10 -> 1), softmax = 1 / sum_t
+ *   exp(x_t - m), minmax = (m - min) / (m - min) with a range < 1e-10 -> 1.  Sums over the classes: class t = 64 b + l in
+ *   lane l, every lane adds its values for b ascending from 0, the lane sums (0 for a lane without a class) meet in the
+ *   adjacent-pair tree over T rounded up to a power of two (64 for T > 64) lanes.
+ * Training keeps one problem on the device: sc_annot_train_begin -> (_forward, _grad, _line, _step) ... -> _end.
+ *   _begin: normalisation, mean_out[g] = column sum / n, the population variance with the zeros counted, scale_out[g] =
+ *     its square root (1 where sklearn's StandardScaler calls the feature constant), the D values in row order and in a
+ *     column-sorted copy.  Column sums: chunks of 512 stored entries (rows ascending), chunk sums in chunk order.
+ *     labels[n] in [0, T), weights[n] finite and > 0 (the s_i of the objective).
+ *   _forward: which = 0: S = the product with (coef, bias); which = 1: Dir = the same for a direction.
+ *   _grad: with R_it = s_i (expit(S_it) - [labels_i = t]): grad_out[t][g] = sum_i d_ig R_it (the column's chunks) + z0_g
+ *     sum_i R_it, grad_out[t][n_genes] = sum_i R_it, loss_out[t] = sum_i s_i (softplus(S_it) - y_it S_it); sums over cells in
+ *     chunks of 1024 cells, chunk sums in chunk order.  The penalty's terms are the caller's.
+ *   _line: at u = S + alpha_t Dir: d1_out[t] = sum_i s_i (expit(u) - y) Dir_it, d2_out[t] = sum_i s_i expit(u) (1 - expit(u))
+ *     Dir_it^2.   _step: S <- S + alpha_t Dir.
+ * 2 <= T <= 256, 1 <= n <= 2^31 - 1, 1 <= n_genes <= 32768, 1 <= stored entries <= 2^32 - 1. */
+int sc_annot_predict(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
+                     int32_t n_genes, int32_t mode, int32_t T, const double *coef, const double *intercept, const double *mean,
+                     const double *scale, float *scores_out, int32_t *labels_out, double *conf_out);
+int sc_annot_transform(sc_ctx *ctx, const void *scores, int dtype, int64_t n, int32_t T, double *conf_out);
+int sc_annot_train_begin(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
+                         int32_t n_genes, int32_t mode, int32_t T, const int32_t *labels, const double *weights,
+                         double *mean_out, double *scale_out);
+int sc_annot_train_forward(sc_ctx *ctx, const double *coef, const double *bias, int32_t which);
+int sc_annot_train_grad(sc_ctx *ctx, double *grad_out, double *loss_out);
+int sc_annot_train_line(sc_ctx *ctx, const double *alpha, double *d1_out, double *d2_out);
+int sc_annot_train_step(sc_ctx *ctx, const double *alpha);
+int sc_annot_train_end(sc_ctx *ctx);
 
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across

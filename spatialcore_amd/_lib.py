@@ -29,6 +29,8 @@ K_LIGREC = 18
 K_RIPLEY_G_LIST, K_RIPLEY_G_RELABEL, K_RIPLEY_G_COUNT = 19, 20, 21
 K_NMF_SETUP, K_NMF_W, K_NMF_H, K_NMF_ERR = 22, 23, 24, 25
 K_DIFF_KNN, K_DIFF_GRAPH, K_DIFF_SPMV, K_DIFF_ORTH = 26, 27, 28, 29
+K_ANNOT_SETUP, K_ANNOT_ROWS, K_ANNOT_GRAD, K_ANNOT_LINE, K_ANNOT_PREDICT, K_ANNOT_STEP = 30, 31, 32, 33, 34, 35
+ANNOT_MODES = {"counts": 0, "log1p": 1, "log1p_renorm": 2}   # sc_annot_*'s input states
 NMF_LOSSES = {"frobenius": 2, "kullback-leibler": 1}   # sc_nmf_fit's codes (sklearn's beta)
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
 
@@ -129,6 +131,14 @@ SYMBOLS = {
     "sc_lanczos_run": [_P, c_int32, _P, _P, POINTER(c_int64)],
     "sc_lanczos_ritz": [_P, _P, c_int64, c_int32, _P, _P, _P],
     "sc_lanczos_end": [_P],
+    "sc_annot_predict": [_P, _P, _P, _P, c_int, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, _P, _P],
+    "sc_annot_transform": [_P, _P, c_int, c_int64, c_int32, _P],
+    "sc_annot_train_begin": [_P, _P, _P, _P, c_int, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, _P],
+    "sc_annot_train_forward": [_P, _P, _P, c_int32],
+    "sc_annot_train_grad": [_P, _P, _P],
+    "sc_annot_train_line": [_P, _P, _P, _P],
+    "sc_annot_train_step": [_P, _P],
+    "sc_annot_train_end": [_P],
     "sc_comm_unique_id": [_P],
     "sc_comm_create": [_P, _P, c_int, c_int, POINTER(c_void_p)],
     "sc_comm_destroy": [_P],
@@ -248,6 +258,7 @@ class Context:
         self.device = int(device)
         self._ripley_radii = 0   # radii of the resident Ripley pair list (shape of ripley_counts / ripley_counter results)
         self._ripley_g_radii = 0   # ... and of the resident Ripley's G neighbour lists
+        self._annot_shape = None   # (classes, genes) of the resident training problem (annot_train_begin .. annot_train_end)
         self._diff_n = self._diff_nnz = self._lanczos_cap = 0   # cells / stored entries of the resident diffusion graph, Lanczos basis cap
 
     def close(self) -> None:
@@ -894,6 +905,104 @@ class Context:
                                     byref(checks), byref(n_iter), byref(err)))
         return {"W": W, "H": H, "n_iter": n_iter.value, "reconstruction_err": err.value,
                 "error_trace": trace[:checks.value].copy()}
+
+    # ---- N14 (extension): annotation ----------------------------------------------------------
+    @staticmethod
+    def _annot_csr(indptr, indices, data, who: str):
+        data = np.ascontiguousarray(data)
+        if data.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{who}: values must be float32 or float64, got {data.dtype}")
+        indptr, indices = _c(indptr, np.int64), _c(indices, np.int32)
+        n = indptr.size - 1
+        if indices.size != data.size or n < 1 or indptr[-1] != data.size:
+            raise ValueError(f"{who}: indptr, indices and values do not describe one CSR matrix")
+        return indptr, indices, data, n
+
+    def annot_predict(self, indptr, indices, data, mode: str, coef, intercept, mean, scale, scores: bool = True) -> dict:
+        """sc_annot_predict on a canonical CSR over the model's genes: ``labels`` (int32, first argmax of the fp64
+        scores), ``confidence_raw`` = expit(max score), ``raw`` / ``zscore`` / ``softmax`` / ``minmax`` (the reference's
+        transforms of the float32-rounded row) and, with ``scores``, the float32 ``scores`` (n, T)."""
+        indptr, indices, data, n = self._annot_csr(indptr, indices, data, "annot_predict")
+        coef, b = _c(coef, np.float64), _c(intercept, np.float64)
+        mean, scale = _c(mean, np.float64), _c(scale, np.float64)
+        if coef.ndim != 2 or b.shape != (coef.shape[0],) or mean.shape != (coef.shape[1],) or scale.shape != mean.shape:
+            raise ValueError("annot_predict: coef must be (T, G), intercept (T,), mean and scale (G,)")
+        T, G = coef.shape
+        out = np.empty((n, T), dtype=np.float32) if scores else None
+        lab = np.empty(n, dtype=np.int32)
+        conf = np.empty((5, n), dtype=np.float64)
+        _check(self._lib.sc_annot_predict(self._h, _ptr(indptr), _ptr(indices), _ptr(data),
+                                          SC_F32 if data.dtype == np.float32 else SC_F64, n, G, ANNOT_MODES[mode], T, _ptr(coef),
+                                          _ptr(b), _ptr(mean), _ptr(scale), _ptr(out), _ptr(lab), _ptr(conf)))
+        return {"labels": lab, "confidence_raw": conf[0], "raw": conf[1], "zscore": conf[2], "softmax": conf[3],
+                "minmax": conf[4], "scores": out}
+
+    def annot_transform(self, scores) -> dict:
+        """sc_annot_transform: the four confidence transforms of an (n, T) float32 or float64 matrix."""
+        S = np.ascontiguousarray(scores)
+        if S.dtype not in (np.float32, np.float64) or S.ndim != 2:
+            raise ValueError("annot_transform: scores must be a 2-D float32 or float64 matrix")
+        n, T = S.shape
+        conf = np.empty((4, n), dtype=np.float64)
+        _check(self._lib.sc_annot_transform(self._h, _ptr(S), SC_F32 if S.dtype == np.float32 else SC_F64, n, T, _ptr(conf)))
+        return {"raw": conf[0], "zscore": conf[1], "softmax": conf[2], "minmax": conf[3]}
+
+    def annot_train_begin(self, indptr, indices, data, n_genes: int, mode: str, n_classes: int, labels, weights):
+        """sc_annot_train_begin: leaves the training problem on the device; returns the scaler's (mean, scale)."""
+        indptr, indices, data, n = self._annot_csr(indptr, indices, data, "annot_train_begin")
+        labels, weights = _c(labels, np.int32), _c(weights, np.float64)
+        if labels.shape != (n,) or weights.shape != (n,):
+            raise ValueError("annot_train_begin: labels and weights must have one entry per cell")
+        G, T = int(n_genes), int(n_classes)
+        self._annot_shape = None   # until the call succeeds this object vouches for no resident problem
+        mean, scale = np.empty(max(G, 1), dtype=np.float64), np.empty(max(G, 1), dtype=np.float64)
+        _check(self._lib.sc_annot_train_begin(self._h, _ptr(indptr), _ptr(indices), _ptr(data),
+                                              SC_F32 if data.dtype == np.float32 else SC_F64, n, G, ANNOT_MODES[mode], T,
+                                              _ptr(labels), _ptr(weights), _ptr(mean), _ptr(scale)))
+        self._annot_shape = (T, G)
+        return mean[:G], scale[:G]
+
+    def annot_train_forward(self, coef, bias, direction: bool = False) -> None:
+        """The resident scores (or, with ``direction``, the direction's product) <- Z coef^T + bias."""
+        T, G = self._annot_dims("annot_train_forward")
+        coef, bias = _c(coef, np.float64), _c(bias, np.float64)
+        if coef.shape != (T, G) or bias.shape != (T,):
+            raise ValueError(f"annot_train_forward: coef must be ({T}, {G}) and bias ({T},)")
+        _check(self._lib.sc_annot_train_forward(self._h, _ptr(coef), _ptr(bias), int(bool(direction))))
+
+    def annot_train_grad(self):
+        """(gradient of the data term at the resident scores, (T, G + 1) with the intercept last; data loss per class)."""
+        T, G = self._annot_dims("annot_train_grad")
+        grad, loss = np.empty((T, G + 1), dtype=np.float64), np.empty(T, dtype=np.float64)
+        _check(self._lib.sc_annot_train_grad(self._h, _ptr(grad), _ptr(loss)))
+        return grad, loss
+
+    def annot_train_line(self, alpha):
+        """First and second derivative of the data term along the resident direction at the step lengths ``alpha``."""
+        T, _ = self._annot_dims("annot_train_line")
+        alpha = _c(alpha, np.float64)
+        if alpha.shape != (T,):
+            raise ValueError(f"annot_train_line: alpha must be ({T},)")
+        d1, d2 = np.empty(T, dtype=np.float64), np.empty(T, dtype=np.float64)
+        _check(self._lib.sc_annot_train_line(self._h, _ptr(alpha), _ptr(d1), _ptr(d2)))
+        return d1, d2
+
+    def annot_train_step(self, alpha) -> None:
+        T, _ = self._annot_dims("annot_train_step")
+        alpha = _c(alpha, np.float64)
+        if alpha.shape != (T,):
+            raise ValueError(f"annot_train_step: alpha must be ({T},)")
+        _check(self._lib.sc_annot_train_step(self._h, _ptr(alpha)))
+
+    def annot_train_end(self) -> None:
+        self._annot_shape = None
+        _check(self._lib.sc_annot_train_end(self._h))
+
+    def _annot_dims(self, who: str):
+        """(classes, genes) of the resident training problem; without one, the library's own state error."""
+        if self._annot_shape is None:
+            raise SpatialCoreHipError(f"{who}: no training problem is resident (annot_train_begin)")
+        return self._annot_shape
 
     # ---- N13 (extension): diffusion maps ------------------------------------------------------
     def knn_dense(self, X, k: int, fetch: bool = True, splits: int = 0):

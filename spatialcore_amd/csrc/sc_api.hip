@@ -238,6 +238,7 @@ int sc_ctx_destroy(sc_ctx *c)
                     &c->rs_idx, &c->rs_idx2, &c->rs_tmp, &c->rs_rank2, &c->rs_tie, &c->rs_nnz, &c->rs_sum, &c->th_sorted};
     for (DBuf *b : bufs) b->release(&c->mem);
     for (DBuf *b : c->df.bufs()) b->release(&c->mem);
+    sc_annot_release(c);
     c->pg.release(&c->mem);
     for (int k = 0; k < SC_K_COUNT_; ++k) {
         for (auto &ev : c->timers[k].pending) {

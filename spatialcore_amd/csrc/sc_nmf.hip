@@ -21,15 +21,14 @@
 #include <cmath>
 #include <vector>
 
+#include "sc_colsort.h"
 #include "sc_ctx.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
 constexpr int NMF_TPB = 256;
 constexpr int NMF_KMAX = 64;
-constexpr int NMF_COL_CHUNK = 512;     // stored entries of a gene column per work item of the H pass
+constexpr int NMF_COL_CHUNK = COL_CHUNK; // stored entries of a gene column per work item of the H pass (512)
 constexpr int NMF_CELL_CHUNK = 1024;   // cells per partial of the sums over cells
 constexpr int NMF_TILE = 64;           // cells of W staged in LDS at a time by k_nmf_cellsums
 constexpr double NMF_EPS = 1.1920928955078125e-07;   // 2^-23: sklearn's EPSILON (float32 eps)
@@ -44,62 +43,14 @@ __device__ __forceinline__ double nmf_group_sum(double v, int kp)
 }
 
 // ---- set-up ------------------------------------------------------------------------------------------------------
-// per stored entry: fp64 value, sort key = its column, payload = its position; per row (one thread): the row id of its entries
+// (the column-sorted copy and its chunk table: sc_colsort.h)
+// per stored entry: its fp64 value
 template <class T>
-__global__ __launch_bounds__(256) void k_nmf_entries(const T *__restrict__ data, const int32_t *__restrict__ indices, int64_t nnz,
-                                                     double *__restrict__ val, u64 *__restrict__ keys, uint32_t *__restrict__ pos)
+__global__ __launch_bounds__(256) void k_nmf_values(const T *__restrict__ data, int64_t nnz, double *__restrict__ val)
 {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= nnz) return;
     val[p] = (double)data[p];
-    keys[p] = (u64)indices[p];
-    pos[p] = (uint32_t)p;
-}
-__global__ __launch_bounds__(256) void k_nmf_rowids(const int64_t *__restrict__ indptr, int64_t n, int32_t *__restrict__ rowid)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (int64_t p = indptr[i]; p < indptr[i + 1]; ++p) rowid[p] = (int32_t)i;
-}
-// the column-sorted copy (the sort is stable, so rows ascend inside a column)
-__global__ __launch_bounds__(256) void k_nmf_csc_fill(const uint32_t *__restrict__ pos, const int32_t *__restrict__ rowid,
-                                                      const double *__restrict__ val, int64_t nnz, int32_t *__restrict__ crow,
-                                                      double *__restrict__ cval)
-{
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= nnz) return;
-    const uint32_t q = pos[p];
-    crow[p] = rowid[q];
-    cval[p] = val[q];
-}
-// colptr[g] = first sorted position whose column is >= g, g = 0 .. G
-__global__ __launch_bounds__(256) void k_nmf_colptr(const u64 *__restrict__ keys, int64_t nnz, int G, int64_t *__restrict__ colptr)
-{
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g > G) return;
-    int64_t lo = 0, hi = nnz;
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (keys[mid] < (u64)g) lo = mid + 1; else hi = mid;
-    }
-    colptr[g] = lo;
-}
-// cptr[g] = first chunk of gene g (cptr[G] = number of chunks): one thread, G <= 32768
-__global__ void k_nmf_chunk_scan(const int64_t *__restrict__ colptr, int G, int64_t *__restrict__ cptr)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int64_t c = 0;
-    for (int g = 0; g < G; ++g) {
-        cptr[g] = c;
-        c += (colptr[g + 1] - colptr[g] + NMF_COL_CHUNK - 1) / NMF_COL_CHUNK;
-    }
-    cptr[G] = c;
-}
-__global__ __launch_bounds__(256) void k_nmf_chunk_fill(const int64_t *__restrict__ cptr, int G, int32_t *__restrict__ cgene)
-{
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= G) return;
-    for (int64_t c = cptr[g]; c < cptr[g + 1]; ++c) cgene[c] = g;
 }
 __global__ __launch_bounds__(256) void k_nmf_transpose(const double *__restrict__ H, int K, int G, double *__restrict__ Ht)
 {
@@ -376,13 +327,14 @@ __global__ void k_nmf_err_final(const double *__restrict__ part, int64_t chunks,
 
 struct NmfBufs {
     sc_ctx *c;
-    enum { INDPTR, INDICES, RAW, VAL, KEYS, KEYS2, POS, POS2, ROWID, CROW, CVAL, COLPTR, CPTR, CGENE, W, H0, H1, HT0, HT1, HHT,
-           HSUM, CELLPART, CELLSUM, HPART, ROWERR, ERRPART, ERR, COUNT };
+    enum { INDPTR, INDICES, RAW, VAL, W, H0, H1, HT0, HT1, HHT, HSUM, CELLPART, CELLSUM, HPART, ROWERR, ERRPART, ERR, COUNT };
     DBuf b[COUNT];
+    ColSort cs;   // the column-sorted copy and its chunk table
     explicit NmfBufs(sc_ctx *ctx) : c(ctx) {}
     ~NmfBufs()
     {
         for (DBuf &d : b) d.release(&c->mem);
+        cs.release(&c->mem);
     }
     int get(int which, size_t bytes) { return b[which].ensure(bytes ? bytes : 8, &c->mem); }
     template <class T> T *as(int which) const { return b[which].as<T>(); }
@@ -431,9 +383,9 @@ struct NmfState {
     void h_pass()   // needs cellsums() of the updated W; flips the current H
     {
         const dim3 block(NMF_TPB);
-        const int64_t *colptr = m->as<int64_t>(NmfBufs::COLPTR), *cptr = m->as<int64_t>(NmfBufs::CPTR);
-        const int32_t *crow = m->as<int32_t>(NmfBufs::CROW), *cgene = m->as<int32_t>(NmfBufs::CGENE);
-        const double *cval = m->as<double>(NmfBufs::CVAL), *W = m->as<double>(NmfBufs::W), *cs = m->as<double>(NmfBufs::CELLSUM);
+        const int64_t *colptr = m->cs.colptr.as<int64_t>(), *cptr = m->cs.cptr.as<int64_t>();
+        const int32_t *crow = m->cs.crow.as<int32_t>(), *cgene = m->cs.cgene.as<int32_t>();
+        const double *cval = m->cs.cval.as<double>(), *W = m->as<double>(NmfBufs::W), *cs = m->as<double>(NmfBufs::CELLSUM);
         double *part = m->as<double>(NmfBufs::HPART);
         if (loss == NMF_FRO) {
             if (chunks) hipLaunchKernelGGL(k_nmf_h<NMF_FRO>, dim3(groups_grid(chunks)), block, 0, c->stream, colptr, crow, cval, cptr, cgene, chunks, K, kp, W, Ht(), part);
@@ -540,15 +492,7 @@ extern "C" int sc_nmf_fit(sc_ctx *c, const int64_t *indptr, const int32_t *indic
     SC_TRY(m.get(NmfBufs::INDICES, sizeof(int32_t) * (size_t)nnz));
     SC_TRY(m.get(NmfBufs::RAW, es * (size_t)nnz));
     SC_TRY(m.get(NmfBufs::VAL, sizeof(double) * (size_t)nnz));
-    SC_TRY(m.get(NmfBufs::KEYS, sizeof(u64) * (size_t)nnz));
-    SC_TRY(m.get(NmfBufs::KEYS2, sizeof(u64) * (size_t)nnz));
-    SC_TRY(m.get(NmfBufs::POS, sizeof(uint32_t) * (size_t)nnz));
-    SC_TRY(m.get(NmfBufs::POS2, sizeof(uint32_t) * (size_t)nnz));
-    SC_TRY(m.get(NmfBufs::ROWID, sizeof(int32_t) * (size_t)nnz));
-    SC_TRY(m.get(NmfBufs::CROW, sizeof(int32_t) * (size_t)nnz));
-    SC_TRY(m.get(NmfBufs::CVAL, sizeof(double) * (size_t)nnz));
-    SC_TRY(m.get(NmfBufs::COLPTR, sizeof(int64_t) * (size_t)(G + 1)));
-    SC_TRY(m.get(NmfBufs::CPTR, sizeof(int64_t) * (size_t)(G + 1)));
+    SC_TRY(colsort_alloc(c, m.cs, nnz, G));
     SC_TRY(m.get(NmfBufs::W, nW));
     SC_TRY(m.get(NmfBufs::H0, nH));
     SC_TRY(m.get(NmfBufs::H1, nH));
@@ -566,42 +510,22 @@ extern "C" int sc_nmf_fit(sc_ctx *c, const int64_t *indptr, const int32_t *indic
     SC_HIP(hipMemcpyAsync(m.b[NmfBufs::RAW].p, data, es * (size_t)nnz, hipMemcpyHostToDevice, s));
     SC_HIP(hipMemcpyAsync(m.b[NmfBufs::W].p, W, nW, hipMemcpyHostToDevice, s));
     SC_HIP(hipMemcpyAsync(m.b[NmfBufs::H0].p, H, nH, hipMemcpyHostToDevice, s));
-    int64_t chunks = 0;
     {
         KernelTimerScope ts(c, SC_K_NMF_SETUP);
-        const dim3 per_entry((unsigned)ceil_div64(nnz, 256)), per_gene((unsigned)ceil_div64(G + 1, 256)), tpb(256);
-        if (dtype == SC_F32)
-            hipLaunchKernelGGL(k_nmf_entries<float>, per_entry, tpb, 0, s, m.as<float>(NmfBufs::RAW), m.as<int32_t>(NmfBufs::INDICES), nnz,
-                               m.as<double>(NmfBufs::VAL), m.as<u64>(NmfBufs::KEYS), m.as<uint32_t>(NmfBufs::POS));
-        else
-            hipLaunchKernelGGL(k_nmf_entries<double>, per_entry, tpb, 0, s, m.as<double>(NmfBufs::RAW), m.as<int32_t>(NmfBufs::INDICES), nnz,
-                               m.as<double>(NmfBufs::VAL), m.as<u64>(NmfBufs::KEYS), m.as<uint32_t>(NmfBufs::POS));
-        hipLaunchKernelGGL(k_nmf_rowids, dim3((unsigned)ceil_div64(n, 256)), tpb, 0, s, m.as<int64_t>(NmfBufs::INDPTR), n, m.as<int32_t>(NmfBufs::ROWID));
-        int end_bit = 1;
-        while ((1 << end_bit) < G) ++end_bit;
-        SC_TRY((rs_sort<u64, uint32_t>(c, m.as<u64>(NmfBufs::KEYS), m.as<u64>(NmfBufs::KEYS2), m.as<uint32_t>(NmfBufs::POS),
-                                        m.as<uint32_t>(NmfBufs::POS2), nnz, end_bit)));
-        hipLaunchKernelGGL(k_nmf_csc_fill, per_entry, tpb, 0, s, m.as<uint32_t>(NmfBufs::POS2), m.as<int32_t>(NmfBufs::ROWID),
-                           m.as<double>(NmfBufs::VAL), nnz, m.as<int32_t>(NmfBufs::CROW), m.as<double>(NmfBufs::CVAL));
-        hipLaunchKernelGGL(k_nmf_colptr, per_gene, tpb, 0, s, m.as<u64>(NmfBufs::KEYS2), nnz, G, m.as<int64_t>(NmfBufs::COLPTR));
-        hipLaunchKernelGGL(k_nmf_chunk_scan, dim3(1), dim3(64), 0, s, m.as<int64_t>(NmfBufs::COLPTR), G, m.as<int64_t>(NmfBufs::CPTR));
+        const dim3 per_entry((unsigned)ceil_div64(nnz, 256)), tpb(256);
+        if (dtype == SC_F32) hipLaunchKernelGGL(k_nmf_values<float>, per_entry, tpb, 0, s, m.as<float>(NmfBufs::RAW), nnz, m.as<double>(NmfBufs::VAL));
+        else hipLaunchKernelGGL(k_nmf_values<double>, per_entry, tpb, 0, s, m.as<double>(NmfBufs::RAW), nnz, m.as<double>(NmfBufs::VAL));
+        SC_TRY(colsort_enqueue(c, m.cs, m.as<int64_t>(NmfBufs::INDPTR), m.as<int32_t>(NmfBufs::INDICES), m.as<double>(NmfBufs::VAL), n, G, nnz));
         hipLaunchKernelGGL(k_nmf_transpose, dim3((unsigned)ceil_div64((int64_t)K * G, 256)), tpb, 0, s, m.as<double>(NmfBufs::H0), (int)K, G,
                            m.as<double>(NmfBufs::HT0));
     }
-    SC_HIP(hipGetLastError());
-    SC_HIP(hipMemcpyAsync(&chunks, m.as<int64_t>(NmfBufs::CPTR) + G, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    SC_HIP(hipStreamSynchronize(s));
-    SC_REQUIRE(chunks >= 1 && chunks <= nnz / NMF_COL_CHUNK + G, SC_ERR_HIP, "sc_nmf_fit: column chunk count %lld out of range",
-               (long long)chunks);
-    st.chunks = chunks;
-    SC_TRY(m.get(NmfBufs::CGENE, sizeof(int32_t) * (size_t)chunks));
-    SC_TRY(m.get(NmfBufs::HPART, sizeof(double) * (size_t)chunks * K));
     {
         KernelTimerScope ts(c, SC_K_NMF_SETUP);
-        hipLaunchKernelGGL(k_nmf_chunk_fill, dim3((unsigned)ceil_div64(G, 256)), dim3(256), 0, s, m.as<int64_t>(NmfBufs::CPTR), G,
-                           m.as<int32_t>(NmfBufs::CGENE));
+        SC_TRY(colsort_finish(c, m.cs, G, nnz, "sc_nmf_fit"));
     }
     SC_HIP(hipGetLastError());
+    st.chunks = m.cs.chunks;
+    SC_TRY(m.get(NmfBufs::HPART, sizeof(double) * (size_t)m.cs.chunks * K));
 
     // ---- sklearn's loop: one scalar comes back per check, nothing else waits for the host -------------------------------
     double e0 = 0.0, e = 0.0;

@@ -1,0 +1,418 @@
+"""spatialcore_amd.annotation on the device: prediction bit for bit against the restatement in the device's summation
+order (tests/annotation_restated.py), the confidence transforms against the reference's golden, training against
+sklearn's newton-cholesky within a bound taken from the reference's own Hessian, and the chain into a cell-type statistic.
+
+Shapes are the smallest at which the kernels can go wrong: T = 2, 5, 33, 64 (two lanes, padded lanes, a full wavefront),
+T = 65 and 130 (two and three blocks of 64 classes), gene columns of 511, 512, 513 and 1543 stored entries, a cell count
+one past a multiple of the row pass's cells per workgroup and above one 1024-cell chunk."""
+import functools
+import json
+import logging
+
+import numpy as np
+import pytest
+from scipy import sparse
+
+import annotation_restated as R
+from conftest import load_golden, make_adata
+from test_cpu_annotation import held_out_margins
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-10
+CONF_KEYS = ("confidence_raw", "raw", "zscore", "softmax", "minmax")
+
+
+def _adata(X, labels=None, names=None):
+    ad = make_adata(np.zeros((X.shape[0], 2)), X)
+    return _labelled(ad, labels, names)
+
+
+def _cells(r, keep, what="X"):
+    """The recipe's cells over the model's genes only, so that the gene set does not shrink (no renormalisation)."""
+    from spatialcore_amd import SimpleAnnData
+
+    return SimpleAnnData(r[what][:, keep], var_names=[f"g{j}" for j in keep])
+
+
+def _labelled(ad, labels=None, names=None):
+    if labels is not None:
+        ad.obs["unified_cell_type"] = np.asarray([f"type{t:03d}" for t in labels]) if names is None else names[labels]
+    return ad
+
+
+@functools.lru_cache(maxsize=None)
+def _predict_case(n, G, T, seed):
+    """A recipe, a random model on its expressed genes, and the ordered restatement of its prediction (computed once)."""
+    from spatialcore_amd.annotation import CellTypeModel
+
+    r = R.recipe(n, G, T, seed)
+    keep = np.flatnonzero(np.diff(r["X"].tocsc().indptr) > 0)
+    X = r["X"][:, keep]
+    mean, scale = R.scaler(X)
+    rng = np.random.default_rng(seed + 7)
+    coef, b = rng.normal(0, 0.7, size=(T, keep.size)), rng.normal(0, 1.0, size=T)
+    b[0] += 3.0                                    # class 0 wins often enough at every T, and ...
+    coef[T - 1], b[T - 1] = coef[0], b[0]          # ... class T - 1 ties it exactly on every cell
+    model = CellTypeModel([f"g{j}" for j in keep], [f"type{t:03d}" for t in range(T)], coef, b, mean, scale)
+    want, tol = R.ulp_tolerance(lambda e: R.ordered_predict(X, coef, b, mean, scale, e), CONF_KEYS)
+    return r, keep, model, want, tol
+
+
+def _annotate(ad, **kw):
+    from spatialcore_amd.annotation import annotate_celltypist
+
+    kw.setdefault("min_confidence", 0.0)
+    return annotate_celltypist(ad, **kw)
+
+
+def _check_prediction(ad, model, want, tol, T):
+    S = ad.obsm["cell_type_decision_scores"]
+    assert S.dtype == np.float32 and np.array_equal(S, want["scores"])                    # bit-equal scores
+    assert np.array_equal(ad.obs["cell_type_predicted"].to_numpy(), model.cell_types[want["labels"]])
+    got = {"confidence_raw": ad.obs["cell_type_confidence_raw"].to_numpy(), "zscore": ad.obs["cell_type_confidence"].to_numpy()}
+    for key, val in got.items():
+        d = np.abs(val - want[key])
+        print(f"T={T} {key}: largest deviation {d.max():.3g}, tolerance at that cell {tol[key][np.argmax(d)]:.3g}")
+        assert np.all(d <= tol[key]), key
+
+
+@pytest.mark.parametrize("n,G,T,seed", R.SHAPES + R.WIDE_SHAPES)
+def test_prediction_is_the_ordered_restatement(n, G, T, seed):
+    from spatialcore_amd import _lib
+
+    r, keep, model, want, tol = _predict_case(n, G, T, seed)
+    ad = _annotate(_cells(r, keep), model=model)
+    _check_prediction(ad, model, want, tol, T)
+    assert ad.uns["cell_type_cell_types"] == list(model.cell_types)
+    ties = want["scores64"][:, 0] == want["scores64"].max(axis=1)
+    assert ties.sum() >= 1 and np.all(want["labels"][ties] == 0)                          # exact ties go to the first class
+    assert np.array_equal(ad.obsm["cell_type_decision_scores"][r["empty"]], want["base"].astype(np.float32))
+    # all four transforms and the raw confidence, straight from the library
+    X = r["X"][:, keep]
+    res = _lib.default_context(0).annot_predict(X.indptr, X.indices, X.data, "log1p", model.coef, model.intercept,
+                                                model.scaler_mean, model.scaler_scale)
+    assert np.array_equal(res["labels"], want["labels"]) and np.array_equal(res["scores"], want["scores"])
+    for key in CONF_KEYS:
+        d = np.abs(res[key] - want[key])
+        print(f"T={T} {key}: largest deviation {d.max():.3g}")
+        assert np.all(d <= tol[key]), key
+    assert np.array_equal(res["raw"], want["raw"]) and np.array_equal(res["minmax"], want["minmax"])   # no exp in these
+
+
+def test_row_count_one_past_a_workgroup_and_above_a_cell_chunk():
+    T = 5
+    n = R.rows_per_workgroup(T) * 33 + 1
+    assert n % R.rows_per_workgroup(T) == 1 and n > R.CELL_CHUNK
+    r, keep, model, want, tol = _predict_case(n, 12, T, 41)
+    _check_prediction(_annotate(_cells(r, keep), model=model), model, want, tol, T)
+
+
+def test_model_genes_the_data_lacks_contribute_nothing():
+    n, G, T, seed = R.SHAPES[1]
+    r, keep, model, _, _ = _predict_case(n, G, T, seed)
+    rng = np.random.default_rng(9)
+    drop = np.sort(rng.choice(keep.size, 6, replace=False))      # the data loses six of the model's genes
+    stay = np.setdiff1d(np.arange(keep.size), drop)
+    ad = _adata(r["X"])
+    data_cols = np.setdiff1d(np.arange(G), keep[drop])
+    sub = ad[:, [f"g{j}" for j in data_cols]]
+    got = _annotate(sub, model=model)
+    # the restatement on the overlap alone, renormalised over it as the reference does (the gene set shrank)
+    Xo = R.log1p_10k(r["counts"][:, keep[stay]])
+    want = R.ordered_predict(Xo, model.coef[:, stay], model.intercept, model.scaler_mean[stay], model.scaler_scale[stay])
+    S = got.obsm["cell_type_decision_scores"]
+    assert got.uns["spatialcore_metadata"]["operations"][-1]["parameters"]["input_state"] == "log1p_renorm"
+    # The device goes expm1 -> / row sum * 1e4 -> log1p where the restatement normalises the counts once: the five roundings
+    # move a normalised value x by at most 8 ulp of x, a score by at most 8 eps sum_g |x_ig / scale_g| |w_tg|; the float32
+    # rounding of the stored score adds half a float32 ulp.
+    eps = np.finfo(np.float64).eps
+    reach = (np.abs(np.asarray(Xo.todense())) / model.scaler_scale[stay]) @ np.abs(model.coef[:, stay]).T
+    tol = 8 * eps * reach + np.spacing(np.abs(want["scores"])).astype(np.float64)
+    d = np.abs(S.astype(np.float64) - want["scores64"])
+    print(f"missing genes: largest score deviation {d.max():.3g}, tolerance there {tol.flat[np.argmax(d)]:.3g}")
+    assert np.all(d <= tol)
+    # ... and within the same reach when the input is the counts themselves (one normalisation on the device, no expm1)
+    counts = _adata(r["counts"])[:, [f"g{j}" for j in data_cols]]
+    gc = _annotate(counts, model=model).obsm["cell_type_decision_scores"]
+    dc = np.abs(gc.astype(np.float64) - want["scores64"])
+    print(f"missing genes, counts input: largest score deviation {dc.max():.3g}")
+    assert np.all(dc <= tol)
+
+
+def test_counts_and_log1p_input_give_the_same_bits():
+    """The log1p input is normalised by numpy on the host, the counts by the device: the equality of the fp64 raw
+    confidence therefore also says that the two log1p implementations and divisions agree on these values.  If a
+    toolchain update ever separates them by an ulp, this test fails without a defect in the product: the float32 scores,
+    the labels and the transforms computed from them are the part that is the code's own property."""
+    n, G, T, seed = R.SHAPES[1]
+    r, keep, model, want, _ = _predict_case(n, G, T, seed)
+    a = _annotate(_cells(r, keep), model=model)
+    b = _annotate(_cells(r, keep, "counts"), model=model)
+    assert b.uns["spatialcore_metadata"]["operations"][-1]["parameters"]["input_state"] == "counts"
+    diff = int((a.obsm["cell_type_decision_scores"] != b.obsm["cell_type_decision_scores"]).sum())
+    print(f"counts vs log1p input: {diff} of {a.obsm['cell_type_decision_scores'].size} float32 scores differ")
+    assert diff == 0
+    for key in ("cell_type_confidence", "cell_type_confidence_raw"):
+        assert np.array_equal(a.obs[key].to_numpy(), b.obs[key].to_numpy())
+    assert np.array_equal(a.obs["cell_type_predicted"].to_numpy(), b.obs["cell_type_predicted"].to_numpy())
+
+
+def test_batch_size_never_changes_a_bit():
+    n, G, T, seed = R.SHAPES[0]
+    r, keep, model, want, _ = _predict_case(n, G, T, seed)
+    runs = [_annotate(_cells(r, keep), model=model, batch_size=bs) for bs in (1, 1000, None, 7)]
+    for other in runs[1:]:
+        assert other.obsm["cell_type_decision_scores"].tobytes() == runs[0].obsm["cell_type_decision_scores"].tobytes()
+        for key in ("cell_type_confidence", "cell_type_confidence_raw"):
+            assert other.obs[key].to_numpy().tobytes() == runs[0].obs[key].to_numpy().tobytes()
+        assert list(other.obs["cell_type"]) == list(runs[0].obs["cell_type"])
+    assert np.array_equal(runs[0].obsm["cell_type_decision_scores"], want["scores"])
+
+
+def test_stored_zeros_add_nothing_and_a_row_of_them_is_an_empty_row():
+    """The library itself accepts stored zeros (the Python layer removes them): in counts mode a row whose stored values are
+    all 0 has a row sum of 0 and must score the base, not 0 / 0."""
+    from spatialcore_amd import _lib
+
+    n, G, T, seed = R.SHAPES[0]
+    r, keep, model, want, _ = _predict_case(n, G, T, seed)
+    C = sparse.csr_matrix(r["counts"][:, keep])
+    indptr = np.concatenate([C.indptr[:r["empty"] + 1], C.indptr[r["empty"] + 1:] + 2]).astype(np.int64)
+    at = C.indptr[r["empty"]]
+    indices = np.concatenate([C.indices[:at], [0, 3], C.indices[at:]]).astype(np.int32)
+    data = np.concatenate([C.data[:at], [0.0, 0.0], C.data[at:]])
+    assert indptr[r["empty"] + 1] - indptr[r["empty"]] == 2 and indptr[-1] == data.size
+    ctx = _lib.default_context(0)
+    args = ("counts", model.coef, model.intercept, model.scaler_mean, model.scaler_scale)
+    res, plain = ctx.annot_predict(indptr, indices, data, *args), ctx.annot_predict(C.indptr, C.indices, C.data, *args)
+    assert np.all(np.isfinite(res["scores"])) and np.array_equal(res["scores"][r["empty"]], want["base"].astype(np.float32))
+    for key in ("scores", "labels") + CONF_KEYS:
+        assert np.array_equal(res[key], plain[key]), key          # the same matrix without its stored zeros
+
+
+def test_training_calls_out_of_order_raise_the_state_error():
+    from spatialcore_amd import _lib
+
+    ctx = _lib.default_context(0)
+    ctx.annot_train_end()
+    for call in (lambda: ctx.annot_train_forward(np.zeros((2, 3)), np.zeros(2)), ctx.annot_train_grad,
+                 lambda: ctx.annot_train_line(np.zeros(2)), lambda: ctx.annot_train_step(np.zeros(2))):
+        with pytest.raises(_lib.SpatialCoreHipError, match="no training problem is resident"):
+            call()
+    X, labels, T = _edge_matrix()
+    ctx.annot_train_begin(X.indptr, X.indices, X.data, X.shape[1], "log1p", T, labels, np.ones(X.shape[0]))
+    try:
+        with pytest.raises(_lib.SpatialCoreHipError, match="no scores are resident"):     # the library's own SC_ERR_STATE
+            ctx.annot_train_grad()
+    finally:
+        ctx.annot_train_end()
+    with pytest.raises(_lib.SpatialCoreHipError, match="no training problem is resident"):
+        ctx.annot_train_grad()
+
+
+def test_transform_confidence_against_the_reference_golden():
+    from spatialcore_amd.annotation import transform_confidence
+
+    g = load_golden("ref_annotation.npz")
+    for case in g["cases"]:
+        S = g[f"{case}_scores"]
+        for method in g["methods"]:
+            for wide, M in (("f32", S.astype(np.float32)), ("f64", S)):     # as recorded: the rounded matrix, the values themselves
+                got = transform_confidence(M, method=str(method))
+                assert got.dtype == np.float64 and got.shape == (M.shape[0],)
+                dev, ulp = float(g[f"{case}_{method}_{wide}_dev"]), float(g[f"{case}_{method}_{wide}_ulp"])
+                tol = 4.0 * dev if dev > 0 else 16.0 * ulp
+                d = float(np.max(np.abs(got - g[f"{case}_{method}_{wide}"].astype(np.float64))))
+                print(f"{case} {method} {wide}: deviation {d:.3g}, tolerance {tol:.3g}")
+                assert d <= tol, (case, method, wide)
+
+
+# ---- training --------------------------------------------------------------------------------------------------------------
+def _train(ad, **kw):
+    from spatialcore_amd.annotation import train_celltypist_model
+
+    kw.setdefault("tol", TOL)
+    return train_celltypist_model(ad, **kw)
+
+
+@pytest.mark.parametrize("balance", [True, False])
+@pytest.mark.parametrize("n,G,T,seed", R.SHAPES)
+def test_training_meets_the_stopping_rule_and_the_reference_bound(n, G, T, seed, balance):
+    r, ref = R.recipe(n, G, T, seed), R.reference_model(n, G, T, seed, balance)
+    out = _train(_adata(r["X"], r["labels"]), balance_cell_type=balance)
+    m, s = out["model"], ref["s"]
+    assert list(m.features) == [f"g{j}" for j in ref["keep"]] and list(m.cell_types) == [f"type{t:03d}" for t in range(T)]
+    np.testing.assert_allclose(m.scaler_mean, ref["mean"], rtol=1e-13, atol=0)
+    np.testing.assert_allclose(m.scaler_scale, ref["scale"], rtol=1e-12, atol=0)
+    g = R.gradient(ref["Z"], r["labels"], s, m.coef, m.intercept, 1.0)
+    gn = np.abs(g).max(axis=1) / s.sum()
+    bound = R.coefficient_bound(ref["Z"], s, ref["coef"], ref["intercept"], 1.0, TOL)
+    diff = np.maximum(np.abs(m.coef - ref["coef"]).max(axis=1), np.abs(m.intercept - ref["intercept"]))
+    print(f"train {(n, G, T)} balance={balance}: n_iter {out['n_iter'].max()}, scaled gradient {gn.max():.3g} (device "
+          f"{out['grad_norm'].max():.3g}), coefficient deviation / bound {np.max(diff / bound):.3g}, bound {bound.min():.3g}"
+          f" .. {bound.max():.3g}")
+    assert out["converged"].all() and out["grad_norm"].max() <= TOL
+    assert gn.max() <= 2e-10
+    assert np.all(diff <= bound)
+    assert out["n_cells_trained"] == n and out["n_genes"] == ref["keep"].size and out["n_cell_types"] == T
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_matrix():
+    """Gene columns with c - 1, c, c + 1 and 3 c + 7 stored entries (c = 512), n one past a multiple of the row pass's
+    cells per workgroup for T = 5 and above one cell chunk."""
+    T, c = 5, R.COL_CHUNK
+    n, G = R.rows_per_workgroup(T) * 52 + 1, 11
+    rng = np.random.default_rng(51)
+    A = rng.poisson(0.6, size=(n, G)).astype(np.float64)
+    for g, cnt in enumerate((c - 1, c, c + 1, 3 * c + 7)):
+        A[:, g] = 0
+        A[rng.choice(n, cnt, replace=False), g] = rng.integers(1, 6, size=cnt)
+    A[A.sum(axis=1) == 0, G - 1] = 1
+    X = R.log1p_10k(sparse.csr_matrix(A))
+    assert list(np.diff(X.tocsc().indptr)[:4]) == [c - 1, c, c + 1, 3 * c + 7]
+    assert n % R.rows_per_workgroup(T) == 1 and n > R.CELL_CHUNK
+    return X, rng.integers(0, T, n).astype(np.int32), T
+
+
+def _passes_against_numpy(X, labels, T, seed):
+    """The device's scaler, forward pass, gradient and line-search derivatives against plain numpy at random coefficients."""
+    from spatialcore_amd import _lib
+
+    n, G = X.shape
+    rng = np.random.default_rng(seed)
+    s = rng.uniform(0.5, 2.0, n)
+    W, b = rng.normal(0, 0.3, size=(T, G)), rng.normal(0, 0.5, size=T)
+    P, pb = rng.normal(0, 0.3, size=(T, G)), rng.normal(0, 0.5, size=T)
+    alpha = rng.uniform(0.1, 1.5, T)
+    ref = R.NumpyProblem(X, labels, s, T)
+    ctx = _lib.default_context(0)
+    mean, scale = ctx.annot_train_begin(X.indptr, X.indices, X.data, G, "log1p", T, labels, s)
+    try:
+        np.testing.assert_allclose(mean, ref.mean, rtol=1e-13, atol=0)
+        np.testing.assert_allclose(scale, ref.scale, rtol=1e-12, atol=0)
+        for be in (ctx, ref):
+            be.annot_train_forward(W, b)
+            be.annot_train_forward(P, pb, True)
+        (g, loss), (g0, loss0) = ctx.annot_train_grad(), ref.annot_train_grad()
+        (d1, d2), (e1, e2) = ctx.annot_train_line(alpha), ref.annot_train_line(alpha)
+        ctx.annot_train_step(alpha)
+        ref.annot_train_step(alpha)
+        g2, g20 = ctx.annot_train_grad()[0], ref.annot_train_grad()[0]
+    finally:
+        ctx.annot_train_end()
+    scale_g = np.abs(ref.Z).T @ (s[:, None] * np.ones((n, T)))          # sum_i s_i |z_ig|: the size of a gradient's terms
+    mag = np.hstack([scale_g.T, np.full((T, 1), s.sum())])
+    for name, a, a0 in (("gradient", g, g0), ("gradient after the step", g2, g20)):
+        rel = np.max(np.abs(a - a0) / mag)
+        print(f"T={T} {name}: largest deviation {rel:.3g} of the terms' size")
+        assert rel <= 1e-12
+    np.testing.assert_allclose(loss, loss0, rtol=1e-12)
+    np.testing.assert_allclose(d1, e1, rtol=0, atol=1e-12 * np.abs(ref.Dir).max() * s.sum())
+    np.testing.assert_allclose(d2, e2, rtol=1e-12)
+
+
+def test_column_chunk_edges_and_row_tail_in_the_training_passes():
+    X, labels, T = _edge_matrix()
+    _passes_against_numpy(X, labels, T, 61)
+
+
+@pytest.mark.parametrize("n,G,T,seed", R.WIDE_SHAPES)
+def test_training_passes_past_one_wavefront_of_classes(n, G, T, seed):
+    r = R.recipe(n, G, T, seed)
+    keep = np.flatnonzero(np.diff(r["X"].tocsc().indptr) > 0)
+    _passes_against_numpy(r["X"][:, keep], r["labels"], T, seed)
+
+
+def test_max_iter_warns_and_reports_not_converged(caplog):
+    n, G, T, seed = R.SHAPES[0]
+    r = R.recipe(n, G, T, seed)
+    lg = logging.getLogger("spatialcore_amd")
+    lg.addHandler(caplog.handler)
+    try:
+        with caplog.at_level(logging.INFO, logger="spatialcore_amd"):
+            out = _train(_adata(r["X"], r["labels"]), max_iter=3, use_SGD=False, epochs=2)
+    finally:
+        lg.removeHandler(caplog.handler)
+    assert not out["converged"].any() and out["n_iter"].max() == 3 and out["grad_norm"].min() > TOL
+    assert any("Maximum number of iterations 3 reached" in rec.getMessage() and rec.levelno == logging.WARNING
+               for rec in caplog.records)
+    assert sum("recorded and ignored" in rec.getMessage() for rec in caplog.records) == 1
+    assert out["training_params"]["epochs"] == 2 and out["training_params"]["use_SGD"] is False
+
+
+def test_two_calls_give_byte_identical_results():
+    n, G, T, seed = R.SHAPES[1]
+    r = R.recipe(n, G, T, seed)
+    a, b = (_train(_adata(r["X"], r["labels"]))["model"] for _ in range(2))
+    for k in ("coef", "intercept", "scaler_mean", "scaler_scale"):
+        assert getattr(a, k).tobytes() == getattr(b, k).tobytes()
+    pa, pb = (_annotate(_adata(r["X"]), model=m) for m in (a, b))     # (the all-zero gene leaves: renormalised on the device)
+    assert pa.obsm["cell_type_decision_scores"].tobytes() == pb.obsm["cell_type_decision_scores"].tobytes()
+    assert pa.obs["cell_type_confidence"].to_numpy().tobytes() == pb.obs["cell_type_confidence"].to_numpy().tobytes()
+
+
+def test_end_to_end_train_write_annotate_and_chain(tmp_path):
+    """train -> write -> annotate(custom_model_path) on held-out cells against the sklearn pipeline, the keys and dtypes,
+    "Unassigned", the metadata entry, and obs["cell_type"] straight into neighborhood_enrichment."""
+    import pandas as pd
+
+    from spatialcore_amd.annotation import CellTypeModel
+    from spatialcore_amd.spatial import neighborhood_enrichment
+
+    held, ref, S_ref, decided = held_out_margins()
+    n, G, T, seed = 777, 37, 5, 32
+    r = R.recipe(n, G, T, seed)
+    names = np.array(["B cell", "NK", "T cell", "mast", "plasma"])
+    path = tmp_path / "models" / "panel.npz"
+    out = _train(_adata(r["X"], r["labels"], names), output_path=path, model_name="panel")
+    assert out["model_path"] == str(path) and out["converged"].all() and out["cell_types"] == list(names)
+    assert np.array_equal(CellTypeModel.load(path).coef, out["model"].coef)
+    with open(out["metadata_path"]) as f:
+        side = json.load(f)
+    assert out["metadata_path"] == str(tmp_path / "models" / "panel_celltypist.json") and side["cell_types"] == list(names)
+    assert side["training_params"]["mini_batch"] is True and side["training_params"]["solver"] == "full-batch L-BFGS"
+
+    first = _annotate(_cells(held, ref["keep"]), custom_model_path=path)
+    thr = float(np.median(first.obs["cell_type_confidence_raw"]))      # a threshold that splits these cells
+    assert not (first.obs["cell_type"] == "Unassigned").any()
+    ad = _cells(held, ref["keep"])
+    ad.obsm["spatial"] = np.random.default_rng(2).uniform(0, 100, (n, 2))
+    got = _annotate(ad, custom_model_path=path, min_confidence=thr)
+    assert got is ad
+    pred = got.obs["cell_type_predicted"].to_numpy()
+    want = names[np.argmax(S_ref, axis=1)]
+    print(f"end to end: {int((~decided).sum())} of {n} cells left out, {int((pred != want).sum())} labels differ overall")
+    assert (~decided).mean() <= 0.001 and np.array_equal(pred[decided], want[decided])
+    conf_raw = got.obs["cell_type_confidence_raw"].to_numpy()
+    np.testing.assert_allclose(conf_raw, R.expit(S_ref.max(axis=1)), rtol=0, atol=1e-4)
+    low = conf_raw < thr
+    assert low.any() and (~low).any()
+    assert isinstance(got.obs["cell_type"].dtype, pd.CategoricalDtype)
+    assert np.all(got.obs["cell_type"].to_numpy()[low] == "Unassigned")
+    assert np.array_equal(got.obs["cell_type"].to_numpy()[~low], pred[~low])
+    assert got.obs["cell_type_confidence"].dtype == np.float64 and got.obs["cell_type_confidence_raw"].dtype == np.float64
+    assert np.all((got.obs["cell_type_confidence"] >= 0) & (got.obs["cell_type_confidence"] <= 1))
+    assert set(got.obs["cell_type_model"]) == {str(path)}
+    assert got.obsm["cell_type_decision_scores"].dtype == np.float32 and got.obsm["cell_type_decision_scores"].shape == (n, T)
+    assert got.uns["cell_type_cell_types"] == list(names)
+    entry = got.uns["spatialcore_metadata"]["operations"][-1]
+    assert entry["function"] == "annotate_celltypist" and entry["parameters"]["min_confidence"] == thr
+    assert entry["parameters"]["input_state"] == "log1p" and entry["outputs"]["obsm"] == "cell_type_decision_scores"
+    # an ensemble of the same model twice: the first wins every tie, no scores are stored, the raw confidence stands in
+    ens = _annotate(_cells(held, ref["keep"]), model=[out["model"], str(path)], min_confidence=thr)
+    assert set(ens.obs["cell_type_model"]) == {"model_0"} and "cell_type_decision_scores" not in ens.obsm
+    assert np.array_equal(ens.obs["cell_type_confidence"].to_numpy(), conf_raw)
+    assert list(ens.obs["cell_type"]) == list(got.obs["cell_type"])
+    # majority voting by a cluster column
+    cl = _cells(held, ref["keep"])
+    cl.obs["leiden"] = (np.arange(n) % 4).astype(str)
+    voted = _annotate(cl, model=out["model"], majority_voting=True, min_confidence=0.0)
+    for c in "0123":
+        assert voted.obs["cell_type"][cl.obs["leiden"] == c].nunique() == 1
+    # the chain: obs["cell_type"] as written
+    ne = neighborhood_enrichment(got, "cell_type", k=6, n_permutations=20)
+    cats = list(ne.uns["neighborhood_enrichment"]["celltypes"])
+    assert "Unassigned" in cats and ne.uns["neighborhood_enrichment"]["count"].shape == (len(cats), len(cats))
+    assert ne.uns["neighborhood_enrichment"]["count"].sum() == 6 * n
