@@ -305,12 +305,14 @@ def _passes_against_numpy(X, labels, T, seed):
     scale_g = np.abs(ref.Z).T @ (s[:, None] * np.ones((n, T)))          # sum_i s_i |z_ig|: the size of a gradient's terms
     mag = np.hstack([scale_g.T, np.full((T, 1), s.sum())])
     for name, a, a0 in (("gradient", g, g0), ("gradient after the step", g2, g20)):
-        rel = np.max(np.abs(a - a0) / mag)
+        assert not a[mag == 0].any()                                    # an all-zero gene has no terms: exactly 0
+        rel = np.max(np.abs(a - a0) / np.where(mag > 0, mag, 1.0))
         print(f"T={T} {name}: largest deviation {rel:.3g} of the terms' size")
         assert rel <= 1e-12
     np.testing.assert_allclose(loss, loss0, rtol=1e-12)
     np.testing.assert_allclose(d1, e1, rtol=0, atol=1e-12 * np.abs(ref.Dir).max() * s.sum())
     np.testing.assert_allclose(d2, e2, rtol=1e-12)
+    return mean, scale, g, loss, d1, d2, g2
 
 
 def test_column_chunk_edges_and_row_tail_in_the_training_passes():
