@@ -73,7 +73,10 @@ extern "C" {
 #define SC_K_ANNOT_LINE 33    /* ... one evaluation of the line search's derivatives */
 #define SC_K_ANNOT_PREDICT 34 /* sc_annot_predict / sc_annot_transform: the row pass with the fused per-cell epilogue */
 #define SC_K_ANNOT_STEP 35    /* sc_annot_train_step: the score update S <- S + alpha Dir */
-#define SC_K_COUNT_ 36
+#define SC_K_PCA_SETUP 36     /* sc_pca_begin: the normalisation of the resident values */
+#define SC_K_PCA_GRAM 37      /* sc_pca_gram: the MFMA Gram kernel, the slice reduction and the column sums */
+#define SC_K_PCA_PROJECT 38   /* sc_pca_project: the row pass X V^T - offset */
+#define SC_K_COUNT_ 39
 
 typedef struct sc_ctx sc_ctx;
 
@@ -784,6 +787,32 @@ int sc_annot_train_grad(sc_ctx *ctx, double *grad_out, double *loss_out);
 int sc_annot_train_line(sc_ctx *ctx, const double *alpha, double *d1_out, double *d2_out);
 int sc_annot_train_step(sc_ctx *ctx, const double *alpha);
 int sc_annot_train_end(sc_ctx *ctx);
+
+/* ---- N15 (extension): exact covariance PCA -- spatialcore_amd.pca ------------------------------------
+ * X is a CANONICAL CSR (rows' columns strictly ascending inside [0, n_genes), values SC_F32 or SC_F64, finite) over the
+ * genes in use; negative values are legal unless normalize != 0.  Everything is fp64, -ffp-contract=off for the plain
+ * C++ sums, no floating-point atomics, and the bytes of every result are a function of the arguments alone.
+ * sc_pca_begin: validates the CSR on the host, uploads it and keeps the fp64 values resident: as they are, or with
+ *   normalize != 0 log1p(x / rowsum * target_sum), the row sum over the stored entries in index order (a row whose sum is
+ *   0 stays 0).  A second _begin replaces the resident matrix (as sc_annot_train_begin does).
+ * sc_pca_gram: gram_out[G][G] = X^T X and colsum_out[G] = column sums of the resident values.  The G x G output is cut
+ *   into 128 x 128 blocks, of which the upper triangle is computed; the rows are cut into S slices of R rows, with
+ *   R = max(16384, ceil(n / max(1, 2048 / blocks)) rounded up to a multiple of 32) and S = ceil(n / R) -- functions of
+ *   (n, n_genes) alone.  One workgroup owns (block, slice): it densifies 32 rows at a time into two column panels and
+ *   accumulates with v_mfma_f64_16x16x4_f64, i.e. an element's slice sum runs over the rows in groups of four: within
+ *   a k-step the hardware's order, the k-steps ascending.  gram[i][j] = the S slice sums added in ascending slice order,
+ *   mirrored into [j][i].  colsum[g] = per slice the rows in ascending order from 0.0, the slice sums in ascending order.
+ * sc_pca_project: scores_out[i][c] = (0.0 + sum_p val[p] * V[c][idx[p]], the row's stored entries in index order,
+ *   multiply and add rounded separately) - offset[c]; out_dtype SC_F64, or SC_F32 = that value rounded once.
+ *   V is [K][n_genes] row-major.  Needs _begin, not _gram.
+ * sc_pca_end: frees the resident matrix.
+ * 2 <= n <= 2^31 - 1, 1 <= n_genes <= 4096, 1 <= K <= 64, stored entries <= 2^32 - 1. */
+int sc_pca_begin(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
+                 int32_t n_genes, int32_t normalize, double target_sum);
+int sc_pca_values(sc_ctx *ctx, double *values_out);   /* the resident fp64 values, one per stored entry in CSR order */
+int sc_pca_gram(sc_ctx *ctx, double *colsum_out, double *gram_out);
+int sc_pca_project(sc_ctx *ctx, const double *V, const double *offset, int32_t K, int out_dtype, void *scores_out);
+int sc_pca_end(sc_ctx *ctx);
 
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across

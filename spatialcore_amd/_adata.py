@@ -1,7 +1,7 @@
 """Minimal in-memory AnnData look-alike.
 
 The hot path only touches a handful of AnnData attributes:
-``X, layers, obs, obsm, obsp, uns, var_names, n_obs, copy()`` and column slicing
+``X, layers, obs, obsm, obsp, varm, uns, var_names, n_obs, copy()`` and column slicing
 ``adata[:, names]``. ``anndata`` is not installed in the build image nor on the GPU box, so
 tests, ``bench.py`` and users without ``anndata`` use this class; every public function in
 ``spatialcore_amd.spatial`` duck-types and works with a real ``anndata.AnnData`` as well.
@@ -30,6 +30,7 @@ class SimpleAnnData:
         obsp: Optional[Dict[str, Any]] = None,
         layers: Optional[Dict[str, Any]] = None,
         uns: Optional[Dict[str, Any]] = None,
+        varm: Optional[Dict[str, Any]] = None,
     ) -> None:
         if not sparse.issparse(X):
             X = np.asarray(X)
@@ -52,6 +53,7 @@ class SimpleAnnData:
         self.obs = obs
         self.obsm = dict(obsm or {})
         self.obsp = dict(obsp or {})
+        self.varm = dict(varm or {})
         self.layers = dict(layers or {})
         self.uns = dict(uns or {})
 
@@ -83,6 +85,7 @@ class SimpleAnnData:
             obsp={k: v.copy() for k, v in self.obsp.items()},
             layers={k: v.copy() for k, v in self.layers.items()},
             uns=_copy.deepcopy(self.uns),
+            varm={k: _copy.deepcopy(v) for k, v in self.varm.items()},
         )
 
     def __getitem__(self, key) -> "SimpleAnnData":
@@ -106,6 +109,7 @@ class SimpleAnnData:
             obsp=self.obsp,
             layers=layers,
             uns=self.uns,
+            varm={k: np.asarray(v)[cols] for k, v in self.varm.items()},
         )
 
     def __repr__(self) -> str:

@@ -30,6 +30,7 @@ K_RIPLEY_G_LIST, K_RIPLEY_G_RELABEL, K_RIPLEY_G_COUNT = 19, 20, 21
 K_NMF_SETUP, K_NMF_W, K_NMF_H, K_NMF_ERR = 22, 23, 24, 25
 K_DIFF_KNN, K_DIFF_GRAPH, K_DIFF_SPMV, K_DIFF_ORTH = 26, 27, 28, 29
 K_ANNOT_SETUP, K_ANNOT_ROWS, K_ANNOT_GRAD, K_ANNOT_LINE, K_ANNOT_PREDICT, K_ANNOT_STEP = 30, 31, 32, 33, 34, 35
+K_PCA_SETUP, K_PCA_GRAM, K_PCA_PROJECT = 36, 37, 38
 ANNOT_MODES = {"counts": 0, "log1p": 1, "log1p_renorm": 2}   # sc_annot_*'s input states
 NMF_LOSSES = {"frobenius": 2, "kullback-leibler": 1}   # sc_nmf_fit's codes (sklearn's beta)
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
@@ -139,6 +140,11 @@ SYMBOLS = {
     "sc_annot_train_line": [_P, _P, _P, _P],
     "sc_annot_train_step": [_P, _P],
     "sc_annot_train_end": [_P],
+    "sc_pca_begin": [_P, _P, _P, _P, c_int, c_int64, c_int32, c_int32, c_double],
+    "sc_pca_values": [_P, _P],
+    "sc_pca_gram": [_P, _P, _P],
+    "sc_pca_project": [_P, _P, _P, c_int32, c_int, _P],
+    "sc_pca_end": [_P],
     "sc_comm_unique_id": [_P],
     "sc_comm_create": [_P, _P, c_int, c_int, POINTER(c_void_p)],
     "sc_comm_destroy": [_P],
@@ -259,6 +265,7 @@ class Context:
         self._ripley_radii = 0   # radii of the resident Ripley pair list (shape of ripley_counts / ripley_counter results)
         self._ripley_g_radii = 0   # ... and of the resident Ripley's G neighbour lists
         self._annot_shape = None   # (classes, genes) of the resident training problem (annot_train_begin .. annot_train_end)
+        self._pca_shape = None     # (cells, genes) of the resident PCA matrix (pca_begin .. pca_end)
         self._diff_n = self._diff_nnz = self._lanczos_cap = 0   # cells / stored entries of the resident diffusion graph, Lanczos basis cap
 
     def close(self) -> None:
@@ -1003,6 +1010,58 @@ class Context:
         if self._annot_shape is None:
             raise SpatialCoreHipError(f"{who}: no training problem is resident (annot_train_begin)")
         return self._annot_shape
+
+    # ---- N15 (extension): PCA ------------------------------------------------------------------
+    def pca_begin(self, indptr, indices, data, n_genes: int, normalize: bool = False, target_sum: float = 1e4) -> None:
+        """sc_pca_begin: validates a canonical CSR over the genes in use and leaves its fp64 values on the device, as they
+        are or as ``log1p(x / rowsum * target_sum)``.  A second call replaces the resident matrix."""
+        indptr, indices, data, n = self._annot_csr(indptr, indices, data, "pca_begin")
+        self._pca_shape = None   # until the call succeeds this object vouches for no resident matrix
+        _check(self._lib.sc_pca_begin(self._h, _ptr(indptr), _ptr(indices), _ptr(data),
+                                      SC_F32 if data.dtype == np.float32 else SC_F64, n, int(n_genes), int(bool(normalize)),
+                                      float(target_sum)))
+        self._pca_shape = (n, int(n_genes))
+        self._pca_nnz = int(data.size)
+
+    def pca_values(self) -> np.ndarray:
+        """sc_pca_values: the resident fp64 values, one per stored entry in CSR order (the normalised ones after
+        ``normalize``): what sc_pca_gram and sc_pca_project read."""
+        self._pca_dims("pca_values")
+        out = np.empty(self._pca_nnz, dtype=np.float64)
+        _check(self._lib.sc_pca_values(self._h, _ptr(out)))
+        return out
+
+    def pca_gram(self):
+        """sc_pca_gram: (column sums (G,), Gram matrix X^T X (G, G)) of the resident values, float64."""
+        _, G = self._pca_dims("pca_gram")
+        colsum, gram = np.empty(G, dtype=np.float64), np.empty((G, G), dtype=np.float64)
+        _check(self._lib.sc_pca_gram(self._h, _ptr(colsum), _ptr(gram)))
+        return colsum, gram
+
+    def pca_project(self, V, offset, dtype=np.float64) -> np.ndarray:
+        """sc_pca_project: ``X V^T - offset`` of the resident values, (n, K) in ``dtype`` (float64, or float32 = the
+        float64 result rounded once).  ``V`` is (K, G), ``offset`` (K,)."""
+        n, G = self._pca_dims("pca_project")
+        V, offset = _c(V, np.float64), _c(offset, np.float64)
+        if V.ndim != 2 or V.shape[1] != G or offset.shape != (V.shape[0],):
+            raise ValueError(f"pca_project: V must be (K, {G}) and offset (K,)")
+        dtype = np.dtype(dtype)
+        if dtype not in (np.float32, np.float64):
+            raise ValueError(f"pca_project: dtype must be float32 or float64, got {dtype}")
+        out = np.empty((n, V.shape[0]), dtype=dtype)
+        _check(self._lib.sc_pca_project(self._h, _ptr(V), _ptr(offset), V.shape[0], SC_F32 if dtype == np.float32 else SC_F64,
+                                        _ptr(out)))
+        return out
+
+    def pca_end(self) -> None:
+        self._pca_shape = None
+        _check(self._lib.sc_pca_end(self._h))
+
+    def _pca_dims(self, who: str):
+        """(cells, genes) of the resident matrix; without one, the library's own state error."""
+        if self._pca_shape is None:
+            raise SpatialCoreHipError(f"{who}: no matrix is resident (pca_begin)")
+        return self._pca_shape
 
     # ---- N13 (extension): diffusion maps ------------------------------------------------------
     def knn_dense(self, X, k: int, fetch: bool = True, splits: int = 0):

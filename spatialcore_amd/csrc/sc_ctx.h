@@ -205,6 +205,8 @@ struct sc_ctx {
     } df;
     // ---- annotation (sc_annotate.hip): the training problem kept on the device between sc_annot_train_begin and _end ----
     struct AnnotTrain *an = nullptr;
+    // ---- PCA (sc_pca.hip): the matrix kept on the device between sc_pca_begin and sc_pca_end ----
+    struct PcaState *pca = nullptr;
 
     // ---- graph (CSR, rows sorted by column) + transpose ----
     int64_t g_n = 0, g_nnz = 0;
@@ -409,5 +411,6 @@ int rs_sort(sc_ctx *c, const K *k_in, K *k_out, const V *v_in, V *v_out, int64_t
 int sc_kmeans_run_labels(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t C, int32_t K, int32_t n_init,
                          int32_t max_iter, double tol, const void *x_mean, const double *uniforms, int32_t *labels_dev);
 void sc_annot_release(sc_ctx *c);   // drops the resident training problem, if any (sc_annotate.hip)
+void sc_pca_release(sc_ctx *c);     // drops the resident PCA matrix, if any (sc_pca.hip)
 void sc_launch_spmv_vec(sc_ctx *c, const int64_t *indptr, const int32_t *indices, const double *w,
                         const double *x, double *y, int64_t n);
