@@ -76,7 +76,9 @@ extern "C" {
 #define SC_K_PCA_SETUP 36     /* sc_pca_begin: the normalisation of the resident values */
 #define SC_K_PCA_GRAM 37      /* sc_pca_gram: the MFMA Gram kernel, the slice reduction and the column sums */
 #define SC_K_PCA_PROJECT 38   /* sc_pca_project: the row pass X V^T - offset */
-#define SC_K_COUNT_ 39
+#define SC_K_LOUVAIN_MOVE 39  /* sc_louvain_level: the move kernels of a round and the sum of tot^2 */
+#define SC_K_LOUVAIN_LEVEL 40 /* sc_louvain_*: degrees, the split (union-find, scans) and the aggregation (sort, run sums) */
+#define SC_K_COUNT_ 41
 
 typedef struct sc_ctx sc_ctx;
 
@@ -813,6 +815,44 @@ int sc_pca_values(sc_ctx *ctx, double *values_out);   /* the resident fp64 value
 int sc_pca_gram(sc_ctx *ctx, double *colsum_out, double *gram_out);
 int sc_pca_project(sc_ctx *ctx, const double *V, const double *offset, int32_t K, int out_dtype, void *scores_out);
 int sc_pca_end(sc_ctx *ctx);
+
+/* ---- N16 (extension): deterministic Louvain communities -- spatialcore_amd.cluster -------------------------
+ * Louvain with a connectivity split, not Leiden.  The graph is a symmetric CANONICAL CSR (columns strictly ascending
+ * inside [0, n)), 1 <= n <= 2^31 - 1, stored entries <= 2^31 - 1, integer weights q_ij = q_ji in [1, 65535]; diagonal
+ * entries count once in the degree and never as a neighbour; rows may be empty and the graph disconnected.
+ * g = rint(resolution 2^16) in [1, 2^23].  Everything on the device is exact integer arithmetic (64-bit degrees and
+ * totals, 128-bit S and Qnum, integer atomics), so every output is a function of the arguments alone.
+ * One level on A with n_l vertices: k_i = sum_j A_ij, M = sum_i k_i, comm_i = i, Qnum(comm) = 2^16 M sum_{comm_i = comm_j}
+ *   A_ij - g sum_c tot_c^2, tot_c = sum_{comm_i = c} k_i; best = the singletons, stale = 0.  Round r = 0, 1, ...: every vertex
+ *   reads the same comm and tot; its candidates are comm_i and the comm_j of its stored neighbours j != i; k_ic = sum_{j != i,
+ *   comm_j = c} A_ij; S_i(c) = 2^16 M k_ic - g k_i (tot_c - [c = comm_i] k_i); allowed are comm_i, c > comm_i in even rounds,
+ *   c < comm_i in odd rounds; the vertex takes the allowed c with the largest S, on equal S its current community, then
+ *   the lowest c; all moves at once; if Qnum of the new comm exceeds the best so far it becomes best and stale = 0, else
+ *   stale += 1; the level ends at stale = 2 or after max_rounds rounds (the search goes on from comm, not from best).
+ *   Split: the connected components of the edges (i != j) inside the communities of best, labelled by the rank of their
+ *   smallest vertex.  As many components as vertices: the hierarchy is finished.  Otherwise A'_ab = sum_{i in a, j in b}
+ *   A_ij is the next level's graph.
+ * sc_louvain_begin: validates on the host, before its first HIP call (SC_ERR_INVALID names the first offending entry: a
+ *   row that is not canonical, a weight of 0, an entry without its mirror, a mirror of another weight), uploads.  A second
+ *   _begin replaces the state.
+ * sc_louvain_resident_weights / sc_louvain_begin_resident: the same on the graph sc_diffmap_graph* left on the device,
+ *   whose structure does not visit the host: _resident_weights fetches its nnz fp64 kernel weights so that the host can
+ *   quantise them, _begin_resident takes the nnz quantised weights in CSR order (NULL: 1 per edge) and checks the
+ *   symmetry on the device.  No resident graph: SC_ERR_STATE.
+ * sc_louvain_level: runs one level.  info_out[12] = n_l, rounds, communities of best, components after the split, Qnum of
+ *   the split partition (signed high limb, low limb), 1 if the hierarchy is finished, 1 if the level ended at max_rounds,
+ *   rows in the wavefront / workgroup / global class of the move kernels (<= 64 / <= 2048 / more entries), stored entries
+ *   of the level.  labels_out[n_l] (may be NULL) = the level's component labels.  After the finished level: SC_ERR_STATE.
+ * sc_louvain_labels: labels_out[n] = the composition of the levels run so far, clusters numbered by descending size, ties
+ *   to the smaller smallest member; *n_clusters_out their number.
+ * sc_louvain_end: frees every device buffer of the state. */
+int sc_louvain_begin(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const uint16_t *q, int64_t n, int32_t g,
+                     int32_t max_rounds);
+int sc_louvain_resident_weights(sc_ctx *ctx, double *w_out, int64_t nnz);
+int sc_louvain_begin_resident(sc_ctx *ctx, const uint16_t *q, int64_t nnz, int32_t g, int32_t max_rounds);
+int sc_louvain_level(sc_ctx *ctx, int64_t *info_out, int32_t *labels_out);
+int sc_louvain_labels(sc_ctx *ctx, int32_t *labels_out, int64_t *n_clusters_out);
+int sc_louvain_end(sc_ctx *ctx);
 
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across

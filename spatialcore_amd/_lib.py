@@ -31,6 +31,7 @@ K_NMF_SETUP, K_NMF_W, K_NMF_H, K_NMF_ERR = 22, 23, 24, 25
 K_DIFF_KNN, K_DIFF_GRAPH, K_DIFF_SPMV, K_DIFF_ORTH = 26, 27, 28, 29
 K_ANNOT_SETUP, K_ANNOT_ROWS, K_ANNOT_GRAD, K_ANNOT_LINE, K_ANNOT_PREDICT, K_ANNOT_STEP = 30, 31, 32, 33, 34, 35
 K_PCA_SETUP, K_PCA_GRAM, K_PCA_PROJECT = 36, 37, 38
+K_LOUVAIN_MOVE, K_LOUVAIN_LEVEL = 39, 40
 ANNOT_MODES = {"counts": 0, "log1p": 1, "log1p_renorm": 2}   # sc_annot_*'s input states
 NMF_LOSSES = {"frobenius": 2, "kullback-leibler": 1}   # sc_nmf_fit's codes (sklearn's beta)
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
@@ -145,6 +146,12 @@ SYMBOLS = {
     "sc_pca_gram": [_P, _P, _P],
     "sc_pca_project": [_P, _P, _P, c_int32, c_int, _P],
     "sc_pca_end": [_P],
+    "sc_louvain_begin": [_P, _P, _P, _P, c_int64, c_int32, c_int32],
+    "sc_louvain_resident_weights": [_P, _P, c_int64],
+    "sc_louvain_begin_resident": [_P, _P, c_int64, c_int32, c_int32],
+    "sc_louvain_level": [_P, _P, _P],
+    "sc_louvain_labels": [_P, _P, POINTER(c_int64)],
+    "sc_louvain_end": [_P],
     "sc_comm_unique_id": [_P],
     "sc_comm_create": [_P, _P, c_int, c_int, POINTER(c_void_p)],
     "sc_comm_destroy": [_P],
@@ -266,6 +273,7 @@ class Context:
         self._ripley_g_radii = 0   # ... and of the resident Ripley's G neighbour lists
         self._annot_shape = None   # (classes, genes) of the resident training problem (annot_train_begin .. annot_train_end)
         self._pca_shape = None     # (cells, genes) of the resident PCA matrix (pca_begin .. pca_end)
+        self._louvain_n = None     # vertices of the next Louvain level (louvain_begin .. louvain_end)
         self._diff_n = self._diff_nnz = self._lanczos_cap = 0   # cells / stored entries of the resident diffusion graph, Lanczos basis cap
 
     def close(self) -> None:
@@ -1062,6 +1070,61 @@ class Context:
         if self._pca_shape is None:
             raise SpatialCoreHipError(f"{who}: no matrix is resident (pca_begin)")
         return self._pca_shape
+
+    # ---- N16 (extension): Louvain communities ---------------------------------------------------
+    def louvain_begin(self, indptr, indices, q, g: int, max_rounds: int) -> None:
+        """sc_louvain_begin: a symmetric canonical CSR with integer weights in [1, 65535] becomes level 0 of a new
+        hierarchy; ``g`` = rint(resolution 2^16).  Everything is validated on the host before the device is touched."""
+        indptr, indices, q = _c(indptr, np.int64), _c(indices, np.int32), _c(q, np.uint16)
+        n = indptr.size - 1
+        if indptr.ndim != 1 or n < 1 or indices.shape != q.shape or indices.ndim != 1 or indptr[-1] != q.size:
+            raise ValueError("louvain_begin: indptr, indices and weights do not describe one CSR matrix")
+        self._louvain_n = None
+        _check(self._lib.sc_louvain_begin(self._h, _ptr(indptr), _ptr(indices), _ptr(q), n, int(g), int(max_rounds)))
+        self._louvain_n = n
+
+    def louvain_resident_weights(self) -> np.ndarray:
+        """sc_louvain_resident_weights: the fp64 kernel weights of the graph ``diffmap_graph`` left on the device, in CSR
+        order (its structure stays where it is)."""
+        w = np.empty(self._diff_nnz, dtype=np.float64)
+        _check(self._lib.sc_louvain_resident_weights(self._h, _ptr(w), int(w.size)))
+        return w
+
+    def louvain_begin_resident(self, q, g: int, max_rounds: int) -> None:
+        """sc_louvain_begin_resident: level 0 = the structure of the resident ``diffmap_graph`` with the integer weights
+        ``q`` in CSR order (None: 1 per edge); the symmetry is checked on the device."""
+        if q is not None:
+            q = _c(q, np.uint16)
+            if q.shape != (self._diff_nnz,):
+                raise ValueError(f"louvain_begin_resident: need {self._diff_nnz} weights, got shape {q.shape}")
+        self._louvain_n = None
+        _check(self._lib.sc_louvain_begin_resident(self._h, _ptr(q), int(self._diff_nnz), int(g), int(max_rounds)))
+        self._louvain_n = int(self._diff_n)
+
+    def louvain_level(self, labels: bool = True) -> dict:
+        """sc_louvain_level: runs the next level and returns its record; ``qnum`` is the exact Python integer."""
+        if self._louvain_n is None:
+            raise SpatialCoreHipError("louvain_level: no graph is resident (louvain_begin)")
+        info = np.zeros(12, dtype=np.int64)
+        lab = np.empty(self._louvain_n, dtype=np.int32) if labels else None
+        _check(self._lib.sc_louvain_level(self._h, _ptr(info), _ptr(lab)))
+        self._louvain_n = int(info[3])
+        return {"n_vertices": int(info[0]), "rounds": int(info[1]), "n_best": int(info[2]), "n_communities": int(info[3]),
+                "qnum": (int(info[4]) << 64) + (int(info[5]) & 0xFFFFFFFFFFFFFFFF), "finished": bool(info[6]),
+                "hit_max_rounds": bool(info[7]), "rows_wavefront": int(info[8]), "rows_workgroup": int(info[9]),
+                "rows_global": int(info[10]), "nnz": int(info[11]), "labels": lab}
+
+    def louvain_labels(self, n: int) -> np.ndarray:
+        """sc_louvain_labels: the labels of the ``n`` input vertices after the levels run so far, clusters numbered by
+        descending size (ties: the smaller smallest member)."""
+        out = np.empty(int(n), dtype=np.int32)
+        nc = c_int64(0)
+        _check(self._lib.sc_louvain_labels(self._h, _ptr(out), byref(nc)))
+        return out
+
+    def louvain_end(self) -> None:
+        self._louvain_n = None
+        _check(self._lib.sc_louvain_end(self._h))
 
     # ---- N13 (extension): diffusion maps ------------------------------------------------------
     def knn_dense(self, X, k: int, fetch: bool = True, splits: int = 0):

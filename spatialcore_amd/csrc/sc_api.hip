@@ -240,6 +240,7 @@ int sc_ctx_destroy(sc_ctx *c)
     for (DBuf *b : c->df.bufs()) b->release(&c->mem);
     sc_annot_release(c);
     sc_pca_release(c);
+    sc_louvain_release(c);
     c->pg.release(&c->mem);
     for (int k = 0; k < SC_K_COUNT_; ++k) {
         for (auto &ev : c->timers[k].pending) {

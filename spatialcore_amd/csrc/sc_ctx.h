@@ -207,6 +207,8 @@ struct sc_ctx {
     struct AnnotTrain *an = nullptr;
     // ---- PCA (sc_pca.hip): the matrix kept on the device between sc_pca_begin and sc_pca_end ----
     struct PcaState *pca = nullptr;
+    // ---- Louvain (sc_louvain.hip): the level graphs and the partition kept on the device between sc_louvain_begin and _end ----
+    struct LouvainState *louvain = nullptr;
 
     // ---- graph (CSR, rows sorted by column) + transpose ----
     int64_t g_n = 0, g_nnz = 0;
@@ -412,5 +414,6 @@ int sc_kmeans_run_labels(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t
                          int32_t max_iter, double tol, const void *x_mean, const double *uniforms, int32_t *labels_dev);
 void sc_annot_release(sc_ctx *c);   // drops the resident training problem, if any (sc_annotate.hip)
 void sc_pca_release(sc_ctx *c);     // drops the resident PCA matrix, if any (sc_pca.hip)
+void sc_louvain_release(sc_ctx *c); // drops the resident Louvain hierarchy, if any (sc_louvain.hip)
 void sc_launch_spmv_vec(sc_ctx *c, const int64_t *indptr, const int32_t *indices, const double *w,
                         const double *x, double *y, int64_t n);
