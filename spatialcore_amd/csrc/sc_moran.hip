@@ -294,6 +294,47 @@ __device__ __forceinline__ void score_fma(const uint32_t (&w)[4], int t, double2
     acc[1] = fma(l.y, v1, acc[1]);
 }
 
+// ---- the byte-plane products of k_moran_score_wg<8, 4, false, true> ----
+// Counts x <= 255 and neighbour sums S = lo + 256 hi <= 65535 are integers, so sum_j S_j x_j = sum lo x + 256 sum hi x, and
+// each plane is a sum of byte products: v_dot4_u32_u8 takes four cells at a time once both operands hold one gene's bytes
+// of the block's four cells in one word.  Exact, and the same doubles as the fp64 products give: a plane sum of a task is
+// at most cells_per_split * 255 * 255 <= 65536 * 65025 = 4 261 478 400 < 2^32 (score_cells_per_split(n) <= 65536 for every
+// n < 2^25 this form serves), and the recombined sum is below 65536 * 65535 * 255 < 2^53.
+
+// o[i] = byte i of the words a, b, c, d of four rows (ascending): the transposed 4 x 4 byte square
+__device__ __forceinline__ void score_transpose4(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t (&o)[4])
+{
+    const uint32_t ab0 = __builtin_amdgcn_perm(b, a, 0x05010400u), ab1 = __builtin_amdgcn_perm(b, a, 0x07030602u);
+    const uint32_t cd0 = __builtin_amdgcn_perm(d, c, 0x05010400u), cd1 = __builtin_amdgcn_perm(d, c, 0x07030602u);
+    o[0] = __builtin_amdgcn_perm(cd0, ab0, 0x05040100u);
+    o[1] = __builtin_amdgcn_perm(cd0, ab0, 0x07060302u);
+    o[2] = __builtin_amdgcn_perm(cd1, ab1, 0x05040100u);
+    o[3] = __builtin_amdgcn_perm(cd1, ab1, 0x07060302u);
+}
+
+// One block of four gathered rows times its plane image sp = &image[block][q]: piece sp[8 t] holds, for tile t, the words
+// {lo, hi of gene 16 t + 2 q; lo, hi of gene 16 t + 2 q + 1}, byte i of a word = cell i of the block.  lo / hi[2 t + e]: the
+// lane's plane sums of gene 16 t + 2 q + e.
+__device__ __forceinline__ void score_dot_block(const uint4 (&x)[4], const uint4 *sp, uint32_t (&lo)[16], uint32_t (&hi)[16])
+{
+    const uint32_t w[4][4] = {{x[0].x, x[0].y, x[0].z, x[0].w}, {x[1].x, x[1].y, x[1].z, x[1].w},
+                              {x[2].x, x[2].y, x[2].z, x[2].w}, {x[3].x, x[3].y, x[3].z, x[3].w}};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {   // word k of the rows: tiles 2 k and 2 k + 1
+        uint32_t o[4];
+        score_transpose4(w[0][k], w[1][k], w[2][k], w[3][k], o);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const uint4 s = sp[(2 * k + h) * 8];
+            const int g = 4 * k + 2 * h;
+            lo[g] = __builtin_amdgcn_udot4(o[2 * h], s.x, lo[g], false);
+            hi[g] = __builtin_amdgcn_udot4(o[2 * h], s.y, hi[g], false);
+            lo[g + 1] = __builtin_amdgcn_udot4(o[2 * h + 1], s.z, lo[g + 1], false);
+            hi[g + 1] = __builtin_amdgcn_udot4(o[2 * h + 1], s.w, hi[g + 1], false);
+        }
+    }
+}
+
 template <int BITS, int CB, bool BIG, bool L16 = false>
 __global__ __launch_bounds__(SCORE_PRIVATE_WAVES * 64) void k_moran_score(
     const uint4 *__restrict__ narrow, const double *__restrict__ Lag, int64_t tile_elems, int tiles16,
@@ -466,6 +507,10 @@ __global__ __launch_bounds__(SCORE_PRIVATE_WAVES * 64) void k_moran_score(
 // same barriers.  What bounds the kernel is the bytes a compute unit pulls in, so a short chunk costs about its share of a
 // full one while enough wavefronts are left to keep the memory path busy; the host sends chunks with fewer than
 // SCORE_WG_MIN_PERMS permutations in their last task to k_moran_score instead.
+// <8, 4, false, true> (uint8 rows, 16-bit lag): the same loop with integer products (score_dot_block).  The lag words are
+// parked as two byte planes, transposed so that a word holds one gene's bytes of a block's four cells: 2 x 4 KB of LDS, 32
+// ds_read_b128 per wavefront and super-block instead of 128, 32 v_perm_b32 + 32 v_dot4_u32_u8 per block and lane instead of
+// 200 instructions of which 128 were fp64.  Its task sums are the same doubles (bound: above score_transpose4).
 // ------------------------------------------------------------------------------------------------
 #define SCORE_SB 16   // cells per lag super-block
 #define SCORE_WG_MIN_PERMS 24   // permutations in a chunk's last (partial) task from which the workgroup form is used
@@ -486,7 +531,9 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void k_moran_score_wg(
     constexpr int SPS = SCORE_SB / CB;            // pipeline stages per super-block
     constexpr int PIECES = SCORE_SB * ROW;        // 16-byte pieces of one super-block's lag rows (<= 1024)
     static_assert(PIECES <= SCORE_WAVES * 64 && (SCORE_WAVES * 64) % PIECES == 0, "every thread loads one piece");
-    __shared__ double2 lds_lag[2][PIECES];        // [buffer][cell][ROW]
+    // PLANES: the uint8 source on 16-bit lag rows multiplies in integers, four cells per instruction (score_dot_block)
+    constexpr bool PLANES = BITS == 8 && CB == 4 && !BIG && L16;
+    __shared__ double2 lds_lag[2][PLANES ? SCORE_SB / 4 * ROW : PIECES];   // [buffer][cell][ROW]; PLANES: [buffer][block][ROW]
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = lane >> 3, q = lane & 7;
     const int pid = (int)threadIdx.x % PIECES;    // this thread's piece of every super-block
@@ -529,6 +576,9 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void k_moran_score_wg(
         uint32_t ai[NIB ? 32 : 1];   // NIB: integer sums of the lane's 32 slots
 #pragma unroll
         for (int k2 = 0; k2 < (NIB ? 32 : 1); ++k2) ai[k2] = 0u;
+        uint32_t plo[PLANES ? 16 : 1], phi[PLANES ? 16 : 1];   // PLANES: plane sums of the lane's 16 genes (score_dot_block)
+#pragma unroll
+        for (int k2 = 0; k2 < (PLANES ? 16 : 1); ++k2) plo[k2] = phi[k2] = 0u;
         const int64_t nsb = (c1 - c0) / SCORE_SB;   // whole super-blocks of the split (the rest: tail loop below)
         const int64_t nblk = nsb * SPS;
 
@@ -536,6 +586,14 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void k_moran_score_wg(
         uint32_t lh = 0;   // L16: the thread's piece as a pair of 16-bit sums
         uint4 xa[CB], xb[CB];
         auto park = [&](int buf) {
+            if constexpr (PLANES) {
+                // the image score_dot_block reads: this thread's word is (cell lcell, tile, q) = {lo, hi, lo, hi} of two genes;
+                // its bytes go to byte lcell % 4 of the four words of piece [block lcell / 4][tile][q].  The eight pieces one
+                // ds_read_b128 fetches (q = 0 .. 7, each broadcast to the 8 permutations) are contiguous: no bank conflict.
+                unsigned char *dst = reinterpret_cast<unsigned char *>(&lds_lag[buf][(lcell >> 2) * ROW + (pid % ROW)]) + (lcell & 3);
+                dst[0] = (unsigned char)lh; dst[4] = (unsigned char)(lh >> 8);
+                dst[8] = (unsigned char)(lh >> 16); dst[12] = (unsigned char)(lh >> 24);
+            } else
             if constexpr (L16) lds_lag[buf][pid] = lag16_to_double2(lh);
             else lds_lag[buf][pid] = lg;
         };
@@ -574,9 +632,10 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void k_moran_score_wg(
             __builtin_amdgcn_sched_barrier(0);
             load_idx(id_next, sb * SPS + k + 1 + SPS);
             __builtin_amdgcn_sched_barrier(0);
-            const double2 *lr = &lds_lag[sb & 1][k * CB * ROW + q];
+            const double2 *lr = &lds_lag[sb & 1][(PLANES ? k * ROW : k * CB * ROW) + q];
+            if constexpr (PLANES) score_dot_block(cur, reinterpret_cast<const uint4 *>(lr), plo, phi);
 #pragma unroll
-            for (int c = 0; c < CB; ++c) {
+            for (int c = 0; c < (PLANES ? 0 : CB); ++c) {
                 mul_cell(cur[c], lr + c * ROW);
                 if constexpr (NIB) __builtin_amdgcn_sched_barrier(0);   // (one cell's operand pieces at a time: hoisted together they spill)
             }
@@ -620,6 +679,22 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void k_moran_score_wg(
             }
         }
         if (live) {
+            if constexpr (PLANES) {
+                // ragged tail of the split (< 16 cells) in plain integers (one cell per trip: vectorised by two, hipcc keeps a second
+                // set of the 32 sums and spills)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+                for (int64_t j = c0 + nsb * SCORE_SB; j < c1; ++j) {
+                    const uint4 x = score_row<BIG>(Xg, qoff, irow[j]);
+                    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                    for (int t = 0; t < TG; ++t) {
+                        const uint32_t s = lag16_g[j * ROW + t * 8 + q], h = w[t >> 1] >> (16 * (t & 1));
+                        const uint32_t x0 = h & 0xffu, x1 = (h >> 8) & 0xffu;
+                        plo[2 * t] += __umul24(x0, s & 0xffu); phi[2 * t] += __umul24(x0, (s >> 8) & 0xffu);
+                        plo[2 * t + 1] += __umul24(x1, (s >> 16) & 0xffu); phi[2 * t + 1] += __umul24(x1, s >> 24);
+                    }
+                }
+            } else
             for (int64_t j = c0 + nsb * SCORE_SB; j < c1; ++j) {   // ragged tail of the split (< 16 cells): straight from global memory
                 const uint4 x = score_row<BIG>(Xg, qoff, irow[j]);
                 const uint32_t w[4] = {x.x, x.y, x.z, x.w};
@@ -655,7 +730,11 @@ __global__ __launch_bounds__(SCORE_WAVES * 64) void k_moran_score_wg(
                 // partial[group][split][perm][16 t + 2 q + e]
                 double2 *out = reinterpret_cast<double2 *>(partial) + (((int64_t)grp * n_splits + split) * n_perm + p) * ROW + q;
 #pragma unroll
-                for (int t = 0; t < TG; ++t) out[t * 8] = make_double2(acc[t][0], acc[t][1]);
+                for (int t = 0; t < TG; ++t) {
+                    if constexpr (PLANES) out[t * 8] = make_double2((double)plo[2 * t] + 256.0 * (double)phi[2 * t],
+                                                                    (double)plo[2 * t + 1] + 256.0 * (double)phi[2 * t + 1]);
+                    else out[t * 8] = make_double2(acc[t][0], acc[t][1]);
+                }
                 }
             }
         }
@@ -1425,9 +1504,11 @@ extern "C" int sc_moran(sc_ctx *c, int64_t n_perm, double *I_out, double *sims_o
 }
 
 // (what the number means and how it was chosen: the comment in front of moran_seeded_streams)
-#define SCORE_RESERVED_CUS 112   // r04 (two runs of 20 steps each, same box, ms per step): 96 -> 163.1 / 162.2, 112 -> 157.7 / 158.5,
-                                 // 128 -> 162.2 / 162.6, 144 -> 171.0 / 169.5; the scoring launches take the same 117 ms on 144 CUs
-                                 // as on 160 (13 rounds of tasks either way), the generator's preparation gets its CUs sooner
+#define SCORE_RESERVED_CUS 128   // byte-plane scoring (two runs of 20 steps each, same box, ms per step): 96 -> 151.2 / 151.8,
+                                 // 112 -> 149.7 / 149.2, 128 -> 143.8 / 143.5, 144 -> 143.9 / 143.8 (and 120 -> 146.1 / 146.3, 125 ->
+                                 // 144.5 / 144.2, 136 -> 147.4 / 146.7).  At 112 the integer kernel's launches are a tenth shorter than the
+                                 // fp64 kernel's (104 ms per step instead of 116) but the chain beside them slows from 123 to 129 ms and
+                                 // the step stays where it was; with 16 more CUs the chain takes 105 ms, the launches 109 ms
 static int moran_seeded_once(sc_ctx *c, uint64_t *state6, int64_t n_perm, double *I_out, double *sims_out,
                              int64_t *count_ge_out, double *sim_sum_out, double *sim_sumsq_out, PermPipe *begun)
 {
