@@ -78,7 +78,8 @@ extern "C" {
 #define SC_K_PCA_PROJECT 38   /* sc_pca_project: the row pass X V^T - offset */
 #define SC_K_LOUVAIN_MOVE 39  /* sc_louvain_level: the move kernels of a round and the sum of tot^2 */
 #define SC_K_LOUVAIN_LEVEL 40 /* sc_louvain_*: degrees, the split (union-find, scans) and the aggregation (sort, run sums) */
-#define SC_K_COUNT_ 41
+#define SC_K_NEIGHBORS_GRAM 41 /* sc_knn_dense_gram: norms, the MFMA filter, the exact re-rank and the fallback scan */
+#define SC_K_COUNT_ 42
 
 typedef struct sc_ctx sc_ctx;
 
@@ -737,6 +738,17 @@ int sc_nmf_fit(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const
  * sc_lanczos_end releases the basis. */
 int sc_knn_dense(sc_ctx *ctx, const void *X, int dtype, int64_t n, int32_t d, int32_t k, int32_t splits, int32_t *idx_out,
                  double *d2_out);
+/* sc_knn_dense_gram: the lists of sc_knn_dense, bit for bit, for every input; the same arguments, limits and refusals, and the
+ *   same state left on the device (sc_diffmap_graph follows unchanged).  `path`: 0 = the library's choice by (n, padded d),
+ *   1 = the direct kernels (the call is sc_knn_dense), 2 = the certified Gram-form filter: norms n_i, g_ij = x_i . x_j by
+ *   v_mfma_f64_16x16x4_f64, s_ij = (n_i + n_j) - 2 g_ij, lo_ij = s_ij - E_ij with E_ij = (4 dp + 32) 2^-52 (n_i + n_j) + 2^-1000
+ *   (dp = d rounded up to a multiple of 8), so that lo_ij <= d2(i, j) as the direct form computes it; a row keeps its
+ *   L = k + slack smallest (lo, j), re-ranks them by the direct form and is certified iff it kept fewer than L or its k-th
+ *   d2 < its L-th lo; the other rows are searched again by the direct form.  `slack`: 0 = the library's choice (8), else
+ *   1 .. 16.  info_out[4] = path taken, L (k on path 1), rows certified by the filter, rows sent to the fallback (both 0 on
+ *   path 1). */
+int sc_knn_dense_gram(sc_ctx *ctx, const void *X, int dtype, int64_t n, int32_t d, int32_t k, int32_t path, int32_t slack,
+                      int32_t *idx_out, double *d2_out, int64_t *info_out);
 int sc_diffmap_graph(sc_ctx *ctx, double *s2_out, int64_t *n_edges_out, int64_t *n_components_out);
 int sc_diffmap_graph_csr(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const double *w, int64_t n,
                          int64_t *n_components_out);

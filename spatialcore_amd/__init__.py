@@ -1,15 +1,15 @@
 """spatialcore_amd -- MI355X-native drop-in for the spatialcore.spatial hot path."""
 from spatialcore_amd._adata import SimpleAnnData
 
-__all__ = ["SimpleAnnData", "init", "diffusion"]
+__all__ = ["SimpleAnnData", "init", "diffusion", "neighbors"]
 __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name == "diffusion":   # imported on first use: the subpackage pulls in scipy.linalg
+    if name in ("diffusion", "neighbors"):   # imported on first use: the subpackages pull in scipy.linalg
         import importlib
 
-        return importlib.import_module("spatialcore_amd.diffusion")
+        return importlib.import_module("spatialcore_amd." + name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

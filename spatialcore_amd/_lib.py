@@ -32,6 +32,7 @@ K_DIFF_KNN, K_DIFF_GRAPH, K_DIFF_SPMV, K_DIFF_ORTH = 26, 27, 28, 29
 K_ANNOT_SETUP, K_ANNOT_ROWS, K_ANNOT_GRAD, K_ANNOT_LINE, K_ANNOT_PREDICT, K_ANNOT_STEP = 30, 31, 32, 33, 34, 35
 K_PCA_SETUP, K_PCA_GRAM, K_PCA_PROJECT = 36, 37, 38
 K_LOUVAIN_MOVE, K_LOUVAIN_LEVEL = 39, 40
+K_NEIGHBORS_GRAM = 41
 ANNOT_MODES = {"counts": 0, "log1p": 1, "log1p_renorm": 2}   # sc_annot_*'s input states
 NMF_LOSSES = {"frobenius": 2, "kullback-leibler": 1}   # sc_nmf_fit's codes (sklearn's beta)
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
@@ -126,6 +127,7 @@ SYMBOLS = {
     "sc_nmf_fit": [_P, _P, _P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P,
                    POINTER(c_int32), POINTER(c_int32), POINTER(c_double)],
     "sc_knn_dense": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, _P, _P],
+    "sc_knn_dense_gram": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P, _P],
     "sc_diffmap_graph": [_P, _P, POINTER(c_int64), POINTER(c_int64)],
     "sc_diffmap_graph_csr": [_P, _P, _P, _P, c_int64, POINTER(c_int64)],
     "sc_diffmap_graph_get": [_P, _P, _P, _P, _P],
@@ -1143,6 +1145,26 @@ class Context:
                                       _ptr(idx), _ptr(d2)))
         self._diff_n = n
         return (idx, d2) if fetch else None
+
+    def knn_dense_gram(self, X, k: int, fetch: bool = True, path: int = 0, slack: int = 0):
+        """sc_knn_dense_gram: the lists of ``knn_dense``, bit for bit, through the certified Gram-form filter on the fp64
+        matrix cores.  ``path``: 0 the library's choice, 1 the direct kernels, 2 the filter; ``slack``: list entries the
+        filter keeps beyond ``k`` (0: the library's choice).  Returns (indices, squared distances, info) -- the first two
+        None without ``fetch`` -- with ``info`` = {``path``, ``list_length``, ``rows_certified``, ``rows_fallback``}."""
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            raise ValueError(f"knn_dense_gram: features must be float32 or float64, got {X.dtype}")
+        if X.ndim != 2:
+            raise ValueError(f"knn_dense_gram: features must have shape (n, d), got {X.shape}")
+        n, d = X.shape
+        idx = np.empty((n, int(k)), dtype=np.int32) if fetch else None
+        d2 = np.empty((n, int(k)), dtype=np.float64) if fetch else None
+        info = np.zeros(4, dtype=np.int64)
+        _check(self._lib.sc_knn_dense_gram(self._h, _ptr(X), SC_F32 if X.dtype == np.float32 else SC_F64, n, d, int(k), int(path),
+                                           int(slack), _ptr(idx), _ptr(d2), _ptr(info)))
+        self._diff_n = n
+        return idx, d2, {"path": int(info[0]), "list_length": int(info[1]), "rows_certified": int(info[2]),
+                         "rows_fallback": int(info[3])}
 
     def diffmap_graph(self) -> dict:
         """sc_diffmap_graph on the lists of the last ``knn_dense``: ``s2`` (local scales), ``n_edges`` (stored entries of

@@ -18,22 +18,17 @@
 #include <cmath>
 #include <vector>
 
-#include "sc_topk.h"
+#include "sc_dense_knn.h"
 #include "sc_unionfind.h"
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int DF_DMAX = 64;
-constexpr int DF_KMAX = 32;
 constexpr int DF_DREG = 32;       // widest (padded) feature row a thread keeps in registers; wider rows live in LDS
 constexpr int DF_QB = 256;        // register form: queries per workgroup ...
 constexpr int DF_TILE = 128;      // ... and candidates staged in LDS at a time
-constexpr int DF_QB_L = 64;       // LDS form (32 < d <= 64): queries per workgroup (their rows take 32 KiB) ...
-constexpr int DF_TILE_L = 32;     // ... and candidates per tile (16 KiB)
-constexpr int64_t DF_SPLIT_BELOW = 100000;   // fewer queries than this: the candidates are split over workgroups
-constexpr int DF_SPLIT_WGS = 2048;           // ... aiming at about this many
+// the LDS form (32 < d <= 64: DF_QB_L queries, DF_TILE_L candidates) and the split rule: sc_dense_knn.h
 constexpr int DF_CHUNK = 1024;    // cells per partial of a dot product
 constexpr int DF_RITZ_MAX = 64;
 
@@ -45,17 +40,7 @@ static int bits_for(int64_t count)   // bits that hold 0 .. count - 1 (at least 
 }
 
 // ---- search ------------------------------------------------------------------------------------------------------
-// X[n][dp] <- the caller's rows widened to fp64, columns d .. dp - 1 zero
-template <class T>
-__global__ __launch_bounds__(256) void k_df_widen(const T *__restrict__ raw, int64_t n, int d, int dp, double *__restrict__ X)
-{
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * dp) return;
-    const int64_t i = t / dp;
-    const int c = (int)(t % dp);
-    X[t] = c < d ? (double)raw[i * d + c] : 0.0;
-}
-
+// (the widening kernel k_df_widen, the direct-form distance df_d2 and the list write-out: sc_dense_knn.h)
 // One thread per query, its row in DR registers; workgroup (x, y) scans the candidates [y * split_len, (y + 1) * split_len)
 // in tiles staged through LDS and read as broadcasts.  Writes the K-list of that split, best first, to
 // (pidx, pd2)[y][query][k]; entries a short split could not fill keep TopK's sentinel (DBL_MAX, INT_MAX).
@@ -81,26 +66,14 @@ __global__ __launch_bounds__(DF_QB) void k_df_knn_reg(const double *__restrict__
         if (i < n) {
             for (int j = 0; j < cnt; ++j) {
                 const double *x = tile + j * DR;
-                const double f0 = q[0] - x[0];
-                double acc = f0 * f0;
-#pragma unroll
-                for (int c = 1; c < DR; ++c) {
-                    const double f = q[c] - x[c];
-                    acc = acc + f * f;
-                }
+                const double acc = df_d2<DR>([&](int c) { return q[c]; }, [&](int c) { return x[c]; }, DR);
                 const int cid = (int)(b + j);
                 if (cid != (int)i && cand_better(acc, cid, best.d[K - 1], best.id[K - 1])) best.insert(acc, cid);
             }
         }
     }
     if (i >= n) return;
-    const int64_t o = ((int64_t)blockIdx.y * n + i) * k;
-#pragma unroll
-    for (int j = 0; j < K; ++j)
-        if (j < k) {
-            pidx[o + j] = best.id[j];
-            pd2[o + j] = best.d[j];
-        }
+    df_write_list(best, k, ((int64_t)blockIdx.y * n + i) * k, pidx, pd2);
 }
 
 // The same with the queries' rows in LDS (column c of the workgroup's queries is one conflict-free row of 64 doubles):
@@ -126,25 +99,14 @@ __global__ __launch_bounds__(DF_QB_L) void k_df_knn_lds(const double *__restrict
         if (i < n) {
             for (int j = 0; j < cnt; ++j) {
                 const double *x = tile + j * dp;
-                const double f0 = qs[t] - x[0];
-                double acc = f0 * f0;
-                for (int c = 1; c < dp; ++c) {
-                    const double f = qs[c * DF_QB_L + t] - x[c];
-                    acc = acc + f * f;
-                }
+                const double acc = df_d2<0>([&](int c) { return qs[c * DF_QB_L + t]; }, [&](int c) { return x[c]; }, dp);
                 const int cid = (int)(b + j);
                 if (cid != (int)i && cand_better(acc, cid, best.d[K - 1], best.id[K - 1])) best.insert(acc, cid);
             }
         }
     }
     if (i >= n) return;
-    const int64_t o = ((int64_t)blockIdx.y * n + i) * k;
-#pragma unroll
-    for (int j = 0; j < K; ++j)
-        if (j < k) {
-            pidx[o + j] = best.id[j];
-            pd2[o + j] = best.d[j];
-        }
+    df_write_list(best, k, ((int64_t)blockIdx.y * n + i) * k, pidx, pd2);
 }
 
 // the k best of a query's `splits` lists, by the same comparison (a sentinel never beats anything)
@@ -164,12 +126,7 @@ __global__ __launch_bounds__(256) void k_df_knn_merge(const int32_t *__restrict_
             if (cand_better(cd, cid, best.d[K - 1], best.id[K - 1])) best.insert(cd, cid);
         }
     }
-#pragma unroll
-    for (int j = 0; j < K; ++j)
-        if (j < k) {
-            idx[i * k + j] = best.id[j];
-            d2[i * k + j] = best.d[j];
-        }
+    df_write_list(best, k, i * k, idx, d2);
 }
 
 template <int K>
@@ -451,15 +408,6 @@ int df_finish_graph(sc_ctx *c, int64_t *n_components_out)
     return SC_OK;
 }
 
-template <class T>
-int df_require_finite(const T *X, int64_t count)
-{
-    for (int64_t p = 0; p < count; ++p)
-        SC_REQUIRE(std::fabs((double)X[p]) < 0x1p500, SC_ERR_INVALID,   // so that no squared distance overflows
-                   "sc_knn_dense: feature value %lld is not finite and below 2^500 in magnitude", (long long)p);
-    return SC_OK;
-}
-
 }  // namespace
 
 extern "C" int sc_knn_dense(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t d, int32_t k, int32_t splits, int32_t *idx_out,
@@ -472,8 +420,8 @@ extern "C" int sc_knn_dense(sc_ctx *c, const void *X, int dtype, int64_t n, int3
     SC_REQUIRE(n > k && n <= INT32_MAX, SC_ERR_INVALID, "sc_knn_dense: need k < n <= 2^31 - 1, got n=%lld, k=%d", (long long)n, k);
     SC_REQUIRE(n * k <= ((int64_t)1 << 29), SC_ERR_INVALID, "sc_knn_dense: need n * k <= 2^29, got %lld", (long long)(n * k));
     SC_REQUIRE(splits >= 0 && splits <= 65535, SC_ERR_INVALID, "sc_knn_dense: need 0 <= splits <= 65535, got %d", splits);
-    if (dtype == SC_F32) SC_TRY(df_require_finite((const float *)X, n * d));
-    else SC_TRY(df_require_finite((const double *)X, n * d));
+    if (dtype == SC_F32) SC_TRY(df_require_finite("sc_knn_dense", (const float *)X, n * d));
+    else SC_TRY(df_require_finite("sc_knn_dense", (const double *)X, n * d));
 
     SC_HIP(hipSetDevice(c->device));
     sc_ctx::Diffusion &f = c->df;
