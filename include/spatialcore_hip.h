@@ -79,7 +79,9 @@ extern "C" {
 #define SC_K_LOUVAIN_MOVE 39  /* sc_louvain_level: the move kernels of a round and the sum of tot^2 */
 #define SC_K_LOUVAIN_LEVEL 40 /* sc_louvain_*: degrees, the split (union-find, scans) and the aggregation (sort, run sums) */
 #define SC_K_NEIGHBORS_GRAM 41 /* sc_knn_dense_gram: norms, the MFMA filter, the exact re-rank and the fallback scan */
-#define SC_K_COUNT_ 42
+#define SC_K_UMAP_GRAPH 42  /* sc_fuzzy_graph: rho, the distance mean, the bisection, union (sort), memberships, normalisation */
+#define SC_K_UMAP_LAYOUT 43 /* sc_umap_layout: the maximum weight and one launch per epoch */
+#define SC_K_COUNT_ 44
 
 typedef struct sc_ctx sc_ctx;
 
@@ -865,6 +867,58 @@ int sc_louvain_begin_resident(sc_ctx *ctx, const uint16_t *q, int64_t nnz, int32
 int sc_louvain_level(sc_ctx *ctx, int64_t *info_out, int32_t *labels_out);
 int sc_louvain_labels(sc_ctx *ctx, int32_t *labels_out, int64_t *n_clusters_out);
 int sc_louvain_end(sc_ctx *ctx);
+
+/* ---- N17 (extension): UMAP connectivities and a deterministic layout -- spatialcore_amd.neighbors(method="umap"),
+ * spatialcore_amd.embedding -------------------------------------------------------------------------
+ * Reference site: umap-learn's umap_.py (smooth_knn_dist, compute_membership_strengths, fuzzy_simplicial_set,
+ * make_epochs_per_sample) and layouts.py (optimize_layout_euclidean), McInnes, Healy, Melville 2018, restated from the
+ * published algorithm with that library's defaults only (local_connectivity = 1, bandwidth = 1, set_op_mix_ratio = 1).
+ * Parity with umap-learn is not pinned.  fp64, every product and sum rounded separately, no floating-point atomics: every
+ * result is a function of the arguments alone, bit for bit.
+ * sc_fuzzy_graph: after sc_knn_dense / sc_knn_dense_gram, on the lists (idx, d2)[n][k] they left on the device.  k counts
+ *   OTHER cells (umap's k is k + 1 and its list holds the cell itself at distance 0).  With d_ij = sqrt(d2_ij), j running
+ *   over row i's list in list order (ascending (d2, j)):
+ *   rho_i = the smallest d_ij > 0, 0 if there is none.  S_i = sum_j d_ij, a running sum from 0.
+ *   target = log2(k + 1) (the host's log2 of the double k + 1).
+ *   sigma_i: lo = 0, hi = inf, mid = 1; at most 64 times: psum = sum_j (t_ij > 0 ? exp(-(t_ij / mid)) : 1) with t_ij = d_ij -
+ *     rho_i, a running sum from 0; stop if |psum - target| < 1e-5; if psum > target: hi = mid, mid = (lo + hi) / 2; else
+ *     lo = mid and mid = mid * 2 while hi is inf, else mid = (lo + hi) / 2.  sigma_i = the last mid, then the floor: sigma_i =
+ *     max(sigma_i, 1e-3 * m_i) with m_i = S_i / (k + 1) if rho_i > 0, else the mean of all distances M = (sum_i S_i) / (n (k + 1)).
+ *     sum_i S_i runs in the order of the Lanczos dot products above: chunks of 1024 rows, inside a chunk element e = r * 64 +
+ *     lane, every lane adds its 16 values for r ascending from the first, the 64 lane sums meet in the adjacent-pair tree, a
+ *     short last chunk is padded with zeros, the chunk sums are added in chunk order from 0.
+ *   p_ij = (t_ij > 0 ? exp(-(t_ij / sigma_i)) : 1) for j in row i's list, 0 otherwise.
+ *   Edges = the symmetric union of the lists, the CSR pattern of sc_diffmap_graph byte for byte (rows sorted by column);
+ *   w_ij = (p_ij + p_ji) - p_ij * p_ji at both positions, which makes the weights bit-symmetric.  A weight can underflow to 0
+ *   only where t_ij > 745 sigma_i in the one direction that lists the edge.
+ *   Then the tail of sc_diffmap_graph on these weights (q, K', D, T, the components), so that sc_diffmap_graph_get,
+ *   sc_lanczos_begin, sc_louvain_resident_weights and sc_louvain_begin_resident follow as after sc_diffmap_graph.
+ *   rho_out[n], sigma_out[n] may be NULL.  No lists resident: SC_ERR_STATE.
+ * sc_umap_layout: epochs [e0, e1) of n_epochs on a symmetric canonical CSR (columns strictly ascending inside [0, n), w
+ *   finite and > 0, rows may be empty; the symmetry is the caller's to check), 1 <= n <= 2^31 - 1; indptr = indices = w =
+ *   NULL takes the graph resident on the device (sc_fuzzy_graph, sc_diffmap_graph*; n must be its size).  Y[n][C] row-major,
+ *   finite, in and out, C = 2 or 3; a, b, alpha0 finite > 0, gamma finite >= 0, 0 <= neg <= 16, n_epochs >= 1, 0 <= e0 <= e1
+ *   <= n_epochs.  Everything is checked on the host before the first HIP call.  A graph without entries leaves Y as it is.
+ *   w_max = the exact maximum of w.  r_t = w_t / w_max.  Stored entry t (its global CSR position) FIRES in epoch e iff
+ *   floor((e + 1) * r_t) > floor(e * r_t), e and e + 1 as doubles.
+ *   Epoch e: alpha = alpha0 * (1 - e / n_epochs) (the division first).  Every vertex i reads the positions Y_old of the
+ *   previous epoch only: cur = Y_old[i]; for every firing entry (i, j) of its row in stored order:
+ *     attract:  step(cur, Y_old[j], attract);
+ *     repel, q = 0 .. neg - 1:  o = Philox4x32-10(key = (seed low word, seed high word), counter = (t low word, t high word,
+ *       e, q >> 2)); s = (o[q & 3] * n) >> 32 (the 64-bit product); unless s == i: step(cur, Y_old[s], repel);
+ *   then Y_new[i] = cur.  step(cur, y, kind): dlt_c = cur_c - y_c; d2 = dlt_0 * dlt_0, then d2 = d2 + dlt_c * dlt_c for c = 1 ..;
+ *     nothing happens unless d2 > 0; pb = pow(d2, b); den = a * pb + 1; coef = (((-2 * a) * b) * (pb / d2)) / den to attract,
+ *     ((2 * gamma) * b) / ((0.001 + d2) * den) to repel; per coordinate g = coef * dlt_c clipped to [-4, 4], cur_c = cur_c +
+ *     alpha * g.  One pow per interaction: d2^(b - 1) is pb / d2.
+ *   Two differences from umap-learn's optimize_layout_euclidean, on purpose: (1) reads come from the previous epoch's
+ *   positions, not from positions other threads are writing (no race, no atomic, no dependence on the schedule); the move
+ *   of an edge's tail is made by the mirrored entry (j, i), which has the same weight and fires in the same epochs; (2) a
+ *   vertex therefore gets 1 attraction per firing and exactly neg negatives, 1 : neg against umap-learn's 2 : neg.
+ *   A call with [e0, e1) followed by one with [e1, e2) gives the bytes of one call with [e0, e2). */
+int sc_fuzzy_graph(sc_ctx *ctx, double *rho_out, double *sigma_out, int64_t *n_edges_out, int64_t *n_components_out);
+int sc_umap_layout(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const double *w, int64_t n, double *Y, int32_t C,
+                   double a, double b, double gamma, double alpha0, int32_t neg, int32_t n_epochs, uint64_t seed, int32_t e0,
+                   int32_t e1);
 
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across

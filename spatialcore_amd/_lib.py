@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p
 from typing import Optional, Tuple
 
 import numpy as np
@@ -33,6 +33,7 @@ K_ANNOT_SETUP, K_ANNOT_ROWS, K_ANNOT_GRAD, K_ANNOT_LINE, K_ANNOT_PREDICT, K_ANNO
 K_PCA_SETUP, K_PCA_GRAM, K_PCA_PROJECT = 36, 37, 38
 K_LOUVAIN_MOVE, K_LOUVAIN_LEVEL = 39, 40
 K_NEIGHBORS_GRAM = 41
+K_UMAP_GRAPH, K_UMAP_LAYOUT = 42, 43
 ANNOT_MODES = {"counts": 0, "log1p": 1, "log1p_renorm": 2}   # sc_annot_*'s input states
 NMF_LOSSES = {"frobenius": 2, "kullback-leibler": 1}   # sc_nmf_fit's codes (sklearn's beta)
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
@@ -131,6 +132,9 @@ SYMBOLS = {
     "sc_diffmap_graph": [_P, _P, POINTER(c_int64), POINTER(c_int64)],
     "sc_diffmap_graph_csr": [_P, _P, _P, _P, c_int64, POINTER(c_int64)],
     "sc_diffmap_graph_get": [_P, _P, _P, _P, _P],
+    "sc_fuzzy_graph": [_P, _P, _P, POINTER(c_int64), POINTER(c_int64)],
+    "sc_umap_layout": [_P, _P, _P, _P, c_int64, _P, c_int32, c_double, c_double, c_double, c_double, c_int32, c_int32, c_uint64,
+                       c_int32, c_int32],
     "sc_lanczos_begin": [_P, _P, c_int64],
     "sc_lanczos_run": [_P, c_int32, _P, _P, POINTER(c_int64)],
     "sc_lanczos_ritz": [_P, _P, c_int64, c_int32, _P, _P, _P],
@@ -1174,6 +1178,36 @@ class Context:
         _check(self._lib.sc_diffmap_graph(self._h, _ptr(s2), byref(ne), byref(nc)))
         self._diff_nnz = ne.value
         return {"s2": s2, "n_edges": ne.value, "n_components": nc.value}
+
+    def fuzzy_graph(self) -> dict:
+        """sc_fuzzy_graph on the lists of the last ``knn_dense``: UMAP's fuzzy simplicial set becomes the resident graph.
+        ``rho`` (first non-zero distances), ``sigma`` (bandwidths), ``n_edges``, ``n_components``."""
+        rho = np.empty(self._diff_n, dtype=np.float64)
+        sigma = np.empty(self._diff_n, dtype=np.float64)
+        ne, nc = c_int64(0), c_int64(0)
+        _check(self._lib.sc_fuzzy_graph(self._h, _ptr(rho), _ptr(sigma), byref(ne), byref(nc)))
+        self._diff_nnz = ne.value
+        return {"rho": rho, "sigma": sigma, "n_edges": ne.value, "n_components": nc.value}
+
+    def umap_layout(self, graph, Y, a: float, b: float, gamma: float, alpha0: float, neg: int, n_epochs: int, seed: int,
+                    e0: int = 0, e1: Optional[int] = None) -> np.ndarray:
+        """sc_umap_layout: epochs [e0, e1) (default: all) of the deterministic layout on ``graph`` = (indptr, indices, w)
+        of a symmetric canonical CSR, or None for the graph resident on the device.  ``Y`` (n, 2 or 3) is the start;
+        returns the new positions (float64), ``Y`` itself is not written."""
+        Y = np.array(Y, dtype=np.float64, order="C", copy=True)
+        if Y.ndim != 2:
+            raise ValueError(f"umap_layout: positions must have shape (n, components), got {Y.shape}")
+        n = Y.shape[0]
+        if graph is None:
+            indptr = indices = w = None
+        else:
+            indptr, indices, w = _c(graph[0], np.int64), _c(graph[1], np.int32), _c(graph[2], np.float64)
+            if indptr.size != n + 1 or indices.size != w.size or indptr[-1] != w.size:
+                raise ValueError("umap_layout: indptr, indices and values do not describe one CSR matrix of the positions' rows")
+        _check(self._lib.sc_umap_layout(self._h, _ptr(indptr), _ptr(indices), _ptr(w), n, _ptr(Y), int(Y.shape[1]), float(a),
+                                        float(b), float(gamma), float(alpha0), int(neg), int(n_epochs),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(e0), int(n_epochs if e1 is None else e1)))
+        return Y
 
     def diffmap_graph_csr(self, indptr, indices, w) -> int:
         """sc_diffmap_graph_csr: a caller's symmetric kernel matrix (canonical CSR) becomes the resident graph; returns

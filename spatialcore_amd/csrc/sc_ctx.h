@@ -197,11 +197,14 @@ struct sc_ctx {
         DBuf s2, keys, keys2, pay, pay2, cnt, off;   // local scales; (row << 32 | column) keys, the sort's payload, first-of-run flags and offsets
         DBuf indptr, indices, w, T, q, parent, flag;   // CSR (rows sorted by column): kernel weights, transition matrix; row sums; union-find
         DBuf gnorm, gkept, gcnt, glo, grows;    // sc_knn_dense_gram: row norms, kept candidates [n][L], their counts, the L-th keys, [count | uncertified rows]
+        DBuf rho, sigma, dsum;                  // sc_fuzzy_graph: first non-zero distance, bandwidth, [row sums of the distances | chunk sums | their total]
+        DBuf lip, lix, lw, ly0, ly1, lmax;      // sc_umap_layout: a caller's CSR, the two position buffers, the bits of w_max
         DBuf V, wv, part, coef, ab, Y, S, res;   // basis [max_basis + 1][n], work vector, chunk partials, coefficients, alpha | beta, Ritz vectors, their coefficients, residuals
         std::vector<DBuf *> bufs()
         {
             return {&X, &raw, &idx, &d2, &pidx, &pd2, &s2, &keys, &keys2, &pay, &pay2, &cnt, &off, &indptr, &indices, &w, &T, &q,
-                    &parent, &flag, &V, &wv, &part, &coef, &ab, &Y, &S, &res, &gnorm, &gkept, &gcnt, &glo, &grows};
+                    &parent, &flag, &V, &wv, &part, &coef, &ab, &Y, &S, &res, &gnorm, &gkept, &gcnt, &glo, &grows,
+                    &rho, &sigma, &dsum, &lip, &lix, &lw, &ly0, &ly1, &lmax};
         }
     } df;
     // ---- annotation (sc_annotate.hip): the training problem kept on the device between sc_annot_train_begin and _end ----

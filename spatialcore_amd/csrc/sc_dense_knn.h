@@ -1,6 +1,8 @@
 // What the two exact searches in d dimensions share (sc_diffusion.hip: sc_knn_dense, the direct kernels; sc_neighbors.hip:
 // sc_knn_dense_gram, the certified Gram-form filter): the limits, the widening of the caller's rows, the direct-form
 // squared distance whose bits every neighbour list of the project is pinned to, the finite check and the list write-out.
+// And what the two graphs on those lists share (sc_diffusion.hip: sc_diffmap_graph; sc_umap.hip: sc_fuzzy_graph): the
+// symmetric union as a CSR pattern and the tail that makes a weighted graph the resident one.
 #pragma once
 
 #include <cmath>
@@ -68,3 +70,21 @@ int df_require_finite(const char *who, const T *X, int64_t count)
                    "%s: feature value %lld is not finite and below 2^500 in magnitude", who, (long long)p);
     return SC_OK;
 }
+
+// the row of stored entry e: the last i with indptr[i] <= e (no row is empty)
+__device__ __forceinline__ int64_t df_row_of(const int64_t *__restrict__ indptr, int64_t n, int64_t e)
+{
+    int64_t lo = 0, hi = n;   // indptr[lo] <= e < indptr[hi]
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (indptr[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// sc_diffusion.hip.  df_build_union: the symmetric union of the resident lists as indptr / indices on the device (rows
+// sorted by column), *nnz_out = its stored entries.  df_finish_graph: on the resident CSR with its weights w in place: row
+// sums, density, transition matrix and the connected components; marks the graph valid for sc_diffmap_graph_get,
+// sc_lanczos_begin and sc_louvain_begin_resident.
+int df_build_union(sc_ctx *c, long long *nnz_out);
+int df_finish_graph(sc_ctx *c, int64_t *n_components_out);

@@ -203,16 +203,6 @@ __global__ __launch_bounds__(256) void k_df_indptr(const u64 *__restrict__ keys,
     }
     indptr[i] = off[lo];
 }
-// the row of stored entry e: the last i with indptr[i] <= e (no row is empty)
-__device__ __forceinline__ int64_t df_row_of(const int64_t *__restrict__ indptr, int64_t n, int64_t e)
-{
-    int64_t lo = 0, hi = n;   // indptr[lo] <= e < indptr[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (indptr[mid] <= e) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 // w_e = sqrt(2 sqrt(s2_i) sqrt(s2_j) / (s2_i + s2_j)) exp(-d2(i, j) / (s2_i + s2_j)), d2 as the search adds it
 __global__ __launch_bounds__(256) void k_df_weights(const int64_t *__restrict__ indptr, const int32_t *__restrict__ indices,
                                                     int64_t n, int64_t nnz, const double *__restrict__ X, int dp,
@@ -378,6 +368,37 @@ int df_dots(sc_ctx *c, const double *V, int64_t nvec, const double *w, double *c
     return SC_OK;
 }
 
+}  // namespace
+
+// the symmetric union of the resident lists as a CSR pattern (rows sorted by column): both directions of every entry as
+// keys, one device-wide sort, the first of every run kept.  Leaves indptr / indices on the device; *nnz_out = stored entries.
+int df_build_union(sc_ctx *c, long long *nnz_out)
+{
+    sc_ctx::Diffusion &f = c->df;
+    hipStream_t s = c->stream;
+    const int64_t n = f.n, nk = n * f.k, total = 2 * nk;
+    SC_TRY(f.keys.ensure(sizeof(u64) * (size_t)total, &c->mem));
+    SC_TRY(f.keys2.ensure(sizeof(u64) * (size_t)total, &c->mem));
+    SC_TRY(f.pay.ensure(sizeof(uint32_t) * (size_t)total, &c->mem));
+    SC_TRY(f.pay2.ensure(sizeof(uint32_t) * (size_t)total, &c->mem));
+    SC_TRY(f.cnt.ensure(sizeof(long long) * (size_t)(total + 1), &c->mem));
+    SC_TRY(f.off.ensure(sizeof(long long) * (size_t)(total + 1), &c->mem));
+    SC_TRY(f.indptr.ensure(sizeof(int64_t) * (size_t)(n + 1), &c->mem));
+    SC_TRY(f.indices.ensure(sizeof(int32_t) * (size_t)total, &c->mem));
+    const dim3 tpb(256);
+    hipLaunchKernelGGL(k_df_keys, dim3((unsigned)ceil_div64(nk, 256)), tpb, 0, s, f.idx.as<int32_t>(), nk, f.k, f.keys.as<u64>(),
+                       f.pay.as<uint32_t>());
+    SC_TRY((rs_sort<u64, uint32_t>(c, f.keys.as<u64>(), f.keys2.as<u64>(), f.pay.as<uint32_t>(), f.pay2.as<uint32_t>(), total,
+                                    32 + bits_for(n))));
+    hipLaunchKernelGGL(k_df_first, dim3((unsigned)ceil_div64(total + 1, 256)), tpb, 0, s, f.keys2.as<u64>(), total, f.cnt.as<long long>());
+    SC_TRY(sc_counts_to_offsets(c, f.cnt.as<long long>(), f.off.as<long long>(), total, nnz_out));
+    hipLaunchKernelGGL(k_df_compact, dim3((unsigned)ceil_div64(total, 256)), tpb, 0, s, f.keys2.as<u64>(), f.cnt.as<long long>(),
+                       f.off.as<long long>(), total, f.indices.as<int32_t>());
+    hipLaunchKernelGGL(k_df_indptr, dim3((unsigned)ceil_div64(n + 1, 256)), tpb, 0, s, f.keys2.as<u64>(), f.off.as<long long>(), total, n,
+                       f.indptr.as<int64_t>());
+    return SC_OK;
+}
+
 // steps 4 and 6 on the resident CSR (indptr, indices, w): q, D, T and the number of connected components
 int df_finish_graph(sc_ctx *c, int64_t *n_components_out)
 {
@@ -407,8 +428,6 @@ int df_finish_graph(sc_ctx *c, int64_t *n_components_out)
     f.lanczos_valid = false;
     return SC_OK;
 }
-
-}  // namespace
 
 extern "C" int sc_knn_dense(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t d, int32_t k, int32_t splits, int32_t *idx_out,
                             double *d2_out)
@@ -482,30 +501,13 @@ extern "C" int sc_diffmap_graph(sc_ctx *c, double *s2_out, int64_t *n_edges_out,
     const int64_t n = f.n, nk = n * f.k, total = 2 * nk;
     f.graph_valid = f.lanczos_valid = false;
     SC_TRY(f.s2.ensure(sizeof(double) * (size_t)n, &c->mem));
-    SC_TRY(f.keys.ensure(sizeof(u64) * (size_t)total, &c->mem));
-    SC_TRY(f.keys2.ensure(sizeof(u64) * (size_t)total, &c->mem));
-    SC_TRY(f.pay.ensure(sizeof(uint32_t) * (size_t)total, &c->mem));
-    SC_TRY(f.pay2.ensure(sizeof(uint32_t) * (size_t)total, &c->mem));
-    SC_TRY(f.cnt.ensure(sizeof(long long) * (size_t)(total + 1), &c->mem));
-    SC_TRY(f.off.ensure(sizeof(long long) * (size_t)(total + 1), &c->mem));
-    SC_TRY(f.indptr.ensure(sizeof(int64_t) * (size_t)(n + 1), &c->mem));
-    SC_TRY(f.indices.ensure(sizeof(int32_t) * (size_t)total, &c->mem));
     std::vector<double> s2_host((size_t)n);
     long long nnz = 0;
     const dim3 rows((unsigned)ceil_div64(n, 256)), tpb(256);
     {
         KernelTimerScope ts(c, SC_K_DIFF_GRAPH);
         hipLaunchKernelGGL(k_df_scale2, rows, tpb, 0, s, f.d2.as<double>(), n, f.k, f.s2.as<double>());
-        hipLaunchKernelGGL(k_df_keys, dim3((unsigned)ceil_div64(nk, 256)), tpb, 0, s, f.idx.as<int32_t>(), nk, f.k, f.keys.as<u64>(),
-                           f.pay.as<uint32_t>());
-        SC_TRY((rs_sort<u64, uint32_t>(c, f.keys.as<u64>(), f.keys2.as<u64>(), f.pay.as<uint32_t>(), f.pay2.as<uint32_t>(), total,
-                                        32 + bits_for(n))));
-        hipLaunchKernelGGL(k_df_first, dim3((unsigned)ceil_div64(total + 1, 256)), tpb, 0, s, f.keys2.as<u64>(), total, f.cnt.as<long long>());
-        SC_TRY(sc_counts_to_offsets(c, f.cnt.as<long long>(), f.off.as<long long>(), total, &nnz));
-        hipLaunchKernelGGL(k_df_compact, dim3((unsigned)ceil_div64(total, 256)), tpb, 0, s, f.keys2.as<u64>(), f.cnt.as<long long>(),
-                           f.off.as<long long>(), total, f.indices.as<int32_t>());
-        hipLaunchKernelGGL(k_df_indptr, dim3((unsigned)ceil_div64(n + 1, 256)), tpb, 0, s, f.keys2.as<u64>(), f.off.as<long long>(), total, n,
-                           f.indptr.as<int64_t>());
+        SC_TRY(df_build_union(c, &nnz));
     }
     SC_HIP(hipGetLastError());
     SC_HIP(hipMemcpyAsync(s2_host.data(), f.s2.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));

@@ -1,8 +1,9 @@
 """neighbors: the exact nearest-neighbour graph of a representation as a first-class object.
 
 The search (sc_knn_dense_gram: a Gram-form filter on the fp64 matrix cores with a proven error bound, an exact re-rank
-and an exact fallback -- the lists of sc_knn_dense bit for bit) and the kernel matrix (sc_diffmap_graph) run in HIP; the
-host checks the arguments and assembles the two sparse matrices.  There is no CPU fallback."""
+and an exact fallback -- the lists of sc_knn_dense bit for bit) and the connectivities (sc_diffmap_graph, or sc_fuzzy_graph
+for ``method="umap"``) run in HIP; the host checks the arguments and assembles the two sparse matrices.  There is no CPU
+fallback."""
 
 from __future__ import annotations
 
@@ -18,9 +19,11 @@ from spatialcore_amd.diffusion.maps import K_MAX, K_MIN, _SUPPORTED, _check_key,
 
 logger = get_logger("neighbors")
 
+METHODS = ("gauss", "umap")
 
-def neighbors(adata, n_neighbors: int = 15, use_rep: str = "X_pca", *, key_added: Optional[str] = None, copy: bool = False,
-              device: int = 0):
+
+def neighbors(adata, n_neighbors: int = 15, use_rep: str = "X_pca", *, method: str = "gauss", key_added: Optional[str] = None,
+              copy: bool = False, device: int = 0):
     """Exact ``n_neighbors`` nearest neighbours of every cell in ``adata.obsm[use_rep]`` (Euclidean), on the GPU, stored
     the way scanpy's ``pp.neighbors`` stores its graph so that ``louvain(graph=...)`` and ``diffusion_map(graph=...)``
     share one search.
@@ -34,15 +37,22 @@ def neighbors(adata, n_neighbors: int = 15, use_rep: str = "X_pca", *, key_added
     Writes ``obsp["distances"]`` (float64 CSR, exactly ``n_neighbors`` stored entries per row, columns sorted, values
     ``sqrt(d2)``; a zero distance is an explicit stored entry), ``obsp["connectivities"]`` (the symmetric union of the
     lists with ``diffusion_map``'s kernel weights: the matrix ``louvain(graph=None)`` clusters) and ``uns["neighbors"]`` =
-    {``connectivities_key``, ``distances_key``, ``params`` (``n_neighbors``, ``method`` = "gauss", ``metric`` =
+    {``connectivities_key``, ``distances_key``, ``params`` (``n_neighbors``, ``method``, ``metric`` =
     "euclidean", ``use_rep``, ``n_features``), ``search`` (``path``, ``list_length``, ``rows_certified``,
     ``rows_fallback``: how the search went, not what it found)}; with ``key_added="x"`` the keys are
     ``obsp["x_distances"]``, ``obsp["x_connectivities"]`` and ``uns["x"]``.  Appends the usual entry to
     ``uns["spatialcore_metadata"]``.  A cell whose local scale is zero (more than half of its neighbours are exact
-    duplicates of it) raises ``ValueError`` and nothing is written.  Parity with scanpy's connectivities (UMAP's fuzzy
-    simplicial set by default) is not pinned; any metric but Euclidean is out of scope."""
+    duplicates of it) raises ``ValueError`` and nothing is written.
+
+    ``method="umap"`` stores UMAP's fuzzy simplicial set instead (sc_fuzzy_graph: ``smooth_knn_dist``, the membership
+    strengths and the probabilistic union ``p_ij + p_ji - p_ij p_ji`` with umap-learn's defaults, on the same union of the
+    lists): the graph scanpy's ``pp.neighbors`` stores by default.  ``params["method"]`` is then "umap"; rho and sigma are
+    not stored, and duplicates are legal (their memberships are 1).  It is restated from the published algorithm; parity
+    with umap-learn's or scanpy's values is not pinned.  Any metric but Euclidean is out of scope."""
     if key_added is not None:
         _check_key("key_added", key_added)
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
     n = int(adata.n_obs)
     if not _is_int(n_neighbors) or not K_MIN <= n_neighbors <= K_MAX or n_neighbors >= n:
         raise ValueError(f"n_neighbors must be an integer in {K_MIN}..{K_MAX} and below the {n} cells, got "
@@ -53,7 +63,10 @@ def neighbors(adata, n_neighbors: int = 15, use_rep: str = "X_pca", *, key_added
     ctx = _lib.default_context(device)
     logger.info(f"neighbors: {n:,} cells x {R.shape[1]} features, {k} neighbours")
     idx, d2, search = ctx.knn_dense_gram(R, k)
-    ctx.diffmap_graph()          # a zero local scale raises here, before anything is written
+    if method == "umap":
+        ctx.fuzzy_graph()
+    else:
+        ctx.diffmap_graph()      # a zero local scale raises here, before anything is written
     indptr, indices, w = ctx.diffmap_graph_get()
     logger.info(f"neighbors: path {search['path']}, {search['rows_fallback']:,} rows through the exact fallback, "
                 f"{indices.size:,} stored connectivities")
@@ -68,7 +81,7 @@ def neighbors(adata, n_neighbors: int = 15, use_rep: str = "X_pca", *, key_added
     uns_key = "neighbors" if key_added is None else key_added
     dist_key = "distances" if key_added is None else key_added + "_distances"
     conn_key = "connectivities" if key_added is None else key_added + "_connectivities"
-    params = {"n_neighbors": k, "method": "gauss", "metric": "euclidean", "use_rep": use_rep, "n_features": int(R.shape[1])}
+    params = {"n_neighbors": k, "method": method, "metric": "euclidean", "use_rep": use_rep, "n_features": int(R.shape[1])}
     adata.obsp[dist_key] = distances
     adata.obsp[conn_key] = connectivities
     adata.uns[uns_key] = {"connectivities_key": conn_key, "distances_key": dist_key, "params": params, "search": search}
