@@ -18,7 +18,7 @@ from scipy import sparse
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from spatialcore_amd import SimpleAnnData, _lib  # noqa: E402
+from spatialcore_amd import SimpleAnnData, _lib, _sparse_input  # noqa: E402
 from spatialcore_amd.nmf import factorize, fit_nmf  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
@@ -59,7 +59,7 @@ def device(loss):
     fit_nmf(SimpleAnnData(X[:4096], var_names=names), K, beta_loss=loss, max_iter=2, tol=0.0)     # code objects, allocations
     wall, _ = timed(fit_nmf, ad, K, beta_loss=loss, max_iter=ITERS, tol=0.0, random_state=0)
     say(f"{loss}: public call {wall:.2f} s")
-    t_csr, (Xc, _) = timed(factorize._canonical_csr, X, np.arange(G), G)
+    t_csr, (Xc, _) = timed(_sparse_input.canonical_csr, X, np.arange(G), G, negative="negative", all_zero="all zero")   # as fit_nmf asks
     t_init, (W0, H0) = timed(factorize.random_init, factorize._scale(Xc, K), n, G, K, 0)
     ctx.reset_timers()
     t_entry, res = timed(ctx.nmf_fit, Xc.indptr, Xc.indices, Xc.data, G, W0, H0, loss, True, ITERS, 0.0)

@@ -9,19 +9,7 @@ from typing import Tuple
 import numpy as np
 from scipy import sparse
 
-
-def _as_csr(X):
-    if sparse.issparse(X):
-        if X.ndim != 2:
-            raise ValueError("the expression matrix must be 2-D")
-        Xc = X.tocsr()
-        return Xc.copy() if Xc is X else Xc
-    A = np.asarray(X)
-    if A.ndim != 2:
-        raise ValueError("the expression matrix must be 2-D")
-    if not (np.issubdtype(A.dtype, np.number) or A.dtype == bool):
-        raise ValueError(f"the expression matrix must be numeric, got {A.dtype}")
-    return sparse.csr_matrix(A)
+from spatialcore_amd._sparse_input import as_csr, float_storage
 
 
 def matrix_state(Xc) -> str:
@@ -59,15 +47,12 @@ def prepare(X, cols: np.ndarray) -> Tuple[sparse.csr_matrix, str]:
     """The matrix restricted to the columns ``cols`` (ascending) as a canonical CSR without stored zeros (float32 stays
     float32, everything else becomes float64) and the library's mode: ``"counts"``, ``"log1p"`` (taken as it is) or
     ``"log1p_renorm"`` (the gene set shrank: expm1, renormalise, log1p, as the reference's annotate.py:464-514)."""
-    Xc = _as_csr(X)
+    Xc = as_csr(X)
     state = matrix_state(Xc)
     shrunk = cols.size != Xc.shape[1]
     if shrunk:
         Xc = Xc[:, cols]
-    dtype = np.float32 if Xc.dtype == np.float32 else np.float64
-    if Xc.dtype != dtype:
-        Xc = Xc.astype(dtype)
-    Xc.sum_duplicates()
+    Xc = float_storage(Xc)
     Xc.eliminate_zeros()
     Xc.sort_indices()
     if Xc.shape[0] > 2**31 - 1 or Xc.nnz > 2**32 - 1:

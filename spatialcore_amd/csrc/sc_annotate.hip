@@ -23,7 +23,9 @@
 #include <vector>
 
 #include "sc_colsort.h"
+#include "sc_csr_input.h"
 #include "sc_ctx.h"
+#include "sc_lane_group.h"
 
 namespace {
 
@@ -34,11 +36,6 @@ constexpr double AN_CLIP = 10.0;      // CellTypist clips the standardised value
 enum { AN_COUNTS = 0, AN_LOG1P = 1, AN_LOG1P_RENORM = 2 };
 enum { AN_OUT_ROWS = 0, AN_OUT_PREDICT = 1 };
 
-__device__ __forceinline__ double an_group_sum(double v, int tp)
-{
-    for (int h = 1; h < tp; h <<= 1) v = v + __shfl_xor(v, h, 64);
-    return v;
-}
 __device__ __forceinline__ double an_group_min(double v, int tp)
 {
     for (int h = 1; h < tp; h <<= 1) {
@@ -95,13 +92,10 @@ __global__ __launch_bounds__(256) void k_an_colstat_chunks(const int64_t *__rest
 {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= chunks) return;
-    const int32_t g = cgene[c];
-    const int64_t p0 = colptr[g] + (c - cptr[g]) * COL_CHUNK;
-    const int64_t pe = colptr[g + 1];
-    const int64_t p1 = p0 + COL_CHUNK < pe ? p0 + COL_CHUNK : pe;
-    const double m = pass ? mean[g] : 0.0;
+    const ColChunk ch = col_chunk(colptr, cptr, cgene, c);
+    const double m = pass ? mean[ch.g] : 0.0;
     double s = 0.0;
-    for (int64_t p = p0; p < p1; ++p) {
+    for (int64_t p = ch.p0; p < ch.p1; ++p) {
         const double d = cval[p] - m;
         s = pass ? s + d * d : s + d;
     }
@@ -169,7 +163,7 @@ __device__ __forceinline__ void an_confidences(const double (&f)[NB], int T, int
 #pragma unroll
     for (int b = 0; b < NB; ++b)
         if (b * 64 + l < T) sum = sum + f[b];
-    const double mean = an_group_sum(sum, tp) / dT;
+    const double mean = group_sum(sum, tp) / dT;
     double ss = 0.0, se = 0.0, mn = INFINITY;
 #pragma unroll
     for (int b = 0; b < NB; ++b)
@@ -179,9 +173,9 @@ __device__ __forceinline__ void an_confidences(const double (&f)[NB], int T, int
             se = se + exp(f[b] - best);
             mn = f[b] < mn ? f[b] : mn;
         }
-    double sd = sqrt(an_group_sum(ss, tp) / dT);
+    double sd = sqrt(group_sum(ss, tp) / dT);
     if (sd < 1e-10) sd = 1.0;
-    se = an_group_sum(se, tp);
+    se = group_sum(se, tp);
     mn = an_group_min(mn, tp);
     double range = best - mn;
     if (range < 1e-10) range = 1.0;
@@ -191,9 +185,29 @@ __device__ __forceinline__ void an_confidences(const double (&f)[NB], int T, int
     out[3] = (best - mn) / range;
 }
 
-// ---- the row pass ------------------------------------------------------------------------------------------------------
-// One group per cell: acc_t = base_t, then + d_ig table[g][t] over the row's stored entries in index order.  The group
-// fetches tp entries at once (lane j holds entry base + j) and hands them round; the entries are still added one by one.
+// ---- the sparse passes --------------------------------------------------------------------------------------------------
+// A lane's part of a row of a [rows][T] table: the values of its classes 64 b + l (0.0 past T), and their accumulation
+template <int NB>
+struct AnRow {
+    double v[NB];
+};
+template <int NB>
+__device__ __forceinline__ AnRow<NB> an_row_of(const double *__restrict__ table, int64_t row, int T, int l)
+{
+    AnRow<NB> r;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) r.v[b] = b * 64 + l < T ? table[row * T + b * 64 + l] : 0.0;
+    return r;
+}
+template <int NB>
+__device__ __forceinline__ void an_row_add(double (&acc)[NB], double x, const AnRow<NB> &r)
+{
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[b] = acc[b] + x * r.v[b];
+}
+
+// Row pass, one group per cell: acc_t = base_t, then + d_ig table[g][t] over the row's stored entries in index order, four
+// table rows in flight (lane_group_walk).
 // AN_OUT_ROWS: out64[i][t] = acc_t.  AN_OUT_PREDICT: label = first argmax of the fp64 scores, conf[0] = expit(max),
 // out32[i][t] = the float32 score (may be NULL), conf[1 .. 4] = the four transforms of the float32-rounded row.
 template <int NB, int OUT>
@@ -209,35 +223,8 @@ __global__ __launch_bounds__(256) void k_an_rows(const int64_t *__restrict__ ind
     double acc[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) acc[b] = b * 64 + l < T ? base[b * 64 + l] : 0.0;
-    const int64_t p1 = indptr[i + 1];
-    for (int64_t pb = indptr[i]; pb < p1; pb += tp) {
-        const int cnt = (int)(p1 - pb < tp ? p1 - pb : tp);
-        const int32_t g_mine = l < cnt ? indices[pb + l] : 0;
-        const double x_mine = l < cnt ? dval[pb + l] : 0.0;
-        // four table rows in flight; the entries are still added one by one in index order
-        int j = 0;
-        for (; j + 4 <= cnt; j += 4) {
-            double w[4][NB];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t g = __shfl(g_mine, j + u, tp);
-#pragma unroll
-                for (int b = 0; b < NB; ++b) w[u][b] = b * 64 + l < T ? table[g * T + b * 64 + l] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const double x = __shfl(x_mine, j + u, tp);
-#pragma unroll
-                for (int b = 0; b < NB; ++b) acc[b] = acc[b] + x * w[u][b];
-            }
-        }
-        for (; j < cnt; ++j) {
-            const int64_t g = __shfl(g_mine, j, tp);
-            const double x = __shfl(x_mine, j, tp);
-#pragma unroll
-            for (int b = 0; b < NB; ++b) acc[b] = acc[b] + x * (b * 64 + l < T ? table[g * T + b * 64 + l] : 0.0);
-        }
-    }
+    lane_group_walk(indices, dval, indptr[i], indptr[i + 1], tp, l, [&](int32_t g) { return an_row_of<NB>(table, g, T, l); },
+                    [&](double x, const AnRow<NB> &w) { an_row_add<NB>(acc, x, w); });
     if (OUT == AN_OUT_ROWS) {
 #pragma unroll
         for (int b = 0; b < NB; ++b)
@@ -343,15 +330,6 @@ __global__ __launch_bounds__(256) void k_an_line(const double *__restrict__ S, c
     d1part[q] = d1;
     d2part[q] = d2;
 }
-// out[e] = part[chunk][e] added in chunk order
-__global__ __launch_bounds__(256) void k_an_chunk_add(const double *__restrict__ part, int64_t chunks, int P, double *__restrict__ out)
-{
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= P) return;
-    double s = 0.0;
-    for (int64_t c = 0; c < chunks; ++c) s = s + part[c * P + e];
-    out[e] = s;
-}
 __global__ __launch_bounds__(256) void k_an_step(double *__restrict__ S, const double *__restrict__ Dir, const double *__restrict__ alpha,
                                                  int64_t total, int T)
 {
@@ -369,41 +347,13 @@ __global__ __launch_bounds__(256) void k_an_gradcols(const int64_t *__restrict__
     const int t = threadIdx.x, grp = t / tp, l = t % tp;
     const int64_t c = (int64_t)blockIdx.x * (AN_TPB / tp) + grp;
     if (c >= chunks) return;   // the whole group leaves
-    const int32_t g = cgene[c];
-    const int64_t p0 = colptr[g] + (c - cptr[g]) * COL_CHUNK;
-    const int64_t pe = colptr[g + 1];
-    const int64_t p1 = p0 + COL_CHUNK < pe ? p0 + COL_CHUNK : pe;
+    const ColChunk ch = col_chunk(colptr, cptr, cgene, c);
     double acc[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) acc[b] = 0.0;
-    for (int64_t pb = p0; pb < p1; pb += tp) {
-        const int cnt = (int)(p1 - pb < tp ? p1 - pb : tp);
-        const int32_t i_mine = l < cnt ? crow[pb + l] : 0;
-        const double x_mine = l < cnt ? cval[pb + l] : 0.0;
-        // as the row pass: four rows of R in flight, added one by one in index order
-        int j = 0;
-        for (; j + 4 <= cnt; j += 4) {
-            double r[4][NB];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t i = __shfl(i_mine, j + u, tp);
-#pragma unroll
-                for (int b = 0; b < NB; ++b) r[u][b] = b * 64 + l < T ? R[i * T + b * 64 + l] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const double x = __shfl(x_mine, j + u, tp);
-#pragma unroll
-                for (int b = 0; b < NB; ++b) acc[b] = acc[b] + x * r[u][b];
-            }
-        }
-        for (; j < cnt; ++j) {
-            const int64_t i = __shfl(i_mine, j, tp);
-            const double x = __shfl(x_mine, j, tp);
-#pragma unroll
-            for (int b = 0; b < NB; ++b) acc[b] = acc[b] + x * (b * 64 + l < T ? R[i * T + b * 64 + l] : 0.0);
-        }
-    }
+    // as the row pass: four rows of R in flight
+    lane_group_walk(crow, cval, ch.p0, ch.p1, tp, l, [&](int32_t i) { return an_row_of<NB>(R, i, T, l); },
+                    [&](double x, const AnRow<NB> &r) { an_row_add<NB>(acc, x, r); });
 #pragma unroll
     for (int b = 0; b < NB; ++b)
         if (b * 64 + l < T) part[c * T + b * 64 + l] = acc[b];
@@ -424,31 +374,17 @@ __global__ __launch_bounds__(256) void k_an_gradfinish(const int64_t *__restrict
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
-struct AnnotData {   // the matrix on the device: CSR, the D values in row order, the scaler
-    DBuf indptr, indices, raw, val, mean, scale, z0, table, base;
+struct AnnotData {   // the matrix on the device (m.val: the D values in row order), the scaler
+    CsrDevice m;
+    DBuf mean, scale, z0, table, base;
     void release(int64_t *acct)
     {
-        for (DBuf *b : {&indptr, &indices, &raw, &val, &mean, &scale, &z0, &table, &base}) b->release(acct);
+        m.release(acct);
+        for (DBuf *b : {&mean, &scale, &z0, &table, &base}) b->release(acct);
     }
 };
 
-int an_lanes(int T)
-{
-    int tp = 2;
-    while (tp < T && tp < 64) tp <<= 1;
-    return tp;
-}
-
-template <class V>
-int an_check_values(const char *who, const V *data, int64_t nnz)
-{
-    for (int64_t p = 0; p < nnz; ++p) {
-        const double x = (double)data[p];
-        SC_REQUIRE(std::isfinite(x), SC_ERR_INVALID, "%s: stored value %lld is not finite", who, (long long)p);
-        SC_REQUIRE(x >= 0.0, SC_ERR_INVALID, "%s: stored value %lld is negative", who, (long long)p);
-    }
-    return SC_OK;
-}
+int an_lanes(int T) { return lanes_for(T, 2, 64); }
 
 // the envelope and the canonical CSR, on the host
 int an_check_matrix(const char *who, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
@@ -461,45 +397,30 @@ int an_check_matrix(const char *who, const int64_t *indptr, const int32_t *indic
     SC_REQUIRE(T >= 2 && T <= AN_TMAX, SC_ERR_INVALID, "%s: need 2 <= classes <= %d, got %d", who, AN_TMAX, T);
     SC_REQUIRE(mode == AN_COUNTS || mode == AN_LOG1P || mode == AN_LOG1P_RENORM, SC_ERR_INVALID,
                "%s: mode must be 0 (counts), 1 (log1p) or 2 (log1p, renormalise), got %d", who, mode);
-    SC_REQUIRE(indptr[0] == 0, SC_ERR_INVALID, "%s: indptr[0] must be 0", who);
-    for (int64_t i = 0; i < n; ++i)
-        SC_REQUIRE(indptr[i + 1] >= indptr[i], SC_ERR_INVALID, "%s: indptr decreases at row %lld", who, (long long)i);
-    const int64_t nnz = indptr[n];
+    int64_t nnz = 0;
+    SC_TRY(csr_check_offsets(who, indptr, n, &nnz));
     SC_REQUIRE(nnz >= min_nnz && nnz <= (int64_t)UINT32_MAX, SC_ERR_INVALID, "%s: need %lld <= stored entries <= 2^32 - 1, got %lld", who,
                (long long)min_nnz, (long long)nnz);
     SC_REQUIRE(nnz == 0 || (indices && data), SC_ERR_INVALID, "%s: null pointer", who);
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t p = indptr[i]; p < indptr[i + 1]; ++p)
-            SC_REQUIRE(indices[p] >= 0 && indices[p] < G && (p == indptr[i] || indices[p] > indices[p - 1]), SC_ERR_INVALID,
-                       "%s: row %lld is not canonical (columns must ascend strictly inside [0, n_genes))", who, (long long)i);
-    if (dtype == SC_F32) SC_TRY(an_check_values(who, (const float *)data, nnz));
-    else SC_TRY(an_check_values(who, (const double *)data, nnz));
+    SC_TRY(csr_check_columns(who, indptr, indices, n, G, "n_genes"));
+    SC_TRY(csr_check_values(who, data, dtype, nnz, true, ""));
     *nnz_out = nnz;
     return SC_OK;
 }
 
-// uploads the CSR and enqueues the normalisation into d.val
+// uploads the CSR and enqueues the normalisation into d.m.val
 int an_upload(sc_ctx *c, AnnotData &d, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
               int G, int mode, int64_t nnz)
 {
     hipStream_t s = c->stream;
-    const size_t es = dtype == SC_F32 ? sizeof(float) : sizeof(double);
-    SC_TRY(d.indptr.ensure(sizeof(int64_t) * (size_t)(n + 1), &c->mem));
-    SC_TRY(d.indices.ensure(sizeof(int32_t) * (size_t)(nnz ? nnz : 1), &c->mem));
-    SC_TRY(d.raw.ensure(es * (size_t)(nnz ? nnz : 1), &c->mem));
-    SC_TRY(d.val.ensure(sizeof(double) * (size_t)(nnz ? nnz : 1), &c->mem));
+    SC_TRY(d.m.upload(c, indptr, indices, data, dtype, n, nnz));
     SC_TRY(d.mean.ensure(sizeof(double) * (size_t)G, &c->mem));
     SC_TRY(d.scale.ensure(sizeof(double) * (size_t)G, &c->mem));
     SC_TRY(d.z0.ensure(sizeof(double) * (size_t)G, &c->mem));
-    SC_HIP(hipMemcpyAsync(d.indptr.p, indptr, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, s));
-    if (nnz) {
-        SC_HIP(hipMemcpyAsync(d.indices.p, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, s));
-        SC_HIP(hipMemcpyAsync(d.raw.p, data, es * (size_t)nnz, hipMemcpyHostToDevice, s));
-    }
     KernelTimerScope ts(c, SC_K_ANNOT_SETUP);
     const dim3 per_row((unsigned)ceil_div64(n, 256)), tpb(256);
-    if (dtype == SC_F32) hipLaunchKernelGGL(k_an_normalise<float>, per_row, tpb, 0, s, d.indptr.as<int64_t>(), d.raw.as<float>(), n, mode, d.val.as<double>());
-    else hipLaunchKernelGGL(k_an_normalise<double>, per_row, tpb, 0, s, d.indptr.as<int64_t>(), d.raw.as<double>(), n, mode, d.val.as<double>());
+    if (dtype == SC_F32) hipLaunchKernelGGL(k_an_normalise<float>, per_row, tpb, 0, s, d.m.indptr.as<int64_t>(), d.m.raw.as<float>(), n, mode, d.m.val.as<double>());
+    else hipLaunchKernelGGL(k_an_normalise<double>, per_row, tpb, 0, s, d.m.indptr.as<int64_t>(), d.m.raw.as<double>(), n, mode, d.m.val.as<double>());
     return SC_OK;
 }
 
@@ -531,9 +452,9 @@ void an_launch_rows(sc_ctx *c, const AnnotData &d, int64_t n, int T, double *out
 {
     const int tp = an_lanes(T), nb = (T + 63) / 64;
     const dim3 grid((unsigned)ceil_div64(n, AN_TPB / tp)), block(AN_TPB);
-    const int64_t *ip = d.indptr.as<int64_t>();
-    const int32_t *ix = d.indices.as<int32_t>();
-    const double *v = d.val.as<double>(), *tab = d.table.as<double>(), *base = d.base.as<double>();
+    const int64_t *ip = d.m.indptr.as<int64_t>();
+    const int32_t *ix = d.m.indices.as<int32_t>();
+    const double *v = d.m.val.as<double>(), *tab = d.table.as<double>(), *base = d.base.as<double>();
     switch (nb) {
     case 1: hipLaunchKernelGGL((k_an_rows<1, OUT>), grid, block, 0, c->stream, ip, ix, v, n, T, tp, tab, base, out64, out32, label, conf); break;
     case 2: hipLaunchKernelGGL((k_an_rows<2, OUT>), grid, block, 0, c->stream, ip, ix, v, n, T, tp, tab, base, out64, out32, label, conf); break;
@@ -574,7 +495,7 @@ struct AnnotTrain {
     AnnotData d;
     ColSort cs;
     DBuf labels, sw, S, Dir, R, cellpart, cellsum, colpart, grad, alpha;
-    int64_t n = 0, nnz = 0, cell_chunks = 0;
+    int64_t cell_chunks = 0;   // the cells and the stored entries: d.m.n, d.m.nnz
     int G = 0, T = 0;
     bool have_scores = false, have_dir = false;
     std::vector<double> z0, tab, base;
@@ -628,8 +549,8 @@ extern "C" int sc_annot_predict(sc_ctx *c, const int64_t *indptr, const int32_t 
     SC_TRY(conf.ensure(sizeof(double) * (size_t)n * 5, &c->mem));
     if (nnz) {
         KernelTimerScope ts(c, SC_K_ANNOT_SETUP);
-        hipLaunchKernelGGL(k_an_dvals<int32_t>, dim3((unsigned)ceil_div64(nnz, 256)), dim3(256), 0, s, d.indices.as<int32_t>(), nnz,
-                           d.mean.as<double>(), d.scale.as<double>(), d.z0.as<double>(), d.val.as<double>());
+        hipLaunchKernelGGL(k_an_dvals<int32_t>, dim3((unsigned)ceil_div64(nnz, 256)), dim3(256), 0, s, d.m.indices.as<int32_t>(), nnz,
+                           d.mean.as<double>(), d.scale.as<double>(), d.z0.as<double>(), d.m.val.as<double>());
     }
     {
         KernelTimerScope ts(c, SC_K_ANNOT_PREDICT);
@@ -692,7 +613,7 @@ extern "C" int sc_annot_train_begin(sc_ctx *c, const int64_t *indptr, const int3
     AnnotTrain &a = *c->an;
     hipStream_t s = c->stream;
     const int G = n_genes;
-    a.n = n, a.nnz = nnz, a.G = G, a.T = T, a.cell_chunks = ceil_div64(n, AN_CELL_CHUNK);
+    a.G = G, a.T = T, a.cell_chunks = ceil_div64(n, AN_CELL_CHUNK);
     auto fail = [&](int rc) { sc_annot_release(c); return rc; };
 #define AN_TRY(call) do { int rc_ = (call); if (rc_ != SC_OK) return fail(rc_); } while (0)
     AN_TRY(an_upload(c, a.d, indptr, indices, data, dtype, n, G, mode, nnz));
@@ -713,7 +634,7 @@ extern "C" int sc_annot_train_begin(sc_ctx *c, const int64_t *indptr, const int3
     }
     {
         KernelTimerScope ts(c, SC_K_ANNOT_SETUP);
-        AN_TRY(colsort_enqueue(c, a.cs, a.d.indptr.as<int64_t>(), a.d.indices.as<int32_t>(), a.d.val.as<double>(), n, G, nnz));
+        AN_TRY(colsort_enqueue(c, a.cs, a.d.m.indptr.as<int64_t>(), a.d.m.indices.as<int32_t>(), a.d.m.val.as<double>(), n, G, nnz));
     }
     AN_TRY(colsort_finish(c, a.cs, G, nnz, who));
     const int64_t chunks = a.cs.chunks;
@@ -728,7 +649,7 @@ extern "C" int sc_annot_train_begin(sc_ctx *c, const int64_t *indptr, const int3
                                pass, mean, part);
             hipLaunchKernelGGL(k_an_colstat_finish, per_gene, tpb, 0, s, colptr, cptr, part, G, n, pass, mean, scale, z0);
         }
-        hipLaunchKernelGGL(k_an_dvals<int32_t>, per_entry, tpb, 0, s, a.d.indices.as<int32_t>(), nnz, mean, scale, z0, a.d.val.as<double>());
+        hipLaunchKernelGGL(k_an_dvals<int32_t>, per_entry, tpb, 0, s, a.d.m.indices.as<int32_t>(), nnz, mean, scale, z0, a.d.m.val.as<double>());
         hipLaunchKernelGGL(k_an_dvals<unsigned long long>, per_entry, tpb, 0, s, a.cs.gene.as<unsigned long long>(), nnz, mean, scale, z0,
                            a.cs.cval.as<double>());
     }
@@ -760,7 +681,7 @@ extern "C" int sc_annot_train_forward(sc_ctx *c, const double *coef, const doubl
     SC_TRY(an_set_table(c, a.d, coef, bias, a.z0.data(), a.G, a.T, a.tab, a.base));
     {
         KernelTimerScope ts(c, SC_K_ANNOT_ROWS);
-        an_launch_rows<AN_OUT_ROWS>(c, a.d, a.n, a.T, which ? a.Dir.as<double>() : a.S.as<double>(), nullptr, nullptr, nullptr);
+        an_launch_rows<AN_OUT_ROWS>(c, a.d, a.d.m.n, a.T, which ? a.Dir.as<double>() : a.S.as<double>(), nullptr, nullptr, nullptr);
     }
     SC_HIP(hipGetLastError());
     SC_HIP(hipStreamSynchronize(c->stream));
@@ -783,9 +704,9 @@ extern "C" int sc_annot_train_grad(sc_ctx *c, double *grad_out, double *loss_out
         KernelTimerScope ts(c, SC_K_ANNOT_GRAD);
         const dim3 tpb(AN_TPB), per_t((unsigned)ceil_div64(T, AN_TPB));
         hipLaunchKernelGGL(k_an_resid, dim3((unsigned)ceil_div64(cc * T, AN_TPB)), tpb, 0, s, a.S.as<double>(), a.labels.as<int32_t>(),
-                           a.sw.as<double>(), a.n, T, cc, a.R.as<double>(), rpart, lpart);
-        hipLaunchKernelGGL(k_an_chunk_add, per_t, tpb, 0, s, rpart, cc, T, rsum);
-        hipLaunchKernelGGL(k_an_chunk_add, per_t, tpb, 0, s, lpart, cc, T, lsum);
+                           a.sw.as<double>(), a.d.m.n, T, cc, a.R.as<double>(), rpart, lpart);
+        hipLaunchKernelGGL(k_chunk_add, per_t, tpb, 0, s, rpart, cc, T, rsum);
+        hipLaunchKernelGGL(k_chunk_add, per_t, tpb, 0, s, lpart, cc, T, lsum);
         const dim3 grid((unsigned)ceil_div64(chunks, AN_TPB / tp));
         const int64_t *colptr = a.cs.colptr.as<int64_t>(), *cptr = a.cs.cptr.as<int64_t>();
         const int32_t *crow = a.cs.crow.as<int32_t>(), *cgene = a.cs.cgene.as<int32_t>();
@@ -830,9 +751,9 @@ extern "C" int sc_annot_train_line(sc_ctx *c, const double *alpha, double *d1_ou
         KernelTimerScope ts(c, SC_K_ANNOT_LINE);
         const dim3 tpb(AN_TPB), per_t((unsigned)ceil_div64(T, AN_TPB));
         hipLaunchKernelGGL(k_an_line, dim3((unsigned)ceil_div64(cc * T, AN_TPB)), tpb, 0, s, a.S.as<double>(), a.Dir.as<double>(),
-                           a.labels.as<int32_t>(), a.sw.as<double>(), a.alpha.as<double>(), a.n, T, cc, p1, p2);
-        hipLaunchKernelGGL(k_an_chunk_add, per_t, tpb, 0, s, p1, cc, T, s1);
-        hipLaunchKernelGGL(k_an_chunk_add, per_t, tpb, 0, s, p2, cc, T, s2);
+                           a.labels.as<int32_t>(), a.sw.as<double>(), a.alpha.as<double>(), a.d.m.n, T, cc, p1, p2);
+        hipLaunchKernelGGL(k_chunk_add, per_t, tpb, 0, s, p1, cc, T, s1);
+        hipLaunchKernelGGL(k_chunk_add, per_t, tpb, 0, s, p2, cc, T, s2);
     }
     SC_HIP(hipGetLastError());
     SC_HIP(hipMemcpyAsync(d1_out, s1, sizeof(double) * (size_t)T, hipMemcpyDeviceToHost, s));
@@ -849,7 +770,7 @@ extern "C" int sc_annot_train_step(sc_ctx *c, const double *alpha)
     AnnotTrain &a = *c->an;
     SC_HIP(hipSetDevice(c->device));
     SC_TRY(an_upload_alpha(c, a, who, alpha));
-    const int64_t total = a.n * a.T;
+    const int64_t total = a.d.m.n * a.T;
     {
         KernelTimerScope ts(c, SC_K_ANNOT_STEP);
         hipLaunchKernelGGL(k_an_step, dim3((unsigned)ceil_div64(total, AN_TPB)), dim3(AN_TPB), 0, c->stream, a.S.as<double>(), a.Dir.as<double>(),

@@ -1,7 +1,8 @@
 // sc_colsort.h -- the column-sorted copy of a canonical CSR and its chunk table, shared by sc_nmf.hip and
 // sc_annotate.hip.  A stable device sort by column keeps the rows ascending inside a column; a
 // gene column's stored entries are then cut into chunks of COL_CHUNK entries, the work items of every pass over columns.
-// Nothing here does floating-point arithmetic: the values are carried, never combined.
+// The sort and the tables do no floating-point arithmetic: the values are carried, never combined.  k_chunk_add is
+// what both files finish a chunked sum with (column chunks here, cell chunks there): the chunk sums in chunk order.
 #pragma once
 
 #include "sc_ctx.h"
@@ -9,6 +10,20 @@
 namespace {
 
 constexpr int COL_CHUNK = 512;   // stored entries of a gene column per work item of a column pass
+
+// column chunk c: its gene g and the range [p0, p1) of its entries in the column-sorted copy
+struct ColChunk {
+    int32_t g;
+    int64_t p0, p1;
+};
+__device__ __forceinline__ ColChunk col_chunk(const int64_t *__restrict__ colptr, const int64_t *__restrict__ cptr,
+                                              const int32_t *__restrict__ cgene, int64_t c)
+{
+    const int32_t g = cgene[c];
+    const int64_t p0 = colptr[g] + (c - cptr[g]) * COL_CHUNK;
+    const int64_t pe = colptr[g + 1];
+    return {g, p0, p0 + COL_CHUNK < pe ? p0 + COL_CHUNK : pe};
+}
 
 // per stored entry: sort key = its column, payload = its position
 __global__ __launch_bounds__(256) void k_cs_keys(const int32_t *__restrict__ indices, int64_t nnz, unsigned long long *__restrict__ keys,
@@ -66,6 +81,16 @@ __global__ __launch_bounds__(256) void k_cs_chunk_fill(const int64_t *__restrict
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= G) return;
     for (int64_t c = cptr[g]; c < cptr[g + 1]; ++c) cgene[c] = g;
+}
+
+// out[e] = part[chunk][e] added in chunk order
+__global__ __launch_bounds__(256) void k_chunk_add(const double *__restrict__ part, int64_t chunks, int P, double *__restrict__ out)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= P) return;
+    double s = 0.0;
+    for (int64_t c = 0; c < chunks; ++c) s = s + part[c * P + e];
+    out[e] = s;
 }
 
 // The column-sorted copy of one matrix: crow / cval = row and value of the sorted entries, gene = their columns (the

@@ -18,6 +18,7 @@
 #include <cmath>
 #include <vector>
 
+#include "sc_csr_input.h"
 #include "sc_dense_knn.h"
 #include "sc_unionfind.h"
 
@@ -543,13 +544,11 @@ extern "C" int sc_diffmap_graph_csr(sc_ctx *c, const int64_t *indptr, const int3
                    (long long)i);
     const int64_t nnz = indptr[n];
     SC_REQUIRE(nnz <= ((int64_t)1 << 32), SC_ERR_INVALID, "sc_diffmap_graph_csr: at most 2^32 stored entries, got %lld", (long long)nnz);
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t p = indptr[i]; p < indptr[i + 1]; ++p) {
-            SC_REQUIRE(indices[p] >= 0 && indices[p] < n && (p == indptr[i] || indices[p] > indices[p - 1]), SC_ERR_INVALID,
-                       "sc_diffmap_graph_csr: row %lld is not canonical (columns must ascend strictly inside [0, n))", (long long)i);
-            SC_REQUIRE(std::isfinite(w[p]) && w[p] > 0.0, SC_ERR_INVALID,
-                       "sc_diffmap_graph_csr: stored value %lld must be finite and > 0", (long long)p);
-        }
+    SC_TRY(csr_check_columns("sc_diffmap_graph_csr", indptr, indices, n, n, "n", [&](int64_t, int64_t p) -> int {
+        SC_REQUIRE(std::isfinite(w[p]) && w[p] > 0.0, SC_ERR_INVALID, "sc_diffmap_graph_csr: stored value %lld must be finite and > 0",
+                   (long long)p);
+        return SC_OK;
+    }));
     SC_HIP(hipSetDevice(c->device));
     sc_ctx::Diffusion &f = c->df;
     hipStream_t s = c->stream;

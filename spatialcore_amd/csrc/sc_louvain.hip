@@ -40,6 +40,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "sc_csr_input.h"
 #include "sc_ctx.h"
 #include "sc_unionfind.h"
 
@@ -714,21 +715,17 @@ extern "C" int sc_louvain_begin(sc_ctx *c, const int64_t *indptr, const int32_t 
     SC_TRY(lv_check_common(who, c, g, max_rounds));
     SC_REQUIRE(indptr, SC_ERR_INVALID, "%s: null pointer", who);
     SC_REQUIRE(n >= 1 && n <= INT32_MAX, SC_ERR_INVALID, "%s: need 1 <= n <= 2^31 - 1, got %lld", who, (long long)n);
-    SC_REQUIRE(indptr[0] == 0, SC_ERR_INVALID, "%s: indptr[0] must be 0", who);
-    for (int64_t i = 0; i < n; ++i)
-        SC_REQUIRE(indptr[i + 1] >= indptr[i], SC_ERR_INVALID, "%s: indptr decreases at row %lld", who, (long long)i);
-    const int64_t nnz = indptr[n];
+    int64_t nnz = 0;
+    SC_TRY(csr_check_offsets(who, indptr, n, &nnz));
     SC_REQUIRE(nnz <= INT32_MAX, SC_ERR_INVALID, "%s: need stored entries <= 2^31 - 1, got %lld", who, (long long)nnz);
     SC_REQUIRE(nnz == 0 || (indices && q), SC_ERR_INVALID, "%s: null pointer", who);
     u64 M = 0;
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t p = indptr[i]; p < indptr[i + 1]; ++p) {
-            SC_REQUIRE(indices[p] >= 0 && indices[p] < n && (p == indptr[i] || indices[p] > indices[p - 1]), SC_ERR_INVALID,
-                       "%s: row %lld is not canonical (columns must ascend strictly inside [0, n))", who, (long long)i);
-            SC_REQUIRE(q[p] >= 1, SC_ERR_INVALID, "%s: weight %lld (row %lld, column %d) is 0: weights are integers in [1, 65535]", who, (long long)p,
-                       (long long)i, indices[p]);
-            M += q[p];
-        }
+    SC_TRY(csr_check_columns(who, indptr, indices, n, n, "n", [&](int64_t i, int64_t p) -> int {
+        SC_REQUIRE(q[p] >= 1, SC_ERR_INVALID, "%s: weight %lld (row %lld, column %d) is 0: weights are integers in [1, 65535]", who, (long long)p,
+                   (long long)i, indices[p]);
+        M += q[p];
+        return SC_OK;
+    }));
     for (int64_t i = 0; i < n; ++i)
         for (int64_t p = indptr[i]; p < indptr[i + 1]; ++p) {
             const int32_t j = indices[p];

@@ -9,7 +9,7 @@
 //  - the K-term dot (W H)_ig of the Kullback-Leibler quotient and of the errors: the K products W_ik H_kg, padded with
 //    zeros to Kp = K rounded up to a power of two, added as the adjacent-pair tree (lane l takes lane l ^ 1, then
 //    l ^ 2, ...: every lane of the group ends with the same bits, since a + b = b + a);
-//  - over a gene column's stored entries: chunks of NMF_COL_CHUNK = 512 entries (rows ascending), each in index order
+//  - over a gene column's stored entries: chunks of COL_CHUNK = 512 entries (rows ascending), each in index order
 //    from 0, the chunk sums added in chunk order;
 //  - over cells (W^T W, colsum(W), the per-cell error terms): chunks of NMF_CELL_CHUNK = 1024 cells, each in index
 //    order from 0, the chunk sums added in chunk order;
@@ -22,25 +22,19 @@
 #include <vector>
 
 #include "sc_colsort.h"
+#include "sc_csr_input.h"
 #include "sc_ctx.h"
+#include "sc_lane_group.h"
 
 namespace {
 
 constexpr int NMF_TPB = 256;
 constexpr int NMF_KMAX = 64;
-constexpr int NMF_COL_CHUNK = COL_CHUNK; // stored entries of a gene column per work item of the H pass (512)
 constexpr int NMF_CELL_CHUNK = 1024;   // cells per partial of the sums over cells
 constexpr int NMF_TILE = 64;           // cells of W staged in LDS at a time by k_nmf_cellsums
 constexpr double NMF_EPS = 1.1920928955078125e-07;   // 2^-23: sklearn's EPSILON (float32 eps)
 constexpr double NMF_TINY = 2.220446049250313e-16;   // 2^-52: the Kullback-Leibler floor of H
 enum { NMF_KL = 1, NMF_FRO = 2 };
-
-// the adjacent-pair tree over the kp lanes of a group (kp a power of two, groups aligned to kp)
-__device__ __forceinline__ double nmf_group_sum(double v, int kp)
-{
-    for (int h = 1; h < kp; h <<= 1) v = v + __shfl_xor(v, h, 64);
-    return v;
-}
 
 // ---- set-up ------------------------------------------------------------------------------------------------------
 // (the column-sorted copy and its chunk table: sc_colsort.h)
@@ -102,30 +96,13 @@ __global__ __launch_bounds__(256) void k_nmf_w(const int64_t *__restrict__ indpt
             if (LOSS == NMF_FRO) {
                 num = num + x * h;
             } else {
-                double d = nmf_group_sum(w * h, kp);
+                double d = group_sum(w * h, kp);
                 d = d < NMF_EPS ? NMF_EPS : d;
                 num = num + (x / d) * h;
             }
         };
         auto row_of = [&](int32_t g) { return k < K ? Ht[(int64_t)g * K + k] : 0.0; };
-        // the group fetches kp entries at once (lane j holds entry base + j) and hands them round, four H^T rows in flight;
-        // the entries are still added one by one in index order
-        const int64_t p1 = indptr[i + 1];
-        for (int64_t base = indptr[i]; base < p1; base += kp) {
-            const int cnt = (int)(p1 - base < kp ? p1 - base : kp);
-            const int32_t g_mine = k < cnt ? indices[base + k] : 0;
-            const double x_mine = k < cnt ? val[base + k] : 0.0;
-            int j = 0;
-            for (; j + 4 <= cnt; j += 4) {
-                const double h0 = row_of(__shfl(g_mine, j, kp)), h1 = row_of(__shfl(g_mine, j + 1, kp));
-                const double h2 = row_of(__shfl(g_mine, j + 2, kp)), h3 = row_of(__shfl(g_mine, j + 3, kp));
-                add(__shfl(x_mine, j, kp), h0);
-                add(__shfl(x_mine, j + 1, kp), h1);
-                add(__shfl(x_mine, j + 2, kp), h2);
-                add(__shfl(x_mine, j + 3, kp), h3);
-            }
-            for (; j < cnt; ++j) add(__shfl(x_mine, j, kp), row_of(__shfl(g_mine, j, kp)));
-        }
+        lane_group_walk(indices, val, indptr[i], indptr[i + 1], kp, k, row_of, add);   // four H^T rows in flight
     }
     if (!live) return;
     double den;
@@ -176,15 +153,6 @@ __global__ __launch_bounds__(256) void k_nmf_cellsums(const double *__restrict__
         if (e < P) part[(int64_t)blockIdx.x * P + e] = acc[j];
     }
 }
-// out[e] = part[chunk][e] added in chunk order
-__global__ __launch_bounds__(256) void k_nmf_chunk_add(const double *__restrict__ part, int64_t chunks, int P, double *__restrict__ out)
-{
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= P) return;
-    double s = 0.0;
-    for (int64_t c = 0; c < chunks; ++c) s = s + part[c * P + e];
-    out[e] = s;
-}
 
 // H pass: one group per column chunk; part[chunk][k] = sum over the chunk's entries of W_ik x (Frobenius: W^T X) or
 // W_ik q with q = x / max((W H)_ig, EPS) (Kullback-Leibler: W^T Q), W the updated one, H the current one
@@ -198,38 +166,20 @@ __global__ __launch_bounds__(256) void k_nmf_h(const int64_t *__restrict__ colpt
     const int t = threadIdx.x, grp = t / kp, k = t % kp;
     const int64_t c = (int64_t)blockIdx.x * (NMF_TPB / kp) + grp;
     if (c >= chunks) return;   // the whole group leaves
-    const int32_t g = cgene[c];
-    const int64_t p0 = colptr[g] + (c - cptr[g]) * NMF_COL_CHUNK;
-    const int64_t pe = colptr[g + 1];
-    const int64_t p1 = p0 + NMF_COL_CHUNK < pe ? p0 + NMF_COL_CHUNK : pe;
-    const double h = (LOSS == NMF_KL && k < K) ? Ht[(int64_t)g * K + k] : 0.0;
+    const ColChunk ch = col_chunk(colptr, cptr, cgene, c);
+    const double h = (LOSS == NMF_KL && k < K) ? Ht[(int64_t)ch.g * K + k] : 0.0;
     double acc = 0.0;
     auto add = [&](double x, double w) {
         if (LOSS == NMF_FRO) {
             acc = acc + w * x;
         } else {
-            double d = nmf_group_sum(w * h, kp);
+            double d = group_sum(w * h, kp);
             d = d < NMF_EPS ? NMF_EPS : d;
             acc = acc + w * (x / d);
         }
     };
     auto row_of = [&](int32_t i) { return k < K ? W[(int64_t)i * K + k] : 0.0; };
-    // as the W pass: kp entries fetched at once, four W rows in flight, added one by one in index order
-    for (int64_t base = p0; base < p1; base += kp) {
-        const int cnt = (int)(p1 - base < kp ? p1 - base : kp);
-        const int32_t i_mine = k < cnt ? crow[base + k] : 0;
-        const double x_mine = k < cnt ? cval[base + k] : 0.0;
-        int j = 0;
-        for (; j + 4 <= cnt; j += 4) {
-            const double w0 = row_of(__shfl(i_mine, j, kp)), w1 = row_of(__shfl(i_mine, j + 1, kp));
-            const double w2 = row_of(__shfl(i_mine, j + 2, kp)), w3 = row_of(__shfl(i_mine, j + 3, kp));
-            add(__shfl(x_mine, j, kp), w0);
-            add(__shfl(x_mine, j + 1, kp), w1);
-            add(__shfl(x_mine, j + 2, kp), w2);
-            add(__shfl(x_mine, j + 3, kp), w3);
-        }
-        for (; j < cnt; ++j) add(__shfl(x_mine, j, kp), row_of(__shfl(i_mine, j, kp)));
-    }
+    lane_group_walk(crow, cval, ch.p0, ch.p1, kp, k, row_of, add);   // four W rows in flight
     if (k < K) part[c * K + k] = acc;
 }
 
@@ -281,7 +231,7 @@ __global__ __launch_bounds__(256) void k_nmf_rowerr(const int64_t *__restrict__ 
         const int32_t g = indices[p];
         const double x = val[p];
         const double h = k < K ? Ht[(int64_t)g * K + k] : 0.0;
-        const double d = nmf_group_sum(w * h, kp);
+        const double d = group_sum(w * h, kp);
         if (LOSS == NMF_FRO) {
             s = s + x * d;
         } else if (x > NMF_EPS) {
@@ -327,13 +277,15 @@ __global__ void k_nmf_err_final(const double *__restrict__ part, int64_t chunks,
 
 struct NmfBufs {
     sc_ctx *c;
-    enum { INDPTR, INDICES, RAW, VAL, W, H0, H1, HT0, HT1, HHT, HSUM, CELLPART, CELLSUM, HPART, ROWERR, ERRPART, ERR, COUNT };
+    enum { W, H0, H1, HT0, HT1, HHT, HSUM, CELLPART, CELLSUM, HPART, ROWERR, ERRPART, ERR, COUNT };
     DBuf b[COUNT];
+    CsrDevice x;  // the matrix in row order
     ColSort cs;   // the column-sorted copy and its chunk table
     explicit NmfBufs(sc_ctx *ctx) : c(ctx) {}
     ~NmfBufs()
     {
         for (DBuf &d : b) d.release(&c->mem);
+        x.release(&c->mem);
         cs.release(&c->mem);
     }
     int get(int which, size_t bytes) { return b[which].ensure(bytes ? bytes : 8, &c->mem); }
@@ -364,15 +316,15 @@ struct NmfState {
         double *part = m->as<double>(NmfBufs::CELLPART);
         if (loss == NMF_FRO) hipLaunchKernelGGL(k_nmf_cellsums<NMF_FRO>, dim3((unsigned)cell_chunks), dim3(NMF_TPB), 0, c->stream, m->as<double>(NmfBufs::W), n, K, part);
         else hipLaunchKernelGGL(k_nmf_cellsums<NMF_KL>, dim3((unsigned)cell_chunks), dim3(NMF_TPB), 0, c->stream, m->as<double>(NmfBufs::W), n, K, part);
-        hipLaunchKernelGGL(k_nmf_chunk_add, dim3((unsigned)ceil_div64(P, NMF_TPB)), dim3(NMF_TPB), 0, c->stream, part, cell_chunks, P,
+        hipLaunchKernelGGL(k_chunk_add, dim3((unsigned)ceil_div64(P, NMF_TPB)), dim3(NMF_TPB), 0, c->stream, part, cell_chunks, P,
                            m->as<double>(NmfBufs::CELLSUM));
     }
     void w_pass() const
     {
         const dim3 grid(groups_grid(n)), block(NMF_TPB);
-        const int64_t *indptr = m->as<int64_t>(NmfBufs::INDPTR);
-        const int32_t *indices = m->as<int32_t>(NmfBufs::INDICES);
-        const double *val = m->as<double>(NmfBufs::VAL);
+        const int64_t *indptr = m->x.indptr.as<int64_t>();
+        const int32_t *indices = m->x.indices.as<int32_t>();
+        const double *val = m->x.val.as<double>();
         if (loss == NMF_FRO)
             hipLaunchKernelGGL(k_nmf_w<NMF_FRO>, grid, block, sizeof(double) * (size_t)(K * K + NMF_TPB), c->stream, indptr, indices, val, n,
                                K, kp, Ht(), m->as<double>(NmfBufs::HHT), m->as<double>(NmfBufs::HSUM), m->as<double>(NmfBufs::W));
@@ -404,9 +356,9 @@ struct NmfState {
             hprep();
             cellsums();
             const dim3 grid(groups_grid(n)), block(NMF_TPB);
-            const int64_t *indptr = m->as<int64_t>(NmfBufs::INDPTR);
-            const int32_t *indices = m->as<int32_t>(NmfBufs::INDICES);
-            const double *val = m->as<double>(NmfBufs::VAL), *W = m->as<double>(NmfBufs::W);
+            const int64_t *indptr = m->x.indptr.as<int64_t>();
+            const int32_t *indices = m->x.indices.as<int32_t>();
+            const double *val = m->x.val.as<double>(), *W = m->as<double>(NmfBufs::W);
             double *rowerr = m->as<double>(NmfBufs::ROWERR), *part = m->as<double>(NmfBufs::ERRPART);
             const double *cs = m->as<double>(NmfBufs::CELLSUM);
             double *err = m->as<double>(NmfBufs::ERR);
@@ -423,20 +375,17 @@ struct NmfState {
     }
 };
 
+// sum x^2 (Frobenius) or the sum of the x > EPS (Kullback-Leibler) over the stored entries, in index order
 template <class T>
-int nmf_check_values(const T *data, int64_t nnz, double *sumsq, double *sumpos)
+double nmf_xconst(const T *data, int64_t nnz, int loss)
 {
-    double a = 0.0, b = 0.0;
+    double s = 0.0;
     for (int64_t p = 0; p < nnz; ++p) {
         const double x = (double)data[p];
-        SC_REQUIRE(std::isfinite(x), SC_ERR_INVALID, "sc_nmf_fit: stored value %lld is not finite", (long long)p);
-        SC_REQUIRE(x >= 0.0, SC_ERR_INVALID, "sc_nmf_fit: stored value %lld is negative", (long long)p);
-        a = a + x * x;
-        if (x > NMF_EPS) b = b + x;
+        if (loss == NMF_FRO) s = s + x * x;
+        else if (x > NMF_EPS) s = s + x;
     }
-    *sumsq = a;
-    *sumpos = b;
-    return SC_OK;
+    return s;
 }
 
 }  // namespace
@@ -455,21 +404,13 @@ extern "C" int sc_nmf_fit(sc_ctx *c, const int64_t *indptr, const int32_t *indic
                "sc_nmf_fit: loss must be 2 (frobenius) or 1 (kullback-leibler), got %d", loss);
     SC_REQUIRE(max_iter >= 1, SC_ERR_INVALID, "sc_nmf_fit: max_iter must be >= 1, got %d", max_iter);
     SC_REQUIRE(std::isfinite(tol) && tol >= 0.0, SC_ERR_INVALID, "sc_nmf_fit: tol must be finite and >= 0");
-    // canonical CSR: offsets from 0, non-decreasing; columns strictly ascending inside a row and inside [0, n_genes)
-    SC_REQUIRE(indptr[0] == 0, SC_ERR_INVALID, "sc_nmf_fit: indptr[0] must be 0");
-    for (int64_t i = 0; i < n; ++i)
-        SC_REQUIRE(indptr[i + 1] >= indptr[i], SC_ERR_INVALID, "sc_nmf_fit: indptr decreases at row %lld", (long long)i);
-    const int64_t nnz = indptr[n];
+    int64_t nnz = 0;
+    SC_TRY(csr_check_offsets("sc_nmf_fit", indptr, n, &nnz));
     SC_REQUIRE(nnz >= 1 && nnz <= (int64_t)UINT32_MAX, SC_ERR_INVALID,
                "sc_nmf_fit: need 1 <= stored entries <= 2^32 - 1, got %lld", (long long)nnz);
     SC_REQUIRE(indices && data, SC_ERR_INVALID, "sc_nmf_fit: null pointer");
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t p = indptr[i]; p < indptr[i + 1]; ++p)
-            SC_REQUIRE(indices[p] >= 0 && indices[p] < n_genes && (p == indptr[i] || indices[p] > indices[p - 1]), SC_ERR_INVALID,
-                       "sc_nmf_fit: row %lld is not canonical (columns must ascend strictly inside [0, n_genes))", (long long)i);
-    double sumsq = 0.0, sumpos = 0.0;
-    if (dtype == SC_F32) SC_TRY(nmf_check_values((const float *)data, nnz, &sumsq, &sumpos));
-    else SC_TRY(nmf_check_values((const double *)data, nnz, &sumsq, &sumpos));
+    SC_TRY(csr_check_columns("sc_nmf_fit", indptr, indices, n, n_genes, "n_genes"));
+    SC_TRY(csr_check_values("sc_nmf_fit", data, dtype, nnz, true, ""));
     for (int64_t q = 0; q < n * K; ++q)
         SC_REQUIRE(std::isfinite(W[q]) && W[q] >= 0.0, SC_ERR_INVALID, "sc_nmf_fit: W0 must be finite and >= 0");
     for (int64_t q = 0; q < (int64_t)K * n_genes; ++q)
@@ -478,20 +419,15 @@ extern "C" int sc_nmf_fit(sc_ctx *c, const int64_t *indptr, const int32_t *indic
     SC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int G = n_genes;
-    int kp = 1;
-    while (kp < K) kp <<= 1;
+    const int kp = lanes_for(K, 1, NMF_KMAX);
     NmfBufs m(c);
     NmfState st{c, &m, n, 0, ceil_div64(n, NMF_CELL_CHUNK), G, (int)K, kp, (int)loss};
-    st.xconst = loss == NMF_FRO ? sumsq : sumpos;
-    const size_t es = dtype == SC_F32 ? sizeof(float) : sizeof(double);
+    st.xconst = dtype == SC_F32 ? nmf_xconst((const float *)data, nnz, loss) : nmf_xconst((const double *)data, nnz, loss);
     const size_t nW = sizeof(double) * (size_t)n * K, nH = sizeof(double) * (size_t)K * G;
     const int P = K * K;
 
     // ---- upload, fp64 values, the column-sorted copy and its chunks -------------------------------------------------
-    SC_TRY(m.get(NmfBufs::INDPTR, sizeof(int64_t) * (size_t)(n + 1)));
-    SC_TRY(m.get(NmfBufs::INDICES, sizeof(int32_t) * (size_t)nnz));
-    SC_TRY(m.get(NmfBufs::RAW, es * (size_t)nnz));
-    SC_TRY(m.get(NmfBufs::VAL, sizeof(double) * (size_t)nnz));
+    SC_TRY(m.x.upload(c, indptr, indices, data, dtype, n, nnz));
     SC_TRY(colsort_alloc(c, m.cs, nnz, G));
     SC_TRY(m.get(NmfBufs::W, nW));
     SC_TRY(m.get(NmfBufs::H0, nH));
@@ -505,17 +441,14 @@ extern "C" int sc_nmf_fit(sc_ctx *c, const int64_t *indptr, const int32_t *indic
     SC_TRY(m.get(NmfBufs::ROWERR, sizeof(double) * (size_t)n));
     SC_TRY(m.get(NmfBufs::ERRPART, sizeof(double) * (size_t)st.cell_chunks));
     SC_TRY(m.get(NmfBufs::ERR, sizeof(double)));
-    SC_HIP(hipMemcpyAsync(m.b[NmfBufs::INDPTR].p, indptr, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemcpyAsync(m.b[NmfBufs::INDICES].p, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemcpyAsync(m.b[NmfBufs::RAW].p, data, es * (size_t)nnz, hipMemcpyHostToDevice, s));
     SC_HIP(hipMemcpyAsync(m.b[NmfBufs::W].p, W, nW, hipMemcpyHostToDevice, s));
     SC_HIP(hipMemcpyAsync(m.b[NmfBufs::H0].p, H, nH, hipMemcpyHostToDevice, s));
     {
         KernelTimerScope ts(c, SC_K_NMF_SETUP);
         const dim3 per_entry((unsigned)ceil_div64(nnz, 256)), tpb(256);
-        if (dtype == SC_F32) hipLaunchKernelGGL(k_nmf_values<float>, per_entry, tpb, 0, s, m.as<float>(NmfBufs::RAW), nnz, m.as<double>(NmfBufs::VAL));
-        else hipLaunchKernelGGL(k_nmf_values<double>, per_entry, tpb, 0, s, m.as<double>(NmfBufs::RAW), nnz, m.as<double>(NmfBufs::VAL));
-        SC_TRY(colsort_enqueue(c, m.cs, m.as<int64_t>(NmfBufs::INDPTR), m.as<int32_t>(NmfBufs::INDICES), m.as<double>(NmfBufs::VAL), n, G, nnz));
+        if (dtype == SC_F32) hipLaunchKernelGGL(k_nmf_values<float>, per_entry, tpb, 0, s, m.x.raw.as<float>(), nnz, m.x.val.as<double>());
+        else hipLaunchKernelGGL(k_nmf_values<double>, per_entry, tpb, 0, s, m.x.raw.as<double>(), nnz, m.x.val.as<double>());
+        SC_TRY(colsort_enqueue(c, m.cs, m.x.indptr.as<int64_t>(), m.x.indices.as<int32_t>(), m.x.val.as<double>(), n, G, nnz));
         hipLaunchKernelGGL(k_nmf_transpose, dim3((unsigned)ceil_div64((int64_t)K * G, 256)), tpb, 0, s, m.as<double>(NmfBufs::H0), (int)K, G,
                            m.as<double>(NmfBufs::HT0));
     }

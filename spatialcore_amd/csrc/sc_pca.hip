@@ -14,12 +14,14 @@
 //    nothing), one sum per (slice, column); k_pca_colsum adds the slice sums in ascending order.
 //  - projection: one group of tp lanes (K rounded up to a power of two, at least 2) per row, lane = component, the row's
 //    stored entries in index order with multiply and add rounded separately (-ffp-contract=off), then - offset.  A group
-//    fetches tp entries at once and hands them round, four table rows in flight, as k_an_rows (sc_annotate.hip) does.
+//    fetches tp entries at once and hands them round, four table rows in flight (sc_lane_group.h).
 #include <climits>
 #include <cmath>
 #include <vector>
 
+#include "sc_csr_input.h"
 #include "sc_ctx.h"
+#include "sc_lane_group.h"
 
 namespace {
 
@@ -183,59 +185,22 @@ __global__ __launch_bounds__(256) void k_pca_rows(const int64_t *__restrict__ in
     if (i >= n) return;   // the whole group leaves
     const bool mine = l < K;
     double acc = 0.0;
-    const int64_t p1 = indptr[i + 1];
-    for (int64_t pb = indptr[i]; pb < p1; pb += tp) {
-        const int cnt = (int)(p1 - pb < tp ? p1 - pb : tp);
-        const int32_t g_mine = l < cnt ? indices[pb + l] : 0;
-        const double x_mine = l < cnt ? val[pb + l] : 0.0;
-        int j = 0;
-        for (; j + 4 <= cnt; j += 4) {
-            double w[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t g = __shfl(g_mine, j + u, tp);
-                w[u] = mine ? table[g * K + l] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc = acc + __shfl(x_mine, j + u, tp) * w[u];
-        }
-        for (; j < cnt; ++j) {
-            const int64_t g = __shfl(g_mine, j, tp);
-            const double x = __shfl(x_mine, j, tp);
-            acc = acc + x * (mine ? table[g * K + l] : 0.0);
-        }
-    }
+    lane_group_walk(indices, val, indptr[i], indptr[i + 1], tp, l, [&](int32_t g) { return mine ? table[(int64_t)g * K + l] : 0.0; },
+                    [&](double x, double w) { acc = acc + x * w; });
     if (mine) out[i * K + l] = (O)(acc - offset[l]);
-}
-
-int pca_lanes(int K)
-{
-    int tp = 2;
-    while (tp < K) tp <<= 1;
-    return tp;
-}
-
-template <class V>
-int pca_check_values(const char *who, const V *data, int64_t nnz, bool nonneg)
-{
-    for (int64_t p = 0; p < nnz; ++p) {
-        const double x = (double)data[p];
-        SC_REQUIRE(std::isfinite(x), SC_ERR_INVALID, "%s: stored value %lld is not finite", who, (long long)p);
-        SC_REQUIRE(!nonneg || x >= 0.0, SC_ERR_INVALID, "%s: stored value %lld is negative (normalize needs counts)", who, (long long)p);
-    }
-    return SC_OK;
 }
 
 }  // namespace
 
 // the matrix resident between sc_pca_begin and sc_pca_end, and the scratch of _gram and _project
 struct PcaState {
-    DBuf indptr, indices, raw, val, bptr, blocks, partial, colpart, gram, colsum, table, offset, out;
-    int64_t n = 0, nnz = 0;
+    CsrDevice m;   // m.raw only inside sc_pca_begin
+    DBuf bptr, blocks, partial, colpart, gram, colsum, table, offset, out;
     int G = 0;
     void release(int64_t *acct)
     {
-        for (DBuf *b : {&indptr, &indices, &raw, &val, &bptr, &blocks, &partial, &colpart, &gram, &colsum, &table, &offset, &out}) b->release(acct);
+        m.release(acct);
+        for (DBuf *b : {&bptr, &blocks, &partial, &colpart, &gram, &colsum, &table, &offset, &out}) b->release(acct);
     }
 };
 
@@ -257,49 +222,35 @@ extern "C" int sc_pca_begin(sc_ctx *c, const int64_t *indptr, const int32_t *ind
     SC_REQUIRE(n >= 2 && n <= INT32_MAX, SC_ERR_INVALID, "%s: need 2 <= n <= 2^31 - 1, got %lld", who, (long long)n);
     SC_REQUIRE(n_genes >= 1 && n_genes <= PCA_GMAX, SC_ERR_INVALID, "%s: need 1 <= n_genes <= %d, got %d", who, PCA_GMAX, n_genes);
     SC_REQUIRE(!normalize || (std::isfinite(target_sum) && target_sum > 0.0), SC_ERR_INVALID, "%s: target_sum must be finite and > 0", who);
-    SC_REQUIRE(indptr[0] == 0, SC_ERR_INVALID, "%s: indptr[0] must be 0", who);
-    for (int64_t i = 0; i < n; ++i)
-        SC_REQUIRE(indptr[i + 1] >= indptr[i], SC_ERR_INVALID, "%s: indptr decreases at row %lld", who, (long long)i);
-    const int64_t nnz = indptr[n];
+    int64_t nnz = 0;
+    SC_TRY(csr_check_offsets(who, indptr, n, &nnz));
     SC_REQUIRE(nnz <= (int64_t)UINT32_MAX, SC_ERR_INVALID, "%s: need stored entries <= 2^32 - 1, got %lld", who, (long long)nnz);
     SC_REQUIRE(nnz == 0 || (indices && data), SC_ERR_INVALID, "%s: null pointer", who);
-    for (int64_t i = 0; i < n; ++i)
-        for (int64_t p = indptr[i]; p < indptr[i + 1]; ++p)
-            SC_REQUIRE(indices[p] >= 0 && indices[p] < n_genes && (p == indptr[i] || indices[p] > indices[p - 1]), SC_ERR_INVALID,
-                       "%s: row %lld is not canonical (columns must ascend strictly inside [0, n_genes))", who, (long long)i);
-    if (dtype == SC_F32) SC_TRY(pca_check_values(who, (const float *)data, nnz, normalize != 0));
-    else SC_TRY(pca_check_values(who, (const double *)data, nnz, normalize != 0));
+    SC_TRY(csr_check_columns(who, indptr, indices, n, n_genes, "n_genes"));
+    SC_TRY(csr_check_values(who, data, dtype, nnz, normalize != 0, " (normalize needs counts)"));
 
     SC_HIP(hipSetDevice(c->device));
     sc_pca_release(c);
     c->pca = new PcaState();
     PcaState &s = *c->pca;
     hipStream_t st = c->stream;
-    s.n = n, s.nnz = nnz, s.G = n_genes;
+    s.G = n_genes;
     auto fail = [&](int rc) { sc_pca_release(c); return rc; };
-    const size_t es = dtype == SC_F32 ? sizeof(float) : sizeof(double), cap = (size_t)(nnz ? nnz : 1);
-    int rc = s.indptr.ensure(sizeof(int64_t) * (size_t)(n + 1), &c->mem);
-    if (rc == SC_OK) rc = s.indices.ensure(sizeof(int32_t) * cap, &c->mem);
-    if (rc == SC_OK) rc = s.raw.ensure(es * cap, &c->mem);
-    if (rc == SC_OK) rc = s.val.ensure(sizeof(double) * cap, &c->mem);
+    const int rc = s.m.upload(c, indptr, indices, data, dtype, n, nnz);
     if (rc != SC_OK) return fail(rc);
-    bool ok = hipMemcpyAsync(s.indptr.p, indptr, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok && nnz)
-        ok = hipMemcpyAsync(s.indices.p, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, st) == hipSuccess &&
-             hipMemcpyAsync(s.raw.p, data, es * (size_t)nnz, hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok) {
+    {
         KernelTimerScope ts(c, SC_K_PCA_SETUP);
         const dim3 per_row((unsigned)ceil_div64(n, PCA_TPB)), tpb(PCA_TPB);
         if (dtype == SC_F32)
-            hipLaunchKernelGGL(k_pca_values<float>, per_row, tpb, 0, st, s.indptr.as<int64_t>(), s.raw.as<float>(), n, normalize, target_sum, s.val.as<double>());
+            hipLaunchKernelGGL(k_pca_values<float>, per_row, tpb, 0, st, s.m.indptr.as<int64_t>(), s.m.raw.as<float>(), n, normalize, target_sum, s.m.val.as<double>());
         else
-            hipLaunchKernelGGL(k_pca_values<double>, per_row, tpb, 0, st, s.indptr.as<int64_t>(), s.raw.as<double>(), n, normalize, target_sum, s.val.as<double>());
+            hipLaunchKernelGGL(k_pca_values<double>, per_row, tpb, 0, st, s.m.indptr.as<int64_t>(), s.m.raw.as<double>(), n, normalize, target_sum, s.m.val.as<double>());
     }
-    if (!ok || hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {   // the caller's arrays are free again
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {   // the caller's arrays are free again
         sc_set_error("%s: upload failed on the device: %s", who, hipGetErrorString(hipGetLastError()));
         return fail(SC_ERR_HIP);
     }
-    s.raw.release(&c->mem);
+    s.m.raw.release(&c->mem);
     return SC_OK;
 }
 
@@ -308,9 +259,9 @@ extern "C" int sc_pca_values(sc_ctx *c, double *values_out)
     const char *who = "sc_pca_values";
     SC_REQUIRE(c && values_out, SC_ERR_INVALID, "%s: null pointer", who);
     SC_REQUIRE(c->pca, SC_ERR_STATE, "%s: no matrix is resident (sc_pca_begin)", who);
-    if (!c->pca->nnz) return SC_OK;
+    if (!c->pca->m.nnz) return SC_OK;
     SC_HIP(hipSetDevice(c->device));
-    SC_HIP(hipMemcpyAsync(values_out, c->pca->val.p, sizeof(double) * (size_t)c->pca->nnz, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(values_out, c->pca->m.val.p, sizeof(double) * (size_t)c->pca->m.nnz, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     return SC_OK;
 }
@@ -329,10 +280,10 @@ extern "C" int sc_pca_gram(sc_ctx *c, double *colsum_out, double *gram_out)
         for (int bj = bi; bj < nb; ++bj) blocks.push_back(int2{bi, bj});
     // the slices: a function of (n, G) alone
     const int64_t smax = PCA_MAX_WG / nq > 1 ? PCA_MAX_WG / nq : 1;
-    const int64_t even = align_up64(ceil_div64(s.n, smax), PCA_CHUNK);
+    const int64_t even = align_up64(ceil_div64(s.m.n, smax), PCA_CHUNK);
     const int64_t slice_rows = even > PCA_SLICE_ROWS ? even : PCA_SLICE_ROWS;
-    const int slices = (int)ceil_div64(s.n, slice_rows);
-    SC_TRY(s.bptr.ensure(sizeof(uint32_t) * (size_t)s.n * (nb + 1), &c->mem));
+    const int slices = (int)ceil_div64(s.m.n, slice_rows);
+    SC_TRY(s.bptr.ensure(sizeof(uint32_t) * (size_t)s.m.n * (nb + 1), &c->mem));
     SC_TRY(s.blocks.ensure(sizeof(int2) * (size_t)nq, &c->mem));
     SC_TRY(s.partial.ensure(sizeof(double) * (size_t)slices * nq * PCA_BLK * PCA_BLK, &c->mem));
     SC_TRY(s.colpart.ensure(sizeof(double) * (size_t)slices * nb * PCA_BLK, &c->mem));
@@ -341,10 +292,10 @@ extern "C" int sc_pca_gram(sc_ctx *c, double *colsum_out, double *gram_out)
     SC_HIP(hipMemcpyAsync(s.blocks.p, blocks.data(), sizeof(int2) * (size_t)nq, hipMemcpyHostToDevice, st));
     {
         KernelTimerScope ts(c, SC_K_PCA_GRAM);
-        hipLaunchKernelGGL(k_pca_block_ptr, dim3((unsigned)ceil_div64(s.n * (nb + 1), PCA_TPB)), dim3(PCA_TPB), 0, st, s.indptr.as<int64_t>(),
-                           s.indices.as<int32_t>(), s.n, nb, s.bptr.as<uint32_t>());
-        hipLaunchKernelGGL(k_pca_gram, dim3((unsigned)nq, (unsigned)slices), dim3(PCA_TPB), 0, st, s.bptr.as<uint32_t>(), s.indices.as<int32_t>(),
-                           s.val.as<double>(), s.n, slice_rows, s.blocks.as<int2>(), nb, s.partial.as<double>(), s.colpart.as<double>());
+        hipLaunchKernelGGL(k_pca_block_ptr, dim3((unsigned)ceil_div64(s.m.n * (nb + 1), PCA_TPB)), dim3(PCA_TPB), 0, st, s.m.indptr.as<int64_t>(),
+                           s.m.indices.as<int32_t>(), s.m.n, nb, s.bptr.as<uint32_t>());
+        hipLaunchKernelGGL(k_pca_gram, dim3((unsigned)nq, (unsigned)slices), dim3(PCA_TPB), 0, st, s.bptr.as<uint32_t>(), s.m.indices.as<int32_t>(),
+                           s.m.val.as<double>(), s.m.n, slice_rows, s.blocks.as<int2>(), nb, s.partial.as<double>(), s.colpart.as<double>());
         hipLaunchKernelGGL(k_pca_gram_reduce, dim3(PCA_BLK * PCA_BLK / PCA_TPB, (unsigned)nq), dim3(PCA_TPB), 0, st, s.partial.as<double>(),
                            s.blocks.as<int2>(), nq, slices, G, s.gram.as<double>());
         hipLaunchKernelGGL(k_pca_colsum, dim3((unsigned)ceil_div64(G, PCA_TPB)), dim3(PCA_TPB), 0, st, s.colpart.as<double>(), nb, slices, G,
@@ -380,22 +331,22 @@ extern "C" int sc_pca_project(sc_ctx *c, const double *V, const double *offset, 
     const size_t os = out_dtype == SC_F32 ? sizeof(float) : sizeof(double);
     SC_TRY(s.table.ensure(sizeof(double) * (size_t)G * K, &c->mem));
     SC_TRY(s.offset.ensure(sizeof(double) * (size_t)K, &c->mem));
-    SC_TRY(s.out.ensure(os * (size_t)s.n * K, &c->mem));
+    SC_TRY(s.out.ensure(os * (size_t)s.m.n * K, &c->mem));
     SC_HIP(hipMemcpyAsync(s.table.p, tab.data(), sizeof(double) * (size_t)G * K, hipMemcpyHostToDevice, st));
     SC_HIP(hipMemcpyAsync(s.offset.p, offset, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, st));
     {
         KernelTimerScope ts(c, SC_K_PCA_PROJECT);
-        const int tp = pca_lanes(K);
-        const dim3 grid((unsigned)ceil_div64(s.n, PCA_TPB / tp)), block(PCA_TPB);
+        const int tp = lanes_for(K, 2, PCA_KMAX);
+        const dim3 grid((unsigned)ceil_div64(s.m.n, PCA_TPB / tp)), block(PCA_TPB);
         if (out_dtype == SC_F32)
-            hipLaunchKernelGGL(k_pca_rows<float>, grid, block, 0, st, s.indptr.as<int64_t>(), s.indices.as<int32_t>(), s.val.as<double>(), s.n, K, tp,
+            hipLaunchKernelGGL(k_pca_rows<float>, grid, block, 0, st, s.m.indptr.as<int64_t>(), s.m.indices.as<int32_t>(), s.m.val.as<double>(), s.m.n, K, tp,
                                s.table.as<double>(), s.offset.as<double>(), s.out.as<float>());
         else
-            hipLaunchKernelGGL(k_pca_rows<double>, grid, block, 0, st, s.indptr.as<int64_t>(), s.indices.as<int32_t>(), s.val.as<double>(), s.n, K, tp,
+            hipLaunchKernelGGL(k_pca_rows<double>, grid, block, 0, st, s.m.indptr.as<int64_t>(), s.m.indices.as<int32_t>(), s.m.val.as<double>(), s.m.n, K, tp,
                                s.table.as<double>(), s.offset.as<double>(), s.out.as<double>());
     }
     SC_HIP(hipGetLastError());
-    SC_HIP(hipMemcpyAsync(scores_out, s.out.p, os * (size_t)s.n * K, hipMemcpyDeviceToHost, st));
+    SC_HIP(hipMemcpyAsync(scores_out, s.out.p, os * (size_t)s.m.n * K, hipMemcpyDeviceToHost, st));
     SC_HIP(hipStreamSynchronize(st));   // `tab` lives until here
     return SC_OK;
 }

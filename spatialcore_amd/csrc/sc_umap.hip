@@ -13,6 +13,7 @@
 #include <cmath>
 #include <vector>
 
+#include "sc_csr_input.h"
 #include "sc_dense_knn.h"
 #include "sc_philox.h"
 #include "sc_umap.h"
@@ -292,16 +293,13 @@ extern "C" int sc_umap_layout(sc_ctx *c, const int64_t *indptr, const int32_t *i
     int64_t nnz = 0;
     if (indptr) {
         SC_REQUIRE(indptr[0] == 0, SC_ERR_INVALID, "sc_umap_layout: indptr[0] must be 0");
-        for (int64_t i = 0; i < n; ++i)
+        for (int64_t i = 0; i < n; ++i)   // (its own wording, which tests/umap_host_checks.cpp pins)
             SC_REQUIRE(indptr[i + 1] >= indptr[i], SC_ERR_INVALID, "sc_umap_layout: indptr descends at row %lld", (long long)i);
         nnz = indptr[n];
-        for (int64_t i = 0; i < n; ++i)
-            for (int64_t p = indptr[i]; p < indptr[i + 1]; ++p) {
-                SC_REQUIRE(indices[p] >= 0 && indices[p] < n && (p == indptr[i] || indices[p] > indices[p - 1]), SC_ERR_INVALID,
-                           "sc_umap_layout: row %lld is not canonical (columns must ascend strictly inside [0, n))", (long long)i);
-                SC_REQUIRE(std::isfinite(w[p]) && w[p] > 0.0, SC_ERR_INVALID,
-                           "sc_umap_layout: stored value %lld must be finite and > 0", (long long)p);
-            }
+        SC_TRY(csr_check_columns("sc_umap_layout", indptr, indices, n, n, "n", [&](int64_t, int64_t p) -> int {
+            SC_REQUIRE(std::isfinite(w[p]) && w[p] > 0.0, SC_ERR_INVALID, "sc_umap_layout: stored value %lld must be finite and > 0", (long long)p);
+            return SC_OK;
+        }));
     } else {
         SC_REQUIRE(f.graph_valid, SC_ERR_STATE, "sc_umap_layout: no graph is resident (call sc_fuzzy_graph or sc_diffmap_graph first)");
         SC_REQUIRE(n == f.n, SC_ERR_INVALID, "sc_umap_layout: the resident graph has %lld vertices, got n=%lld", (long long)f.n,

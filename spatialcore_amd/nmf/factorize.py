@@ -7,14 +7,14 @@ every error evaluation runs in HIP, in fp64 and in one documented summation orde
 from __future__ import annotations
 
 import numbers
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import Optional, Sequence, Union
 
 import numpy as np
-from scipy import sparse
 
 from spatialcore_amd import _lib
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
+from spatialcore_amd._sparse_input import canonical_csr, gene_columns
 
 logger = get_logger("nmf")
 
@@ -51,58 +51,11 @@ def _check_components(n_components) -> int:
     return int(n_components)
 
 
-def _gene_columns(adata, genes) -> Tuple[List[str], np.ndarray]:
-    """Names as morans_i resolves them (None: every gene, a string: that gene) and their columns, in the order given."""
-    if genes is None:
-        names = list(adata.var_names)
-    elif isinstance(genes, str):
-        names = [genes]
-    else:
-        names = [str(g) for g in genes]
-    if not names:
-        raise ValueError("genes must name at least one gene")
-    missing = set(names) - set(adata.var_names)
-    if missing:
-        raise ValueError(f"Genes not found in adata.var_names: {sorted(missing)[:10]}")
-    if len(set(names)) != len(names):
-        raise ValueError("genes must not repeat a gene")
-    if len(names) > 32768:
-        raise ValueError(f"at most 32768 genes are supported, got {len(names)}")
-    return names, np.asarray([adata.var_names.get_loc(g) for g in names], dtype=np.intp)
-
-
-def _canonical_csr(X, cols: np.ndarray, n_vars: int):
-    """The matrix restricted to ``cols`` as a canonical CSR without stored zeros: float32 stays float32, every other type
-    becomes float64.  Returns (csr, output dtype).  The caller's matrix is never modified."""
-    identity = cols.size == n_vars and np.array_equal(cols, np.arange(n_vars))
-    if sparse.issparse(X):
-        if X.ndim != 2:
-            raise ValueError("the expression matrix must be 2-D")
-        Xc = X.tocsr()
-        if not identity:
-            Xc = Xc[:, cols]
-        if Xc is X or Xc.data is getattr(X, "data", None):
-            Xc = Xc.copy()
-    else:
-        A = np.asarray(X)
-        if A.ndim != 2:
-            raise ValueError("the expression matrix must be 2-D")
-        if not (np.issubdtype(A.dtype, np.number) or A.dtype == bool):
-            raise ValueError(f"the expression matrix must be numeric, got {A.dtype}")
-        if not identity:
-            A = A[:, cols]
-        Xc = sparse.csr_matrix(A)
-    dtype = np.float32 if Xc.dtype == np.float32 else np.float64
-    if Xc.dtype != dtype:
-        Xc = Xc.astype(dtype)
-    Xc.sum_duplicates()      # sorts the columns of every row, too
-    if Xc.nnz and not np.all(np.isfinite(Xc.data)):
-        raise ValueError("the expression matrix contains NaN or infinite values")
-    if Xc.nnz and Xc.data.min() < 0:
-        raise ValueError("Negative values in data passed to NMF (input X)")
-    Xc.eliminate_zeros()
-    if Xc.nnz == 0:
-        raise ValueError("the expression matrix is all zero: there is nothing to factorise")
+def _matrix(adata, layer, cols: np.ndarray):
+    """The layer (or ``adata.X``) restricted to ``cols`` as sc_nmf_fit takes it, and the dtype of the result."""
+    X = adata.layers[layer] if layer is not None else adata.X
+    Xc, dtype = canonical_csr(X, cols, len(adata.var_names), negative="Negative values in data passed to NMF (input X)",
+                              all_zero="the expression matrix is all zero: there is nothing to factorise")
     if Xc.shape[0] > 2**31 - 1 or Xc.nnz > 2**32 - 1:
         raise ValueError("at most 2^31 - 1 cells and 2^32 - 1 stored entries are supported")
     return Xc, dtype
@@ -199,8 +152,8 @@ def fit_nmf(adata, n_components: int, genes: Optional[Union[str, Sequence[str]]]
         raise ValueError('init="custom" needs both W (cells x n_components) and H (n_components x genes)')
     if init != "custom" and (W is not None or H is not None):
         raise ValueError('W and H are only used with init="custom"')
-    names, cols = _gene_columns(adata, genes)
-    Xc, dtype = _canonical_csr(adata.layers[layer] if layer is not None else adata.X, cols, len(adata.var_names))
+    names, cols = gene_columns(adata, genes)
+    Xc, dtype = _matrix(adata, layer, cols)
     n, G = Xc.shape
     if init == "custom":
         W0, H0 = _check_factor(W, (n, K), "W"), _check_factor(H, (K, G), "H")
@@ -230,9 +183,9 @@ def project_nmf(adata, components, genes: Sequence[str], layer: Optional[str] = 
     K = _check_components(C.shape[0])
     if genes is None or isinstance(genes, str) and C.shape[1] != 1:
         raise ValueError("genes must name the columns of components")
-    names, cols = _gene_columns(adata, genes)
+    names, cols = gene_columns(adata, genes)
     H0 = _check_factor(C, (K, len(names)), "H")
-    Xc, dtype = _canonical_csr(adata.layers[layer] if layer is not None else adata.X, cols, len(adata.var_names))
+    Xc, dtype = _matrix(adata, layer, cols)
     n, G = Xc.shape
     logger.info(f"NMF projection ({beta_loss}): {n:,} cells x {G} genes onto {K} components")
     ctx = _lib.default_context(device)

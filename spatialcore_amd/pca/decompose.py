@@ -14,12 +14,12 @@ import numbers
 from typing import Optional, Sequence, Union
 
 import numpy as np
-from scipy import linalg, sparse
+from scipy import linalg
 
 from spatialcore_amd import _lib
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
-from spatialcore_amd.nmf.factorize import _gene_columns
+from spatialcore_amd._sparse_input import canonical_csr, gene_columns
 
 logger = get_logger("pca")
 
@@ -57,38 +57,11 @@ def _keys(key_added):
     return ("X_pca", "PCs", "pca") if key_added is None else (key_added, key_added, key_added)
 
 
-def _canonical_csr(X, cols: np.ndarray, n_vars: int, nonneg: bool):
-    """The matrix restricted to ``cols`` as a canonical CSR without stored zeros: float32 stays float32, every other type
-    becomes float64.  The caller's matrix is never modified."""
-    identity = cols.size == n_vars and np.array_equal(cols, np.arange(n_vars))
-    if sparse.issparse(X):
-        if X.ndim != 2:
-            raise ValueError("the expression matrix must be 2-D")
-        Xc = X.tocsr()
-        if not identity:
-            Xc = Xc[:, cols]
-        if Xc is X or Xc.data is getattr(X, "data", None):
-            Xc = Xc.copy()
-    else:
-        A = np.asarray(X)
-        if A.ndim != 2:
-            raise ValueError("the expression matrix must be 2-D")
-        if not (np.issubdtype(A.dtype, np.number) or A.dtype == bool) or np.issubdtype(A.dtype, np.complexfloating):
-            raise ValueError(f"the expression matrix must be real, got {A.dtype}")
-        if not identity:
-            A = A[:, cols]
-        Xc = sparse.csr_matrix(A)
-    dtype = np.float32 if Xc.dtype == np.float32 else np.float64
-    if Xc.dtype != dtype:
-        Xc = Xc.astype(dtype)
-    Xc.sum_duplicates()      # sorts the columns of every row, too
-    if Xc.nnz and not np.all(np.isfinite(Xc.data)):
-        raise ValueError("the expression matrix contains NaN or infinite values")
-    if nonneg and Xc.nnz and Xc.data.min() < 0:
-        raise ValueError("normalize=True needs non-negative values (counts); the expression matrix has negative entries")
-    Xc.eliminate_zeros()
-    if Xc.nnz == 0:
-        raise ValueError("the expression matrix is all zero: there is nothing to decompose")
+def _matrix(X, cols: np.ndarray, n_vars: int, nonneg: bool):
+    """The matrix restricted to ``cols`` as sc_pca_begin takes it."""
+    Xc, _ = canonical_csr(X, cols, n_vars, real=True, all_zero="the expression matrix is all zero: there is nothing to decompose",
+                          negative="normalize=True needs non-negative values (counts); the expression matrix has negative entries"
+                          if nonneg else None)
     if Xc.nnz > 2**32 - 1:
         raise ValueError("at most 2^32 - 1 stored entries are supported")
     return Xc
@@ -215,10 +188,10 @@ def pca(adata, n_comps: int = 50, *, genes: Optional[Union[str, Sequence[str]]] 
         raise ValueError(f"target_sum must be a finite number > 0, got {target_sum!r}")
     dtype = _check_dtype(dtype)
     _check_key(key_added)
-    names, cols = _gene_columns(adata, genes)
+    names, cols = gene_columns(adata, genes)
     X = adata.layers[layer] if layer is not None else adata.X
     _check_shape(int(X.shape[0]), len(names), K)
-    Xc = _canonical_csr(X, cols, len(adata.var_names), normalize)
+    Xc = _matrix(X, cols, len(adata.var_names), normalize)
     n, G = Xc.shape
     logger.info(f"PCA (covariance, exact): {n:,} cells x {G} genes, {K} components"
                 + (", log1p-normalised" if normalize else "") + (", scaled" if scale else ""))
@@ -292,10 +265,10 @@ def project_pca(adata, source, *, layer: Optional[str] = None, key_added: Option
     missing = sorted(set(genes) - set(adata.var_names))
     if missing:
         raise ValueError(f"Genes of the decomposition not found in adata.var_names: {missing[:10]}")
-    names, cols = _gene_columns(adata, genes)
+    names, cols = gene_columns(adata, genes)
     X = adata.layers[layer] if layer is not None else adata.X
     _check_shape(int(X.shape[0]), len(names), None)
-    Xc = _canonical_csr(X, cols, len(adata.var_names), normalize)
+    Xc = _matrix(X, cols, len(adata.var_names), normalize)
     n, G = Xc.shape
     K = components.shape[0]
     logger.info(f"PCA projection: {n:,} cells x {G} genes onto {K} stored components")

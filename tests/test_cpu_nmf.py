@@ -128,7 +128,7 @@ def test_argument_errors_need_no_gpu():
 
 def test_host_hands_over_one_canonical_matrix():
     """Dense, CSR, CSC, unsorted CSR with duplicates and CSR with stored zeros become the same arrays; the caller's matrix stays."""
-    from spatialcore_amd.nmf.factorize import _canonical_csr
+    from spatialcore_amd._sparse_input import canonical_csr as _canonical_csr
 
     X = R.counts(50, 12, 3, 8)
     A = X.toarray()
