@@ -81,7 +81,10 @@ extern "C" {
 #define SC_K_NEIGHBORS_GRAM 41 /* sc_knn_dense_gram: norms, the MFMA filter, the exact re-rank and the fallback scan */
 #define SC_K_UMAP_GRAPH 42  /* sc_fuzzy_graph: rho, the distance mean, the bisection, union (sort), memberships, normalisation */
 #define SC_K_UMAP_LAYOUT 43 /* sc_umap_layout: the maximum weight and one launch per epoch */
-#define SC_K_COUNT_ 44
+#define SC_K_HVG_SETUP 44   /* sc_hvg_pearson: row sums, the column-sorted copy, the per-gene sums of x and x^2, their total */
+#define SC_K_HVG_DENSE 45   /* ... the dense zero term: one division and one square root per (cell, gene) pair */
+#define SC_K_HVG_SPARSE 46  /* ... the correction per stored entry and the per-gene finish */
+#define SC_K_COUNT_ 47
 
 typedef struct sc_ctx sc_ctx;
 
@@ -919,6 +922,27 @@ int sc_fuzzy_graph(sc_ctx *ctx, double *rho_out, double *sigma_out, int64_t *n_e
 int sc_umap_layout(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const double *w, int64_t n, double *Y, int32_t C,
                    double a, double b, double gamma, double alpha0, int32_t neg, int32_t n_epochs, uint64_t seed, int32_t e0,
                    int32_t e1);
+
+/* ---- N18 (extension): Pearson-residual gene selection -- spatialcore_amd.preprocessing ---------------
+ * Lause, Berens & Kobak 2021, the analytic Pearson residuals of a count matrix under a negative binomial null with the
+ * overdispersion theta (infinity: Poisson), restated from the published formula; parity with scanpy is not pinned.
+ * X is a CANONICAL CSR (rows' columns strictly ascending inside [0, n_genes), values SC_F32 or SC_F64, finite, >= 0, at
+ * least one > 0).  fp64, every multiply and add rounded separately, correctly rounded division and square root, no
+ * floating-point atomics: every result is a function of the arguments alone, bit for bit.
+ * sc_hvg_pearson: with s_i = the sum of row i (stored entries in index order), t_g = the sum of column g, T = sum_g t_g,
+ *   p_g = t_g / T, mu = s_i * p_g, v = mu * (1 + mu * (1 / theta)), z(x) = (x - mu) / sqrt(v), the residual of a pair is
+ *   r = min(max(z(x_ig), -clip), clip), and 0 where mu == 0 (an empty cell, an all-zero gene).  Nothing is densified:
+ *   sum_i r = [sum over all n cells of r0 = max(z(0), -clip)] + [sum over the stored entries of r - r0], and the same for
+ *   r^2 with r0^2 and r^2 - r0^2.  The first term is cut into slices of 1024 ceil(n / 2^22) cells, added in slice order;
+ *   the second and t_g, q_g = sum x^2 run over the column-sorted copy in chunks of 512 entries, added in chunk order;
+ *   T adds t_j + t_(j + 256) + ... per j < 256, then those 256 sums in order.  sum_out[g] = t_g, sumsq_out[g] = q_g (exact
+ *   on integer counts below 2^53), resid_mean_out[g] = S1 / n, resid_var_out[g] = max(S2 / n - mean^2, 0): the population
+ *   variance over all n cells.
+ * Validated on the host before the first HIP call: null pointers, dtype, the canonical CSR, finite non-negative values,
+ * 2 <= n <= 2^31 - 1, 1 <= n_genes <= 32768, stored entries <= 2^32 - 1, theta > 0, clip > 0 (either may be infinite). */
+int sc_hvg_pearson(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
+                   int32_t n_genes, double theta, double clip, double *sum_out, double *sumsq_out, double *resid_mean_out,
+                   double *resid_var_out);
 
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across

@@ -34,6 +34,7 @@ K_PCA_SETUP, K_PCA_GRAM, K_PCA_PROJECT = 36, 37, 38
 K_LOUVAIN_MOVE, K_LOUVAIN_LEVEL = 39, 40
 K_NEIGHBORS_GRAM = 41
 K_UMAP_GRAPH, K_UMAP_LAYOUT = 42, 43
+K_HVG_SETUP, K_HVG_DENSE, K_HVG_SPARSE = 44, 45, 46
 ANNOT_MODES = {"counts": 0, "log1p": 1, "log1p_renorm": 2}   # sc_annot_*'s input states
 NMF_LOSSES = {"frobenius": 2, "kullback-leibler": 1}   # sc_nmf_fit's codes (sklearn's beta)
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
@@ -152,6 +153,7 @@ SYMBOLS = {
     "sc_pca_gram": [_P, _P, _P],
     "sc_pca_project": [_P, _P, _P, c_int32, c_int, _P],
     "sc_pca_end": [_P],
+    "sc_hvg_pearson": [_P, _P, _P, _P, c_int, c_int64, c_int32, c_double, c_double, _P, _P, _P, _P],
     "sc_louvain_begin": [_P, _P, _P, _P, c_int64, c_int32, c_int32],
     "sc_louvain_resident_weights": [_P, _P, c_int64],
     "sc_louvain_begin_resident": [_P, _P, c_int64, c_int32, c_int32],
@@ -1076,6 +1078,20 @@ class Context:
         if self._pca_shape is None:
             raise SpatialCoreHipError(f"{who}: no matrix is resident (pca_begin)")
         return self._pca_shape
+
+    # ---- N18 (extension): Pearson-residual gene selection ------------------------------------
+    def hvg_pearson(self, indptr, indices, data, n_genes: int, theta: float, clip: float):
+        """sc_hvg_pearson on a canonical CSR of counts: per gene (sum x, sum x^2, mean of the clipped Pearson residuals,
+        their population variance over all cells), float64.  Validated on the host before the device is touched."""
+        indptr, indices, data, n = self._annot_csr(indptr, indices, data, "hvg_pearson")
+        G = int(n_genes)
+        if not 1 <= G <= 32768:
+            raise ValueError(f"hvg_pearson: need 1 <= n_genes <= 32768, got {G}")
+        out = np.empty((4, G), dtype=np.float64)
+        _check(self._lib.sc_hvg_pearson(self._h, _ptr(indptr), _ptr(indices), _ptr(data),
+                                        SC_F32 if data.dtype == np.float32 else SC_F64, n, G, float(theta), float(clip),
+                                        _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3])))
+        return out[0], out[1], out[2], out[3]
 
     # ---- N16 (extension): Louvain communities ---------------------------------------------------
     def louvain_begin(self, indptr, indices, q, g: int, max_rounds: int) -> None:
