@@ -1149,20 +1149,26 @@ class Context:
         _check(self._lib.sc_louvain_end(self._h))
 
     # ---- N13 (extension): diffusion maps ------------------------------------------------------
+    @staticmethod
+    def _dense_features(who, X, k, fetch):
+        """``knn_dense`` / ``knn_dense_gram`` before the call: (features, dtype code, indices, squared distances or None)."""
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{who}: features must be float32 or float64, got {X.dtype}")
+        if X.ndim != 2:
+            raise ValueError(f"{who}: features must have shape (n, d), got {X.shape}")
+        n = X.shape[0]
+        idx = np.empty((n, int(k)), dtype=np.int32) if fetch else None
+        d2 = np.empty((n, int(k)), dtype=np.float64) if fetch else None
+        return X, SC_F32 if X.dtype == np.float32 else SC_F64, idx, d2
+
     def knn_dense(self, X, k: int, fetch: bool = True, splits: int = 0):
         """sc_knn_dense: the exact k nearest neighbours of every row of ``X`` (n, d), float32 or float64, by (squared
         distance, index).  The lists stay on the device for ``diffmap_graph``; ``fetch`` also returns (indices, squared
         distances).  ``splits`` forces a number of candidate splits (0: the library's choice; the result never differs)."""
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            raise ValueError(f"knn_dense: features must be float32 or float64, got {X.dtype}")
-        if X.ndim != 2:
-            raise ValueError(f"knn_dense: features must have shape (n, d), got {X.shape}")
+        X, dtype, idx, d2 = self._dense_features("knn_dense", X, k, fetch)
         n, d = X.shape
-        idx = np.empty((n, int(k)), dtype=np.int32) if fetch else None
-        d2 = np.empty((n, int(k)), dtype=np.float64) if fetch else None
-        _check(self._lib.sc_knn_dense(self._h, _ptr(X), SC_F32 if X.dtype == np.float32 else SC_F64, n, d, int(k), int(splits),
-                                      _ptr(idx), _ptr(d2)))
+        _check(self._lib.sc_knn_dense(self._h, _ptr(X), dtype, n, d, int(k), int(splits), _ptr(idx), _ptr(d2)))
         self._diff_n = n
         return (idx, d2) if fetch else None
 
@@ -1171,17 +1177,11 @@ class Context:
         matrix cores.  ``path``: 0 the library's choice, 1 the direct kernels, 2 the filter; ``slack``: list entries the
         filter keeps beyond ``k`` (0: the library's choice).  Returns (indices, squared distances, info) -- the first two
         None without ``fetch`` -- with ``info`` = {``path``, ``list_length``, ``rows_certified``, ``rows_fallback``}."""
-        X = np.ascontiguousarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            raise ValueError(f"knn_dense_gram: features must be float32 or float64, got {X.dtype}")
-        if X.ndim != 2:
-            raise ValueError(f"knn_dense_gram: features must have shape (n, d), got {X.shape}")
+        X, dtype, idx, d2 = self._dense_features("knn_dense_gram", X, k, fetch)
         n, d = X.shape
-        idx = np.empty((n, int(k)), dtype=np.int32) if fetch else None
-        d2 = np.empty((n, int(k)), dtype=np.float64) if fetch else None
         info = np.zeros(4, dtype=np.int64)
-        _check(self._lib.sc_knn_dense_gram(self._h, _ptr(X), SC_F32 if X.dtype == np.float32 else SC_F64, n, d, int(k), int(path),
-                                           int(slack), _ptr(idx), _ptr(d2), _ptr(info)))
+        _check(self._lib.sc_knn_dense_gram(self._h, _ptr(X), dtype, n, d, int(k), int(path), int(slack), _ptr(idx), _ptr(d2),
+                                           _ptr(info)))
         self._diff_n = n
         return idx, d2, {"path": int(info[0]), "list_length": int(info[1]), "rows_certified": int(info[2]),
                          "rows_fallback": int(info[3])}

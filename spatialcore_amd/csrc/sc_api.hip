@@ -237,6 +237,7 @@ int sc_ctx_destroy(sc_ctx *c)
                     &c->rs_goff, &c->rs_neg, &c->rs_flag, &c->rs_keys, &c->rs_keys2, &c->rs_pay, &c->rs_pay2, &c->rs_gkey, &c->rs_gkey2,
                     &c->rs_idx, &c->rs_idx2, &c->rs_tmp, &c->rs_rank2, &c->rs_tie, &c->rs_nnz, &c->rs_sum, &c->th_sorted};
     for (DBuf *b : bufs) b->release(&c->mem);
+    for (DBuf *b : c->knn.bufs()) b->release(&c->mem);
     for (DBuf *b : c->df.bufs()) b->release(&c->mem);
     sc_annot_release(c);
     sc_pca_release(c);

@@ -187,24 +187,34 @@ struct sc_ctx {
     // ---- thresholds (sc_threshold.hip): the sorted fp64 scores of the last sc_ks_prepare, for sc_ks_argmax ----
     DBuf th_sorted;
     int64_t th_n = 0;
-    // ---- diffusion maps (sc_diffusion.hip): what one call leaves for the next -- the fp64 features and neighbour lists of
-    // the last sc_knn_dense, the kernel / transition matrix of the last sc_diffmap_graph*, the Lanczos basis ----
+    // ---- the dense search (sc_neighbors.hip): the fp64 features and neighbour lists of the last sc_knn_dense[_gram].  Written
+    // by sc_neighbors.hip alone; read by df_build_union (idx), sc_diffmap_graph (X, d2, d) and sc_fuzzy_graph (idx, d2, k).
+    // What invalidates what: a new search and sc_diffmap_graph_csr clear knn.valid, df.graph_valid and df.lanczos_valid (a
+    // finished search sets knn.valid); a graph from the lists clears the other two; df_finish_graph sets df.graph_valid;
+    // sc_lanczos_begin sets df.lanczos_valid, a breakdown and sc_lanczos_end clear it ----
+    struct DenseKnn {
+        int64_t n = 0;      // rows of the lists
+        int d = 0, k = 0;   // columns of X (the features padded to a multiple of 8), list length
+        bool valid = false;
+        DBuf X, raw, idx, d2, pidx, pd2;        // [n][d] fp64, the upload, [n][k] result, [split][query][k] partial lists
+        DBuf gnorm, gkept, gcnt, glo, grows;    // the Gram filter: row norms, kept candidates [n][L], their counts, the L-th keys, [count | uncertified rows]
+        std::vector<DBuf *> bufs() { return {&X, &raw, &idx, &d2, &pidx, &pd2, &gnorm, &gkept, &gcnt, &glo, &grows}; }
+    } knn;
+    // ---- graphs on those lists or from a caller (sc_diffusion.hip, sc_umap.hip): the resident weighted graph with its
+    // transition matrix, UMAP's bandwidths and layout buffers, the Lanczos basis ----
     struct Diffusion {
-        int64_t n = 0, nnz = 0, m = 0, max_basis = 0;   // cells, stored entries, Lanczos steps taken, basis vectors allocated for
-        int d = 0, k = 0;                               // columns of X (the features padded to a multiple of 8), list length
-        bool knn_valid = false, graph_valid = false, lanczos_valid = false;
-        DBuf X, raw, idx, d2, pidx, pd2;        // [n][d] fp64, the upload, [n][k] result, [split][n][k] partial lists
+        // the resident graph's vertices (df_build_union: knn.n; sc_diffmap_graph_csr: its n) and stored entries; Lanczos steps, basis size
+        int64_t n = 0, nnz = 0, m = 0, max_basis = 0;
+        bool graph_valid = false, lanczos_valid = false;
         DBuf s2, keys, keys2, pay, pay2, cnt, off;   // local scales; (row << 32 | column) keys, the sort's payload, first-of-run flags and offsets
         DBuf indptr, indices, w, T, q, parent, flag;   // CSR (rows sorted by column): kernel weights, transition matrix; row sums; union-find
-        DBuf gnorm, gkept, gcnt, glo, grows;    // sc_knn_dense_gram: row norms, kept candidates [n][L], their counts, the L-th keys, [count | uncertified rows]
         DBuf rho, sigma, dsum;                  // sc_fuzzy_graph: first non-zero distance, bandwidth, [row sums of the distances | chunk sums | their total]
         DBuf lip, lix, lw, ly0, ly1, lmax;      // sc_umap_layout: a caller's CSR, the two position buffers, the bits of w_max
         DBuf V, wv, part, coef, ab, Y, S, res;   // basis [max_basis + 1][n], work vector, chunk partials, coefficients, alpha | beta, Ritz vectors, their coefficients, residuals
         std::vector<DBuf *> bufs()
         {
-            return {&X, &raw, &idx, &d2, &pidx, &pd2, &s2, &keys, &keys2, &pay, &pay2, &cnt, &off, &indptr, &indices, &w, &T, &q,
-                    &parent, &flag, &V, &wv, &part, &coef, &ab, &Y, &S, &res, &gnorm, &gkept, &gcnt, &glo, &grows,
-                    &rho, &sigma, &dsum, &lip, &lix, &lw, &ly0, &ly1, &lmax};
+            return {&s2, &keys, &keys2, &pay, &pay2, &cnt, &off, &indptr, &indices, &w, &T, &q, &parent, &flag, &V, &wv, &part,
+                    &coef, &ab, &Y, &S, &res, &rho, &sigma, &dsum, &lip, &lix, &lw, &ly0, &ly1, &lmax};
         }
     } df;
     // ---- annotation (sc_annotate.hip): the training problem kept on the device between sc_annot_train_begin and _end ----

@@ -1,11 +1,9 @@
-// sc_diffusion.hip -- diffusion maps (Haghverdi et al. 2016): exact k nearest neighbours in d <= 64 dimensions, the
-// locally scaled Gaussian kernel on the symmetric union of the lists, the density-normalised symmetric transition matrix,
-// its connected components, and Lanczos with full reorthogonalisation on it.  DESIGN.md 4.6m; restated in the same
-// orders by tests/diffusion_restated.py.  gfx950 only.
+// sc_diffusion.hip -- diffusion maps (Haghverdi et al. 2016) on the neighbour lists the dense search leaves on the device
+// (sc_neighbors.hip): the locally scaled Gaussian kernel on the symmetric union of the lists, the density-normalised
+// symmetric transition matrix, its connected components, and Lanczos with full reorthogonalisation on it.  DESIGN.md
+// 4.6m; restated in the same orders by tests/diffusion_restated.py.  gfx950 only.
 //
 // fp64 throughout, -ffp-contract=off, no floating-point atomics.  ONE order per sum:
-//  - a squared distance: the d terms (x_ic - x_jc)^2 in column order, starting from the c = 0 term (the device rows are
-//    padded with zeros to a multiple of 8 columns; a padded term adds +0 to a non-negative sum, which changes no bit);
 //  - a row of the kernel matrix, of K' and of T x: the stored entries in column order, a running sum from 0;
 //  - a dot product over the cells (v . w, w . w): chunks of DF_CHUNK = 1024 cells; inside a chunk element e = r * 64 + lane,
 //    a lane adds its 16 products for r ascending starting from the first, the 64 lane sums meet in the adjacent-pair
@@ -13,8 +11,7 @@
 //    are added in chunk order, a running sum from 0;
 //  - w_i - sum_l v_li c_l: one subtraction per l, l ascending;
 //  - a Ritz vector sum_j v_ji s_j: j ascending, starting from the j = 0 product.
-// None of this depends on the grid.  The neighbour lists are the k smallest (d2, index) pairs, a total order, so they do
-// not depend on how the candidates were split over workgroups either.
+// None of this depends on the grid.  (A weight's squared distance is the search's: sc_dense_knn.h, df_d2.)
 #include <cmath>
 #include <vector>
 
@@ -26,10 +23,6 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr int DF_DREG = 32;       // widest (padded) feature row a thread keeps in registers; wider rows live in LDS
-constexpr int DF_QB = 256;        // register form: queries per workgroup ...
-constexpr int DF_TILE = 128;      // ... and candidates staged in LDS at a time
-// the LDS form (32 < d <= 64: DF_QB_L queries, DF_TILE_L candidates) and the split rule: sc_dense_knn.h
 constexpr int DF_CHUNK = 1024;    // cells per partial of a dot product
 constexpr int DF_RITZ_MAX = 64;
 
@@ -38,121 +31,6 @@ static int bits_for(int64_t count)   // bits that hold 0 .. count - 1 (at least 
     int b = 1;
     while (((int64_t)1 << b) < count) ++b;
     return b;
-}
-
-// ---- search ------------------------------------------------------------------------------------------------------
-// (the widening kernel k_df_widen, the direct-form distance df_d2 and the list write-out: sc_dense_knn.h)
-// One thread per query, its row in DR registers; workgroup (x, y) scans the candidates [y * split_len, (y + 1) * split_len)
-// in tiles staged through LDS and read as broadcasts.  Writes the K-list of that split, best first, to
-// (pidx, pd2)[y][query][k]; entries a short split could not fill keep TopK's sentinel (DBL_MAX, INT_MAX).
-template <int K, int DR>
-__global__ __launch_bounds__(DF_QB) void k_df_knn_reg(const double *__restrict__ X, int64_t n, int k, int64_t split_len,
-                                                      int32_t *__restrict__ pidx, double *__restrict__ pd2)
-{
-    __shared__ double tile[DF_TILE * DR];
-    const int t = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * DF_QB + t;
-    const int64_t c0 = (int64_t)blockIdx.y * split_len;
-    const int64_t c1 = c0 + split_len < n ? c0 + split_len : n;
-    double q[DR];
-#pragma unroll
-    for (int c = 0; c < DR; ++c) q[c] = i < n ? X[i * DR + c] : 0.0;
-    TopK<K> best;
-    best.init();
-    for (int64_t b = c0; b < c1; b += DF_TILE) {
-        const int cnt = (int)(c1 - b < DF_TILE ? c1 - b : DF_TILE);
-        __syncthreads();
-        for (int e = t; e < cnt * DR; e += DF_QB) tile[e] = X[b * DR + e];
-        __syncthreads();
-        if (i < n) {
-            for (int j = 0; j < cnt; ++j) {
-                const double *x = tile + j * DR;
-                const double acc = df_d2<DR>([&](int c) { return q[c]; }, [&](int c) { return x[c]; }, DR);
-                const int cid = (int)(b + j);
-                if (cid != (int)i && cand_better(acc, cid, best.d[K - 1], best.id[K - 1])) best.insert(acc, cid);
-            }
-        }
-    }
-    if (i >= n) return;
-    df_write_list(best, k, ((int64_t)blockIdx.y * n + i) * k, pidx, pd2);
-}
-
-// The same with the queries' rows in LDS (column c of the workgroup's queries is one conflict-free row of 64 doubles):
-// 32 < dp <= 64, where the registers of the row next to a 32-entry list would spill.
-template <int K>
-__global__ __launch_bounds__(DF_QB_L) void k_df_knn_lds(const double *__restrict__ X, int64_t n, int dp, int k, int64_t split_len,
-                                                        int32_t *__restrict__ pidx, double *__restrict__ pd2)
-{
-    __shared__ double qs[DF_DMAX * DF_QB_L];
-    __shared__ double tile[DF_TILE_L * DF_DMAX];
-    const int t = threadIdx.x;
-    const int64_t i = (int64_t)blockIdx.x * DF_QB_L + t;
-    const int64_t c0 = (int64_t)blockIdx.y * split_len;
-    const int64_t c1 = c0 + split_len < n ? c0 + split_len : n;
-    for (int c = 0; c < dp; ++c) qs[c * DF_QB_L + t] = i < n ? X[i * dp + c] : 0.0;
-    TopK<K> best;
-    best.init();
-    for (int64_t b = c0; b < c1; b += DF_TILE_L) {
-        const int cnt = (int)(c1 - b < DF_TILE_L ? c1 - b : DF_TILE_L);
-        __syncthreads();
-        for (int e = t; e < cnt * dp; e += DF_QB_L) tile[e] = X[b * dp + e];
-        __syncthreads();
-        if (i < n) {
-            for (int j = 0; j < cnt; ++j) {
-                const double *x = tile + j * dp;
-                const double acc = df_d2<0>([&](int c) { return qs[c * DF_QB_L + t]; }, [&](int c) { return x[c]; }, dp);
-                const int cid = (int)(b + j);
-                if (cid != (int)i && cand_better(acc, cid, best.d[K - 1], best.id[K - 1])) best.insert(acc, cid);
-            }
-        }
-    }
-    if (i >= n) return;
-    df_write_list(best, k, ((int64_t)blockIdx.y * n + i) * k, pidx, pd2);
-}
-
-// the k best of a query's `splits` lists, by the same comparison (a sentinel never beats anything)
-template <int K>
-__global__ __launch_bounds__(256) void k_df_knn_merge(const int32_t *__restrict__ pidx, const double *__restrict__ pd2, int64_t n,
-                                                      int k, int splits, int32_t *__restrict__ idx, double *__restrict__ d2)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    TopK<K> best;
-    best.init();
-    for (int s = 0; s < splits; ++s) {
-        const int64_t o = ((int64_t)s * n + i) * k;
-        for (int j = 0; j < k; ++j) {
-            const double cd = pd2[o + j];
-            const int cid = pidx[o + j];
-            if (cand_better(cd, cid, best.d[K - 1], best.id[K - 1])) best.insert(cd, cid);
-        }
-    }
-    df_write_list(best, k, i * k, idx, d2);
-}
-
-template <int K>
-void df_launch_search(sc_ctx *c, int64_t n, int dp, int k, int splits, int64_t split_len, int32_t *pidx, double *pd2)
-{
-    const double *X = c->df.X.as<double>();
-    if (dp > DF_DREG) {
-        const dim3 grid((unsigned)ceil_div64(n, DF_QB_L), (unsigned)splits);
-        hipLaunchKernelGGL(k_df_knn_lds<K>, grid, dim3(DF_QB_L), 0, c->stream, X, n, dp, k, split_len, pidx, pd2);
-        return;
-    }
-    const dim3 grid((unsigned)ceil_div64(n, DF_QB), (unsigned)splits), block(DF_QB);
-    switch (dp) {
-    case 8: hipLaunchKernelGGL((k_df_knn_reg<K, 8>), grid, block, 0, c->stream, X, n, k, split_len, pidx, pd2); break;
-    case 16: hipLaunchKernelGGL((k_df_knn_reg<K, 16>), grid, block, 0, c->stream, X, n, k, split_len, pidx, pd2); break;
-    case 24: hipLaunchKernelGGL((k_df_knn_reg<K, 24>), grid, block, 0, c->stream, X, n, k, split_len, pidx, pd2); break;
-    default: hipLaunchKernelGGL((k_df_knn_reg<K, 32>), grid, block, 0, c->stream, X, n, k, split_len, pidx, pd2); break;
-    }
-}
-
-template <int K>
-void df_launch_merge(sc_ctx *c, int64_t n, int k, int splits)
-{
-    hipLaunchKernelGGL(k_df_knn_merge<K>, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, c->stream, c->df.pidx.as<int32_t>(),
-                       c->df.pd2.as<double>(), n, k, splits, c->df.idx.as<int32_t>(), c->df.d2.as<double>());
 }
 
 // ---- graph -------------------------------------------------------------------------------------------------------
@@ -213,6 +91,7 @@ __global__ __launch_bounds__(256) void k_df_weights(const int64_t *__restrict__ 
     if (e >= nnz) return;
     const int64_t i = df_row_of(indptr, n, e), j = indices[e];
     const double *a = X + i * dp, *b = X + j * dp;
+    // df_d2<0>'s terms written out: through the helper one compare-and-branch comes out inverted, and this code is kept as it was
     const double f0 = a[0] - b[0];
     double acc = f0 * f0;
     for (int c = 1; c < dp; ++c) {
@@ -376,8 +255,9 @@ int df_dots(sc_ctx *c, const double *V, int64_t nvec, const double *w, double *c
 int df_build_union(sc_ctx *c, long long *nnz_out)
 {
     sc_ctx::Diffusion &f = c->df;
+    const sc_ctx::DenseKnn &kn = c->knn;
     hipStream_t s = c->stream;
-    const int64_t n = f.n, nk = n * f.k, total = 2 * nk;
+    const int64_t n = f.n = kn.n, nk = n * kn.k, total = 2 * nk;
     SC_TRY(f.keys.ensure(sizeof(u64) * (size_t)total, &c->mem));
     SC_TRY(f.keys2.ensure(sizeof(u64) * (size_t)total, &c->mem));
     SC_TRY(f.pay.ensure(sizeof(uint32_t) * (size_t)total, &c->mem));
@@ -387,7 +267,7 @@ int df_build_union(sc_ctx *c, long long *nnz_out)
     SC_TRY(f.indptr.ensure(sizeof(int64_t) * (size_t)(n + 1), &c->mem));
     SC_TRY(f.indices.ensure(sizeof(int32_t) * (size_t)total, &c->mem));
     const dim3 tpb(256);
-    hipLaunchKernelGGL(k_df_keys, dim3((unsigned)ceil_div64(nk, 256)), tpb, 0, s, f.idx.as<int32_t>(), nk, f.k, f.keys.as<u64>(),
+    hipLaunchKernelGGL(k_df_keys, dim3((unsigned)ceil_div64(nk, 256)), tpb, 0, s, kn.idx.as<int32_t>(), nk, kn.k, f.keys.as<u64>(),
                        f.pay.as<uint32_t>());
     SC_TRY((rs_sort<u64, uint32_t>(c, f.keys.as<u64>(), f.keys2.as<u64>(), f.pay.as<uint32_t>(), f.pay2.as<uint32_t>(), total,
                                     32 + bits_for(n))));
@@ -430,76 +310,15 @@ int df_finish_graph(sc_ctx *c, int64_t *n_components_out)
     return SC_OK;
 }
 
-extern "C" int sc_knn_dense(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t d, int32_t k, int32_t splits, int32_t *idx_out,
-                            double *d2_out)
-{
-    SC_REQUIRE(c && X, SC_ERR_INVALID, "sc_knn_dense: null pointer");
-    SC_REQUIRE(dtype == SC_F32 || dtype == SC_F64, SC_ERR_INVALID, "sc_knn_dense: dtype must be SC_F32 or SC_F64");
-    SC_REQUIRE(d >= 1 && d <= DF_DMAX, SC_ERR_INVALID, "sc_knn_dense: need 1 <= d <= %d, got %d", DF_DMAX, d);
-    SC_REQUIRE(k >= 2 && k <= DF_KMAX, SC_ERR_INVALID, "sc_knn_dense: need 2 <= k <= %d, got %d", DF_KMAX, k);
-    SC_REQUIRE(n > k && n <= INT32_MAX, SC_ERR_INVALID, "sc_knn_dense: need k < n <= 2^31 - 1, got n=%lld, k=%d", (long long)n, k);
-    SC_REQUIRE(n * k <= ((int64_t)1 << 29), SC_ERR_INVALID, "sc_knn_dense: need n * k <= 2^29, got %lld", (long long)(n * k));
-    SC_REQUIRE(splits >= 0 && splits <= 65535, SC_ERR_INVALID, "sc_knn_dense: need 0 <= splits <= 65535, got %d", splits);
-    if (dtype == SC_F32) SC_TRY(df_require_finite("sc_knn_dense", (const float *)X, n * d));
-    else SC_TRY(df_require_finite("sc_knn_dense", (const double *)X, n * d));
-
-    SC_HIP(hipSetDevice(c->device));
-    sc_ctx::Diffusion &f = c->df;
-    hipStream_t s = c->stream;
-    f.knn_valid = f.graph_valid = f.lanczos_valid = false;
-    const int dp = (int)align_up64(d, 8);
-    const size_t es = dtype == SC_F32 ? sizeof(float) : sizeof(double);
-    const int tile = dp > DF_DREG ? DF_TILE_L : DF_TILE, qb = dp > DF_DREG ? DF_QB_L : DF_QB;
-    // the candidate ranges: whole tiles, the last one whatever is left
-    int64_t want = splits;
-    if (want == 0) want = n < DF_SPLIT_BELOW ? DF_SPLIT_WGS / ceil_div64(n, qb) : 1;
-    if (want < 1) want = 1;
-    const int64_t split_len = align_up64(ceil_div64(n, want), tile);
-    const int S = (int)ceil_div64(n, split_len);
-    SC_TRY(f.raw.ensure(es * (size_t)(n * d), &c->mem));
-    SC_TRY(f.X.ensure(sizeof(double) * (size_t)(n * dp), &c->mem));
-    SC_TRY(f.idx.ensure(sizeof(int32_t) * (size_t)(n * k), &c->mem));
-    SC_TRY(f.d2.ensure(sizeof(double) * (size_t)(n * k), &c->mem));
-    if (S > 1) {
-        SC_TRY(f.pidx.ensure(sizeof(int32_t) * (size_t)(n * k) * S, &c->mem));
-        SC_TRY(f.pd2.ensure(sizeof(double) * (size_t)(n * k) * S, &c->mem));
-    }
-    SC_HIP(hipMemcpyAsync(f.raw.p, X, es * (size_t)(n * d), hipMemcpyHostToDevice, s));
-    const dim3 widen((unsigned)ceil_div64(n * dp, 256)), tpb(256);
-    if (dtype == SC_F32) hipLaunchKernelGGL(k_df_widen<float>, widen, tpb, 0, s, f.raw.as<float>(), n, (int)d, dp, f.X.as<double>());
-    else hipLaunchKernelGGL(k_df_widen<double>, widen, tpb, 0, s, f.raw.as<double>(), n, (int)d, dp, f.X.as<double>());
-    {
-        KernelTimerScope ts(c, SC_K_DIFF_KNN);
-        int32_t *pidx = S > 1 ? f.pidx.as<int32_t>() : f.idx.as<int32_t>();
-        double *pd2 = S > 1 ? f.pd2.as<double>() : f.d2.as<double>();
-        if (k <= 8) df_launch_search<8>(c, n, dp, k, S, split_len, pidx, pd2);
-        else if (k <= 16) df_launch_search<16>(c, n, dp, k, S, split_len, pidx, pd2);
-        else df_launch_search<32>(c, n, dp, k, S, split_len, pidx, pd2);
-        if (S > 1) {
-            if (k <= 8) df_launch_merge<8>(c, n, k, S);
-            else if (k <= 16) df_launch_merge<16>(c, n, k, S);
-            else df_launch_merge<32>(c, n, k, S);
-        }
-    }
-    SC_HIP(hipGetLastError());
-    if (idx_out) SC_HIP(hipMemcpyAsync(idx_out, f.idx.p, sizeof(int32_t) * (size_t)(n * k), hipMemcpyDeviceToHost, s));
-    if (d2_out) SC_HIP(hipMemcpyAsync(d2_out, f.d2.p, sizeof(double) * (size_t)(n * k), hipMemcpyDeviceToHost, s));
-    SC_HIP(hipStreamSynchronize(s));
-    f.n = n;
-    f.d = dp;
-    f.k = k;
-    f.knn_valid = true;
-    return SC_OK;
-}
-
 extern "C" int sc_diffmap_graph(sc_ctx *c, double *s2_out, int64_t *n_edges_out, int64_t *n_components_out)
 {
     SC_REQUIRE(c && n_edges_out && n_components_out, SC_ERR_INVALID, "sc_diffmap_graph: null pointer");
     sc_ctx::Diffusion &f = c->df;
-    SC_REQUIRE(f.knn_valid, SC_ERR_STATE, "sc_diffmap_graph: no neighbour lists are resident (call sc_knn_dense first)");
+    const sc_ctx::DenseKnn &kn = c->knn;
+    SC_REQUIRE(kn.valid, SC_ERR_STATE, "sc_diffmap_graph: no neighbour lists are resident (call sc_knn_dense first)");
     SC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const int64_t n = f.n, nk = n * f.k, total = 2 * nk;
+    const int64_t n = kn.n, nk = n * kn.k, total = 2 * nk;
     f.graph_valid = f.lanczos_valid = false;
     SC_TRY(f.s2.ensure(sizeof(double) * (size_t)n, &c->mem));
     std::vector<double> s2_host((size_t)n);
@@ -507,7 +326,7 @@ extern "C" int sc_diffmap_graph(sc_ctx *c, double *s2_out, int64_t *n_edges_out,
     const dim3 rows((unsigned)ceil_div64(n, 256)), tpb(256);
     {
         KernelTimerScope ts(c, SC_K_DIFF_GRAPH);
-        hipLaunchKernelGGL(k_df_scale2, rows, tpb, 0, s, f.d2.as<double>(), n, f.k, f.s2.as<double>());
+        hipLaunchKernelGGL(k_df_scale2, rows, tpb, 0, s, kn.d2.as<double>(), n, kn.k, f.s2.as<double>());
         SC_TRY(df_build_union(c, &nnz));
     }
     SC_HIP(hipGetLastError());
@@ -518,7 +337,7 @@ extern "C" int sc_diffmap_graph(sc_ctx *c, double *s2_out, int64_t *n_edges_out,
         SC_REQUIRE(s2_host[(size_t)i] > 0.0, SC_ERR_INVALID,
                    "sc_diffmap_graph: the local scale of cell %lld is zero: more than half of its %d nearest neighbours are exact "
                    "duplicates of it, and the kernel is undefined there (remove the duplicates or use a larger n_neighbors)",
-                   (long long)i, f.k);
+                   (long long)i, kn.k);
     if (s2_out)
         for (int64_t i = 0; i < n; ++i) s2_out[i] = s2_host[(size_t)i];
     f.nnz = nnz;
@@ -526,7 +345,7 @@ extern "C" int sc_diffmap_graph(sc_ctx *c, double *s2_out, int64_t *n_edges_out,
     {
         KernelTimerScope ts(c, SC_K_DIFF_GRAPH);
         hipLaunchKernelGGL(k_df_weights, dim3((unsigned)ceil_div64(nnz, 256)), tpb, 0, s, f.indptr.as<int64_t>(), f.indices.as<int32_t>(), n,
-                           (int64_t)nnz, f.X.as<double>(), f.d, f.s2.as<double>(), f.w.as<double>());
+                           (int64_t)nnz, kn.X.as<double>(), kn.d, f.s2.as<double>(), f.w.as<double>());
         SC_TRY(df_finish_graph(c, n_components_out));
     }
     *n_edges_out = nnz;
@@ -552,7 +371,7 @@ extern "C" int sc_diffmap_graph_csr(sc_ctx *c, const int64_t *indptr, const int3
     SC_HIP(hipSetDevice(c->device));
     sc_ctx::Diffusion &f = c->df;
     hipStream_t s = c->stream;
-    f.knn_valid = f.graph_valid = f.lanczos_valid = false;
+    c->knn.valid = f.graph_valid = f.lanczos_valid = false;
     f.n = n;
     f.nnz = nnz;
     SC_TRY(f.indptr.ensure(sizeof(int64_t) * (size_t)(n + 1), &c->mem));
@@ -708,7 +527,9 @@ extern "C" int sc_lanczos_end(sc_ctx *c)
     SC_HIP(hipSetDevice(c->device));
     SC_HIP(hipStreamSynchronize(c->stream));
     sc_ctx::Diffusion &f = c->df;
-    for (DBuf *b : {&f.V, &f.Y, &f.part, &f.pidx, &f.pd2}) b->release(&c->mem);
+    // the end of a diffusion map gives back its large transients: the basis, and the search's partial lists (knn.pidx / pd2),
+    // which nothing reads after the search that filled them and which the next search sizes again
+    for (DBuf *b : {&f.V, &f.Y, &f.part, &c->knn.pidx, &c->knn.pd2}) b->release(&c->mem);
     f.lanczos_valid = false;
     return SC_OK;
 }

@@ -1,8 +1,16 @@
-// sc_neighbors.hip -- sc_knn_dense_gram: the exact k nearest neighbours of sc_knn_dense, bit for bit, found through a
-// Gram-form filter on the fp64 matrix cores (restated by tests/neighbors_restated.py).  gfx950 only.
+// sc_neighbors.hip -- the exact k nearest neighbours in d <= 64 dimensions, two ways to the same bits (DESIGN.md 4.6m, 4.6q;
+// restated by tests/diffusion_restated.py: knn, and tests/neighbors_restated.py).  gfx950 only.
+//   sc_knn_dense        the direct kernels: every query scans every candidate
+//   sc_knn_dense_gram   a Gram-form filter on the fp64 matrix cores, certified row by row; the direct kernels for the rest
+// Both leave the widened features and the lists in ctx->knn for sc_diffmap_graph and sc_fuzzy_graph.
 //
-// A neighbour list is pinned to the direct form d2 = sum_c (x_ic - x_jc)^2 (sc_dense_knn.h: df_d2), which a Gram-form
-// distance |x|^2 + |y|^2 - 2 x.y does not reproduce.  So the Gram form only FILTERS, with a proven bound:
+// fp64 throughout, -ffp-contract=off, no floating-point atomics.  A squared distance has ONE order: the d terms
+// (x_ic - x_jc)^2 in column order, starting from the c = 0 term (sc_dense_knn.h: df_d2; the device rows are padded with
+// zeros to a multiple of 8 columns; a padded term adds +0 to a non-negative sum, which changes no bit).  The lists are the
+// k smallest (d2, index) pairs, a total order, so they do not depend on how the candidates were split over workgroups.
+//
+// A neighbour list is pinned to that direct form, which a Gram-form distance |x|^2 + |y|^2 - 2 x.y does not reproduce.  So
+// the Gram form only FILTERS, with a proven bound:
 //   1. norms       n_i = sum_c x_ic^2 (fp64, column order; any order satisfies the bound)
 //   2. filter      g_ij = x_i . x_j by v_mfma_f64_16x16x4_f64, s_ij = (n_i + n_j) - 2 g_ij,
 //                  E_ij = c_E 2^-52 (n_i + n_j) + 2^-1000 with c_E = 4 dp + 32, lo_ij = s_ij - E_ij <= d2_dev(i, j);
@@ -11,16 +19,36 @@
 //                  certified iff it kept fewer than L candidates or D < lo_(L) strictly: every candidate not kept has
 //                  d2_dev >= lo >= lo_(L) > D
 //   4. fallback    the uncertified rows, compacted into a list, scan every candidate in the direct form
-// An uncertified row costs time and never correctness; the lists, the widened X and knn_valid are left in ctx->df exactly
-// as sc_knn_dense leaves them.
+// An uncertified row costs time and never correctness.
 #include <cfloat>
+#include <cmath>
+#include <type_traits>
 
 #include "sc_dense_knn.h"
+#include "sc_topk.h"
+
+// X[n][dp] <- the caller's rows widened to fp64, columns d .. dp - 1 zero
+template <class T>
+__global__ __launch_bounds__(256) void k_df_widen(const T *__restrict__ raw, int64_t n, int d, int dp, double *__restrict__ X)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * dp) return;
+    const int64_t i = t / dp;
+    const int c = (int)(t % dp);
+    X[t] = c < d ? (double)raw[i * d + c] : 0.0;
+}
 
 namespace {
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
+constexpr int DF_DREG = 32;       // widest (padded) feature row a thread keeps in registers; wider rows live in LDS
+constexpr int DF_QB = 256;        // register form: queries per workgroup ...
+constexpr int DF_TILE = 128;      // ... and candidates staged in LDS at a time
+constexpr int DF_QB_L = 64;       // LDS form: queries per workgroup (their rows take 32 KiB) ...
+constexpr int DF_TILE_L = 32;     // ... and candidates per tile (16 KiB)
+constexpr int64_t DF_SPLIT_BELOW = 100000;   // fewer queries than this: the candidates are split over workgroups
+constexpr int DF_SPLIT_WGS = 2048;           // ... aiming at about this many
 constexpr int NB_TPB = 512;       // filter: 8 wavefronts of 16 queries (one B operand block each) ...
 constexpr int NB_QB = 128;        // ... = queries per workgroup
 constexpr int NB_TC = 64;         // candidates per LDS tile: 4 A operand blocks, taken two at a time
@@ -31,6 +59,116 @@ constexpr int NB_SLACK_DEFAULT = 8;
 // direct search reads its queries from LDS, and widths 24 and 32; narrower rows stay on the direct register kernels
 constexpr int64_t NB_GRAM_FROM_WIDE = 10000;
 constexpr int64_t NB_GRAM_FROM = 100000;
+
+// the first k entries of a finished list, best first, to (idx, d2)[o .. o + k)
+template <int K>
+__device__ __forceinline__ void df_write_list(const TopK<K> &best, int k, int64_t o, int32_t *__restrict__ idx, double *__restrict__ d2)
+{
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        if (j < k) {
+            idx[o + j] = best.id[j];
+            d2[o + j] = best.d[j];
+        }
+}
+
+// One thread per query, its row in DR registers; workgroup (x, y) scans the candidates [y * split_len, (y + 1) * split_len)
+// in tiles staged through LDS and read as broadcasts.  Writes the K-list of that split, best first, to
+// (pidx, pd2)[y][query][k]; entries a short split could not fill keep TopK's sentinel (DBL_MAX, INT_MAX).
+template <int K, int DR>
+__global__ __launch_bounds__(DF_QB) void k_df_knn_reg(const double *__restrict__ X, int64_t n, int k, int64_t split_len,
+                                                      int32_t *__restrict__ pidx, double *__restrict__ pd2)
+{
+    __shared__ double tile[DF_TILE * DR];
+    const int t = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * DF_QB + t;
+    const int64_t c0 = (int64_t)blockIdx.y * split_len;
+    const int64_t c1 = c0 + split_len < n ? c0 + split_len : n;
+    double q[DR];
+#pragma unroll
+    for (int c = 0; c < DR; ++c) q[c] = i < n ? X[i * DR + c] : 0.0;
+    TopK<K> best;
+    best.init();
+    for (int64_t b = c0; b < c1; b += DF_TILE) {
+        const int cnt = (int)(c1 - b < DF_TILE ? c1 - b : DF_TILE);
+        __syncthreads();
+        for (int e = t; e < cnt * DR; e += DF_QB) tile[e] = X[b * DR + e];
+        __syncthreads();
+        if (i < n) {
+            for (int j = 0; j < cnt; ++j) {
+                const double *x = tile + j * DR;
+                const double acc = df_d2<DR>([&](int c) { return q[c]; }, [&](int c) { return x[c]; }, DR);
+                const int cid = (int)(b + j);
+                if (cid != (int)i && cand_better(acc, cid, best.d[K - 1], best.id[K - 1])) best.insert(acc, cid);
+            }
+        }
+    }
+    if (i >= n) return;
+    df_write_list(best, k, ((int64_t)blockIdx.y * n + i) * k, pidx, pd2);
+}
+
+// The same with the queries' rows in LDS (column c of the workgroup's queries is one conflict-free row of 64 doubles):
+// 32 < dp <= 64, where the registers of the row next to a 32-entry list would spill.  Slot r = blockIdx.x * DF_QB_L + t of
+// the nq queries stands for query r (LISTED = false, nq = n: the direct search) or for query rows[r] (LISTED = true: the
+// fallback of the Gram filter, at any width); the K-list of a split goes to (pidx, pd2)[y][slot][k].
+template <int K, bool LISTED>
+__global__ __launch_bounds__(DF_QB_L) void k_df_knn_lds(const double *__restrict__ X, int64_t n, int dp, int k, int64_t split_len,
+                                                        int32_t *__restrict__ pidx, double *__restrict__ pd2,
+                                                        const int32_t *__restrict__ rows, int64_t nq)
+{
+    __shared__ double qs[DF_DMAX * DF_QB_L];
+    __shared__ double tile[DF_TILE_L * DF_DMAX];
+    const int t = threadIdx.x;
+    const int64_t r = (int64_t)blockIdx.x * DF_QB_L + t;
+    const bool on = r < nq;
+    int64_t i = r;
+    if constexpr (LISTED) i = on ? rows[r] : 0;
+    const int64_t c0 = (int64_t)blockIdx.y * split_len;
+    const int64_t c1 = c0 + split_len < n ? c0 + split_len : n;
+    for (int c = 0; c < dp; ++c) qs[c * DF_QB_L + t] = on ? X[i * dp + c] : 0.0;
+    TopK<K> best;
+    best.init();
+    for (int64_t b = c0; b < c1; b += DF_TILE_L) {
+        const int cnt = (int)(c1 - b < DF_TILE_L ? c1 - b : DF_TILE_L);
+        __syncthreads();
+        for (int e = t; e < cnt * dp; e += DF_QB_L) tile[e] = X[b * dp + e];
+        __syncthreads();
+        if (on) {
+            for (int j = 0; j < cnt; ++j) {
+                const double *x = tile + j * dp;
+                const double acc = df_d2<0>([&](int c) { return qs[c * DF_QB_L + t]; }, [&](int c) { return x[c]; }, dp);
+                const int cid = (int)(b + j);
+                if (cid != (int)i && cand_better(acc, cid, best.d[K - 1], best.id[K - 1])) best.insert(acc, cid);
+            }
+        }
+    }
+    if (!on) return;
+    df_write_list(best, k, ((int64_t)blockIdx.y * nq + r) * k, pidx, pd2);
+}
+
+// the k best of the `splits` lists of slot r, by the same comparison (a sentinel never beats anything), to row r of the
+// result or, LISTED, to row rows[r]
+template <int K, bool LISTED>
+__global__ __launch_bounds__(256) void k_df_knn_merge(const int32_t *__restrict__ pidx, const double *__restrict__ pd2, int64_t nq,
+                                                      int k, int splits, int32_t *__restrict__ idx, double *__restrict__ d2,
+                                                      const int32_t *__restrict__ rows)
+{
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nq) return;
+    TopK<K> best;
+    best.init();
+    for (int s = 0; s < splits; ++s) {
+        const int64_t o = ((int64_t)s * nq + r) * k;
+        for (int j = 0; j < k; ++j) {
+            const double cd = pd2[o + j];
+            const int cid = pidx[o + j];
+            if (cand_better(cd, cid, best.d[K - 1], best.id[K - 1])) best.insert(cd, cid);
+        }
+    }
+    int64_t i = r;
+    if constexpr (LISTED) i = rows[r];
+    df_write_list(best, k, i * k, idx, d2);
+}
 
 __global__ __launch_bounds__(256) void k_nb_norms(const double *__restrict__ X, int64_t n, int dp, double *__restrict__ nrm)
 {
@@ -180,7 +318,7 @@ __global__ __launch_bounds__(NB_TPB) void k_nb_filter(const double *__restrict__
 }
 
 // One thread per query: the direct-form d2 of its kept candidates, the k best, the certificate.  An uncertified row goes
-// on the fallback list (an integer atomic: the order of the list changes no result).
+// on the fallback list (an integer atomic: the order of the list changes no result), which k_df_knn_lds<K, true> scans.
 template <int K>
 __global__ __launch_bounds__(256) void k_nb_rerank(const double *__restrict__ X, int64_t n, int dp, int k, int L,
                                                    const int32_t *__restrict__ kept, const int32_t *__restrict__ kcnt,
@@ -203,66 +341,10 @@ __global__ __launch_bounds__(256) void k_nb_rerank(const double *__restrict__ X,
     if (!(m < L || best.kth(k) < klo[i])) rows[atomicAdd(nrows, 1)] = (int32_t)i;
 }
 
-// The fallback: k_df_knn_lds (sc_diffusion.hip) for the listed queries only -- one thread per listed query, its row in
-// LDS, workgroup (x, y) scans the candidates [y * split_len, (y + 1) * split_len) in tiles; the K-list of that split goes to
-// (pidx, pd2)[y][list position][k].
-template <int K>
-__global__ __launch_bounds__(DF_QB_L) void k_nb_fallback(const double *__restrict__ X, int64_t n, int dp, int k,
-                                                         const int32_t *__restrict__ rows, int64_t nrows, int64_t split_len,
-                                                         int32_t *__restrict__ pidx, double *__restrict__ pd2)
-{
-    __shared__ double qs[DF_DMAX * DF_QB_L];
-    __shared__ double tile[DF_TILE_L * DF_DMAX];
-    const int t = threadIdx.x;
-    const int64_t r = (int64_t)blockIdx.x * DF_QB_L + t;
-    const int64_t i = r < nrows ? rows[r] : -1;
-    const int64_t c0 = (int64_t)blockIdx.y * split_len;
-    const int64_t c1 = c0 + split_len < n ? c0 + split_len : n;
-    for (int c = 0; c < dp; ++c) qs[c * DF_QB_L + t] = i >= 0 ? X[i * dp + c] : 0.0;
-    TopK<K> best;
-    best.init();
-    for (int64_t b = c0; b < c1; b += DF_TILE_L) {
-        const int cnt = (int)(c1 - b < DF_TILE_L ? c1 - b : DF_TILE_L);
-        __syncthreads();
-        for (int e = t; e < cnt * dp; e += DF_QB_L) tile[e] = X[b * dp + e];
-        __syncthreads();
-        if (i >= 0) {
-            for (int j = 0; j < cnt; ++j) {
-                const double *x = tile + j * dp;
-                const double acc = df_d2<0>([&](int c) { return qs[c * DF_QB_L + t]; }, [&](int c) { return x[c]; }, dp);
-                const int cid = (int)(b + j);
-                if (cid != (int)i && cand_better(acc, cid, best.d[K - 1], best.id[K - 1])) best.insert(acc, cid);
-            }
-        }
-    }
-    if (i < 0) return;
-    df_write_list(best, k, ((int64_t)blockIdx.y * nrows + r) * k, pidx, pd2);
-}
-
-// the k best of a listed query's `splits` lists, written over its row of the result
-template <int K>
-__global__ __launch_bounds__(256) void k_nb_fallback_merge(const int32_t *__restrict__ pidx, const double *__restrict__ pd2,
-                                                           const int32_t *__restrict__ rows, int64_t nrows, int k, int splits,
-                                                           int32_t *__restrict__ idx, double *__restrict__ d2)
-{
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= nrows) return;
-    TopK<K> best;
-    best.init();
-    for (int s = 0; s < splits; ++s) {
-        const int64_t o = ((int64_t)s * nrows + r) * k;
-        for (int j = 0; j < k; ++j) {
-            const double cd = pd2[o + j];
-            const int cid = pidx[o + j];
-            if (cand_better(cd, cid, best.d[K - 1], best.id[K - 1])) best.insert(cd, cid);
-        }
-    }
-    df_write_list(best, k, (int64_t)rows[r] * k, idx, d2);
-}
-
+// ---- host ---------------------------------------------------------------------------------------------------------
 void nb_launch_filter(sc_ctx *c, int64_t n, int dp, int L, double ce)
 {
-    sc_ctx::Diffusion &f = c->df;
+    sc_ctx::DenseKnn &f = c->knn;
     const dim3 grid((unsigned)ceil_div64(n, NB_QB)), block(NB_TPB);
     const double *X = f.X.as<double>(), *nrm = f.gnorm.as<double>();
     int32_t *kept = f.gkept.as<int32_t>(), *kcnt = f.gcnt.as<int32_t>();
@@ -282,109 +364,217 @@ void nb_launch_filter(sc_ctx *c, int64_t n, int dp, int L, double ce)
 template <int K>
 void nb_launch_rerank(sc_ctx *c, int64_t n, int dp, int k, int L)
 {
-    sc_ctx::Diffusion &f = c->df;
+    sc_ctx::DenseKnn &f = c->knn;
     hipLaunchKernelGGL(k_nb_rerank<K>, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, c->stream, f.X.as<double>(), n, dp, k, L,
                        f.gkept.as<int32_t>(), f.gcnt.as<int32_t>(), f.glo.as<double>(), f.idx.as<int32_t>(), f.d2.as<double>(),
                        f.grows.as<int32_t>() + 1, f.grows.as<int32_t>());
 }
 
-template <int K>
-void nb_launch_fallback(sc_ctx *c, int64_t n, int dp, int k, int64_t nrows, int S, int64_t split_len)
+// call f with K = 8, 16 or 32 as a std::integral_constant: the shortest list of TopK's three that holds k entries
+template <class F>
+void dk_by_k(int k, F &&f)
 {
-    sc_ctx::Diffusion &f = c->df;
-    const int32_t *rows = f.grows.as<int32_t>() + 1;
-    hipLaunchKernelGGL(k_nb_fallback<K>, dim3((unsigned)ceil_div64(nrows, DF_QB_L), (unsigned)S), dim3(DF_QB_L), 0, c->stream,
-                       f.X.as<double>(), n, dp, k, rows, nrows, split_len, f.pidx.as<int32_t>(), f.pd2.as<double>());
-    hipLaunchKernelGGL(k_nb_fallback_merge<K>, dim3((unsigned)ceil_div64(nrows, 256)), dim3(256), 0, c->stream, f.pidx.as<int32_t>(),
-                       f.pd2.as<double>(), rows, nrows, k, S, f.idx.as<int32_t>(), f.d2.as<double>());
+    if (k <= 8) f(std::integral_constant<int, 8>());
+    else if (k <= 16) f(std::integral_constant<int, 16>());
+    else f(std::integral_constant<int, 32>());
 }
 
-}  // namespace
-
-extern "C" int sc_knn_dense_gram(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t d, int32_t k, int32_t path, int32_t slack,
-                                 int32_t *idx_out, double *d2_out, int64_t *info_out)
+// The candidate ranges of a scan by nq queries in blocks of qb: `forced` of them, or (0) about DF_SPLIT_WGS workgroups'
+// worth below DF_SPLIT_BELOW queries and one range above.  A range is whole tiles, the last one whatever is left of n.
+struct DkSplit { int64_t len; int S; };
+DkSplit dk_split(int64_t nq, int qb, int tile, int64_t n, int forced)
 {
-    SC_REQUIRE(c && X && info_out, SC_ERR_INVALID, "sc_knn_dense_gram: null pointer");
-    SC_REQUIRE(dtype == SC_F32 || dtype == SC_F64, SC_ERR_INVALID, "sc_knn_dense_gram: dtype must be SC_F32 or SC_F64");
-    SC_REQUIRE(d >= 1 && d <= DF_DMAX, SC_ERR_INVALID, "sc_knn_dense_gram: need 1 <= d <= %d, got %d", DF_DMAX, d);
-    SC_REQUIRE(k >= 2 && k <= DF_KMAX, SC_ERR_INVALID, "sc_knn_dense_gram: need 2 <= k <= %d, got %d", DF_KMAX, k);
-    SC_REQUIRE(n > k && n <= INT32_MAX, SC_ERR_INVALID, "sc_knn_dense_gram: need k < n <= 2^31 - 1, got n=%lld, k=%d", (long long)n, k);
-    SC_REQUIRE(n * k <= ((int64_t)1 << 29), SC_ERR_INVALID, "sc_knn_dense_gram: need n * k <= 2^29, got %lld", (long long)(n * k));
-    SC_REQUIRE(path >= 0 && path <= 2, SC_ERR_INVALID, "sc_knn_dense_gram: path must be 0 (the library's choice), 1 (direct) or 2 (Gram filter), got %d",
-               path);
-    SC_REQUIRE(slack >= 0 && slack <= NB_SLACK_MAX, SC_ERR_INVALID, "sc_knn_dense_gram: need 0 <= slack <= %d, got %d", NB_SLACK_MAX, slack);
-    const int dp = (int)align_up64(d, 8);
-    if (path == 0) path = (dp > 32 && n >= NB_GRAM_FROM_WIDE) || (dp >= 24 && n >= NB_GRAM_FROM) ? 2 : 1;
-    if (path == 1) {   // the direct kernels: the call is sc_knn_dense, which reads the values once for its own finite check
-        SC_TRY(sc_knn_dense(c, X, dtype, n, d, k, 0, idx_out, d2_out));
-        info_out[0] = 1;
-        info_out[1] = k;
-        info_out[2] = 0;
-        info_out[3] = 0;
-        return SC_OK;
-    }
-    if (dtype == SC_F32) SC_TRY(df_require_finite("sc_knn_dense_gram", (const float *)X, n * d));
-    else SC_TRY(df_require_finite("sc_knn_dense_gram", (const double *)X, n * d));
+    int64_t want = forced;
+    if (want == 0) want = nq < DF_SPLIT_BELOW ? DF_SPLIT_WGS / ceil_div64(nq, qb) : 1;
+    if (want < 1) want = 1;
+    const int64_t len = align_up64(ceil_div64(n, want), tile);
+    return {len, (int)ceil_div64(n, len)};
+}
 
+template <int K>
+void df_launch_search(sc_ctx *c, int64_t n, int dp, int k, int splits, int64_t split_len, int32_t *pidx, double *pd2)
+{
+    const double *X = c->knn.X.as<double>();
+    if (dp > DF_DREG) {
+        const dim3 grid((unsigned)ceil_div64(n, DF_QB_L), (unsigned)splits);
+        hipLaunchKernelGGL((k_df_knn_lds<K, false>), grid, dim3(DF_QB_L), 0, c->stream, X, n, dp, k, split_len, pidx, pd2,
+                           (const int32_t *)nullptr, n);
+        return;
+    }
+    const dim3 grid((unsigned)ceil_div64(n, DF_QB), (unsigned)splits), block(DF_QB);
+    switch (dp) {
+    case 8: hipLaunchKernelGGL((k_df_knn_reg<K, 8>), grid, block, 0, c->stream, X, n, k, split_len, pidx, pd2); break;
+    case 16: hipLaunchKernelGGL((k_df_knn_reg<K, 16>), grid, block, 0, c->stream, X, n, k, split_len, pidx, pd2); break;
+    case 24: hipLaunchKernelGGL((k_df_knn_reg<K, 24>), grid, block, 0, c->stream, X, n, k, split_len, pidx, pd2); break;
+    default: hipLaunchKernelGGL((k_df_knn_reg<K, 32>), grid, block, 0, c->stream, X, n, k, split_len, pidx, pd2); break;
+    }
+}
+
+template <int K, bool LISTED>
+void df_launch_merge(sc_ctx *c, int64_t nq, int k, int splits, const int32_t *rows)
+{
+    hipLaunchKernelGGL((k_df_knn_merge<K, LISTED>), dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, c->stream, c->knn.pidx.as<int32_t>(),
+                       c->knn.pd2.as<double>(), nq, k, splits, c->knn.idx.as<int32_t>(), c->knn.d2.as<double>(), rows);
+}
+
+template <class T>
+int df_require_finite(const char *who, const T *X, int64_t count)
+{
+    for (int64_t p = 0; p < count; ++p)
+        SC_REQUIRE(std::fabs((double)X[p]) < 0x1p500, SC_ERR_INVALID,   // so that no squared distance overflows
+                   "%s: feature value %lld is not finite and below 2^500 in magnitude", who, (long long)p);
+    return SC_OK;
+}
+
+// ---- what the two entry points share: the gate, and the three steps around the search itself ---------------------------
+int dk_check(const char *who, sc_ctx *c, const void *X, int dtype, int64_t n, int32_t d, int32_t k)
+{
+    SC_REQUIRE(c && X, SC_ERR_INVALID, "%s: null pointer", who);
+    SC_REQUIRE(dtype == SC_F32 || dtype == SC_F64, SC_ERR_INVALID, "%s: dtype must be SC_F32 or SC_F64", who);
+    SC_REQUIRE(d >= 1 && d <= DF_DMAX, SC_ERR_INVALID, "%s: need 1 <= d <= %d, got %d", who, DF_DMAX, d);
+    SC_REQUIRE(k >= 2 && k <= DF_KMAX, SC_ERR_INVALID, "%s: need 2 <= k <= %d, got %d", who, DF_KMAX, k);
+    SC_REQUIRE(n > k && n <= INT32_MAX, SC_ERR_INVALID, "%s: need k < n <= 2^31 - 1, got n=%lld, k=%d", who, (long long)n, k);
+    SC_REQUIRE(n * k <= ((int64_t)1 << 29), SC_ERR_INVALID, "%s: need n * k <= 2^29, got %lld", who, (long long)(n * k));
+    return SC_OK;
+}
+
+// the last refusal of an entry point, after its own argument checks: it reads all n * d values, once per call
+int dk_check_finite(const char *who, const void *X, int dtype, int64_t count)
+{
+    return dtype == SC_F32 ? df_require_finite(who, (const float *)X, count) : df_require_finite(who, (const double *)X, count);
+}
+
+// a new search: nothing that stood on the old lists stays valid; the lists' buffers, the upload, X widened to dp columns
+int dk_begin(sc_ctx *c, const void *X, int dtype, int64_t n, int d, int k)
+{
     SC_HIP(hipSetDevice(c->device));
-    sc_ctx::Diffusion &f = c->df;
+    sc_ctx::DenseKnn &f = c->knn;
     hipStream_t s = c->stream;
-    f.knn_valid = f.graph_valid = f.lanczos_valid = false;
-    const int L = k + (slack ? slack : NB_SLACK_DEFAULT);
-    const double ce = (double)(4 * dp + 32) * 0x1p-52;
+    f.valid = c->df.graph_valid = c->df.lanczos_valid = false;
+    const int dp = (int)align_up64(d, 8);
     const size_t es = dtype == SC_F32 ? sizeof(float) : sizeof(double);
     SC_TRY(f.raw.ensure(es * (size_t)(n * d), &c->mem));
     SC_TRY(f.X.ensure(sizeof(double) * (size_t)(n * dp), &c->mem));
     SC_TRY(f.idx.ensure(sizeof(int32_t) * (size_t)(n * k), &c->mem));
     SC_TRY(f.d2.ensure(sizeof(double) * (size_t)(n * k), &c->mem));
+    SC_HIP(hipMemcpyAsync(f.raw.p, X, es * (size_t)(n * d), hipMemcpyHostToDevice, s));
+    const dim3 widen((unsigned)ceil_div64(n * dp, 256)), tpb(256);
+    if (dtype == SC_F32) hipLaunchKernelGGL(k_df_widen<float>, widen, tpb, 0, s, f.raw.as<float>(), n, d, dp, f.X.as<double>());
+    else hipLaunchKernelGGL(k_df_widen<double>, widen, tpb, 0, s, f.raw.as<double>(), n, d, dp, f.X.as<double>());
+    return SC_OK;
+}
+
+// the direct search on the resident X: with one candidate range straight into the result, else partial lists and a merge
+int dk_direct(sc_ctx *c, int64_t n, int dp, int k, int splits)
+{
+    sc_ctx::DenseKnn &f = c->knn;
+    const bool lds = dp > DF_DREG;
+    const DkSplit sp = dk_split(n, lds ? DF_QB_L : DF_QB, lds ? DF_TILE_L : DF_TILE, n, splits);
+    if (sp.S > 1) {
+        SC_TRY(f.pidx.ensure(sizeof(int32_t) * (size_t)(n * k) * sp.S, &c->mem));
+        SC_TRY(f.pd2.ensure(sizeof(double) * (size_t)(n * k) * sp.S, &c->mem));
+    }
+    KernelTimerScope ts(c, SC_K_DIFF_KNN);
+    int32_t *pidx = sp.S > 1 ? f.pidx.as<int32_t>() : f.idx.as<int32_t>();
+    double *pd2 = sp.S > 1 ? f.pd2.as<double>() : f.d2.as<double>();
+    dk_by_k(k, [&](auto K) {
+        df_launch_search<decltype(K)::value>(c, n, dp, k, sp.S, sp.len, pidx, pd2);
+        if (sp.S > 1) df_launch_merge<decltype(K)::value, false>(c, n, k, sp.S, nullptr);
+    });
+    return SC_OK;
+}
+
+// steps 1 to 4 of the Gram path on the resident X; *nrows_out = the rows that went through the fallback
+int nb_filtered(sc_ctx *c, int64_t n, int dp, int k, int L, int64_t *nrows_out)
+{
+    sc_ctx::DenseKnn &f = c->knn;
+    hipStream_t s = c->stream;
+    const double ce = (double)(4 * dp + 32) * 0x1p-52;
     SC_TRY(f.gnorm.ensure(sizeof(double) * (size_t)n, &c->mem));
     SC_TRY(f.gkept.ensure(sizeof(int32_t) * (size_t)(n * L), &c->mem));
     SC_TRY(f.gcnt.ensure(sizeof(int32_t) * (size_t)n, &c->mem));
     SC_TRY(f.glo.ensure(sizeof(double) * (size_t)n, &c->mem));
     SC_TRY(f.grows.ensure(sizeof(int32_t) * (size_t)(n + 1), &c->mem));   // [0]: the number of listed rows, then the rows
-    SC_HIP(hipMemcpyAsync(f.raw.p, X, es * (size_t)(n * d), hipMemcpyHostToDevice, s));
-    const dim3 widen((unsigned)ceil_div64(n * dp, 256)), rows((unsigned)ceil_div64(n, 256)), tpb(256);
-    if (dtype == SC_F32) hipLaunchKernelGGL(k_df_widen<float>, widen, tpb, 0, s, f.raw.as<float>(), n, (int)d, dp, f.X.as<double>());
-    else hipLaunchKernelGGL(k_df_widen<double>, widen, tpb, 0, s, f.raw.as<double>(), n, (int)d, dp, f.X.as<double>());
+    const int32_t *rows = f.grows.as<int32_t>() + 1;
     int32_t nrows32 = 0;
     {
         KernelTimerScope ts(c, SC_K_NEIGHBORS_GRAM);
-        hipLaunchKernelGGL(k_nb_norms, rows, tpb, 0, s, f.X.as<double>(), n, dp, f.gnorm.as<double>());
+        hipLaunchKernelGGL(k_nb_norms, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, s, f.X.as<double>(), n, dp, f.gnorm.as<double>());
         hipLaunchKernelGGL(k_nb_zero, dim3(1), dim3(1), 0, s, f.grows.as<int32_t>());
         nb_launch_filter(c, n, dp, L, ce);
-        if (k <= 8) nb_launch_rerank<8>(c, n, dp, k, L);
-        else if (k <= 16) nb_launch_rerank<16>(c, n, dp, k, L);
-        else nb_launch_rerank<32>(c, n, dp, k, L);
+        dk_by_k(k, [&](auto K) { nb_launch_rerank<decltype(K)::value>(c, n, dp, k, L); });
     }
     SC_HIP(hipGetLastError());
     SC_HIP(hipMemcpyAsync(&nrows32, f.grows.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     const int64_t nrows = nrows32;
     SC_REQUIRE(nrows >= 0 && nrows <= n, SC_ERR_HIP, "sc_knn_dense_gram: %lld uncertified rows out of range", (long long)nrows);
-    if (nrows > 0) {
-        // the candidate ranges of sc_knn_dense's LDS form, by the number of listed rows
-        int64_t want = nrows < DF_SPLIT_BELOW ? DF_SPLIT_WGS / ceil_div64(nrows, DF_QB_L) : 1;
-        if (want < 1) want = 1;
-        const int64_t split_len = align_up64(ceil_div64(n, want), DF_TILE_L);
-        const int S = (int)ceil_div64(n, split_len);
-        SC_TRY(f.pidx.ensure(sizeof(int32_t) * (size_t)(nrows * k) * S, &c->mem));
-        SC_TRY(f.pd2.ensure(sizeof(double) * (size_t)(nrows * k) * S, &c->mem));
-        KernelTimerScope ts(c, SC_K_NEIGHBORS_GRAM);
-        if (k <= 8) nb_launch_fallback<8>(c, n, dp, k, nrows, S, split_len);
-        else if (k <= 16) nb_launch_fallback<16>(c, n, dp, k, nrows, S, split_len);
-        else nb_launch_fallback<32>(c, n, dp, k, nrows, S, split_len);
-    }
+    *nrows_out = nrows;
+    if (nrows == 0) return SC_OK;
+    // the fallback: the LDS form of the direct search for the listed rows, its candidate ranges by their number
+    const DkSplit sp = dk_split(nrows, DF_QB_L, DF_TILE_L, n, 0);
+    SC_TRY(f.pidx.ensure(sizeof(int32_t) * (size_t)(nrows * k) * sp.S, &c->mem));
+    SC_TRY(f.pd2.ensure(sizeof(double) * (size_t)(nrows * k) * sp.S, &c->mem));
+    KernelTimerScope ts(c, SC_K_NEIGHBORS_GRAM);
+    dk_by_k(k, [&](auto K) {
+        hipLaunchKernelGGL((k_df_knn_lds<decltype(K)::value, true>), dim3((unsigned)ceil_div64(nrows, DF_QB_L), (unsigned)sp.S), dim3(DF_QB_L),
+                           0, s, f.X.as<double>(), n, dp, k, sp.len, f.pidx.as<int32_t>(), f.pd2.as<double>(), rows, nrows);
+        df_launch_merge<decltype(K)::value, true>(c, nrows, k, sp.S, rows);
+    });
+    return SC_OK;
+}
+
+// the lists to the caller, if asked for, and resident for the graphs
+int dk_end(sc_ctx *c, int64_t n, int dp, int k, int32_t *idx_out, double *d2_out)
+{
+    sc_ctx::DenseKnn &f = c->knn;
     SC_HIP(hipGetLastError());
-    if (idx_out) SC_HIP(hipMemcpyAsync(idx_out, f.idx.p, sizeof(int32_t) * (size_t)(n * k), hipMemcpyDeviceToHost, s));
-    if (d2_out) SC_HIP(hipMemcpyAsync(d2_out, f.d2.p, sizeof(double) * (size_t)(n * k), hipMemcpyDeviceToHost, s));
-    SC_HIP(hipStreamSynchronize(s));
+    if (idx_out) SC_HIP(hipMemcpyAsync(idx_out, f.idx.p, sizeof(int32_t) * (size_t)(n * k), hipMemcpyDeviceToHost, c->stream));
+    if (d2_out) SC_HIP(hipMemcpyAsync(d2_out, f.d2.p, sizeof(double) * (size_t)(n * k), hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipStreamSynchronize(c->stream));
     f.n = n;
     f.d = dp;
     f.k = k;
-    f.knn_valid = true;
-    info_out[0] = 2;
+    f.valid = true;
+    return SC_OK;
+}
+
+}  // namespace
+
+extern "C" int sc_knn_dense(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t d, int32_t k, int32_t splits, int32_t *idx_out,
+                            double *d2_out)
+{
+    const char *who = "sc_knn_dense";
+    SC_TRY(dk_check(who, c, X, dtype, n, d, k));
+    SC_REQUIRE(splits >= 0 && splits <= 65535, SC_ERR_INVALID, "%s: need 0 <= splits <= 65535, got %d", who, splits);
+    SC_TRY(dk_check_finite(who, X, dtype, n * d));
+    const int dp = (int)align_up64(d, 8);
+    SC_TRY(dk_begin(c, X, dtype, n, d, k));
+    SC_TRY(dk_direct(c, n, dp, k, splits));
+    return dk_end(c, n, dp, k, idx_out, d2_out);
+}
+
+extern "C" int sc_knn_dense_gram(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t d, int32_t k, int32_t path, int32_t slack,
+                                 int32_t *idx_out, double *d2_out, int64_t *info_out)
+{
+    const char *who = "sc_knn_dense_gram";
+    SC_REQUIRE(info_out, SC_ERR_INVALID, "%s: null pointer", who);
+    SC_TRY(dk_check(who, c, X, dtype, n, d, k));
+    SC_REQUIRE(path >= 0 && path <= 2, SC_ERR_INVALID, "%s: path must be 0 (the library's choice), 1 (direct) or 2 (Gram filter), got %d", who,
+               path);
+    SC_REQUIRE(slack >= 0 && slack <= NB_SLACK_MAX, SC_ERR_INVALID, "%s: need 0 <= slack <= %d, got %d", who, NB_SLACK_MAX, slack);
+    SC_TRY(dk_check_finite(who, X, dtype, n * d));
+    const int dp = (int)align_up64(d, 8);
+    if (path == 0) path = (dp > 32 && n >= NB_GRAM_FROM_WIDE) || (dp >= 24 && n >= NB_GRAM_FROM) ? 2 : 1;
+    const int L = path == 1 ? k : k + (slack ? slack : NB_SLACK_DEFAULT);
+    int64_t nrows = 0;
+    SC_TRY(dk_begin(c, X, dtype, n, d, k));
+    if (path == 1) SC_TRY(dk_direct(c, n, dp, k, 0));
+    else SC_TRY(nb_filtered(c, n, dp, k, L, &nrows));
+    SC_TRY(dk_end(c, n, dp, k, idx_out, d2_out));
+    info_out[0] = path;
     info_out[1] = L;
-    info_out[2] = n - nrows;
+    info_out[2] = path == 1 ? 0 : n - nrows;
     info_out[3] = nrows;
     return SC_OK;
 }

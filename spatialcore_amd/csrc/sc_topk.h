@@ -1,5 +1,5 @@
 // The order of neighbour candidates and the register top-k list built on it (device helpers; sc_search.hip: the planar
-// searches, sc_diffusion.hip: the search in d dimensions).  Every neighbour list of the project is pinned bit for bit, so
+// searches, sc_neighbors.hip: the search in d dimensions).  Every neighbour list of the project is pinned bit for bit, so
 // the comparison that decides it is written here once.
 #pragma once
 
@@ -13,7 +13,7 @@ __device__ __forceinline__ bool cand_better(double d, int id, double ed, int eid
     return d < ed || (d == ed && id < eid);
 }
 
-// The K best candidates of a query in registers, best first (sc_search.hip: k_knn; sc_diffusion.hip: the dense search)
+// The K best candidates of a query in registers, best first (sc_search.hip: k_knn; sc_neighbors.hip: the dense search)
 template <int K>
 struct TopK {
     double d[K];

@@ -223,11 +223,12 @@ extern "C" int sc_fuzzy_graph(sc_ctx *c, double *rho_out, double *sigma_out, int
 {
     SC_REQUIRE(c && n_edges_out && n_components_out, SC_ERR_INVALID, "sc_fuzzy_graph: null pointer");
     sc_ctx::Diffusion &f = c->df;
-    SC_REQUIRE(f.knn_valid, SC_ERR_STATE, "sc_fuzzy_graph: no neighbour lists are resident (call sc_knn_dense first)");
+    const sc_ctx::DenseKnn &kn = c->knn;
+    SC_REQUIRE(kn.valid, SC_ERR_STATE, "sc_fuzzy_graph: no neighbour lists are resident (call sc_knn_dense first)");
     SC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const int64_t n = f.n, nk = n * f.k, chunks = ceil_div64(n, UM_CHUNK);
-    const int k = f.k;
+    const int64_t n = kn.n, nk = n * kn.k, chunks = ceil_div64(n, UM_CHUNK);
+    const int k = kn.k;
     f.graph_valid = f.lanczos_valid = false;
     SC_TRY(f.rho.ensure(sizeof(double) * (size_t)n, &c->mem));
     SC_TRY(f.sigma.ensure(sizeof(double) * (size_t)n, &c->mem));
@@ -238,17 +239,17 @@ extern "C" int sc_fuzzy_graph(sc_ctx *c, double *rho_out, double *sigma_out, int
     const double target = std::log2((double)(k + 1));
     {
         KernelTimerScope ts(c, SC_K_UMAP_GRAPH);
-        hipLaunchKernelGGL(k_um_rho, rows, tpb, 0, s, f.d2.as<double>(), n, k, f.rho.as<double>(), dsum);
+        hipLaunchKernelGGL(k_um_rho, rows, tpb, 0, s, kn.d2.as<double>(), n, k, f.rho.as<double>(), dsum);
         hipLaunchKernelGGL(k_um_chunk_sum, dim3((unsigned)chunks), dim3(64), 0, s, dsum, n, part);
         hipLaunchKernelGGL(k_um_mean, dim3(1), dim3(1), 0, s, part, chunks, (double)(n * (k + 1)), mean);
         if (k <= 8)
-            hipLaunchKernelGGL(k_um_sigma<8>, rows, tpb, 0, s, f.d2.as<double>(), n, k, target, f.rho.as<double>(), dsum, mean,
+            hipLaunchKernelGGL(k_um_sigma<8>, rows, tpb, 0, s, kn.d2.as<double>(), n, k, target, f.rho.as<double>(), dsum, mean,
                                f.sigma.as<double>());
         else if (k <= 16)
-            hipLaunchKernelGGL(k_um_sigma<16>, rows, tpb, 0, s, f.d2.as<double>(), n, k, target, f.rho.as<double>(), dsum, mean,
+            hipLaunchKernelGGL(k_um_sigma<16>, rows, tpb, 0, s, kn.d2.as<double>(), n, k, target, f.rho.as<double>(), dsum, mean,
                                f.sigma.as<double>());
         else
-            hipLaunchKernelGGL(k_um_sigma<32>, rows, tpb, 0, s, f.d2.as<double>(), n, k, target, f.rho.as<double>(), dsum, mean,
+            hipLaunchKernelGGL(k_um_sigma<32>, rows, tpb, 0, s, kn.d2.as<double>(), n, k, target, f.rho.as<double>(), dsum, mean,
                                f.sigma.as<double>());
         SC_TRY(df_build_union(c, &nnz));
     }
@@ -259,7 +260,7 @@ extern "C" int sc_fuzzy_graph(sc_ctx *c, double *rho_out, double *sigma_out, int
     {
         KernelTimerScope ts(c, SC_K_UMAP_GRAPH);
         hipLaunchKernelGGL(k_um_weights, dim3((unsigned)ceil_div64(nnz, 256)), tpb, 0, s, f.indptr.as<int64_t>(), f.indices.as<int32_t>(), n,
-                           (int64_t)nnz, f.idx.as<int32_t>(), f.d2.as<double>(), k, f.rho.as<double>(), f.sigma.as<double>(),
+                           (int64_t)nnz, kn.idx.as<int32_t>(), kn.d2.as<double>(), k, f.rho.as<double>(), f.sigma.as<double>(),
                            f.w.as<double>());
         SC_TRY(df_finish_graph(c, n_components_out));
     }

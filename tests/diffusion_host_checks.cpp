@@ -3,6 +3,7 @@
 // AddressSanitizer + UBSan objects and runs it.  The context is constructed on the host and every call below is refused
 // before its first HIP call, so no device is needed or touched: what runs is the host code that reads the caller's
 // arrays -- the CSR walk, the finite checks, the state checks -- on inputs sized exactly, so a read past an end is caught.
+// (sc_knn_dense's gate: tests/neighbors_host_checks.cpp, next to sc_knn_dense_gram's.)
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
@@ -28,30 +29,6 @@ int main()
     sc_ctx ctx;
     sc_ctx *c = &ctx;
     const int64_t n = 40;
-    std::vector<double> X((size_t)n * 3);
-    for (size_t p = 0; p < X.size(); ++p) X[p] = sin((double)p);
-    std::vector<float> Xf(X.begin(), X.end());
-    std::vector<int32_t> idx((size_t)n * 5);
-    std::vector<double> d2((size_t)n * 5);
-
-    // ---- sc_knn_dense ----
-    expect("knn null ctx", sc_knn_dense(nullptr, X.data(), SC_F64, n, 3, 5, 0, idx.data(), d2.data()), SC_ERR_INVALID, "null pointer");
-    expect("knn null X", sc_knn_dense(c, nullptr, SC_F64, n, 3, 5, 0, idx.data(), d2.data()), SC_ERR_INVALID, "null pointer");
-    expect("knn dtype", sc_knn_dense(c, X.data(), 7, n, 3, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "dtype");
-    expect("knn d = 0", sc_knn_dense(c, X.data(), SC_F64, n, 0, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "1 <= d <= 64");
-    expect("knn d = 65", sc_knn_dense(c, X.data(), SC_F64, n, 65, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "1 <= d <= 64");
-    expect("knn k = 1", sc_knn_dense(c, X.data(), SC_F64, n, 3, 1, 0, nullptr, nullptr), SC_ERR_INVALID, "2 <= k <= 32");
-    expect("knn k = 33", sc_knn_dense(c, X.data(), SC_F64, n, 3, 33, 0, nullptr, nullptr), SC_ERR_INVALID, "2 <= k <= 32");
-    expect("knn n = k", sc_knn_dense(c, X.data(), SC_F64, 5, 3, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "k < n");
-    expect("knn n * k", sc_knn_dense(c, X.data(), SC_F64, (int64_t)1 << 27, 3, 8, 0, nullptr, nullptr), SC_ERR_INVALID, "n * k");
-    expect("knn splits", sc_knn_dense(c, X.data(), SC_F64, n, 3, 5, -1, nullptr, nullptr), SC_ERR_INVALID, "splits");
-    expect("knn splits", sc_knn_dense(c, X.data(), SC_F64, n, 3, 5, 65536, nullptr, nullptr), SC_ERR_INVALID, "splits");
-    X[(size_t)n * 3 - 1] = NAN;      // the very last value: the check reads all n * d of them and no more
-    expect("knn nan", sc_knn_dense(c, X.data(), SC_F64, n, 3, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "feature value 119");
-    X[(size_t)n * 3 - 1] = 0x1p500;
-    expect("knn huge", sc_knn_dense(c, X.data(), SC_F64, n, 3, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "feature value 119");
-    Xf[(size_t)n * 3 - 1] = INFINITY;
-    expect("knn inf f32", sc_knn_dense(c, Xf.data(), SC_F32, n, 3, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "feature value 119");
 
     // ---- sc_diffmap_graph / _get: nothing is resident ----
     int64_t edges = 0, comps = 0;

@@ -1,4 +1,5 @@
-// Host-only check of sc_knn_dense_gram's argument validation (csrc/sc_neighbors.hip), meant for the sanitizer build:
+// Host-only check of the dense search's argument validation, sc_knn_dense and sc_knn_dense_gram (csrc/sc_neighbors.hip:
+// one gate for both), meant for the sanitizer build:
 // `make -C spatialcore_amd/csrc asan_neighbors` links this program (its own main, nothing preloaded) against the
 // AddressSanitizer + UBSan objects and runs it.  The context is constructed on the host and every call below is refused
 // before its first HIP call, so no device is needed or touched: what runs is the host code that reads the caller's array
@@ -38,6 +39,28 @@ int main()
         return sc_knn_dense_gram(cc, x, dtype, rows, d, k, path, slack, idx.data(), d2.data(), inf);
     };
 
+    // ---- sc_knn_dense ----
+    expect("knn null ctx", sc_knn_dense(nullptr, X.data(), SC_F64, n, 3, 5, 0, idx.data(), d2.data()), SC_ERR_INVALID, "null pointer");
+    expect("knn null X", sc_knn_dense(c, nullptr, SC_F64, n, 3, 5, 0, idx.data(), d2.data()), SC_ERR_INVALID, "null pointer");
+    expect("knn dtype", sc_knn_dense(c, X.data(), 7, n, 3, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "dtype");
+    expect("knn d = 0", sc_knn_dense(c, X.data(), SC_F64, n, 0, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "1 <= d <= 64");
+    expect("knn d = 65", sc_knn_dense(c, X.data(), SC_F64, n, 65, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "1 <= d <= 64");
+    expect("knn k = 1", sc_knn_dense(c, X.data(), SC_F64, n, 3, 1, 0, nullptr, nullptr), SC_ERR_INVALID, "2 <= k <= 32");
+    expect("knn k = 33", sc_knn_dense(c, X.data(), SC_F64, n, 3, 33, 0, nullptr, nullptr), SC_ERR_INVALID, "2 <= k <= 32");
+    expect("knn n = k", sc_knn_dense(c, X.data(), SC_F64, 5, 3, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "k < n");
+    expect("knn n * k", sc_knn_dense(c, X.data(), SC_F64, (int64_t)1 << 27, 3, 8, 0, nullptr, nullptr), SC_ERR_INVALID, "n * k");
+    expect("knn splits", sc_knn_dense(c, X.data(), SC_F64, n, 3, 5, -1, nullptr, nullptr), SC_ERR_INVALID, "splits");
+    expect("knn splits", sc_knn_dense(c, X.data(), SC_F64, n, 3, 5, 65536, nullptr, nullptr), SC_ERR_INVALID, "splits");
+    X[(size_t)n * 3 - 1] = NAN;      // the very last value: the check reads all n * d of them and no more
+    expect("knn nan", sc_knn_dense(c, X.data(), SC_F64, n, 3, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "feature value 119");
+    X[(size_t)n * 3 - 1] = 0x1p500;
+    expect("knn huge", sc_knn_dense(c, X.data(), SC_F64, n, 3, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "feature value 119");
+    X[(size_t)n * 3 - 1] = 0.5;
+    Xf[(size_t)n * 3 - 1] = INFINITY;
+    expect("knn inf f32", sc_knn_dense(c, Xf.data(), SC_F32, n, 3, 5, 0, nullptr, nullptr), SC_ERR_INVALID, "feature value 119");
+    Xf[(size_t)n * 3 - 1] = 0.5f;
+
+    // ---- sc_knn_dense_gram ----
     for (int path = 0; path <= 2; ++path) {   // the refusals do not depend on the path asked for
         expect("null ctx", gram(nullptr, X.data(), SC_F64, n, 3, 5, path, 0, info), SC_ERR_INVALID, "null pointer");
         expect("null X", gram(c, nullptr, SC_F64, n, 3, 5, path, 0, info), SC_ERR_INVALID, "null pointer");
@@ -66,7 +89,7 @@ int main()
     expect("path = -1", gram(c, X.data(), SC_F64, n, 3, 5, -1, 0, info), SC_ERR_INVALID, "path must be 0");
     expect("path = 3", gram(c, X.data(), SC_F64, n, 3, 5, 3, 0, info), SC_ERR_INVALID, "path must be 0");
     // a refused call leaves the caller's record alone and no list claimed resident
-    if (info[0] != -1 || info[3] != -1 || ctx.df.knn_valid) {
+    if (info[0] != -1 || info[3] != -1 || ctx.knn.valid) {
         ++failures;
         printf("FAIL a refused call wrote to info_out or claimed resident lists\n");
     }

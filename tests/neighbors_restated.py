@@ -127,6 +127,27 @@ def duplicates(distinct=100, copies=40, d=50, seed=0):
     return np.tile(pca_like(distinct, d, seed), (copies, 1))
 
 
+def far_copies(d, m, dtype=np.float64):
+    """pca_like(1000, d, CERT_SEED) and, far from it, ``m`` copies of the point (1000, 0, .., 0).  A point repeated more
+    than L = k + slack times has D = 0 and lo_(L) <= 0, so exactly the copies miss the certificate: the fallback's list
+    holds ``m`` rows, the last ``m``."""
+    far = np.zeros((m, d))
+    far[:, 0] = 1000.0
+    return np.vstack([pca_like(1000, d, CERT_SEED), far]).astype(dtype)
+
+
+# (d, dtype, k, slack, m) of far_copies: the listed-row count at the edges of the fallback scan's block of 64 queries
+# (DF_QB_L).  The fewest rows that can be listed (m = L + 1, at k = 2 and at k = 15); one row short of a block, a block, one
+# and two blocks and a row (n = 1063 leaves a last candidate split of 7 < k: the merge sees sentinels); the LDS scan at the
+# padded widths 8 and 40, which the direct search never gives it; float32 input.
+LISTED_EDGE = [
+    (50, np.float64, 2, 1, 4), (50, np.float64, 15, 0, 24),
+    (50, np.float64, 15, 0, 63), (50, np.float64, 15, 0, 64), (50, np.float64, 15, 0, 65), (50, np.float64, 15, 0, 129),
+    (3, np.float64, 15, 0, 65), (33, np.float64, 15, 0, 65), (50, np.float32, 15, 0, 65),
+]
+LISTED_EDGE_IDS = [f"d{d}-{np.dtype(t).name}-k{k}-slack{s}-m{m}" for d, t, k, s, m in LISTED_EDGE]
+
+
 def recipes(n):
     """name -> features: the families of the bound and of the rule."""
     base = pca_like(n, 50, 1)

@@ -108,6 +108,37 @@ def test_forty_fold_duplicates_certify_no_row():
         assert not certified.any()
 
 
+@pytest.mark.parametrize("d, dtype, k, slack, m", N.LISTED_EDGE, ids=N.LISTED_EDGE_IDS)
+def test_far_copies_leave_exactly_the_copies_uncertified(d, dtype, k, slack, m):
+    """The samples on which tests/test_gpu_neighbors.py asserts rows_fallback == m: the m copies miss the certificate
+    (D = 0 and lo_(L) <= 0, whatever the rounding), every other row's margin is at least 1e6 of its largest E.
+
+    A row's largest E is taken in two parts, since E_ij grows with |x_j|^2 and a copy's norm is 1e6.  Among the first 1000
+    cells, which decide the row's kept list and its L-th key: margin >= 1e6 max_j E_ij.  The copies: their lo lies beyond
+    the row's L-th key by at least 1e6 of their own (larger) E, so no rounding brings one of them into the kept list."""
+    X = N.far_copies(d, m, dtype)
+    nrm = N.norms(X)
+    ce = N.c_e(d) * 2.0 ** -52
+    e_near = ce * (nrm[:1000] + nrm[:1000].max()) + N.TINY
+    e_far = ce * (nrm[:1000] + nrm[1000]) + N.TINY
+    _, d2, certified, margin = N.filtered_knn(X, k, slack)
+    lo_L = margin[:1000] + d2[:1000, k - 1]
+    lo_far = R.pair_d2(X, np.arange(1000), np.full(1000, 1000)) - e_far
+    near, far = (margin[:1000] / e_near).min(), ((lo_far - lo_L) / e_far).min()
+    print(f"far_copies d={d}, k={k}, slack={slack}, m={m}: over the first 1000 rows min (lo_(L) - D) / max E = {near:.3g}, "
+          f"min (lo_copy - lo_(L)) / E_copy = {far:.3g}")
+    assert certified[:1000].all() and not certified[1000:].any()
+    assert near >= 1e6 and far >= 1e6
+    assert np.all(d2[1000:] == 0.0) and np.all(margin[1000:] <= 0.0)
+
+
+@pytest.mark.parametrize("k, slack, m", [(15, 0, 23), (2, 1, 3)])
+def test_far_copies_no_more_than_the_list_holds_are_certified(k, slack, m):
+    """The control: m = L copies have L - 1 twins each, so the L-th kept candidate is a distant cell and every row is certified."""
+    _, _, certified, _ = N.filtered_knn(N.far_copies(50, m), k, slack)
+    assert certified.all()
+
+
 def test_lattice_certifies_some_rows_and_not_others():
     X = _recipe("lattice")
     _, _, certified, margin = N.filtered_knn(X, 15, 0)

@@ -87,6 +87,21 @@ def test_forty_fold_duplicates_all_take_the_fallback():
         assert _same((idx, d2), truth)
 
 
+@pytest.mark.parametrize("d, dtype, k, slack, m", N.LISTED_EDGE, ids=N.LISTED_EDGE_IDS)
+def test_fallback_at_listed_row_block_edges(d, dtype, k, slack, m):
+    """Exactly the ``m`` copies are listed for the fallback (the margins: test_cpu_neighbors.py), with ``m`` at the edges
+    of its scan's query block; their lists and everybody else's are the exact search's."""
+    X = N.far_copies(d, m, dtype)
+    truth = R.knn(X, k)
+    ctx = _ctx()
+    idx, d2, info = ctx.knn_dense_gram(X, k, path=2, slack=slack)
+    print(f"far_copies d={d} {np.dtype(dtype).name} k={k} slack={slack} m={m}: {info}")
+    assert info["rows_fallback"] == m
+    assert info["rows_certified"] == 1000
+    assert _same((idx, d2), truth)
+    assert _same((idx, d2), ctx.knn_dense(X, k))
+
+
 def test_lattice_is_certified_in_part():
     X, k = N.lattice(2000, 2), 15
     truth = R.knn(X, k)
