@@ -944,6 +944,52 @@ int sc_hvg_pearson(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, c
                    int32_t n_genes, double theta, double clip, double *sum_out, double *sumsq_out, double *resid_mean_out,
                    double *resid_var_out);
 
+/* ---- N19 (extension): Harmony batch correction of an embedding -- spatialcore_amd.integration --------
+ * Korsunsky et al. 2019, restated from the published algorithm (harmonypy's cluster / update_R / moe_correct_ridge for ONE
+ * one-hot covariate); parity with harmonypy is not pinned.  On-purpose differences: strided blocks (cell i is in block
+ * i mod n_blocks) in place of a random order, per-block tables that are summed and never subtracted, the row-minimum shift
+ * of the distances before exp.  fp64, no floating-point atomics, sums over cells in slices that depend on the shape alone
+ * and are added in slice order: every result is a function of the arguments alone, bit for bit.  sc_harmony.hip's head
+ * states the one expression order; tests/harmony_restated.py restates the algorithm.
+ * sc_harmony_begin: Z[n][d] row-major (SC_F32 or SC_F64), batch[n] codes in [0, n_batches), Y[K][d] the starting centres
+ *   (any scale; row-normalised here), n_blocks, sigma, theta, lamb.  Leaves on the device: Z, Zc = Z with unit rows,
+ *   dist = 2 (1 - Zc Y^T), S = exp(-(dist - rowmin) / sigma), R = S / rowsum, the per-block tables O[n_blocks][K][n_batches]
+ *   (O[t][k][b] = the sum of R[i][k] over the cells of block t and batch b); objective_out[0] = the objective of that state.
+ *   Validated on the host before the first HIP call: null pointers, dtype, 2 <= n <= 2^31 - 1, 1 <= d <= 64,
+ *   2 <= K <= min(128, n), 2 <= n_batches <= 64, 1 <= n_blocks <= min(1024, n), every code in range, every batch with a
+ *   cell, Z and Y finite without an all-zero row, sigma > 0, theta >= 0, lamb > 0 (all finite).
+ * sc_harmony_cluster: at most max_iter (1 .. 4096) clustering rounds.  A round: Y = the row-normalised R^T Zc (a cluster
+ *   without mass keeps its centre); dist and S again; then the blocks in order, for block t: O- = the sum of the other
+ *   blocks' tables in ascending order, E-_kb = (sum_b O-_kb) n_b / n, R_ik proportional to S_ik ((E-_kb + 1) / (O-_kb + 1))^theta
+ *   for the block's cells, and O[t] rebuilt from them; then the objective sum R dist + sigma sum R log R + sigma theta
+ *   sum_i sum_k R_ik log((O_kb(i) + 1) / (E_kb(i) + 1)).  objectives_out[r] = the objective after round r, rounds_out = the
+ *   rounds done.  Stops after round r > 3 when |old - new| / |old| < epsilon with old = obj[r-1] + obj[r-2] + obj[r-3] and
+ *   new = obj[r] + obj[r-1] + obj[r-2] (harmonypy's window of 3); epsilon < 0 never stops and waits for the device once.
+ *   9 + 2 n_blocks launches per round.
+ * sc_harmony_correct: per cluster the ridge system [[s, o^T], [o, diag(o + lamb)]] of the one-hot design, in closed form:
+ *   r_b = sum_{i in b} R_ik Z_i (the original Z), r_0 = sum_b r_b, w_0 = (r_0 - sum_b o_b r_b / (o_b + lamb)) / (s - sum_b
+ *   o_b^2 / (o_b + lamb)), W_kb = (r_b - o_b w_0) / (o_b + lamb), intercept dropped; Zcorr_i = Z_i - sum_k R_ik W_kb(i) and
+ *   Zc = Zcorr with unit rows.
+ * sc_harmony_get: one array of the resident state in the CALLER's cell order: SC_HARMONY_ZCORR / _ZC [n][d] (Zcorr is Z
+ *   before the first correction), _R / _DIST [n][K], _Y [K][d], _O [n_blocks][K][n_batches], _W [K][n_batches][d] (zero
+ *   before the first correction), all double; _ORDER int64[n], the cell at every position of the (block, batch, cell) sort.
+ * sc_harmony_end frees the state (also done by the next sc_harmony_begin and by sc_ctx_destroy). */
+#define SC_HARMONY_ZCORR 0
+#define SC_HARMONY_ZC 1
+#define SC_HARMONY_R 2
+#define SC_HARMONY_Y 3
+#define SC_HARMONY_O 4
+#define SC_HARMONY_W 5
+#define SC_HARMONY_ORDER 6
+#define SC_HARMONY_DIST 7
+int sc_harmony_begin(sc_ctx *ctx, const void *Z, int dtype, int64_t n, int32_t d, const int32_t *batch, int32_t n_batches,
+                     const double *Y, int32_t K, int32_t n_blocks, double sigma, double theta, double lamb,
+                     double *objective_out);
+int sc_harmony_cluster(sc_ctx *ctx, int32_t max_iter, double epsilon, int32_t *rounds_out, double *objectives_out);
+int sc_harmony_correct(sc_ctx *ctx);
+int sc_harmony_get(sc_ctx *ctx, int32_t what, void *out);
+int sc_harmony_end(sc_ctx *ctx);
+
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across
  * one process per GPU with no data-path communication; at the end ONE ncclAllGather over RCCL (xGMI inside a node)

@@ -1,12 +1,12 @@
 """spatialcore_amd -- MI355X-native drop-in for the spatialcore.spatial hot path."""
 from spatialcore_amd._adata import SimpleAnnData
 
-__all__ = ["SimpleAnnData", "init", "diffusion", "neighbors", "embedding", "preprocessing"]
+__all__ = ["SimpleAnnData", "init", "diffusion", "neighbors", "embedding", "preprocessing", "integration"]
 __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name in ("diffusion", "neighbors", "embedding", "preprocessing"):   # imported on first use: the subpackages pull in scipy.linalg
+    if name in ("diffusion", "neighbors", "embedding", "preprocessing", "integration"):   # imported on first use: the subpackages pull in scipy.linalg
         import importlib
 
         return importlib.import_module("spatialcore_amd." + name)

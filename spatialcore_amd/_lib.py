@@ -35,6 +35,7 @@ K_LOUVAIN_MOVE, K_LOUVAIN_LEVEL = 39, 40
 K_NEIGHBORS_GRAM = 41
 K_UMAP_GRAPH, K_UMAP_LAYOUT = 42, 43
 K_HVG_SETUP, K_HVG_DENSE, K_HVG_SPARSE = 44, 45, 46
+HARMONY_ARRAYS = {"Zcorr": 0, "Zc": 1, "R": 2, "Y": 3, "O": 4, "W": 5, "order": 6, "dist": 7}   # sc_harmony_get's codes
 ANNOT_MODES = {"counts": 0, "log1p": 1, "log1p_renorm": 2}   # sc_annot_*'s input states
 NMF_LOSSES = {"frobenius": 2, "kullback-leibler": 1}   # sc_nmf_fit's codes (sklearn's beta)
 METAGENE_METHODS = ("shifted_geometric_mean", "geometric_mean", "arithmetic_mean", "median", "minimum")   # sc_metagene_score's codes
@@ -154,6 +155,11 @@ SYMBOLS = {
     "sc_pca_project": [_P, _P, _P, c_int32, c_int, _P],
     "sc_pca_end": [_P],
     "sc_hvg_pearson": [_P, _P, _P, _P, c_int, c_int64, c_int32, c_double, c_double, _P, _P, _P, _P],
+    "sc_harmony_begin": [_P, _P, c_int, c_int64, c_int32, _P, c_int32, _P, c_int32, c_int32, c_double, c_double, c_double, _P],
+    "sc_harmony_cluster": [_P, c_int32, c_double, _P, _P],
+    "sc_harmony_correct": [_P],
+    "sc_harmony_get": [_P, c_int32, _P],
+    "sc_harmony_end": [_P],
     "sc_louvain_begin": [_P, _P, _P, _P, c_int64, c_int32, c_int32],
     "sc_louvain_resident_weights": [_P, _P, c_int64],
     "sc_louvain_begin_resident": [_P, _P, c_int64, c_int32, c_int32],
@@ -281,6 +287,7 @@ class Context:
         self._ripley_g_radii = 0   # ... and of the resident Ripley's G neighbour lists
         self._annot_shape = None   # (classes, genes) of the resident training problem (annot_train_begin .. annot_train_end)
         self._pca_shape = None     # (cells, genes) of the resident PCA matrix (pca_begin .. pca_end)
+        self._harmony = None       # (n, d, K, B, blocks) of the resident Harmony problem (harmony_begin .. harmony_end)
         self._louvain_n = None     # vertices of the next Louvain level (louvain_begin .. louvain_end)
         self._diff_n = self._diff_nnz = self._lanczos_cap = 0   # cells / stored entries of the resident diffusion graph, Lanczos basis cap
 
@@ -1092,6 +1099,63 @@ class Context:
                                         SC_F32 if data.dtype == np.float32 else SC_F64, n, G, float(theta), float(clip),
                                         _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3])))
         return out[0], out[1], out[2], out[3]
+
+
+    # ---- N19: harmony_integrate ----------------------------------------------------------------
+    def harmony_begin(self, Z, batch, n_batches: int, Y, n_blocks: int, sigma: float, theta: float, lamb: float) -> float:
+        """sc_harmony_begin: leaves Z (n, d; float32 or float64), its unit rows, the assignments from the centres Y (K, d) and
+        the per-block tables on the device; returns the objective of that state."""
+        Z = np.ascontiguousarray(Z)
+        if Z.dtype not in (np.float32, np.float64) or Z.ndim != 2:
+            raise ValueError(f"harmony_begin: Z must be a 2-D float32 or float64 array, got {Z.dtype} {Z.shape}")
+        batch, Y = _c(batch, np.int32), _c(Y, np.float64)
+        n, d = Z.shape
+        if batch.shape != (n,) or Y.ndim != 2 or Y.shape[1] != d:
+            raise ValueError(f"harmony_begin: batch must have {n} entries and Y {d} columns")
+        self._harmony = None   # until the call succeeds this object vouches for no resident problem
+        obj = c_double(0.0)
+        _check(self._lib.sc_harmony_begin(self._h, _ptr(Z), SC_F32 if Z.dtype == np.float32 else SC_F64, n, d, _ptr(batch),
+                                          int(n_batches), _ptr(Y), Y.shape[0], int(n_blocks), float(sigma), float(theta),
+                                          float(lamb), byref(obj)))
+        self._harmony = (n, d, Y.shape[0], int(n_batches), int(n_blocks))
+        return obj.value
+
+    def _harmony_dims(self, who: str):
+        if self._harmony is None:
+            raise SpatialCoreHipError(f"{who}: no problem is resident (harmony_begin)")
+        return self._harmony
+
+    def harmony_cluster(self, max_iter: int, epsilon: float) -> np.ndarray:
+        """sc_harmony_cluster: the objective after every clustering round done (at most ``max_iter``; ``epsilon`` < 0 runs
+        them all)."""
+        self._harmony_dims("harmony_cluster")
+        if not 1 <= int(max_iter) <= 4096:
+            raise ValueError(f"harmony_cluster: need 1 <= max_iter <= 4096, got {max_iter}")
+        out = np.empty(int(max_iter), dtype=np.float64)
+        rounds = c_int32(0)
+        _check(self._lib.sc_harmony_cluster(self._h, int(max_iter), float(epsilon), byref(rounds), _ptr(out)))
+        return out[:rounds.value].copy()
+
+    def harmony_correct(self) -> None:
+        """sc_harmony_correct: the ridge correction from the resident assignments; Zcorr, Zc and W change."""
+        self._harmony_dims("harmony_correct")
+        _check(self._lib.sc_harmony_correct(self._h))
+
+    def harmony_get(self, name: str) -> np.ndarray:
+        """sc_harmony_get: "Zcorr" / "Zc" (n, d), "R" / "dist" (n, K), "Y" (K, d), "O" (blocks, K, B), "W" (K, B, d) as
+        float64 in the caller's cell order; "order" (n,) int64, the cell at every position of the device's sort."""
+        n, d, K, B, nb = self._harmony_dims("harmony_get")
+        if name not in HARMONY_ARRAYS:
+            raise ValueError(f"harmony_get: unknown array {name!r}; one of {sorted(HARMONY_ARRAYS)}")
+        shape = {"Zcorr": (n, d), "Zc": (n, d), "R": (n, K), "dist": (n, K), "Y": (K, d), "O": (nb, K, B), "W": (K, B, d),
+                 "order": (n,)}[name]
+        out = np.empty(shape, dtype=np.int64 if name == "order" else np.float64)
+        _check(self._lib.sc_harmony_get(self._h, HARMONY_ARRAYS[name], _ptr(out)))
+        return out
+
+    def harmony_end(self) -> None:
+        self._harmony = None
+        _check(self._lib.sc_harmony_end(self._h))
 
     # ---- N16 (extension): Louvain communities ---------------------------------------------------
     def louvain_begin(self, indptr, indices, q, g: int, max_rounds: int) -> None:

@@ -242,6 +242,7 @@ int sc_ctx_destroy(sc_ctx *c)
     sc_annot_release(c);
     sc_pca_release(c);
     sc_louvain_release(c);
+    sc_harmony_release(c);
     c->pg.release(&c->mem);
     for (int k = 0; k < SC_K_COUNT_; ++k) {
         for (auto &ev : c->timers[k].pending) {

@@ -223,6 +223,8 @@ struct sc_ctx {
     struct PcaState *pca = nullptr;
     // ---- Louvain (sc_louvain.hip): the level graphs and the partition kept on the device between sc_louvain_begin and _end ----
     struct LouvainState *louvain = nullptr;
+    // ---- Harmony (sc_harmony.hip): the embedding, the assignments and the block tables between sc_harmony_begin and _end ----
+    struct HarmonyState *harmony = nullptr;
 
     // ---- graph (CSR, rows sorted by column) + transpose ----
     int64_t g_n = 0, g_nnz = 0;
@@ -429,5 +431,6 @@ int sc_kmeans_run_labels(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t
 void sc_annot_release(sc_ctx *c);   // drops the resident training problem, if any (sc_annotate.hip)
 void sc_pca_release(sc_ctx *c);     // drops the resident PCA matrix, if any (sc_pca.hip)
 void sc_louvain_release(sc_ctx *c); // drops the resident Louvain hierarchy, if any (sc_louvain.hip)
+void sc_harmony_release(sc_ctx *c); // drops the resident Harmony problem, if any (sc_harmony.hip)
 void sc_launch_spmv_vec(sc_ctx *c, const int64_t *indptr, const int32_t *indices, const double *w,
                         const double *x, double *y, int64_t n);

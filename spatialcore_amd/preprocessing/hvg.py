@@ -15,9 +15,9 @@ import numbers
 from typing import Optional
 
 import numpy as np
-import pandas as pd
 
 from spatialcore_amd import _lib
+from spatialcore_amd._batches import batch_groups
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
 from spatialcore_amd._sparse_input import canonical_csr, gene_columns
@@ -92,26 +92,6 @@ def _check_positive(name: str, value, note: str = "") -> float:
     return float(value)
 
 
-def _batches(adata, batch_key):
-    """[(category, its rows ascending)] in sorted category order."""
-    if not isinstance(batch_key, str) or batch_key not in adata.obs:
-        raise ValueError(f"batch_key={batch_key!r} is not a column of adata.obs")
-    values = np.asarray(adata.obs[batch_key])
-    if pd.isna(values).any():
-        raise ValueError(f"adata.obs[{batch_key!r}] has missing values")
-    try:
-        cats, codes = np.unique(values, return_inverse=True)
-    except TypeError:
-        raise ValueError(f"adata.obs[{batch_key!r}] mixes values that cannot be sorted") from None
-    out = []
-    for b, cat in enumerate(cats):
-        rows = np.flatnonzero(codes == b)
-        if rows.size < 2:
-            raise ValueError(f"batch {cat!r} of adata.obs[{batch_key!r}] has {rows.size} cell; every batch needs at least 2")
-        out.append((cat.item() if hasattr(cat, "item") else cat, rows))
-    return out
-
-
 def _check_part(Xc, what: str) -> None:
     """What one device call needs of its rows, checked before the device is touched; warns about cells without a count."""
     n = Xc.shape[0]
@@ -179,7 +159,7 @@ def highly_variable_genes(adata, *, n_top_genes: int = 2000, flavor: str = "pear
     n_all = int(X.shape[0])
     if not 2 <= n_all <= 2**31 - 1:
         raise ValueError(f"highly_variable_genes needs 2 <= cells <= 2^31 - 1, got {n_all}; supported: {_SUPPORTED}")
-    groups = None if batch_key is None else _batches(adata, batch_key)
+    groups = None if batch_key is None else batch_groups(adata, batch_key)
     Xc, _ = canonical_csr(X, cols, len(adata.var_names), real=True,
                           negative="Pearson residuals need raw counts; the expression matrix has negative entries",
                           all_zero="the expression matrix is all zero: there is nothing to rank")
