@@ -377,11 +377,6 @@ __global__ __launch_bounds__(256) void k_an_gradfinish(const int64_t *__restrict
 struct AnnotData {   // the matrix on the device (m.val: the D values in row order), the scaler
     CsrDevice m;
     DBuf mean, scale, z0, table, base;
-    void release(int64_t *acct)
-    {
-        m.release(acct);
-        for (DBuf *b : {&mean, &scale, &z0, &table, &base}) b->release(acct);
-    }
 };
 
 int an_lanes(int T) { return lanes_for(T, 2, 64); }
@@ -476,22 +471,10 @@ void an_launch_transform(sc_ctx *c, const V *scores, int64_t n, int T, double *c
     }
 }
 
-struct Releaser {   // frees a call's own buffers on every return path
-    sc_ctx *c;
-    AnnotData *d;
-    std::vector<DBuf *> more;
-    ~Releaser()
-    {
-        (void)hipStreamSynchronize(c->stream);
-        if (d) d->release(&c->mem);
-        for (DBuf *b : more) b->release(&c->mem);
-    }
-};
-
 }  // namespace
 
 // the training problem resident between sc_annot_train_begin and sc_annot_train_end
-struct AnnotTrain {
+struct AnnotTrain : Resident {
     AnnotData d;
     ColSort cs;
     DBuf labels, sw, S, Dir, R, cellpart, cellsum, colpart, grad, alpha;
@@ -499,22 +482,8 @@ struct AnnotTrain {
     int G = 0, T = 0;
     bool have_scores = false, have_dir = false;
     std::vector<double> z0, tab, base;
-    void release(int64_t *acct)
-    {
-        d.release(acct);
-        cs.release(acct);
-        for (DBuf *b : {&labels, &sw, &S, &Dir, &R, &cellpart, &cellsum, &colpart, &grad, &alpha}) b->release(acct);
-    }
 };
-
-void sc_annot_release(sc_ctx *c)
-{
-    if (!c->an) return;
-    (void)hipStreamSynchronize(c->stream);
-    c->an->release(&c->mem);
-    delete c->an;
-    c->an = nullptr;
-}
+static AnnotTrain *an_state(const sc_ctx *c) { return resident<AnnotTrain>(c->an); }
 
 extern "C" int sc_annot_predict(sc_ctx *c, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
                                 int32_t n_genes, int32_t mode, int32_t T, const double *coef, const double *intercept,
@@ -538,7 +507,7 @@ extern "C" int sc_annot_predict(sc_ctx *c, const int64_t *indptr, const int32_t 
     hipStream_t s = c->stream;
     AnnotData d;
     DBuf o32, lab, conf;
-    Releaser rel{c, &d, {&o32, &lab, &conf}};
+    StreamWaitOnExit wait{c->stream};   // after the buffers and z0 / tab / base, which the copies read
     SC_TRY(an_upload(c, d, indptr, indices, data, dtype, n, G, mode, nnz));
     SC_HIP(hipMemcpyAsync(d.mean.p, mean, sizeof(double) * (size_t)G, hipMemcpyHostToDevice, s));
     SC_HIP(hipMemcpyAsync(d.scale.p, scale, sizeof(double) * (size_t)G, hipMemcpyHostToDevice, s));
@@ -578,7 +547,7 @@ extern "C" int sc_annot_transform(sc_ctx *c, const void *scores, int dtype, int6
     SC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     DBuf in, conf;
-    Releaser rel{c, nullptr, {&in, &conf}};
+    StreamWaitOnExit wait{c->stream};
     const size_t bytes = (dtype == SC_F32 ? sizeof(float) : sizeof(double)) * (size_t)n * T;
     SC_TRY(in.ensure(bytes, &c->mem));
     SC_TRY(conf.ensure(sizeof(double) * (size_t)n * 4, &c->mem));
@@ -608,14 +577,13 @@ extern "C" int sc_annot_train_begin(sc_ctx *c, const int64_t *indptr, const int3
                    (long long)i);
     }
     SC_HIP(hipSetDevice(c->device));
-    sc_annot_release(c);
-    c->an = new AnnotTrain();
-    AnnotTrain &a = *c->an;
+    sc_resident_drop(c, c->an);
+    c->an.reset(new AnnotTrain());
+    AnnotTrain &a = *an_state(c);
     hipStream_t s = c->stream;
     const int G = n_genes;
     a.G = G, a.T = T, a.cell_chunks = ceil_div64(n, AN_CELL_CHUNK);
-    auto fail = [&](int rc) { sc_annot_release(c); return rc; };
-#define AN_TRY(call) do { int rc_ = (call); if (rc_ != SC_OK) return fail(rc_); } while (0)
+#define AN_TRY(call) do { int rc_ = (call); if (rc_ != SC_OK) { sc_resident_drop(c, c->an); return rc_; } } while (0)
     AN_TRY(an_upload(c, a.d, indptr, indices, data, dtype, n, G, mode, nnz));
     AN_TRY(colsort_alloc(c, a.cs, nnz, G));
     AN_TRY(a.labels.ensure(sizeof(int32_t) * (size_t)n, &c->mem));
@@ -630,7 +598,8 @@ extern "C" int sc_annot_train_begin(sc_ctx *c, const int64_t *indptr, const int3
     if (hipMemcpyAsync(a.labels.p, labels, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(a.sw.p, weights, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s) != hipSuccess) {
         sc_set_error("%s: upload failed", who);
-        return fail(SC_ERR_HIP);
+        sc_resident_drop(c, c->an);
+        return SC_ERR_HIP;
     }
     {
         KernelTimerScope ts(c, SC_K_ANNOT_SETUP);
@@ -660,7 +629,8 @@ extern "C" int sc_annot_train_begin(sc_ctx *c, const int64_t *indptr, const int3
         hipMemcpyAsync(a.z0.data(), a.d.z0.p, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) {
         sc_set_error("%s: set-up failed on the device: %s", who, hipGetErrorString(hipGetLastError()));
-        return fail(SC_ERR_HIP);
+        sc_resident_drop(c, c->an);
+        return SC_ERR_HIP;
     }
 #undef AN_TRY
     return SC_OK;
@@ -673,7 +643,7 @@ extern "C" int sc_annot_train_forward(sc_ctx *c, const double *coef, const doubl
     SC_REQUIRE(c && coef && bias, SC_ERR_INVALID, "%s: null pointer", who);
     SC_REQUIRE(c->an, SC_ERR_STATE, "%s: no training problem is resident (sc_annot_train_begin)", who);
     SC_REQUIRE(which == 0 || which == 1, SC_ERR_INVALID, "%s: which must be 0 (scores) or 1 (direction), got %d", who, which);
-    AnnotTrain &a = *c->an;
+    AnnotTrain &a = *an_state(c);
     for (int64_t q = 0; q < (int64_t)a.T * a.G; ++q) SC_REQUIRE(std::isfinite(coef[q]), SC_ERR_INVALID, "%s: coefficients must be finite", who);
     for (int t = 0; t < a.T; ++t) SC_REQUIRE(std::isfinite(bias[t]), SC_ERR_INVALID, "%s: biases must be finite", who);
     SC_HIP(hipSetDevice(c->device));
@@ -693,8 +663,8 @@ extern "C" int sc_annot_train_grad(sc_ctx *c, double *grad_out, double *loss_out
 {
     const char *who = "sc_annot_train_grad";
     SC_REQUIRE(c && grad_out && loss_out, SC_ERR_INVALID, "%s: null pointer", who);
-    SC_REQUIRE(c->an && c->an->have_scores, SC_ERR_STATE, "%s: no scores are resident (sc_annot_train_forward with which = 0)", who);
-    AnnotTrain &a = *c->an;
+    SC_REQUIRE(c->an && an_state(c)->have_scores, SC_ERR_STATE, "%s: no scores are resident (sc_annot_train_forward with which = 0)", who);
+    AnnotTrain &a = *an_state(c);
     SC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int T = a.T, G = a.G, tp = an_lanes(T), nb = (T + 63) / 64;
@@ -739,8 +709,8 @@ extern "C" int sc_annot_train_line(sc_ctx *c, const double *alpha, double *d1_ou
 {
     const char *who = "sc_annot_train_line";
     SC_REQUIRE(c && alpha && d1_out && d2_out, SC_ERR_INVALID, "%s: null pointer", who);
-    SC_REQUIRE(c->an && c->an->have_scores && c->an->have_dir, SC_ERR_STATE, "%s: needs resident scores and a direction product", who);
-    AnnotTrain &a = *c->an;
+    SC_REQUIRE(c->an && an_state(c)->have_scores && an_state(c)->have_dir, SC_ERR_STATE, "%s: needs resident scores and a direction product", who);
+    AnnotTrain &a = *an_state(c);
     SC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     SC_TRY(an_upload_alpha(c, a, who, alpha));
@@ -766,8 +736,8 @@ extern "C" int sc_annot_train_step(sc_ctx *c, const double *alpha)
 {
     const char *who = "sc_annot_train_step";
     SC_REQUIRE(c && alpha, SC_ERR_INVALID, "%s: null pointer", who);
-    SC_REQUIRE(c->an && c->an->have_scores && c->an->have_dir, SC_ERR_STATE, "%s: needs resident scores and a direction product", who);
-    AnnotTrain &a = *c->an;
+    SC_REQUIRE(c->an && an_state(c)->have_scores && an_state(c)->have_dir, SC_ERR_STATE, "%s: needs resident scores and a direction product", who);
+    AnnotTrain &a = *an_state(c);
     SC_HIP(hipSetDevice(c->device));
     SC_TRY(an_upload_alpha(c, a, who, alpha));
     const int64_t total = a.d.m.n * a.T;
@@ -785,6 +755,6 @@ extern "C" int sc_annot_train_end(sc_ctx *c)
 {
     SC_REQUIRE(c, SC_ERR_INVALID, "sc_annot_train_end: null pointer");
     SC_HIP(hipSetDevice(c->device));
-    sc_annot_release(c);
+    sc_resident_drop(c, c->an);
     return SC_OK;
 }

@@ -29,15 +29,11 @@ void sc_set_error(const char *fmt, ...)
     va_end(ap);
 }
 
-int DBuf::ensure(size_t bytes, int64_t *acct)
+int DBuf::ensure(size_t bytes, int64_t *charge_to)
 {
     if (bytes <= cap) return SC_OK;
-    if (p) {
-        (void)hipFree(p);
-        *acct -= (int64_t)cap;
-        p = nullptr;
-        cap = 0;
-    }
+    release();
+    acct = charge_to;
     // round up so that small growth does not re-allocate
     size_t want = (bytes + 255) & ~(size_t)255;
     hipError_t e = hipMalloc(&p, want);
@@ -51,7 +47,7 @@ int DBuf::ensure(size_t bytes, int64_t *acct)
     return SC_OK;
 }
 
-void DBuf::release(int64_t *acct)
+void DBuf::release()
 {
     if (p) {
         (void)hipFree(p);
@@ -112,12 +108,19 @@ int StreamTable::replace(int new_placement, const int *new_level)
     return SC_OK;
 }
 
-void StreamTable::release()
+StreamTable::~StreamTable()
 {
-    for (hipStream_t &sp : s) {
+    for (hipStream_t sp : s)
         if (sp) (void)hipStreamDestroy(sp);
-        sp = nullptr;
-    }
+}
+
+KTimer::~KTimer()
+{
+    for (auto *list : {&pending, &pool})
+        for (auto &ev : *list) {
+            (void)hipEventDestroy(ev.first);
+            (void)hipEventDestroy(ev.second);
+        }
 }
 
 KernelTimerScope::KernelTimerScope(sc_ctx *ctx, int kid, hipStream_t on) : c(ctx), id(kid), s(on ? on : ctx->stream)
@@ -220,41 +223,8 @@ int sc_ctx_destroy(sc_ctx *c)
     if (c->mom_done) (void)hipEventDestroy(c->mom_done);
     if (c->knn_done) (void)hipEventDestroy(c->knn_done);
     (void)hipStreamSynchronize(c->stream);
-    DBuf *bufs[] = {&c->px, &c->py, &c->sx, &c->sy, &c->sid, &c->bin_start, &c->bin_keys,
-                    &c->bin_keys2, &c->sid2, &c->cub_tmp, &c->knn_idx, &c->knn_rd, &c->knn_hd, &c->knn_hi, &c->rad_indptr,
-                    &c->g_indptr, &c->g_indices, &c->g_data, &c->gt_indptr, &c->gt_indices,
-                    &c->gt_data, &c->gt_cursor, &c->gt_tmp, &c->mom_dev, &c->X, &c->Z, &c->Lag, &c->X32, &c->inv, &c->e_tmp_indptr,
-                    &c->e_tmp_indices, &c->e_tmp_data, &c->e_colmap, &c->g_mean, &c->g_var,
-                    &c->g_z2, &c->g_scale, &c->g_Inum, &c->g_I, &c->red_tmp, &c->perm, &c->perm_flag,
-                    &c->partial, &c->sims, &c->counts, &c->sim_sum, &c->sim_sumsq, &c->scratch_a,
-                    &c->scratch_b, &c->scratch_out, &c->scratch_idx, &c->lee_U, &c->lee_Zc, &c->lee_Uc, &c->lee_part, &c->lee_obs, &c->lee_cnt,
-                    &c->lee_rowmap, &c->lee_lperm, &c->g_slag, &c->g_xsum, &c->g_flags, &c->g_xmax, &c->g_lat, &c->g_meanc, &c->g_seff, &c->g_corr, &c->g_thr, &c->sims_raw, &c->g_order, &c->g_rank, &c->g_indices_r, &c->g_w32, &c->g_erow_r, &c->lm_ys, &c->lm_out, &c->lm_tab, &c->s0_tmp, &c->nib_map,
-                    &c->np_cnt, &c->np_comp, &c->np_leaves, &c->np_leafsum,
-                    &c->rp_cnt, &c->rp_indptr, &c->rp_row, &c->rp_col, &c->rp_bin, &c->rp_rank,
-                    &c->rg_cnt, &c->rg_indptr, &c->rg_col, &c->rg_bin, &c->rg_rank,
-                    &c->dm_parent, &c->dm_qcomp, &c->dm_clear,
-                    &c->rs_order, &c->rs_pstart, &c->rs_pgroup, &c->rs_gpiece, &c->rs_groupn, &c->rs_psum, &c->rs_pnnz, &c->rs_poff,
-                    &c->rs_goff, &c->rs_neg, &c->rs_flag, &c->rs_keys, &c->rs_keys2, &c->rs_pay, &c->rs_pay2, &c->rs_gkey, &c->rs_gkey2,
-                    &c->rs_idx, &c->rs_idx2, &c->rs_tmp, &c->rs_rank2, &c->rs_tie, &c->rs_nnz, &c->rs_sum, &c->th_sorted};
-    for (DBuf *b : bufs) b->release(&c->mem);
-    for (DBuf *b : c->knn.bufs()) b->release(&c->mem);
-    for (DBuf *b : c->df.bufs()) b->release(&c->mem);
-    sc_annot_release(c);
-    sc_pca_release(c);
-    sc_louvain_release(c);
-    sc_harmony_release(c);
-    c->pg.release(&c->mem);
-    for (int k = 0; k < SC_K_COUNT_; ++k) {
-        for (auto &ev : c->timers[k].pending) {
-            (void)hipEventDestroy(ev.first);
-            (void)hipEventDestroy(ev.second);
-        }
-        for (auto &ev : c->timers[k].pool) {
-            (void)hipEventDestroy(ev.first);
-            (void)hipEventDestroy(ev.second);
-        }
-    }
-    c->streams.release();
+    // the members free themselves, in the order sc_ctx (sc_ctx.h) states: buffers and resident problems, the generator,
+    // the timer events, the streams last
     delete c;
     return SC_OK;
 }

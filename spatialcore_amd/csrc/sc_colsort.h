@@ -98,10 +98,6 @@ __global__ __launch_bounds__(256) void k_chunk_add(const double *__restrict__ pa
 struct ColSort {
     DBuf keys, gene, pos, pos2, rowid, crow, cval, colptr, cptr, cgene;
     int64_t chunks = 0;
-    void release(int64_t *acct)
-    {
-        for (DBuf *b : {&keys, &gene, &pos, &pos2, &rowid, &crow, &cval, &colptr, &cptr, &cgene}) b->release(acct);
-    }
 };
 
 // Allocates the arrays for nnz stored entries and G genes (everything but cgene, whose size is known after the scan).

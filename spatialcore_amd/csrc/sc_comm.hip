@@ -83,8 +83,8 @@ struct sc_comm {
     sc_ctx *ctx = nullptr;
     RcclComm comm = nullptr;
     int world = 1, rank = 0;
+    int64_t mem = 0;   // declared before the buffers, which take their bytes off it when they go
     DBuf send, recv;
-    int64_t mem = 0;
 };
 
 extern "C" int sc_comm_unique_id(uint8_t *id_out)
@@ -126,8 +126,8 @@ extern "C" int sc_comm_destroy(sc_comm *m)
     if (!m) return SC_OK;
     if (m->ctx) (void)hipSetDevice(m->ctx->device);
     if (m->comm && g_rccl.comm_destroy) (void)g_rccl.comm_destroy(m->comm);
-    m->send.release(&m->mem);
-    m->recv.release(&m->mem);
+    m->send.release();
+    m->recv.release();
     delete m;
     return SC_OK;
 }

@@ -81,10 +81,6 @@ struct CsrDevice {
         }
         return SC_OK;
     }
-    void release(int64_t *acct)
-    {
-        for (DBuf *b : {&indptr, &indices, &raw, &val}) b->release(acct);
-    }
 };
 
 }  // namespace

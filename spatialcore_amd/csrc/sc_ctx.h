@@ -42,13 +42,37 @@ void sc_set_error(const char *fmt, ...);
         }                              \
     } while (0)
 
-// Device buffer that only ever grows; freed with the context.
+// Device buffer that only ever grows and frees itself with its owner: the context, a resident problem or a call
+// (DESIGN.md "Device memory").  It remembers the counter its bytes were charged to and takes them off again when it dies;
+// a buffer that never allocated makes no HIP call.  Moving leaves the source empty; copying is not possible.
 struct DBuf {
     void *p = nullptr;
     size_t cap = 0;
-    int ensure(size_t bytes, int64_t *acct);
-    void release(int64_t *acct);
+    int64_t *acct = nullptr;   // the counter `cap` is charged to (the one handed to ensure)
+    DBuf() = default;
+    DBuf(const DBuf &) = delete;
+    DBuf &operator=(const DBuf &) = delete;
+    DBuf(DBuf &&o) noexcept : p(o.p), cap(o.cap), acct(o.acct) { o.p = nullptr, o.cap = 0; }
+    DBuf &operator=(DBuf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p, cap = o.cap, acct = o.acct;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~DBuf() { release(); }
+    int ensure(size_t bytes, int64_t *charge_to);
+    void release();   // gives the memory back early; the buffer is empty again and may grow anew
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
+// Waits for the context stream when its scope ends.  A call whose buffers (or host vectors that an asynchronous copy
+// still reads) may be in use on an early return declares one AFTER them, so that the wait runs before they go.
+struct StreamWaitOnExit {
+    hipStream_t &stream;
+    ~StreamWaitOnExit() { (void)hipStreamSynchronize(stream); }
 };
 
 struct KTimer {
@@ -56,6 +80,9 @@ struct KTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
     double ms = 0.0;
     int64_t launches = 0;
+    KTimer() = default;
+    KTimer(const KTimer &) = delete;
+    ~KTimer();   // destroys the events of both lists
 };
 
 // The one owner of a context's streams (sc_streams.h: roles, placements; sc_api.hip).  A role's stream is created on
@@ -71,7 +98,9 @@ struct StreamTable {
     int sync(unsigned roles);            // wait for the existing streams among `roles` (bit r = role r)
     // Take another placement.  Existing streams must be idle: they are destroyed and created again where they belong.
     int replace(int new_placement, const int *new_level);
-    void release();
+    StreamTable() = default;
+    StreamTable(const StreamTable &) = delete;
+    ~StreamTable();                      // destroys the streams
 };
 
 // The numpy-exact permutation generator's state in the context (sc_permgen.h): scratch, its events, its form, counters
@@ -100,15 +129,15 @@ struct PermGen {
             if (!e) SC_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         return SC_OK;
     }
-    int sync() { return streams->sync(SR_MASK_GENERATOR); }   // wait for the generator's own streams
+    int sync() { return streams ? streams->sync(SR_MASK_GENERATOR) : SC_OK; }   // wait for the generator's own streams
     // sc_ctx_set_permgen_mode.  Re-arms: a context that fell back to the sequential scan after one stalled hand-over (a transient: GPU
     // shared with another process, a profiler pass) goes through the placement ladder again and may return to the block-parallel form
     void rearm(int new_mode) { mode = new_mode; streams_serial = false; probed = false; note.clear(); placement_note.clear(); }
-    void release(int64_t *acct)      // buffers, events (the streams are the table's)
+    PermGen() = default;
+    PermGen(const PermGen &) = delete;
+    ~PermGen()                       // waits for its streams (the table's, which outlives it), drops the events; then the buffers go
     {
         (void)sync();
-        for (DBuf *b : {&J, &raw, &out, &bits, &enter, &sblk, &flags, &desc, &tbits, &events, &hard, &seglist, &seg, &ctbits, &segmode})
-            b->release(acct);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
     }
@@ -126,8 +155,21 @@ struct MoranRing {
 
 struct PermPipe;   // a generator job in flight (sc_permgen.h, sc_perm.hip; begun by sc_moran_seeded_begin, consumed by _finish)
 
+// A problem kept on the device between a _begin and an _end (annotation training, PCA, Louvain, Harmony).  Its type is
+// complete only in its own file; the context owns it through this base.
+struct Resident {
+    virtual ~Resident() = default;
+};
+template <class T> T *resident(const std::unique_ptr<Resident> &r) { return static_cast<T *>(r.get()); }
+
+// Teardown (sc_ctx_destroy, then the members in reverse declaration order) relies on that order in three places:
+// `mem` is declared before every DBuf, since each takes its bytes off it when it dies; `streams` and `timers` are
+// declared before `pg`, every DBuf and the resident problems, so that the buffers go first, then the generator (which
+// waits for its streams and drops its events), then the timer events, and the streams last.  sc_ctx_destroy has waited
+// for the work in flight before any of this runs.  A new DBuf member needs no line anywhere else.
 struct sc_ctx {
     int device = 0;
+    int64_t mem = 0;  // bytes allocated through DBuf
     std::unique_ptr<PermPipe> pipe;  // the generator / consumer pipeline begun by sc_moran_seeded_begin, until _finish
     StreamTable streams;            // every stream of the context, by role; the names below are its entries
     hipStream_t &stream = streams.s[SR_SCORE];
@@ -138,13 +180,12 @@ struct sc_ctx {
                                                        // sc_local_stat_seeded); Moran's finalise launches, beside the next chunk's scoring (sc_moran.hip: MoranRing)
     hipStream_t &stream_px = streams.s[SR_EXPAND];     // the generator verifies + expands a finished chunk here, beside the next chunk's chain
     hipStream_t *const stream_pg = streams.s + SR_PREP0;   // [4]: its preparation streams
+    bool timing = true;
+    KTimer timers[SC_K_COUNT_];
     PermGen pg;       // the numpy-exact permutation generator's state
     sc_ctx();         // (sc_api.hip, where PermPipe is complete)
     ~sc_ctx();
     sc_ctx(const sc_ctx &) = delete;
-    int64_t mem = 0;  // bytes allocated through DBuf
-    bool timing = true;
-    KTimer timers[SC_K_COUNT_];
 
     // ---- points (kNN / radius) ----
     int64_t pts_n = 0;
@@ -198,7 +239,6 @@ struct sc_ctx {
         bool valid = false;
         DBuf X, raw, idx, d2, pidx, pd2;        // [n][d] fp64, the upload, [n][k] result, [split][query][k] partial lists
         DBuf gnorm, gkept, gcnt, glo, grows;    // the Gram filter: row norms, kept candidates [n][L], their counts, the L-th keys, [count | uncertified rows]
-        std::vector<DBuf *> bufs() { return {&X, &raw, &idx, &d2, &pidx, &pd2, &gnorm, &gkept, &gcnt, &glo, &grows}; }
     } knn;
     // ---- graphs on those lists or from a caller (sc_diffusion.hip, sc_umap.hip): the resident weighted graph with its
     // transition matrix, UMAP's bandwidths and layout buffers, the Lanczos basis ----
@@ -211,20 +251,15 @@ struct sc_ctx {
         DBuf rho, sigma, dsum;                  // sc_fuzzy_graph: first non-zero distance, bandwidth, [row sums of the distances | chunk sums | their total]
         DBuf lip, lix, lw, ly0, ly1, lmax;      // sc_umap_layout: a caller's CSR, the two position buffers, the bits of w_max
         DBuf V, wv, part, coef, ab, Y, S, res;   // basis [max_basis + 1][n], work vector, chunk partials, coefficients, alpha | beta, Ritz vectors, their coefficients, residuals
-        std::vector<DBuf *> bufs()
-        {
-            return {&s2, &keys, &keys2, &pay, &pay2, &cnt, &off, &indptr, &indices, &w, &T, &q, &parent, &flag, &V, &wv, &part,
-                    &coef, &ab, &Y, &S, &res, &rho, &sigma, &dsum, &lip, &lix, &lw, &ly0, &ly1, &lmax};
-        }
     } df;
     // ---- annotation (sc_annotate.hip): the training problem kept on the device between sc_annot_train_begin and _end ----
-    struct AnnotTrain *an = nullptr;
+    std::unique_ptr<Resident> an;        // AnnotTrain
     // ---- PCA (sc_pca.hip): the matrix kept on the device between sc_pca_begin and sc_pca_end ----
-    struct PcaState *pca = nullptr;
+    std::unique_ptr<Resident> pca;       // PcaState
     // ---- Louvain (sc_louvain.hip): the level graphs and the partition kept on the device between sc_louvain_begin and _end ----
-    struct LouvainState *louvain = nullptr;
+    std::unique_ptr<Resident> louvain;   // LouvainState
     // ---- Harmony (sc_harmony.hip): the embedding, the assignments and the block tables between sc_harmony_begin and _end ----
-    struct HarmonyState *harmony = nullptr;
+    std::unique_ptr<Resident> harmony;   // HarmonyState
 
     // ---- graph (CSR, rows sorted by column) + transpose ----
     int64_t g_n = 0, g_nnz = 0;
@@ -308,6 +343,15 @@ struct sc_ctx {
     DBuf s0_tmp;
     DBuf np_cnt, np_comp, np_leaves, np_leafsum;  // numpy-order column sums: block counts, compacted values, leaf table, leaf sums
 };
+
+// Drops a resident problem, if there is one: waits for the context stream, whose work may still use its buffers and host
+// vectors, then frees it.  The one way out for an _end, a new _begin, a _begin that fails half-way and a failed level.
+inline void sc_resident_drop(sc_ctx *c, std::unique_ptr<Resident> &r)
+{
+    if (!r) return;
+    (void)hipStreamSynchronize(c->stream);
+    r.reset();
+}
 
 struct KernelTimerScope {
     sc_ctx *c;
@@ -428,9 +472,5 @@ int rs_sort(sc_ctx *c, const K *k_in, K *k_out, const V *v_in, V *v_out, int64_t
 // labels_dev[n_init][n] is a device array, written on c->stream (sc_kmeans.hip)
 int sc_kmeans_run_labels(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t C, int32_t K, int32_t n_init,
                          int32_t max_iter, double tol, const void *x_mean, const double *uniforms, int32_t *labels_dev);
-void sc_annot_release(sc_ctx *c);   // drops the resident training problem, if any (sc_annotate.hip)
-void sc_pca_release(sc_ctx *c);     // drops the resident PCA matrix, if any (sc_pca.hip)
-void sc_louvain_release(sc_ctx *c); // drops the resident Louvain hierarchy, if any (sc_louvain.hip)
-void sc_harmony_release(sc_ctx *c); // drops the resident Harmony problem, if any (sc_harmony.hip)
 void sc_launch_spmv_vec(sc_ctx *c, const int64_t *indptr, const int32_t *indices, const double *w,
                         const double *x, double *y, int64_t n);

@@ -529,7 +529,7 @@ extern "C" int sc_lanczos_end(sc_ctx *c)
     sc_ctx::Diffusion &f = c->df;
     // the end of a diffusion map gives back its large transients: the basis, and the search's partial lists (knn.pidx / pd2),
     // which nothing reads after the search that filled them and which the next search sizes again
-    for (DBuf *b : {&f.V, &f.Y, &f.part, &c->knn.pidx, &c->knn.pd2}) b->release(&c->mem);
+    for (DBuf *b : {&f.V, &f.Y, &f.part, &c->knn.pidx, &c->knn.pd2}) b->release();
     f.lanczos_valid = false;
     return SC_OK;
 }

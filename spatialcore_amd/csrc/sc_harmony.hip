@@ -483,29 +483,15 @@ int hm_check_rows(const char *who, const char *what, const V *X, int64_t rows, i
 }  // namespace
 
 // the problem resident between sc_harmony_begin and sc_harmony_end
-struct HarmonyState {
+struct HarmonyState : Resident {
     int64_t n = 0;
     int d = 0, K = 0, B = 0, nb = 0, n_slices = 0, n_groups = 0;   // groups of 64 consecutive slices (k_hm_fold)
     double sigma = 0.0, theta = 0.0, lamb = 0.0;
     std::vector<int64_t> order;             // position -> cell
     std::vector<int32_t> blk_first;         // [nb + 1] first slice of every block
     DBuf Z, Zc, Zcorr, dist, S, R, Y, inv_sum, slices, seg_first, pr, opart, oblk, pen, otot, lratio, objpart, obj, part, fold, rb, W;
-    void release(int64_t *acct)
-    {
-        for (DBuf *b : {&Z, &Zc, &Zcorr, &dist, &S, &R, &Y, &inv_sum, &slices, &seg_first, &pr, &opart, &oblk, &pen, &otot, &lratio,
-                        &objpart, &obj, &part, &fold, &rb, &W})
-            b->release(acct);
-    }
 };
-
-void sc_harmony_release(sc_ctx *c)
-{
-    if (!c->harmony) return;
-    (void)hipStreamSynchronize(c->stream);
-    c->harmony->release(&c->mem);
-    delete c->harmony;
-    c->harmony = nullptr;
-}
+static HarmonyState *hm_state(const sc_ctx *c) { return resident<HarmonyState>(c->harmony); }
 
 namespace {
 
@@ -608,10 +594,9 @@ extern "C" int sc_harmony_begin(sc_ctx *c, const void *Z, int dtype, int64_t n, 
     for (int b = 0; b < B; ++b) pr[b] = (double)batch_n[b] / (double)n;
 
     SC_HIP(hipSetDevice(c->device));
-    sc_harmony_release(c);
-    c->harmony = new HarmonyState();
-    HarmonyState &s = *c->harmony;
-    auto fail = [&](int rc) { sc_harmony_release(c); return rc; };
+    sc_resident_drop(c, c->harmony);
+    c->harmony.reset(new HarmonyState());
+    HarmonyState &s = *hm_state(c);
     s.n = n, s.d = d, s.K = K, s.B = B, s.nb = nb, s.n_slices = (int)slices.size();
     s.n_groups = (s.n_slices + HM_GROUP - 1) / HM_GROUP;
     s.sigma = sigma, s.theta = theta, s.lamb = lamb;
@@ -626,7 +611,10 @@ extern "C" int sc_harmony_begin(sc_ctx *c, const void *Z, int dtype, int64_t n, 
         {&s.part, sizeof(double) * slices.size() * K * d}, {&s.fold, sizeof(double) * (size_t)s.n_groups * (K * d > 3 ? K * d : 3)}, {&s.rb, kb * (size_t)d}, {&s.W, kb * (size_t)d}};
     for (auto &w : want) {
         const int rc = w.b->ensure(w.bytes, &c->mem);
-        if (rc != SC_OK) return fail(rc);
+        if (rc != SC_OK) {
+            sc_resident_drop(c, c->harmony);
+            return rc;
+        }
     }
     hipStream_t st = c->stream;
     bool ok = hipMemcpyAsync(s.Z.p, zs.data(), nd, hipMemcpyHostToDevice, st) == hipSuccess;
@@ -651,7 +639,8 @@ extern "C" int sc_harmony_begin(sc_ctx *c, const void *Z, int dtype, int64_t n, 
     }
     if (!ok || hipStreamSynchronize(st) != hipSuccess) {   // the host arrays are free again
         sc_set_error("%s: failed on the device: %s", who, hipGetErrorString(hipGetLastError()));
-        return fail(SC_ERR_HIP);
+        sc_resident_drop(c, c->harmony);
+        return SC_ERR_HIP;
     }
     return SC_OK;
 }
@@ -663,7 +652,7 @@ extern "C" int sc_harmony_cluster(sc_ctx *c, int32_t max_iter, double epsilon, i
     SC_REQUIRE(max_iter >= 1 && max_iter <= 4096, SC_ERR_INVALID, "%s: need 1 <= max_iter <= 4096, got %d", who, max_iter);
     SC_REQUIRE(!std::isnan(epsilon), SC_ERR_INVALID, "%s: epsilon is NaN", who);
     SC_REQUIRE(c->harmony, SC_ERR_STATE, "%s: no problem is resident (sc_harmony_begin)", who);
-    HarmonyState &s = *c->harmony;
+    HarmonyState &s = *hm_state(c);
     SC_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     int done = 0;
@@ -696,7 +685,7 @@ extern "C" int sc_harmony_correct(sc_ctx *c)
     const char *who = "sc_harmony_correct";
     SC_REQUIRE(c, SC_ERR_INVALID, "%s: null pointer", who);
     SC_REQUIRE(c->harmony, SC_ERR_STATE, "%s: no problem is resident (sc_harmony_begin)", who);
-    HarmonyState &s = *c->harmony;
+    HarmonyState &s = *hm_state(c);
     SC_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     // otot = the sum of the tables as they stand (after begin and after every round k_hm_tables left exactly that)
@@ -718,7 +707,7 @@ extern "C" int sc_harmony_get(sc_ctx *c, int32_t what, void *out)
     SC_REQUIRE(c && out, SC_ERR_INVALID, "%s: null pointer", who);
     SC_REQUIRE(what >= SC_HARMONY_ZCORR && what <= SC_HARMONY_DIST, SC_ERR_INVALID, "%s: unknown array %d", who, what);
     SC_REQUIRE(c->harmony, SC_ERR_STATE, "%s: no problem is resident (sc_harmony_begin)", who);
-    HarmonyState &s = *c->harmony;
+    HarmonyState &s = *hm_state(c);
     const int64_t n = s.n;
     const int d = s.d, K = s.K, B = s.B;
     if (what == SC_HARMONY_ORDER) {
@@ -761,6 +750,6 @@ extern "C" int sc_harmony_end(sc_ctx *c)
     SC_REQUIRE(c, SC_ERR_INVALID, "sc_harmony_end: null pointer");
     if (!c->harmony) return SC_OK;
     SC_HIP(hipSetDevice(c->device));
-    sc_harmony_release(c);
+    sc_resident_drop(c, c->harmony);
     return SC_OK;
 }

@@ -181,20 +181,11 @@ __global__ __launch_bounds__(256) void k_hvg_finish(const int64_t *__restrict__ 
     var_out[g] = var > 0.0 ? var : 0.0;
 }
 
-// a call's own buffers, freed on every return path
+// a call's own buffers
 struct HvgBufs {
-    sc_ctx *c;
     CsrDevice m;
     ColSort cs;
     DBuf s, sums, total, part, dpart, dsum, out;
-    explicit HvgBufs(sc_ctx *ctx) : c(ctx) {}
-    ~HvgBufs()
-    {
-        (void)hipStreamSynchronize(c->stream);
-        m.release(&c->mem);
-        cs.release(&c->mem);
-        for (DBuf *b : {&s, &sums, &total, &part, &dpart, &dsum, &out}) b->release(&c->mem);
-    }
 };
 
 // true if any stored value is > 0
@@ -233,7 +224,8 @@ extern "C" int sc_hvg_pearson(sc_ctx *c, const int64_t *indptr, const int32_t *i
     const int G = n_genes;
     const double inv_theta = 1.0 / theta;
     const int64_t slice_rows = hvg_slice_rows(n), slices = ceil_div64(n, slice_rows);
-    HvgBufs b(c);
+    HvgBufs b;
+    StreamWaitOnExit wait{c->stream};   // after the buffers: an early return may leave work on them in flight
     SC_TRY(b.m.upload(c, indptr, indices, data, dtype, n, nnz));
     SC_TRY(colsort_alloc(c, b.cs, nnz, G));
     SC_TRY(b.s.ensure(sizeof(double) * (size_t)n, &c->mem));

@@ -447,16 +447,6 @@ __global__ __launch_bounds__(256) void k_km_same(const int32_t *__restrict__ la,
     if (p < n && lb[p] != lb[first[la[p]]]) atomicOr(differ, 1);
 }
 
-struct KmBufs {
-    sc_ctx *c;
-    DBuf b[20];
-    explicit KmBufs(sc_ctx *ctx) : c(ctx) {}
-    ~KmBufs()
-    {
-        for (DBuf &d : b) d.release(&c->mem);
-    }
-};
-
 // numpy's RandomState.choice(n, p=w / w.sum()) for unit weights w of type T, given its one random_sample() draw
 template <class T>
 std::vector<int64_t> first_centres(int64_t n, const double *u0, int64_t stride, int R)
@@ -491,7 +481,7 @@ int kmeans_fit(sc_ctx *c, const T *X, int64_t n, int C, int K, int R, int max_it
     const int64_t NB = std::max<int64_t>(1, std::min<int64_t>({tiles, 256, ((int64_t)1 << 25) / std::max<int64_t>(1, R * KC)}));
     const bool fast = C <= KM_FAST && K <= KM_FAST;
 
-    KmBufs m(c);
+    DBuf m[20];
     enum { XC, XN, D2, S0, S1, CAND, CPART, CENTRE, SEEDS, POT, U, LAB, CENT, PART, CNT, CHG, INERT, SUMS, COUNTS, STATE };
     const size_t sz[20] = {sizeof(T) * (size_t)(n * C), sizeof(double) * (size_t)n, sizeof(T) * (size_t)(R * n),
                            sizeof(double) * (size_t)(R * G * KM_CH), sizeof(double) * (size_t)(R * G),
@@ -502,45 +492,44 @@ int kmeans_fit(sc_ctx *c, const T *X, int64_t n, int C, int K, int R, int max_it
                            sizeof(int64_t) * (size_t)(R * NB * K), sizeof(int64_t) * (size_t)(R * NB),
                            sizeof(double) * (size_t)(R * NB), sizeof(double) * (size_t)(R * KC),
                            sizeof(int64_t) * (size_t)(R * K), sizeof(int64_t) * (size_t)(R * ST_WORDS)};
-    for (int i = 0; i < 20; ++i) SC_TRY(m.b[i].ensure(std::max<size_t>(sz[i], 64), &c->mem));
+    for (int i = 0; i < 20; ++i) SC_TRY(m[i].ensure(std::max<size_t>(sz[i], 64), &c->mem));
 
     // ---- centring; first centres from the runs' random_sample draws --------------------------------
     DBuf xin, xmean;
-    struct Rel { sc_ctx *c; DBuf *a, *b; ~Rel() { a->release(&c->mem); b->release(&c->mem); } } rel{c, &xin, &xmean};
     SC_TRY(xin.ensure(sizeof(T) * (size_t)(n * C), &c->mem));
     SC_TRY(xmean.ensure(sizeof(T) * (size_t)C, &c->mem));
     SC_HIP(hipMemcpyAsync(xin.p, X, sizeof(T) * (size_t)(n * C), hipMemcpyHostToDevice, s));
     SC_HIP(hipMemcpyAsync(xmean.p, x_mean, sizeof(T) * (size_t)C, hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemcpyAsync(m.b[U].p, uniforms, sz[U], hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(m[U].p, uniforms, sz[U], hipMemcpyHostToDevice, s));
     std::vector<int64_t> c0 = first_centres<T>(n, uniforms, ustride, R);
     std::vector<int64_t> seeds0((size_t)(R * K), -1);
     for (int r = 0; r < R; ++r) seeds0[(size_t)r * K] = c0[(size_t)r];
-    SC_HIP(hipMemcpyAsync(m.b[CENTRE].p, c0.data(), sz[CENTRE], hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemcpyAsync(m.b[SEEDS].p, seeds0.data(), sz[SEEDS], hipMemcpyHostToDevice, s));
-    T *Xc = m.b[XC].template as<T>();
-    const double *xn = m.b[XN].template as<double>();
+    SC_HIP(hipMemcpyAsync(m[CENTRE].p, c0.data(), sz[CENTRE], hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(m[SEEDS].p, seeds0.data(), sz[SEEDS], hipMemcpyHostToDevice, s));
+    T *Xc = m[XC].template as<T>();
+    const double *xn = m[XN].template as<double>();
     {
         KernelTimerScope ts(c, SC_K_KMEANS_SEED);
         hipLaunchKernelGGL(k_km_center<T>, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, s, xin.template as<T>(),
-                           xmean.template as<T>(), n, C, Xc, m.b[XN].template as<double>());
+                           xmean.template as<T>(), n, C, Xc, m[XN].template as<double>());
         // ---- k-means++ seeding, all runs per launch ------------------------------------------------
         for (int round = 1; round < K; ++round) {
             hipLaunchKernelGGL(k_seed_scan<T>, dim3((unsigned)G, (unsigned)R), dim3(KM_CH), 0, s, Xc, xn, n, C,
-                               m.b[D2].template as<T>(), m.b[CENTRE].template as<int64_t>(), round == 1 ? 1 : 0, m.b[S0].template as<double>(),
-                               m.b[S1].template as<double>());
-            hipLaunchKernelGGL(k_seed_search<T>, dim3((unsigned)R), dim3(KM_CH), 0, s, m.b[S0].template as<double>(),
-                               m.b[S1].template as<double>(), m.b[D2].template as<T>(), n, G,
-                               m.b[U].template as<double>() + 1 + (int64_t)(round - 1) * L, ustride, L, m.b[CAND].template as<int64_t>(),
-                               m.b[POT].template as<double>());
+                               m[D2].template as<T>(), m[CENTRE].template as<int64_t>(), round == 1 ? 1 : 0, m[S0].template as<double>(),
+                               m[S1].template as<double>());
+            hipLaunchKernelGGL(k_seed_search<T>, dim3((unsigned)R), dim3(KM_CH), 0, s, m[S0].template as<double>(),
+                               m[S1].template as<double>(), m[D2].template as<T>(), n, G,
+                               m[U].template as<double>() + 1 + (int64_t)(round - 1) * L, ustride, L, m[CAND].template as<int64_t>(),
+                               m[POT].template as<double>());
             hipLaunchKernelGGL(k_seed_cand<T>, dim3((unsigned)G, (unsigned)R), dim3(KM_CH), 0, s, Xc, xn, n, C,
-                               m.b[D2].template as<T>(), m.b[CAND].template as<int64_t>(), L, m.b[CPART].template as<double>());
-            hipLaunchKernelGGL(k_seed_best<T>, dim3((unsigned)R), dim3(KM_CH), 0, s, m.b[CPART].template as<double>(), G, L,
-                               m.b[CAND].template as<int64_t>(), m.b[CENTRE].template as<int64_t>(), m.b[SEEDS].template as<int64_t>(), K, round);
+                               m[D2].template as<T>(), m[CAND].template as<int64_t>(), L, m[CPART].template as<double>());
+            hipLaunchKernelGGL(k_seed_best<T>, dim3((unsigned)R), dim3(KM_CH), 0, s, m[CPART].template as<double>(), G, L,
+                               m[CAND].template as<int64_t>(), m[CENTRE].template as<int64_t>(), m[SEEDS].template as<int64_t>(), K, round);
         }
         const int64_t w = std::max<int64_t>(n, std::max<int64_t>(KC, ST_WORDS));
         hipLaunchKernelGGL(k_km_init<T>, dim3((unsigned)ceil_div64(w, 256), (unsigned)R), dim3(256), 0, s, Xc, n, C, K,
-                           m.b[SEEDS].template as<int64_t>(), m.b[CENT].template as<T>(), m.b[LAB].template as<int32_t>(),
-                           m.b[STATE].template as<int64_t>());
+                           m[SEEDS].template as<int64_t>(), m[CENT].template as<T>(), m[LAB].template as<int32_t>(),
+                           m[STATE].template as<int64_t>());
     }
     SC_HIP(hipGetLastError());
 
@@ -549,31 +538,30 @@ int kmeans_fit(sc_ctx *c, const T *X, int64_t n, int C, int K, int R, int max_it
     auto estep = [&](int mode) {
         if (fast)
             hipLaunchKernelGGL((k_km_estep<T, true>), dim3((unsigned)NB, (unsigned)R), dim3(KM_TPB), 0, s, Xc, n, C, K,
-                               m.b[CENT].template as<T>(), m.b[LAB].template as<int32_t>(), m.b[STATE].template as<int64_t>(), mode,
-                               m.b[PART].template as<double>(), m.b[CNT].template as<int64_t>(), m.b[CHG].template as<int64_t>(),
-                               m.b[INERT].template as<double>());
+                               m[CENT].template as<T>(), m[LAB].template as<int32_t>(), m[STATE].template as<int64_t>(), mode,
+                               m[PART].template as<double>(), m[CNT].template as<int64_t>(), m[CHG].template as<int64_t>(),
+                               m[INERT].template as<double>());
         else
             hipLaunchKernelGGL((k_km_estep<T, false>), dim3((unsigned)NB, (unsigned)R), dim3(KM_TPB), 0, s, Xc, n, C, K,
-                               m.b[CENT].template as<T>(), m.b[LAB].template as<int32_t>(), m.b[STATE].template as<int64_t>(), mode,
-                               m.b[PART].template as<double>(), m.b[CNT].template as<int64_t>(), m.b[CHG].template as<int64_t>(),
-                               m.b[INERT].template as<double>());
+                               m[CENT].template as<T>(), m[LAB].template as<int32_t>(), m[STATE].template as<int64_t>(), mode,
+                               m[PART].template as<double>(), m[CNT].template as<int64_t>(), m[CHG].template as<int64_t>(),
+                               m[INERT].template as<double>());
     };
     std::vector<double> hsums, hdist;
     std::vector<int64_t> hcounts;
     std::vector<int32_t> hlab;
     DBuf ddist;
-    struct Rel1 { sc_ctx *c; DBuf *a; ~Rel1() { a->release(&c->mem); } } rel1{c, &ddist};
     for (int it = 0; it < max_iter; ++it) {
         {
             KernelTimerScope ts(c, SC_K_KMEANS_LLOYD);
             estep(0);
-            hipLaunchKernelGGL(k_km_reduce<T>, dim3((unsigned)R), dim3(KM_TPB), 0, s, m.b[PART].template as<double>(),
-                               m.b[CNT].template as<int64_t>(), m.b[CHG].template as<int64_t>(), NB, m.b[SUMS].template as<double>(),
-                               m.b[COUNTS].template as<int64_t>(), m.b[CENT].template as<T>(), m.b[STATE].template as<int64_t>(), K, C, tol,
+            hipLaunchKernelGGL(k_km_reduce<T>, dim3((unsigned)R), dim3(KM_TPB), 0, s, m[PART].template as<double>(),
+                               m[CNT].template as<int64_t>(), m[CHG].template as<int64_t>(), NB, m[SUMS].template as<double>(),
+                               m[COUNTS].template as<int64_t>(), m[CENT].template as<T>(), m[STATE].template as<int64_t>(), K, C, tol,
                                max_iter);
         }
         SC_HIP(hipGetLastError());
-        SC_HIP(hipMemcpyAsync(st.data(), m.b[STATE].p, sz[STATE], hipMemcpyDeviceToHost, s));
+        SC_HIP(hipMemcpyAsync(st.data(), m[STATE].p, sz[STATE], hipMemcpyDeviceToHost, s));
         SC_HIP(hipStreamSynchronize(s));
         for (int r = 0; r < R; ++r) {
             if (!st[(size_t)r * ST_WORDS + ST_RELOC]) continue;
@@ -585,13 +573,13 @@ int kmeans_fit(sc_ctx *c, const T *X, int64_t n, int C, int K, int R, int max_it
             hdist.resize((size_t)n);
             SC_TRY(ddist.ensure(sizeof(double) * (size_t)n, &c->mem));
             hipLaunchKernelGGL(k_km_reloc_dist<T>, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, s, Xc, n, C, K,
-                               m.b[CENT].template as<T>(), m.b[LAB].template as<int32_t>(), r, ddist.template as<double>());
+                               m[CENT].template as<T>(), m[LAB].template as<int32_t>(), r, ddist.template as<double>());
             SC_HIP(hipGetLastError());
-            SC_HIP(hipMemcpyAsync(hsums.data(), m.b[SUMS].template as<double>() + (int64_t)r * KC, sizeof(double) * (size_t)KC,
+            SC_HIP(hipMemcpyAsync(hsums.data(), m[SUMS].template as<double>() + (int64_t)r * KC, sizeof(double) * (size_t)KC,
                                   hipMemcpyDeviceToHost, s));
-            SC_HIP(hipMemcpyAsync(hcounts.data(), m.b[COUNTS].template as<int64_t>() + (int64_t)r * K, sizeof(int64_t) * (size_t)K,
+            SC_HIP(hipMemcpyAsync(hcounts.data(), m[COUNTS].template as<int64_t>() + (int64_t)r * K, sizeof(int64_t) * (size_t)K,
                                   hipMemcpyDeviceToHost, s));
-            SC_HIP(hipMemcpyAsync(hlab.data(), m.b[LAB].template as<int32_t>() + (int64_t)r * n, sizeof(int32_t) * (size_t)n,
+            SC_HIP(hipMemcpyAsync(hlab.data(), m[LAB].template as<int32_t>() + (int64_t)r * n, sizeof(int32_t) * (size_t)n,
                                   hipMemcpyDeviceToHost, s));
             SC_HIP(hipMemcpyAsync(hdist.data(), ddist.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
             SC_HIP(hipStreamSynchronize(s));
@@ -616,15 +604,15 @@ int kmeans_fit(sc_ctx *c, const T *X, int64_t n, int C, int K, int R, int max_it
                 hcounts[(size_t)nk] = 1;
                 hcounts[(size_t)ok] -= 1;
             }
-            SC_HIP(hipMemcpyAsync(m.b[SUMS].template as<double>() + (int64_t)r * KC, hsums.data(), sizeof(double) * (size_t)KC,
+            SC_HIP(hipMemcpyAsync(m[SUMS].template as<double>() + (int64_t)r * KC, hsums.data(), sizeof(double) * (size_t)KC,
                                   hipMemcpyHostToDevice, s));
-            SC_HIP(hipMemcpyAsync(m.b[COUNTS].template as<int64_t>() + (int64_t)r * K, hcounts.data(), sizeof(int64_t) * (size_t)K,
+            SC_HIP(hipMemcpyAsync(m[COUNTS].template as<int64_t>() + (int64_t)r * K, hcounts.data(), sizeof(int64_t) * (size_t)K,
                                   hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_km_apply<T>, dim3(1), dim3(KM_TPB), 0, s, r, m.b[SUMS].template as<double>(),
-                               m.b[COUNTS].template as<int64_t>(), m.b[CENT].template as<T>(), m.b[STATE].template as<int64_t>(), K, C, tol,
+            hipLaunchKernelGGL(k_km_apply<T>, dim3(1), dim3(KM_TPB), 0, s, r, m[SUMS].template as<double>(),
+                               m[COUNTS].template as<int64_t>(), m[CENT].template as<T>(), m[STATE].template as<int64_t>(), K, C, tol,
                                max_iter);
             SC_HIP(hipGetLastError());
-            SC_HIP(hipMemcpyAsync(st.data() + (size_t)r * ST_WORDS, m.b[STATE].template as<int64_t>() + (int64_t)r * ST_WORDS,
+            SC_HIP(hipMemcpyAsync(st.data() + (size_t)r * ST_WORDS, m[STATE].template as<int64_t>() + (int64_t)r * ST_WORDS,
                                   sizeof(int64_t) * ST_WORDS, hipMemcpyDeviceToHost, s));
             SC_HIP(hipStreamSynchronize(s));
         }
@@ -641,13 +629,13 @@ int kmeans_fit(sc_ctx *c, const T *X, int64_t n, int C, int K, int R, int max_it
     }
     SC_HIP(hipGetLastError());
     if (run_labels_dev) {   // sc_kmeans_run_labels: every run's labels stay on the device; no best run is chosen
-        SC_HIP(hipMemcpyAsync(run_labels_dev, m.b[LAB].p, sz[LAB], hipMemcpyDeviceToDevice, s));
+        SC_HIP(hipMemcpyAsync(run_labels_dev, m[LAB].p, sz[LAB], hipMemcpyDeviceToDevice, s));
         SC_HIP(hipStreamSynchronize(s));
         return SC_OK;
     }
-    SC_HIP(hipMemcpyAsync(inert.data(), m.b[INERT].p, sz[INERT], hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(st.data(), m.b[STATE].p, sz[STATE], hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(seeds_out, m.b[SEEDS].p, sz[SEEDS], hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(inert.data(), m[INERT].p, sz[INERT], hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(st.data(), m[STATE].p, sz[STATE], hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(seeds_out, m[SEEDS].p, sz[SEEDS], hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     std::vector<double> inertia((size_t)R);
     for (int r = 0; r < R; ++r) {
@@ -659,11 +647,10 @@ int kmeans_fit(sc_ctx *c, const T *X, int64_t n, int C, int K, int R, int max_it
     // ---- best run: a later run replaces the best only if its inertia is lower and its partition differs ----------
     int best = 0;
     DBuf dfirst;
-    struct Rel2 { sc_ctx *c; DBuf *a; ~Rel2() { a->release(&c->mem); } } rel2{c, &dfirst};
     SC_TRY(dfirst.ensure(sizeof(int) * (size_t)(K + 1), &c->mem));
     for (int r = 1; r < R; ++r) {
         if (!(inertia[(size_t)r] < inertia[(size_t)best])) continue;
-        const int32_t *la = m.b[LAB].template as<int32_t>() + (int64_t)r * n, *lb = m.b[LAB].template as<int32_t>() + (int64_t)best * n;
+        const int32_t *la = m[LAB].template as<int32_t>() + (int64_t)r * n, *lb = m[LAB].template as<int32_t>() + (int64_t)best * n;
         SC_HIP(hipMemsetAsync(dfirst.p, 0x7f, sizeof(int) * (size_t)K, s));
         SC_HIP(hipMemsetAsync(dfirst.template as<int>() + K, 0, sizeof(int), s));
         hipLaunchKernelGGL(k_km_first, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, s, la, n, dfirst.template as<int>());
@@ -675,9 +662,9 @@ int kmeans_fit(sc_ctx *c, const T *X, int64_t n, int C, int K, int R, int max_it
         SC_HIP(hipStreamSynchronize(s));
         if (differ) best = r;
     }
-    SC_HIP(hipMemcpyAsync(labels_out, m.b[LAB].template as<int32_t>() + (int64_t)best * n, sizeof(int32_t) * (size_t)n,
+    SC_HIP(hipMemcpyAsync(labels_out, m[LAB].template as<int32_t>() + (int64_t)best * n, sizeof(int32_t) * (size_t)n,
                           hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(centers_out, m.b[CENT].template as<T>() + (int64_t)best * KC, sizeof(T) * (size_t)KC,
+    SC_HIP(hipMemcpyAsync(centers_out, m[CENT].template as<T>() + (int64_t)best * KC, sizeof(T) * (size_t)KC,
                           hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     for (int64_t i = 0; i < KC; ++i) centers_out[i] = centers_out[i] + x_mean[i % C];   // best_centers += X_mean

@@ -449,7 +449,7 @@ struct LvGraph {
 };
 
 // everything between sc_louvain_begin and sc_louvain_end
-struct LouvainState {
+struct LouvainState : Resident {
     LvGraph gr[2];
     int cur = 0;
     DBuf k, knew, comm, next, best, tot, tot2, acc, cls, map, parent, root, flag, rank, used, label, list_wg, list_gl, coff, ccap, gkeys, gvals;
@@ -458,22 +458,8 @@ struct LouvainState {
     u64 M = 0;
     int32_t g = 0, max_rounds = 0, levels = 0;
     bool finished = false;
-    std::vector<DBuf *> bufs()
-    {
-        return {&gr[0].indptr, &gr[0].indices, &gr[0].w, &gr[1].indptr, &gr[1].indices, &gr[1].w, &k, &knew, &comm, &next, &best, &tot, &tot2,
-                &acc, &cls, &map, &parent, &root, &flag, &rank, &used, &label, &list_wg, &list_gl, &coff, &ccap, &gkeys, &gvals, &keys, &keys2,
-                &pay, &pay2, &tmp};
-    }
 };
-
-void sc_louvain_release(sc_ctx *c)
-{
-    if (!c->louvain) return;
-    (void)hipStreamSynchronize(c->stream);
-    for (DBuf *b : c->louvain->bufs()) b->release(&c->mem);
-    delete c->louvain;
-    c->louvain = nullptr;
-}
+static LouvainState *lv_state(const sc_ctx *c) { return resident<LouvainState>(c->louvain); }
 
 namespace {
 
@@ -499,9 +485,9 @@ int lv_check_common(const char *who, const sc_ctx *c, int32_t g, int32_t max_rou
 // a fresh state whose level 0 has room for (n, nnz)
 int lv_new_state(sc_ctx *c, int64_t n, int64_t nnz, u64 M, int32_t g, int32_t max_rounds)
 {
-    sc_louvain_release(c);
-    c->louvain = new LouvainState();
-    LouvainState &s = *c->louvain;
+    sc_resident_drop(c, c->louvain);
+    c->louvain.reset(new LouvainState());
+    LouvainState &s = *lv_state(c);
     s.n0 = n, s.M = M, s.g = g, s.max_rounds = max_rounds;
     LvGraph &G = s.gr[0];
     G.n = n, G.nnz = nnz, G.wide = false;
@@ -516,7 +502,7 @@ int lv_new_state(sc_ctx *c, int64_t n, int64_t nnz, u64 M, int32_t g, int32_t ma
 // after the upload of level 0: degrees, the identity map
 int lv_finish_begin(sc_ctx *c)
 {
-    LouvainState &s = *c->louvain;
+    LouvainState &s = *lv_state(c);
     LvGraph &G = s.gr[0];
     hipStream_t st = c->stream;
     KernelTimerScope ts(c, SC_K_LOUVAIN_LEVEL);
@@ -740,7 +726,7 @@ extern "C" int sc_louvain_begin(sc_ctx *c, const int64_t *indptr, const int32_t 
     SC_HIP(hipSetDevice(c->device));
     int rc = lv_new_state(c, n, nnz, M, g, max_rounds);
     if (rc == SC_OK) {
-        LvGraph &G = c->louvain->gr[0];
+        LvGraph &G = lv_state(c)->gr[0];
         hipStream_t st = c->stream;
         bool ok = hipMemcpyAsync(G.indptr.p, indptr, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, st) == hipSuccess;
         if (ok && nnz)
@@ -752,7 +738,7 @@ extern "C" int sc_louvain_begin(sc_ctx *c, const int64_t *indptr, const int32_t 
             rc = SC_ERR_HIP;
         }
     }
-    if (rc != SC_OK) sc_louvain_release(c);
+    if (rc != SC_OK) sc_resident_drop(c, c->louvain);
     return rc;
 }
 
@@ -793,7 +779,7 @@ extern "C" int sc_louvain_begin_resident(sc_ctx *c, const uint16_t *q, int64_t n
     int rc = lv_new_state(c, n, nnz, M, g, max_rounds);
     u64 flag = ~0ull;
     if (rc == SC_OK) {
-        LouvainState &s = *c->louvain;
+        LouvainState &s = *lv_state(c);
         LvGraph &G = s.gr[0];
         hipStream_t st = c->stream;
         rc = s.acc.ensure(sizeof(u64) * LV_ACC, &c->mem);
@@ -817,7 +803,7 @@ extern "C" int sc_louvain_begin_resident(sc_ctx *c, const uint16_t *q, int64_t n
             rc = SC_ERR_INVALID;
         }
     }
-    if (rc != SC_OK) sc_louvain_release(c);
+    if (rc != SC_OK) sc_resident_drop(c, c->louvain);
     return rc;
 }
 
@@ -826,9 +812,9 @@ extern "C" int sc_louvain_level(sc_ctx *c, int64_t *info_out, int32_t *labels_ou
     const char *who = "sc_louvain_level";
     SC_REQUIRE(c && info_out, SC_ERR_INVALID, "%s: null pointer", who);
     SC_REQUIRE(c->louvain, SC_ERR_STATE, "%s: no graph is resident (sc_louvain_begin)", who);
-    SC_REQUIRE(!c->louvain->finished, SC_ERR_STATE, "%s: the hierarchy is finished", who);
+    SC_REQUIRE(!lv_state(c)->finished, SC_ERR_STATE, "%s: the hierarchy is finished", who);
     SC_HIP(hipSetDevice(c->device));
-    LouvainState &s = *c->louvain;
+    LouvainState &s = *lv_state(c);
     return s.gr[s.cur].wide ? lv_level<u64>(c, s, info_out, labels_out) : lv_level<uint16_t>(c, s, info_out, labels_out);
 }
 
@@ -837,7 +823,7 @@ extern "C" int sc_louvain_labels(sc_ctx *c, int32_t *labels_out, int64_t *n_clus
     const char *who = "sc_louvain_labels";
     SC_REQUIRE(c && labels_out && n_clusters_out, SC_ERR_INVALID, "%s: null pointer", who);
     SC_REQUIRE(c->louvain, SC_ERR_STATE, "%s: no graph is resident (sc_louvain_begin)", who);
-    LouvainState &s = *c->louvain;
+    LouvainState &s = *lv_state(c);
     SC_REQUIRE(s.levels >= 1, SC_ERR_STATE, "%s: no level has run (sc_louvain_level)", who);
     SC_HIP(hipSetDevice(c->device));
     SC_HIP(hipMemcpyAsync(labels_out, s.map.p, sizeof(int32_t) * (size_t)s.n0, hipMemcpyDeviceToHost, c->stream));
@@ -866,6 +852,6 @@ extern "C" int sc_louvain_end(sc_ctx *c)
     SC_REQUIRE(c, SC_ERR_INVALID, "sc_louvain_end: null pointer");
     if (!c->louvain) return SC_OK;
     SC_HIP(hipSetDevice(c->device));
-    sc_louvain_release(c);
+    sc_resident_drop(c, c->louvain);
     return SC_OK;
 }

@@ -275,19 +275,13 @@ __global__ void k_nmf_err_final(const double *__restrict__ part, int64_t chunks,
     *out = sqrt(2.0 * (D > 0.0 ? D : 0.0));
 }
 
-struct NmfBufs {
+struct NmfBufs {   // a call's own buffers
     sc_ctx *c;
     enum { W, H0, H1, HT0, HT1, HHT, HSUM, CELLPART, CELLSUM, HPART, ROWERR, ERRPART, ERR, COUNT };
     DBuf b[COUNT];
     CsrDevice x;  // the matrix in row order
     ColSort cs;   // the column-sorted copy and its chunk table
     explicit NmfBufs(sc_ctx *ctx) : c(ctx) {}
-    ~NmfBufs()
-    {
-        for (DBuf &d : b) d.release(&c->mem);
-        x.release(&c->mem);
-        cs.release(&c->mem);
-    }
     int get(int which, size_t bytes) { return b[which].ensure(bytes ? bytes : 8, &c->mem); }
     template <class T> T *as(int which) const { return b[which].as<T>(); }
 };

@@ -193,25 +193,12 @@ __global__ __launch_bounds__(256) void k_pca_rows(const int64_t *__restrict__ in
 }  // namespace
 
 // the matrix resident between sc_pca_begin and sc_pca_end, and the scratch of _gram and _project
-struct PcaState {
+struct PcaState : Resident {
     CsrDevice m;   // m.raw only inside sc_pca_begin
     DBuf bptr, blocks, partial, colpart, gram, colsum, table, offset, out;
     int G = 0;
-    void release(int64_t *acct)
-    {
-        m.release(acct);
-        for (DBuf *b : {&bptr, &blocks, &partial, &colpart, &gram, &colsum, &table, &offset, &out}) b->release(acct);
-    }
 };
-
-void sc_pca_release(sc_ctx *c)
-{
-    if (!c->pca) return;
-    (void)hipStreamSynchronize(c->stream);
-    c->pca->release(&c->mem);
-    delete c->pca;
-    c->pca = nullptr;
-}
+static PcaState *pca_state(const sc_ctx *c) { return resident<PcaState>(c->pca); }
 
 extern "C" int sc_pca_begin(sc_ctx *c, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
                             int32_t n_genes, int32_t normalize, double target_sum)
@@ -230,14 +217,16 @@ extern "C" int sc_pca_begin(sc_ctx *c, const int64_t *indptr, const int32_t *ind
     SC_TRY(csr_check_values(who, data, dtype, nnz, normalize != 0, " (normalize needs counts)"));
 
     SC_HIP(hipSetDevice(c->device));
-    sc_pca_release(c);
-    c->pca = new PcaState();
-    PcaState &s = *c->pca;
+    sc_resident_drop(c, c->pca);
+    c->pca.reset(new PcaState());
+    PcaState &s = *pca_state(c);
     hipStream_t st = c->stream;
     s.G = n_genes;
-    auto fail = [&](int rc) { sc_pca_release(c); return rc; };
     const int rc = s.m.upload(c, indptr, indices, data, dtype, n, nnz);
-    if (rc != SC_OK) return fail(rc);
+    if (rc != SC_OK) {
+        sc_resident_drop(c, c->pca);
+        return rc;
+    }
     {
         KernelTimerScope ts(c, SC_K_PCA_SETUP);
         const dim3 per_row((unsigned)ceil_div64(n, PCA_TPB)), tpb(PCA_TPB);
@@ -248,9 +237,10 @@ extern "C" int sc_pca_begin(sc_ctx *c, const int64_t *indptr, const int32_t *ind
     }
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {   // the caller's arrays are free again
         sc_set_error("%s: upload failed on the device: %s", who, hipGetErrorString(hipGetLastError()));
-        return fail(SC_ERR_HIP);
+        sc_resident_drop(c, c->pca);
+        return SC_ERR_HIP;
     }
-    s.m.raw.release(&c->mem);
+    s.m.raw.release();
     return SC_OK;
 }
 
@@ -259,9 +249,10 @@ extern "C" int sc_pca_values(sc_ctx *c, double *values_out)
     const char *who = "sc_pca_values";
     SC_REQUIRE(c && values_out, SC_ERR_INVALID, "%s: null pointer", who);
     SC_REQUIRE(c->pca, SC_ERR_STATE, "%s: no matrix is resident (sc_pca_begin)", who);
-    if (!c->pca->m.nnz) return SC_OK;
+    const CsrDevice &m = pca_state(c)->m;
+    if (!m.nnz) return SC_OK;
     SC_HIP(hipSetDevice(c->device));
-    SC_HIP(hipMemcpyAsync(values_out, c->pca->m.val.p, sizeof(double) * (size_t)c->pca->m.nnz, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(values_out, m.val.p, sizeof(double) * (size_t)m.nnz, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     return SC_OK;
 }
@@ -271,7 +262,7 @@ extern "C" int sc_pca_gram(sc_ctx *c, double *colsum_out, double *gram_out)
     const char *who = "sc_pca_gram";
     SC_REQUIRE(c && colsum_out && gram_out, SC_ERR_INVALID, "%s: null pointer", who);
     SC_REQUIRE(c->pca, SC_ERR_STATE, "%s: no matrix is resident (sc_pca_begin)", who);
-    PcaState &s = *c->pca;
+    PcaState &s = *pca_state(c);
     SC_HIP(hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const int G = s.G, nb = (G + PCA_BLK - 1) / PCA_BLK, nq = nb * (nb + 1) / 2;
@@ -315,7 +306,7 @@ extern "C" int sc_pca_project(sc_ctx *c, const double *V, const double *offset, 
     SC_REQUIRE(K >= 1 && K <= PCA_KMAX, SC_ERR_INVALID, "%s: need 1 <= K <= %d, got %d", who, PCA_KMAX, K);
     SC_REQUIRE(out_dtype == SC_F32 || out_dtype == SC_F64, SC_ERR_INVALID, "%s: out_dtype must be SC_F32 or SC_F64", who);
     SC_REQUIRE(c->pca, SC_ERR_STATE, "%s: no matrix is resident (sc_pca_begin)", who);
-    PcaState &s = *c->pca;
+    PcaState &s = *pca_state(c);
     const int G = s.G;
     std::vector<double> tab((size_t)G * K);
     for (int k = 0; k < K; ++k) {
@@ -356,6 +347,6 @@ extern "C" int sc_pca_end(sc_ctx *c)
     SC_REQUIRE(c, SC_ERR_INVALID, "sc_pca_end: null pointer");
     if (!c->pca) return SC_OK;
     SC_HIP(hipSetDevice(c->device));
-    sc_pca_release(c);
+    sc_resident_drop(c, c->pca);
     return SC_OK;
 }

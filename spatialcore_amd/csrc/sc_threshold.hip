@@ -516,17 +516,6 @@ __global__ __launch_bounds__(256) void k_gmm_posterior(const T *__restrict__ X, 
     if (t == 0 && cnt) atomicAdd(n_high, (u64)cnt);
 }
 
-template <int N>
-struct ThBufs {
-    sc_ctx *c;
-    DBuf b[N];
-    explicit ThBufs(sc_ctx *ctx) : c(ctx) {}
-    ~ThBufs()
-    {
-        for (DBuf &d : b) d.release(&c->mem);
-    }
-};
-
 inline size_t esize(int dtype) { return dtype == SC_F32 ? sizeof(float) : sizeof(double); }
 
 int gmm_pass(sc_ctx *c, int dtype, bool init, const void *X, int64_t n, int K, int R, const GmmRun *runs,
@@ -562,35 +551,35 @@ extern "C" int sc_metagene_score(sc_ctx *c, const void *features, int dtype, int
     hipStream_t s = c->stream;
     const size_t es = esize(dtype);
     const int64_t NB = ceil_div64(n, TH_BLK);
-    ThBufs<6> m(c);
+    DBuf m[6];
     enum { X, VALID, SCORE, PART, STATS, COUNTS };
-    SC_TRY(m.b[X].ensure(es * (size_t)(n * n_features), &c->mem));
-    SC_TRY(m.b[VALID].ensure((size_t)n, &c->mem));
-    SC_TRY(m.b[SCORE].ensure(es * (size_t)n, &c->mem));
-    SC_TRY(m.b[PART].ensure(sizeof(double) * 3 * (size_t)NB, &c->mem));
-    SC_TRY(m.b[STATS].ensure(sizeof(double) * 3, &c->mem));
-    SC_TRY(m.b[COUNTS].ensure(sizeof(u64) * 3, &c->mem));
-    SC_HIP(hipMemcpyAsync(m.b[X].p, features, es * (size_t)(n * n_features), hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemsetAsync(m.b[COUNTS].p, 0, sizeof(u64) * 3, s));
+    SC_TRY(m[X].ensure(es * (size_t)(n * n_features), &c->mem));
+    SC_TRY(m[VALID].ensure((size_t)n, &c->mem));
+    SC_TRY(m[SCORE].ensure(es * (size_t)n, &c->mem));
+    SC_TRY(m[PART].ensure(sizeof(double) * 3 * (size_t)NB, &c->mem));
+    SC_TRY(m[STATS].ensure(sizeof(double) * 3, &c->mem));
+    SC_TRY(m[COUNTS].ensure(sizeof(u64) * 3, &c->mem));
+    SC_HIP(hipMemcpyAsync(m[X].p, features, es * (size_t)(n * n_features), hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemsetAsync(m[COUNTS].p, 0, sizeof(u64) * 3, s));
     {
         KernelTimerScope ts(c, SC_K_THRESH_SCORE);
         if (dtype == SC_F32)
-            hipLaunchKernelGGL(k_metagene<float>, dim3((unsigned)NB), dim3(TH_TPB), 0, s, m.b[X].as<float>(), n, (int)n_features,
-                               (int)method, pseudocount, m.b[VALID].as<uint8_t>(), m.b[SCORE].as<float>(),
-                               m.b[PART].as<double>(), m.b[COUNTS].as<u64>());
+            hipLaunchKernelGGL(k_metagene<float>, dim3((unsigned)NB), dim3(TH_TPB), 0, s, m[X].as<float>(), n, (int)n_features,
+                               (int)method, pseudocount, m[VALID].as<uint8_t>(), m[SCORE].as<float>(),
+                               m[PART].as<double>(), m[COUNTS].as<u64>());
         else
-            hipLaunchKernelGGL(k_metagene<double>, dim3((unsigned)NB), dim3(TH_TPB), 0, s, m.b[X].as<double>(), n, (int)n_features,
-                               (int)method, pseudocount, m.b[VALID].as<uint8_t>(), m.b[SCORE].as<double>(),
-                               m.b[PART].as<double>(), m.b[COUNTS].as<u64>());
-        hipLaunchKernelGGL(k_metagene_final, dim3(1), dim3(64), 0, s, m.b[PART].as<double>(), NB, m.b[STATS].as<double>());
+            hipLaunchKernelGGL(k_metagene<double>, dim3((unsigned)NB), dim3(TH_TPB), 0, s, m[X].as<double>(), n, (int)n_features,
+                               (int)method, pseudocount, m[VALID].as<uint8_t>(), m[SCORE].as<double>(),
+                               m[PART].as<double>(), m[COUNTS].as<u64>());
+        hipLaunchKernelGGL(k_metagene_final, dim3(1), dim3(64), 0, s, m[PART].as<double>(), NB, m[STATS].as<double>());
     }
     SC_HIP(hipGetLastError());
     double st[3];
     u64 cnt[3];
-    SC_HIP(hipMemcpyAsync(valid_out, m.b[VALID].p, (size_t)n, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(score_out, m.b[SCORE].p, es * (size_t)n, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(st, m.b[STATS].p, sizeof(st), hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(cnt, m.b[COUNTS].p, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(valid_out, m[VALID].p, (size_t)n, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(score_out, m[SCORE].p, es * (size_t)n, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(st, m[STATS].p, sizeof(st), hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(cnt, m[COUNTS].p, sizeof(cnt), hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     stats_out[0] = st[1];
     stats_out[1] = st[2];
@@ -619,48 +608,48 @@ extern "C" int sc_ks_prepare(sc_ctx *c, const void *scores, int dtype, int64_t n
     if (m_bg > n) m_bg = n;
     const int64_t NB = ceil_div64(m_bg, TH_BLK);
     c->th_n = 0;
-    ThBufs<9> m(c);
+    DBuf m[9];
     enum { X, K1, K2, I1, I2, PART, RED, RANKS, RVAL };
-    SC_TRY(m.b[X].ensure(es * (size_t)n, &c->mem));
-    SC_TRY(m.b[K1].ensure(sizeof(u64) * (size_t)n, &c->mem));
-    SC_TRY(m.b[K2].ensure(sizeof(u64) * (size_t)n, &c->mem));
-    SC_TRY(m.b[I1].ensure(sizeof(uint32_t) * (size_t)n, &c->mem));
-    SC_TRY(m.b[I2].ensure(sizeof(uint32_t) * (size_t)n, &c->mem));
-    SC_TRY(m.b[PART].ensure(sizeof(double) * (size_t)NB, &c->mem));
-    SC_TRY(m.b[RED].ensure(sizeof(double) * 2, &c->mem));
-    SC_TRY(m.b[RANKS].ensure(sizeof(int64_t) * 64, &c->mem));
-    SC_TRY(m.b[RVAL].ensure(sizeof(double) * 64, &c->mem));
+    SC_TRY(m[X].ensure(es * (size_t)n, &c->mem));
+    SC_TRY(m[K1].ensure(sizeof(u64) * (size_t)n, &c->mem));
+    SC_TRY(m[K2].ensure(sizeof(u64) * (size_t)n, &c->mem));
+    SC_TRY(m[I1].ensure(sizeof(uint32_t) * (size_t)n, &c->mem));
+    SC_TRY(m[I2].ensure(sizeof(uint32_t) * (size_t)n, &c->mem));
+    SC_TRY(m[PART].ensure(sizeof(double) * (size_t)NB, &c->mem));
+    SC_TRY(m[RED].ensure(sizeof(double) * 2, &c->mem));
+    SC_TRY(m[RANKS].ensure(sizeof(int64_t) * 64, &c->mem));
+    SC_TRY(m[RVAL].ensure(sizeof(double) * 64, &c->mem));
     SC_TRY(c->th_sorted.ensure(sizeof(double) * (size_t)n, &c->mem));
-    SC_HIP(hipMemcpyAsync(m.b[X].p, scores, es * (size_t)n, hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(m[X].p, scores, es * (size_t)n, hipMemcpyHostToDevice, s));
     const dim3 flat((unsigned)ceil_div64(n, 256)), tpb(256);
     double *sorted = c->th_sorted.as<double>();
     double sum = 0.0, ss = 0.0;
     {
         KernelTimerScope ts(c, SC_K_THRESH_SORT);
-        if (dtype == SC_F32) hipLaunchKernelGGL(k_ks_keys<float>, flat, tpb, 0, s, m.b[X].as<float>(), n, m.b[K1].as<u64>(), m.b[I1].as<uint32_t>());
-        else hipLaunchKernelGGL(k_ks_keys<double>, flat, tpb, 0, s, m.b[X].as<double>(), n, m.b[K1].as<u64>(), m.b[I1].as<uint32_t>());
-        SC_TRY((rs_sort<u64, uint32_t>(c, m.b[K1].as<u64>(), m.b[K2].as<u64>(), m.b[I1].as<uint32_t>(), m.b[I2].as<uint32_t>(), n, 64)));
-        hipLaunchKernelGGL(k_ks_unkey, flat, tpb, 0, s, m.b[K2].as<u64>(), n, sorted);
+        if (dtype == SC_F32) hipLaunchKernelGGL(k_ks_keys<float>, flat, tpb, 0, s, m[X].as<float>(), n, m[K1].as<u64>(), m[I1].as<uint32_t>());
+        else hipLaunchKernelGGL(k_ks_keys<double>, flat, tpb, 0, s, m[X].as<double>(), n, m[K1].as<u64>(), m[I1].as<uint32_t>());
+        SC_TRY((rs_sort<u64, uint32_t>(c, m[K1].as<u64>(), m[K2].as<u64>(), m[I1].as<uint32_t>(), m[I2].as<uint32_t>(), n, 64)));
+        hipLaunchKernelGGL(k_ks_unkey, flat, tpb, 0, s, m[K2].as<u64>(), n, sorted);
         // background moments: the mean, then the squared deviations around it (two passes, as numpy's std)
-        hipLaunchKernelGGL(k_th_sum, dim3((unsigned)NB), tpb, 0, s, sorted, m_bg, 0, 0.0, m.b[PART].as<double>());
-        hipLaunchKernelGGL(k_th_final, dim3(1), dim3(64), 0, s, m.b[PART].as<double>(), NB, 1, m.b[RED].as<double>());
+        hipLaunchKernelGGL(k_th_sum, dim3((unsigned)NB), tpb, 0, s, sorted, m_bg, 0, 0.0, m[PART].as<double>());
+        hipLaunchKernelGGL(k_th_final, dim3(1), dim3(64), 0, s, m[PART].as<double>(), NB, 1, m[RED].as<double>());
     }
     SC_HIP(hipGetLastError());
-    SC_HIP(hipMemcpyAsync(&sum, m.b[RED].p, sizeof(double), hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(&sum, m[RED].p, sizeof(double), hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     const double mean = sum / (double)m_bg;
     {
         KernelTimerScope ts(c, SC_K_THRESH_SORT);
-        hipLaunchKernelGGL(k_th_sum, dim3((unsigned)NB), tpb, 0, s, sorted, m_bg, 1, mean, m.b[PART].as<double>());
-        hipLaunchKernelGGL(k_th_final, dim3(1), dim3(64), 0, s, m.b[PART].as<double>(), NB, 1, m.b[RED].as<double>() + 1);
+        hipLaunchKernelGGL(k_th_sum, dim3((unsigned)NB), tpb, 0, s, sorted, m_bg, 1, mean, m[PART].as<double>());
+        hipLaunchKernelGGL(k_th_final, dim3(1), dim3(64), 0, s, m[PART].as<double>(), NB, 1, m[RED].as<double>() + 1);
         if (n_ranks > 0) {
-            SC_HIP(hipMemcpyAsync(m.b[RANKS].p, ranks, sizeof(int64_t) * (size_t)n_ranks, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_gather, dim3(1), dim3(64), 0, s, sorted, m.b[RANKS].as<int64_t>(), (int)n_ranks, m.b[RVAL].as<double>());
+            SC_HIP(hipMemcpyAsync(m[RANKS].p, ranks, sizeof(int64_t) * (size_t)n_ranks, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_gather, dim3(1), dim3(64), 0, s, sorted, m[RANKS].as<int64_t>(), (int)n_ranks, m[RVAL].as<double>());
         }
     }
     SC_HIP(hipGetLastError());
-    SC_HIP(hipMemcpyAsync(&ss, m.b[RED].as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost, s));
-    if (n_ranks > 0) SC_HIP(hipMemcpyAsync(rank_out, m.b[RVAL].p, sizeof(double) * (size_t)n_ranks, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(&ss, m[RED].as<double>() + 1, sizeof(double), hipMemcpyDeviceToHost, s));
+    if (n_ranks > 0) SC_HIP(hipMemcpyAsync(rank_out, m[RVAL].p, sizeof(double) * (size_t)n_ranks, hipMemcpyDeviceToHost, s));
     if (sorted_out) SC_HIP(hipMemcpyAsync(sorted_out, sorted, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     bg_out[0] = mean;
@@ -678,23 +667,23 @@ extern "C" int sc_ks_argmax(sc_ctx *c, double bg_mean, double bg_std, int64_t *i
     SC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const int64_t n = c->th_n, NB = ceil_div64(n, TH_BLK);
-    ThBufs<4> m(c);
+    DBuf m[4];
     enum { BVAL, BIDX, OUT, IOUT };
-    SC_TRY(m.b[BVAL].ensure(sizeof(double) * (size_t)NB, &c->mem));
-    SC_TRY(m.b[BIDX].ensure(sizeof(int64_t) * (size_t)NB, &c->mem));
-    SC_TRY(m.b[OUT].ensure(sizeof(double) * 2, &c->mem));
-    SC_TRY(m.b[IOUT].ensure(sizeof(int64_t), &c->mem));
+    SC_TRY(m[BVAL].ensure(sizeof(double) * (size_t)NB, &c->mem));
+    SC_TRY(m[BIDX].ensure(sizeof(int64_t) * (size_t)NB, &c->mem));
+    SC_TRY(m[OUT].ensure(sizeof(double) * 2, &c->mem));
+    SC_TRY(m[IOUT].ensure(sizeof(int64_t), &c->mem));
     {
         KernelTimerScope ts(c, SC_K_THRESH_KS);
         hipLaunchKernelGGL(k_ks_argmax, dim3((unsigned)NB), dim3(TH_TPB), 0, s, c->th_sorted.as<double>(), n, bg_mean, bg_std,
-                           m.b[BVAL].as<double>(), m.b[BIDX].as<int64_t>());
-        hipLaunchKernelGGL(k_ks_argmax_final, dim3(1), dim3(64), 0, s, m.b[BVAL].as<double>(), m.b[BIDX].as<int64_t>(), NB,
-                           c->th_sorted.as<double>(), m.b[OUT].as<double>(), m.b[IOUT].as<int64_t>());
+                           m[BVAL].as<double>(), m[BIDX].as<int64_t>());
+        hipLaunchKernelGGL(k_ks_argmax_final, dim3(1), dim3(64), 0, s, m[BVAL].as<double>(), m[BIDX].as<int64_t>(), NB,
+                           c->th_sorted.as<double>(), m[OUT].as<double>(), m[IOUT].as<int64_t>());
     }
     SC_HIP(hipGetLastError());
     double out[2];
-    SC_HIP(hipMemcpyAsync(out, m.b[OUT].p, sizeof(out), hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(index_out, m.b[IOUT].p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(out, m[OUT].p, sizeof(out), hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(index_out, m[IOUT].p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     *d_out = out[0];
     *score_out = out[1];
@@ -714,29 +703,29 @@ extern "C" int sc_ks_classify(sc_ctx *c, const void *scores, int dtype, int64_t 
     const size_t es = esize(dtype);
     double range = max_score - threshold;
     if (range < 1e-10) range = 1e-10;
-    ThBufs<4> m(c);
+    DBuf m[4];
     enum { X, DEV, LAB, CNT };
-    SC_TRY(m.b[X].ensure(es * (size_t)n, &c->mem));
-    SC_TRY(m.b[DEV].ensure(sizeof(double) * (size_t)n, &c->mem));
-    SC_TRY(m.b[LAB].ensure(sizeof(int32_t) * (size_t)n, &c->mem));
-    SC_TRY(m.b[CNT].ensure(sizeof(u64), &c->mem));
-    SC_HIP(hipMemcpyAsync(m.b[X].p, scores, es * (size_t)n, hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemsetAsync(m.b[CNT].p, 0, sizeof(u64), s));
+    SC_TRY(m[X].ensure(es * (size_t)n, &c->mem));
+    SC_TRY(m[DEV].ensure(sizeof(double) * (size_t)n, &c->mem));
+    SC_TRY(m[LAB].ensure(sizeof(int32_t) * (size_t)n, &c->mem));
+    SC_TRY(m[CNT].ensure(sizeof(u64), &c->mem));
+    SC_HIP(hipMemcpyAsync(m[X].p, scores, es * (size_t)n, hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemsetAsync(m[CNT].p, 0, sizeof(u64), s));
     const dim3 flat((unsigned)ceil_div64(n, 256)), tpb(256);
     {
         KernelTimerScope ts(c, SC_K_THRESH_KS);
         if (dtype == SC_F32)
-            hipLaunchKernelGGL(k_ks_classify<float>, flat, tpb, 0, s, m.b[X].as<float>(), n, threshold, range, m.b[DEV].as<double>(),
-                               m.b[LAB].as<int32_t>(), m.b[CNT].as<u64>());
+            hipLaunchKernelGGL(k_ks_classify<float>, flat, tpb, 0, s, m[X].as<float>(), n, threshold, range, m[DEV].as<double>(),
+                               m[LAB].as<int32_t>(), m[CNT].as<u64>());
         else
-            hipLaunchKernelGGL(k_ks_classify<double>, flat, tpb, 0, s, m.b[X].as<double>(), n, threshold, range, m.b[DEV].as<double>(),
-                               m.b[LAB].as<int32_t>(), m.b[CNT].as<u64>());
+            hipLaunchKernelGGL(k_ks_classify<double>, flat, tpb, 0, s, m[X].as<double>(), n, threshold, range, m[DEV].as<double>(),
+                               m[LAB].as<int32_t>(), m[CNT].as<u64>());
     }
     SC_HIP(hipGetLastError());
     u64 cnt = 0;
-    SC_HIP(hipMemcpyAsync(deviation_out, m.b[DEV].p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(labels_out, m.b[LAB].p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(&cnt, m.b[CNT].p, sizeof(u64), hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(deviation_out, m[DEV].p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(labels_out, m[LAB].p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(&cnt, m[CNT].p, sizeof(u64), hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     *n_high_out = (int64_t)cnt;
     return SC_OK;
@@ -765,18 +754,18 @@ extern "C" int sc_gmm_fit(sc_ctx *c, const void *scores, int dtype, int64_t n, i
     const size_t es = esize(dtype);
     const int R = n_init;
     const int64_t NB = ceil_div64(n, TH_BLK);
-    ThBufs<4> m(c);
+    DBuf m[4];
     enum { X, LAB, PART, RUNS };
-    SC_TRY(m.b[X].ensure(es * (size_t)n, &c->mem));
-    SC_TRY(m.b[LAB].ensure(sizeof(int32_t) * (size_t)R * (size_t)n, &c->mem));
-    SC_TRY(m.b[PART].ensure(sizeof(double) * (size_t)R * (size_t)NB * GMM_NV, &c->mem));
-    SC_TRY(m.b[RUNS].ensure(sizeof(GmmRun) * (size_t)R, &c->mem));
+    SC_TRY(m[X].ensure(es * (size_t)n, &c->mem));
+    SC_TRY(m[LAB].ensure(sizeof(int32_t) * (size_t)R * (size_t)n, &c->mem));
+    SC_TRY(m[PART].ensure(sizeof(double) * (size_t)R * (size_t)NB * GMM_NV, &c->mem));
+    SC_TRY(m[RUNS].ensure(sizeof(GmmRun) * (size_t)R, &c->mem));
 
     // ---- every run's k-means labels (sc_kmeans.hip) --------------------------------------------------------------
-    SC_TRY(sc_kmeans_run_labels(c, scores, dtype, n, 1, K, R, km_max_iter, km_tol, x_mean, uniforms, m.b[LAB].as<int32_t>()));
+    SC_TRY(sc_kmeans_run_labels(c, scores, dtype, n, 1, K, R, km_max_iter, km_tol, x_mean, uniforms, m[LAB].as<int32_t>()));
     if (km_labels_out)
-        SC_HIP(hipMemcpyAsync(km_labels_out, m.b[LAB].p, sizeof(int32_t) * (size_t)R * (size_t)n, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(m.b[X].p, scores, es * (size_t)n, hipMemcpyHostToDevice, s));
+        SC_HIP(hipMemcpyAsync(km_labels_out, m[LAB].p, sizeof(int32_t) * (size_t)R * (size_t)n, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(m[X].p, scores, es * (size_t)n, hipMemcpyHostToDevice, s));
 
     // ---- initialisation: means, then variances around them ---------------------------------------------------------
     std::vector<GmmRun> runs((size_t)R);
@@ -785,18 +774,18 @@ extern "C" int sc_gmm_fit(sc_ctx *c, const void *scores, int dtype, int64_t n, i
         g.lb = -INFINITY;
         g.active = 1;
     }
-    SC_HIP(hipMemcpyAsync(m.b[RUNS].p, runs.data(), sizeof(GmmRun) * (size_t)R, hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(m[RUNS].p, runs.data(), sizeof(GmmRun) * (size_t)R, hipMemcpyHostToDevice, s));
     const double shift0 = dtype == SC_F32 ? (double)*(const float *)x_mean : *(const double *)x_mean;
-    GmmRun *druns = m.b[RUNS].as<GmmRun>();
-    double *part = m.b[PART].as<double>();
+    GmmRun *druns = m[RUNS].as<GmmRun>();
+    double *part = m[PART].as<double>();
     auto stage2 = [&](int mode) {
         hipLaunchKernelGGL(k_gmm_stage2, dim3((unsigned)R), dim3(64), 0, s, part, NB, (int)K, n, mode, reg_covar, tol, (int)max_iter, druns);
     };
     {
         KernelTimerScope ts(c, SC_K_GMM_EM);
-        SC_TRY(gmm_pass(c, dtype, true, m.b[X].p, n, K, R, druns, m.b[LAB].as<int32_t>(), 0, shift0, part));
+        SC_TRY(gmm_pass(c, dtype, true, m[X].p, n, K, R, druns, m[LAB].as<int32_t>(), 0, shift0, part));
         stage2(0);
-        SC_TRY(gmm_pass(c, dtype, true, m.b[X].p, n, K, R, druns, m.b[LAB].as<int32_t>(), 1, shift0, part));
+        SC_TRY(gmm_pass(c, dtype, true, m[X].p, n, K, R, druns, m[LAB].as<int32_t>(), 1, shift0, part));
         stage2(1);
     }
     SC_HIP(hipGetLastError());
@@ -805,7 +794,7 @@ extern "C" int sc_gmm_fit(sc_ctx *c, const void *scores, int dtype, int64_t n, i
     for (int it = 0; it < max_iter; ++it) {
         {
             KernelTimerScope ts(c, SC_K_GMM_EM);
-            SC_TRY(gmm_pass(c, dtype, false, m.b[X].p, n, K, R, druns, nullptr, 1, 0.0, part));
+            SC_TRY(gmm_pass(c, dtype, false, m[X].p, n, K, R, druns, nullptr, 1, 0.0, part));
             stage2(2);
         }
         SC_HIP(hipGetLastError());
@@ -860,35 +849,35 @@ extern "C" int sc_gmm_posterior(sc_ctx *c, const void *scores, int dtype, int64_
     SC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t es = esize(dtype);
-    ThBufs<6> m(c);
+    DBuf m[6];
     enum { X, PAR, HIGH, PROB, LAB, CNT };
-    SC_TRY(m.b[X].ensure(es * (size_t)n, &c->mem));
-    SC_TRY(m.b[PAR].ensure(sizeof(par), &c->mem));
-    SC_TRY(m.b[HIGH].ensure(sizeof(int32_t) * GMM_KMAX, &c->mem));
-    SC_TRY(m.b[PROB].ensure(sizeof(double) * (size_t)n, &c->mem));
-    SC_TRY(m.b[LAB].ensure(sizeof(int32_t) * (size_t)n, &c->mem));
-    SC_TRY(m.b[CNT].ensure(sizeof(u64), &c->mem));
-    SC_HIP(hipMemcpyAsync(m.b[X].p, scores, es * (size_t)n, hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemcpyAsync(m.b[PAR].p, par, sizeof(par), hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemcpyAsync(m.b[HIGH].p, high, sizeof(int32_t) * (size_t)n_high, hipMemcpyHostToDevice, s));
-    SC_HIP(hipMemsetAsync(m.b[CNT].p, 0, sizeof(u64), s));
+    SC_TRY(m[X].ensure(es * (size_t)n, &c->mem));
+    SC_TRY(m[PAR].ensure(sizeof(par), &c->mem));
+    SC_TRY(m[HIGH].ensure(sizeof(int32_t) * GMM_KMAX, &c->mem));
+    SC_TRY(m[PROB].ensure(sizeof(double) * (size_t)n, &c->mem));
+    SC_TRY(m[LAB].ensure(sizeof(int32_t) * (size_t)n, &c->mem));
+    SC_TRY(m[CNT].ensure(sizeof(u64), &c->mem));
+    SC_HIP(hipMemcpyAsync(m[X].p, scores, es * (size_t)n, hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(m[PAR].p, par, sizeof(par), hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(m[HIGH].p, high, sizeof(int32_t) * (size_t)n_high, hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemsetAsync(m[CNT].p, 0, sizeof(u64), s));
     const dim3 flat((unsigned)ceil_div64(n, 256)), tpb(256);
     {
         KernelTimerScope ts(c, SC_K_GMM_POST);
         if (dtype == SC_F32)
-            hipLaunchKernelGGL(k_gmm_posterior<float>, flat, tpb, 0, s, m.b[X].as<float>(), n, (int)K, m.b[PAR].as<double>(),
-                               m.b[HIGH].as<int32_t>(), (int)n_high, cutoff, m.b[PROB].as<double>(), m.b[LAB].as<int32_t>(),
-                               m.b[CNT].as<u64>());
+            hipLaunchKernelGGL(k_gmm_posterior<float>, flat, tpb, 0, s, m[X].as<float>(), n, (int)K, m[PAR].as<double>(),
+                               m[HIGH].as<int32_t>(), (int)n_high, cutoff, m[PROB].as<double>(), m[LAB].as<int32_t>(),
+                               m[CNT].as<u64>());
         else
-            hipLaunchKernelGGL(k_gmm_posterior<double>, flat, tpb, 0, s, m.b[X].as<double>(), n, (int)K, m.b[PAR].as<double>(),
-                               m.b[HIGH].as<int32_t>(), (int)n_high, cutoff, m.b[PROB].as<double>(), m.b[LAB].as<int32_t>(),
-                               m.b[CNT].as<u64>());
+            hipLaunchKernelGGL(k_gmm_posterior<double>, flat, tpb, 0, s, m[X].as<double>(), n, (int)K, m[PAR].as<double>(),
+                               m[HIGH].as<int32_t>(), (int)n_high, cutoff, m[PROB].as<double>(), m[LAB].as<int32_t>(),
+                               m[CNT].as<u64>());
     }
     SC_HIP(hipGetLastError());
     u64 cnt = 0;
-    SC_HIP(hipMemcpyAsync(prob_out, m.b[PROB].p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(labels_out, m.b[LAB].p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
-    SC_HIP(hipMemcpyAsync(&cnt, m.b[CNT].p, sizeof(u64), hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(prob_out, m[PROB].p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(labels_out, m[LAB].p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipMemcpyAsync(&cnt, m[CNT].p, sizeof(u64), hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     *n_high_cells_out = (int64_t)cnt;
     return SC_OK;
