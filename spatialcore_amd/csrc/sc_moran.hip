@@ -1508,7 +1508,10 @@ extern "C" int sc_moran(sc_ctx *c, int64_t n_perm, double *I_out, double *sims_o
                                  // 112 -> 149.7 / 149.2, 128 -> 143.8 / 143.5, 144 -> 143.9 / 143.8 (and 120 -> 146.1 / 146.3, 125 ->
                                  // 144.5 / 144.2, 136 -> 147.4 / 146.7).  At 112 the integer kernel's launches are a tenth shorter than the
                                  // fp64 kernel's (104 ms per step instead of 116) but the chain beside them slows from 123 to 129 ms and
-                                 // the step stays where it was; with 16 more CUs the chain takes 105 ms, the launches 109 ms
+                                 // the step stays where it was; with 16 more CUs the chain takes 105 ms, the launches 109 ms.
+                                 // Swept again with the coalesced expansion (k_expand 10.8 instead of 17.7 ms of the generator's CUs
+                                 // per step), same protocol: 112 -> 145.1 / 144.4, 120 -> 144.1 / 142.6, 128 -> 140.3 / 139.7 (chain
+                                 // 126 / 120 / 101 ms): the cheaper expansion does not let the generator give CUs back, 128 stays
 static int moran_seeded_once(sc_ctx *c, uint64_t *state6, int64_t n_perm, double *I_out, double *sims_out,
                              int64_t *count_ge_out, double *sim_sum_out, double *sim_sumsq_out, PermPipe *begun)
 {
