@@ -5,7 +5,7 @@
 // what both files finish a chunked sum with (column chunks here, cell chunks there): the chunk sums in chunk order.
 #pragma once
 
-#include "sc_ctx.h"
+#include "sc_sortscan.h"
 
 namespace {
 
@@ -124,9 +124,8 @@ inline int colsort_enqueue(sc_ctx *c, ColSort &cs, const int64_t *indptr, const 
     const dim3 per_entry((unsigned)ceil_div64(nnz, 256)), per_gene((unsigned)ceil_div64(G + 1, 256)), tpb(256);
     hipLaunchKernelGGL(k_cs_keys, per_entry, tpb, 0, s, indices, nnz, cs.keys.as<u64>(), cs.pos.as<uint32_t>());
     hipLaunchKernelGGL(k_cs_rowids, dim3((unsigned)ceil_div64(n, 256)), tpb, 0, s, indptr, n, cs.rowid.as<int32_t>());
-    int end_bit = 1;
-    while ((1 << end_bit) < G) ++end_bit;
-    SC_TRY((rs_sort<u64, uint32_t>(c, cs.keys.as<u64>(), cs.gene.as<u64>(), cs.pos.as<uint32_t>(), cs.pos2.as<uint32_t>(), nnz, end_bit)));
+    SC_TRY(sc_sort_pairs(c, c->rs_tmp, s, cs.keys.as<u64>(), cs.gene.as<u64>(), cs.pos.as<uint32_t>(), cs.pos2.as<uint32_t>(), nnz,
+                         sc_bits_for(G)));
     hipLaunchKernelGGL(k_cs_fill, per_entry, tpb, 0, s, cs.pos2.as<uint32_t>(), cs.rowid.as<int32_t>(), val, nnz, cs.crow.as<int32_t>(),
                        cs.cval.as<double>());
     hipLaunchKernelGGL(k_cs_colptr, per_gene, tpb, 0, s, cs.gene.as<u64>(), nnz, G, cs.colptr.as<int64_t>());

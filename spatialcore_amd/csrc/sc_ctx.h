@@ -229,10 +229,8 @@ struct sc_ctx {
     DBuf th_sorted;
     int64_t th_n = 0;
     // ---- the dense search (sc_neighbors.hip): the fp64 features and neighbour lists of the last sc_knn_dense[_gram].  Written
-    // by sc_neighbors.hip alone; read by df_build_union (idx), sc_diffmap_graph (X, d2, d) and sc_fuzzy_graph (idx, d2, k).
-    // What invalidates what: a new search and sc_diffmap_graph_csr clear knn.valid, df.graph_valid and df.lanczos_valid (a
-    // finished search sets knn.valid); a graph from the lists clears the other two; df_finish_graph sets df.graph_valid;
-    // sc_lanczos_begin sets df.lanczos_valid, a breakdown and sc_lanczos_end clear it ----
+    // by sc_neighbors.hip alone; read by lg_build_union (idx), sc_diffmap_graph (X, d2, d) and sc_fuzzy_graph (idx, d2, k).
+    // What invalidates what among knn.valid, lg.valid and lz.valid: the functions of sc_list_graph.h ----
     struct DenseKnn {
         int64_t n = 0;      // rows of the lists
         int d = 0, k = 0;   // columns of X (the features padded to a multiple of 8), list length
@@ -240,18 +238,29 @@ struct sc_ctx {
         DBuf X, raw, idx, d2, pidx, pd2;        // [n][d] fp64, the upload, [n][k] result, [split][query][k] partial lists
         DBuf gnorm, gkept, gcnt, glo, grows;    // the Gram filter: row norms, kept candidates [n][L], their counts, the L-th keys, [count | uncertified rows]
     } knn;
-    // ---- graphs on those lists or from a caller (sc_diffusion.hip, sc_umap.hip): the resident weighted graph with its
-    // transition matrix, UMAP's bandwidths and layout buffers, the Lanczos basis ----
-    struct Diffusion {
-        // the resident graph's vertices (df_build_union: knn.n; sc_diffmap_graph_csr: its n) and stored entries; Lanczos steps, basis size
-        int64_t n = 0, nnz = 0, m = 0, max_basis = 0;
-        bool graph_valid = false, lanczos_valid = false;
-        DBuf s2, keys, keys2, pay, pay2, cnt, off;   // local scales; (row << 32 | column) keys, the sort's payload, first-of-run flags and offsets
-        DBuf indptr, indices, w, T, q, parent, flag;   // CSR (rows sorted by column): kernel weights, transition matrix; row sums; union-find
+    // ---- the resident weighted graph (sc_list_graph.h).  Written by sc_list_graph.hip (the union, the upload, the finish;
+    // `valid` by its validity functions alone) and by the two kernels that fill `w` between the union and the finish
+    // (sc_diffmap_graph, sc_fuzzy_graph, which also set nnz); read by Lanczos, sc_umap_layout and Louvain through lg_resident ----
+    struct ListGraph {
+        int64_t n = 0, nnz = 0;   // vertices (lg_build_union: knn.n; sc_diffmap_graph_csr: its n) and stored entries
+        bool valid = false;
+        DBuf indptr, indices, w;            // CSR, rows sorted by column; the weights
+        DBuf T, q, parent, flag;            // lg_finish: transition matrix, [row sums | density], union-find, root count
+        DBuf keys, keys2, pay, pay2, cnt, off;   // lg_build_union: (row << 32 | column) keys, the sort's payload, first-of-run flags and offsets
+    } lg;
+    // ---- diffusion's own (sc_diffusion.hip writes and reads it; `valid` through lz_open / lz_close of sc_list_graph.h): the
+    // local scales of sc_diffmap_graph, and the Lanczos run on lg's transition matrix ----
+    struct Lanczos {
+        int64_t m = 0, max_basis = 0;   // steps taken, basis size
+        bool valid = false;
+        DBuf s2;                        // sc_diffmap_graph's local scales
+        DBuf V, wv, part, coef, ab, Y, S, res;   // basis [max_basis + 1][n], work vector, chunk partials, coefficients, alpha | beta, Ritz vectors, their coefficients, residuals
+    } lz;
+    // ---- UMAP's work buffers (sc_umap.hip writes and reads them; nothing else does) ----
+    struct UmapWork {
         DBuf rho, sigma, dsum;                  // sc_fuzzy_graph: first non-zero distance, bandwidth, [row sums of the distances | chunk sums | their total]
         DBuf lip, lix, lw, ly0, ly1, lmax;      // sc_umap_layout: a caller's CSR, the two position buffers, the bits of w_max
-        DBuf V, wv, part, coef, ab, Y, S, res;   // basis [max_basis + 1][n], work vector, chunk partials, coefficients, alpha | beta, Ritz vectors, their coefficients, residuals
-    } df;
+    } um;
     // ---- annotation (sc_annotate.hip): the training problem kept on the device between sc_annot_train_begin and _end ----
     std::unique_ptr<Resident> an;        // AnnotTrain
     // ---- PCA (sc_pca.hip): the matrix kept on the device between sc_pca_begin and sc_pca_end ----
@@ -463,11 +472,6 @@ void sc_graph_moments_drain(sc_ctx *c);  // wait for a begun computation (before
 int sc_graph_capture_order(sc_ctx *c, int64_t n);  // called by the graph setters
 int sc_graph_ensure_order(sc_ctx *c);           // rank / relabelled columns / float weights, built on first use
 int sc_perm_generate_device(sc_ctx *c, uint64_t *state6, int64_t n, int64_t n_perm);
-// ---- shared with sc_threshold.hip ----
-// device-wide radix sort of cnt (key, payload) pairs on the key bits [0, end_bit), on c->stream; scratch in c->rs_tmp
-// (sc_ranksum.hip, which instantiates the combinations in use)
-template <class K, class V>
-int rs_sort(sc_ctx *c, const K *k_in, K *k_out, const V *v_in, V *v_out, int64_t cnt, int end_bit);
 // sc_kmeans_fit's seeding and Lloyd passes for n_init runs (same arguments), keeping EVERY run's final labels:
 // labels_dev[n_init][n] is a device array, written on c->stream (sc_kmeans.hip)
 int sc_kmeans_run_labels(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t C, int32_t K, int32_t n_init,

@@ -1,8 +1,6 @@
 // What more than one unit needs of the exact search in d dimensions (sc_neighbors.hip: sc_knn_dense, the direct kernels,
 // and sc_knn_dense_gram, the certified Gram-form filter): the limits and the direct-form squared distance whose bits every
-// neighbour list of the project is pinned to, which sc_diffmap_graph's weights repeat.  And what the two graphs on those
-// lists share (sc_diffusion.hip: sc_diffmap_graph; sc_umap.hip: sc_fuzzy_graph): the row of a stored entry, the symmetric
-// union as a CSR pattern and the tail that makes a weighted graph the resident one.
+// neighbour list of the project is pinned to, which sc_diffmap_graph's weights repeat.
 #pragma once
 
 #include "sc_ctx.h"
@@ -32,21 +30,3 @@ __device__ __forceinline__ double df_d2(const Q &q, const X &x, int dp)
     }
     return acc;
 }
-
-// the row of stored entry e: the last i with indptr[i] <= e (no row is empty)
-__device__ __forceinline__ int64_t df_row_of(const int64_t *__restrict__ indptr, int64_t n, int64_t e)
-{
-    int64_t lo = 0, hi = n;   // indptr[lo] <= e < indptr[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (indptr[mid] <= e) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// sc_diffusion.hip.  df_build_union: the symmetric union of the resident lists (ctx->knn) as indptr / indices on the device
-// (rows sorted by column), *nnz_out = its stored entries; df.n becomes the lists' row count.  df_finish_graph: on the
-// resident CSR with its weights w in place: row sums, density, transition matrix and the connected components; marks the
-// graph valid for sc_diffmap_graph_get, sc_lanczos_begin and sc_louvain_begin_resident.
-int df_build_union(sc_ctx *c, long long *nnz_out);
-int df_finish_graph(sc_ctx *c, int64_t *n_components_out);

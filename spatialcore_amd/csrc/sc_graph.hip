@@ -3,10 +3,9 @@
 #include <float.h>
 #include <math.h>
 
-#include <hipcub/hipcub.hpp>
 #include <vector>
 
-#include "sc_ctx.h"
+#include "sc_sortscan.h"
 
 // ------------------------------------------------------------------------------------------------
 // A3: CSR graph
@@ -301,12 +300,7 @@ static int graph_build_transpose(sc_ctx *c, bool wait)
     if (nnz > 0)
         hipLaunchKernelGGL(k_col_count, dim3((unsigned)ceil_div64(nnz, 256)), dim3(256), 0, c->stream,
                            c->g_indices.as<int32_t>(), nnz, cur);
-    size_t tmp_bytes = 0;
-    SC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (long long *)cur, c->gt_indptr.as<long long>(),
-                                            (int)(n + 1), c->stream));
-    SC_TRY(c->gt_tmp.ensure(tmp_bytes, &c->mem));
-    SC_HIP(hipcub::DeviceScan::ExclusiveSum(c->gt_tmp.p, tmp_bytes, (long long *)cur, c->gt_indptr.as<long long>(),
-                                            (int)(n + 1), c->stream));
+    SC_TRY(sc_exclusive_sum(c, c->gt_tmp, c->stream, (long long *)cur, c->gt_indptr.as<long long>(), n + 1));
     SC_HIP(hipMemcpyAsync(cur, c->gt_indptr.p, sizeof(long long) * (size_t)(n + 1), hipMemcpyDeviceToDevice,
                           c->stream));
     hipLaunchKernelGGL(k_transpose_fill, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, c->stream,

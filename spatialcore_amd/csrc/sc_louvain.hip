@@ -38,10 +38,9 @@
 #include <algorithm>
 #include <vector>
 
-#include <hipcub/hipcub.hpp>
-
 #include "sc_csr_input.h"
-#include "sc_ctx.h"
+#include "sc_list_graph.h"
+#include "sc_sortscan.h"
 #include "sc_unionfind.h"
 
 namespace {
@@ -376,14 +375,8 @@ __global__ __launch_bounds__(256) void k_lv_keys(const int64_t *__restrict__ ind
         pay[p] = (uint32_t)p;
     }
 }
-__global__ __launch_bounds__(256) void k_lv_heads(const u64 *__restrict__ keys, int64_t nnz, long long *__restrict__ head)
-{
-    const int64_t p = (int64_t)blockIdx.x * LV_TPB + threadIdx.x;
-    if (p > nnz) return;
-    head[p] = p < nnz && (p == 0 || keys[p] != keys[p - 1]);
-}
-// seg = exclusive sums of head: entry p belongs to run seg[p] + head[p] - 1.  A thread adds LV_CHUNK consecutive entries
-// and touches memory when the run changes.  The first entry of a run writes its column; the first run of a row, and the
+// head = 1 at the first of every run of equal sorted keys (sc_sortscan.h: sc_run_heads), seg = exclusive sums of head: entry p
+// belongs to run seg[p] + head[p] - 1.  A thread adds LV_CHUNK consecutive entries and touches memory when the run changes.  The first entry of a run writes its column; the first run of a row, and the
 // last entry of all, write the row offsets.
 template <class W>
 __global__ __launch_bounds__(256) void k_lv_fill(const u64 *__restrict__ keys, const uint32_t *__restrict__ pay, const long long *__restrict__ head,
@@ -433,13 +426,6 @@ __global__ __launch_bounds__(256) void k_lv_symmetric(const int64_t *__restrict_
 
 inline unsigned lv_blocks(int64_t count) { return (unsigned)ceil_div64(count > 0 ? count : 1, LV_TPB); }
 
-int lv_bits_for(int64_t count)   // bits that hold 0 .. count - 1 (at least 1)
-{
-    int b = 1;
-    while (((int64_t)1 << b) < count) ++b;
-    return b;
-}
-
 }  // namespace
 
 struct LvGraph {
@@ -466,10 +452,7 @@ namespace {
 // offsets[0 .. cnt] = exclusive sums of counts[0 .. cnt] on the state's own scratch; *total = offsets[cnt] after the caller's wait
 int lv_scan(sc_ctx *c, LouvainState &s, long long *counts, long long *offsets, int64_t cnt, long long *total)
 {
-    size_t bytes = 0;
-    SC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, counts, offsets, (int)(cnt + 1), c->stream));
-    SC_TRY(s.tmp.ensure(bytes ? bytes : 1, &c->mem));
-    SC_HIP(hipcub::DeviceScan::ExclusiveSum(s.tmp.p, bytes, counts, offsets, (int)(cnt + 1), c->stream));
+    SC_TRY(sc_exclusive_sum(c, s.tmp, c->stream, counts, offsets, cnt + 1));
     SC_HIP(hipMemcpyAsync(total, offsets + cnt, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     return SC_OK;
 }
@@ -552,14 +535,9 @@ int lv_aggregate(sc_ctx *c, LouvainState &s, const LvGraph &G, LvGraph &H, int64
     SC_TRY(s.rank.ensure(sizeof(long long) * (cap + 1), &c->mem));
     hipLaunchKernelGGL(k_lv_keys, dim3(lv_blocks(G.n)), dim3(LV_TPB), 0, st, G.indptr.as<int64_t>(), G.indices.as<int32_t>(), s.label.as<int32_t>(), G.n,
                        s.keys.as<u64>(), s.pay.as<uint32_t>());
-    size_t bytes = 0;
-    const int end_bit = 32 + lv_bits_for(nc);
-    SC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, s.keys.as<u64>(), s.keys2.as<u64>(), s.pay.as<uint32_t>(), s.pay2.as<uint32_t>(),
-                                              (size_t)nnz, 0, end_bit, st));
-    SC_TRY(s.tmp.ensure(bytes ? bytes : 1, &c->mem));
-    SC_HIP(hipcub::DeviceRadixSort::SortPairs(s.tmp.p, bytes, s.keys.as<u64>(), s.keys2.as<u64>(), s.pay.as<uint32_t>(), s.pay2.as<uint32_t>(),
-                                              (size_t)nnz, 0, end_bit, st));
-    hipLaunchKernelGGL(k_lv_heads, dim3(lv_blocks(nnz + 1)), dim3(LV_TPB), 0, st, s.keys2.as<u64>(), nnz, s.flag.as<long long>());
+    SC_TRY(sc_sort_pairs(c, s.tmp, st, s.keys.as<u64>(), s.keys2.as<u64>(), s.pay.as<uint32_t>(), s.pay2.as<uint32_t>(), nnz,
+                         32 + sc_bits_for(nc)));
+    sc_run_heads(st, s.keys2.as<u64>(), nnz, s.flag.as<long long>());
     long long runs = 0;
     SC_TRY(lv_scan(c, s, s.flag.as<long long>(), s.rank.as<long long>(), nnz, &runs));
     SC_HIP(hipStreamSynchronize(st));
@@ -746,10 +724,11 @@ extern "C" int sc_louvain_resident_weights(sc_ctx *c, double *w_out, int64_t nnz
 {
     const char *who = "sc_louvain_resident_weights";
     SC_REQUIRE(c && w_out, SC_ERR_INVALID, "%s: null pointer", who);
-    SC_REQUIRE(c->df.graph_valid, SC_ERR_STATE, "%s: no graph is resident (sc_diffmap_graph)", who);
-    SC_REQUIRE(nnz == c->df.nnz, SC_ERR_INVALID, "%s: the resident graph stores %lld entries, not %lld", who, (long long)c->df.nnz, (long long)nnz);
+    const sc_ctx::ListGraph *f = nullptr;
+    SC_TRY(lg_resident(c, who, " (sc_diffmap_graph)", &f));
+    SC_REQUIRE(nnz == f->nnz, SC_ERR_INVALID, "%s: the resident graph stores %lld entries, not %lld", who, (long long)f->nnz, (long long)nnz);
     SC_HIP(hipSetDevice(c->device));
-    SC_HIP(hipMemcpyAsync(w_out, c->df.w.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, c->stream));
+    SC_HIP(hipMemcpyAsync(w_out, f->w.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, c->stream));
     SC_HIP(hipStreamSynchronize(c->stream));
     return SC_OK;
 }
@@ -758,8 +737,9 @@ extern "C" int sc_louvain_begin_resident(sc_ctx *c, const uint16_t *q, int64_t n
 {
     const char *who = "sc_louvain_begin_resident";
     SC_TRY(lv_check_common(who, c, g, max_rounds));
-    sc_ctx::Diffusion &f = c->df;
-    SC_REQUIRE(f.graph_valid, SC_ERR_STATE, "%s: no graph is resident (sc_diffmap_graph)", who);
+    const sc_ctx::ListGraph *resident = nullptr;
+    SC_TRY(lg_resident(c, who, " (sc_diffmap_graph)", &resident));
+    const sc_ctx::ListGraph &f = *resident;
     SC_REQUIRE(nnz == f.nnz, SC_ERR_INVALID, "%s: the resident graph stores %lld entries, not %lld", who, (long long)f.nnz, (long long)nnz);
     SC_REQUIRE(nnz <= INT32_MAX, SC_ERR_INVALID, "%s: need stored entries <= 2^31 - 1, got %lld", who, (long long)nnz);
     std::vector<uint16_t> ones;

@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "sc_dense_knn.h"
+#include "sc_list_graph.h"
 #include "sc_topk.h"
 
 // X[n][dp] <- the caller's rows widened to fp64, columns d .. dp - 1 zero
@@ -450,7 +451,7 @@ int dk_begin(sc_ctx *c, const void *X, int dtype, int64_t n, int d, int k)
     SC_HIP(hipSetDevice(c->device));
     sc_ctx::DenseKnn &f = c->knn;
     hipStream_t s = c->stream;
-    f.valid = c->df.graph_valid = c->df.lanczos_valid = false;
+    lg_invalidate(c, true);
     const int dp = (int)align_up64(d, 8);
     const size_t es = dtype == SC_F32 ? sizeof(float) : sizeof(double);
     SC_TRY(f.raw.ensure(es * (size_t)(n * d), &c->mem));

@@ -19,7 +19,7 @@
 
 #include <vector>
 
-#include "sc_ctx.h"
+#include "sc_sortscan.h"
 
 #define RS_PIECE 256                         // ranked cells of one group per workgroup of the count / scatter walk
 #define RS_CHUNK 2048                        // sorted pairs per workgroup of k_rs_runs: 256 threads x 8
@@ -334,25 +334,6 @@ __global__ __launch_bounds__(256) void k_rs_final(const double *__restrict__ psu
 // host
 // ------------------------------------------------------------------------------------------------
 
-template <class K, class V>
-int rs_sort(sc_ctx *c, const K *k_in, K *k_out, const V *v_in, V *v_out, int64_t cnt, int end_bit)
-{
-    size_t tmp = 0;
-    SC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, k_in, k_out, v_in, v_out, (size_t)cnt, 0, end_bit, c->stream));
-    SC_TRY(c->rs_tmp.ensure(tmp, &c->mem));
-    SC_HIP(hipcub::DeviceRadixSort::SortPairs(c->rs_tmp.p, tmp, k_in, k_out, v_in, v_out, (size_t)cnt, 0, end_bit, c->stream));
-    return SC_OK;
-}
-
-template int rs_sort<u64, uint32_t>(sc_ctx *, const u64 *, u64 *, const uint32_t *, uint32_t *, int64_t, int);   // also sc_threshold.hip's
-
-static int bits_for(int64_t count)   // bits that hold 0 .. count - 1 (at least 1)
-{
-    int b = 1;
-    while (((int64_t)1 << b) < count) ++b;
-    return b;
-}
-
 extern "C" int sc_ranksum(sc_ctx *c, const int32_t *group_code, int64_t n, int32_t n_groups, int64_t *rank2_out,
                           uint64_t *tie_out, int64_t *nnz_out, double *sum_out, int64_t *n_neg_out, int64_t *group_n_out)
 {
@@ -440,12 +421,7 @@ extern "C" int sc_ranksum(sc_ctx *c, const int32_t *group_code, int64_t n, int32
                            c->rs_order.as<int32_t>(), c->rs_pstart.as<int64_t>(), P, c->rs_psum.as<double>(),
                            c->rs_pnnz.as<long long>(), c->rs_neg.as<u64>(), c->rs_flag.as<uint32_t>());
         SC_HIP(hipGetLastError());
-        size_t tmp = 0;
-        SC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, c->rs_pnnz.as<long long>(), c->rs_poff.as<long long>(),
-                                                gp_entries + 1, c->stream));
-        SC_TRY(c->rs_tmp.ensure(tmp, &c->mem));
-        SC_HIP(hipcub::DeviceScan::ExclusiveSum(c->rs_tmp.p, tmp, c->rs_pnnz.as<long long>(), c->rs_poff.as<long long>(),
-                                                gp_entries + 1, c->stream));
+        SC_TRY(sc_exclusive_sum(c, c->rs_tmp, c->stream, c->rs_pnnz.as<long long>(), c->rs_poff.as<long long>(), (int64_t)gp_entries + 1));
         hipLaunchKernelGGL(k_rs_gene_offsets, dim3((unsigned)ceil_div64(Gp + 1, 256)), dim3(256), 0, c->stream,
                            c->rs_poff.as<long long>(), P, Gp, c->rs_goff.as<long long>());
         SC_HIP(hipGetLastError());
@@ -490,8 +466,8 @@ extern "C" int sc_ranksum(sc_ctx *c, const int32_t *group_code, int64_t n, int32
         const u64 *keys = nullptr;
         if (k32) {
             KernelTimerScope ts(c, SC_K_RANK_SORT);
-            SC_TRY(rs_sort(c, c->rs_keys.as<u64>(), c->rs_keys2.as<u64>(), c->rs_pay.as<uint16_t>(), c->rs_pay2.as<uint16_t>(),
-                           cnt, 32 + bits_for(genes_here)));
+            SC_TRY(sc_sort_pairs(c, c->rs_tmp, c->stream, c->rs_keys.as<u64>(), c->rs_keys2.as<u64>(), c->rs_pay.as<uint16_t>(),
+                                 c->rs_pay2.as<uint16_t>(), cnt, 32 + sc_bits_for(genes_here)));
             keys = c->rs_keys2.as<u64>();
         } else {
             KernelTimerScope ts(c, SC_K_RANK_SORT);
@@ -499,13 +475,13 @@ extern "C" int sc_ranksum(sc_ctx *c, const int32_t *group_code, int64_t n, int32
             SC_TRY(c->rs_gkey2.ensure(sizeof(uint32_t) * (size_t)cnt, &c->mem));
             SC_TRY(c->rs_idx.ensure(sizeof(uint32_t) * (size_t)cnt, &c->mem));
             SC_TRY(c->rs_idx2.ensure(sizeof(uint32_t) * (size_t)cnt, &c->mem));
-            SC_TRY(rs_sort(c, c->rs_keys.as<u64>(), c->rs_keys2.as<u64>(), c->rs_pay.as<uint32_t>(), c->rs_pay2.as<uint32_t>(),
-                           cnt, 64));
+            SC_TRY(sc_sort_pairs(c, c->rs_tmp, c->stream, c->rs_keys.as<u64>(), c->rs_keys2.as<u64>(), c->rs_pay.as<uint32_t>(),
+                                 c->rs_pay2.as<uint32_t>(), cnt, 64));
             hipLaunchKernelGGL(k_rs_gene_keys, dim3(flat), dim3(256), 0, c->stream, c->rs_pay2.as<uint32_t>(), cnt,
                                c->rs_gkey.as<uint32_t>(), c->rs_idx.as<uint32_t>());
             SC_HIP(hipGetLastError());
-            SC_TRY(rs_sort(c, c->rs_gkey.as<uint32_t>(), c->rs_gkey2.as<uint32_t>(), c->rs_idx.as<uint32_t>(),
-                           c->rs_idx2.as<uint32_t>(), cnt, bits_for(genes_here)));
+            SC_TRY(sc_sort_pairs(c, c->rs_tmp, c->stream, c->rs_gkey.as<uint32_t>(), c->rs_gkey2.as<uint32_t>(), c->rs_idx.as<uint32_t>(),
+                                 c->rs_idx2.as<uint32_t>(), cnt, sc_bits_for(genes_here)));
             hipLaunchKernelGGL(k_rs_gather, dim3(flat), dim3(256), 0, c->stream, c->rs_keys2.as<u64>(), c->rs_pay2.as<uint32_t>(),
                                c->rs_idx2.as<uint32_t>(), cnt, c->rs_keys.as<u64>(), c->rs_pay.as<uint32_t>());
             SC_HIP(hipGetLastError());

@@ -11,10 +11,10 @@
 #include <float.h>
 #include <math.h>
 
-#include <hipcub/hipcub.hpp>
 #include <vector>
 
 #include "sc_search.h"
+#include "sc_sortscan.h"
 #include "sc_topk.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -107,16 +107,8 @@ int sc_bin_points(sc_ctx *c, const double *xy, int64_t n, double target_per_bin,
                        c->px.as<double>(), c->py.as<double>(), n);
     hipLaunchKernelGGL(k_bin_keys, dim3(grid), dim3(256), 0, c->stream, c->px.as<double>(), c->py.as<double>(), n,
                        xmin, ymin, 1.0 / h, nbx, nby, c->bin_keys.as<uint32_t>(), c->sid2.as<int32_t>());
-    int bits = 1;
-    while (((int64_t)1 << bits) < nbins) ++bits;
-    size_t tmp_bytes = 0;
-    SC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, c->bin_keys.as<uint32_t>(),
-                                              c->bin_keys2.as<uint32_t>(), c->sid2.as<int32_t>(),
-                                              c->sid.as<int32_t>(), (int)n, 0, bits, c->stream));
-    SC_TRY(c->cub_tmp.ensure(tmp_bytes, &c->mem));
-    SC_HIP(hipcub::DeviceRadixSort::SortPairs(c->cub_tmp.p, tmp_bytes, c->bin_keys.as<uint32_t>(),
-                                              c->bin_keys2.as<uint32_t>(), c->sid2.as<int32_t>(),
-                                              c->sid.as<int32_t>(), (int)n, 0, bits, c->stream));
+    SC_TRY(sc_sort_pairs(c, c->cub_tmp, c->stream, c->bin_keys.as<uint32_t>(), c->bin_keys2.as<uint32_t>(), c->sid2.as<int32_t>(),
+                         c->sid.as<int32_t>(), n, sc_bits_for(nbins)));
     hipLaunchKernelGGL(k_gather_sorted, dim3(grid), dim3(256), 0, c->stream, c->px.as<double>(), c->py.as<double>(),
                        c->sid.as<int32_t>(), n, c->sx.as<double>(), c->sy.as<double>());
     hipLaunchKernelGGL(k_bin_start, dim3((unsigned)ceil_div64(n + 1, 256)), dim3(256), 0, c->stream,
@@ -140,10 +132,7 @@ int sc_window_rings(const sc_ctx *c, double radius)
 
 int sc_counts_to_offsets(sc_ctx *c, long long *counts, long long *offsets, int64_t n, long long *total)
 {
-    size_t tmp_bytes = 0;
-    SC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, counts, offsets, (int)(n + 1), c->stream));
-    SC_TRY(c->cub_tmp.ensure(tmp_bytes, &c->mem));
-    SC_HIP(hipcub::DeviceScan::ExclusiveSum(c->cub_tmp.p, tmp_bytes, counts, offsets, (int)(n + 1), c->stream));
+    SC_TRY(sc_exclusive_sum(c, c->cub_tmp, c->stream, counts, offsets, n + 1));
     SC_HIP(hipMemcpyAsync(total, offsets + n, sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     return SC_OK;
 }

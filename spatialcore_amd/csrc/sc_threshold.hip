@@ -17,7 +17,7 @@
 #include <cmath>
 #include <vector>
 
-#include "sc_ctx.h"
+#include "sc_sortscan.h"
 
 namespace {
 
@@ -628,7 +628,7 @@ extern "C" int sc_ks_prepare(sc_ctx *c, const void *scores, int dtype, int64_t n
         KernelTimerScope ts(c, SC_K_THRESH_SORT);
         if (dtype == SC_F32) hipLaunchKernelGGL(k_ks_keys<float>, flat, tpb, 0, s, m[X].as<float>(), n, m[K1].as<u64>(), m[I1].as<uint32_t>());
         else hipLaunchKernelGGL(k_ks_keys<double>, flat, tpb, 0, s, m[X].as<double>(), n, m[K1].as<u64>(), m[I1].as<uint32_t>());
-        SC_TRY((rs_sort<u64, uint32_t>(c, m[K1].as<u64>(), m[K2].as<u64>(), m[I1].as<uint32_t>(), m[I2].as<uint32_t>(), n, 64)));
+        SC_TRY(sc_sort_pairs(c, c->rs_tmp, s, m[K1].as<u64>(), m[K2].as<u64>(), m[I1].as<uint32_t>(), m[I2].as<uint32_t>(), n, 64));
         hipLaunchKernelGGL(k_ks_unkey, flat, tpb, 0, s, m[K2].as<u64>(), n, sorted);
         // background moments: the mean, then the squared deviations around it (two passes, as numpy's std)
         hipLaunchKernelGGL(k_th_sum, dim3((unsigned)NB), tpb, 0, s, sorted, m_bg, 0, 0.0, m[PART].as<double>());

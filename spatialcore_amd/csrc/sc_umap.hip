@@ -5,16 +5,16 @@
 //
 // fp64 throughout, -ffp-contract=off, no floating-point atomics.  ONE order per sum:
 //  - a row's distance sum and a row's membership sum: the k list entries in list order, a running sum from 0;
-//  - the sum of all distances: the n row sums in the chunked order of sc_diffusion.hip's dot products (chunks of 1024
-//    rows, element e = r * 64 + lane, 16 values per lane for r ascending, the adjacent-pair tree, chunk sums in chunk order);
+//  - the sum of all distances: the n row sums in the chunked order of sc_chunk_sum.h, the chunk sums added in chunk order;
 //  - a squared distance of the layout: the C coordinates in order, from the first product;
 //  - a vertex's position: its stored entries in CSR order, per firing entry the attraction, then the negatives q ascending.
 // The layout reads the positions of the previous epoch only, so no result depends on the grid or on the hardware queues.
 #include <cmath>
 #include <vector>
 
+#include "sc_chunk_sum.h"
 #include "sc_csr_input.h"
-#include "sc_dense_knn.h"
+#include "sc_list_graph.h"
 #include "sc_philox.h"
 #include "sc_umap.h"
 
@@ -22,7 +22,6 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr int UM_CHUNK = 1024;     // rows per partial of the distance sum (DF_CHUNK's order)
 constexpr int UM_ITERS = 64;       // umap's bisection limit
 constexpr int UM_NEG_MAX = 16;
 
@@ -43,13 +42,13 @@ __global__ __launch_bounds__(256) void k_um_rho(const double *__restrict__ d2, i
     rho[i] = lo;
     dsum[i] = s;
 }
-// part[chunk] = the chunk's share of sum_i v_i: one wavefront per chunk, in the order of k_df_dots
+// part[chunk] = the chunk's share of sum_i v_i: one wavefront per chunk, in the order of sc_chunk_sum.h
 __global__ __launch_bounds__(64) void k_um_chunk_sum(const double *__restrict__ v, int64_t n, double *__restrict__ part)
 {
     const int lane = threadIdx.x;
-    const int64_t e0 = (int64_t)blockIdx.x * UM_CHUNK + lane;
+    const int64_t e0 = (int64_t)blockIdx.x * SUM_CHUNK + lane;
     double s = e0 < n ? v[e0] : 0.0;
-    for (int r = 1; r < UM_CHUNK / 64; ++r) {
+    for (int r = 1; r < SUM_CHUNK / 64; ++r) {
         const int64_t e = e0 + r * 64;
         s = s + (e < n ? v[e] : 0.0);
     }
@@ -222,14 +221,15 @@ __global__ __launch_bounds__(256) void k_um_epoch(const int64_t *__restrict__ in
 extern "C" int sc_fuzzy_graph(sc_ctx *c, double *rho_out, double *sigma_out, int64_t *n_edges_out, int64_t *n_components_out)
 {
     SC_REQUIRE(c && n_edges_out && n_components_out, SC_ERR_INVALID, "sc_fuzzy_graph: null pointer");
-    sc_ctx::Diffusion &f = c->df;
+    sc_ctx::UmapWork &f = c->um;
+    sc_ctx::ListGraph &g = c->lg;
     const sc_ctx::DenseKnn &kn = c->knn;
     SC_REQUIRE(kn.valid, SC_ERR_STATE, "sc_fuzzy_graph: no neighbour lists are resident (call sc_knn_dense first)");
     SC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    const int64_t n = kn.n, nk = n * kn.k, chunks = ceil_div64(n, UM_CHUNK);
+    const int64_t n = kn.n, nk = n * kn.k, chunks = ceil_div64(n, SUM_CHUNK);
     const int k = kn.k;
-    f.graph_valid = f.lanczos_valid = false;
+    lg_invalidate(c, false);
     SC_TRY(f.rho.ensure(sizeof(double) * (size_t)n, &c->mem));
     SC_TRY(f.sigma.ensure(sizeof(double) * (size_t)n, &c->mem));
     SC_TRY(f.dsum.ensure(sizeof(double) * (size_t)(n + chunks + 1), &c->mem));
@@ -251,18 +251,18 @@ extern "C" int sc_fuzzy_graph(sc_ctx *c, double *rho_out, double *sigma_out, int
         else
             hipLaunchKernelGGL(k_um_sigma<32>, rows, tpb, 0, s, kn.d2.as<double>(), n, k, target, f.rho.as<double>(), dsum, mean,
                                f.sigma.as<double>());
-        SC_TRY(df_build_union(c, &nnz));
+        SC_TRY(lg_build_union(c, &nnz));
     }
     SC_HIP(hipGetLastError());
     SC_REQUIRE(nnz >= nk && nnz <= 2 * nk, SC_ERR_HIP, "sc_fuzzy_graph: edge count %lld out of range", nnz);
-    f.nnz = nnz;
-    SC_TRY(f.w.ensure(sizeof(double) * (size_t)nnz, &c->mem));
+    g.nnz = nnz;
+    SC_TRY(g.w.ensure(sizeof(double) * (size_t)nnz, &c->mem));
     {
         KernelTimerScope ts(c, SC_K_UMAP_GRAPH);
-        hipLaunchKernelGGL(k_um_weights, dim3((unsigned)ceil_div64(nnz, 256)), tpb, 0, s, f.indptr.as<int64_t>(), f.indices.as<int32_t>(), n,
+        hipLaunchKernelGGL(k_um_weights, dim3((unsigned)ceil_div64(nnz, 256)), tpb, 0, s, g.indptr.as<int64_t>(), g.indices.as<int32_t>(), n,
                            (int64_t)nnz, kn.idx.as<int32_t>(), kn.d2.as<double>(), k, f.rho.as<double>(), f.sigma.as<double>(),
-                           f.w.as<double>());
-        SC_TRY(df_finish_graph(c, n_components_out));
+                           g.w.as<double>());
+        SC_TRY(lg_finish(c, n_components_out));
     }
     if (rho_out) SC_HIP(hipMemcpyAsync(rho_out, f.rho.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
     if (sigma_out) SC_HIP(hipMemcpyAsync(sigma_out, f.sigma.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
@@ -290,7 +290,8 @@ extern "C" int sc_umap_layout(sc_ctx *c, const int64_t *indptr, const int32_t *i
                "sc_umap_layout: the epoch range [%d, %d) must lie inside [0, %d)", e0, e1, n_epochs);
     for (int64_t p = 0; p < n * C; ++p)
         SC_REQUIRE(std::isfinite(Y[p]), SC_ERR_INVALID, "sc_umap_layout: position value %lld is not finite", (long long)p);
-    sc_ctx::Diffusion &f = c->df;
+    sc_ctx::UmapWork &f = c->um;
+    const sc_ctx::ListGraph *g = nullptr;
     int64_t nnz = 0;
     if (indptr) {
         SC_REQUIRE(indptr[0] == 0, SC_ERR_INVALID, "sc_umap_layout: indptr[0] must be 0");
@@ -302,10 +303,10 @@ extern "C" int sc_umap_layout(sc_ctx *c, const int64_t *indptr, const int32_t *i
             return SC_OK;
         }));
     } else {
-        SC_REQUIRE(f.graph_valid, SC_ERR_STATE, "sc_umap_layout: no graph is resident (call sc_fuzzy_graph or sc_diffmap_graph first)");
-        SC_REQUIRE(n == f.n, SC_ERR_INVALID, "sc_umap_layout: the resident graph has %lld vertices, got n=%lld", (long long)f.n,
+        SC_TRY(lg_resident(c, "sc_umap_layout", " (call sc_fuzzy_graph or sc_diffmap_graph first)", &g));
+        SC_REQUIRE(n == g->n, SC_ERR_INVALID, "sc_umap_layout: the resident graph has %lld vertices, got n=%lld", (long long)g->n,
                    (long long)n);
-        nnz = f.nnz;
+        nnz = g->nnz;
     }
     SC_HIP(hipSetDevice(c->device));
     hipStream_t s = c->stream;
@@ -313,9 +314,9 @@ extern "C" int sc_umap_layout(sc_ctx *c, const int64_t *indptr, const int32_t *i
     SC_TRY(f.ly0.ensure(ybytes, &c->mem));
     SC_TRY(f.ly1.ensure(ybytes, &c->mem));
     SC_TRY(f.lmax.ensure(sizeof(u64), &c->mem));
-    const int64_t *d_indptr = f.indptr.as<int64_t>();
-    const int32_t *d_indices = f.indices.as<int32_t>();
-    const double *d_w = f.w.as<double>();
+    const int64_t *d_indptr = nullptr;
+    const int32_t *d_indices = nullptr;
+    const double *d_w = nullptr;
     if (indptr) {
         SC_TRY(f.lip.ensure(sizeof(int64_t) * (size_t)(n + 1), &c->mem));
         SC_TRY(f.lix.ensure(sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1), &c->mem));
@@ -328,6 +329,10 @@ extern "C" int sc_umap_layout(sc_ctx *c, const int64_t *indptr, const int32_t *i
         d_indptr = f.lip.as<int64_t>();
         d_indices = f.lix.as<int32_t>();
         d_w = f.lw.as<double>();
+    } else {
+        d_indptr = g->indptr.as<int64_t>();
+        d_indices = g->indices.as<int32_t>();
+        d_w = g->w.as<double>();
     }
     SC_HIP(hipMemcpyAsync(f.ly0.p, Y, ybytes, hipMemcpyHostToDevice, s));
     SC_HIP(hipMemsetAsync(f.lmax.p, 0, sizeof(u64), s));

@@ -99,17 +99,17 @@ int main()
 
     // the checks behind the state checks, on a context that claims a graph and an open run of 4 steps over 40 cells
     // (claims only: each of these calls is refused before it would touch the device)
-    ctx.df.n = n;
-    ctx.df.graph_valid = true;
+    ctx.lg.n = n;
+    ctx.lg.valid = true;
     expect("begin max_basis = 0", sc_lanczos_begin(c, start.data(), 0), SC_ERR_INVALID, "1 <= max_basis <= n");
     expect("begin max_basis > n", sc_lanczos_begin(c, start.data(), n + 1), SC_ERR_INVALID, "1 <= max_basis <= n");
     start[(size_t)n - 1] = INFINITY;
     expect("begin inf", sc_lanczos_begin(c, start.data(), 4), SC_ERR_INVALID, "start value 39");
     std::fill(start.begin(), start.end(), 0.0);
     expect("begin zero", sc_lanczos_begin(c, start.data(), 4), SC_ERR_INVALID, "all zero");
-    ctx.df.lanczos_valid = true;
-    ctx.df.m = 4;
-    ctx.df.max_basis = 4;
+    ctx.lz.valid = true;
+    ctx.lz.m = 4;
+    ctx.lz.max_basis = 4;
     expect("run negative", sc_lanczos_run(c, -1, alpha.data(), beta.data(), &m), SC_ERR_INVALID, "exceed the basis");
     expect("run past the basis", sc_lanczos_run(c, 1, alpha.data(), beta.data(), &m), SC_ERR_INVALID, "exceed the basis");
     expect("ritz m = 0", sc_lanczos_ritz(c, S.data(), 0, 2, lam.data(), vecs.data(), res.data()), SC_ERR_INVALID, "1 <= m <= 4");

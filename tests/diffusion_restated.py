@@ -10,7 +10,7 @@ import numpy as np
 from scipy import sparse
 from scipy.linalg import eigh_tridiagonal
 
-CHUNK = 1024            # DF_CHUNK: cells per partial of a dot product
+CHUNK = 1024            # SUM_CHUNK (sc_chunk_sum.h): cells per partial of a dot product
 LANES = 64
 QUERY_BLOCK = 256       # DF_QB: queries per workgroup of the register form (padded d <= 32)
 TILE = 128              # DF_TILE: candidates per LDS tile of the register form

@@ -93,7 +93,7 @@ int main()
     expect("fuzzy: null ctx", sc_fuzzy_graph(nullptr, nullptr, nullptr, &ne, &nc), SC_ERR_INVALID, "null pointer");
     expect("fuzzy: null counts", sc_fuzzy_graph(c, nullptr, nullptr, nullptr, &nc), SC_ERR_INVALID, "null pointer");
     expect("fuzzy: no lists", sc_fuzzy_graph(c, nullptr, nullptr, &ne, &nc), SC_ERR_STATE, "no neighbour lists are resident");
-    if (ne != -1 || nc != -1 || ctx.df.graph_valid) {
+    if (ne != -1 || nc != -1 || ctx.lg.valid) {
         ++failures;
         printf("FAIL a refused sc_fuzzy_graph wrote its counts or claimed a resident graph\n");
     }
