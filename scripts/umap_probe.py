@@ -7,7 +7,8 @@ interaction rate against the two bounds that apply.  As a CPU figure the numpy r
 at 50,000 cells on the same host, on the lists the device found, and scaled linearly; umap-learn is not installed.
 
 `--tolerances` measures instead the largest difference between the device and the restatement over every input of
-tests/test_gpu_umap.py: the figures that file's assertions are ten times of.
+tests/test_gpu_umap.py ("tolerances") and of tests/test_gpu_umap_edges.py ("tolerances_edges"): the figures those files'
+assertions are ten times of.
 
 Every GPU step is a child process under its own time limit; a step that fails or runs out of time ends the probe.  Writes
 profiles/umap_1m.json (or the path given last); the two modes fill two sections of the same file.
@@ -94,6 +95,47 @@ def step_tolerances():
         out["cases"][name] = {"layout_of_extent_10": worst}
         out["layout_of_extent_10"] = max(out["layout_of_extent_10"], worst)
         say(name, worst)
+    return out
+
+
+def step_tolerances_edges():
+    """The same over ``fuzzy_edge_recipes`` and ``layout_edge_recipes`` (tests/test_gpu_umap_edges.py): sigma over the
+    rows with rho > 0 (the others are compared by bytes), the positions over every case's own extent and epochs."""
+    from spatialcore_amd import _lib
+
+    R, U = restated()
+    ctx = _lib.default_context(0)
+    normal = 1e-300
+    out = {"sigma": 0.0, "w": 0.0, "layout_of_extent": 0.0, "set_by": {}, "cases": {}}
+
+    def rel(got, ref):
+        big = ref >= normal
+        return float(np.max(np.abs(got[big] - ref[big]) / ref[big])) if big.any() else 0.0
+
+    def record(name, rec):
+        out["cases"][name] = rec
+        for key in ("sigma", "w", "layout_of_extent"):
+            if rec.get(key, 0.0) > out[key]:
+                out[key], out["set_by"][key] = rec[key], name
+        say(name, rec)
+
+    for name, (X, k) in U.fuzzy_edge_recipes().items():
+        idx, d2 = R.knn(X, k)
+        g = U.fuzzy_graph(idx, d2)
+        ctx.knn_dense(X, k, fetch=False)
+        info = ctx.fuzzy_graph()
+        _, _, w = ctx.diffmap_graph_get()
+        zero = g["rho"] == 0
+        record(name, {"sigma": rel(info["sigma"][~zero], g["sigma"][~zero]), "w": rel(w, g["w"]),
+                      "rho_equal": bool(np.array_equal(info["rho"], g["rho"])), "rows_with_rho_0": int(zero.sum()),
+                      "their_sigma_equal": bool(info["sigma"][zero].tobytes() == g["sigma"][zero].tobytes())})
+    for name, case in U.layout_edge_recipes().items():
+        run, worst = case["run"], 0.0
+        for e1, ref in U.layout_case_epochs(case):
+            got = ctx.umap_layout(case["graph"], case["Y0"], run["a"], run["b"], run["gamma"], 1.0, run["neg"], run["n_epochs"],
+                                  run["seed"], run["e0"], e1)
+            worst = max(worst, float(np.max(np.abs(got - ref))) / case["extent"])
+        record(name, {"layout_of_extent": worst, "extent": case["extent"]})
     return out
 
 
@@ -227,6 +269,10 @@ def main():
         out["tolerances"]["note"] = ("largest differences between the device and tests/umap_restated.py over the inputs of "
                                      "tests/test_gpu_umap.py; relative for sigma and w, |dY| / 10 for three epochs of the layout")
         write(out, out_path)
+        out["tolerances_edges"] = child(300, "tolerances-edges")
+        out["tolerances_edges"]["note"] = ("the same over the inputs of tests/test_gpu_umap_edges.py; sigma over the rows with rho > 0, "
+                                           "|dY| over every case's extent and epochs")
+        write(out, out_path)
         return
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
     G = int(sys.argv[2]) if len(sys.argv) > 2 else 500
@@ -254,6 +300,8 @@ if __name__ == "__main__":
         a = sys.argv[3:]
         if sys.argv[2] == "tolerances":
             rec = step_tolerances()
+        elif sys.argv[2] == "tolerances-edges":
+            rec = step_tolerances_edges()
         elif sys.argv[2] == "pipeline":
             rec = step_pipeline(int(a[0]), int(a[1]))
         else:

@@ -1,5 +1,5 @@
-"""Host side of spatialcore_amd.embedding.umap and neighbors(method="umap"): the recipes of tests/test_gpu_umap.py have the
-properties those tests rely on (counted by the numpy restatement, tests/umap_restated.py), the curve fit gives scanpy's
+"""Host side of spatialcore_amd.embedding.umap and neighbors(method="umap"): the recipes of tests/test_gpu_umap.py and
+tests/test_gpu_umap_edges.py have the properties those tests rely on (counted by the numpy restatement, tests/umap_restated.py), the curve fit gives scanpy's
 published a and b, every bad argument is refused before a device is touched, and the restated fuzzy graph is a fuzzy graph."""
 import functools
 
@@ -108,6 +108,154 @@ def test_negatives_are_philox_words_scaled_to_n(oracle):
         for p, tt in enumerate(t):
             o = oracle.philox4x32_10(np.array([int(tt) & 0xFFFFFFFF, int(tt) >> 32, e, q >> 2], dtype=np.uint32), (4, 9))
             assert got[p] == (int(o[q & 3]) * n) >> 32
+
+
+# ---- the recipes at the kernels' constants (tests/test_gpu_umap_edges.py) -----------------------------------------------
+@pytest.mark.parametrize("n, k", U.MIXED_CASES)
+def test_mixed_recipes_floor_the_copies_at_a_global_mean_that_sees_the_order(n, k):
+    """k + 2 identical cells among ordinary ones: the only rows with rho = 0, floored at 1e-3 of a global mean that is not
+    zero and whose chunked order (sc_chunk_sum.h) gives other bits than the rows added one after another."""
+    X, copies = U.mixed(n, k)
+    assert X.shape == (n, 8) and copies.size == k + 2 and np.all(X[copies] == X[0])
+    idx, d2 = R.knn(X, k)
+    rho, sigma, info = U.smooth_knn(d2)
+    assert -(-n // R.CHUNK) == {1023: 1, 1024: 1, 1025: 2, 2049: 3}[n]           # the partial sums k_um_mean adds
+    zero = np.flatnonzero(rho == 0)
+    assert zero.size == k + 2 and np.array_equal(zero, copies)
+    assert np.all(d2[copies] == 0)
+    mean = info["global_mean"]
+    print(f"mixed({n}, {k}): global mean {mean!r}, plain order {U.plain_mean(info['row_sums'], k)!r}")
+    assert mean > 0 and 6.5 < mean < 8.6
+    assert sigma[copies].tobytes() == np.full(k + 2, 1e-3 * mean).tobytes()
+    assert U.plain_mean(info["row_sums"], k) != mean                              # what makes the case see the order
+    # The cells whose nearest cell is the copied one list k copies at one distance d > 0: rho = d, every t = 0, psum = k >
+    # log2(k + 1), the row-mean floor.  They and the copies are the floored rows; every other row converges unfloored.
+    tied = np.flatnonzero((d2[:, 0] > 0) & (d2[:, 0] == d2[:, -1]))
+    assert 1 <= tied.size <= 4 and np.all(np.isin(idx[tied], copies))
+    assert np.array_equal(np.flatnonzero(info["floored"]), np.union1d(copies, tied))
+    assert np.array_equal(np.flatnonzero(info["floored"] & (rho == 0)), copies)   # the global-mean floor: the copies alone
+    assert np.array_equal(np.flatnonzero(~info["converged"]), np.union1d(copies, tied))
+    assert np.array_equal(sigma[tied], 1e-3 * (info["row_sums"][tied] / float(k + 1)))
+    assert n - copies.size - tied.size >= 1000                                    # ordinary rows through k_um_sigma<K>
+
+
+@pytest.mark.parametrize("k", U.WIDTH_KS)
+def test_width_recipes_converge_unfloored(k):
+    assert {8, 9, 17, 31} < set(U.WIDTH_KS) and min(U.WIDTH_KS) == 2              # sc_knn_dense refuses k = 1
+    _, d2 = R.knn(U.features(129, 8), k)
+    info = U.smooth_knn(d2)[2]
+    assert info["converged"].all() and not info["floored"].any()
+    assert set(U.fuzzy_edge_recipes()) == {f"mixed-n{n}-k{kk}" for n, kk in U.MIXED_CASES} | {f"width-k{kk}" for kk in U.WIDTH_KS}
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_cases():
+    return U.layout_edge_recipes()
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_run(name):
+    """(restated positions after the case's last epoch, its statistics)"""
+    stats = U.new_stats()
+    return U.layout_case_epochs(_edge_cases()[name], stats=stats)[-1][1], stats
+
+
+def test_edge_layout_recipes_are_the_listed_cases():
+    cases = _edge_cases()
+    assert set(cases) == ({f"neg{q}-C2" for q in (1, 3, 4, 8, 9, 16)} | {"neg4-C3", "neg16-C3", "seed-high-word", "ring-wmax-tail",
+                          "star-empty-rows", "gamma0", "gamma0-neg0", "a1.5-b0.9", "late-epochs"})
+    for name, case in cases.items():
+        run = case["run"]
+        assert case["Y0"].shape[1] == (3 if name.endswith("C3") else 2)
+        assert (run["n_epochs"], run["e0"], run["e1"]) == {"ring-wmax-tail": (4, 0, 2), "late-epochs": (
+            2 ** 31 - 1, 10 ** 9, 10 ** 9 + 3)}.get(name, (10, 0, 3))
+        assert case["extent"] == (100.0 if name == "ring-wmax-tail" else 10.0)
+        assert np.abs(case["Y0"]).max() <= case["extent"]
+
+
+@pytest.mark.parametrize("name", [f"neg{q}-C2" for q in (1, 3, 4, 8, 9, 16)] + ["neg4-C3", "neg16-C3"])
+def test_sample_block_recipes_skip_and_clip(name):
+    case = _edge_cases()[name]
+    neg = case["run"]["neg"]
+    assert neg == int(name[3:].split("-")[0]) and case["run"]["seed"] == 11
+    _, stats = _edge_run(name)
+    print(name, stats)
+    assert stats["skipped"] >= 1 and stats["clipped"] >= 1 and stats["coincident"] == 0
+
+
+def test_high_seed_word_changes_the_restated_layout():
+    graph, Y0, neg = U.layout_recipes()["n257-C2"]
+    case = _edge_cases()["seed-high-word"]
+    assert case["run"]["seed"] >> 32 == 5 and case["run"]["seed"] & 0xFFFFFFFF == 11 and case["run"]["neg"] == neg
+    assert case["Y0"].tobytes() == Y0.tobytes()
+    low = U.layout(*graph, Y0, 10, 0, 3, neg=neg, seed=11)
+    assert not np.array_equal(_edge_run("seed-high-word")[0], low)
+
+
+def test_ring_holds_its_largest_weight_past_the_strided_grid():
+    (indptr, indices, w), top = U.ring()
+    assert indptr[-1] == w.size == 560_000 and top.tolist() == [559_971, 559_999]
+    assert np.all(top >= U.WMAX_GRID) and U.WMAX_GRID == 524_288
+    rows = np.repeat(np.arange(20000), 28)
+    assert sorted(zip(rows[top].tolist(), indices[top].tolist())) == [(19998, 19999), (19999, 19998)]
+    assert np.all(np.diff(indices.reshape(20000, 28), axis=1) > 0)                       # canonical
+    A = sparse.csr_matrix((w, indices, indptr), shape=(20000, 20000))
+    At = A.T.tocsr()
+    At.sort_indices()
+    assert np.array_equal(At.indices, indices) and At.data.tobytes() == w.tobytes()       # symmetric
+    head = float(w[:U.WMAX_GRID].max())
+    assert head <= 0.55 < w[U.WMAX_GRID:].max() == w.max() == 1.0 and w.min() >= 0.05
+    case = _edge_cases()["ring-wmax-tail"]
+    assert case["run"]["neg"] == 5 and case["graph"][2].tobytes() == w.tobytes()
+    true, stats = _edge_run("ring-wmax-tail")
+    assert stats["firings"] > 50_000
+    wrong = U.layout_case_epochs(case, w_max=head)[-1][1]                                # w_max of the unstrided part only
+    assert np.all(np.abs(wrong - true).max(axis=1) > 1e-6)                               # moves every vertex
+
+
+def test_empty_rows_keep_their_start_in_the_restatement():
+    case = _edge_cases()["star-empty-rows"]
+    indptr, indices, w = case["graph"]
+    deg = np.diff(indptr)
+    assert deg.size == 302 and np.flatnonzero(deg == 0).tolist() == [0, 301] and deg[1] == 299
+    assert indices.min() == 1 and indices.max() == 300 and w.tobytes() == U.star(300)[2].tobytes()
+    out, _ = _edge_run("star-empty-rows")
+    assert out[[0, 301]].tobytes() == case["Y0"][[0, 301]].tobytes()
+    moved = np.any(out[1:301] != case["Y0"][1:301], axis=1)            # a row whose weights are small fires in no early epoch
+    assert moved[0] and moved.sum() >= 200
+
+
+def test_gamma_zero_is_the_run_without_negatives_and_other_a_b_is_another_run():
+    cases = _edge_cases()
+    zero, none = cases["gamma0"], cases["gamma0-neg0"]
+    assert zero["run"]["gamma"] == none["run"]["gamma"] == 0.0 and zero["run"]["neg"] == 5 and none["run"]["neg"] == 0
+    assert not np.any(zero["Y0"] == 0.0)                              # no -0.0, which adding alpha * 0 would turn into +0.0
+    assert _edge_run("gamma0")[0].tobytes() == _edge_run("gamma0-neg0")[0].tobytes()
+    assert not np.any(_edge_run("gamma0")[0] == 0.0)
+    assert _edge_run("gamma0")[1]["skipped"] >= 1                     # the negatives were drawn
+    ab = cases["a1.5-b0.9"]
+    assert (ab["run"]["a"], ab["run"]["b"]) == (1.5, 0.9)
+    default = U.layout(*ab["graph"], ab["Y0"], **{**ab["run"], "a": U.A_DEFAULT, "b": U.B_DEFAULT})
+    assert not np.array_equal(_edge_run("a1.5-b0.9")[0], default)
+
+
+def test_late_epochs_fire_where_a_float32_epoch_index_would_not():
+    case = _edge_cases()["late-epochs"]
+    run, w = case["run"], case["graph"][2]
+    assert run["e0"] > 2 ** 24 and run["e1"] <= run["n_epochs"] == 2 ** 31 - 1
+    for e in range(run["e0"], run["e1"]):
+        true, narrow = U.firing(w, e), U.firing_float32(w, e)
+        assert true.any() and np.any(true != narrow), e
+    assert 0.5 < 1.0 - run["e0"] / run["n_epochs"] < 0.6             # alpha: the steps are not negligible
+    assert np.abs(_edge_run("late-epochs")[0] - case["Y0"]).max() > 1.0
+
+
+def test_edge_layout_recipes_are_well_conditioned():
+    """The rule of ``test_layout_recipes_are_well_conditioned`` for every new case, over its own epochs and arguments."""
+    for name, case in _edge_cases().items():
+        moved = U.conditioning(case["graph"], case["Y0"], None, extent=case["extent"], run=case["run"])
+        print(name, moved)
+        assert moved <= 1e-12, name
 
 
 # ---- the public calls --------------------------------------------------------------------------------------------------

@@ -95,10 +95,18 @@ def fuzzy_graph(idx, d2):
 
 
 # ---- layout ---------------------------------------------------------------------------------------------------------------
-def firing(w, e):
-    """Which stored entries fire in epoch e."""
-    r = np.asarray(w, dtype=np.float64) / np.max(w)
+def firing(w, e, w_max=None):
+    """Which stored entries fire in epoch e.  ``w_max`` replaces the exact maximum (a recipe's host check asks what a
+    wrong one would change)."""
+    r = np.asarray(w, dtype=np.float64) / (np.max(w) if w_max is None else w_max)
     return np.floor(float(e + 1) * r) > np.floor(float(e) * r)
+
+
+def firing_float32(w, e):
+    """``firing`` with the epoch index converted through float32, which is exact only up to 2^24: what a kernel that
+    converted e to float would compute."""
+    r = np.asarray(w, dtype=np.float64) / np.max(w)
+    return np.floor(float(np.float32(e + 1)) * r) > np.floor(float(np.float32(e)) * r)
 
 
 def negatives(t, e, q, n, seed):
@@ -129,13 +137,13 @@ def _step(cur, y, attract, a, b, gamma, alpha, stats):
     return out
 
 
-def epoch(indptr, indices, w, Y_old, e, n_epochs, a, b, gamma, alpha0, neg, seed, stats):
+def epoch(indptr, indices, w, Y_old, e, n_epochs, a, b, gamma, alpha0, neg, seed, stats, w_max=None):
     """Y_new of epoch e: every vertex walks its firing entries in stored order, reading Y_old only.  Vectorised over the
     vertices: pass p handles the p-th firing entry of every row that has one."""
     n = Y_old.shape[0]
     alpha = alpha0 * (1.0 - e / n_epochs)
     rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
-    ft = np.flatnonzero(firing(w, e))
+    ft = np.flatnonzero(firing(w, e, w_max))
     fi = rows[ft]
     count = np.bincount(fi, minlength=n)
     rank = np.arange(ft.size) - (np.cumsum(count) - count)[fi]
@@ -158,12 +166,12 @@ def new_stats():
 
 
 def layout(indptr, indices, w, Y, n_epochs, e0=0, e1=None, a=A_DEFAULT, b=B_DEFAULT, gamma=1.0, alpha0=1.0, neg=5, seed=0,
-           stats=None):
+           stats=None, w_max=None):
     """Epochs [e0, e1) of sc_umap_layout from the positions Y."""
     stats = new_stats() if stats is None else stats
     Y = np.array(Y, dtype=np.float64, copy=True)
     for e in range(e0, n_epochs if e1 is None else e1):
-        Y = epoch(indptr, indices, w, Y, e, n_epochs, a, b, gamma, alpha0, neg, seed, stats)
+        Y = epoch(indptr, indices, w, Y, e, n_epochs, a, b, gamma, alpha0, neg, seed, stats, w_max)
     return Y
 
 
@@ -256,20 +264,120 @@ def layout_recipes():
     }
 
 
-def conditioning(graph, Y0, neg, reps=4, seed=0):
+def conditioning(graph, Y0, neg, reps=4, seed=0, extent=10.0, run=None):
     """The largest movement (of the extent 10) of three restated epochs when every pow result is changed by -1, 0 or +1
-    unit in the last place at random: what the reference itself cannot tell apart."""
+    unit in the last place at random: what the reference itself cannot tell apart.  ``run`` replaces the arguments of
+    ``layout`` (an edge case's own epochs, seed, a, b, gamma and neg) and ``extent`` the start's extent."""
     global np_power
     rng = np.random.default_rng(seed)
-    ref = layout(*graph, Y0, 10, 0, 3, neg=neg, seed=11)
+    run = dict(n_epochs=10, e0=0, e1=3, neg=neg, seed=11) if run is None else run
+    ref = layout(*graph, Y0, **run)
     exact, worst = np_power, 0.0
     try:
         np_power = lambda x, b: exact(x, b) * (1.0 + rng.integers(-1, 2, size=np.shape(x)) * 2.0 ** -52)   # noqa: E731
         for _ in range(reps):
-            worst = max(worst, float(np.abs(layout(*graph, Y0, 10, 0, 3, neg=neg, seed=11) - ref).max()) / 10.0)
+            worst = max(worst, float(np.abs(layout(*graph, Y0, **run) - ref).max()) / extent)
     finally:
         np_power = exact
     return worst
+
+
+# ---- recipes at the kernels' constants --------------------------------------------------------------------------------
+MIXED_CASES = [(1023, 16), (1024, 8), (1024, 9), (1025, 17), (2049, 16)]    # (n, k) around SUM_CHUNK = 1024 rows
+WIDTH_KS = [2, 8, 9, 17, 31]        # sc_knn_dense admits k >= 2; 8 | 9 and 16 | 17 are the edges of k_um_sigma<8/16/32>
+WMAX_GRID = 2048 * 256              # threads of k_um_wmax's largest grid: stored entries from here on are strided
+HIGH_SEED = (5 << 32) | 11          # the seed of the other tests with a non-zero high word (Philox key word k1)
+LATE_EPOCHS, LATE_E0 = 2 ** 31 - 1, 1_000_000_000      # epoch indices a float32 cannot tell apart (exact up to 2^24)
+
+
+def mixed(n, k):
+    """pca_like(n - k - 1, 8, 5) and k + 1 further copies of its row 0: the k + 2 identical cells list zero distances only
+    (rho = 0, so their floor is 1e-3 of the global mean, which the other rows make non-zero).  The few cells whose nearest
+    cell is row 0 list k of the copies at one distance d > 0 (rho = d, every t = 0, psum = k: the row-mean floor); every
+    other row is ordinary and converges.  Returns (features, the indices of the identical cells)."""
+    X = N.pca_like(n - k - 1, 8, 5)
+    return np.concatenate([X, np.tile(X[0], (k + 1, 1))]), np.concatenate([[0], np.arange(n - k - 1, n)])
+
+
+def plain_mean(row_sums, k):
+    """The mean of all distances with the row sums added in row order, a running sum from 0: NOT the device's order."""
+    s = 0.0
+    for v in row_sums.tolist():
+        s = s + v
+    return s / float(row_sums.size * (k + 1))
+
+
+def fuzzy_edge_recipes():
+    """name -> (features, k): ``mixed`` at one chunk of row sums less one, one chunk, one chunk and one, two chunks and one,
+    with list widths on both sides of the k_um_sigma instantiations; the (129, 8) trajectory at those widths, the widest
+    but one and the smallest the search admits."""
+    out = {f"mixed-n{n}-k{k}": (mixed(n, k)[0], k) for n, k in MIXED_CASES}
+    out.update({f"width-k{k}": (features(129, 8), k) for k in WIDTH_KS})
+    return out
+
+
+def ring(n=20000, reach=14):
+    """A ring lattice, every vertex joined to ``reach`` neighbours on either side: w{lo, hi} = 0.05 + 0.5 ((31 lo + 17 hi)
+    % 97) / 96 <= 0.55, and the edge {n - 2, n - 1} set to 1.0.  With n = 20,000 its two stored positions are 559,971 and
+    559,999 of 560,000: the maximum lies in the part of w that k_um_wmax reaches only by striding.  Returns (graph, the two
+    positions)."""
+    i = np.repeat(np.arange(n, dtype=np.int64), 2 * reach)
+    off = np.tile(np.concatenate([np.arange(-reach, 0), np.arange(1, reach + 1)]), n)
+    j = (i + off) % n
+    order = np.lexsort((j, i))
+    i, j = i[order], j[order]
+    lo, hi = np.minimum(i, j), np.maximum(i, j)
+    w = 0.05 + 0.5 * ((31 * lo + 17 * hi) % 97).astype(np.float64) / 96
+    top = np.flatnonzero((lo == n - 2) & (hi == n - 1))
+    w[top] = 1.0
+    indptr = np.arange(n + 1, dtype=np.int64) * (2 * reach)
+    return (indptr, j.astype(np.int32), w), top
+
+
+def star_with_empty_rows():
+    """The star with a vertex without stored entries put in front (every index moves up by one) and one appended."""
+    indptr, indices, w = star(300)
+    return np.concatenate([[0], indptr, indptr[-1:]]).astype(np.int64), (indices + 1).astype(np.int32), w
+
+
+def _case(graph, Y0, neg=5, seed=11, n_epochs=10, e0=0, e1=3, a=A_DEFAULT, b=B_DEFAULT, gamma=1.0, extent=10.0):
+    return {"graph": graph, "Y0": Y0, "extent": extent,
+            "run": dict(n_epochs=n_epochs, e0=e0, e1=e1, a=a, b=b, gamma=gamma, neg=neg, seed=seed)}
+
+
+def layout_edge_recipes():
+    """name -> {graph, Y0, extent, run (the arguments of ``layout``)}: the n = 257 graph with the negatives ending inside
+    and exactly at every block of four (k_um_epoch draws four per Philox call) up to UM_NEG_MAX = 16, a seed with a high
+    word, the ring whose largest weight lies past k_um_wmax's grid, rows without entries, gamma = 0 and its neg = 0 twin,
+    another a and b, and three epochs of a 2^31 - 1 epoch schedule from the 10^9-th.
+
+    The starts are the ones of ``layout_recipes`` (seed 4 in two dimensions, 8 for the star) and seed 9 for the ring,
+    with two exceptions made on the host as for the star there.  With a = 1.5, b = 0.9 the restatement itself moves by
+    1.1e-12 of the extent from seed 4 under a one-ulp change of its pow (``conditioning``), above the 1e-12 that
+    tests/test_cpu_umap.py asserts for every case; from seed 5, the next, it moves by 1.3e-14.  In three dimensions no
+    step of neg = 4 is clipped from seed 6, the start of ``n257-C3``; from seed 7, the next, one is, for both neg."""
+    g257 = layout_graph(257, 8, 15)
+    y2, y3 = start(257, 2, 4), start(257, 3, 7)
+    out = {f"neg{q}-C2": _case(g257, y2, neg=q) for q in (1, 3, 4, 8, 9, 16)}
+    out.update({f"neg{q}-C3": _case(g257, y3, neg=q) for q in (4, 16)})
+    out["seed-high-word"] = _case(g257, y2, seed=HIGH_SEED)
+    out["ring-wmax-tail"] = _case(ring()[0], np.random.default_rng(9).uniform(-100.0, 100.0, size=(20000, 2)), n_epochs=4, e1=2,
+                                  extent=100.0)
+    out["star-empty-rows"] = _case(star_with_empty_rows(), start(302, 2, 8))
+    out["gamma0"] = _case(g257, y2, gamma=0.0)
+    out["gamma0-neg0"] = _case(g257, y2, gamma=0.0, neg=0)
+    out["a1.5-b0.9"] = _case(g257, start(257, 2, 5), a=1.5, b=0.9)
+    out["late-epochs"] = _case(g257, y2, n_epochs=LATE_EPOCHS, e0=LATE_E0, e1=LATE_E0 + 3)
+    return out
+
+
+def layout_case_epochs(case, stats=None, w_max=None):
+    """[(e1, restated positions after the epochs [e0, e1))] of an edge case, one epoch at a time."""
+    run, ref, out = case["run"], case["Y0"], []
+    for e1 in range(run["e0"] + 1, run["e1"] + 1):
+        ref = layout(*case["graph"], ref, **{**run, "e0": e1 - 1, "e1": e1}, stats=stats, w_max=w_max)
+        out.append((e1, ref))
+    return out
 
 
 def blobs(n=1500, seed=0):
