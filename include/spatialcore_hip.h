@@ -59,10 +59,10 @@ extern "C" {
 #define SC_K_RIPLEY_G_LIST 19    /* sc_ripley_g_build: count and fill passes of the ordered neighbour lists */
 #define SC_K_RIPLEY_G_RELABEL 20 /* sc_ripley_g_*: permutation rows -> label words at the cells' positions */
 #define SC_K_RIPLEY_G_COUNT 21   /* sc_ripley_g_*: the per-cell first-contact counting kernel, observed pass included */
-#define SC_K_NMF_SETUP 22  /* sc_nmf_fit: fp64 values, the column-sorted copy (stable device sort) and its chunk table */
-#define SC_K_NMF_W 23      /* ... H H^T / rowsum(H) and the W pass over the rows */
+#define SC_K_NMF_SETUP 22  /* sc_nmf_fit, sc_nmf_fit_graph: fp64 values, the column-sorted copy (stable device sort) and its chunk table */
+#define SC_K_NMF_W 23      /* ... H H^T / rowsum(H) and the W pass over the rows (sc_nmf_fit_graph: with the graph term) */
 #define SC_K_NMF_H 24      /* ... W^T W / colsum(W), the H pass over the column chunks and its finish */
-#define SC_K_NMF_ERR 25    /* ... an error evaluation (the initial one, every tenth iteration, the final one) */
+#define SC_K_NMF_ERR 25    /* ... an error evaluation (the initial one, every tenth iteration, the final one; sc_nmf_fit_graph: with the penalty) */
 #define SC_K_DIFF_KNN 26   /* sc_knn_dense: the brute-force search kernel and the merge of the candidate splits */
 #define SC_K_DIFF_GRAPH 27 /* sc_diffmap_graph*: scales, union (sort), kernel weights, normalisation, components */
 #define SC_K_DIFF_SPMV 28  /* sc_lanczos_run: the sparse matrix-vector products */
@@ -710,6 +710,36 @@ int sc_gmm_posterior(sc_ctx *ctx, const void *scores, int dtype, int64_t n, int3
 int sc_nmf_fit(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
                int32_t n_genes, int32_t K, int32_t loss, int32_t update_H, int32_t max_iter, double tol, double *W, double *H,
                double *err_trace_out, int32_t *n_checks_out, int32_t *n_iter_out, double *recon_err_out);
+
+/* sc_nmf_fit_graph -- graph-regularised NMF (GNMF; Cai, He, Han & Huang, IEEE TPAMI 2011), Frobenius loss, H updated:
+ *   F(W, H) = 1/2 ||X - W H||_F^2 + (lambda / 2) tr(W^T L W),  L = diag(d) - A,  d_i = sum_j a_ij,
+ *   tr(W^T L W) = 1/2 sum_ij a_ij ||w_i - w_j||^2.
+ * X as for sc_nmf_fit.  A is an n x n CANONICAL CSR (gptr[n + 1] int64 from 0, gidx int32 strictly ascending inside a
+ * row, gval double): no diagonal entry, every value finite and > 0, every entry (i, j) with a mirror (j, i) of equal
+ * value; empty rows are legal (an isolated cell gets sc_nmf_fit's update) and so is a graph without entries (gidx and
+ * gval may then be NULL).  lambda finite and >= 0.  Each refusal is SC_ERR_INVALID and names the first offending entry.
+ *  - per iteration, first W, then H with the new W (sc_nmf_fit's Frobenius H pass):
+ *      W_ik <- W_ik ((X H^T)_ik + lambda (A W)_ik) / ((W H H^T)_ik + lambda d_i W_ik)
+ *    A W reads the W of the PREVIOUS iteration for every row (Jacobi: the form Cai et al. prove non-increasing in F), so
+ *    the pass reads one W buffer and writes the other.  No normalisation inside the loop: the descent is kept, and the
+ *    scale may drift (W shrinks, H grows; reconstruction_err and penalty show it).
+ *  - order, on top of sc_nmf_fit's: d_i = sum_e a_e and g_ik = sum_e a_e Wold[j_e][k] over the row's stored entries in
+ *    index order from 0; num = nx + lambda g (nx = sc_nmf_fit's numerator); den = dx + (lambda d_i) w (dx = sc_nmf_fit's
+ *    denominator); den == 0 -> EPS; Wnew = w (num / den).
+ *  - penalty: r_i = sum_e a_e T_k((w_ik - w_jk)^2) over the row's entries in index order, T the adjacent-pair tree over
+ *    the components padded with zeros to the next power of two; R = the r_i added in chunks of 1024 cells, each in index
+ *    order, the chunk sums in chunk order; tr(W^T L W) = R / 2.
+ *  - F = D + (lambda (R / 2)) / 2 with D as sc_nmf_fit's Frobenius D; the objective is e = sqrt(2 max(F, 0)).
+ *    e0 = e(W0, H0), prev = e0; e is evaluated after every iteration whose number is a multiple of 10, whatever tol is;
+ *    if tol > 0: stop if (prev - e) / e0 < tol, else prev = e.
+ *  - with lambda = 0 every added term is + 0 x finite: W and H equal sc_nmf_fit's (loss 2, update_H 1) byte for byte.
+ * Out: obj_trace_out[1 + max_iter / 10] and err_trace_out[1 + max_iter / 10] = e and sqrt(2 max(D, 0)) at the start and
+ * at every check, *n_checks_out = their number, *recon_err_out = sqrt(2 max(D, 0)) and *penalty_out = tr(W^T L W) of the
+ * returned factors.  Limits as sc_nmf_fit's; stored graph entries <= 2^32 - 1. */
+int sc_nmf_fit_graph(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const void *data, int dtype, int64_t n,
+                     int32_t n_genes, int32_t K, const int64_t *gptr, const int32_t *gidx, const double *gval, double lambda,
+                     int32_t max_iter, double tol, double *W, double *H, double *obj_trace_out, double *err_trace_out,
+                     int32_t *n_checks_out, int32_t *n_iter_out, double *recon_err_out, double *penalty_out);
 
 /* ---- N13 (extension): diffusion maps (Haghverdi et al. 2016) -- spatialcore_amd.diffusion -----------------------------
  * All arithmetic fp64, every product and sum rounded separately, no floating-point atomics: every result is a function

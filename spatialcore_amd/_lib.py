@@ -129,6 +129,8 @@ SYMBOLS = {
     "sc_gmm_posterior": [_P, _P, c_int, c_int64, c_int32, _P, _P, _P, _P, c_int32, c_double, _P, _P, POINTER(c_int64)],
     "sc_nmf_fit": [_P, _P, _P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, _P,
                    POINTER(c_int32), POINTER(c_int32), POINTER(c_double)],
+    "sc_nmf_fit_graph": [_P, _P, _P, _P, c_int, c_int64, c_int32, c_int32, _P, _P, _P, c_double, c_int32, c_double, _P, _P, _P, _P,
+                         POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)],
     "sc_knn_dense": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, _P, _P],
     "sc_knn_dense_gram": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P, _P],
     "sc_diffmap_graph": [_P, _P, POINTER(c_int64), POINTER(c_int64)],
@@ -935,6 +937,34 @@ class Context:
                                     byref(checks), byref(n_iter), byref(err)))
         return {"W": W, "H": H, "n_iter": n_iter.value, "reconstruction_err": err.value,
                 "error_trace": trace[:checks.value].copy()}
+
+    def nmf_fit_graph(self, indptr, indices, data, n_genes: int, gptr, gidx, gval, spatial_alpha: float, W0, H0,
+                      max_iter: int = 200, tol: float = 1e-4) -> dict:
+        """sc_nmf_fit_graph: graph-regularised NMF (Frobenius loss) of a canonical CSR over the symmetric graph
+        (``gptr``, ``gidx``, ``gval``), n x n canonical CSR without a diagonal.  The keys of ``nmf_fit`` plus
+        ``objective_trace`` (sqrt(2 max(F, 0)) at the start and at every check) and ``penalty`` = tr(W^T L W)."""
+        data = np.ascontiguousarray(data)
+        if data.dtype not in (np.float32, np.float64):
+            raise ValueError(f"nmf_fit_graph: values must be float32 or float64, got {data.dtype}")
+        indptr, indices = _c(indptr, np.int64), _c(indices, np.int32)
+        gptr, gidx, gval = _c(gptr, np.int64), _c(gidx, np.int32), _c(gval, np.float64)
+        W, H = np.array(W0, dtype=np.float64, order="C"), np.array(H0, dtype=np.float64, order="C")
+        n, G = indptr.size - 1, int(n_genes)
+        if W.ndim != 2 or H.ndim != 2 or W.shape[0] != n or H.shape != (W.shape[1], G):
+            raise ValueError(f"nmf_fit_graph: W0 must be (n, K) and H0 (K, n_genes), got {W.shape} and {H.shape}")
+        if indices.size != data.size or n < 1 or indptr[-1] != data.size:
+            raise ValueError("nmf_fit_graph: indptr, indices and values do not describe one CSR matrix")
+        if gptr.size != n + 1 or gidx.size != gval.size or gptr[-1] != gval.size:
+            raise ValueError("nmf_fit_graph: gptr, gidx and gval do not describe one n x n CSR matrix")
+        slots = 2 + max(int(max_iter), 0) // 10
+        obj, trace = np.zeros(slots, dtype=np.float64), np.zeros(slots, dtype=np.float64)
+        checks, n_iter, err, pen = c_int32(0), c_int32(0), c_double(0.0), c_double(0.0)
+        _check(self._lib.sc_nmf_fit_graph(self._h, _ptr(indptr), _ptr(indices), _ptr(data),
+                                          SC_F32 if data.dtype == np.float32 else SC_F64, n, G, W.shape[1], _ptr(gptr),
+                                          _ptr(gidx), _ptr(gval), float(spatial_alpha), int(max_iter), float(tol), _ptr(W),
+                                          _ptr(H), _ptr(obj), _ptr(trace), byref(checks), byref(n_iter), byref(err), byref(pen)))
+        return {"W": W, "H": H, "n_iter": n_iter.value, "reconstruction_err": err.value, "penalty": pen.value,
+                "error_trace": trace[:checks.value].copy(), "objective_trace": obj[:checks.value].copy()}
 
     # ---- N14 (extension): annotation ----------------------------------------------------------
     @staticmethod
