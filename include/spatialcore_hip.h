@@ -1020,6 +1020,42 @@ int sc_harmony_correct(sc_ctx *ctx);
 int sc_harmony_get(sc_ctx *ctx, int32_t what, void *out);
 int sc_harmony_end(sc_ctx *ctx);
 
+/* ---- multi-hop neighbourhood shells and their aggregates (sc_hops.hip) ----------
+ * CellCharter's neighbourhood aggregation (Varrone et al. 2024), restated from the published algorithm; parity with a
+ * cellcharter run is not pinned.  The graph is a pattern on n cells: shell l of cell i = the cells whose shortest path
+ * from i, along stored entries, has exactly l edges.  tests/hops_restated.py restates shells and aggregates.
+ * sc_hop_begin: the pattern as CSR (int64 indptr[n + 1], int32 indices), 1 <= n <= 2^31 - 1, every row's columns strictly
+ *   ascending inside [0, n) and off the diagonal; anything else is SC_ERR_INVALID naming the first offending row, on the
+ *   host, before the first HIP call.  Leaves shell 1 (the rows themselves) resident.
+ * sc_hop_next: shell l + 1 from shell l, which stays as part of the visited set (at most SC_HOP_MAX shells).  Per cell an
+ *   open-addressing table of the visited cells (integer atomicCAS), in one of three places chosen by the bound
+ *   1 + sum |shells 1 .. l| + sum of the degrees of shell l's members: a wavefront's LDS (bound <= SC_HOP_WAVE_KEYS), a
+ *   workgroup's LDS (<= SC_HOP_WG_KEYS), global memory in batches of at most 64 MiB beyond.  Count, exclusive scan, fill,
+ *   then the device-wide radix sort on (row, column): the shell is a canonical CSR whatever the class.  nnz_out = its
+ *   stored entries, max_row_out = its longest row, empty_rows_out = its empty rows.  A shell whose arrays exceed the free
+ *   device memory gives SC_ERR_NOMEM after the count, before anything is written; the resident shell is then unchanged.
+ * sc_hop_get: the resident shell, indptr_out[n + 1] and indices_out[nnz].
+ * sc_hop_aggregate: out[n][d] (fp64) over the resident shell of X[n][d] (row-major, SC_F32 widened on load, or SC_F64;
+ *   finite; 1 <= d <= 64).  what = SC_HOP_MEAN: m = (sum_j x_j) / c, the sum in ascending j from 0.0, one division;
+ *   SC_HOP_VAR: (sum_j x_j x_j) / c - m m, product, division and subtraction rounded one by one.  An empty shell gives
+ *   zeros.  X goes to the device on the first call after sc_hop_begin and stays; a later call re-sends it only if the
+ *   pointer, dtype or d differ.
+ * sc_hop_times: milliseconds of the last sc_hop_next's count (bound included), fill and sort, and of the last
+ *   sc_hop_aggregate's kernel (0.0 for a phase that did not run).
+ * sc_hop_end frees the state (also done by the next sc_hop_begin and by sc_ctx_destroy).  No floating-point atomics:
+ * every result is a function of the arguments alone, bit for bit. */
+#define SC_HOP_MEAN 1
+#define SC_HOP_VAR 2
+#define SC_HOP_MAX 64
+#define SC_HOP_WAVE_KEYS 512
+#define SC_HOP_WG_KEYS 16384
+int sc_hop_begin(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, int64_t n);
+int sc_hop_next(sc_ctx *ctx, int64_t *nnz_out, int32_t *max_row_out, int64_t *empty_rows_out);
+int sc_hop_get(sc_ctx *ctx, int64_t *indptr_out, int32_t *indices_out);
+int sc_hop_aggregate(sc_ctx *ctx, const void *X, int dtype, int32_t d, int32_t what, double *out);
+int sc_hop_times(sc_ctx *ctx, double *ms_out_4);
+int sc_hop_end(sc_ctx *ctx);
+
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across
  * one process per GPU with no data-path communication; at the end ONE ncclAllGather over RCCL (xGMI inside a node)

@@ -35,6 +35,8 @@ K_LOUVAIN_MOVE, K_LOUVAIN_LEVEL = 39, 40
 K_NEIGHBORS_GRAM = 41
 K_UMAP_GRAPH, K_UMAP_LAYOUT = 42, 43
 K_HVG_SETUP, K_HVG_DENSE, K_HVG_SPARSE = 44, 45, 46
+HOP_AGGREGATIONS = {"mean": 1, "var": 2}   # SC_HOP_MEAN / SC_HOP_VAR
+HOP_MAX, HOP_WAVE_KEYS, HOP_WG_KEYS = 64, 512, 16384   # SC_HOP_MAX, SC_HOP_WAVE_KEYS, SC_HOP_WG_KEYS
 HARMONY_ARRAYS = {"Zcorr": 0, "Zc": 1, "R": 2, "Y": 3, "O": 4, "W": 5, "order": 6, "dist": 7}   # sc_harmony_get's codes
 ANNOT_MODES = {"counts": 0, "log1p": 1, "log1p_renorm": 2}   # sc_annot_*'s input states
 NMF_LOSSES = {"frobenius": 2, "kullback-leibler": 1}   # sc_nmf_fit's codes (sklearn's beta)
@@ -162,6 +164,12 @@ SYMBOLS = {
     "sc_harmony_correct": [_P],
     "sc_harmony_get": [_P, c_int32, _P],
     "sc_harmony_end": [_P],
+    "sc_hop_begin": [_P, _P, _P, c_int64],
+    "sc_hop_next": [_P, POINTER(c_int64), POINTER(c_int32), POINTER(c_int64)],
+    "sc_hop_get": [_P, _P, _P],
+    "sc_hop_aggregate": [_P, _P, c_int, c_int32, c_int32, _P],
+    "sc_hop_times": [_P, _P],
+    "sc_hop_end": [_P],
     "sc_louvain_begin": [_P, _P, _P, _P, c_int64, c_int32, c_int32],
     "sc_louvain_resident_weights": [_P, _P, c_int64],
     "sc_louvain_begin_resident": [_P, _P, c_int64, c_int32, c_int32],
@@ -290,6 +298,7 @@ class Context:
         self._annot_shape = None   # (classes, genes) of the resident training problem (annot_train_begin .. annot_train_end)
         self._pca_shape = None     # (cells, genes) of the resident PCA matrix (pca_begin .. pca_end)
         self._harmony = None       # (n, d, K, B, blocks) of the resident Harmony problem (harmony_begin .. harmony_end)
+        self._hop = None           # [n, stored entries of the resident shell, X as uploaded] (hop_begin .. hop_end)
         self._louvain_n = None     # vertices of the next Louvain level (louvain_begin .. louvain_end)
         self._diff_n = self._diff_nnz = self._lanczos_cap = 0   # cells / stored entries of the resident diffusion graph, Lanczos basis cap
 
@@ -1186,6 +1195,64 @@ class Context:
     def harmony_end(self) -> None:
         self._harmony = None
         _check(self._lib.sc_harmony_end(self._h))
+
+    # ---- N20: aggregate_neighbors --------------------------------------------------------------
+    def hop_begin(self, indptr, indices, n: int) -> None:
+        """sc_hop_begin: leaves the pattern (canonical CSR without a diagonal, n x n) resident as shell 1."""
+        indptr, indices = _c(indptr, np.int64), _c(indices, np.int32)
+        if indptr.ndim != 1 or indptr.size != int(n) + 1 or indices.ndim != 1 or (indptr.size and indices.size != int(indptr[-1])):
+            raise ValueError(f"hop_begin: indptr must have {int(n) + 1} entries and indices indptr[-1], got {indptr.shape} and {indices.shape}")
+        self._hop = None   # until the call succeeds this object vouches for no resident graph
+        _check(self._lib.sc_hop_begin(self._h, _ptr(indptr), _ptr(indices), int(n)))
+        self._hop = [int(n), int(indices.size), None]
+
+    def _hop_state(self, who: str):
+        if self._hop is None:
+            raise SpatialCoreHipError(f"{who}: no graph is resident (hop_begin)")
+        return self._hop
+
+    def hop_next(self) -> Tuple[int, int, int]:
+        """sc_hop_next: the next shell becomes resident; (its stored entries, its longest row, its empty rows)."""
+        st = self._hop_state("hop_next")
+        nnz, longest, empty = c_int64(0), c_int32(0), c_int64(0)
+        _check(self._lib.sc_hop_next(self._h, byref(nnz), byref(longest), byref(empty)))
+        st[1] = nnz.value
+        return nnz.value, longest.value, empty.value
+
+    def hop_get(self) -> Tuple[np.ndarray, np.ndarray]:
+        """sc_hop_get: the resident shell as canonical CSR (int64 indptr, int32 indices)."""
+        n, nnz, _ = self._hop_state("hop_get")
+        indptr, indices = np.empty(n + 1, dtype=np.int64), np.empty(nnz, dtype=np.int32)
+        _check(self._lib.sc_hop_get(self._h, _ptr(indptr), _ptr(indices)))
+        return indptr, indices
+
+    def hop_aggregate(self, X, what: str) -> np.ndarray:
+        """sc_hop_aggregate: "mean" or "var" of X (n, d; float32 or float64) over the resident shell, (n, d) float64.  X goes
+        to the device once per hop_begin as long as the same array is handed in."""
+        st = self._hop_state("hop_aggregate")
+        if what not in HOP_AGGREGATIONS:
+            raise ValueError(f"hop_aggregate: unknown aggregation {what!r}; one of {sorted(HOP_AGGREGATIONS)}")
+        if st[2] is None or st[2][0] is not X:
+            if not isinstance(X, np.ndarray) or X.ndim != 2 or X.shape[0] != st[0] or X.dtype not in (np.float32, np.float64):
+                raise ValueError(f"hop_aggregate: X must be a float32 or float64 array with {st[0]} rows, got {getattr(X, 'dtype', None)} "
+                                 f"{getattr(X, 'shape', None)}")
+            st[2] = (X, np.ascontiguousarray(X))   # the contiguous array is the one the library saw: kept, so its address stays
+        Xc = st[2][1]
+        out = np.empty(Xc.shape, dtype=np.float64)
+        _check(self._lib.sc_hop_aggregate(self._h, _ptr(Xc), SC_F32 if Xc.dtype == np.float32 else SC_F64, Xc.shape[1],
+                                          HOP_AGGREGATIONS[what], _ptr(out)))
+        return out
+
+    def hop_times(self) -> dict:
+        """sc_hop_times: milliseconds of the last hop_next's count, fill and sort and of the last hop_aggregate's kernel."""
+        self._hop_state("hop_times")
+        ms = np.zeros(4)
+        _check(self._lib.sc_hop_times(self._h, _ptr(ms)))
+        return dict(zip(("count", "fill", "sort", "aggregate"), ms.tolist()))
+
+    def hop_end(self) -> None:
+        self._hop = None
+        _check(self._lib.sc_hop_end(self._h))
 
     # ---- N16 (extension): Louvain communities ---------------------------------------------------
     def louvain_begin(self, indptr, indices, q, g: int, max_rounds: int) -> None:

@@ -269,6 +269,8 @@ struct sc_ctx {
     std::unique_ptr<Resident> louvain;   // LouvainState
     // ---- Harmony (sc_harmony.hip): the embedding, the assignments and the block tables between sc_harmony_begin and _end ----
     std::unique_ptr<Resident> harmony;   // HarmonyState
+    // ---- neighbourhood shells (sc_hops.hip): the pattern, the shells so far and X between sc_hop_begin and _end ----
+    std::unique_ptr<Resident> hops;      // HopState
 
     // ---- graph (CSR, rows sorted by column) + transpose ----
     int64_t g_n = 0, g_nnz = 0;

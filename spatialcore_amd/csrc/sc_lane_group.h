@@ -56,4 +56,26 @@ __device__ __forceinline__ void lane_group_walk(const int32_t *__restrict__ idx,
     }
 }
 
+// The same walk over a pattern, entries without values (sc_hops.hip's k_hop_aggregate): add(operand) per entry, in the
+// same fixed order.
+template <class Fetch, class Add>
+__device__ __forceinline__ void lane_group_walk_pattern(const int32_t *__restrict__ idx, int64_t p0, int64_t p1, int w, int lane,
+                                                        Fetch fetch, Add add)
+{
+    for (int64_t base = p0; base < p1; base += w) {
+        const int cnt = (int)(p1 - base < w ? p1 - base : w);
+        const int32_t id_mine = lane < cnt ? idx[base + lane] : 0;
+        int j = 0;
+        for (; j + 4 <= cnt; j += 4) {
+            const auto r0 = fetch(__shfl(id_mine, j, w)), r1 = fetch(__shfl(id_mine, j + 1, w));
+            const auto r2 = fetch(__shfl(id_mine, j + 2, w)), r3 = fetch(__shfl(id_mine, j + 3, w));
+            add(r0);
+            add(r1);
+            add(r2);
+            add(r3);
+        }
+        for (; j < cnt; ++j) add(fetch(__shfl(id_mine, j, w)));
+    }
+}
+
 }  // namespace

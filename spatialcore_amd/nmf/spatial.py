@@ -13,18 +13,16 @@ import numbers
 from typing import Optional, Sequence, Union
 
 import numpy as np
-from scipy import sparse
 
 from spatialcore_amd import _lib
 from spatialcore_amd._batches import batch_groups
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._sparse_input import gene_columns
-from spatialcore_amd.cluster.communities import symmetric_graph
+from spatialcore_amd._spatial_graph import K_NEIGHBORS_MAX, _coordinates, _given_graph, knn_union_graph
+from spatialcore_amd._spatial_graph import union_of_knn  # noqa: F401  (its name stays importable from here)
 from spatialcore_amd.nmf import factorize
 
 logger = get_logger("nmf")
-
-K_NEIGHBORS_MAX = 65536   # sc_knn_2d's limit
 
 
 def _check_alpha(spatial_alpha) -> float:
@@ -32,47 +30,6 @@ def _check_alpha(spatial_alpha) -> float:
             or spatial_alpha < 0):
         raise ValueError(f"spatial_alpha must be a finite number >= 0, got {spatial_alpha!r}")
     return float(spatial_alpha)
-
-
-def _coordinates(adata, spatial_key) -> np.ndarray:
-    if not isinstance(spatial_key, str) or spatial_key not in adata.obsm:
-        raise ValueError(f"adata.obsm[{spatial_key!r}] not found. Spatial coordinates are required unless graph= is given.")
-    xy = np.asarray(adata.obsm[spatial_key])
-    if xy.ndim != 2 or xy.shape[1] != 2:
-        raise ValueError(f"only 2-D coordinates are supported (adata.obsm[{spatial_key!r}] has shape {xy.shape})")
-    xy = np.ascontiguousarray(xy, dtype=np.float64)
-    if not np.all(np.isfinite(xy)):
-        raise ValueError(f"adata.obsm[{spatial_key!r}] contains NaN or infinite values")
-    return xy
-
-
-def _given_graph(adata, graph, n: int):
-    """The caller's graph without its diagonal, validated as the communities module validates one."""
-    source = f"obsp[{graph!r}]" if isinstance(graph, str) else "matrix"
-    if isinstance(graph, str):
-        if graph not in adata.obsp:
-            raise ValueError(f"graph={graph!r} is not an entry of adata.obsp (available: {sorted(adata.obsp)})")
-        graph = adata.obsp[graph]
-    if sparse.issparse(graph) and graph.ndim == 2 and graph.shape == (n, n):
-        coo = sparse.coo_matrix(graph)
-        off = coo.row != coo.col
-        graph = sparse.csr_matrix((coo.data[off], (coo.row[off], coo.col[off])), shape=(n, n))
-    return symmetric_graph(adata, graph, n), source
-
-
-def union_of_knn(lists: np.ndarray, rows: Optional[np.ndarray], n: int) -> sparse.csr_matrix:
-    """The symmetric union of neighbour lists with weight 1.0: ``lists`` (m, k) holds positions into ``rows`` (None: the
-    cells themselves); entry (i, j) is stored if j is a neighbour of i or i one of j.  Canonical CSR, n x n."""
-    m, k = lists.shape
-    src = np.repeat(np.arange(m, dtype=np.int64), k)
-    dst = lists.astype(np.int64).ravel()
-    if rows is not None:
-        src, dst = rows[src], rows[dst]
-    A = sparse.coo_matrix((np.ones(2 * src.size), (np.concatenate([src, dst]), np.concatenate([dst, src]))), shape=(n, n)).tocsr()
-    A.sum_duplicates()     # an edge both lists hold, or one list holds twice, is one entry
-    A.sort_indices()
-    A.data[:] = 1.0
-    return A
 
 
 def fit_spatial_nmf(adata, n_components: int, spatial_alpha: float = 1.0, *, graph=None, spatial_key: str = "spatial",
@@ -136,12 +93,7 @@ def fit_spatial_nmf(adata, n_components: int, spatial_alpha: float = 1.0, *, gra
     logger.info(f"Spatial NMF (frobenius, graph-regularised, alpha={lam:g}): {n:,} cells x {G} genes, {K} components")
     ctx = _lib.default_context(device)
     if A is None:
-        parts = []
-        for _, rows in groups:
-            lists = ctx.knn(xy if rows is None else xy[rows], int(n_neighbors))
-            parts.append(union_of_knn(lists, rows, n))
-        A = parts[0] if len(parts) == 1 else sum(parts[1:], parts[0]).tocsr()
-        A.sort_indices()
+        A = knn_union_graph(ctx, xy, groups, n_neighbors, n)
     if init == "random":
         W0, H0 = factorize.random_init(factorize._scale(Xc, K), n, G, K, random_state)
     res = ctx.nmf_fit_graph(Xc.indptr, Xc.indices, Xc.data, G, A.indptr, A.indices, A.data, lam, W0, H0, int(max_iter), float(tol))

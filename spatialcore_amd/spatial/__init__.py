@@ -11,6 +11,7 @@ from spatialcore_amd.spatial.autocorrelation import (
 from spatialcore_amd.spatial.distance import calculate_domain_distances, get_distance_matrix
 from spatialcore_amd.spatial.local_stats import local_gearys_c, local_getis_ord
 from spatialcore_amd.spatial.domains import get_domain_summary, make_spatial_domains
+from spatialcore_amd.spatial.hops import aggregate_neighbors
 from spatialcore_amd.spatial.markers import rank_genes_groups
 from spatialcore_amd.spatial.neighborhoods import (
     co_occurrence,
@@ -37,6 +38,7 @@ __all__ = [
     "co_occurrence",  # extension: squidpy's function, not in the reference
     "ligrec",  # extension: squidpy's function, not in the reference
     "ripley_g",  # extension: not in the reference
+    "aggregate_neighbors",  # extension: cellcharter's function, not in the reference
     "make_spatial_domains",
     "get_domain_summary",
     "calculate_domain_distances",

@@ -1,0 +1,232 @@
+"""aggregate_neighbors without a device: the restatement against itself (tests/hops_restated.py), the argument checks of
+the public function, the moved graph helpers, the C surface.
+
+The bounds of test_ordered_against_textbook are first-order summation and rounding error of the two expression orders,
+c = the row's length, u = 2^-53; they are not measured numbers.  ordered: c - 1 additions and one division, at most
+c u sum|x| / c.  textbook: 1 / c rounded, c products, c - 1 additions, at most (c + 2) u sum|x| / c.  Together at most
+2 (c + 2) u sum|x_j| / c.  The variance adds one product per entry on each side and the square of the mean, whose error
+is twice the mean's relative error: 4 (c + 2) u sum x_j^2 / c."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+from scipy import sparse
+
+import hops_restated as R
+from conftest import make_adata
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ---- 1. the shells: the textbook recursion against the search ---------------------------------------------------------------
+def _same_shells(A, L):
+    want = R.shells_bfs(A, L)
+    got = R.shells_textbook(A, L)
+    assert len(got) == len(want) == L
+    for l, (S, (indptr, indices)) in enumerate(zip(got, want), start=1):
+        assert S.has_canonical_format, l
+        np.testing.assert_array_equal(S.indptr, indptr, err_msg=f"shell {l}")
+        np.testing.assert_array_equal(S.indices, indices, err_msg=f"shell {l}")
+    return got
+
+
+@pytest.mark.parametrize("name", list(R.KNN_CASES))
+def test_textbook_shells_equal_the_search_on_knn_graphs(name):
+    A, L = R.knn_case(name)
+    assert (A != A.T).nnz == 0 and A.diagonal().sum() == 0
+    shells = _same_shells(A, L)
+    print(f"{name}: shell entries {[int(S.nnz) for S in shells]}, largest visited set {R.largest_visited_set(shells)} keys")
+    assert all(S.nnz > 0 for S in shells)
+    total = sum(shells[1:], shells[0])
+    assert total.data.max() == 1.0 and total.diagonal().sum() == 0      # the shells are disjoint and never hold the cell itself
+
+
+def test_textbook_shells_equal_the_search_on_a_directed_graph():
+    A = R.directed(500, 4, 3)
+    assert (A != A.T).nnz > 0.9 * A.nnz
+    _same_shells(A, 4)
+
+
+def test_textbook_shells_on_small_graphs_by_hand():
+    shells = R.shells_textbook(R.path(5), 6)
+    assert [S[0].indices.tolist() for S in shells] == [[1], [2], [3], [4], [], []]
+    assert [S[2].indices.tolist() for S in shells] == [[1, 3], [0, 4], [], [], [], []]
+    star = R.shells_textbook(R.star(4, pendant=True), 3)
+    assert [S[0].indices.tolist() for S in star] == [[1, 2, 3, 4], [5], []]
+    assert [S[5].indices.tolist() for S in star] == [[1], [0], [2, 3, 4]]
+    d = R.shells_textbook(R.directed_star(4), 3)
+    assert [S[1].indices.tolist() for S in d] == [[0], [2, 3, 4], []] and [S[2].nnz for S in d] == [0, 0, 0]
+
+
+# ---- 2. the aggregates: the device's order against the textbook --------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_ordered_against_textbook(dtype):
+    A, L = R.knn_case("knn3000k15")
+    X = (np.random.default_rng(2).normal(size=(A.shape[0], 8)) * 3 + 1).astype(dtype)
+    for l, S in enumerate(R.shells_textbook(A, L), start=1):
+        (m, v), (tm, tv), (bm, bv) = R.ordered(S, X), R.textbook(S, X), R.bounds(S, X)
+        em, ev = np.abs(m - tm), np.abs(v - tv)
+        print(f"shell {l}: mean error / bound {np.max(em / bm):.3f}, variance error / bound {np.max(ev / bv):.3f}")
+        assert np.all(em <= bm) and np.all(ev <= bv)
+
+
+def test_ordered_gives_zeros_on_an_empty_row():
+    A = R.with_isolated_cell(R.path(6), 2)
+    X = np.arange(12.0).reshape(6, 2) + 1
+    m, v = R.ordered(A, X)
+    assert not m[2].any() and not v[2].any() and np.all(np.isfinite(m)) and np.all(np.isfinite(v))
+    np.testing.assert_array_equal(m[0], X[1])
+    np.testing.assert_array_equal(m[4], (X[3] + X[5]) / 2.0)
+    np.testing.assert_array_equal(v[4], (X[3] * X[3] + X[5] * X[5]) / 2.0 - m[4] * m[4])
+
+
+def test_ari():
+    a = np.array([0, 0, 1, 1, 2, 2])
+    assert R.ari(a, a) == 1.0 and R.ari(a, np.array([5, 5, 3, 3, 9, 9])) == 1.0
+    assert abs(R.ari(np.array([0, 0, 0, 1, 1, 1]), np.array([0, 0, 1, 1, 2, 2])) - 0.24242424242424243) < 1e-15   # sklearn's value
+    rng = np.random.default_rng(0)
+    assert abs(R.ari(rng.integers(0, 3, 5000), rng.integers(0, 3, 5000))) < 0.01
+
+
+# ---- 3. the public function's argument checks ---------------------------------------------------------------------------------
+def _adata(n=60, d=5, seed=0):
+    rng = np.random.default_rng(seed)
+    ad = make_adata(rng.uniform(size=(n, 2)), np.zeros((n, 3)))
+    ad.obsm["X_pca"] = rng.normal(size=(n, d))
+    ad.obs["slide"] = np.where(np.arange(n) < n // 2, "a", "b")
+    return ad
+
+
+def test_argument_errors_are_raised_without_a_gpu(monkeypatch):
+    from spatialcore_amd import _lib
+    from spatialcore_amd.spatial import aggregate_neighbors
+
+    def no_context(*a, **k):
+        raise AssertionError("an argument error must be raised before a context is created")
+
+    monkeypatch.setattr(_lib, "default_context", no_context)
+    ad = _adata()
+    n = ad.n_obs
+    ring = sparse.csr_matrix((np.ones(n), (np.arange(n), (np.arange(n) + 1) % n)), shape=(n, n))
+    ad.obsp["ring"] = ring
+
+    def refused(fragment, **kw):
+        with pytest.raises(ValueError, match=re.escape(fragment)):
+            aggregate_neighbors(ad, **kw)
+
+    for bad in (-1, 17, True, 2.0, "3", None):
+        refused("n_layers must be an integer in 0..16 or a sequence of such layers", n_layers=bad)
+    for bad in ([], [1, -1], [1, 17], [1, 2.5], [True]):
+        refused("n_layers must hold at least one layer, each an integer in 0..16", n_layers=bad)
+    refused("n_layers holds a layer twice", n_layers=[1, 2, 1])
+    for bad in ("median", ["mean", "max"], [], 3, None, [1]):
+        refused('is not supported; supported: "mean", "var" or a sequence of the two', aggregations=bad)
+    refused("aggregations holds an aggregation twice", aggregations=["var", "var"])
+    for bad in ("", 3, None):
+        refused("out_key must be a non-empty string", out_key=bad)
+    refused("use_rep='X_umap' is not an entry of adata.obsm", use_rep="X_umap")
+    ad.obsm["wide"] = np.zeros((n, 65))
+    refused("adata.obsm['wide'] has 65 columns; 1..64 are supported", use_rep="wide")
+    ad.obsm["none"] = np.zeros((n, 0))
+    refused("adata.obsm['none'] has 0 columns; 1..64 are supported", use_rep="none")
+    ad.obsm["ints"] = np.zeros((n, 3), dtype=np.int64)
+    refused("adata.obsm['ints'] must be a 2-D float32 or float64 array", use_rep="ints")
+    ad.obsm["flat"] = np.zeros(n)
+    refused("adata.obsm['flat'] must be a 2-D float32 or float64 array", use_rep="flat")
+    for value in (np.nan, np.inf):
+        ad.obsm["holes"] = ad.obsm["X_pca"].copy()
+        ad.obsm["holes"][n - 1, 4] = value
+        refused("adata.obsm['holes'] contains NaN or infinite values", use_rep="holes")
+    # a given graph
+    refused("connectivity_key='knn' is not an entry of adata.obsp (available: ['ring'])", connectivity_key="knn")
+    refused("connectivity_key must be None, the name of an adata.obsp entry or a scipy sparse matrix, got ndarray",
+            connectivity_key=np.eye(n))
+    refused(f"the graph (matrix) must be cells x cells = ({n}, {n}), got (3, 3)", connectivity_key=sparse.identity(3, format="csr"))
+    refused("sample_key='batch' is not a column of adata.obs", connectivity_key="ring", sample_key="batch")
+    # the ring joins the last cell of slide a to the first of b, and the last of b to the first of a
+    refused(f"the graph (obsp['ring']) joins cells of different samples of adata.obs['slide']: 2 stored entries, the first at "
+            f"({n // 2 - 1}, {n // 2})", connectivity_key="ring", sample_key="slide")
+    # the default graph
+    for bad in (0, 65537, 2.0, True, None):
+        refused("n_neighbors must be an integer in 1..65536", n_neighbors=bad)
+    refused("adata.obsm['where'] not found", spatial_key="where")
+    refused("sample_key='batch' is not a column of adata.obs", sample_key="batch")
+    refused(f"n_neighbors={n} needs more than the {n} cells of the smallest data set", n_neighbors=n)
+    refused(f"n_neighbors={n // 2} needs more than the {n // 2} cells of the smallest sample", n_neighbors=n // 2, sample_key="slide")
+    ad.obsm["xyz"] = np.zeros((n, 3))
+    refused("only 2-D coordinates are supported", spatial_key="xyz")
+
+
+def test_pattern_graph_is_lax_where_the_nmf_graph_is_strict():
+    """Any pattern goes: directed, weighted, with a diagonal and stored zeros; the NMF helper still demands symmetry."""
+    from spatialcore_amd.nmf.spatial import _given_graph
+    from spatialcore_amd.spatial.hops import pattern_graph
+
+    ad = _adata(6)
+    rows, cols, data = [0, 0, 1, 2, 2, 3, 3], [2, 1, 1, 0, 5, 4, 4], [0.5, -2.0, 1.0, 0.0, 7.0, 1.0, 1.0]
+    G = sparse.coo_matrix((data, (rows, cols)), shape=(6, 6))   # (1, 1) on the diagonal, (2, 0) a stored zero, (3, 4) twice
+    A, source = pattern_graph(ad, G, 6)
+    assert source == "matrix" and A.has_canonical_format and A.indptr.tolist() == [0, 2, 2, 3, 4, 4, 4]
+    assert A.indices.tolist() == [1, 2, 5, 4] and A.data.tolist() == [1.0, 1.0, 1.0, 1.0]
+    with pytest.raises(ValueError):
+        _given_graph(ad, sparse.csr_matrix(G), 6)
+
+
+def test_without_a_gpu_a_valid_call_reaches_the_device_and_fails_there():
+    from spatialcore_amd import _lib
+    from spatialcore_amd.spatial import aggregate_neighbors
+
+    if _lib.device_count() > 0:
+        pytest.skip("a GPU is visible")
+    with pytest.raises(_lib.SpatialCoreHipError):
+        aggregate_neighbors(_adata())
+
+
+# ---- 4. the moved helpers, the surface ---------------------------------------------------------------------------------------------
+def test_the_graph_helpers_stay_importable_from_nmf_spatial():
+    from spatialcore_amd import _spatial_graph
+    from spatialcore_amd.nmf import spatial as nmf_spatial
+
+    for name in ("_coordinates", "_given_graph", "union_of_knn", "K_NEIGHBORS_MAX"):
+        assert getattr(nmf_spatial, name) is getattr(_spatial_graph, name)
+    lists = np.array([[1], [2], [0]], dtype=np.int32)
+    assert nmf_spatial.union_of_knn(lists, None, 3).toarray().tolist() == [[0, 1, 1], [1, 0, 1], [1, 1, 0]]
+
+
+def test_ctypes_surface_and_all():
+    from spatialcore_amd import _lib, spatial
+
+    assert "aggregate_neighbors" in spatial.__all__ and callable(spatial.aggregate_neighbors)
+    lib = _lib.load_library()
+    for name in ("sc_hop_begin", "sc_hop_next", "sc_hop_get", "sc_hop_aggregate", "sc_hop_times", "sc_hop_end"):
+        assert name in _lib.SYMBOLS and hasattr(lib, name) and hasattr(_lib.Context, name[3:])
+    header = open(os.path.join(ROOT, "include", "spatialcore_hip.h")).read()
+    codes = {k: int(v) for k, v in re.findall(r"#define SC_HOP_(\w+) (\d+)", header)}
+    assert codes == {"MEAN": _lib.HOP_AGGREGATIONS["mean"], "VAR": _lib.HOP_AGGREGATIONS["var"], "MAX": _lib.HOP_MAX,
+                     "WAVE_KEYS": _lib.HOP_WAVE_KEYS, "WG_KEYS": _lib.HOP_WG_KEYS}
+    # the entry points refuse on the host, before any HIP call: no context, no device
+    assert lib.sc_hop_end(None) == _lib.SC_ERR_INVALID and b"sc_hop_end: null pointer" in lib.sc_last_error()
+    indptr, indices = np.array([0, 1, 2], dtype=np.int64), np.array([1, 0], dtype=np.int32)
+    rc = lib.sc_hop_begin(None, indptr.ctypes.data_as(ctypes.c_void_p), indices.ctypes.data_as(ctypes.c_void_p), 2)
+    assert rc == _lib.SC_ERR_INVALID and b"sc_hop_begin: null pointer" in lib.sc_last_error()
+    makefile = open(os.path.join(ROOT, "spatialcore_amd", "csrc", "Makefile")).read()
+    assert "sc_hops.hip" in makefile.split("SRCS =")[1].split("\n")[0] and "asan_hops:" in makefile
+
+
+def test_host_checks_pass_under_the_sanitizers():
+    """`make asan_hops`: tests/hops_host_checks.cpp (its own main, nothing preloaded) against the AddressSanitizer + UBSan
+    objects of the library.  Every call in it is refused before its first HIP call: no device is touched."""
+    csrc = os.path.join(ROOT, "spatialcore_amd", "csrc")
+    if shutil.which("make") is None or not os.access(csrc, os.W_OK):
+        pytest.skip("make is missing or the source tree cannot be written to: the sanitizer objects cannot be built here")
+    jobs = str(max(1, min(16, os.cpu_count() or 1)))
+    objects = subprocess.run(["make", "-C", csrc, f"-j{jobs}", "asan_build/sc_hops.o", "asan_build/sc_api.o"], capture_output=True, text=True)
+    if objects.returncode != 0:
+        pytest.skip("the sanitizer objects cannot be built here: " + objects.stderr[-300:])
+    run = subprocess.run(["make", "-C", csrc, f"-j{jobs}", "asan_hops"], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout[-3000:] + run.stderr[-3000:]
+    assert "hops host checks ok" in run.stdout and "FAIL" not in run.stdout
