@@ -30,22 +30,30 @@ class _OrderedGraph(_Ordered):
         self.grow = np.repeat(np.arange(self.n), np.diff(self.gptr))
         self.deg = _seg_sum(self.a, self.gptr)                  # d_i: the row's weights in index order from 0
 
-    def w_pass(self, W, H, HHt, Hsum):
-        """Jacobi: every row reads the W it was handed, the previous iteration's, for its neighbours."""
+    def w_terms(self, W, H, HHt):
+        """(num, den) of the W pass before the den == 0 -> EPS guard."""
         Ht = H.T
         nx = _seg_sum(self.x[:, None] * Ht[self.col], self.indptr)
         dx = _seq(W[:, :, None] * HHt[None, :, :], 1)
         g = _seg_sum(self.a[:, None] * W[self.gcol], self.gptr)
         num = nx + self.lam * g
         den = dx + (self.lam * self.deg)[:, None] * W
+        return num, den
+
+    def w_pass(self, W, H, HHt, Hsum):
+        """Jacobi: every row reads the W it was handed, the previous iteration's, for its neighbours."""
+        num, den = self.w_terms(W, H, HHt)
         den[den == 0] = EPS
         return W * (num / den)
 
-    def penalty(self, W):
-        """tr(W^T L W) = R / 2, R = sum_i sum_e a_e T_k((w_ik - w_jk)^2), cells in chunks of 1024."""
+    def row_penalties(self, W):
+        """r_i = sum_e a_e T_k((w_ik - w_jk)^2), the graph row's stored entries in index order from 0."""
         diff = W[self.grow] - W[self.gcol]
-        r = _seg_sum(self.a * _tree(diff * diff), self.gptr)
-        R = float(_seq(_seg_sum(r, self.cell_ptr), 0))
+        return _seg_sum(self.a * _tree(diff * diff), self.gptr)
+
+    def penalty(self, W):
+        """tr(W^T L W) = R / 2, R = sum_i r_i, cells in chunks of 1024."""
+        R = float(_seq(_seg_sum(self.row_penalties(W), self.cell_ptr), 0))
         return R / 2.0
 
     def evaluate(self, W, H):
