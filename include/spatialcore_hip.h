@@ -31,6 +31,7 @@ extern "C" {
 #define SC_ERR_HIP 3      /* HIP runtime failure     -> RuntimeError                   */
 #define SC_ERR_NOMEM 4    /* device/host allocation  -> MemoryError                    */
 #define SC_ERR_EMPTY 5    /* empty neighbourhoods (NB:253-260) -> ValueError           */
+#define SC_ERR_ILLDEFINED 6 /* sc_mixture_*: a covariance is not positive definite -> ValueError (sklearn's message) */
 
 /* expression value types accepted by sc_expr_* */
 #define SC_F32 0
@@ -84,7 +85,10 @@ extern "C" {
 #define SC_K_HVG_SETUP 44   /* sc_hvg_pearson: row sums, the column-sorted copy, the per-gene sums of x and x^2, their total */
 #define SC_K_HVG_DENSE 45   /* ... the dense zero term: one division and one square root per (cell, gene) pair */
 #define SC_K_HVG_SPARSE 46  /* ... the correction per stored entry and the per-gene finish */
-#define SC_K_COUNT_ 47
+#define SC_K_COUNT_ 47      /* the ids up to here; stays as tests/test_cpu_hvg.py pins it.  The table ends at SC_K_END_ */
+#define SC_K_MIX_ESTEP 47   /* sc_mixture_*: weighted log-probabilities, normalisation and the log-likelihood sum */
+#define SC_K_MIX_MSTEP 48   /* sc_mixture_*: both M-step passes with their slice reductions, and the precision stage */
+#define SC_K_END_ 49        /* one past the last kernel id: what sc_ctx_kernel_time accepts */
 
 typedef struct sc_ctx sc_ctx;
 
@@ -1055,6 +1059,57 @@ int sc_hop_get(sc_ctx *ctx, int64_t *indptr_out, int32_t *indices_out);
 int sc_hop_aggregate(sc_ctx *ctx, const void *X, int dtype, int32_t d, int32_t what, double *out);
 int sc_hop_times(sc_ctx *ctx, double *ms_out_4);
 int sc_hop_end(sc_ctx *ctx);
+
+/* ---- Gaussian mixtures (extension; restated by tests/mixture_restated.py) --------------------------------
+ * sc_mixture_fit -- sklearn 1.7.2's GaussianMixture(n_components=K, covariance_type, n_init, max_iter, tol, reg_covar,
+ *   init_params="kmeans", random_state).fit_predict on X[n][D] (float32 or float64; every value is widened to fp64 first
+ *   and all arithmetic is fp64).  cov_type SC_MIX_FULL or SC_MIX_DIAG.  Envelope: 1 <= n <= 2^31 - 1, 1 <= D <= 256,
+ *   1 <= K <= min(64, n), 1 <= n_init <= 10, max_iter >= 1, tol >= 0, reg_covar >= 0, every value finite: anything else is
+ *   SC_ERR_INVALID with the argument in the message, on the host, before the first HIP call.
+ *   Start (_initialize_parameters): run r takes the labels of KMeans(K, n_init=1, random_state=<the shared RandomState>)
+ *   from sc_kmeans_fit's seeding and Lloyd kernels on the fp64 values: km_max_iter, km_tol and x_mean[D] (fp64) are sklearn's
+ *   KMeans arguments as in sc_kmeans_fit, uniforms[n_init][1 + (K - 1) L] the draws of ONE RandomState shared by the runs,
+ *   exactly as T3 documents (kmeans_draws' layout).  One-hot responsibilities, then the M-step.  K = 1 runs no k-means
+ *   (x_mean and uniforms may be NULL): every responsibility is 1.
+ *   M-step (_estimate_gaussian_parameters): rows are cut into slices of S rows, S = max(1024, ceil(n / smax) rounded up to
+ *   32), smax = clamp(2^28 / bytes of one slice's partials, 1, 4096), the partials being K nq 64 64 8 bytes ("full", nq =
+ *   nb (nb + 1) / 2, nb = ceil(D / 64)) or K D 8 bytes ("diag"): a function of (n, D, K, cov_type) alone, and the
+ *   covariance partials stay within 256 MiB.  nk = (sum_i r_ik: rows ascending in a slice, slices ascending) + 10 * 2^-52,
+ *   mean = (sum_i r_ik x_i, same order) / nk, weights = nk / (sum_k nk, k ascending).  Then a second pass around the NEW
+ *   mean: cov_k = (sum_i r_ik (x_i - mu_k)(x_i - mu_k)^T) / nk + reg_covar I; "full": upper triangle by
+ *   v_mfma_f64_16x16x4_f64, 32 rows at a time, four rows per k-step in ascending order, slices added in ascending order,
+ *   then mirrored; "diag": the diagonal of the same, rows ascending, product and sum rounded separately.
+ *   Precisions (_compute_precision_cholesky): cov = L L^T by right-looking column steps, P = L^-T by forward
+ *   substitution in ascending order, log det = sum_j log P_jj, b = mu^T P; "diag": P = 1 / sqrt(var).  A pivot (variance)
+ *   that is not finite and > 0 gives SC_ERR_ILLDEFINED (decided by a flag the host reads; the context stays usable).
+ *   E-step (_estimate_log_prob_resp): q_ik = sum_j ((x_i P_k)_j - b_kj)^2 ("diag": ((x_ij - mu_kj) P_kj)^2), log p_ik =
+ *   (-(D log 2 pi + q_ik) / 2 + log det_k) + log w_k; log-sum-exp as max + log sum_k exp(. - max), k ascending with Kahan's compensation;
+ *   responsibilities exp(log p - max) / that sum (sklearn's exp(log p - lse) without the rounding of lse, so that a
+ *   row adds up to 1 within a few ulp); label = the first largest log p.  The mean log-likelihood adds 256-row block sums
+ *   (rows ascending) in two levels: 256 runs of ceil(blocks / 256) consecutive blocks, each ascending, then the runs
+ *   ascending.
+ *   Loop (fit_predict): prev = -inf; per iteration E-step, M-step, lb = that E-step's mean log-likelihood; converged when
+ *   |lb - prev| < tol.  Runs go one after another; a later run replaces the best only on a strictly larger lb.
+ *   Out, per run r: weights_out[n_init][K], means_out[n_init][K][D], covariances_out[n_init][K][D][D] ("diag":
+ *   [n_init][K][D]), lower_bound_out, n_iter_out, converged_out [n_init]; *best_out.  For the best run: labels_out[n] and
+ *   (may be NULL) proba_out[n][K], from one more E-step under its final parameters, and *loglik_out, that E-step's mean
+ *   log-likelihood (sklearn's score(X), what bic and aic are made of).
+ * sc_mixture_predict -- that last E-step for any cells under given parameters: labels_out[n], proba_out[n][K] (may be
+ *   NULL), *loglik_out = the mean log-likelihood.  On the fitted cells and the fit's parameters it returns the fit's
+ *   labels and responsibilities byte for byte.  Weights must be finite and > 0, means and covariances finite.
+ * sc_mixture_slice_rows -- *rows_out = S, the rows per M-step slice sc_mixture_fit uses for this shape (host only, no
+ *   context, no HIP call): what the tests place n around.
+ * No floating-point atomics: every result is a function of the arguments alone, bit for bit. */
+#define SC_MIX_FULL 0
+#define SC_MIX_DIAG 1
+int sc_mixture_fit(sc_ctx *ctx, const void *X, int dtype, int64_t n, int32_t D, int32_t K, int32_t cov_type, int32_t n_init,
+                   int32_t km_max_iter, double km_tol, const double *x_mean, const double *uniforms, int32_t max_iter, double tol,
+                   double reg_covar, double *weights_out, double *means_out, double *covariances_out, double *lower_bound_out,
+                   int32_t *n_iter_out, int32_t *converged_out, int32_t *best_out, int32_t *labels_out, double *proba_out,
+                   double *loglik_out);
+int sc_mixture_predict(sc_ctx *ctx, const void *X, int dtype, int64_t n, int32_t D, int32_t K, int32_t cov_type, const double *weights,
+                       const double *means, const double *covariances, int32_t *labels_out, double *proba_out, double *loglik_out);
+int sc_mixture_slice_rows(int64_t n, int32_t D, int32_t K, int32_t cov_type, int64_t *rows_out);
 
 /* ---- multi-GPU: the path's one collective -------------------------------
  * The reference is single-process (n_jobs=1 hard-coded at AC:580; no collective anywhere).  Here genes shard across

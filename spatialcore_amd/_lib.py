@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SPATIALCORE_HIP_LIB: another build of the same library -- the sanitizer build of `make asan`, a build of another commit)
 LIB_PATH = os.environ.get("SPATIALCORE_HIP_LIB") or os.path.join(_HERE, "libspatialcore_hip.so")
 
-SC_OK, SC_ERR_INVALID, SC_ERR_STATE, SC_ERR_HIP, SC_ERR_NOMEM, SC_ERR_EMPTY = 0, 1, 2, 3, 4, 5
+SC_OK, SC_ERR_INVALID, SC_ERR_STATE, SC_ERR_HIP, SC_ERR_NOMEM, SC_ERR_EMPTY, SC_ERR_ILLDEFINED = 0, 1, 2, 3, 4, 5, 6
 SC_F32, SC_F64 = 0, 1
 K_MORAN_PERM, K_LAG, K_KNN, K_PERMGEN, K_LEE_PERM, K_PERM_SCAN, K_PERM_SWAP = 0, 1, 2, 3, 4, 5, 6
 K_KMEANS_SEED, K_KMEANS_LLOYD = 7, 8
@@ -35,6 +35,9 @@ K_LOUVAIN_MOVE, K_LOUVAIN_LEVEL = 39, 40
 K_NEIGHBORS_GRAM = 41
 K_UMAP_GRAPH, K_UMAP_LAYOUT = 42, 43
 K_HVG_SETUP, K_HVG_DENSE, K_HVG_SPARSE = 44, 45, 46
+K_MIX_ESTEP, K_MIX_MSTEP = 47, 48
+MIX_COVARIANCES = {"full": 0, "diag": 1}   # SC_MIX_FULL / SC_MIX_DIAG
+MIX_D_MAX, MIX_K_MAX, MIX_N_INIT_MAX = 256, 64, 10   # sc_mixture_fit's limits
 HOP_AGGREGATIONS = {"mean": 1, "var": 2}   # SC_HOP_MEAN / SC_HOP_VAR
 HOP_MAX, HOP_WAVE_KEYS, HOP_WG_KEYS = 64, 512, 16384   # SC_HOP_MAX, SC_HOP_WAVE_KEYS, SC_HOP_WG_KEYS
 HARMONY_ARRAYS = {"Zcorr": 0, "Zc": 1, "R": 2, "Y": 3, "O": 4, "W": 5, "order": 6, "dist": 7}   # sc_harmony_get's codes
@@ -170,6 +173,10 @@ SYMBOLS = {
     "sc_hop_aggregate": [_P, _P, c_int, c_int32, c_int32, _P],
     "sc_hop_times": [_P, _P],
     "sc_hop_end": [_P],
+    "sc_mixture_fit": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, _P, _P, c_int32, c_double,
+                       c_double, _P, _P, _P, _P, _P, _P, POINTER(c_int32), _P, _P, POINTER(c_double)],
+    "sc_mixture_predict": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, POINTER(c_double)],
+    "sc_mixture_slice_rows": [c_int64, c_int32, c_int32, c_int32, POINTER(c_int64)],
     "sc_louvain_begin": [_P, _P, _P, _P, c_int64, c_int32, c_int32],
     "sc_louvain_resident_weights": [_P, _P, c_int64],
     "sc_louvain_begin_resident": [_P, _P, c_int64, c_int32, c_int32],
@@ -232,9 +239,21 @@ def _check(rc: int) -> None:
     msg = load_library().sc_last_error().decode("utf-8", "replace")
     if rc in (SC_ERR_INVALID, SC_ERR_EMPTY):
         raise ValueError(msg)
+    if rc == SC_ERR_ILLDEFINED:   # sklearn's _compute_precision_cholesky message
+        raise ValueError("Fitting the mixture model failed because some components have ill-defined empirical covariance "
+                         "(for instance caused by singleton or collapsed samples). Try to decrease the number of components, "
+                         f"increase reg_covar, or scale the input data. ({msg})")
     if rc == SC_ERR_NOMEM:
         raise MemoryError(msg)
     raise SpatialCoreHipError(msg)
+
+
+def mixture_slice_rows(n: int, D: int, K: int, covariance_type: str = "full") -> int:
+    """sc_mixture_slice_rows: the rows per M-step slice of sc_mixture_fit, a function of the shape alone.  The library
+    states the rule once; no device is needed."""
+    rows = c_int64(0)
+    _check(load_library().sc_mixture_slice_rows(int(n), int(D), int(K), MIX_COVARIANCES[covariance_type], byref(rows)))
+    return rows.value
 
 
 def device_count() -> int:
@@ -921,6 +940,65 @@ class Context:
                                           _ptr(w), _ptr(mu), _ptr(var), _ptr(hi), hi.size, float(cutoff), _ptr(prob),
                                           _ptr(lab), byref(nh)))
         return prob, lab, nh.value
+
+    # ---- Gaussian mixtures (extension) --------------------------------------------------------
+    @staticmethod
+    def _mixture_input(X, who: str) -> np.ndarray:
+        X = np.ascontiguousarray(X)
+        if X.dtype not in (np.float32, np.float64) or X.ndim != 2:
+            raise ValueError(f"{who}: X must be a 2-D float32 or float64 array, got {X.dtype} {X.shape}")
+        return X
+
+    def mixture_fit(self, X, n_components: int, covariance_type: str, n_init: int, km_max_iter: int, km_tol: float, x_mean,
+                    uniforms, max_iter: int = 100, tol: float = 1e-3, reg_covar: float = 1e-6, return_proba: bool = False) -> dict:
+        """sc_mixture_fit: every run's ``weights`` (n_init, K), ``means`` (n_init, K, D), ``covariances`` (n_init, K, D, D) or
+        (n_init, K, D), ``lower_bound``, ``n_iter``, ``converged``; ``best``; the best run's ``labels``, ``loglik`` (the mean log-likelihood
+        under its final parameters) and, on request, ``proba`` (n, K)."""
+        X = self._mixture_input(X, "mixture_fit")
+        n, D = X.shape
+        K, R = int(n_components), int(n_init)
+        full = MIX_COVARIANCES[covariance_type] == 0
+        xm = u = None
+        if K > 1:
+            xm = _c(np.asarray(x_mean).reshape(-1), np.float64)
+            u = _c(uniforms, np.float64)
+            L = 2 + int(np.log(K))
+            if xm.size != D or u.size != R * (1 + (K - 1) * L):
+                raise ValueError("mixture_fit: x_mean must have D entries and uniforms n_init * (1 + (K - 1) * L)")
+        R1, K1 = max(R, 1), max(K, 1)
+        w = np.empty((R1, K1), dtype=np.float64)
+        mu = np.empty((R1, K1, D), dtype=np.float64)
+        cov = np.empty((R1, K1, D, D) if full else (R1, K1, D), dtype=np.float64)
+        lb = np.empty(R1, dtype=np.float64)
+        n_iter = np.empty(R1, dtype=np.int32)
+        conv = np.empty(R1, dtype=np.int32)
+        labels = np.empty(n, dtype=np.int32)
+        proba = np.empty((n, K1), dtype=np.float64) if return_proba else None
+        best, ll = c_int32(0), c_double(0.0)
+        _check(self._lib.sc_mixture_fit(self._h, _ptr(X), SC_F32 if X.dtype == np.float32 else SC_F64, n, D, K,
+                                        MIX_COVARIANCES[covariance_type], R, int(km_max_iter), float(km_tol), _ptr(xm), _ptr(u),
+                                        int(max_iter), float(tol), float(reg_covar), _ptr(w), _ptr(mu), _ptr(cov), _ptr(lb),
+                                        _ptr(n_iter), _ptr(conv), byref(best), _ptr(labels), _ptr(proba), byref(ll)))
+        return {"weights": w, "means": mu, "covariances": cov, "lower_bound": lb, "n_iter": n_iter,
+                "converged": conv.astype(bool), "best": best.value, "labels": labels, "proba": proba, "loglik": ll.value}
+
+    def mixture_predict(self, X, covariance_type: str, weights, means, covariances, return_proba: bool = False):
+        """sc_mixture_predict: (labels int32, responsibilities (n, K) float64 or None, mean log-likelihood)."""
+        X = self._mixture_input(X, "mixture_predict")
+        n, D = X.shape
+        w, mu, cov = _c(weights, np.float64), _c(means, np.float64), _c(covariances, np.float64)
+        K = w.size
+        want = (K, D, D) if MIX_COVARIANCES[covariance_type] == 0 else (K, D)
+        if w.ndim != 1 or mu.shape != (K, D) or cov.shape != want:
+            raise ValueError(f"mixture_predict: need weights (K,), means (K, {D}) and covariances {want}, got {w.shape}, "
+                             f"{mu.shape} and {cov.shape}")
+        labels = np.empty(n, dtype=np.int32)
+        proba = np.empty((n, K), dtype=np.float64) if return_proba else None
+        ll = c_double(0.0)
+        _check(self._lib.sc_mixture_predict(self._h, _ptr(X), SC_F32 if X.dtype == np.float32 else SC_F64, n, D, K,
+                                            MIX_COVARIANCES[covariance_type], _ptr(w), _ptr(mu), _ptr(cov), _ptr(labels),
+                                            _ptr(proba), byref(ll)))
+        return labels, proba, ll.value
 
     # ---- N12 (extension): NMF ---------------------------------------------------------------
     def nmf_fit(self, indptr, indices, data, n_genes: int, W0, H0, loss: str, update_H: bool = True, max_iter: int = 200,

@@ -152,7 +152,7 @@ KernelTimerScope::~KernelTimerScope()
 int sc_timer_collect(sc_ctx *c)
 {
     SC_TRY(c->streams.sync(SR_MASK_PIPELINE));
-    for (int k = 0; k < SC_K_COUNT_; ++k) {
+    for (int k = 0; k < SC_K_END_; ++k) {
         KTimer &t = c->timers[k];
         for (auto &ev : t.pending) {
             float ms = 0.f;
@@ -254,7 +254,7 @@ int sc_debug_copy(sc_ctx *c, int which, int64_t offset, void *out, int64_t bytes
 int sc_ctx_kernel_time(sc_ctx *c, int kernel_id, double *ms, int64_t *launches)
 {
     SC_REQUIRE(c, SC_ERR_INVALID, "null context");
-    SC_REQUIRE(kernel_id >= 0 && kernel_id < SC_K_COUNT_, SC_ERR_INVALID, "bad kernel id %d", kernel_id);
+    SC_REQUIRE(kernel_id >= 0 && kernel_id < SC_K_END_, SC_ERR_INVALID, "bad kernel id %d", kernel_id);
     SC_TRY(sc_timer_collect(c));
     if (ms) *ms = c->timers[kernel_id].ms;
     if (launches) *launches = c->timers[kernel_id].launches;
@@ -265,7 +265,7 @@ int sc_ctx_reset_timers(sc_ctx *c)
 {
     SC_REQUIRE(c, SC_ERR_INVALID, "null context");
     SC_TRY(sc_timer_collect(c));
-    for (int k = 0; k < SC_K_COUNT_; ++k) {
+    for (int k = 0; k < SC_K_END_; ++k) {
         c->timers[k].ms = 0.0;
         c->timers[k].launches = 0;
     }

@@ -181,7 +181,7 @@ struct sc_ctx {
     hipStream_t &stream_px = streams.s[SR_EXPAND];     // the generator verifies + expands a finished chunk here, beside the next chunk's chain
     hipStream_t *const stream_pg = streams.s + SR_PREP0;   // [4]: its preparation streams
     bool timing = true;
-    KTimer timers[SC_K_COUNT_];
+    KTimer timers[SC_K_END_];
     PermGen pg;       // the numpy-exact permutation generator's state
     sc_ctx();         // (sc_api.hip, where PermPipe is complete)
     ~sc_ctx();
