@@ -2,7 +2,7 @@
 truncated to d = 20, 32, 40, 50, 64, k = 15.  Per d: sc_knn_dense (path 1) once and the certified Gram-form filter
 (path 2) three times, with the `info` counts of every run and a digest of the lists (the two paths must agree); what
 path 0 picks.  Then pca (50) -> neighbors -> louvain(graph="connectivities") and diffusion_map(graph="connectivities")
-against the two calls with graph=None, each of which searches for itself.
+against the two calls with graph=None, each of which runs the same search and graph step again.
 
 Every GPU step is a child process under its own time limit (the path 1 limits are sized from the 57 s on record at 50
 features: three times the time scaled by d / 50); a step that fails or runs out of time ends the probe.  Writes

@@ -1,5 +1,6 @@
-"""The cell-cell graphs of the spatial modules: the coordinates, a caller's graph, and the symmetric union of the exact
-kNN lists that ``fit_spatial_nmf`` (nmf/spatial.py) and ``aggregate_neighbors`` (spatial/hops.py) build by default."""
+"""The cell-cell graphs of the spatial modules: the coordinates and the symmetric union of the exact kNN lists that
+``fit_spatial_nmf`` (nmf/spatial.py) and ``aggregate_neighbors`` (spatial/hops.py) build by default.  A caller's own graph
+is read by _cell_graph.py."""
 
 from __future__ import annotations
 
@@ -7,8 +8,6 @@ from typing import Optional
 
 import numpy as np
 from scipy import sparse
-
-from spatialcore_amd.cluster.communities import symmetric_graph
 
 K_NEIGHBORS_MAX = 65536   # sc_knn_2d's limit
 
@@ -23,20 +22,6 @@ def _coordinates(adata, spatial_key) -> np.ndarray:
     if not np.all(np.isfinite(xy)):
         raise ValueError(f"adata.obsm[{spatial_key!r}] contains NaN or infinite values")
     return xy
-
-
-def _given_graph(adata, graph, n: int):
-    """The caller's graph without its diagonal, validated as the communities module validates one."""
-    source = f"obsp[{graph!r}]" if isinstance(graph, str) else "matrix"
-    if isinstance(graph, str):
-        if graph not in adata.obsp:
-            raise ValueError(f"graph={graph!r} is not an entry of adata.obsp (available: {sorted(adata.obsp)})")
-        graph = adata.obsp[graph]
-    if sparse.issparse(graph) and graph.ndim == 2 and graph.shape == (n, n):
-        coo = sparse.coo_matrix(graph)
-        off = coo.row != coo.col
-        graph = sparse.csr_matrix((coo.data[off], (coo.row[off], coo.col[off])), shape=(n, n))
-    return symmetric_graph(adata, graph, n), source
 
 
 def union_of_knn(lists: np.ndarray, rows: Optional[np.ndarray], n: int) -> sparse.csr_matrix:

@@ -12,12 +12,12 @@ import numbers
 
 import numpy as np
 import pandas as pd
-from scipy import sparse
 
 from spatialcore_amd import _lib
+from spatialcore_amd._cell_graph import symmetric_graph      # its name stays importable from here
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
-from spatialcore_amd.diffusion.maps import K_MAX, _representation
+from spatialcore_amd._rep_graph import K_MAX, _check_key, representation, resident_graph
 
 logger = get_logger("cluster")
 
@@ -46,55 +46,13 @@ def quantise_weights(w):
     return q.astype(np.uint16), w_max / Q_MAX
 
 
-def symmetric_graph(adata, graph, n: int) -> sparse.csr_matrix:
-    """The caller's graph as a canonical float64 CSR: n x n, finite, positive, symmetric in structure and value.  A failure
-    of the symmetry names the first offending entry in row order."""
-    if isinstance(graph, str):
-        if graph not in adata.obsp:
-            raise ValueError(f"graph={graph!r} is not an entry of adata.obsp (available: {sorted(adata.obsp)})")
-        graph = adata.obsp[graph]
-    if not sparse.issparse(graph):
-        raise ValueError("graph must be None, the name of an adata.obsp entry or a scipy sparse matrix")
-    if graph.ndim != 2 or graph.shape != (n, n):
-        raise ValueError(f"graph must be {n} x {n} (cells x cells), got {graph.shape}")
-    if np.issubdtype(graph.dtype, np.complexfloating):
-        raise ValueError("graph must be real")
-    A = sparse.csr_matrix(graph, dtype=np.float64, copy=True)
-    A.sum_duplicates()
-    A.sort_indices()
-    if A.nnz > 2**31 - 1:
-        raise ValueError("at most 2^31 - 1 stored entries are supported")
-    if A.nnz and not np.all(np.isfinite(A.data)):
-        bad = int(np.flatnonzero(~np.isfinite(A.data))[0])
-        raise ValueError(f"graph contains NaN or infinite values (first: stored entry {bad})")
-    if A.nnz and A.data.min() <= 0:
-        bad = int(np.flatnonzero(A.data <= 0)[0])
-        row = int(np.searchsorted(A.indptr, bad, side="right") - 1)
-        raise ValueError(f"graph must be positive: entry ({row}, {int(A.indices[bad])}) is {float(A.data[bad])!r}")
-    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(A.indptr))
-    T = A.T.tocsr()
-    T.sort_indices()
-    if T.nnz != A.nnz or not np.array_equal(T.indptr, A.indptr) or not np.array_equal(T.indices, A.indices):
-        here = rows * n + A.indices
-        there = np.repeat(np.arange(n, dtype=np.int64), np.diff(T.indptr)) * n + T.indices
-        bad = int(np.flatnonzero(~np.isin(here, there))[0])    # as many entries either way: one of A's has no mirror
-        raise ValueError(f"graph must be symmetric: entry ({int(rows[bad])}, {int(A.indices[bad])}) is stored, "
-                         f"({int(A.indices[bad])}, {int(rows[bad])}) is not")
-    if not np.array_equal(T.data, A.data):
-        bad = int(np.flatnonzero(T.data != A.data)[0])
-        raise ValueError(f"graph must be symmetric: entry ({int(rows[bad])}, {int(A.indices[bad])}) is {float(A.data[bad])!r}, "
-                         f"({int(A.indices[bad])}, {int(rows[bad])}) is {float(T.data[bad])!r}")
-    return A
-
-
 def _check_arguments(resolution, weights, max_rounds, key_added, copy) -> int:
     g = resolution_units(resolution)
     if weights not in WEIGHTS:
         raise ValueError(f"weights must be one of {WEIGHTS}, got {weights!r}")
     if not isinstance(max_rounds, numbers.Integral) or isinstance(max_rounds, bool) or not 1 <= max_rounds <= 2**31 - 1:
         raise ValueError(f"max_rounds must be an integer in 1..2^31 - 1, got {max_rounds!r}")
-    if not isinstance(key_added, str) or not key_added:
-        raise ValueError(f"key_added must be a non-empty string, got {key_added!r}")
+    _check_key("key_added", key_added)
     if not isinstance(copy, (bool, np.bool_)):
         raise ValueError(f"copy must be True or False, got {copy!r}")
     return g
@@ -117,7 +75,8 @@ def louvain(adata, resolution: float = 1.0, *, graph=None, use_rep: str = "X_pca
     """Unsupervised graph clustering of the cells: Louvain modularity optimisation with a connectivity split, on the GPU.
 
     ``graph=None`` builds the exact ``n_neighbors``-nearest-neighbour graph of ``obsm[use_rep]`` (at most 64 columns,
-    2 <= ``n_neighbors`` <= 32) and its symmetric union with ``diffusion_map``'s kernel weights; ``weights="binary"`` gives
+    2 <= ``n_neighbors`` <= 32) and its symmetric union with ``diffusion_map``'s kernel weights, by the search and the
+    graph of ``neighbors`` (spatialcore_amd/_rep_graph.py): what ``graph="connectivities"`` reads back; ``weights="binary"`` gives
     every edge of that union the weight 1.  ``graph`` may instead name an ``obsp`` entry or be a scipy sparse matrix:
     cells x cells, finite, positive, symmetric in structure and value (diagonal entries are legal, empty rows and several
     components too); ``use_rep``, ``n_neighbors`` and ``weights="kernel"`` are then ignored, ``weights="binary"`` still
@@ -139,7 +98,7 @@ def louvain(adata, resolution: float = 1.0, *, graph=None, use_rep: str = "X_pca
     else:
         if not isinstance(n_neighbors, numbers.Integral) or isinstance(n_neighbors, bool) or not 2 <= n_neighbors <= K_MAX:
             raise ValueError(f"n_neighbors must be an integer in 2..{K_MAX}, got {n_neighbors!r}")
-        R = _representation(adata, use_rep)
+        R = representation(adata, use_rep)
         if n <= n_neighbors:
             raise ValueError(f"n_neighbors={n_neighbors} needs more than {n_neighbors} cells, got {n}")
     ctx = _lib.default_context(device)
@@ -148,8 +107,7 @@ def louvain(adata, resolution: float = 1.0, *, graph=None, use_rep: str = "X_pca
             ctx.louvain_begin(A.indptr, A.indices, q, g, int(max_rounds))
             n_edges = int(A.nnz)
         else:
-            ctx.knn_dense(R, int(n_neighbors), fetch=False)
-            n_edges = int(ctx.diffmap_graph()["n_edges"])
+            n_edges = resident_graph(ctx, R, int(n_neighbors))["n_edges"]
             if weights == "binary":
                 q, scale = None, 1.0
             else:

@@ -18,9 +18,9 @@ import numpy as np
 import pandas as pd
 
 from spatialcore_amd import _lib
+from spatialcore_amd._kmeans_draws import kmeans_draws
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
-from spatialcore_amd.spatial.neighborhoods import kmeans_draws
 
 logger = get_logger("mixture")
 

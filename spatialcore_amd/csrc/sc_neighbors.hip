@@ -540,19 +540,40 @@ int dk_end(sc_ctx *c, int64_t n, int dp, int k, int32_t *idx_out, double *d2_out
     return SC_OK;
 }
 
+// what the two entry points share once each has checked its own arguments: the finite check, the upload, the search
+// (path 0: the size rule's choice; 1: the direct kernels over `splits` candidate ranges; 2: the filter with `slack` spare
+// list entries), the lists out; info_out (may be null): path taken, list length, rows certified, rows through the fallback
+int dk_search(const char *who, sc_ctx *c, const void *X, int dtype, int64_t n, int d, int k, int path, int splits, int slack,
+              int32_t *idx_out, double *d2_out, int64_t *info_out)
+{
+    SC_TRY(dk_check_finite(who, X, dtype, n * d));
+    const int dp = (int)align_up64(d, 8);
+    if (path == 0) path = (dp > 32 && n >= NB_GRAM_FROM_WIDE) || (dp >= 24 && n >= NB_GRAM_FROM) ? 2 : 1;
+    const int L = path == 1 ? k : k + (slack ? slack : NB_SLACK_DEFAULT);
+    int64_t nrows = 0;
+    SC_TRY(dk_begin(c, X, dtype, n, d, k));
+    if (path == 1) SC_TRY(dk_direct(c, n, dp, k, splits));
+    else SC_TRY(nb_filtered(c, n, dp, k, L, &nrows));
+    SC_TRY(dk_end(c, n, dp, k, idx_out, d2_out));
+    if (info_out) {
+        info_out[0] = path;
+        info_out[1] = L;
+        info_out[2] = path == 1 ? 0 : n - nrows;
+        info_out[3] = nrows;
+    }
+    return SC_OK;
+}
+
 }  // namespace
 
+// an entry point: the shared gate, the refusals of its own arguments, the shared body -- the order a call is refused in
 extern "C" int sc_knn_dense(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t d, int32_t k, int32_t splits, int32_t *idx_out,
                             double *d2_out)
 {
     const char *who = "sc_knn_dense";
     SC_TRY(dk_check(who, c, X, dtype, n, d, k));
     SC_REQUIRE(splits >= 0 && splits <= 65535, SC_ERR_INVALID, "%s: need 0 <= splits <= 65535, got %d", who, splits);
-    SC_TRY(dk_check_finite(who, X, dtype, n * d));
-    const int dp = (int)align_up64(d, 8);
-    SC_TRY(dk_begin(c, X, dtype, n, d, k));
-    SC_TRY(dk_direct(c, n, dp, k, splits));
-    return dk_end(c, n, dp, k, idx_out, d2_out);
+    return dk_search(who, c, X, dtype, n, d, k, 1, splits, 0, idx_out, d2_out, nullptr);
 }
 
 extern "C" int sc_knn_dense_gram(sc_ctx *c, const void *X, int dtype, int64_t n, int32_t d, int32_t k, int32_t path, int32_t slack,
@@ -564,18 +585,5 @@ extern "C" int sc_knn_dense_gram(sc_ctx *c, const void *X, int dtype, int64_t n,
     SC_REQUIRE(path >= 0 && path <= 2, SC_ERR_INVALID, "%s: path must be 0 (the library's choice), 1 (direct) or 2 (Gram filter), got %d", who,
                path);
     SC_REQUIRE(slack >= 0 && slack <= NB_SLACK_MAX, SC_ERR_INVALID, "%s: need 0 <= slack <= %d, got %d", who, NB_SLACK_MAX, slack);
-    SC_TRY(dk_check_finite(who, X, dtype, n * d));
-    const int dp = (int)align_up64(d, 8);
-    if (path == 0) path = (dp > 32 && n >= NB_GRAM_FROM_WIDE) || (dp >= 24 && n >= NB_GRAM_FROM) ? 2 : 1;
-    const int L = path == 1 ? k : k + (slack ? slack : NB_SLACK_DEFAULT);
-    int64_t nrows = 0;
-    SC_TRY(dk_begin(c, X, dtype, n, d, k));
-    if (path == 1) SC_TRY(dk_direct(c, n, dp, k, 0));
-    else SC_TRY(nb_filtered(c, n, dp, k, L, &nrows));
-    SC_TRY(dk_end(c, n, dp, k, idx_out, d2_out));
-    info_out[0] = path;
-    info_out[1] = L;
-    info_out[2] = path == 1 ? 0 : n - nrows;
-    info_out[3] = nrows;
-    return SC_OK;
+    return dk_search(who, c, X, dtype, n, d, k, path, 0, slack, idx_out, d2_out, info_out);
 }

@@ -1,9 +1,10 @@
 """diffusion_map / diffusion_pseudotime.
 
 The neighbour search, the kernel matrix, its normalisation, the connected components and every Lanczos step run in HIP,
-in fp64 and in one documented summation order (sc_knn_dense, sc_diffmap_graph, sc_lanczos_*); the host checks the
-arguments, solves the small tridiagonal eigenproblem between batches of steps and applies the sign rule.  There is no CPU
-fallback.  Pseudotime is O(cells x components) on a stored map and runs in numpy."""
+in fp64 and in one documented summation order (sc_knn_dense_gram and sc_diffmap_graph through _rep_graph.py, the path
+``neighbors`` takes; sc_lanczos_*); the host checks the arguments, solves the small tridiagonal eigenproblem between
+batches of steps and applies the sign rule.  There is no CPU fallback.  Pseudotime is O(cells x components) on a stored
+map and runs in numpy."""
 
 from __future__ import annotations
 
@@ -15,77 +16,16 @@ from scipy import sparse
 from scipy.linalg import eigh_tridiagonal
 
 from spatialcore_amd import _lib
+from spatialcore_amd._cell_graph import kernel_matrix
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
+from spatialcore_amd._rep_graph import (COMPS_MAX, COMPS_MIN, _SUPPORTED, _check_key, _is_int, check_n_neighbors, representation,
+                                        resident_graph)
 
 logger = get_logger("diffusion")
 
-D_MAX = 64
-K_MIN, K_MAX = 2, 32
-COMPS_MIN, COMPS_MAX = 2, 64
 BASIS_DEFAULT = 1024
 CHECK_EVERY = 16          # Lanczos steps between two solutions of the tridiagonal problem
-_SUPPORTED = (f"a finite float32 or float64 representation with 1..{D_MAX} columns, {K_MIN} <= n_neighbors <= {K_MAX}, "
-              f"{COMPS_MIN} <= n_comps <= {COMPS_MAX}, both below the number of cells, one connected graph")
-
-
-def _is_int(v) -> bool:
-    return isinstance(v, numbers.Integral) and not isinstance(v, bool)
-
-
-def _check_key(name: str, value) -> str:
-    if not isinstance(value, str) or not value:
-        raise ValueError(f"{name} must be a non-empty string, got {value!r}")
-    return value
-
-
-def _representation(adata, use_rep) -> np.ndarray:
-    if not isinstance(use_rep, str) or use_rep not in adata.obsm:
-        raise ValueError(f"use_rep={use_rep!r} is not an entry of adata.obsm (available: {sorted(adata.obsm)}); "
-                         f"supported: {_SUPPORTED}")
-    R = adata.obsm[use_rep]
-    R = R.toarray() if sparse.issparse(R) else np.asarray(getattr(R, "values", R))
-    if R.ndim != 2 or R.dtype == object or not (np.issubdtype(R.dtype, np.number) or R.dtype == bool) \
-            or np.issubdtype(R.dtype, np.complexfloating):
-        raise ValueError(f"obsm[{use_rep!r}] must be a real 2-D array, got shape {R.shape} of {R.dtype}; supported: {_SUPPORTED}")
-    if not 1 <= R.shape[1] <= D_MAX:
-        raise ValueError(f"obsm[{use_rep!r}] has {R.shape[1]} columns; supported: {_SUPPORTED}")
-    if R.dtype not in (np.float32, np.float64):
-        R = R.astype(np.float64)
-    R = np.ascontiguousarray(R)
-    if not np.all(np.isfinite(R)):
-        raise ValueError(f"obsm[{use_rep!r}] contains NaN or infinite values; supported: {_SUPPORTED}")
-    if R.size and np.abs(R).max() >= 2.0 ** 500:
-        raise ValueError(f"obsm[{use_rep!r}] holds values of magnitude 2^500 or more, whose squared distances overflow")
-    return R
-
-
-def _kernel_matrix(adata, graph, n: int) -> sparse.csr_matrix:
-    """The caller's kernel matrix as a canonical float64 CSR: n x n, symmetric, positive stored values, no empty row."""
-    if isinstance(graph, str):
-        if graph not in adata.obsp:
-            raise ValueError(f"graph={graph!r} is not an entry of adata.obsp (available: {sorted(adata.obsp)})")
-        graph = adata.obsp[graph]
-    if not sparse.issparse(graph):
-        raise ValueError("graph must be the name of an adata.obsp entry or a scipy sparse matrix")
-    if graph.shape != (n, n):
-        raise ValueError(f"graph must be {n} x {n} (cells x cells), got {graph.shape}")
-    if np.issubdtype(graph.dtype, np.complexfloating):
-        raise ValueError("graph must be real")
-    A = sparse.csr_matrix(graph, dtype=np.float64, copy=True)
-    A.sum_duplicates()
-    if A.nnz and not np.all(np.isfinite(A.data)):
-        raise ValueError("graph contains NaN or infinite values")
-    if A.nnz and A.data.min() < 0:
-        raise ValueError("graph must be non-negative")
-    A.eliminate_zeros()
-    A.sort_indices()
-    if (A != A.T).nnz:
-        raise ValueError("graph must be symmetric (it is the kernel matrix of an undirected graph)")
-    empty = np.flatnonzero(np.diff(A.indptr) == 0)
-    if empty.size:
-        raise ValueError(f"graph has {empty.size} empty rows (first: {int(empty[0])}): every cell needs a neighbour")
-    return A
 
 
 def _sign(vecs: np.ndarray) -> np.ndarray:
@@ -159,12 +99,10 @@ def diffusion_map(adata, use_rep: str = "X_nmf", n_neighbors: int = 15, n_comps:
         raise ValueError(f"random_state must be an integer in [0, 2^32), got {random_state!r}")
     A = R = None
     if graph is not None:
-        A = _kernel_matrix(adata, graph, n)
+        A = kernel_matrix(adata, graph, n)
     else:
-        if not _is_int(n_neighbors) or not K_MIN <= n_neighbors <= K_MAX or n_neighbors >= n:
-            raise ValueError(f"n_neighbors must be an integer in {K_MIN}..{K_MAX} and below the {n} cells, got "
-                             f"{n_neighbors!r}; supported: {_SUPPORTED}")
-        R = _representation(adata, use_rep)
+        check_n_neighbors(n_neighbors, n)
+        R = representation(adata, use_rep)
 
     ctx = _lib.default_context(device)
     if A is not None:
@@ -172,8 +110,7 @@ def diffusion_map(adata, use_rep: str = "X_nmf", n_neighbors: int = 15, n_comps:
         n_components, n_edges = ctx.diffmap_graph_csr(A.indptr, A.indices, A.data), int(A.nnz)
     else:
         logger.info(f"diffusion map: {n:,} cells x {R.shape[1]} features, {n_neighbors} neighbours, {n_comps} components")
-        ctx.knn_dense(R, int(n_neighbors), fetch=False)
-        info = ctx.diffmap_graph()
+        info = resident_graph(ctx, R, int(n_neighbors))
         n_components, n_edges = info["n_components"], info["n_edges"]
     if n_components != 1:
         raise ValueError(f"the neighbour graph has {n_components} connected components; a diffusion map needs one "

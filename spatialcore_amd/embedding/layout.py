@@ -18,9 +18,9 @@ import numpy as np
 from scipy import sparse
 
 from spatialcore_amd import _lib
+from spatialcore_amd._cell_graph import symmetric_graph
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
-from spatialcore_amd.cluster.communities import symmetric_graph
 
 logger = get_logger("embedding")
 

@@ -28,6 +28,7 @@ from scipy import sparse
 
 from spatialcore_amd import _lib
 from spatialcore_amd._batches import batch_groups
+from spatialcore_amd._kmeans_draws import kmeans_draws
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
 
@@ -102,8 +103,6 @@ def unit_rows(Z) -> np.ndarray:
 def kmeans_start(ctx, Zc, nclust: int, n_init: int, random_state) -> np.ndarray:
     """The starting centres: sc_kmeans_fit on the unit rows with the draws of ``RandomState(random_state)``, as
     identify_niches supplies them."""
-    from spatialcore_amd.spatial.neighborhoods import kmeans_draws
-
     tol = float(np.mean(np.var(Zc, axis=0)) * 1e-4)
     fit = ctx.kmeans(Zc, nclust, n_init, KMEANS_MAX_ITER, tol, Zc.mean(axis=0), kmeans_draws(random_state, n_init, nclust))
     centres = np.asarray(fit["centers"], dtype=np.float64)

@@ -15,7 +15,7 @@ from scipy import sparse
 from spatialcore_amd import _lib
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
-from spatialcore_amd.diffusion.maps import K_MAX, K_MIN, _SUPPORTED, _check_key, _is_int, _representation
+from spatialcore_amd._rep_graph import _check_key, check_n_neighbors, representation, resident_graph
 
 logger = get_logger("neighbors")
 
@@ -32,7 +32,8 @@ def neighbors(adata, n_neighbors: int = 15, use_rep: str = "X_pca", *, method: s
     (its ``n_neighbors=16`` is ``n_neighbors=15`` here).  ``use_rep`` names a float32 / float64 (anything else is
     converted to float64) finite ``obsm`` entry with 1..64 columns; 2 <= ``n_neighbors`` <= 32 and below the number of
     cells.  The neighbours of a cell are the ``n_neighbors`` other cells smallest in (squared distance, index), the
-    squared distance added in column order in fp64: the lists ``louvain`` and ``diffusion_map`` search for themselves.
+    squared distance added in column order in fp64: the lists ``louvain(graph=None)`` and ``diffusion_map(graph=None)``
+    build on too, through the same search (spatialcore_amd/_rep_graph.py).
 
     Writes ``obsp["distances"]`` (float64 CSR, exactly ``n_neighbors`` stored entries per row, columns sorted, values
     ``sqrt(d2)``; a zero distance is an explicit stored entry), ``obsp["connectivities"]`` (the symmetric union of the
@@ -54,19 +55,13 @@ def neighbors(adata, n_neighbors: int = 15, use_rep: str = "X_pca", *, method: s
     if method not in METHODS:
         raise ValueError(f"method must be one of {METHODS}, got {method!r}")
     n = int(adata.n_obs)
-    if not _is_int(n_neighbors) or not K_MIN <= n_neighbors <= K_MAX or n_neighbors >= n:
-        raise ValueError(f"n_neighbors must be an integer in {K_MIN}..{K_MAX} and below the {n} cells, got "
-                         f"{n_neighbors!r}; supported: {_SUPPORTED}")
-    R = _representation(adata, use_rep)
-    k = int(n_neighbors)
+    k = check_n_neighbors(n_neighbors, n)
+    R = representation(adata, use_rep)
 
     ctx = _lib.default_context(device)
     logger.info(f"neighbors: {n:,} cells x {R.shape[1]} features, {k} neighbours")
-    idx, d2, search = ctx.knn_dense_gram(R, k)
-    if method == "umap":
-        ctx.fuzzy_graph()
-    else:
-        ctx.diffmap_graph()      # a zero local scale raises here, before anything is written
+    found = resident_graph(ctx, R, k, method, fetch=True)      # a zero local scale raises here, before anything is written
+    idx, d2, search = found["idx"], found["d2"], found["search"]
     indptr, indices, w = ctx.diffmap_graph_get()
     logger.info(f"neighbors: path {search['path']}, {search['rows_fallback']:,} rows through the exact fallback, "
                 f"{indices.size:,} stored connectivities")

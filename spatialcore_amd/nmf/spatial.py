@@ -16,9 +16,10 @@ import numpy as np
 
 from spatialcore_amd import _lib
 from spatialcore_amd._batches import batch_groups
+from spatialcore_amd._cell_graph import given_graph as _given_graph      # its earlier name stays importable from here
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._sparse_input import gene_columns
-from spatialcore_amd._spatial_graph import K_NEIGHBORS_MAX, _coordinates, _given_graph, knn_union_graph
+from spatialcore_amd._spatial_graph import K_NEIGHBORS_MAX, _coordinates, knn_union_graph
 from spatialcore_amd._spatial_graph import union_of_knn  # noqa: F401  (its name stays importable from here)
 from spatialcore_amd.nmf import factorize
 

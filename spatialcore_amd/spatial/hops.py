@@ -12,10 +12,10 @@ import numbers
 from typing import Optional, Sequence, Union
 
 import numpy as np
-from scipy import sparse
 
 from spatialcore_amd import _lib
 from spatialcore_amd._batches import batch_groups
+from spatialcore_amd._cell_graph import pattern_graph      # its name stays importable from here
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
 from spatialcore_amd._spatial_graph import K_NEIGHBORS_MAX, _coordinates, knn_union_graph
@@ -63,27 +63,6 @@ def _representation(adata, use_rep) -> np.ndarray:
     if not np.all(np.isfinite(X)):
         raise ValueError(f"adata.obsm[{use_rep!r}] contains NaN or infinite values")
     return np.ascontiguousarray(X)
-
-
-def pattern_graph(adata, graph, n: int):
-    """A caller's graph as the pattern the shells are taken on: any square pattern, directed or not; weights are ignored,
-    the diagonal and stored zeros are dropped.  Canonical CSR (int64 indptr, int32 indices) and its source."""
-    source = f"obsp[{graph!r}]" if isinstance(graph, str) else "matrix"
-    if isinstance(graph, str):
-        if graph not in adata.obsp:
-            raise ValueError(f"connectivity_key={graph!r} is not an entry of adata.obsp (available: {sorted(adata.obsp)})")
-        graph = adata.obsp[graph]
-    if not sparse.issparse(graph):
-        raise ValueError(f"connectivity_key must be None, the name of an adata.obsp entry or a scipy sparse matrix, got {type(graph).__name__}")
-    if graph.ndim != 2 or graph.shape != (n, n):
-        raise ValueError(f"the graph ({source}) must be cells x cells = ({n}, {n}), got {graph.shape}")
-    coo = sparse.coo_matrix(graph)
-    keep = (coo.row != coo.col) & (coo.data != 0)
-    A = sparse.csr_matrix((np.ones(int(keep.sum())), (coo.row[keep], coo.col[keep])), shape=(n, n))
-    A.sum_duplicates()     # an entry stored twice is one entry
-    A.sort_indices()
-    A.data[:] = 1.0
-    return A, source
 
 
 def _sample_codes(adata, sample_key) -> np.ndarray:

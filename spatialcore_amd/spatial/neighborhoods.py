@@ -22,6 +22,7 @@ import numpy as np
 import pandas as pd
 
 from spatialcore_amd import _lib
+from spatialcore_amd._kmeans_draws import kmeans_draws      # its name stays importable from here
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
 
@@ -1090,25 +1091,6 @@ def _niche_request_problem(adata, n_niches, method, neighborhood_key) -> Optiona
     if n_niches > adata.n_obs:
         return f"n_niches ({n_niches}) cannot exceed number of cells ({adata.n_obs})"
     return None
-
-
-def kmeans_draws(random_state, n_init: int, n_clusters: int) -> np.ndarray:
-    """Every draw of sklearn's k-means++ over ``n_init`` runs of ONE ``check_random_state(random_state)``: per run the
-    ``random_sample()`` of the first centre's ``choice`` and ``uniform(size=L)`` for each later centre,
-    L = 2 + int(log(K)).  The stream does not depend on the data, so it is drawn here up front."""
-    if random_state is None:
-        rs = np.random.mtrand._rand
-    elif isinstance(random_state, np.random.RandomState):
-        rs = random_state
-    else:
-        rs = np.random.RandomState(random_state)
-    L = 2 + int(np.log(n_clusters))
-    out = np.empty((n_init, 1 + (n_clusters - 1) * L), dtype=np.float64)
-    for r in range(n_init):
-        out[r, 0] = rs.random_sample()
-        for c in range(n_clusters - 1):
-            out[r, 1 + c * L:1 + (c + 1) * L] = rs.uniform(size=L)
-    return out
 
 
 def identify_niches(

@@ -16,9 +16,9 @@ from typing import List, Optional, Union
 import numpy as np
 
 from spatialcore_amd import _lib
+from spatialcore_amd._kmeans_draws import kmeans_draws
 from spatialcore_amd._logging import get_logger
 from spatialcore_amd._metadata import update_metadata
-from spatialcore_amd.spatial.neighborhoods import kmeans_draws
 
 logger = get_logger(__name__.replace("spatialcore_amd.", ""))
 

@@ -122,6 +122,11 @@ def lattice(n, seed=0):
     return np.random.default_rng(seed).integers(0, 4, size=(n, 33)).astype(np.float64)
 
 
+def lattice_wide(n, seed=0):
+    """``lattice`` with seven columns of zeros appended: the same distances and ties in 40 columns."""
+    return np.hstack([lattice(n, seed), np.zeros((n, 7))])
+
+
 def duplicates(distinct=100, copies=40, d=50, seed=0):
     """Every cell 40 times: the 39 nearest neighbours of a cell are at distance zero."""
     return np.tile(pca_like(distinct, d, seed), (copies, 1))

@@ -188,11 +188,12 @@ def test_without_a_gpu_a_valid_call_reaches_the_device_and_fails_there():
 
 # ---- 4. the moved helpers, the surface ---------------------------------------------------------------------------------------------
 def test_the_graph_helpers_stay_importable_from_nmf_spatial():
-    from spatialcore_amd import _spatial_graph
+    from spatialcore_amd import _cell_graph, _spatial_graph
     from spatialcore_amd.nmf import spatial as nmf_spatial
 
-    for name in ("_coordinates", "_given_graph", "union_of_knn", "K_NEIGHBORS_MAX"):
+    for name in ("_coordinates", "union_of_knn", "K_NEIGHBORS_MAX"):
         assert getattr(nmf_spatial, name) is getattr(_spatial_graph, name)
+    assert nmf_spatial._given_graph is _cell_graph.given_graph      # the reader of a caller's graph lives with the other three
     lists = np.array([[1], [2], [0]], dtype=np.int32)
     assert nmf_spatial.union_of_knn(lists, None, 3).toarray().tolist() == [[0, 1, 1], [1, 0, 1], [1, 1, 0]]
 

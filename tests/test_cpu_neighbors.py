@@ -149,6 +149,19 @@ def test_lattice_certifies_some_rows_and_not_others():
     assert np.all(np.abs(margin - np.rint(margin)) < 1e-6)
 
 
+def test_wide_lattice_sends_rows_through_the_fallback_without_a_zero_scale():
+    """The second input of the drivers' tests in tests/test_gpu_neighbors.py, at the size where path 0 takes the filter: a
+    row whose k-th and L-th kept distances tie (margin <= 0 at integer distances, whatever the rounding) misses the
+    certificate, and no cell has the 8 twins that would make the median of its 15 neighbour distances zero."""
+    X, k = N.lattice_wide(10000, 2), 15
+    assert X.shape == (10000, 40)
+    _, _, certified, margin = N.filtered_knn(X, k, 0)
+    tied = int(np.count_nonzero(margin < 0.5))
+    print(f"wide lattice: {int((~certified).sum())} of 10000 rows uncertified, {tied} of them by a tie")
+    assert tied > 0 and not certified[margin < 0.5].any()
+    assert np.unique(X, axis=0, return_counts=True)[1].max() <= k // 2
+
+
 # ---- the public function on the host ------------------------------------------------------------------------------------
 @pytest.fixture
 def no_device(monkeypatch):

@@ -255,3 +255,65 @@ def test_neighbors_zero_scale_raises_and_writes_nothing():
     with pytest.raises(ValueError, match="local scale of cell 50 is zero.*duplicates"):
         neighbors(ad, n_neighbors=6)
     assert not ad.obsp and "neighbors" not in ad.uns and "spatialcore_metadata" not in ad.uns
+
+
+# ---- the drivers where path 0 takes the filter: their own search against the direct one --------------------------------
+# 10,000 cells at a padded width of 40 (test_path_0_takes_the_filter_where_the_rule_says_so), k = 15: a trajectory, and the
+# wide lattice, whose tied rows go through the exact fallback (test_cpu_neighbors.py checks the recipe on the host)
+ABOVE_THE_RULE = {"traj": lambda: _features(10000, 40), "lattice": lambda: N.lattice_wide(10000, 2)}
+K_DRIVERS = 15
+
+
+@functools.lru_cache(maxsize=None)
+def _direct_kernel_graph(name):
+    """(features, the kernel matrix on the lists of sc_knn_dense): the reference, built without the code under test."""
+    X = ABOVE_THE_RULE[name]()
+    X.setflags(write=False)
+    ctx = _ctx()
+    ctx.knn_dense(X, K_DRIVERS, fetch=False)
+    ctx.diffmap_graph()
+    indptr, indices, w = ctx.diffmap_graph_get()
+    return X, sparse.csr_matrix((w, indices, indptr), shape=(X.shape[0], X.shape[0]))
+
+
+def _takes_the_filter(name, X):
+    info = _ctx().knn_dense_gram(X, K_DRIVERS)[2]
+    print(f"{name}: {info}")
+    assert info["path"] == 2
+    if name == "lattice":
+        assert info["rows_fallback"] > 0
+
+
+@pytest.mark.parametrize("name", list(ABOVE_THE_RULE))
+def test_diffusion_map_own_search_above_the_rule_equals_the_direct_search(name):
+    from spatialcore_amd.diffusion import diffusion_map
+
+    X, ref = _direct_kernel_graph(name)
+    _takes_the_filter(name, X)
+    ad = diffusion_map(_adata(X), use_rep="X_pca", n_neighbors=K_DRIVERS, n_comps=5, store_graph=True)
+    C = ad.obsp["diffmap_connectivities"]
+    for part in ("indptr", "indices", "data"):
+        a, b = getattr(C, part), getattr(ref, part)
+        assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), part
+    given = diffusion_map(_adata(X), graph=ref, n_comps=5)
+    assert ad.obsm["X_diffmap"].tobytes() == given.obsm["X_diffmap"].tobytes()
+    assert ad.uns["diffmap_evals"].tobytes() == given.uns["diffmap_evals"].tobytes()
+
+
+@pytest.mark.parametrize("name", list(ABOVE_THE_RULE))
+def test_louvain_own_search_above_the_rule_equals_the_direct_search(name):
+    from spatialcore_amd.cluster import louvain
+    from spatialcore_amd.cluster.communities import quantise_weights, resolution_units, run_levels
+
+    X = _direct_kernel_graph(name)[0]
+    _takes_the_filter(name, X)
+    ctx = _ctx()
+    ctx.knn_dense(X, K_DRIVERS, fetch=False)
+    ctx.diffmap_graph()
+    try:
+        ctx.louvain_begin_resident(quantise_weights(ctx.louvain_resident_weights())[0], resolution_units(1.0), 500)
+        want = run_levels(ctx, X.shape[0])[0]
+    finally:
+        ctx.louvain_end()
+    ad = louvain(_adata(X), use_rep="X_pca", n_neighbors=K_DRIVERS)
+    assert np.array_equal(np.asarray(ad.obs["louvain"].cat.codes), want)
