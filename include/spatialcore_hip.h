@@ -88,7 +88,8 @@ extern "C" {
 #define SC_K_COUNT_ 47      /* the ids up to here; stays as tests/test_cpu_hvg.py pins it.  The table ends at SC_K_END_ */
 #define SC_K_MIX_ESTEP 47   /* sc_mixture_*: weighted log-probabilities, normalisation and the log-likelihood sum */
 #define SC_K_MIX_MSTEP 48   /* sc_mixture_*: both M-step passes with their slice reductions, and the precision stage */
-#define SC_K_END_ 49        /* one past the last kernel id: what sc_ctx_kernel_time accepts */
+#define SC_K_INGEST 49      /* sc_cross_vote / sc_cross_regress: the gather kernels on the lists of sc_knn_cross */
+#define SC_K_END_ 50        /* one past the last kernel id: what sc_ctx_kernel_time accepts */
 
 typedef struct sc_ctx sc_ctx;
 
@@ -789,6 +790,38 @@ int sc_knn_dense(sc_ctx *ctx, const void *X, int dtype, int64_t n, int32_t d, in
 int sc_knn_dense_gram(sc_ctx *ctx, const void *X, int dtype, int64_t n, int32_t d, int32_t k, int32_t path, int32_t slack,
                       int32_t *idx_out, double *d2_out, int64_t *info_out);
 int sc_diffmap_graph(sc_ctx *ctx, double *s2_out, int64_t *n_edges_out, int64_t *n_components_out);
+/* ---- ingest (extension; restated by tests/ingest_restated.py): query rows among reference rows ---------
+ * sc_knn_cross: for every row q of Q[n_query][d] the k rows j of R[n_ref][d] smallest in (d2(q, j), j), d2 as sc_knn_dense
+ *   computes it (the terms (q_c - r_jc)^2 added in column order from the c = 0 term).  Nothing is excluded: a query equal
+ *   to a reference row finds it at d2 = 0.  R and Q are row-major SC_F32 or SC_F64, each widened exactly and on its own
+ *   (mixed dtypes are legal), finite, |x| < 2^500.  1 <= d <= 64, 1 <= k <= 32, k <= n_ref <= 2^31 - 1, 1 <= n_query,
+ *   n_query * k <= 2^29.  `path`, `slack` and info_out[4] as sc_knn_dense_gram's; path 0 chooses by (n_query, n_query * n_ref,
+ *   padded d), the rule of sc_knn_dense_gram where the two sets are one (the same kernels in their cross form:
+ *   lo_qj = (n_q + n_j) - 2 g_qj - E_qj; a row is certified iff it kept fewer than L = k + slack candidates, which
+ *   includes n_ref < L, or its k-th d2 < its L-th lo); the lists are the same bytes on every path and for every slack.
+ *   idx_out[n_query][k] / d2_out[n_query][k] may be NULL (the lists stay on the device for the two calls below).
+ *   What it invalidates: everything a new sc_knn_dense invalidates (the self lists, the resident graph, an open Lanczos
+ *   run), and it leaves NO self lists: sc_diffmap_graph and sc_fuzzy_graph ("no neighbour lists are resident") and every
+ *   reader of the resident graph (sc_louvain_begin_resident, ...) return SC_ERR_STATE until sc_knn_dense[_gram] has run
+ *   again.  The cross lists in turn are gone with the next search of either kind.
+ * sc_cross_vote: on the resident cross lists.  codes_ref[n_ref] in [0, n_classes), 1 <= n_classes <= 2^31 - 1 (an entry's
+ *   class is compared with the <= 32 entries of its own row, so the cost does not depend on n_classes).
+ *   weighting SC_CROSS_UNIFORM: integer counts per class; label = the class with the largest count, the lowest code on
+ *   ties; conf = count / k; proba = count / k.  SC_CROSS_DISTANCE (sklearn's weights="distance"): w_t = 1 / sqrt(d2_t); a row
+ *   that holds any d2 = 0 gives weight 1 to its zero-distance entries and 0 to the rest; class sums and the total are added
+ *   in list order (t ascending, the first term starts the sum); proba = class sum / total; label = the class of the
+ *   largest proba, the lowest code on ties; conf = that proba.  label_out[n_query] (int32), conf_out[n_query];
+ *   proba_out[n_query][n_classes] may be NULL (with it, n_query * n_classes <= 2^28).
+ * sc_cross_regress: out[q][c] = (sum_t w_t Y[j_t][c]) / (sum_t w_t), both sums in list order from their first term, with
+ *   the weights above (uniform: w_t = 1).  Y[n_ref][C] SC_F32 or SC_F64, finite; 1 <= C <= 64; out[n_query][C] fp64.
+ * No cross lists resident: SC_ERR_STATE.  fp64 throughout, no floating-point atomics. */
+#define SC_CROSS_UNIFORM 0
+#define SC_CROSS_DISTANCE 1
+int sc_knn_cross(sc_ctx *ctx, const void *R, int dtype_r, int64_t n_ref, const void *Q, int dtype_q, int64_t n_query, int32_t d,
+                 int32_t k, int32_t path, int32_t slack, int32_t *idx_out, double *d2_out, int64_t *info_out);
+int sc_cross_vote(sc_ctx *ctx, const int32_t *codes_ref, int32_t n_classes, int32_t weighting, int32_t *label_out, double *conf_out,
+                  double *proba_out);
+int sc_cross_regress(sc_ctx *ctx, const void *Y_ref, int dtype, int32_t C, int32_t weighting, double *out);
 int sc_diffmap_graph_csr(sc_ctx *ctx, const int64_t *indptr, const int32_t *indices, const double *w, int64_t n,
                          int64_t *n_components_out);
 int sc_diffmap_graph_get(sc_ctx *ctx, int64_t *indptr, int32_t *indices, double *w, double *T);

@@ -36,6 +36,8 @@ K_NEIGHBORS_GRAM = 41
 K_UMAP_GRAPH, K_UMAP_LAYOUT = 42, 43
 K_HVG_SETUP, K_HVG_DENSE, K_HVG_SPARSE = 44, 45, 46
 K_MIX_ESTEP, K_MIX_MSTEP = 47, 48
+K_INGEST = 49
+CROSS_WEIGHTINGS = {"uniform": 0, "distance": 1}   # SC_CROSS_UNIFORM / SC_CROSS_DISTANCE
 MIX_COVARIANCES = {"full": 0, "diag": 1}   # SC_MIX_FULL / SC_MIX_DIAG
 MIX_D_MAX, MIX_K_MAX, MIX_N_INIT_MAX = 256, 64, 10   # sc_mixture_fit's limits
 HOP_AGGREGATIONS = {"mean": 1, "var": 2}   # SC_HOP_MEAN / SC_HOP_VAR
@@ -138,6 +140,9 @@ SYMBOLS = {
                          POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double)],
     "sc_knn_dense": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, _P, _P],
     "sc_knn_dense_gram": [_P, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P, _P],
+    "sc_knn_cross": [_P, _P, c_int, c_int64, _P, c_int, c_int64, c_int32, c_int32, c_int32, c_int32, _P, _P, _P],
+    "sc_cross_vote": [_P, _P, c_int32, c_int32, _P, _P, _P],
+    "sc_cross_regress": [_P, _P, c_int, c_int32, c_int32, _P],
     "sc_diffmap_graph": [_P, _P, POINTER(c_int64), POINTER(c_int64)],
     "sc_diffmap_graph_csr": [_P, _P, _P, _P, c_int64, POINTER(c_int64)],
     "sc_diffmap_graph_get": [_P, _P, _P, _P, _P],
@@ -320,6 +325,7 @@ class Context:
         self._hop = None           # [n, stored entries of the resident shell, X as uploaded] (hop_begin .. hop_end)
         self._louvain_n = None     # vertices of the next Louvain level (louvain_begin .. louvain_end)
         self._diff_n = self._diff_nnz = self._lanczos_cap = 0   # cells / stored entries of the resident diffusion graph, Lanczos basis cap
+        self._cross_nq = self._cross_nref = None                # rows of the last knn_cross's lists, its reference rows
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -1424,6 +1430,62 @@ class Context:
         self._diff_n = n
         return idx, d2, {"path": int(info[0]), "list_length": int(info[1]), "rows_certified": int(info[2]),
                          "rows_fallback": int(info[3])}
+
+    def knn_cross(self, R, Q, k: int, fetch: bool = True, path: int = 0, slack: int = 0):
+        """sc_knn_cross: for every row of ``Q`` (n_query, d) the ``k`` rows of ``R`` (n_ref, d) smallest in (squared
+        distance, index); nothing is excluded.  Either array float32 or float64.  ``path`` and ``slack`` as
+        ``knn_dense_gram``; the lists are the same bytes whatever they are.  The lists stay on the device for
+        ``cross_vote`` and ``cross_regress``, and no self lists or graph stay resident.  Returns (indices, squared
+        distances, info) as ``knn_dense_gram``."""
+        R, dtype_r, _, _ = self._dense_features("knn_cross", R, k, False)
+        Q, dtype_q, idx, d2 = self._dense_features("knn_cross", Q, k, fetch)
+        if R.shape[1] != Q.shape[1]:
+            raise ValueError(f"knn_cross: the reference has {R.shape[1]} columns and the queries have {Q.shape[1]}")
+        info = np.zeros(4, dtype=np.int64)
+        self._cross_nq = None
+        _check(self._lib.sc_knn_cross(self._h, _ptr(R), dtype_r, R.shape[0], _ptr(Q), dtype_q, Q.shape[0], R.shape[1], int(k),
+                                      int(path), int(slack), _ptr(idx), _ptr(d2), _ptr(info)))
+        self._cross_nq, self._cross_nref = Q.shape[0], R.shape[0]
+        return idx, d2, {"path": int(info[0]), "list_length": int(info[1]), "rows_certified": int(info[2]),
+                         "rows_fallback": int(info[3])}
+
+    def _cross_shape(self, who):
+        if self._cross_nq is None:
+            raise SpatialCoreHipError(f"{who}: no cross lists are resident (call knn_cross first)")
+        return self._cross_nq, self._cross_nref
+
+    def cross_vote(self, codes_ref, n_classes: int, weighting: str = "uniform", proba: bool = False):
+        """sc_cross_vote on the lists of the last ``knn_cross``: ``codes_ref`` (n_ref,) integer codes in [0, n_classes).
+        ``weighting`` "uniform" or "distance" (sklearn's).  Returns (labels int32, confidence float64, probabilities
+        (n_query, n_classes) or None); ties go to the lowest code."""
+        nq, nref = self._cross_shape("cross_vote")
+        if weighting not in CROSS_WEIGHTINGS:
+            raise ValueError(f"cross_vote: weighting must be one of {sorted(CROSS_WEIGHTINGS)}, got {weighting!r}")
+        codes = np.ascontiguousarray(codes_ref, dtype=np.int32)
+        if codes.shape != (nref,):
+            raise ValueError(f"cross_vote: codes_ref must have shape ({nref},), got {codes.shape}")
+        label = np.empty(nq, dtype=np.int32)
+        conf = np.empty(nq, dtype=np.float64)
+        P = np.empty((nq, int(n_classes)), dtype=np.float64) if proba else None
+        _check(self._lib.sc_cross_vote(self._h, _ptr(codes), int(n_classes), CROSS_WEIGHTINGS[weighting], _ptr(label), _ptr(conf),
+                                       _ptr(P)))
+        return label, conf, P
+
+    def cross_regress(self, Y_ref, weighting: str = "uniform") -> np.ndarray:
+        """sc_cross_regress on the lists of the last ``knn_cross``: the weighted average of the neighbours' rows of
+        ``Y_ref`` (n_ref, C), float32 or float64, C <= 64, in list order; float64 (n_query, C)."""
+        nq, nref = self._cross_shape("cross_regress")
+        if weighting not in CROSS_WEIGHTINGS:
+            raise ValueError(f"cross_regress: weighting must be one of {sorted(CROSS_WEIGHTINGS)}, got {weighting!r}")
+        Y = np.ascontiguousarray(Y_ref)
+        if Y.dtype not in (np.float32, np.float64):
+            Y = Y.astype(np.float64)
+        if Y.ndim != 2 or Y.shape[0] != nref:
+            raise ValueError(f"cross_regress: Y_ref must have shape ({nref}, C), got {Y.shape}")
+        out = np.empty((nq, Y.shape[1]), dtype=np.float64)
+        _check(self._lib.sc_cross_regress(self._h, _ptr(Y), SC_F32 if Y.dtype == np.float32 else SC_F64, Y.shape[1],
+                                          CROSS_WEIGHTINGS[weighting], _ptr(out)))
+        return out
 
     def diffmap_graph(self) -> dict:
         """sc_diffmap_graph on the lists of the last ``knn_dense``: ``s2`` (local scales), ``n_edges`` (stored entries of

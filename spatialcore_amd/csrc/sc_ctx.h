@@ -230,14 +230,22 @@ struct sc_ctx {
     int64_t th_n = 0;
     // ---- the dense search (sc_neighbors.hip): the fp64 features and neighbour lists of the last sc_knn_dense[_gram].  Written
     // by sc_neighbors.hip alone; read by lg_build_union (idx), sc_diffmap_graph (X, d2, d) and sc_fuzzy_graph (idx, d2, k).
-    // What invalidates what among knn.valid, lg.valid and lz.valid: the functions of sc_list_graph.h ----
+    // What invalidates what among knn.valid, lg.valid and lz.valid: the functions of sc_list_graph.h.
+    // sc_knn_cross uses the same buffers for the lists of nq query rows (Q) among the n reference rows (X): it leaves
+    // `cross` set and `valid` clear, so that no reader of a self graph takes them; sc_cross_vote and sc_cross_regress
+    // (sc_ingest.hip) read idx, d2, n, nq and k under `cross`.  Every search clears both flags when it begins ----
     struct DenseKnn {
-        int64_t n = 0;      // rows of the lists
+        int64_t n = 0;      // rows of the lists; after a cross search: the reference rows, the lists' indices are below it
         int d = 0, k = 0;   // columns of X (the features padded to a multiple of 8), list length
         bool valid = false;
         DBuf X, raw, idx, d2, pidx, pd2;        // [n][d] fp64, the upload, [n][k] result, [split][query][k] partial lists
         DBuf gnorm, gkept, gcnt, glo, grows;    // the Gram filter: row norms, kept candidates [n][L], their counts, the L-th keys, [count | uncertified rows]
+        int64_t nq = 0;     // a cross search: rows of the lists
+        bool cross = false;
+        DBuf Q, qraw, qnorm;                    // ... its queries [nq][d] fp64, their upload, their norms
     } knn;
+    // ---- ingest (sc_ingest.hip): the codes or the values of the reference rows that the cross lists gather from ----
+    DBuf ig_ref, ig_raw, ig_label, ig_conf, ig_out;
     // ---- the resident weighted graph (sc_list_graph.h).  Written by sc_list_graph.hip (the union, the upload, the finish;
     // `valid` by its validity functions alone) and by the two kernels that fill `w` between the union and the finish
     // (sc_diffmap_graph, sc_fuzzy_graph, which also set nnz); read by Lanczos, sc_umap_layout and Louvain through lg_resident ----

@@ -21,7 +21,8 @@ __device__ __forceinline__ int64_t df_row_of(const int64_t *__restrict__ indptr,
 // ---- what invalidates what: knn.valid (the lists), lg.valid (the graph), lz.valid (the Lanczos run on it) ----
 // A new search (lists_too; sc_neighbors.hip sets knn.valid itself when the search has finished), a graph from the lists
 // (the lists stay) and an uploaded graph (lists_too: its vertices are not the lists' rows): nothing that stood on the old
-// graph stays, and with lists_too nothing that stood on the old lists.
+// graph stays, and with lists_too nothing that stood on the old lists.  A cross search (sc_knn_cross) is a new search that
+// never sets knn.valid: its lists (knn.cross) have query rows, not vertices, and no graph is ever built on them.
 void lg_invalidate(sc_ctx *c, bool lists_too);
 void lg_mark_finished(sc_ctx *c);   // lg_finish has run: the graph is the resident one; no Lanczos run is open on it
 void lz_open(sc_ctx *c);            // sc_lanczos_begin has its start vector
